@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py — posterior samples/s of the GP hot path (Gram build + Cholesky + predict) at N = 4096.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--steps K is the number of timed steps of the region `value` and `ms_per_step` come from (K >= 1); --dump-outputs DIR
+writes what the last timed step computed (dump_outputs).  Inputs are seeded: equal arguments give equal inputs.
 
 N > 1 without a process group in the environment (no WORLD_SIZE): this process only launches
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>` as a CHILD (before
@@ -109,7 +112,50 @@ def parse():
     ap.add_argument("--timing-only", action="store_true",
                     help="measurement only (timing-only kernel variants whose results are garbage by construction): ignore "
                          "the status of the calls and skip every result check; the line is labelled")
-    return ap.parse_args([x for x in sys.argv[1:] if x != "--"])
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (meanSATE, varSATE, meanITE of every "
+                         "rank's samples) as DIR/<name>.npy in float64, at most 64 MB in all (dump_outputs)")
+    a = ap.parse_args([x for x in sys.argv[1:] if x != "--"])
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
+    return a
+
+
+DUMP_BYTES = 64_000_000     # the whole dump, .npy headers included
+DUMP_SEED = 1234
+
+
+def dump_outputs(path, arrays):
+    """Write [(name, array)] as path/<name>.npy in float64, DUMP_BYTES in all.  An array larger than its share of what is left
+    (arrays are taken smallest first) is replaced by a fixed seeded sample of its entries: <name>_sample.npy holds the values,
+    <name>_sample_index.npy their indices into the column-major flattened array (float64, exact).  The sample draws one entry
+    per stratum of equal width, so it depends only on the array's size and DUMP_SEED: equal arguments sample equal entries."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def save(fname, v):
+        f = os.path.join(path, fname + ".npy")
+        np.save(f, v)
+        return os.path.getsize(f)
+
+    arrays = sorted(((k, np.asarray(v, dtype=np.float64)) for k, v in arrays), key=lambda kv: kv[1].size)
+    left = DUMP_BYTES
+    for i, (name, v) in enumerate(arrays):
+        for stale in (name, name + "_sample", name + "_sample_index"):     # a DIR reused from a run of another size
+            if os.path.exists(os.path.join(path, stale + ".npy")):
+                os.remove(os.path.join(path, stale + ".npy"))
+        share = left // (len(arrays) - i) - 2 * 256       # room for two .npy headers
+        if v.nbytes <= share:
+            left -= save(name, v)
+        else:
+            k = max(1, share // 16)                         # a value and its index per entry
+            edges = (np.arange(k + 1) * (v.size / k)).astype(np.int64)      # k strata [edges[j], edges[j + 1]), none empty
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.minimum(edges[:-1] + (rng.random(k) * np.diff(edges)).astype(np.int64), edges[1:] - 1)
+            left -= save(name + "_sample", v.reshape(-1, order="F")[idx])
+            left -= save(name + "_sample_index", idx.astype(np.float64))
 
 
 def git_blob_sha(path):
@@ -681,6 +727,22 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             d1 = float(tt.item())
         region_s.append(d1)
+    if a.dump_outputs:
+        # what the last timed step left in its output buffers, before the panel leg below overwrites them: every rank's shard,
+        # gathered in rank order along the sample axis (the layout of a one-rank run with Sr * world samples)
+        outs = [("meanSATE", mS, (Sr, L)), ("varSATE", vS, (Sr, L))] + ([] if mI is None else [("meanITE", mI, (n, Sr, L))])
+        host = {}
+        for name, t, shape in outs:
+            parts = [t.cpu().numpy()]
+            if use_dist:
+                src = t.cpu() if rehearsal else t
+                gl = [torch.empty_like(src) for _ in range(world)]
+                dist.all_gather(gl, src)
+                parts = [g.cpu().numpy() for g in gl]
+            host[name] = np.concatenate([p.reshape(shape, order="F") for p in parts], axis=len(shape) - 2)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, list(host.items()))
+        del host
     kname = "tile_gemm_nt_kernel<1, 0> (f64 MFMA tile update: trailing updates of the blocked Cholesky)"
     kname1 = "tile_fused_strip_kernel<8> (f64 MFMA tile update: in-panel column update fused with the panel solve)"
     # Round 6: at the default sizes the whole factorisation is ONE persistent launch of tile tasks.  The schedule of rounds 1-5

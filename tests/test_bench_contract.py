@@ -196,3 +196,55 @@ def test_one_rank_over_rccl_runs_the_collective_path():
     assert d["n_gpus"] == 1 and d["value"] > 0 and "REHEARSAL" not in d["data"]
     assert "1 rank(s)" in d["config"]["sharding"] and d["config4"]["parity"]["ok"]
     assert abs(d["value"] - 48 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr and r.stdout.strip() == ""
+
+
+def test_dump_outputs_writes_float64_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays verbatim; an array over its share becomes a seeded sample with its column-major indices,
+    the same entries for the same size, and the whole dump stays within DUMP_BYTES."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    rng = np.random.default_rng(0)
+    sate, ite = rng.standard_normal((24, 2)), rng.standard_normal((100, 24, 2))   # ite: 38,400 B, fits
+    bench.dump_outputs(str(tmp_path / "a"), [("meanITE", ite), ("meanSATE", sate)])
+    assert np.array_equal(np.load(tmp_path / "a" / "meanITE.npy"), ite)
+    assert np.load(tmp_path / "a" / "meanSATE.npy").dtype == np.float64
+    big = rng.standard_normal((500, 48, 2))                                      # 384,000 B: sampled
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), [("meanSATE", sate.astype(np.float32)), ("meanITE", big)])
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["meanITE_sample.npy", "meanITE_sample_index.npy", "meanSATE.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= bench.DUMP_BYTES
+    idx = np.load(tmp_path / "b" / "meanITE_sample_index.npy")
+    val = np.load(tmp_path / "b" / "meanITE_sample.npy")
+    assert idx.dtype == np.float64 and len(idx) > 1000 and np.all(np.diff(idx) > 0) and idx[-1] < big.size
+    assert np.array_equal(val, big.reshape(-1, order="F")[idx.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    # a DIR reused at a smaller size holds no sample left over from the larger run
+    bench.dump_outputs(str(tmp_path / "b"), [("meanSATE", sate), ("meanITE", ite)])
+    assert sorted(os.listdir(tmp_path / "b")) == ["meanITE.npy", "meanSATE.npy"]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_timed_steps_results(tmp_path):
+    """bench.py --dump-outputs on a small problem: --steps is echoed, ms_per_step matches value, and the dumped arrays are the
+    timed path's outputs (finite, shapes of S x L and n x S x L, MeanSATE = the mean of MeanITE over instances)."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--n", "640", "--d", "4", "--nu", "1", "--samples-per-step", "48",
+              "--levels", "2", "--no-cpu-baseline", "--no-units", "--no-configs", "--no-config4", "--repeats", "1",
+              "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and abs(d["value"] - 48 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    ms, vs, mi = (np.load(out / f"{k}.npy") for k in ("meanSATE", "varSATE", "meanITE"))
+    assert ms.shape == vs.shape == (48, 2) and mi.shape == (640, 48, 2)
+    assert all(x.dtype == np.float64 and np.all(np.isfinite(x)) for x in (ms, vs, mi)) and np.all(vs > 0)
+    assert np.max(np.abs(mi.mean(axis=0) - ms)) <= 1e-8 * max(1.0, np.max(np.abs(ms)))
