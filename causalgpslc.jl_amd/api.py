@@ -43,6 +43,19 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _intervention(doT, n):
+    """An ``Intervention`` (src/types.jl:138-143) for n individuals -> (scalar, None) or (None, d).
+
+    A Python / NumPy scalar or Bool is one level for everyone (``fill(doT, n)``); a 1-D array or list of length n (Bool ->
+    0/1) gives each individual its own treatment value.  Any other shape raises ValueError before anything runs on a device."""
+    a = np.asarray(doT)
+    if a.ndim == 0:
+        return float(a), None
+    if a.ndim == 1 and a.shape[0] == n:
+        return None, np.ascontiguousarray(a, dtype=np.float64)
+    raise ValueError(f"doT must be a scalar or a vector of length n = {n}, got an array of shape {a.shape}")
+
+
 class Context:
     """RAII wrapper of gpslc_ctx (one per GPU and data set)."""
 
@@ -318,10 +331,15 @@ def likelihoodDistribution(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT):
     (src/likelihood.jl:8-174; the method is chosen by which of U / X is None, like the reference's dispatch)."""
     g = _single(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y)
     n = g.getN()
+    x, d = _intervention(doT, n)
     ctx = g.ctx()
     outs = [np.empty((n, n), order="F") for _ in range(7)]
-    st = ctx.lib.gpslc_likelihood_distribution(ctx.h, _p(g.U), _p(g.uyLS), _p(g.xyLS), float(tyLS), float(yScale),
-                                               float(yNoise), float(doT), *[_p(o) for o in outs])
+    if d is None:
+        st = ctx.lib.gpslc_likelihood_distribution(ctx.h, _p(g.U), _p(g.uyLS), _p(g.xyLS), float(tyLS), float(yScale),
+                                                   float(yNoise), x, *[_p(o) for o in outs])
+    else:
+        st = ctx.lib.gpslc_likelihood_distribution_vec(ctx.h, _p(g.U), _p(g.uyLS), _p(g.xyLS), float(tyLS), float(yScale),
+                                                       float(yNoise), _p(d), *[_p(o) for o in outs])
     ctx.check(st)
     return (g.Y.copy(), *outs)
 
@@ -346,10 +364,14 @@ def conditionalITE(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT):
 
 def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True):
     n, S = g.getN(), g.getNumPosteriorSamples()
+    x, d = _intervention(doT, n)
     ctx = g.ctx()
     M = np.empty((S, n), order="F")
     Cv = np.empty((S, n, n), order="F") if want_cov else None
-    st = ctx.lib.gpslc_ite_distributions(ctx.h, S, *g._params(), float(doT), float(pred_noise), _p(M), _p(Cv))
+    if d is None:
+        st = ctx.lib.gpslc_ite_distributions(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
+    else:
+        st = ctx.lib.gpslc_ite_distributions_vec(ctx.h, S, *g._params(), _p(d), float(pred_noise), _p(M), _p(Cv))
     ctx.check(st)
     return M, Cv
 
@@ -368,7 +390,7 @@ def conditionalSATE(MeanITE, CovITE):
 def SATEDistributions(g: GPSLCObject, doT):
     """MeanSATEs (S,), VarSATEs (S,) (src/estimation.jl:127-140) — O(N^2) per sample on the GPU,
     without materialising CovITE."""
-    m, v, _ = predict(g, [doT])
+    m, v, _ = predict(g, _levels(g, doT))
     return m[:, 0].copy(), v[:, 0].copy()
 
 
@@ -386,14 +408,29 @@ def SATEsamples(MeanSATEs, VarSATEs, nSamplesPerMixture, z=None, seed=0):
     return out
 
 
-def predict(g: GPSLCObject, doTs: Sequence[float], want_mean_ite=False, spp=0, z=None, seed=0,
+def _levels(g: GPSLCObject, doT):
+    """One intervention as the ``doTs`` of predict: [x] for a scalar, a (1, n) array for a per-individual vector."""
+    x, d = _intervention(doT, g.getN())
+    return [x] if d is None else d[None, :]
+
+
+def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
             want_draws=False, devices: Optional[Sequence[int]] = None):
     """The ensemble entry point (gpslc_predict): returns MeanSATE (S, L), VarSATE (S, L) and, when
-    asked, MeanITE (n, S, L) / draws (L, n, S*spp).  ``devices`` = a list of GPU indices shards the posterior samples
-    over one context per entry through ``gpslc_predict_multi`` (same results, bit for bit)."""
+    asked, MeanITE (n, S, L) / draws (L, n, S*spp).  ``doTs``: L scalar levels (1-D), or an (L, n) array of L per-individual
+    intervention vectors (gpslc_predict_vec).  ``devices`` = a list of GPU indices shards the posterior samples
+    over one context per entry through ``gpslc_predict_multi`` (same results, bit for bit; scalar levels only)."""
     n, S = g.getN(), g.getNumPosteriorSamples()
-    doTs = np.ascontiguousarray(np.atleast_1d(np.asarray(doTs, dtype=np.float64)))
-    L = doTs.shape[0]
+    doTs = np.asarray(doTs, dtype=np.float64)
+    vec = doTs.ndim == 2
+    if doTs.ndim > 2 or (vec and doTs.shape[1] != n):
+        raise ValueError(f"doTs must be L scalar levels or an (L, n) array of intervention vectors with n = {n}, "
+                         f"got an array of shape {doTs.shape}")
+    if vec and devices is not None:
+        raise NotImplementedError("vector interventions are not sharded over devices: call predict without devices=")
+    # vector levels: n x L column-major, doT[i + n*l]
+    doTs = np.asfortranarray(doTs.T) if vec else np.ascontiguousarray(np.atleast_1d(doTs))
+    L = doTs.shape[1] if vec else doTs.shape[0]
     ctx = g.ctx() if devices is None else g.ctxs(devices)[0]
     ms = np.empty((S, L), order="F")
     vs = np.empty((S, L), order="F")
@@ -405,8 +442,9 @@ def predict(g: GPSLCObject, doTs: Sequence[float], want_mean_ite=False, spp=0, z
         if zz.shape != (n, spp, S, L):
             raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
     if devices is None:
-        st = ctx.lib.gpslc_predict(ctx.h, S, *g._params(), L, _p(doTs), float(g.hyperparams.predictionCovarianceNoise),
-                                   int(spp), int(seed), _p(zz), _p(ms), _p(vs), _p(mi), _p(dr))
+        fn = ctx.lib.gpslc_predict_vec if vec else ctx.lib.gpslc_predict
+        st = fn(ctx.h, S, *g._params(), L, _p(doTs), float(g.hyperparams.predictionCovarianceNoise),
+                int(spp), int(seed), _p(zz), _p(ms), _p(vs), _p(mi), _p(dr))
     else:
         cs = g.ctxs(devices)
         hs = (C.c_void_p * len(cs))(*[c.h for c in cs])
@@ -428,7 +466,7 @@ def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0):
         n, S = g.getN(), g.getNumPosteriorSamples()
         # column j*spp + d  ->  [i, d, j] under a column-major reshape
         zz = np.asarray(z, dtype=np.float64).reshape(n, nSamplesPerMixture, S, order="F")[:, :, :, None]
-    _, _, _, dr = predict(g, [doT], spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True)
+    _, _, _, dr = predict(g, _levels(g, doT), spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True)
     return np.asfortranarray(dr[0])
 
 

@@ -648,6 +648,7 @@ struct PredictIO {
     const double* X = nullptr;   // device X to use (ctx or override)
     int L = 0;
     const double* doT = nullptr;
+    bool vec = false;                // vector levels: doT is n x L (level l at doT + n*l), not L scalars
     double pred_noise = 0;
     int spp = 0;
     uint64_t seed = 0;
@@ -723,6 +724,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
                + (size_t)(with_sums ? 2 * nt * Np * 8 : 0)
                + (size_t)(2 * Np * 8)                // bsum, ksum
                + (size_t)(std::max(L, 1) * 8)        // sumdelta
+               + (size_t)(io.vec && with_sums ? (size_t)L * nt * 8 : 0)   // vector levels: per-tile shares of sum(Delta)
                + (size_t)(2 * Np * 8)                // zwork + alpha
                + (size_t)(io.ndraw ? 16 * Np * 8 : 0)   // operand image of the node draw's normals
                + 1024;
@@ -778,6 +780,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         double* bsum = ar.take<double>((size_t)nb * Np);
         double* ksum = ar.take<double>((size_t)nb * Np);
         double* sumdelta = ar.take<double>((size_t)nb * std::max(L, 1));
+        double* vpart = (io.vec && with_sums) ? ar.take<double>((size_t)nb * L * nt) : nullptr;
         double* zwork = ar.take<double>((size_t)2 * nb * Np);
         const long long bstride = tiles_per * GP_TSQ;
         const long long inv_bs = (long long)nt * GP_TSQ;
@@ -815,7 +818,9 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
 
         RhsArgs ra{};
         ra.T = c->dT; ra.Y = io.Y; ra.y_sstride = io.y_sstride; ra.tyLS = io.p.tyLS; ra.doT = io.doT; ra.s0 = s0;
-        ra.n = n; ra.nt = nt; ra.naug = naug; ra.L = with_sums ? L : 0; ra.with_sums = with_sums ? 1 : 0;
+        // vector levels: rhs_tiles writes zeros into the level rows and rhs_prepare no level sums (L = 0 here); launch_vec_sums
+        // fills both below
+        ra.n = n; ra.nt = nt; ra.naug = naug; ra.L = (with_sums && !io.vec) ? L : 0; ra.with_sums = with_sums ? 1 : 0;
         ra.part = part; ra.bsum = bsum; ra.ksum = ksum; ra.sumdelta = sumdelta; ra.M = M;
         static const int epi_rows_on = diag_env("GPSLC_EPI_ROWS", 1);      // measurement switch (A/B of the extra tile update)
         const bool epi_rows = (naug == 1) && epi_rows_on;
@@ -824,6 +829,14 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
             ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
         }
         launch_rhs(ra, nb, st);
+        VecArgs va{};
+        if (io.vec) {
+            va.X = io.X; va.T = c->dT; va.p = io.p; va.s0 = s0;
+            va.n = n; va.nX = io.nX; va.nU = io.nU; va.nt = nt; va.L = L; va.doT = io.doT;
+            va.M = M; va.part = vpart; va.sumdelta = sumdelta;
+            va.Y = io.Y; va.y_sstride = io.y_sstride;
+            if (with_sums) launch_vec_sums(va, nb, st);
+        }
 
         // NB: the MeanITE pass takes K alpha as Y - yNoise alpha (k_solve.hip, ite_mean_kernel): it relies on alpha solving
         // EXACTLY (K_gram + yNoise I) alpha = Y.  Any future jitter, robust fallback or different right-hand side in this
@@ -855,16 +868,27 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
             ba.M = M; ba.inv = inv; ba.inv_bstride = inv_bs; ba.nt = nt; ba.naug = naug; ba.zwork = zwork;
             if (!back_done) launch_backsolve(ba, nb, st);
             const double* alpha = zwork + (long long)nb * Np;
+            if (io.vec) {
+                va.alpha = alpha;
+                if (meanITE) {
+                    va.meanITE = meanITE; va.si = 1; va.ss = n; va.sl = (long long)n * io.S;
+                    launch_vec_mean(va, nb, st);
+                }
+                if (io.MeanITEs) {   // reference layout S x n (single level)
+                    va.meanITE = io.MeanITEs; va.si = io.S; va.ss = 1; va.sl = 0;
+                    launch_vec_mean(va, nb, st);
+                }
+            }
             IteMeanArgs ia{};
             ia.X = io.X; ia.T = c->dT; ia.p = io.p; ia.s0 = s0; ia.S = io.S;
             ia.n = n; ia.nX = io.nX; ia.nU = io.nU; ia.nt = nt; ia.L = L; ia.doT = io.doT; ia.alpha = alpha;
             ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.p.yNoise;
             ia.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
-            if (meanITE) {
+            if (meanITE && !io.vec) {
                 ia.meanITE = meanITE; ia.si = 1; ia.ss = n; ia.sl = (long long)n * io.S;
                 launch_ite_mean(ia, nb, st);
             }
-            if (io.MeanITEs) {   // reference layout S x n (single level)
+            if (io.MeanITEs && !io.vec) {   // reference layout S x n (single level)
                 ia.meanITE = io.MeanITEs; ia.si = io.S; ia.ss = 1; ia.sl = 0;
                 launch_ite_mean(ia, nb, st);
             }
@@ -897,6 +921,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
                     DtArgs da{};
                     da.X = io.X; da.T = c->dT; da.p = io.p; da.s0 = s0 + g0;
                     da.n = n; da.nX = io.nX; da.nU = io.nU; da.nt = nt; da.doT = io.doT; da.l0 = l0; da.lc = lc;
+                    da.vec = io.vec ? 1 : 0;
                     da.pred_noise = io.pred_noise; da.W = W; da.Cm = Cm;
                     launch_dt_build(da, ub, st);
                     // W <- D L^-T, left-looking over tile columns; the panel product with inv(L_kk)^T is applied by the
@@ -1548,10 +1573,10 @@ static int predict_dev_inner(gpslc_ctx* c, int64_t S, const double* U, const dou
                              const double* tyLS, const double* yScale, const double* yNoise, int32_t L,
                              const double* doT, double pred_noise, int32_t spp, uint64_t seed, const double* z,
                              double* meanSATE, double* varSATE, double* meanITE, double* ite_draws,
-                             int64_t ens_off = 0, int64_t ens_S = 0) {
+                             int64_t ens_off = 0, int64_t ens_S = 0, bool vec = false) {
     PredictIO io;
     io.S = S; io.p = SampleParams{U, uyLS, xyLS, tyLS, yScale, yNoise}; io.X = c->dX;
-    io.L = L; io.doT = doT; io.pred_noise = pred_noise; io.spp = spp; io.seed = seed; io.z = z;
+    io.L = L; io.doT = doT; io.vec = vec; io.pred_noise = pred_noise; io.spp = spp; io.seed = seed; io.z = z;
     io.meanSATE = meanSATE; io.varSATE = varSATE; io.meanITE = meanITE; io.ite_draws = ite_draws;
     io.ens_off = ens_off; io.ens_S = ens_S;
     io.info = c->io.take<int>((size_t)S);
@@ -1587,7 +1612,7 @@ struct HostPlacement {
 static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
                         const double* yScale, const double* yNoise, int32_t L, const double* doT, double pred_noise, int32_t spp,
                         uint64_t seed, const double* z, double* meanSATE, double* varSATE, double* meanITE, double* ite_draws,
-                        const HostPlacement& pl) {
+                        const HostPlacement& pl, bool vec = false) {
     return guarded(c, [&]() {
         const size_t n = (size_t)c->n;
         const size_t s0 = (size_t)pl.s0, St = (size_t)pl.S_total;
@@ -1598,7 +1623,7 @@ static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* 
         const double* dty = up(c, tyLS + s0, S);
         const double* dys = up(c, yScale + s0, S);
         const double* dyn = up(c, yNoise + s0, S);
-        const double* ddo = up(c, doT, L);
+        const double* ddo = up(c, doT, vec ? n * L : (size_t)L);     // vector levels: n x L
         const double* dz = nullptr;
         if (z && ite_draws) {      // caller's normals n x spp x S_total x L: level l of the shard is one run of n spp S doubles
             double* d = c->io.take<double>(n * spp * S * L);
@@ -1611,7 +1636,7 @@ static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* 
         double* omi = meanITE ? c->io.take<double>(n * S * L) : nullptr;
         double* odr = ite_draws ? c->io.take<double>((size_t)L * n * S * spp) : nullptr;
         int st = predict_dev_inner(c, S, dU, duy, dxy, dty, dys, dyn, L, ddo, pred_noise, spp, seed, dz,
-                                   oms, ovs, omi, odr, pl.ens_off, pl.ens_S);
+                                   oms, ovs, omi, odr, pl.ens_off, pl.ens_S, vec);
         if (st < 0) return st;
         const size_t sb = (size_t)S * sizeof(double);
         if (meanSATE) HC(hipMemcpy2D(meanSATE + s0, St * sizeof(double), oms, sb, sb, (size_t)L, hipMemcpyDeviceToHost));
@@ -1634,6 +1659,37 @@ int gpslc_predict(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, 
     pl.S_total = S;
     return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE, varSATE, meanITE,
                         ite_draws, pl);
+}
+
+// vector levels (gpslc_*_vec): every entry of the n x L host array doT must be finite; the fp32 kernel mode covers the
+// scalar levels only
+static int vec_levels_check(gpslc_ctx* c, const double* doT, int64_t count, int argk) {
+    if (!doT) return bad_arg(c, argk, "doT is NULL");
+    for (int64_t i = 0; i < count; ++i)
+        if (!std::isfinite(doT[i])) return bad_arg(c, argk, "doT has a non-finite entry");
+    return 0;
+}
+static int vec_mode_check(gpslc_ctx* c) {
+    if (c->flags & GPSLC_FLAG_FP32_KERNEL) {
+        set_err(c, "vector interventions are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
+        return GPSLC_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+
+int gpslc_predict_vec(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                      const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
+                      double pred_noise, int32_t spp, uint64_t seed, const double* z, double* meanSATE,
+                      double* varSATE, double* meanITE, double* ite_draws) {
+    int rc = predict_check(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, ite_draws);
+    if (rc) return rc;
+    if ((rc = vec_levels_check(c, doT, c->n * (int64_t)L, 10))) return rc;
+    if ((rc = vec_mode_check(c))) return rc;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    HostPlacement pl;
+    pl.S_total = S;
+    return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE, varSATE, meanITE,
+                        ite_draws, pl, /*vec=*/true);
 }
 
 int gpslc_shard_range(int64_t S, int32_t nblocks, int32_t k, int64_t* s0, int64_t* s1) {
@@ -1728,12 +1784,10 @@ int gpslc_predict_multi(int32_t nctx, gpslc_ctx* const* ctxs, int64_t S, const d
     }
 }
 
-int gpslc_ite_distributions(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
-                            const double* tyLS, const double* yScale, const double* yNoise, double doT,
-                            double pred_noise, double* MeanITEs, double* CovITEs) {
-    int rc = check_common(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise);
-    if (rc) return rc;
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+// doT: one level (host), a scalar (vec = false) or n values (vec = true)
+static int ite_distributions_impl(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                                  const double* tyLS, const double* yScale, const double* yNoise, const double* doT, bool vec,
+                                  double pred_noise, double* MeanITEs, double* CovITEs) {
     return guarded(c, [&]() {
         const size_t n = (size_t)c->n;
         c->io.reset();
@@ -1743,18 +1797,38 @@ int gpslc_ite_distributions(gpslc_ctx* c, int64_t S, const double* U, const doub
         const double* dty = up(c, tyLS, S);
         const double* dys = up(c, yScale, S);
         const double* dyn = up(c, yNoise, S);
-        const double* ddo = up(c, &doT, 1);
+        const double* ddo = up(c, doT, vec ? n : 1);
         double* om = MeanITEs ? c->io.take<double>((size_t)S * n) : nullptr;
         double* oc = CovITEs ? c->io.take<double>((size_t)S * n * n) : nullptr;
         PredictIO io;
         io.S = S; io.p = SampleParams{dU, duy, dxy, dty, dys, dyn}; io.X = c->dX;
-        io.L = 1; io.doT = ddo; io.pred_noise = pred_noise;
+        io.L = 1; io.doT = ddo; io.vec = vec; io.pred_noise = pred_noise;
         io.MeanITEs = om; io.CovITEs = oc; io.info = c->io.take<int>((size_t)S);
         run_predict(c, io);
         if (MeanITEs) HC(hipMemcpy(MeanITEs, om, sizeof(double) * S * n, hipMemcpyDeviceToHost));
         if (CovITEs) copy_out_large(c, CovITEs, oc, sizeof(double) * (size_t)S * n * n);
         return first_info(c);
     });
+}
+
+int gpslc_ite_distributions(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                            const double* tyLS, const double* yScale, const double* yNoise, double doT,
+                            double pred_noise, double* MeanITEs, double* CovITEs) {
+    int rc = check_common(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise);
+    if (rc) return rc;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return ite_distributions_impl(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, &doT, false, pred_noise, MeanITEs, CovITEs);
+}
+
+int gpslc_ite_distributions_vec(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                                const double* tyLS, const double* yScale, const double* yNoise, const double* doT,
+                                double pred_noise, double* MeanITEs, double* CovITEs) {
+    int rc = check_common(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise);
+    if (rc) return rc;
+    if ((rc = vec_levels_check(c, doT, c->n, 9))) return rc;
+    if ((rc = vec_mode_check(c))) return rc;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return ite_distributions_impl(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, doT, true, pred_noise, MeanITEs, CovITEs);
 }
 
 // logpdf[s] = -(n log 2pi + logdet_s + quad_s) / 2 from the device-side epilogue values
@@ -2166,19 +2240,18 @@ int gpslc_mvn_draw(gpslc_ctx* c, int64_t S, const double* cov, const double* cov
     });
 }
 
-int gpslc_likelihood_distribution(gpslc_ctx* c, const double* U, const double* uyLS, const double* xyLS,
-                                  double tyLS, double yScale, double yNoise, double doT, double* CovWW,
-                                  double* CovWWs, double* CovWWp, double* CovC11, double* CovC12,
-                                  double* CovC21, double* CovC22) {
+// doTv: null = the scalar doT, else the per-individual intervention (n, host)
+static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const double* uyLS, const double* xyLS,
+                                        double tyLS, double yScale, double yNoise, double doT, const double* doTv,
+                                        double* CovWW, double* CovWWs, double* CovWWp, double* CovC11, double* CovC12,
+                                        double* CovC21, double* CovC22) {
     const double ty = tyLS, ysc = yScale, yno = yNoise;
-    int rc = check_common(c, 1, U, uyLS, xyLS, &ty, &ysc, &yno);
-    if (rc) return rc;
     return guarded(c, [&]() {
         ensure_streams(c);
         hipStream_t st = c->streams[0];
         const int n = (int)c->n, nt = c->nt;
         const long long nlow = (long long)nt * (nt + 1) / 2, nsq = (long long)nt * nt;
-        DevBuf bU, buy, bxy, bty, bys, byn, info, tiles, inv, part, rect, outb;
+        DevBuf bU, buy, bxy, bty, bys, byn, bdo, info, tiles, inv, part, rect, outb;
         const double* dU = c->nU ? up(bU, U, (size_t)n * c->nU) : nullptr;
         const double* duy = c->nU ? up(buy, uyLS, c->nU) : nullptr;
         const double* dxy = c->nX ? up(bxy, xyLS, c->nX) : nullptr;
@@ -2204,6 +2277,7 @@ int gpslc_likelihood_distribution(gpslc_ctx* c, const double* U, const double* u
         launch_gram(ga, 1, st);
         potrf_tiles(c, M, nt, nt, inv.as<double>(), (long long)nt * GP_TSQ, info.as<int>(), 0, 1, st);
         LdBuildArgs la{c->dX, c->dT, sp, 0, n, c->nX, c->nU, nt, doT, Kt, Kst, KsTt, Ksst};
+        if (doTv) la.doTv = up(bdo, doTv, (size_t)n);
         launch_ld_build(la, st);
         auto emit = [&](const TRef& R, double* host, double diag_add) {
             if (!host) return;
@@ -2257,6 +2331,29 @@ int gpslc_likelihood_distribution(gpslc_ctx* c, const double* U, const double* u
         c->last_info.assign(1, hinfo);
         return hinfo;
     });
+}
+
+int gpslc_likelihood_distribution(gpslc_ctx* c, const double* U, const double* uyLS, const double* xyLS,
+                                  double tyLS, double yScale, double yNoise, double doT, double* CovWW,
+                                  double* CovWWs, double* CovWWp, double* CovC11, double* CovC12,
+                                  double* CovC21, double* CovC22) {
+    const double ty = tyLS, ysc = yScale, yno = yNoise;
+    int rc = check_common(c, 1, U, uyLS, xyLS, &ty, &ysc, &yno);
+    if (rc) return rc;
+    return likelihood_distribution_impl(c, U, uyLS, xyLS, tyLS, yScale, yNoise, doT, nullptr, CovWW, CovWWs, CovWWp, CovC11,
+                                        CovC12, CovC21, CovC22);
+}
+
+int gpslc_likelihood_distribution_vec(gpslc_ctx* c, const double* U, const double* uyLS, const double* xyLS,
+                                      double tyLS, double yScale, double yNoise, const double* doT, double* CovWW,
+                                      double* CovWWs, double* CovWWp, double* CovC11, double* CovC12,
+                                      double* CovC21, double* CovC22) {
+    const double ty = tyLS, ysc = yScale, yno = yNoise;
+    int rc = check_common(c, 1, U, uyLS, xyLS, &ty, &ysc, &yno);
+    if (rc) return rc;
+    if ((rc = vec_levels_check(c, doT, c->n, 8))) return rc;
+    return likelihood_distribution_impl(c, U, uyLS, xyLS, tyLS, yScale, yNoise, 0.0, doT, CovWW, CovWWs, CovWWp, CovC11,
+                                        CovC12, CovC21, CovC22);
 }
 
 static int summarize_impl(gpslc_ctx* c, const double* dx, int64_t n, int64_t m, int64_t rs, int64_t cs,

@@ -207,6 +207,20 @@ struct IteMeanArgs {
 };
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st);
 
+// vector levels (per-individual interventions, k_vec.hip): the level sums and MeanITE as passes over the pairs
+struct VecArgs {
+    const double* X; const double* T; SampleParams p; long long s0;
+    int n, nX, nU, nt, L;
+    const double* doT;     // n x L: d_l[i] at doT[i + n*l]
+    // launch_vec_sums: c_l into row 1 + l of the augmented tiles of M, 1' Delta_l 1 into sumdelta [b][L] (part: [b][L][nt])
+    TRef M; double* part; double* sumdelta;
+    // launch_vec_mean: alpha [b][Np] solves (K + yNoise I) alpha = Y; element (i, s, l) at meanITE[i*si + s*ss + l*sl]
+    const double* alpha; const double* Y; long long y_sstride;
+    double* meanITE; long long si, ss, sl;
+};
+void launch_vec_sums(const VecArgs& a, int nbatch, hipStream_t st);
+void launch_vec_mean(const VecArgs& a, int nbatch, hipStream_t st);
+
 void launch_rbf_log(const double* X1, const double* X2, long long n, int d, const double* ls,
                     int ls_len, double* out, hipStream_t st);
 void launch_process_cov(const double* in, long long n, double scale, double noise, double* out,
@@ -218,6 +232,7 @@ struct DtArgs {
     int n, nX, nU, nt;
     const double* doT;     // device: intervention levels; batch element b = (sample s0 + b / lc, level l0 + b % lc)
     int l0, lc;
+    int vec;               // vector levels: doT is n x L (level l at doT + n*l), g_ij / g_ji / h_ij per pair
     double pred_noise;
     TRef W;    // nt x nt rectangular: receives D (rows = i, cols = j), D_ij = B_ij (r_j - e_ij)
     TRef Cm;   // lower packed nt: receives Delta + pred_noise*I (identity on the padding)
@@ -264,6 +279,7 @@ struct LdBuildArgs {
     const double* X; const double* T; SampleParams p; long long s0;
     int n, nX, nU, nt; double doT;
     TRef K, Ks, KsT, Kss;   // nt x nt rectangular each: CovWW, CovWWs, CovWWs', CovWsWs
+    const double* doTv;     // non-null: per-individual intervention d (n, device) instead of the scalar doT
 };
 void launch_ld_build(const LdBuildArgs& a, hipStream_t st);
 struct RectGatherArgs { TRef R; int n, nt; double* out; double diag_add; };   // -> column-major n x n

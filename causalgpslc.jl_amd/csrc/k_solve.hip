@@ -382,7 +382,10 @@ void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
 // dt_build: tiles of D (D_ij = B_ij (r_j - e_ij), src/estimation.jl:46 "CovWWs' - CovWW") into the
 // rectangular matrix W and Delta + pred_noise*I (Delta_ij = B_ij (e_ij - r_i - r_j + 1) =
 // CovWW - CovWWs - CovWWs' + CovWsWs, src/likelihood.jl:46-49 / estimation.jl:47, :82) into Cm.
+// VEC (per-individual intervention d, k_vec.hip): r_i, r_j become g_ij = exp(-(T_i - d_j)^2 / tyLS^2), g_ji, and the 1 of
+// CovWsWs becomes h_ij = exp(-(d_i - d_j)^2 / tyLS^2); the staged rr_ / rc_ hold d of the row / column block instead of r.
 // ---------------------------------------------------------------------------------------
+template <bool VEC>
 __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
@@ -395,8 +398,9 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
     const int tid = threadIdx.x;
     const int ti = blockIdx.x / a.nt, tj = blockIdx.x % a.nt;
     const long long b = blockIdx.y, s = a.s0 + b / a.lc;       // batch element = (sample, level) pair
-    const double doT = a.doT[a.l0 + (int)(b % a.lc)];
     const int n = a.n;
+    const double doT = VEC ? 0.0 : a.doT[a.l0 + (int)(b % a.lc)];
+    const double* dv = VEC ? a.doT + (long long)n * (a.l0 + (int)(b % a.lc)) : nullptr;
     const int gi0 = ti * GP_TS, gj0 = tj * GP_TS;
     const double tl = a.p.tyLS[s];
     const double wt = 1.0 / (tl * tl);
@@ -412,9 +416,14 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
         const double t1 = (gi0 + tid < n) ? a.T[gi0 + tid] : 0.0;
         const double t2 = (gj0 + tid < n) ? a.T[gj0 + tid] : 0.0;
         tr[tid] = t1; tc[tid] = t2;
-        const double d1 = t1 - doT, d2 = t2 - doT;
-        rr_[tid] = gp_exp_neg(-((d1 * d1) * wt));
-        rc_[tid] = gp_exp_neg(-((d2 * d2) * wt));
+        if (VEC) {
+            rr_[tid] = (gi0 + tid < n) ? dv[gi0 + tid] : 0.0;
+            rc_[tid] = (gj0 + tid < n) ? dv[gj0 + tid] : 0.0;
+        } else {
+            const double d1 = t1 - doT, d2 = t2 - doT;
+            rr_[tid] = gp_exp_neg(-((d1 * d1) * wt));
+            rc_[tid] = gp_exp_neg(-((d2 * d2) * wt));
+        }
     }
     __syncthreads();
     const double ys = a.p.yScale[s];
@@ -444,9 +453,17 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
             const double dt = tr[rp] - tcq;
             const double Bv = ys * gp_exp_neg(-lux[p]);
             const double Ev = gp_exp_neg(-((dt * dt) * wt));
-            const double ri = rr_[rp];
-            double Dv = Bv * (rj - Ev);
-            double Cv = Bv * (((Ev - ri) - rj) + 1.0);
+            double Dv, Cv;
+            if (VEC) {
+                const double di = rr_[rp], gij = tr[rp] - rj, gji = tcq - di, hij = di - rj;
+                const double Gij = gp_exp_neg(-((gij * gij) * wt)), Gji = gp_exp_neg(-((gji * gji) * wt));
+                Dv = Bv * (Gji - Ev);
+                Cv = Bv * (((Ev - Gij) - Gji) + gp_exp_neg(-((hij * hij) * wt)));
+            } else {
+                const double ri = rr_[rp];
+                Dv = Bv * (rj - Ev);
+                Cv = Bv * (((Ev - ri) - rj) + 1.0);
+            }
             const bool inside = (gi < n) && (gj < n);
             if (!inside) { Dv = 0.0; Cv = (gi == gj) ? 1.0 : 0.0; }
             else if (gi == gj) Cv += a.pred_noise;
@@ -457,10 +474,15 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
 }
 #define DT_LDS_BYTES(F) ((2 * (F) * GP_TS + 4 * GP_TS) * 8)
 
-void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st) {
+template <bool VEC>
+static void launch_dt_build_t(const DtArgs& a, int nbatch, hipStream_t st) {
     static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)dt_build_kernel, DT_LDS_BYTES(MAXF));
-    hipLaunchKernelGGL(dt_build_kernel, dim3(a.nt * a.nt, nbatch), dim3(256), DT_LDS_BYTES(a.nU + a.nX), st, a);
+    lds_opt_in(attr_set, (const void*)dt_build_kernel<VEC>, DT_LDS_BYTES(MAXF));
+    hipLaunchKernelGGL(dt_build_kernel<VEC>, dim3(a.nt * a.nt, nbatch), dim3(256), DT_LDS_BYTES(a.nU + a.nX), st, a);
+}
+void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st) {
+    if (a.vec) launch_dt_build_t<true>(a, nbatch, st);
+    else launch_dt_build_t<false>(a, nbatch, st);
 }
 
 // CovITEs[s + S*(i + n*j)] (src/estimation.jl:75, :82 layout: sample index fastest), both triangles
@@ -887,7 +909,10 @@ void launch_draws_scatter(const double* tmp, double* out, long long n, int L, in
 
 // ---------------------------------------------------------------------------------------
 // likelihoodDistribution blocks (src/likelihood.jl:24-39): K = B.*E, Ks = diag(r) B, Ks' = B diag(r), Kss = B
+// VEC (per-individual intervention d): Ks = B.*G, Ks' = B.*G', Kss = B.*H with G_ij = exp(-(T_i - d_j)^2 / tyLS^2),
+// H_ij = exp(-(d_i - d_j)^2 / tyLS^2); rr_ / rc_ then hold d of the row / column block
 // ---------------------------------------------------------------------------------------
+template <bool VEC>
 __global__ __launch_bounds__(256) void ld_build_kernel(LdBuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
@@ -916,9 +941,14 @@ __global__ __launch_bounds__(256) void ld_build_kernel(LdBuildArgs a) {
         const double t1 = (gi0 + tid < n) ? a.T[gi0 + tid] : 0.0;
         const double t2 = (gj0 + tid < n) ? a.T[gj0 + tid] : 0.0;
         tr[tid] = t1; tc[tid] = t2;
-        const double d1 = t1 - a.doT, d2 = t2 - a.doT;
-        rr_[tid] = gp_exp_neg(-((d1 * d1) * wt));
-        rc_[tid] = gp_exp_neg(-((d2 * d2) * wt));
+        if (VEC) {
+            rr_[tid] = (gi0 + tid < n) ? a.doTv[gi0 + tid] : 0.0;
+            rc_[tid] = (gj0 + tid < n) ? a.doTv[gj0 + tid] : 0.0;
+        } else {
+            const double d1 = t1 - a.doT, d2 = t2 - a.doT;
+            rr_[tid] = gp_exp_neg(-((d1 * d1) * wt));
+            rc_[tid] = gp_exp_neg(-((d2 * d2) * wt));
+        }
     }
     __syncthreads();
     const double ys = a.p.yScale[s];
@@ -938,17 +968,29 @@ __global__ __launch_bounds__(256) void ld_build_kernel(LdBuildArgs a) {
         double Ev = gp_exp_neg(-((dt * dt) * wt));
         if (gi0 + r >= n || gj0 + c >= n) { Bv = 0.0; Ev = 0.0; }
         tK[idx] = Bv * Ev;
-        tKs[idx] = rr_[r] * Bv;
-        tKsT[idx] = Bv * rc_[c];
-        tKss[idx] = Bv;
+        if (VEC) {
+            const double gij = tr[r] - rc_[c], gji = tc[c] - rr_[r], hij = rr_[r] - rc_[c];
+            tKs[idx] = gp_exp_neg(-((gij * gij) * wt)) * Bv;
+            tKsT[idx] = Bv * gp_exp_neg(-((gji * gji) * wt));
+            tKss[idx] = Bv * gp_exp_neg(-((hij * hij) * wt));
+        } else {
+            tKs[idx] = rr_[r] * Bv;
+            tKsT[idx] = Bv * rc_[c];
+            tKss[idx] = Bv;
+        }
     }
 }
 void launch_ld_build(const LdBuildArgs& a, hipStream_t st) {
     const int F = a.nU + a.nX;
     const int bytes = (2 * F * GP_TS + 4 * GP_TS) * 8;
-    static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)ld_build_kernel, (2 * MAXF * GP_TS + 4 * GP_TS) * 8);
-    hipLaunchKernelGGL(ld_build_kernel, dim3(a.nt * a.nt), dim3(256), bytes, st, a);
+    static DeviceOnce attr_set, attr_set_v;
+    if (a.doTv) {
+        lds_opt_in(attr_set_v, (const void*)ld_build_kernel<true>, (2 * MAXF * GP_TS + 4 * GP_TS) * 8);
+        hipLaunchKernelGGL(ld_build_kernel<true>, dim3(a.nt * a.nt), dim3(256), bytes, st, a);
+        return;
+    }
+    lds_opt_in(attr_set, (const void*)ld_build_kernel<false>, (2 * MAXF * GP_TS + 4 * GP_TS) * 8);
+    hipLaunchKernelGGL(ld_build_kernel<false>, dim3(a.nt * a.nt), dim3(256), bytes, st, a);
 }
 
 __global__ __launch_bounds__(256) void rect_gather_kernel(RectGatherArgs a) {

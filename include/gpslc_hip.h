@@ -223,6 +223,24 @@ int gpslc_predict_dev(gpslc_ctx* ctx, int64_t S, const double* U, const double* 
                       int32_t spp, uint64_t seed, const double* z_or_null,
                       double* meanSATE, double* varSATE, double* meanITE, double* ite_draws);
 
+/* Per-individual interventions (the Vector{Float64} / Vector{Bool} forms of `Intervention`, src/types.jl:138-143): level l
+ * is a vector d_l of n values that replaces fill(doT, n) in src/likelihood.jl:27-28 — tyCovLogS = rbfKernelLog(T, d_l, tyLS),
+ * tyCovLogSS = rbfKernelLog(d_l, d_l, tyLS) — so CovWWs = B .* G_l, CovWsWs = B .* H_l with G_l[i,j] = exp(-(T_i - d_l[j])^2 /
+ * tyLS^2), H_l[i,j] = exp(-(d_l[i] - d_l[j])^2 / tyLS^2).  A Bool vector is passed as 0.0 / 1.0; a scalar doT is exactly the
+ * vector fill(doT, n).  (The reference declares these forms for every estimation entry point but fails on them: fill(doT, n)
+ * of a vector has no rbfKernelLog method.)  doT is an n x L host array, doT[i + n*l]; every entry must be finite (else
+ * -10, "argument #10 is invalid").  Everything else — arguments, outputs and layouts, the normals (z layout, Philox stream
+ * s + S*l, gpslc_set_ensemble placement), chunking, schedule and gpslc_last_info — is gpslc_predict's.  Individuals with
+ * d_l[i] == T_i get MeanITE exactly 0.0 (row i of CovWWs' - CovWW is identically zero, src/estimation.jl:46); d_l == T gives
+ * exact zeros for MeanITE, meanSATE and CovITE - pred_noise*I.  fp64 only: a ctx created with GPSLC_FLAG_FP32_KERNEL returns
+ * GPSLC_ERR_UNSUPPORTED.  Each vector level costs passes over the (sample, pair) grid that a scalar level does not
+ * (DESIGN.md §11). */
+int gpslc_predict_vec(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                      const double* xyLS, const double* tyLS, const double* yScale,
+                      const double* yNoise, int32_t L, const double* doT, double pred_noise,
+                      int32_t spp, uint64_t seed, const double* z_or_null,
+                      double* meanSATE, double* varSATE, double* meanITE, double* ite_draws);
+
 /* The same call sharded over several GPUs of one node: what the loop of predictCounterfactualEffects (src/prediction.jl:30-33)
  * over the posterior samples (src/estimation.jl:78-84) becomes when the ensemble is partitioned.  ctxs[0..nctx) are
  * DISTINCT contexts created with the same (n, nX, nU), one per device (gpslc_create(&ctx_k, device_k, ...)), each holding the data
@@ -255,6 +273,13 @@ int gpslc_ite_distributions(gpslc_ctx* ctx, int64_t S, const double* U, const do
                             const double* yNoise, double doT, double pred_noise,
                             double* MeanITEs, double* CovITEs);
 
+/* ITEDistributions(g, doT) for a per-individual intervention doT (n values, host; see gpslc_predict_vec): same outputs and
+ * layouts as gpslc_ite_distributions.  A non-finite entry of doT returns -9.  GPSLC_FLAG_FP32_KERNEL: GPSLC_ERR_UNSUPPORTED. */
+int gpslc_ite_distributions_vec(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                                const double* xyLS, const double* tyLS, const double* yScale,
+                                const double* yNoise, const double* doT, double pred_noise,
+                                double* MeanITEs, double* CovITEs);
+
 /* likelihoodDistribution(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT) (src/likelihood.jl:8-52 and
  * its three reduced methods :55-94, :97-136, :139-174) for ONE parameter set, as the reference exports it:
  * the dense n x n blocks CovWW, CovWWs, CovWWp and the four posterior blocks CovC11..CovC22 (:46-49),
@@ -263,6 +288,13 @@ int gpslc_likelihood_distribution(gpslc_ctx* ctx, const double* U, const double*
                                   double tyLS, double yScale, double yNoise, double doT, double* CovWW,
                                   double* CovWWs, double* CovWWp, double* CovC11, double* CovC12,
                                   double* CovC21, double* CovC22);
+/* The same blocks for a per-individual intervention doT (n values, host; see gpslc_predict_vec): CovWWs = B .* G,
+ * CovWsWs = B .* H behind CovC12, CovC21, CovC22 (src/likelihood.jl:27-28, 35-39, 46-49).  A non-finite entry of doT returns
+ * -8.  Like gpslc_likelihood_distribution this entry point always evaluates in fp64, on any ctx. */
+int gpslc_likelihood_distribution_vec(gpslc_ctx* ctx, const double* U, const double* uyLS, const double* xyLS,
+                                      double tyLS, double yScale, double yNoise, const double* doT, double* CovWW,
+                                      double* CovWWs, double* CovWWp, double* CovC11, double* CovC12,
+                                      double* CovC21, double* CovC22);
 
 /* SATEsamples (src/estimation.jl:148-163): out[j*spp + d] = mean[j] + var[j] * z — the variance
  * is used as the standard deviation, as the reference does (src/estimation.jl:159).  Host-only

@@ -251,6 +251,26 @@ function predict(c::Ctx, p::Pack, doT::Vector{Float64}, pred_noise::Float64; spp
     mS, vS, mI, dr
 end
 
+"""`predict` for per-individual interventions: column l of `doT` (n x L) is the treatment vector of level l
+(gpslc_predict_vec; a scalar level x is the column fill(x, n)).  Same keywords and return value as `predict`."""
+function predict_vec(c::Ctx, p::Pack, doT::Matrix{Float64}, pred_noise::Float64; spp::Integer=0, seed::Integer=0,
+                     z=nothing, want_mean_ite::Bool=false, want_draws::Bool=false)
+    S, L, n = length(p.tyLS), size(doT, 2), c.n
+    size(doT, 1) == n || throw(DimensionMismatch("doT has $(size(doT, 1)) rows, n = $n"))
+    mS, vS = Matrix{Float64}(undef, S, L), Matrix{Float64}(undef, S, L)
+    mI = want_mean_ite ? Array{Float64}(undef, n, S, L) : nothing
+    dr = want_draws ? Array{Float64}(undef, L, n, S * spp) : nothing
+    zf = f64(z)
+    GC.@preserve p doT zf mS vS mI dr check(c, ccall((:gpslc_predict_vec, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Ptr{Float64}, Float64, Int32, UInt64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        L, pointer(doT), pred_noise, spp, seed, ptr(zf),
+        pointer(mS), pointer(vS), ptr(mI), ptr(dr)))
+    mS, vS, mI, dr
+end
+
 """`predict` sharded over several GPUs of one node — `cs` = one context per device (`Ctx(n, nX, nU; device=k)`, each with
 the data: `set_data!` on every one), the posterior samples split into contiguous blocks, one host thread per context inside the
 library, every device copying its block of the results into these host arrays.  Same results as `predict(cs[1], …)` over all S
@@ -305,6 +325,36 @@ function ite_distributions(c::Ctx, p::Pack, doT::Float64, pred_noise::Float64; w
         c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
         doT, pred_noise, pointer(M), ptr(Cv)))
     M, Cv
+end
+
+"""`ite_distributions` for a per-individual intervention `doT` (n values): gpslc_ite_distributions_vec."""
+function ite_distributions_vec(c::Ctx, p::Pack, doT::Vector{Float64}, pred_noise::Float64; want_cov::Bool=true)
+    S, n = length(p.tyLS), c.n
+    length(doT) == n || throw(DimensionMismatch("doT has length $(length(doT)), n = $n"))
+    M = Matrix{Float64}(undef, S, n)
+    Cv = want_cov ? Array{Float64}(undef, S, n, n) : nothing
+    GC.@preserve p doT M Cv check(c, ccall((:gpslc_ite_distributions_vec, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        pointer(doT), pred_noise, pointer(M), ptr(Cv)))
+    M, Cv
+end
+
+"""`likelihood_distribution` for a per-individual intervention `doT` (n values): gpslc_likelihood_distribution_vec."""
+function likelihood_distribution_vec(c::Ctx, U, uyLS, xyLS, tyLS::Float64, yScale::Float64, yNoise::Float64,
+                                     doT::Vector{Float64})
+    n = c.n
+    length(doT) == n || throw(DimensionMismatch("doT has length $(length(doT)), n = $n"))
+    blocks = [Matrix{Float64}(undef, n, n) for _ in 1:7]
+    Uf, uy, xy = f64(U), f64(uyLS), f64(xyLS)
+    GC.@preserve Uf uy xy doT blocks check(c, ccall((:gpslc_likelihood_distribution_vec, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Float64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, ptr(Uf), ptr(uy), ptr(xy), tyLS, yScale, yNoise, pointer(doT),
+        pointer(blocks[1]), pointer(blocks[2]), pointer(blocks[3]), pointer(blocks[4]), pointer(blocks[5]),
+        pointer(blocks[6]), pointer(blocks[7])))
+    blocks
 end
 
 """The seven dense blocks of likelihoodDistribution for one parameter set (src/likelihood.jl:8-174)."""
@@ -531,9 +581,22 @@ function _features(parts_and_ls::Pair...)
     end
     Matrix{Float64}(reduce(hcat, blocks)), ls
 end
-_dot(doT::Union{Bool,Float64}) = Float64(doT)
-_dot(doT) = throw(ArgumentError("vector interventions: fill(doT, n) of a vector has no rbfKernelLog method in the " *
-                                "reference either (src/likelihood.jl:27-28)"))
+# An Intervention (src/types.jl:138-143) for n individuals: a scalar stays a Float64 (one level, fill(doT, n)); a Vector{Float64}
+# / Vector{Bool} of length n becomes the per-individual level the *_vec entry points take (the reference declares these forms
+# but fails on them: fill(doT, n) of a vector has no rbfKernelLog method, src/likelihood.jl:27-28)
+_dot(doT::Union{Bool,Float64}, n::Integer) = Float64(doT)
+function _dot(doT::Union{Vector{Bool},Vector{Float64}}, n::Integer)
+    length(doT) == n || throw(DimensionMismatch("intervention vector of length $(length(doT)) for n = $n individuals"))
+    Float64.(doT)
+end
+# one level through the scalar or the vector entry point
+_ld_blocks(c, Um, uyLS, xyLS, tyLS, yScale, yNoise, d::Float64) = GPSLCHip.likelihood_distribution(c, Um, uyLS, xyLS, tyLS, yScale, yNoise, d)
+_ld_blocks(c, Um, uyLS, xyLS, tyLS, yScale, yNoise, d::Vector{Float64}) =
+    GPSLCHip.likelihood_distribution_vec(c, Um, uyLS, xyLS, tyLS, yScale, yNoise, d)
+_ite_dists(c, p, d::Float64, pn) = GPSLCHip.ite_distributions(c, p, d, pn)
+_ite_dists(c, p, d::Vector{Float64}, pn) = GPSLCHip.ite_distributions_vec(c, p, d, pn)
+_levels(d::Float64) = [d]
+_levels(d::Vector{Float64}) = reshape(d, :, 1)
 
 # ---- the device side of a GPSLCObject: one Ctx + one posterior pack, for as long as the object lives ----------------
 # GPSLCObject is an immutable struct (src/types.jl:249-258): it can carry neither a finalizer nor be a WeakKeyDict key.
@@ -613,6 +676,11 @@ function _predict(g::GPSLCObject, devices, doT::Vector{Float64}; kw...)
     mS, vS, mI, ite, _ = GPSLCHip.predict_multi(ctxs(g, devices), posterior_pack(g), doT, pn; kw...)
     mS, vS, mI, ite
 end
+# per-individual levels (n x L): one GPU only (gpslc_predict_multi takes scalar levels)
+function _predict(g::GPSLCObject, devices, doT::Matrix{Float64}; kw...)
+    devices === nothing || throw(ArgumentError("vector interventions are not sharded over devices: pass devices=nothing"))
+    GPSLCHip.predict_vec(ctx(g), posterior_pack(g), doT, g.hyperparams.predictionCovarianceNoise; kw...)
+end
 
 """ctx(g): the device context holding g.X, g.T, g.Y (src/types.jl:249-258), created on first use."""
 ctx(g::GPSLCObject) = _device_side(g).ctx
@@ -667,7 +735,7 @@ function _likelihood_blocks(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT)
     Um = _umat(U)
     c = GPSLCHip.dctx(n, X === nothing ? 0 : size(X, 2), _ncols(Um))
     GPSLCHip.set_data!(c, X, T, Y)
-    b = GPSLCHip.likelihood_distribution(c, Um, uyLS, xyLS, tyLS, yScale, yNoise, _dot(doT))
+    b = _ld_blocks(c, Um, uyLS, xyLS, tyLS, yScale, yNoise, _dot(doT, n))
     # CovWW and CovWWp come back as the reference returns them, wrapped in Symmetric (src/likelihood.jl:31-32): a caller's
     # `CovWWp \ y` then dispatches to Bunch-Kaufman as it does there, not to LU
     Y, LinearAlgebra.Symmetric(b[1]), b[2], LinearAlgebra.Symmetric(b[3]), b[4], b[5], b[6], b[7]   # Y, CovWW, CovWWs, CovWWp, CovC11, CovC12, CovC21, CovC22 (:51)
@@ -716,7 +784,7 @@ function conditionalITE(uyLS::Union{Vector{Float64},Nothing}, xyLS::Union{Array{
                       uyLS === nothing ? nothing : reshape(copy(uyLS), :, 1),
                       xyLS === nothing ? nothing : reshape(GPSLCHip.f64(vec(xyLS)), :, 1),
                       [tyLS], [yNoise], [yScale])
-    M, Cv = GPSLCHip.ite_distributions(c, p, _dot(doT), 0.0)             # CovITE itself: the jitter is ITEDistributions' (:82)
+    M, Cv = _ite_dists(c, p, _dot(doT, n), 0.0)                          # CovITE itself: the jitter is ITEDistributions' (:82)
     M[1, :], Cv[1, :, :]
 end
 
@@ -726,11 +794,11 @@ function conditionalITE(g::GPSLCObject, psindex::Int64, doT::Intervention)      
 end
 
 function ITEDistributions(g::GPSLCObject, doT::Intervention)                                                       # :66-86
-    GPSLCHip.ite_distributions(ctx(g), posterior_pack(g), _dot(doT), g.hyperparams.predictionCovarianceNoise)
+    _ite_dists(ctx(g), posterior_pack(g), _dot(doT, getN(g)), g.hyperparams.predictionCovarianceNoise)
 end
 
 function SATEDistributions(g::GPSLCObject, doT::Intervention; devices=nothing)                                    # :127-140
-    mS, vS, _, _ = _predict(g, devices, [_dot(doT)])
+    mS, vS, _, _ = _predict(g, devices, _levels(_dot(doT, getN(g))))
     mS[:, 1], vS[:, 1]          # O(N^2) per posterior sample: the N x N covariance is never formed
 end
 
@@ -751,7 +819,7 @@ function sampleITE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64
                    seed::Union{Nothing,Integer}=nothing, devices=nothing)                                          # :86-89
     n, S = getN(g), getNumPosteriorSamples(g)
     sd, z = _normals(n, samplesPerPosterior, S, 1, seed)
-    _, _, _, ite = _predict(g, devices, [_dot(doT)]; spp=samplesPerPosterior, seed=sd, z=z, want_draws=true)
+    _, _, _, ite = _predict(g, devices, _levels(_dot(doT, n)); spp=samplesPerPosterior, seed=sd, z=z, want_draws=true)
     ite[1, :, :]                                                          # n x (S * spp), sample outer / draw inner (:100-107)
 end
 
