@@ -137,7 +137,8 @@ struct gpslc_ctx {
     std::vector<size_t> task_sync_ints;
     std::vector<TaskList> task_lists;
     unsigned long long task_clock = 0;
-    bool task_used = false;
+    bool task_used = false;        // a persistent launch ran since the time-out words were last read (check_task_timeout)
+    bool task_timed_out = false;   // a time-out word read when its slot's buffer was replaced by a larger one, not yet reported
     int task_min_nt = 2, task_max_nt = TASK_MAX_NT;   // tile counts in this range take the persistent launch (128 < N <= 4096: with
                                             // groups of 32 it wins at every tile count the descriptor can hold — N = 256 +1..3 %, 384 +6 %, 512 +10 %,
                                             // 1024 +6 %, 1536 +4 %, 2048 +2.4 %, 3072 +1.8 %, 4096 +1.0..1.3 % against panels of 8 + trailing
@@ -460,15 +461,26 @@ void potrf_tasks(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, lon
     if (c->task_sync.size() <= slot) { c->task_sync.resize(slot + 1, nullptr); c->task_sync_ints.resize(slot + 1, 0); }
     const size_t ints = TASK_SYNC_HDR + (size_t)TASK_SYNC_STRIDE * nb;
     if (c->task_sync_ints[slot] < ints) {
-        if (c->task_sync[slot]) { HC(hipDeviceSynchronize()); HC(hipFree(c->task_sync[slot])); c->task_sync[slot] = nullptr; }
+        if (c->task_sync[slot]) {
+            HC(hipDeviceSynchronize());
+            int w = 0;           // a time-out of an earlier chunk of this call must survive the larger buffer
+            HC(hipMemcpy(&w, c->task_sync[slot] + 8, sizeof(int), hipMemcpyDeviceToHost));
+            if (w != 0) c->task_timed_out = true;
+            HC(hipFree(c->task_sync[slot]));
+            c->task_sync[slot] = nullptr;
+        }
         HC(hipMalloc((void**)&c->task_sync[slot], ints * sizeof(int)));
+        HC(hipMemsetAsync(c->task_sync[slot], 0, ints * sizeof(int), st));
         c->task_sync_ints[slot] = ints;
     }
     static const int g_env = diag_env("GPSLC_TASK_G", 0);
     static const int r_env = diag_env("GPSLC_TASK_ROWS", 0);
     const TaskList& tl = task_list_for(c, nt, back_alpha ? 1 : 0, nb, g_env > 0 ? g_env : c->task_group,
                                        std::max(1, std::min(4, r_env > 0 ? r_env : (nt > 8 ? 1 : c->task_rows))), short_rows > 32);
-    HC(hipMemsetAsync(c->task_sync[slot], 0, ints * sizeof(int), st));
+    // every word but the time-out word [8]: a time-out of an earlier chunk on this slot stays set until check_task_timeout has
+    // read it (zeroing it here lets a later chunk wipe it: the call then returns OK, or a failed pivot, from stale tiles)
+    HC(hipMemsetAsync(c->task_sync[slot], 0, 8 * sizeof(int), st));
+    HC(hipMemsetAsync(c->task_sync[slot] + 9, 0, (ints - 9) * sizeof(int), st));
     PotrfTaskArgs a{};
     a.g.A = M; a.g.B = M; a.g.C = M;
     a.g.F = TRef{inv, inv_bstride, 1, 0, 0, 0};
@@ -481,6 +493,13 @@ void potrf_tasks(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, lon
     c->task_used = true;
     const double Np = (double)nt * GP_TS;
 #ifdef GPSLC_DIAG
+    // measurement build, GPSLC_TASK_FENCE bit 7: bit 6 (the withheld publish of the time-out test) applies to the first persistent
+    // launch of the process only — the later chunks of the same call run normally (tests/test_gpu_tasks.py)
+    if (a.fence_mode & 0x80) {
+        static std::atomic<int> launches{0};
+        if (launches.fetch_add(1) > 0) a.fence_mode &= ~0x40;
+        a.fence_mode &= ~0x80;
+    }
     // measurement build, GPSLC_TASK_DBG=<n>: per-task stamps of the n-th launch -> gpurun_out/task_dbg.bin (tools/task_stamps.py)
     static const int dbg_at = diag_env("GPSLC_TASK_DBG", 0);
     static int dbg_seen = 0;
@@ -507,16 +526,39 @@ void potrf_tasks(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, lon
 #endif
 }
 
-// after the call's streams have drained: a time-out inside a persistent factorisation launch is an internal error
-void check_task_timeout(gpslc_ctx* c) {
-    if (!c->task_used) return;
+// the time-out words of every stream slot, read and cleared (the launches leave them alone: see potrf_tasks), once the streams
+// have drained; true when any persistent launch since the last read timed out
+bool take_task_timeouts(gpslc_ctx* c) {
+    bool timed_out = c->task_timed_out;
     c->task_used = false;
+    c->task_timed_out = false;
     for (size_t i = 0; i < c->task_sync.size(); ++i) {
         if (!c->task_sync[i]) continue;
         int w = 0;
         HC(hipMemcpy(&w, c->task_sync[i] + 8, sizeof(int), hipMemcpyDeviceToHost));
-        if (w != 0) throw std::runtime_error("persistent factorisation launch timed out waiting for a producer task");
+        if (w != 0) {
+            const int zero = 0;
+            HC(hipMemcpy(c->task_sync[i] + 8, &zero, sizeof(int), hipMemcpyHostToDevice));
+            timed_out = true;
+        }
     }
+    return timed_out;
+}
+
+// after the call's streams have drained: a time-out inside any persistent factorisation launch of the call (any chunk, any
+// stream slot) is an internal error
+void check_task_timeout(gpslc_ctx* c) {
+    if (c->task_used && take_task_timeouts(c))
+        throw std::runtime_error("persistent factorisation launch timed out waiting for a producer task");
+}
+
+// at the start of a call: a previous call that threw between its persistent launches and check_task_timeout (a HIP error, an
+// allocation failure) left its time-out words unread — drain what it left in flight and clear them, so that they neither fail
+// this call nor let its launches stop waiting for their producers
+void reset_stale_task_timeouts(gpslc_ctx* c) {
+    if (!c->task_used) return;
+    for (auto st : c->streams) HC(hipStreamSynchronize(st));
+    (void)take_task_timeouts(c);
 }
 
 // Blocked Cholesky of the leading nt x nt tiles of the lower-packed ntot x ntot tile matrix M; the
@@ -701,6 +743,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     if (io.nX < 0) io.nX = c->nX;
     if (!io.Y) { io.Y = c->dY; io.y_sstride = 0; }
     if (io.p.u_sstride == 0 && io.nU > 0 && io.p.U != nullptr && !io.p_shared_u) io.p.u_sstride = (long long)c->n * io.nU;
+    reset_stale_task_timeouts(c);
     ensure_streams(c);
     const int n = (int)c->n, nt = c->nt;
     const int L = io.L;

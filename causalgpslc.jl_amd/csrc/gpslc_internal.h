@@ -147,7 +147,9 @@ struct PotrfTaskArgs {
     GemmArgs g;             // A = B = C = the tile matrix, F = the inverted diagonal blocks, k0 = 0, short_row0 = nt, short_rows,
                             // sym = 3 with an augmented row riding along, info / info_base, nbatch
     const unsigned* list;   // TASK_LIST_HDR header words, then the descriptors of the eight queues
-    int* sync;              // TASK_SYNC_HDR + TASK_SYNC_STRIDE * nbatch ints, zeroed by the launcher's caller before every launch
+    int* sync;              // TASK_SYNC_HDR + TASK_SYNC_STRIDE * nbatch ints: the launcher's caller zeroes all of them when it allocates
+                            // the buffer and all but the time-out word [8] before every launch; [8] is read and cleared once per
+                            // call, after every chunk has drained (check_task_timeout), so that no later chunk can wipe a time-out
     int nt;
     double* alpha;          // non-null: the list ends every matrix with its back-substitution, alpha = L^-T z -> alpha[b][nt 128]
     int fence_mode;         // measurement build only (0 = release / acquire as documented)

@@ -3,7 +3,10 @@ schedule it replaces at small tile counts.  Both run the same device functions o
 output must be equal BIT FOR BIT — a stale read between two workgroups (a missing release / acquire, a task that starts
 before its producer has published) shows up as a difference, not as a tolerance question.  The work replaced:
 src/likelihood.jl:42-43, src/estimation.jl:46 (the reference factorises CovWWp three times per unit, one matrix at a time).
-Parity with the oracle at these sizes is covered by the other GPU suites, which now run through this launch by default."""
+The tests here force the launch down to a handful of matrices (gpslc_set_task_schedule); by default it needs >= 256 matrices
+per chunk, which the oracle-parity suites at S <= 48 (test_gpu_fullsize.py and the others) never reach.  Parity of the DEFAULT
+launch with the oracle is covered by tests/test_gpu_task_load.py (bench-scale calls against the batched host reference, every
+queue run's first and last matrix included) and test_gpu_vector_intervention.py::test_predict_vec_persistent_task_launch."""
 import numpy as np
 import pytest
 
@@ -170,3 +173,49 @@ def test_a_broken_hand_off_times_out_instead_of_hanging(tmp_path):
     assert "ERROR" in out and "timed out" in out, out
     secs = float(out.strip().splitlines()[-1].split()[1])
     assert secs < 60, out
+
+
+@pytest.mark.parametrize("streams", [1, 2])
+def test_a_time_out_in_any_chunk_fails_the_call_and_does_not_leak(tmp_path, streams):
+    """A time-out in the FIRST of three chunks must fail the call: the later chunks' launches (on the same stream slot with one
+    stream, on both slots with two) must not wipe the time-out word before the call reads it — else the call comes back OK, or
+    with a failed pivot, from the timed-out chunk's stale tiles.  The next call on the same context must then succeed and equal
+    the per-column schedule bit for bit — no stale time-out reaches it.  Measurement build, GPSLC_TASK_FENCE bit 6 (diag(1) of
+    matrix 0 withholds its publish) with bit 7 (... in the process's first persistent launch only), in a fresh process as above."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    diag = os.path.join(root, "causalgpslc.jl_amd", "csrc", "libgpslc_hip_diag.so")
+    if not os.path.exists(diag):
+        pytest.skip("measurement build not present (make -C causalgpslc.jl_amd/csrc diag)")
+    code = (
+        "import sys, numpy as np\n"
+        f"sys.path[:0] = [{root!r}, {os.path.join(root, 'tests')!r}, {os.path.join(root, 'oracle')!r}]\n"
+        "import causalgpslc_jl_amd as gp, cases\n"
+        "gp._lib.LIB_PATH = gp._lib.LIB_PATH.replace('libgpslc_hip.so', 'libgpslc_hip_diag.so')\n"
+        "c = cases.make_case(520, 'UX', False, S=9, seed=3)\n"
+        "outs = []\n"
+        "for tiles in (32, 0):\n"
+        "    g = cases.gpslc_object(gp, c)\n"
+        "    g.ctx().set_task_schedule(2, tiles, 1, 0)\n"
+        f"    g.ctx().set_tuning(3, 0, {streams})\n"
+        "    if tiles:\n"
+        "        try:\n"
+        "            gp.predict(g, [0.2], want_mean_ite=True)\n"
+        "            print('NO ERROR')\n"
+        "        except gp.GPSLCError as e:\n"
+        "            print('ERROR', e.status, str(e))\n"
+        "        except gp.PosDefException as e:\n"             # the garbage of the timed-out chunk, reported as a pivot
+        "            print('NOT POSITIVE DEFINITE', e.info)\n"
+        "    outs.append(gp.predict(g, [0.2], want_mean_ite=True))\n"
+        "    print('SECOND CALL OK')\n"
+        "same = all(np.array_equal(x, y) for x, y in zip(*outs))\n"
+        "print('BIT-IDENTICAL' if same else 'DIFFERENT')\n")
+    env = dict(os.environ, GPSLC_TASK_FENCE=str(0x30 | 0x40 | 0x80))
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=240)
+    out = r.stdout
+    assert r.returncode == 0, (out, r.stderr[-2000:])
+    lines = out.strip().splitlines()
+    assert lines and lines[0].startswith("ERROR") and "timed out" in lines[0], out
+    assert lines[1:] == ["SECOND CALL OK", "SECOND CALL OK", "BIT-IDENTICAL"], out
