@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — posterior samples/s of the GP hot path (Gram build + Cholesky + predict) at N = 4096.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 --steps K is the number of timed steps of the region `value` and `ms_per_step` come from (K >= 1); --dump-outputs DIR
 writes what the last timed step computed (dump_outputs).  Inputs are seeded: equal arguments give equal inputs.
+
+A plain run does only what the headline figure needs: it sets up, runs W warm-up steps, times the K steps, writes the dump
+if asked and prints the JSON line (with the roofline of the timed region's own launches).  --full adds everything else the
+line can carry, each part in runs of its own after the timed region: the extra timed regions of --repeats, the panel-schedule
+leg, config4, cpu_baseline with sate_rel_err, units, configs and multi_abi (each still skipped by its --no-* option).
 
 N > 1 without a process group in the environment (no WORLD_SIZE): this process only launches
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>` as a CHILD (before
@@ -18,7 +23,7 @@ for L = 1 intervention level).  Inputs are resident in HBM before the timed regi
 device pointers; torch only provides device memory and the process group).  Posterior samples shard over ranks
 with no data-path collective; one all_gather of the (S x L) SATE arrays closes each step (weak scaling).
 
-The JSON line carries
+The JSON line carries, beyond the headline keys (roofline in every run, its panel_schedule and the rest under --full)
   roofline      the dominant kernel (tile_gemm_nt_kernel<1, 0>, the f64-MFMA tile update): algorithmic flop
                 (textbook count: diagonal tiles half, augmented rows by their live rows) / HIP-event time of every
                 launch inside the timed region, against the fp64 matrix peak (78.6 TFLOP/s, AMD spec; the guides
@@ -85,6 +90,12 @@ def parse():
                                                                      "the persistent launch (0 = the library's default)")
     ap.add_argument("--task-group", type=int, default=0, help="gpslc_set_task_schedule: matrices per group of the task order")
     ap.add_argument("--no-mean-ite", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what the headline figure does not need: the other timed regions of "
+                         "--repeats, the panel-schedule leg, config4, the CPU baseline and sate_rel_err, units B / C, BASELINE "
+                         "configs 2 / 3 / 5 and multi_abi.  The options of those legs (--repeats, --no-cpu-baseline, --cpu-units, "
+                         "--no-units, --unit-b-*, --no-config4, --config4-*, --no-configs, --no-panel-leg, --no-multi-abi) "
+                         "apply under --full only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-units", type=int, default=3)
     ap.add_argument("--no-units", action="store_true", help="skip the unit B / unit C measurements")
@@ -94,7 +105,7 @@ def parse():
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--repeats", type=int, default=3,
                     help="timed regions of --steps steps each: `value` is the first, `value_runs` lists all (box-to-box spread is "
-                         "about 1 %; this shows the run-to-run spread on one box)")
+                         "about 1 %%; this shows the run-to-run spread on one box)")
     ap.add_argument("--no-config4", action="store_true", help="skip the BASELINE configs[3] leg (64 intervention levels per sample)")
     ap.add_argument("--config4-levels", type=int, default=64)
     ap.add_argument("--config4-steps", type=int, default=2)
@@ -120,6 +131,10 @@ def parse():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.dump_outputs:
         a.dump_outputs = os.path.abspath(a.dump_outputs)
+    if not a.full:
+        # a plain run: set up, warm up, time --steps steps, dump, print the line; every other leg belongs to --full
+        a.repeats = 1
+        a.no_panel_leg = a.no_config4 = a.no_cpu_baseline = a.no_units = a.no_configs = a.no_multi_abi = True
     return a
 
 
@@ -991,7 +1006,7 @@ def main():
                         "2.4 GHz: SQ_ACTIVE_INST_VALU x 4 clocks / 1024 SIMDs per 1,024-sample launch, " + gnote + "): the "
                         "MFMA-only ceiling ignores that both instruction classes use the same fp64 units")
             out["units"]["A"] = ua
-        if world > 1:
+        if world > 1 and a.full:
             out["units"] = "N=1 only (units B / C and the unit-A ceilings are single-GPU measurements: run without --gpus)"
             out["configs"] = "N=1 only (BASELINE configs[1] and configs[4] are timed on one GPU: run without --gpus)"
         if world == 1 and not a.no_configs and not a.timing_only:

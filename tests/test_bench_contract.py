@@ -149,7 +149,7 @@ def test_two_rank_rehearsal_line_carries_the_whole_contract():
     env["GPSLC_BENCH_REHEARSAL"] = "1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--", "--gpus", "2", "--steps", "1",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--", "--full", "--gpus", "2", "--steps", "1",
            "--warmup", "1", "--n", "640", "--d", "4", "--nu", "1", "--samples-per-step", "24", "--config4-levels", "8",
            "--config4-steps", "1", "--cpu-units", "2"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -185,7 +185,7 @@ def test_one_rank_over_rccl_runs_the_collective_path():
     env["GPSLC_BENCH_FORCE_DIST"] = "1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--", "--gpus", "1", "--steps", "2",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--", "--full", "--gpus", "1", "--steps", "2",
            "--warmup", "1", "--n", "640", "--d", "4", "--nu", "1", "--samples-per-step", "48", "--config4-levels", "8",
            "--config4-steps", "1", "--no-cpu-baseline", "--no-units", "--no-configs", "--repeats", "1"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -196,6 +196,54 @@ def test_one_rank_over_rccl_runs_the_collective_path():
     assert d["n_gpus"] == 1 and d["value"] > 0 and "REHEARSAL" not in d["data"]
     assert "1 rank(s)" in d["config"]["sharding"] and d["config4"]["parity"]["ok"]
     assert abs(d["value"] - 48 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+
+
+# the keys only --full puts on the line (legs after the timed region, each with runs of its own)
+FULL_ONLY = ("cpu_baseline", "sate_rel_err", "units", "config4", "configs", "multi_abi")
+
+
+def test_plain_run_leaves_every_other_leg_to_full(monkeypatch):
+    """A plain run times one region and runs no leg after it, whatever --no-* / --repeats say; --full runs them as before."""
+    sys.path.insert(0, ROOT)
+    import bench
+    legs = ("no_panel_leg", "no_config4", "no_cpu_baseline", "no_units", "no_configs", "no_multi_abi")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2", "--repeats", "5"])
+    a = bench.parse()
+    assert not a.full and a.repeats == 1 and all(getattr(a, k) for k in legs)
+    assert (a.steps, a.warmup, a.gpus) == (4, 2, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full and a.repeats == 3 and not any(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-units", "--repeats", "1"])
+    a = bench.parse()
+    assert a.no_units and a.repeats == 1 and not a.no_config4
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_line_only(tmp_path):
+    """bench.py without --full on a small problem: exit 0, the headline keys with the roofline of the timed region, one timed
+    region (value_runs), none of the --full legs, and the same dump as a --full run of the same arguments."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--n", "640", "--d", "4", "--nu", "1", "--samples-per-step", "48"]
+    r = _run(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["metric"].endswith("SATE rel-err vs CPU") and d["unit"] == "posterior samples/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - 48 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["value_runs"] == [d["value"]] and "panel_schedule" not in d.get("roofline", {})
+    assert not [k for k in FULL_ONLY if k in d]
+    r = _run(args + ["--full", "--no-cpu-baseline", "--no-units", "--no-configs", "--config4-levels", "4", "--config4-steps", "1",
+                     "--dump-outputs", str(tmp_path / "full")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    f = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert len(f["value_runs"]) == 3 and f["config4"]["parity"]["ok"]
+    for k in ("meanSATE", "varSATE", "meanITE"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f"{k}.npy"), np.load(tmp_path / "full" / f"{k}.npy")), k
 
 
 def test_steps_must_be_positive():

@@ -8,7 +8,7 @@ timeout -k 10 800 python3 -m pytest tests/test_gpu_estimation.py tests/test_gpu_
 tail -4 $OUT/tests.log
 run() {
   label=$1; shift
-  timeout -k 10 300 python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs --no-config4 --diag-lib "$@" > $OUT/c.json 2> $OUT/c.err || tail -3 $OUT/c.err
+  timeout -k 10 300 python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-configs --no-config4 --diag-lib "$@" > $OUT/c.json 2> $OUT/c.err || tail -3 $OUT/c.err
   python3 -c "
 import json
 d=json.loads(open('$OUT/c.json').read().strip().splitlines()[-1]); u=d['units']; print('$label: B', round(u['B']['value'],1), round(u['B']['frac'],3), 'single-level', round(u['B']['single_level']['value'],1), round(u['B']['single_level']['frac'],3), 'parity', u['B']['parity']['ok'], u['B']['parity']['draw_err'])" | tee -a $OUT/log.txt

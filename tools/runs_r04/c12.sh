@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 L=causalgpslc.jl_amd/csrc
 run() {
   label=$1; shift
-  timeout -k 10 200 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-units --no-configs "$@" > $OUT/c.json 2> $OUT/c.err || tail -3 $OUT/c.err
+  timeout -k 10 200 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-units --no-configs "$@" > $OUT/c.json 2> $OUT/c.err || tail -3 $OUT/c.err
   python3 -c "
 import json
 d=json.loads(open('$OUT/c.json').read().strip().splitlines()[-1]); r=d['roofline']; print('$label:', round(d['value'],1), r['kernel'][:24], round(r['achieved'],2), round(r.get('second_kernel',{}).get('achieved',0),2), 'parity', d.get('config4',{}).get('parity',{}).get('ok'))" | tee -a $OUT/log.txt

@@ -11,4 +11,4 @@ val() { python3 -c "import json,sys; d=json.loads(open('$1').read().strip().spli
 for r in 1 2 3 4; do
 GPSLC_TASK_ROWS=$r timeout -k 10 300 $B --diag-lib > $O/rows$r.json 2> $O/err.txt; val $O/rows$r.json "N=4096 rows per strip task=$r (measurement build)"
 done
-S=$(date +%s); timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$? in $(( $(date +%s) - S )) s"; cut -c1-400 $O/bench_default.json
+S=$(date +%s); timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$? in $(( $(date +%s) - S )) s"; cut -c1-400 $O/bench_default.json
