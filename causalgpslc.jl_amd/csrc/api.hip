@@ -162,11 +162,15 @@ struct gpslc_ctx {
     std::vector<double> stage_f, stage_rest;   // host staging of gpslc_nodes_logpdf's batched pass (grown, never shrunk)
     std::string err;
     std::vector<int32_t> last_info;
-    // cached factor of the last dense covariance given to gpslc_mvn_logpdf (SigmaU is constant per data set)
+    // the last dense covariance handed to gpslc_mvn_logpdf / gpslc_mvn_draw (SigmaU is constant per data set).  n <= 640 (both
+    // paths can run): the matrix itself, always, whichever path the hand-over took; the tiled factor is built from it when a
+    // call on the tiled path finds it missing or older (mvn_tiles_gen != mvn_gen).  n > 640: only the tiled factor.
     double* mvn_tiles = nullptr;     // tiled factor (substitution-based: no inverted diagonal blocks are kept)
-    double* mvn_dense = nullptr;     // small n: the dense covariance itself (every evaluation refactorises it in LDS)
-    double mvn_logdet = 0.0;
-    int mvn_info = 0;
+    double* mvn_dense = nullptr;     // n <= 640: the dense covariance itself (the single-workgroup path refactorises it in LDS)
+    uint64_t mvn_gen = 0;            // hand-overs so far
+    uint64_t mvn_tiles_gen = 0;      // the hand-over mvn_tiles was factorised from (0 = none)
+    double mvn_logdet = 0.0;         // of mvn_tiles
+    int mvn_info = 0;                // LAPACK-style info of the latest covariance
     bool mvn_valid = false;
     // L2-blocked visiting orders of the lower-triangular tile sets, keyed by the triangle size m
     std::vector<unsigned short*> tri_order;
@@ -2106,41 +2110,64 @@ int gpslc_nodes_draw(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, doubl
     });
 }
 
-// caches the dense covariance (small n: every evaluation refactorises it in LDS) or its tiled factor (substitution-based:
-// SigmaU * uNoise is near-singular by construction, 1e-13 jitter, src/utils.jl:17-33) in the context; mvn_info = its LAPACK-style info
+// both paths of gpslc_mvn_logpdf / gpslc_mvn_draw can run on this ctx (n <= 640): then the dense covariance is always kept
+static bool mvn_dual(const gpslc_ctx* c) { return fast_path_ok(c, 0, 1); }
+
+// the tiled factor of the device covariance dcov (substitution-based: SigmaU * uNoise is near-singular by construction, 1e-13
+// jitter, src/utils.jl:17-33); mvn_logdet / mvn_info from it, and it now stands for hand-over mvn_gen
+static void mvn_factor_tiles(gpslc_ctx* c, const double* dcov) {
+    ensure_streams(c);
+    const int nt = c->nt;
+    const long long nlow = (long long)nt * (nt + 1) / 2;
+    hipStream_t st = c->streams[0];
+    c->mvn_tiles_gen = 0;
+    if (!c->mvn_tiles) HC(hipMalloc((void**)&c->mvn_tiles, (size_t)nlow * GP_TSQ * 8));
+    DevBuf old, oq, info;
+    old.alloc(8); oq.alloc(8); info.alloc(sizeof(int));
+    HC(hipMemsetAsync(info.p, 0, sizeof(int), st));
+    TRef M = lower_ref(c->mvn_tiles, nlow * GP_TSQ);
+    launch_dense_load(DenseLoadArgs{dcov, (int)c->n, nt, M}, st);
+    potrf_tiles(c, M, nt, nt, nullptr, 0, info.as<int>(), 0, 1, st, 0, 0, /*robust=*/true);
+    launch_quad_rows(QuadRowsArgs{M, (int)c->n, nt, 0, 0, old.as<double>(), oq.as<double>()}, st);
+    HC(hipStreamSynchronize(st));
+    HC(hipGetLastError());
+    HC(hipMemcpy(&c->mvn_logdet, old.p, 8, hipMemcpyDeviceToHost));
+    HC(hipMemcpy(&c->mvn_info, info.p, sizeof(int), hipMemcpyDeviceToHost));
+    c->mvn_tiles_gen = c->mvn_gen;
+}
+
+// hands a covariance over: n <= 640 keeps the dense matrix (and validates it on the single-workgroup kernel when the call takes
+// that path), the tiled path factorises it; mvn_info = its LAPACK-style info
 static void mvn_cache(gpslc_ctx* c, const double* cov, bool small) {
     const size_t n = (size_t)c->n;
     c->mvn_valid = false;
+    ++c->mvn_gen;
+    if (!mvn_dual(c)) {      // n > 640 (or the fp32 kernel mode): the tiled path is the only one
+        DevBuf bcov;
+        mvn_factor_tiles(c, up(bcov, cov, n * n));
+        c->mvn_valid = true;
+        return;
+    }
+    if (!c->mvn_dense) HC(hipMalloc((void**)&c->mvn_dense, n * n * sizeof(double)));
+    HC(hipMemcpy(c->mvn_dense, cov, n * n * sizeof(double), hipMemcpyHostToDevice));
     if (small) {
-        if (!c->mvn_dense) HC(hipMalloc((void**)&c->mvn_dense, n * n * sizeof(double)));
-        HC(hipMemcpy(c->mvn_dense, cov, n * n * sizeof(double), hipMemcpyHostToDevice));
-        // validate once (as the general path does when it caches the factor): info of cov itself
+        // validate once (as the tiled path does when it factorises): info of cov itself
         std::vector<double> zeros(n, 0.0);
         HostNode probe{};
         probe.dev_cov = c->mvn_dense; probe.covscale = 1.0; probe.target = zeros.data();
         double dummy = 0.0;
         c->mvn_info = small_nodes_logpdf(c, 1, &probe, &dummy);
-        c->mvn_valid = true;
-        return;
+    } else {
+        mvn_factor_tiles(c, c->mvn_dense);
     }
-    ensure_streams(c);
-    const int nt = c->nt;
-    const long long nlow = (long long)nt * (nt + 1) / 2;
-    hipStream_t st = c->streams[0];
-    if (!c->mvn_tiles) HC(hipMalloc((void**)&c->mvn_tiles, (size_t)nlow * GP_TSQ * 8));
-    DevBuf bcov, old, oq, info;
-    const double* dcov = up(bcov, cov, n * n);
-    old.alloc(8); oq.alloc(8); info.alloc(sizeof(int));
-    HC(hipMemsetAsync(info.p, 0, sizeof(int), st));
-    TRef M = lower_ref(c->mvn_tiles, nlow * GP_TSQ);
-    launch_dense_load(DenseLoadArgs{dcov, (int)n, nt, M}, st);
-    potrf_tiles(c, M, nt, nt, nullptr, 0, info.as<int>(), 0, 1, st, 0, 0, /*robust=*/true);
-    launch_quad_rows(QuadRowsArgs{M, (int)n, nt, 0, 0, old.as<double>(), oq.as<double>()}, st);
-    HC(hipStreamSynchronize(st));
-    HC(hipGetLastError());
-    HC(hipMemcpy(&c->mvn_logdet, old.p, 8, hipMemcpyDeviceToHost));
-    HC(hipMemcpy(&c->mvn_info, info.p, sizeof(int), hipMemcpyDeviceToHost));
     c->mvn_valid = true;
+}
+
+// before a cov = NULL call on the tiled path: the factor of the latest hand-over (rebuilt from the dense copy when an earlier
+// hand-over went to the single-workgroup path)
+static void mvn_tiles_current(gpslc_ctx* c) {
+    if (c->mvn_tiles && c->mvn_tiles_gen == c->mvn_gen) return;
+    mvn_factor_tiles(c, c->mvn_dense);
 }
 
 int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* covscale, const double* x,
@@ -2156,7 +2183,6 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
         return guarded(c, [&]() {
             const size_t n = (size_t)c->n;
             if (cov) mvn_cache(c, cov, true);
-            else if (!c->mvn_dense) return bad_arg(c, 3, "cov is NULL and the cached factor belongs to the tiled path (S > 512 earlier)");
             c->last_info.assign((size_t)S, c->mvn_info);
             if (S == 0 || c->mvn_info != 0) {
                 for (int64_t s = 0; s < S; ++s) logpdf[s] = NAN;
@@ -2180,7 +2206,7 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
         const long long nlow = (long long)nt * (nt + 1) / 2;
         hipStream_t st = c->streams[0];
         if (cov) mvn_cache(c, cov, false);   // factor once, keep L in the context
-        else if (!c->mvn_tiles) return bad_arg(c, 3, "cov is NULL and no tiled factor is cached");
+        else mvn_tiles_current(c);
         c->last_info.assign((size_t)S, c->mvn_info);
         if (S == 0 || c->mvn_info != 0) {
             for (int64_t s = 0; s < S; ++s) logpdf[s] = NAN;
@@ -2237,7 +2263,7 @@ int gpslc_mvn_draw(gpslc_ctx* c, int64_t S, const double* cov, const double* cov
     return guarded(c, [&]() {
         const size_t n = (size_t)c->n;
         if (cov) mvn_cache(c, cov, small);
-        else if (small ? !c->mvn_dense : !c->mvn_tiles) return bad_arg(c, 3, "cov is NULL and the cached covariance belongs to the other path");
+        else if (!small) mvn_tiles_current(c);
         c->last_info.assign((size_t)S, c->mvn_info);
         if (S == 0) return GPSLC_OK;
         if (c->mvn_info != 0) {

@@ -175,8 +175,10 @@ int gpslc_nodes_draw(gpslc_ctx* ctx, int32_t count, const gpslc_node* nodes, dou
 /* log N(x_s; 0, covscale_s * cov) for S vectors and one dense n x n covariance: the :U => u => :U nodes
  * (generateUfromSigmaU, src/model_likelihood.jl:4-10 with uCov = SigmaU * uNoise; generateU,
  * src/model_prior.jl:27-30).  A non-NULL cov is handed over and cached in the ctx (SigmaU is constant for a data
- * set) — as the matrix itself for n <= 640 (every evaluation scales and factorises it inside one workgroup), as its
- * tiled factor beyond; cov = NULL re-uses it.  S = 0 with a non-NULL cov just hands over and validates (returns the
+ * set).  n <= 640: the matrix itself is kept whichever path the call takes (calls the single-workgroup kernels cover scale
+ * and factorise it inside one workgroup each; larger calls use its tiled factor, built from the kept matrix when missing or
+ * older); n > 640: its tiled factor only.  cov = NULL means the last covariance handed over (here or to gpslc_mvn_draw), for
+ * any S; before any hand-over it is an argument error.  S = 0 with a non-NULL cov just hands over and validates (returns the
  * failing pivot if cov is not positive definite).  covscale may be NULL (= 1).  SigmaU is positive definite only by
  * its 1e-13 jitter (src/utils.jl:17-33): every factorisation and solve here is substitution-based (no products with
  * inverted blocks), i.e. backward stable like LAPACK's potrf / trsm. */
@@ -186,7 +188,7 @@ int gpslc_mvn_logpdf(gpslc_ctx* ctx, int64_t S, const double* cov, const double*
 /* draws[:, s] = chol(covscale_s * cov) z[:, s] for the host's standard normals z: Gen's `mvnormal(zeros(n), uCov)` inside
  * `elliptical_slice(trace, :U => k => :U, zeros(n), uCov)` (uCov = SigmaU * uNoise, src/inference.jl:48-54, 92-98, 233-239,
  * 293-299) and the prior draw of generateUfromSigmaU (src/model_likelihood.jl:4-10).  cov as for gpslc_mvn_logpdf: non-NULL =
- * handed over and cached, NULL = the cached one (the one gpslc_mvn_logpdf holds for the data set's SigmaU); chol(s C) =
+ * handed over and cached, NULL = the last covariance handed over to either entry point, for any S; chol(s C) =
  * sqrt(s) chol(C), so one factor serves every uNoise.  n <= 640: the node kernels' draw mode; beyond: the cached tiled
  * factor streamed once per vector by the predictive-draw kernel.  Returns 0, the failing pivot of cov, or a negative status. */
 int gpslc_mvn_draw(gpslc_ctx* ctx, int64_t S, const double* cov, const double* covscale /* S */,

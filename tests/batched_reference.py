@@ -9,7 +9,11 @@ the same order for a batch of samples with torch's batched CPU linear algebra:
     w = L^-1 c,  MeanSATE = w.z / n,  VarSATE = (sum K - 2 r.colsum(B) + sum B - w.w + n eps) / n^2,
     logdet = 2 sum log diag L,  quad = z.z,  MeanITE = (L^-1 D')' z with D = B o (r_j - e_ij).
 
-tests/test_batched_reference.py pins it to the oracle.  Threads are capped at 16 for the duration of a call (never sized
+node_scores and mvn_scores do the same for the Gaussian node scores and prior draws (gpslc_nodes_logpdf / nodes_draw,
+gpslc_mvn_logpdf / mvn_draw): K = processCov(rbfKernelLog(F, F, ls), scale, noise) per node, or one covariance scaled per
+vector; log N(target; 0, K) and chol(K) target.
+
+tests/test_batched_reference.py pins all of them to the oracle.  Threads are capped at 16 for the duration of a call (never sized
 from the machine's CPU count: a shared host grants a process far fewer CPUs than it shows).
 """
 import contextlib
@@ -119,4 +123,70 @@ def structured_batch(X, T, Y, post, samples, doTs, ite_samples=(), pred_noise=or
                 out["meanITE"][s] = mi
             del Bm, E, K, Lf
     out["logpdf"] = -0.5 * (n * np.log(2 * np.pi) + out["logdet"] + out["quad"])
+    return out
+
+
+_L2PI = float(np.log(2 * np.pi))
+
+
+def node_scores(nodes):
+    """For each node (F (n, nF) | None, ls (nF,), scale, noise, target (n,)): K = processCov(rbfKernelLog(F, F, ls), scale,
+    noise) (F = None or nF = 0: scale 11' + noise I).  Returns dict(logpdf (m,), draw (n, m) = chol(K) target, info (m,)):
+    info is LAPACK's (1-based first failing pivot, 0 = fine); a failing node's logpdf and draw are NaN."""
+    m = len(nodes)
+    n = int(np.asarray(nodes[0][4]).shape[0])
+    out = dict(logpdf=np.full(m, np.nan), draw=np.full((n, m), np.nan), info=np.zeros(m, dtype=np.int64))
+    chunk = max(1, min(m, CHUNK_BYTES // (8 * n * n)))
+    with _threads(), torch.no_grad():
+        for c0 in range(0, m, chunk):
+            part = nodes[c0:c0 + chunk]
+            b = len(part)
+            lk = torch.zeros((b, n, n), dtype=torch.float64)
+            for j, (F, ls, _, _, _) in enumerate(part):
+                if F is None or np.asarray(F).size == 0:
+                    continue
+                Ft = _t(orc._as_2d(F))
+                lst = _t(np.atleast_1d(ls))
+                for k in range(Ft.shape[1]):     # sequential sum over the features, as rbf_kernel_log
+                    d = Ft[:, k][:, None] - Ft[:, k][None, :]
+                    lk[j] -= d * d / lst[k] ** 2
+            sc = _t([float(q[2]) for q in part])
+            nz = _t([float(q[3]) for q in part])
+            K = sc[:, None, None] * torch.exp(lk)
+            del lk
+            K.diagonal(dim1=1, dim2=2).add_(nz[:, None])
+            Lf, info = torch.linalg.cholesky_ex(K)
+            del K
+            tg = _t(np.stack([np.asarray(q[4], dtype=np.float64) for q in part], axis=1).T)     # (b, n)
+            z = torch.linalg.solve_triangular(Lf, tg[:, :, None], upper=False)[:, :, 0]
+            lp = -0.5 * (n * _L2PI + 2.0 * torch.log(torch.diagonal(Lf, dim1=1, dim2=2)).sum(dim=1) + (z * z).sum(dim=1))
+            dr = torch.bmm(Lf, tg[:, :, None])[:, :, 0]
+            bad = info.numpy() != 0
+            sl = slice(c0, c0 + b)
+            out["info"][sl] = info.numpy()
+            out["logpdf"][sl] = np.where(bad, np.nan, lp.numpy())
+            out["draw"][:, sl] = np.where(bad[None, :], np.nan, dr.numpy().T)
+    return out
+
+
+def mvn_scores(cov, X, covscale=None):
+    """log N(x_s; 0, c_s cov) and sqrt(c_s) chol(cov) x_s for the columns x_s of X (n, S), c = covscale (S,) or 1.
+    Returns dict(logpdf (S,), draw (n, S)); raises numpy's LinAlgError when cov is not positive definite."""
+    X = np.asarray(X, dtype=np.float64).reshape(np.shape(X)[0], -1)
+    n, S = X.shape
+    cs = np.ones(S) if covscale is None else np.array(np.broadcast_to(np.asarray(covscale, dtype=np.float64), (S,)))
+    out = dict(logpdf=np.zeros(S), draw=np.zeros((n, S)))
+    chunk = max(1, min(S, CHUNK_BYTES // (8 * n)))
+    with _threads(), torch.no_grad():
+        Lf, info = torch.linalg.cholesky_ex(_t(cov))
+        if int(info) != 0:
+            raise np.linalg.LinAlgError(f"not positive definite (info = {int(info)})")
+        logdet = 2.0 * float(torch.log(torch.diagonal(Lf)).sum())
+        for c0 in range(0, S, chunk):
+            sl = slice(c0, min(S, c0 + chunk))
+            x = _t(X[:, sl])
+            c = _t(cs[sl])
+            z = torch.linalg.solve_triangular(Lf, x, upper=False)
+            out["logpdf"][sl] = (-0.5 * (n * _L2PI + n * torch.log(c) + logdet + (z * z).sum(dim=0) / c)).numpy()
+            out["draw"][:, sl] = (torch.sqrt(c)[None, :] * (Lf @ x)).numpy()
     return out

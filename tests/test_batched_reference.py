@@ -1,6 +1,7 @@
 """tests/batched_reference.py (the host reference the bench-scale GPU suite checks thousands of posterior samples against)
 pinned to the oracle it restates: oracle.structured_sate / structured_ite per sample at 1e-12, and one sample against the
-LITERAL restatement (ite_distributions + conditional_sate)."""
+LITERAL restatement (ite_distributions + conditional_sate); node_scores / mvn_scores against orc.mvnormal_logpdf of
+orc.process_cov and numpy's Cholesky."""
 import numpy as np
 import pytest
 
@@ -72,3 +73,53 @@ def test_batched_reference_against_the_literal_restatement():
         assert np.max(np.abs(out["meanITE"][s][:, l] - M[0])) <= 1e-9 * np.max(np.abs(M[0]))
     lp = orc.y_logpdf(p.uyLS, p.xyLS, p.tyLS, p.yScale, p.yNoise, p.U, c["X"], c["T"], c["Y"])
     assert abs(out["logpdf"][0] - lp) <= 1e-10 * abs(lp)
+
+
+def _nodes(n, nFs, seed):
+    rng = np.random.default_rng(seed)
+    nodes = []
+    for nF in nFs:
+        F = None if nF == 0 else rng.standard_normal((n, nF))
+        ls = None if nF == 0 else rng.uniform(0.6, 2.0, nF)
+        nodes.append((F, ls, rng.uniform(0.5, 2.0), rng.uniform(0.2, 1.5), rng.standard_normal(n)))
+    return nodes
+
+
+@pytest.mark.parametrize("n", [1, 17, 150, 300])
+def test_node_scores_equal_the_oracle(n, monkeypatch):
+    """Heterogeneous feature counts (0 .. 32) in one call, over several chunks, against orc.mvnormal_logpdf(process_cov(...))
+    and numpy's Cholesky; a node that is not positive definite gets LAPACK's info and NaN, the others are unaffected."""
+    monkeypatch.setattr(br, "CHUNK_BYTES", 3 * 8 * n * n)
+    nodes = _nodes(n, (0, 1, 3, 8, 16, 32, 2), seed=n)
+    F, ls, sc, _, tg = nodes[3]
+    nodes.append((F, ls, sc, -sc - 1.0, tg))                  # diagonal sc + noise = -1: fails at the first pivot
+    out = br.node_scores(nodes)
+    for i, (F, ls, sc, nz, tg) in enumerate(nodes[:-1]):
+        K = sc * np.ones((n, n)) + nz * np.eye(n) if F is None else orc.process_cov(orc.rbf_kernel_log(F, F, ls), sc, nz)
+        np.testing.assert_allclose(out["logpdf"][i], orc.mvnormal_logpdf(tg, K), rtol=RTOL, atol=0)
+        ref = np.linalg.cholesky(K) @ tg
+        assert np.max(np.abs(out["draw"][:, i] - ref)) <= RTOL * np.max(np.abs(ref)), i
+        assert out["info"][i] == 0
+    assert out["info"][-1] == 1 and np.isnan(out["logpdf"][-1]) and np.isnan(out["draw"][:, -1]).all()
+
+
+@pytest.mark.parametrize("n,S", [(1, 3), (150, 7), (300, 40)])
+def test_mvn_scores_equal_the_oracle(n, S, monkeypatch):
+    monkeypatch.setattr(br, "CHUNK_BYTES", 8 * 8 * n)        # several column chunks
+    rng = np.random.default_rng(100 + n)
+    G = rng.standard_normal((n, n))
+    cov = G @ G.T / n + np.eye(n)
+    X = rng.standard_normal((n, S))
+    cs = rng.uniform(0.3, 3.0, S)
+    out = br.mvn_scores(cov, X, cs)
+    L = np.linalg.cholesky(cov)
+    for s in range(S):
+        np.testing.assert_allclose(out["logpdf"][s], orc.mvnormal_logpdf(X[:, s], cs[s] * cov), rtol=RTOL, atol=0)
+        ref = np.sqrt(cs[s]) * (L @ X[:, s])
+        assert np.max(np.abs(out["draw"][:, s] - ref)) <= RTOL * np.max(np.abs(ref)), s
+    one = br.mvn_scores(cov, X)
+    np.testing.assert_allclose(one["logpdf"], [orc.mvnormal_logpdf(X[:, s], cov) for s in range(S)], rtol=RTOL, atol=0)
+    bad = cov.copy()
+    bad[n // 2, n // 2] = -1.0
+    with pytest.raises(np.linalg.LinAlgError):
+        br.mvn_scores(bad, X)

@@ -95,8 +95,9 @@ def test_task_order_group_size_and_chunking_do_not_change_results(gp, group):
 
 
 def test_task_launch_draws_and_logpdf_paths(gp):
-    """Unit B (full ITE covariance + draws) keeps its own schedule after the task launch has factorised A; the :Y score
-    (logdet and quadratic form from the same factorisation) goes through it too."""
+    """Unit B (full ITE covariance + draws) keeps its own schedule after the task launch has factorised A.  The :Y score of
+    these 6 samples runs on the single-workgroup kernel under either schedule, so it only checks that the schedule switch
+    leaves it alone; tests/test_gpu_path_limits.py scores :Y through the task launch."""
     c = cases.make_case(400, "UX", False, S=6, seed=9)
     outs = []
     for tiles in (8, 0):
