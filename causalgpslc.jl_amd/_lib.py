@@ -33,7 +33,9 @@ class GPSLCError(RuntimeError):
 class PosDefException(ArithmeticError):
     """Mirrors Julia's LinearAlgebra.PosDefException(info) raised by PDMats inside Gen.mvnormal:
     ``info`` is the 1-based pivot at which the Cholesky factorisation broke down (values > n refer
-    to the CovITE factorisation, pivot = info - n)."""
+    to the CovITE factorisation, pivot = info - n: that of the lowest-index failing level of the
+    sample, as the reference's level loop meets it).  From gpslc_predict it is the first nonzero
+    code in sample order; ``Context.last_info`` has every sample's."""
 
     def __init__(self, info):
         super().__init__(f"matrix is not positive definite; Cholesky factorization failed (info = {info})")

@@ -793,7 +793,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     // per unit: 1 / 2 / 4 / 8 blocks of 16 draws (draws_nq, k_solve.hip: the stream kernel's template parameter)
     const size_t zimage_doubles = zimage ? (size_t)16 * (io.spp <= 16 ? 1 : io.spp <= 32 ? 2 : io.spp <= 64 ? 4 : 8) * Np : 0;
     const size_t draws_per = want_draws ? ((zimage ? zimage_doubles * 8 + 256 : (io.z ? 0 : (size_t)io.spp * n * 8 + 256)) +
-                                           (L > 1 ? (size_t)io.spp * n * 8 + 256 : 0)) : 0;
+                                           (L > 1 ? (size_t)io.spp * n * 8 + 256 : 0) + sizeof(int) + 256) : 0;
     const size_t unitB_all = unitB_per + draws_per;
     // chunk size and sub-batch from what the device has (the sub-batch's workspace is sized from the pairs the call
     // really has, and the 30 % rule of the automatic chunk covers its per-sample part only)
@@ -955,6 +955,8 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
             double* zgen = (want_draws && !io.z && !zimage) ? ar.take<double>((size_t)Bb * io.spp * n) : nullptr;
             double* zt = zimage ? ar.take<double>((size_t)Bb * zimage_doubles) : nullptr;
             double* dtmp = (want_draws && L > 1) ? ar.take<double>((size_t)gs_max * L * io.spp * n) : nullptr;
+            // failure codes of the CovITE factors, one per pair of a sub-batch (folded into io.info after each sub-batch)
+            int* pinfo = want_draws ? ar.take<int>((size_t)Bb) : nullptr;
             const long long wbs = (long long)nt * nt * GP_TSQ, cbs = nlow * GP_TSQ;
             for (int g0 = 0; g0 < nb; g0 += gs_max) {
                 const int gs = std::min(gs_max, nb - g0);
@@ -1026,7 +1028,12 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
                         launch_gather_cov(gc, ub, st);
                     }
                     if (want_draws) {
-                        potrf_tiles(c, Cm, nt, nt, nullptr, 0, io.info + s0 + g0, n, ub, st, 0, 3, /*robust=*/true, /*info_div=*/lc);
+                        // one failure code per pair, then per sample the code of its lowest-index failing level (the
+                        // reference's loop order, src/prediction.jl:30-33): a shared word per sample would let the lc levels
+                        // of a diagonal launch race, and the lowest failing tile column win across launches
+                        HC(hipMemsetAsync(pinfo, 0, sizeof(int) * ub, st));
+                        potrf_tiles(c, Cm, nt, nt, nullptr, 0, pinfo, n, ub, st, 0, 3, /*robust=*/true, /*info_div=*/1);
+                        launch_fold_pair_info(pinfo, io.info + s0 + g0, gs, lc, st);
                         DrawArgs dr{};
                         dr.Lc = Cm; dr.n = n; dr.nt = nt; dr.s0 = s0 + g0; dr.S = io.S; dr.l = l0; dr.lc = lc; dr.L = L;
                         dr.spp = io.spp; dr.mean = meanITE; dr.z = io.z; dr.zgen = zgen; dr.zt = zt; dr.seed = io.seed;

@@ -167,6 +167,8 @@ void launch_gram(const GramArgs& g, int nbatch, hipStream_t st);
 // substitution-based (backward-stable) diagonal-tile factorisation and panel solve for near-singular matrices (k_robust.hip)
 void launch_diag_robust(const TRef& M, int k, int* info, int info_base, int nbatch, hipStream_t st, int info_div = 1);
 void launch_trsm_robust(const TRef& X, const TRef& L, int k, int i0, int count, int nbatch, hipStream_t st);
+// info[g] (if still 0) <- the first nonzero of pair_info[g*lc .. g*lc + lc - 1], g < gs (k_robust.hip)
+void launch_fold_pair_info(const int* pair_info, int* info, int gs, int lc, hipStream_t st);
 
 struct RhsArgs {
     const double* T; const double* Y; const double* tyLS; const double* doT;

@@ -197,3 +197,23 @@ void launch_trsm_robust(const TRef& X, const TRef& L, int k, int i0, int count, 
     lds_opt_in(once, (const void*)tile_trsm_robust_kernel, bytes);
     hipLaunchKernelGGL(tile_trsm_robust_kernel, dim3(count, nbatch), dim3(256), bytes, st, X, L, k, i0);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Failure codes of a unit-B sub-batch (gs samples x lc levels, pair b = sample b / lc, level b % lc): the robust factor
+// writes one code per pair (info_div = 1); sample g keeps the code of its lowest-index failing level, unless it already
+// holds one (its A factorisation or an earlier level chunk, run before on the same stream).  src/prediction.jl:30-33
+// visits the levels in order and stops at the first PosDefException.
+__global__ __launch_bounds__(64) void fold_pair_info_kernel(const int* __restrict__ pair_info, int* __restrict__ info,
+                                                            int gs, int lc) {
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= gs || info[g] != 0) return;
+    for (int l = 0; l < lc; ++l) {
+        const int v = pair_info[(long long)g * lc + l];
+        if (v != 0) { info[g] = v; return; }
+    }
+}
+
+void launch_fold_pair_info(const int* pair_info, int* info, int gs, int lc, hipStream_t st) {
+    if (gs <= 0) return;
+    hipLaunchKernelGGL(fold_pair_info_kernel, dim3((unsigned)((gs + 63) / 64)), dim3(64), 0, st, pair_info, info, gs, lc);
+}

@@ -317,7 +317,10 @@ int gpslc_summarize_dev(gpslc_ctx* ctx, const double* samples, int64_t n, int64_
                         int64_t col_stride, double credible_interval, double* mean, double* lower, double* upper);
 
 /* 1-based failing pivot (0 = ok) of every posterior sample of the last predict / y_logpdf /
- * ite_distributions call; codes > n refer to the CovITE factorisation (pivot - n). */
+ * ite_distributions call.  Codes <= n refer to the factorisation of the sample's A = K + yNoise I; codes > n to a CovITE
+ * factorisation of the draws (pivot = code - n), that of the sample's lowest-index failing level (the order of the
+ * reference's level loop, src/prediction.jl:30-33) — the same code whatever the chunking, streams or repeat.  A failing A
+ * takes precedence over the sample's CovITE codes. */
 int gpslc_last_info(const gpslc_ctx* ctx, int32_t* info, int64_t S);
 
 /* ---- posterior pack (replaces Serialization of a GPSLCObject, src/io.jl:14-34) ----

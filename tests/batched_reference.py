@@ -13,6 +13,12 @@ node_scores and mvn_scores do the same for the Gaussian node scores and prior dr
 gpslc_mvn_logpdf / mvn_draw): K = processCov(rbfKernelLog(F, F, ls), scale, noise) per node, or one covariance scaled per
 vector; log N(target; 0, K) and chol(K) target.
 
+ite_pairs and ite_pair_draws do the same for the full ITE covariance of (posterior sample, level) pairs (gpslc_predict's unit B
+and C: ITEDistributions, sampleITE, predictCounterfactualEffects): with Q_ij = exp(-(T_i - d_j)^2 / tyLS^2) and
+H_ij = exp(-(d_i - d_j)^2 / tyLS^2) for the level's intervention d (a scalar level: Q_ij = r_i, H = 1),
+D = B o (Q' - E),  Delta = B o (E - Q - Q' + H),  V = L^-1 D',  MeanITE = V' z,  CovITE = Symmetric(Delta - V'V) + eps I,
+and the draws M + chol(CovITE) z.
+
 tests/test_batched_reference.py pins all of them to the oracle.  Threads are capped at 16 for the duration of a call (never sized
 from the machine's CPU count: a shared host grants a process far fewer CPUs than it shows).
 """
@@ -21,6 +27,7 @@ import contextlib
 import numpy as np
 import torch
 
+import cases
 import gpslc_oracle as orc
 
 MAX_THREADS = 16
@@ -190,3 +197,139 @@ def mvn_scores(cov, X, covscale=None):
             out["logpdf"][sl] = (-0.5 * (n * _L2PI + n * torch.log(c) + logdet + (z * z).sum(dim=0) / c)).numpy()
             out["draw"][:, sl] = (torch.sqrt(c)[None, :] * (Lf @ x)).numpy()
     return out
+
+
+def _level(doTs, l, n):
+    """level l of doTs as an (n,) intervention vector: doTs is (L,) scalar levels or (L, n) vectors"""
+    d = np.asarray(doTs, dtype=np.float64)
+    return np.full(n, float(d[l])) if d.ndim == 1 else np.ascontiguousarray(d[l])
+
+
+def _ite_chunks(X, T, Y, post, pairs, doTs, pred_noise):
+    """Yields (j0, MeanITE (b, n), CovITE + pred_noise I (b, n, n)) for consecutive chunks of `pairs` ((s, l) tuples); the factor
+    of A is formed once per sample of a chunk."""
+    pairs = [(int(s), int(l)) for s, l in pairs]
+    d_all = np.asarray(doTs, dtype=np.float64)
+    vec = d_all.ndim == 2
+    Yn = np.asarray(Y, dtype=np.float64)
+    n = Yn.shape[0]
+    U = post.get("U")
+    Tt = _t(orc._as_2d(T)[:, 0])
+    Yt = _t(Yn)
+    Xt = _t(orc._as_2d(X)) if X is not None else None
+    dT2 = (Tt[:, None] - Tt[None, :]) ** 2
+    chunk = max(1, min(len(pairs), CHUNK_BYTES // (8 * n * n)))
+    eye = torch.eye(n, dtype=torch.float64)
+    for j0 in range(0, len(pairs), chunk):
+        part = pairs[j0:j0 + chunk]
+        smp = sorted(set(s for s, _ in part))
+        fac = {}
+        for s in smp:
+            lux = torch.zeros((n, n), dtype=torch.float64)
+            if U is not None:
+                Us = _t(np.asarray(U)[:, :, s])
+                uls = _t(_col(post["uyLS"], s))
+                for k in range(Us.shape[1]):
+                    d = Us[:, k][:, None] - Us[:, k][None, :]
+                    lux += d * d / uls[k] ** 2
+            if Xt is not None:
+                xls = _t(_col(post["xyLS"], s))
+                for k in range(Xt.shape[1]):
+                    d = Xt[:, k][:, None] - Xt[:, k][None, :]
+                    lux += d * d / xls[k] ** 2
+            tls = float(post["tyLS"][s])
+            Bm = float(post["yScale"][s]) * torch.exp(-lux)
+            E = torch.exp(-dT2 / tls ** 2)
+            Lf = torch.linalg.cholesky(Bm * E + float(post["yNoise"][s]) * eye)
+            z = torch.linalg.solve_triangular(Lf, Yt[:, None], upper=False)[:, 0]
+            fac[s] = (Bm, E, Lf, z, tls)
+        b = len(part)
+        M = torch.zeros((b, n), dtype=torch.float64)
+        Cv = torch.zeros((b, n, n), dtype=torch.float64)
+        for j, (s, l) in enumerate(part):
+            Bm, E, Lf, z, tls = fac[s]
+            if vec:
+                dv = _t(d_all[l])
+                Q = torch.exp(-((Tt[:, None] - dv[None, :]) ** 2) / tls ** 2)
+                H = torch.exp(-((dv[:, None] - dv[None, :]) ** 2) / tls ** 2)
+                D = Bm * (Q.T - E)
+                Delta = Bm * (E - Q - Q.T + H)
+            else:
+                r = torch.exp(-((Tt - float(d_all[l])) ** 2) / tls ** 2)
+                D = Bm * (r[None, :] - E)
+                Delta = Bm * (E - r[:, None] - r[None, :] + 1.0)
+            V = torch.linalg.solve_triangular(Lf, D.T.contiguous(), upper=False)
+            M[j] = V.T @ z
+            C = Delta - V.T @ V
+            Cv[j] = torch.triu(C) + torch.triu(C, 1).T          # Symmetric(C): the upper triangle wins (src/estimation.jl:82)
+            Cv[j].diagonal().add_(pred_noise)
+        yield j0, M, Cv
+
+
+def ite_pairs(X, T, Y, post, pairs, doTs, pred_noise=orc.PREDICTION_COVARIANCE_NOISE):
+    """MeanITE (m, n) and CovITE + pred_noise I (m, n, n) of the (sample, level) pairs `pairs`, in their order.  doTs: (L,) scalar
+    levels or (L, n) intervention vectors; post as for structured_batch."""
+    n = np.asarray(Y).shape[0]
+    m = len(pairs)
+    out = dict(mean=np.zeros((m, n)), cov=np.zeros((m, n, n)))
+    with _threads(), torch.no_grad():
+        for j0, M, Cv in _ite_chunks(X, T, Y, post, pairs, doTs, pred_noise):
+            out["mean"][j0:j0 + M.shape[0]] = M.numpy()
+            out["cov"][j0:j0 + M.shape[0]] = Cv.numpy()
+    return out
+
+
+def ite_pair_draws(X, T, Y, post, pairs, doTs, z, pred_noise=orc.PREDICTION_COVARIANCE_NOISE):
+    """M + chol(C) z_j for the pairs (C = CovITE + pred_noise I; z: (m, n, spp), one block of normals per pair).  Keeps no
+    covariance beyond its chunk.  Returns dict(draws (m, n, spp), lam_min (m,), lam_max (m,)): the extreme eigenvalues of C, for
+    cases.draw_bounds."""
+    z = np.asarray(z, dtype=np.float64)
+    m, n, spp = z.shape
+    assert m == len(pairs)
+    out = dict(draws=np.zeros((m, n, spp)), lam_min=np.zeros(m), lam_max=np.zeros(m))
+    with _threads(), torch.no_grad():
+        for j0, M, Cv in _ite_chunks(X, T, Y, post, pairs, doTs, pred_noise):
+            b = M.shape[0]
+            Lc = torch.linalg.cholesky(Cv)
+            out["draws"][j0:j0 + b] = (M[:, :, None] + Lc @ _t(z[j0:j0 + b])).numpy()
+            ev = torch.linalg.eigvalsh(Cv)
+            out["lam_min"][j0:j0 + b] = ev[:, 0].numpy()
+            out["lam_max"][j0:j0 + b] = ev[:, -1].numpy()
+    return out
+
+
+def first_failing_pivot(C):
+    """LAPACK dpotrf's info of C (..., n, n): the 1-based first pivot at which the Cholesky factorisation breaks down, 0 when C
+    is positive definite."""
+    with _threads(), torch.no_grad():
+        info = torch.linalg.cholesky_ex(_t(C)).info
+    return info.numpy() if info.ndim else int(info)
+
+
+def schur_pivots(C, p):
+    """The Schur pivots of C up to the 1-based pivot p: (pivots 1 .. p-1 of the factorisation, pivot p), which must have
+    succeeded before it (the leading (p-1) x (p-1) block positive definite)."""
+    with _threads(), torch.no_grad():
+        Ct = _t(C)
+        if p == 1:
+            return np.zeros(0), float(Ct[0, 0])
+        Lf = torch.linalg.cholesky(Ct[:p - 1, :p - 1])
+        w = torch.linalg.solve_triangular(Lf, Ct[:p - 1, p - 1:p], upper=False)[:, 0]
+        return (torch.diagonal(Lf) ** 2).numpy(), float(Ct[p - 1, p - 1] - w @ w)
+
+
+def draws_match(got, ref, lam_min, lam_max, z, tight=True):
+    """Every draw column of one pair (got, ref, z: (n, spp)) within cases.draw_bounds: the tight bound (tight=True; a
+    conditioning too poor for it fails) or the conditioning-aware one.  Returns (ok, worst error / bound)."""
+    got, ref, z = (np.asarray(a, dtype=np.float64).reshape(np.shape(a)[0], -1) for a in (got, ref, z))
+    worst = 0.0
+    for d in range(ref.shape[1]):
+        bound, tb, _ = cases.draw_bounds(lam_min, lam_max, np.linalg.norm(z[:, d]), np.linalg.norm(ref[:, d]))
+        lim = tb if tight else bound
+        if lim is None:
+            return False, np.inf
+        err = np.linalg.norm(got[:, d] - ref[:, d])
+        if not np.isfinite(err):
+            return False, np.inf
+        worst = max(worst, err / lim)
+    return worst <= 1.0, worst

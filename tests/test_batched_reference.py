@@ -123,3 +123,166 @@ def test_mvn_scores_equal_the_oracle(n, S, monkeypatch):
     bad[n // 2, n // 2] = -1.0
     with pytest.raises(np.linalg.LinAlgError):
         br.mvn_scores(bad, X)
+
+
+# ---- unit B / C: ITE covariances and draws of (sample, level) pairs ---------------------------------------------------------
+
+def _pairs_case(n, L, S=3, seed=0):
+    c = cases.make_case(n, "UX", False, S=S, seed=seed)
+    return c, np.linspace(-0.8, 1.1, L)
+
+
+@pytest.mark.parametrize("n", [129, 300])
+def test_ite_pairs_equal_the_structured_and_literal_oracle(n, monkeypatch):
+    """ite_pairs against orc.structured_ite (1e-12, the same formulas) and orc.ite_distributions (the literal restatement:
+    three symmetric-indefinite solves; 1e-9) for pairs out of order and over several chunks; a ragged n."""
+    monkeypatch.setattr(br, "CHUNK_BYTES", 2 * 8 * n * n)
+    c, doTs = _pairs_case(n, 3)
+    pn = 1e-3
+    pairs = [(2, 1), (0, 0), (1, 2), (2, 0), (0, 2)]
+    out = br.ite_pairs(c["X"], c["T"], c["Y"], c, pairs, doTs, pn)
+    smp = cases.samples_of(c)
+    for j, (s, l) in enumerate(pairs):
+        m, C = orc.structured_ite(smp[s], c["X"], c["T"], c["Y"], doTs[l])
+        C = orc._symmetric_upper(C) + pn * np.eye(n)
+        assert np.max(np.abs(out["mean"][j] - m)) <= RTOL * np.max(np.abs(m)), (s, l)
+        assert np.max(np.abs(out["cov"][j] - C)) <= RTOL * np.max(np.abs(C)), (s, l)
+        assert np.array_equal(out["cov"][j], out["cov"][j].T)
+        M, Cv = orc.ite_distributions([smp[s]], c["X"], c["T"], c["Y"], doTs[l], pn)
+        assert np.max(np.abs(out["mean"][j] - M[0])) <= 1e-9 * np.max(np.abs(M[0])), (s, l)
+        assert np.max(np.abs(out["cov"][j] - Cv[0])) <= 1e-9 * np.max(np.abs(Cv[0])), (s, l)
+
+
+def test_ite_pairs_vector_levels_equal_the_vector_restatement():
+    """(L, n) intervention vectors: against vector_restatement.ite_distributions_vec (the literal formula with d in place of
+    fill(doT, n)); and a constant vector gives the scalar level's result."""
+    import vector_restatement as vr
+    n = 150
+    c, _ = _pairs_case(n, 2, seed=3)
+    D = vr.policy(c, 2, seed=5)
+    pn = 1e-3
+    pairs = [(0, 1), (2, 0)]
+    out = br.ite_pairs(c["X"], c["T"], c["Y"], c, pairs, D, pn)
+    smp = cases.samples_of(c)
+    for j, (s, l) in enumerate(pairs):
+        M, Cv = vr.ite_distributions_vec([smp[s]], c["X"], c["T"], c["Y"], D[l], pn)
+        assert np.max(np.abs(out["mean"][j] - M[0])) <= 1e-9 * np.max(np.abs(M[0])), (s, l)
+        assert np.max(np.abs(out["cov"][j] - Cv[0])) <= 1e-9 * np.max(np.abs(Cv[0])), (s, l)
+    flat = br.ite_pairs(c["X"], c["T"], c["Y"], c, [(1, 0)], np.full((1, n), 0.3), pn)
+    scal = br.ite_pairs(c["X"], c["T"], c["Y"], c, [(1, 0)], np.array([0.3]), pn)
+    assert np.max(np.abs(flat["cov"] - scal["cov"])) <= RTOL * np.max(np.abs(scal["cov"]))
+    assert np.max(np.abs(flat["mean"] - scal["mean"])) <= RTOL * np.max(np.abs(scal["mean"]))
+
+
+def test_ite_pair_draws_equal_the_oracle_samples(monkeypatch):
+    """ite_pair_draws against orc.ite_samples on the same CovITE (1e-12) and its eigenvalue bounds against numpy's; at the
+    default jitter against orc.sample_ite (the literal chain) within draw_bounds' conditioning-aware bound."""
+    n, spp = 257, 3
+    monkeypatch.setattr(br, "CHUNK_BYTES", 2 * 8 * n * n)
+    c, doTs = _pairs_case(n, 2, seed=4)
+    pairs = [(s, l) for s in range(3) for l in range(2)]
+    z = np.random.default_rng(1).standard_normal((len(pairs), n, spp))
+    smp = cases.samples_of(c)
+    for pn in (1e-3, orc.PREDICTION_COVARIANCE_NOISE):
+        ref = br.ite_pairs(c["X"], c["T"], c["Y"], c, pairs, doTs, pn)
+        out = br.ite_pair_draws(c["X"], c["T"], c["Y"], c, pairs, doTs, z, pn)
+        for j, (s, l) in enumerate(pairs):
+            want = orc.ite_samples(ref["mean"][j][None], ref["cov"][j][None], spp, z[j])
+            assert np.max(np.abs(out["draws"][j] - want)) <= RTOL * np.max(np.abs(want)), (pn, s, l)
+            ev = np.linalg.eigvalsh(ref["cov"][j])
+            assert abs(out["lam_max"][j] - ev[-1]) <= 1e-12 * ev[-1]
+            assert abs(out["lam_min"][j] - ev[0]) <= 1e-12 * ev[-1]
+        if pn == 1e-3:
+            continue
+        s, l = 1, 0
+        lit = orc.sample_ite([smp[s]], c["X"], c["T"], c["Y"], doTs[l], spp, z[pairs.index((s, l))], pn)
+        j = pairs.index((s, l))
+        ok, worst = br.draws_match(out["draws"][j], lit, out["lam_min"][j], out["lam_max"][j], z[j], tight=False)
+        assert ok, worst
+
+
+def test_first_failing_pivot_is_lapack_info():
+    rng = np.random.default_rng(2)
+    n = 300
+    G = rng.standard_normal((n, n))
+    C = G @ G.T / n + 0.1 * np.eye(n)
+    assert br.first_failing_pivot(C) == 0
+    for p in (1, 128, 129, 300):
+        # the leading p-1 block is untouched; pivot p becomes its Schur complement minus 1
+        piv, d = br.schur_pivots(C, p)
+        assert np.all(piv > 0) and d > 0
+        B = C.copy()
+        B[p - 1, p - 1] -= d + 1.0
+        assert br.first_failing_pivot(B) == p
+        piv2, d2 = br.schur_pivots(B, p)
+        np.testing.assert_allclose(piv2, piv, rtol=1e-12)
+        assert abs(d2 + 1.0) <= 1e-9
+    assert list(br.first_failing_pivot(np.stack([C, B]))) == [0, 300]
+
+
+# The GPU tests hold every draw column of a pair to draw_bounds' tight bound through br.draws_match.  Those tolerances must
+# discriminate: each deliberately wrong reference below (a plausible indexing slip of the draw path, restated on the host)
+# must fail for every pair it touches.
+
+def _sens_case():
+    n, S, L, spp = 383, 3, 3, 4            # nt = 3: a middle tile row (rows 128 .. 255) and a ragged last tile
+    c, doTs = _pairs_case(n, L, S=S, seed=8)
+    pn = 1e-3
+    pairs = [(s, l) for s in range(S) for l in range(L)]
+    seed = 17
+    z = np.stack([orc.philox_normals(seed, s + S * l, n * spp).reshape(n, spp, order="F") for s, l in pairs])
+    ref = br.ite_pair_draws(c["X"], c["T"], c["Y"], c, pairs, doTs, z, pn)
+    return c, doTs, pn, pairs, z, ref, seed
+
+
+@pytest.fixture(scope="module")
+def sens():
+    return _sens_case()
+
+
+def test_draw_tolerance_accepts_the_right_reference(sens):
+    c, doTs, pn, pairs, z, ref, _ = sens
+    for j in range(len(pairs)):
+        ok, worst = br.draws_match(ref["draws"][j], ref["draws"][j], ref["lam_min"][j], ref["lam_max"][j], z[j])
+        assert ok and worst == 0.0
+
+
+def test_draw_tolerance_rejects_a_level_shifted_by_one(sens):
+    c, doTs, pn, pairs, z, ref, _ = sens
+    L = len(doTs)
+    for j, (s, l) in enumerate(pairs):
+        wrong = br.ite_pair_draws(c["X"], c["T"], c["Y"], c, [(s, (l + 1) % L)], doTs, z[j:j + 1], pn)["draws"][0]
+        assert not br.draws_match(wrong, ref["draws"][j], ref["lam_min"][j], ref["lam_max"][j], z[j])[0], (s, l)
+
+
+def test_draw_tolerance_rejects_the_philox_stream_of_the_next_sample(sens):
+    c, doTs, pn, pairs, z, ref, seed = sens
+    n, spp = z.shape[1], z.shape[2]
+    S = c["S"]
+    for j, (s, l) in enumerate(pairs):
+        zw = orc.philox_normals(seed, (s + 1) + S * l, n * spp).reshape(1, n, spp, order="F")
+        wrong = br.ite_pair_draws(c["X"], c["T"], c["Y"], c, [(s, l)], doTs, zw, pn)["draws"][0]
+        assert not br.draws_match(wrong, ref["draws"][j], ref["lam_min"][j], ref["lam_max"][j], z[j])[0], (s, l)
+
+
+def test_draw_tolerance_rejects_a_lost_middle_tile_row(sens):
+    """The middle tile row of nt = 3 (no partner row in the streaming draw kernel) left at the mean: L_c z dropped there."""
+    c, doTs, pn, pairs, z, ref, _ = sens
+    means = br.ite_pairs(c["X"], c["T"], c["Y"], c, pairs, doTs, pn)["mean"]
+    for j in range(len(pairs)):
+        wrong = ref["draws"][j].copy()
+        wrong[128:256] = means[j][128:256, None]
+        assert not br.draws_match(wrong, ref["draws"][j], ref["lam_min"][j], ref["lam_max"][j], z[j])[0], pairs[j]
+
+
+def test_draw_tolerance_rejects_a_later_sub_batch_from_the_previous_sample(sens):
+    """A later sub-batch (sample group g0 > 0) written with the previous sample's draws: its own normals, the wrong
+    sample's MeanITE and factor."""
+    c, doTs, pn, pairs, z, ref, _ = sens
+    for j, (s, l) in enumerate(pairs):
+        if s == 0:
+            continue
+        wrong = br.ite_pair_draws(c["X"], c["T"], c["Y"], c, [(s - 1, l)], doTs, z[j:j + 1], pn)["draws"][0]
+        assert not br.draws_match(wrong, ref["draws"][j], ref["lam_min"][j], ref["lam_max"][j], z[j])[0], (s, l)
+        prev = ref["draws"][pairs.index((s - 1, l))]
+        assert not br.draws_match(prev, ref["draws"][j], ref["lam_min"][j], ref["lam_max"][j], z[j])[0], (s, l)
