@@ -112,6 +112,15 @@ struct TaskList {
     unsigned long long used = 0;
 };
 
+// one HIP stream of a ctx and what its launches use: the chunks of a call alternate over the slots
+struct StreamSlot {
+    hipStream_t st = nullptr;
+    Arena arena;
+    int* queue = nullptr;          // ticket-counter block (16 ints), see GemmArgs::queue
+    int* sync = nullptr;           // progress words of the persistent factorisation launch (PotrfTaskArgs::sync)
+    size_t sync_ints = 0;
+};
+
 }  // namespace
 
 struct gpslc_ctx {
@@ -128,17 +137,13 @@ struct gpslc_ctx {
     bool panel_set = false;        // gpslc_set_tuning gave a panel width: the persistent launch then serves nt <= panel only
     int64_t ens_off = 0, ens_S = 0;   // gpslc_set_ensemble: placement of a call's samples for the Philox stream ids
     int nstreams = 1;   // chunks of one call alternate over this many HIP streams (2 buys ~1-2 %, see profiles/)
-    std::vector<hipStream_t> streams;
-    std::vector<Arena> arenas;     // one per stream slot
-    std::vector<int*> queues;      // one ticket-counter block (16 ints) per stream slot, see GemmArgs::queue
-    // persistent factorisation launch (potrf_tasks_kernel): progress words per stream slot, cached task lists, and whether
-    // a call has used it (its time-out word is then checked when the call's streams have drained)
-    std::vector<int*> task_sync;
-    std::vector<size_t> task_sync_ints;
+    std::vector<StreamSlot> slots;   // one per stream (ensure_streams)
+    // persistent factorisation launch (potrf_tasks_kernel): cached task lists, the time-out word every launch of the ctx sets
+    // when a poll exceeds its bound, and whether a call has used it (the word is then checked when the call's streams have drained)
     std::vector<TaskList> task_lists;
     unsigned long long task_clock = 0;
-    bool task_used = false;        // a persistent launch ran since the time-out words were last read (check_task_timeout)
-    bool task_timed_out = false;   // a time-out word read when its slot's buffer was replaced by a larger one, not yet reported
+    int* task_timeout = nullptr;
+    bool task_used = false;        // a persistent launch ran since the time-out word was last read (check_task_timeout)
     int task_min_nt = 2, task_max_nt = TASK_MAX_NT;   // tile counts in this range take the persistent launch (128 < N <= 4096: with
                                             // groups of 32 it wins at every tile count the descriptor can hold — N = 256 +1..3 %, 384 +6 %, 512 +10 %,
                                             // 1024 +6 %, 1536 +4 %, 2048 +2.4 %, 3072 +1.8 %, 4096 +1.0..1.3 % against panels of 8 + trailing
@@ -236,19 +241,21 @@ void arena_reserve(gpslc_ctx* c, Arena& a, size_t bytes) {
 }
 
 void ensure_streams(gpslc_ctx* c) {
-    while ((int)c->streams.size() < c->nstreams) {
-        hipStream_t s;
-        HC(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        c->streams.push_back(s);
+    if (!c->task_timeout) {
+        HC(hipMalloc((void**)&c->task_timeout, sizeof(int)));
+        HC(hipMemset(c->task_timeout, 0, sizeof(int)));
     }
-    if ((int)c->arenas.size() < c->nstreams) c->arenas.resize(c->nstreams);
-    while ((int)c->queues.size() < c->nstreams) {
-        int* q = nullptr;
-        HC(hipMalloc((void**)&q, 16 * sizeof(int)));
-        HC(hipMemset(q, 0, 16 * sizeof(int)));
-        c->queues.push_back(q);
+    while ((int)c->slots.size() < c->nstreams) {
+        StreamSlot& s = c->slots.emplace_back();
+        HC(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+        HC(hipMalloc((void**)&s.queue, 16 * sizeof(int)));
+        HC(hipMemset(s.queue, 0, 16 * sizeof(int)));
     }
 }
+
+// the tile kernels leave their ticket counters zeroed; a factorisation re-arms them anyway so that an aborted launch (device
+// error in an earlier call) can never make a later one skip work items
+void rearm_queue(StreamSlot& s) { HC(hipMemsetAsync(s.queue, 0, 16 * sizeof(int), s.st)); }
 
 // ---- profiled launch of the accumulate-mode tile kernel ---------------------------------
 // GPSLC_SYRK_DIAG=0 keeps the diagonal tiles in the general kernel (A/B switch for measurements)
@@ -285,17 +292,16 @@ static void launch_sym_diag_tiles(const GemmArgs& g, hipStream_t st) {
     launch_syrk_diag(d, g.sym == 3 && g.short_rows > 0, st);
 }
 
-void gemm(gpslc_ctx* c, const GemmArgs& g0, hipStream_t st, int prof_base = 0) {
+// prof_base: the kernel class of the profiled launches (0 = class 0 or 1 by the launch's shape)
+void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
+    hipStream_t st = s.st;
     GemmArgs g = g0;
     g.diag_skip = 0;
     g.dbg = nullptr;
     static const int nt_c = diag_env("GPSLC_NT_C", 0);
     g.nt_c = (nt_c && g.shape == 0) ? 1 : 0;      // trailing updates only
     static const int use_queue = diag_env("GPSLC_GEMM_QUEUE", 1);
-    g.queue = nullptr;
-    if (use_queue)
-        for (size_t i = 0; i < c->streams.size() && i < c->queues.size(); ++i)
-            if (c->streams[i] == st) g.queue = c->queues[i];
+    g.queue = use_queue ? s.queue : nullptr;
     if (g.ntiles <= 0 || g.nbatch <= 0 || (g.k1 <= g.k0 && g.accumulate && !g.fuse)) return;     // fuse with an empty K range: panel product only
 #ifdef GPSLC_DIAG
     // measurement build only: timing-only kernel variants (results are garbage by construction) and in-kernel
@@ -319,7 +325,7 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, hipStream_t st, int prof_base = 0) {
 #endif
     // sym == 2: the full-size diagonal tiles (those above the augmented rows) go to the lower-triangle kernel
     auto launch_diag_tiles = [&]() {
-        if (g.fuse) return;     // potrf_tiles launched them before the diagonal-block kernel (launch_sym_diag_tiles)
+        if (g.fuse) return;     // factor_panels launched them before the diagonal-block kernel (launch_sym_diag_tiles)
         if (g.sym >= 2 && g.i0 == g.j0 && (g.diag_skip == 0 || g.diag_skip == 3)) {
             GemmArgs d = g;
             const int cand = g.shape == 0 ? g.mi : 1;      // a column update holds one diagonal tile
@@ -456,42 +462,34 @@ bool potrf_tasks_ok(const gpslc_ctx* c, int nt, int ntot, int short_rows, bool s
 }
 
 // back_alpha (optional, [nb][nt 128]): every matrix's task chain ends with its back-substitution alpha = L^-T z (z = right-hand
-// side 0 after the forward solve the factorisation carries): launch_backsolve's result, bit for bit
-void potrf_tasks(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, long long inv_bstride, int* info, int info_base,
-                 int nb, hipStream_t st, int short_rows, double* back_alpha) {
-    size_t slot = 0;
-    for (size_t i = 0; i < c->streams.size(); ++i)
-        if (c->streams[i] == st) slot = i;
-    if (c->task_sync.size() <= slot) { c->task_sync.resize(slot + 1, nullptr); c->task_sync_ints.resize(slot + 1, 0); }
+// side 0 after the forward solve the factorisation carries): launch_backsolve's result, bit for bit.  The caller checks the
+// time-out word when its streams have drained (check_task_timeout).
+void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv, long long inv_bstride, int* info, int info_base,
+                 int nb, int short_rows, double* back_alpha) {
+    hipStream_t st = s.st;
+    rearm_queue(s);
     const size_t ints = TASK_SYNC_HDR + (size_t)TASK_SYNC_STRIDE * nb;
-    if (c->task_sync_ints[slot] < ints) {
-        if (c->task_sync[slot]) {
+    if (s.sync_ints < ints) {
+        if (s.sync) {
             HC(hipDeviceSynchronize());
-            int w = 0;           // a time-out of an earlier chunk of this call must survive the larger buffer
-            HC(hipMemcpy(&w, c->task_sync[slot] + 8, sizeof(int), hipMemcpyDeviceToHost));
-            if (w != 0) c->task_timed_out = true;
-            HC(hipFree(c->task_sync[slot]));
-            c->task_sync[slot] = nullptr;
+            HC(hipFree(s.sync));
+            s.sync = nullptr;
         }
-        HC(hipMalloc((void**)&c->task_sync[slot], ints * sizeof(int)));
-        HC(hipMemsetAsync(c->task_sync[slot], 0, ints * sizeof(int), st));
-        c->task_sync_ints[slot] = ints;
+        HC(hipMalloc((void**)&s.sync, ints * sizeof(int)));
+        s.sync_ints = ints;
     }
     static const int g_env = diag_env("GPSLC_TASK_G", 0);
     static const int r_env = diag_env("GPSLC_TASK_ROWS", 0);
     const TaskList& tl = task_list_for(c, nt, back_alpha ? 1 : 0, nb, g_env > 0 ? g_env : c->task_group,
                                        std::max(1, std::min(4, r_env > 0 ? r_env : (nt > 8 ? 1 : c->task_rows))), short_rows > 32);
-    // every word but the time-out word [8]: a time-out of an earlier chunk on this slot stays set until check_task_timeout has
-    // read it (zeroing it here lets a later chunk wipe it: the call then returns OK, or a failed pivot, from stale tiles)
-    HC(hipMemsetAsync(c->task_sync[slot], 0, 8 * sizeof(int), st));
-    HC(hipMemsetAsync(c->task_sync[slot] + 9, 0, (ints - 9) * sizeof(int), st));
+    HC(hipMemsetAsync(s.sync, 0, ints * sizeof(int), st));
     PotrfTaskArgs a{};
     a.g.A = M; a.g.B = M; a.g.C = M;
     a.g.F = TRef{inv, inv_bstride, 1, 0, 0, 0};
     a.g.shape = 1; a.g.k0 = 0; a.g.accumulate = 1; a.g.fuse = 1; a.g.nbatch = nb;
     a.g.short_row0 = nt; a.g.short_rows = short_rows; a.g.sym = 3;
     a.g.info = info; a.g.info_base = info_base;
-    a.list = tl.dev; a.sync = c->task_sync[slot]; a.nt = nt; a.alpha = back_alpha;
+    a.list = tl.dev; a.sync = s.sync; a.timeout = c->task_timeout; a.nt = nt; a.alpha = back_alpha;
     a.fence_mode = diag_env("GPSLC_TASK_FENCE", 0x30);      // measurement build: bit 0 = no release fence (WRONG results: the
                                                             // price of the fence), bits 4..5 = priority of the diagonal tasks
     c->task_used = true;
@@ -530,95 +528,73 @@ void potrf_tasks(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, lon
 #endif
 }
 
-// the time-out words of every stream slot, read and cleared (the launches leave them alone: see potrf_tasks), once the streams
-// have drained; true when any persistent launch since the last read timed out
-bool take_task_timeouts(gpslc_ctx* c) {
-    bool timed_out = c->task_timed_out;
-    c->task_used = false;
-    c->task_timed_out = false;
-    for (size_t i = 0; i < c->task_sync.size(); ++i) {
-        if (!c->task_sync[i]) continue;
-        int w = 0;
-        HC(hipMemcpy(&w, c->task_sync[i] + 8, sizeof(int), hipMemcpyDeviceToHost));
-        if (w != 0) {
-            const int zero = 0;
-            HC(hipMemcpy(c->task_sync[i] + 8, &zero, sizeof(int), hipMemcpyHostToDevice));
-            timed_out = true;
-        }
-    }
-    return timed_out;
-}
-
-// after the call's streams have drained: a time-out inside any persistent factorisation launch of the call (any chunk, any
-// stream slot) is an internal error
+// after the call's streams have drained: the ctx's time-out word, read and cleared (no launch zeroes it).  A time-out inside any
+// persistent factorisation launch since the last read (any chunk, any stream slot) is an internal error
 void check_task_timeout(gpslc_ctx* c) {
-    if (c->task_used && take_task_timeouts(c))
-        throw std::runtime_error("persistent factorisation launch timed out waiting for a producer task");
+    if (!c->task_used) return;
+    c->task_used = false;
+    int w = 0;
+    HC(hipMemcpy(&w, c->task_timeout, sizeof(int), hipMemcpyDeviceToHost));
+    if (w == 0) return;
+    HC(hipMemset(c->task_timeout, 0, sizeof(int)));
+    throw std::runtime_error("persistent factorisation launch timed out waiting for a producer task");
 }
 
 // at the start of a call: a previous call that threw between its persistent launches and check_task_timeout (a HIP error, an
-// allocation failure) left its time-out words unread — drain what it left in flight and clear them, so that they neither fail
-// this call nor let its launches stop waiting for their producers
+// allocation failure) left the time-out word unread — drain what it left in flight and clear the word, so that it neither fails
+// this call nor lets its launches stop waiting for their producers
 void reset_stale_task_timeouts(gpslc_ctx* c) {
     if (!c->task_used) return;
-    for (auto st : c->streams) HC(hipStreamSynchronize(st));
-    (void)take_task_timeouts(c);
+    for (auto& s : c->slots) HC(hipStreamSynchronize(s.st));
+    c->task_used = false;
+    HC(hipMemset(c->task_timeout, 0, sizeof(int)));
 }
 
-// Blocked Cholesky of the leading nt x nt tiles of the lower-packed ntot x ntot tile matrix M; the
-// rows nt..ntot-1 are carried along (augmented rows): after the call they hold R = rows * L^-T and the
-// trailing (ntot-nt)^2 block its Schur complement.  Panels of `pw` tile columns: left-looking inside a
-// panel, one right-looking trailing update (K = pw*128) per panel.
-// tasks: the caller checks the persistent launch's time-out word when its streams have drained (check_task_timeout);
-// back_alpha: where the back-substitution alpha = L^-T z may be delivered by that launch.  Returns true when it was (the
-// caller then skips launch_backsolve).
-bool potrf_tiles(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, long long inv_bstride,
-                 int* info, int info_base, int nb, hipStream_t st, int aug_rows = 0, int prof_base = 0,
-                 bool robust = false, int info_div = 1, bool skip_aug_diag = false, bool tasks = false,
-                 double* back_alpha = nullptr) {
+// Blocked Cholesky of the lower-packed nt x nt tile matrix M for near-singular matrices (CovITE + 1e-10 I, SigmaU with its 1e-13
+// jitter): no multiplication by an inverted block anywhere — the diagonal tile and the panel below it are solved by substitution
+// (k_robust.hip); the column and trailing updates stay on the MFMA tile kernel (a product is backward stable whatever the
+// conditioning).  Panels as in factor_panels.  prof_base: see gemm.
+void factor_robust(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int* info, int info_base, int nb, int prof_base) {
+    const int pw = std::max(1, c->panel);
+    rearm_queue(s);
+    for (int k = 0; k < nt; ++k) {
+        const int ka = (k / pw) * pw;
+        const int kend = std::min(ka + pw, nt);
+        if (k > ka) {
+            GemmArgs g{};
+            g.A = M; g.B = M; g.C = M;
+            g.shape = 1; g.i0 = k; g.j0 = k; g.mi = nt - k; g.mj = 1; g.sym = col_sym_mode();
+            g.k0 = ka; g.k1 = k; g.accumulate = 1; g.nbatch = nb; g.ntiles = g.mi;
+            gemm(c, g, s, prof_base);
+        }
+        launch_diag_robust(M, k, info, info_base, nb, s.st);
+        launch_trsm_robust(M, M, k, k + 1, nt - k - 1, nb, s.st);
+        if (k == kend - 1 && nt - kend > 0) {
+            GemmArgs g{};
+            g.A = M; g.B = M; g.C = M;
+            const int m = nt - kend;
+            g.shape = 0; g.i0 = kend; g.j0 = kend; g.mi = m; g.mj = m; g.sym = sym_mode();
+            g.k0 = ka; g.k1 = kend; g.accumulate = 1; g.nbatch = nb; g.ntiles = m * (m + 1) / 2;
+            g.order = tri_order(c, m);
+            gemm(c, g, s, prof_base);
+        }
+    }
+    HC(hipGetLastError());
+}
+
+// Blocked Cholesky of the leading nt x nt tiles of the lower-packed ntot x ntot tile matrix M (inverted diagonal blocks into inv);
+// the rows nt..ntot-1 are carried along (augmented rows): after the call they hold R = rows * L^-T and the trailing (ntot-nt)^2
+// block its Schur complement.  Panels of `pw` tile columns: left-looking inside a panel, one right-looking trailing update
+// (K = pw*128) per panel.  prof_base: see gemm.
+void factor_panels(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int ntot, double* inv, long long inv_bstride,
+                   int* info, int info_base, int nb, int aug_rows, bool skip_aug_diag, int prof_base) {
+    hipStream_t st = s.st;
     // aug_rows > 0: the tile rows nt.. hold only that many live rows in total (right-hand sides);
     // a single augmented tile row is the common case and the only one the kernel shortens
     const int short_rows = (aug_rows > 0 && ntot == nt + 1) ? aug_rows : 0;
     const int pw = std::max(1, c->panel);
-    // the tile kernels leave their ticket counters zeroed; re-arm them anyway so that an aborted launch
-    // (device error in an earlier call) can never make a later factorisation skip work items
-    for (size_t i = 0; i < c->streams.size() && i < c->queues.size(); ++i)
-        if (c->streams[i] == st) HC(hipMemsetAsync(c->queues[i], 0, 16 * sizeof(int), st));
+    rearm_queue(s);
     TRef invref = TRef{inv, inv_bstride, 1, 0, 0, 0};   // tile (j, kk) -> inv[kk]
-    if (robust && ntot == nt) {
-        // Near-singular matrices (CovITE + 1e-10 I, SigmaU with its 1e-13 jitter): no multiplication by an inverted block
-        // anywhere — the diagonal tile and the panel below it are solved by substitution (k_robust.hip); the column and
-        // trailing updates stay on the MFMA tile kernel (a product is backward stable whatever the conditioning).
-        for (int k = 0; k < nt; ++k) {
-            const int ka = (k / pw) * pw;
-            const int kend = std::min(ka + pw, nt);
-            if (k > ka) {
-                GemmArgs g{};
-                g.A = M; g.B = M; g.C = M;
-                g.shape = 1; g.i0 = k; g.j0 = k; g.mi = nt - k; g.mj = 1; g.sym = col_sym_mode();
-                g.k0 = ka; g.k1 = k; g.accumulate = 1; g.nbatch = nb; g.ntiles = g.mi;
-                gemm(c, g, st, prof_base);
-            }
-            launch_diag_robust(M, k, info, info_base, nb, st, info_div);
-            launch_trsm_robust(M, M, k, k + 1, nt - k - 1, nb, st);
-            if (k == kend - 1 && nt - kend > 0) {
-                GemmArgs g{};
-                g.A = M; g.B = M; g.C = M;
-                const int m = nt - kend;
-                g.shape = 0; g.i0 = kend; g.j0 = kend; g.mi = m; g.mj = m; g.sym = sym_mode();
-                g.k0 = ka; g.k1 = kend; g.accumulate = 1; g.nbatch = nb; g.ntiles = m * (m + 1) / 2;
-                g.order = tri_order(c, m);
-                gemm(c, g, st, prof_base);
-            }
-        }
-        HC(hipGetLastError());
-        return false;
-    }
-    // small tile counts: the whole factorisation (and the back-substitution) as ONE persistent launch of tile tasks
-    if (tasks && info_div == 1 && prof_base == 0 && potrf_tasks_ok(c, nt, ntot, short_rows, skip_aug_diag, nb, inv)) {
-        potrf_tasks(c, M, nt, ntot, inv, inv_bstride, info, info_base, nb, st, short_rows, back_alpha);
-        return back_alpha != nullptr;
-    }
     for (int k = 0; k < nt; ++k) {
         const int ka = (k / pw) * pw;
         const int kend = std::min(ka + pw, nt);
@@ -635,8 +611,7 @@ bool potrf_tiles(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, lon
                 // GPSLC_DIAG_FOLD (measurement switch, default on): update + factorisation of the diagonal tile in ONE
                 // launch (diag_update_potrf_kernel) instead of tile_syrk_diag_kernel followed by diag_potrf_inv_la_kernel
                 static const int fold = diag_env("GPSLC_DIAG_FOLD", 1);
-                const bool fold_ok = fold && info_div == 1;
-                if (fold_ok) {
+                if (fold) {
                     GemmArgs d = g;
                     d.F = invref; d.info = info; d.info_base = info_base;
                     launch_diag_update_potrf(d, g.sym == 3 && short_rows > 0, st);
@@ -645,10 +620,10 @@ bool potrf_tiles(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, lon
                     launch_diag(M, k, inv, inv_bstride, info, info_base, nb, st);
                 }
                 g.fuse = 1; g.F = invref; g.fk = k;
-                gemm(c, g, st, prof_base);
+                gemm(c, g, s, prof_base);
                 fused = true;
             } else {
-                gemm(c, g, st, prof_base);
+                gemm(c, g, s, prof_base);
             }
         }
         if (!fused) launch_diag(M, k, inv, inv_bstride, info, info_base, nb, st);
@@ -668,7 +643,7 @@ bool potrf_tiles(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, lon
             } else {
                 g.B = invref; g.k0 = k; g.k1 = k + 1; g.accumulate = 0;
             }
-            gemm(c, g, st, prof_base);
+            gemm(c, g, s, prof_base);
         }
         // skip_aug_diag (single short augmented row, epilogue sums from the rows of R): the augmented diagonal tile is
         // never updated — after the last panel it would be the launch's only item
@@ -682,10 +657,9 @@ bool potrf_tiles(gpslc_ctx* c, const TRef& M, int nt, int ntot, double* inv, lon
             g.k0 = ka; g.k1 = kend; g.accumulate = 1; g.nbatch = nb; g.ntiles = m * (m + 1) / 2;
             g.order = tri_order(c, m);
             g.short_row0 = nt; g.short_rows = short_rows;
-            gemm(c, g, st, prof_base);
+            gemm(c, g, s, prof_base);
         }
     }
-    return false;
 }
 
 struct PredictIO {
@@ -718,7 +692,7 @@ struct PredictIO {
 
 // chunk and unit-B sub-batch sizes of a call (batch_plan.h holds the arithmetic; here: what the schedule would like and what
 // the device has)
-BatchPlan auto_batch(gpslc_ctx* c, int64_t S, int L, size_t per_sample_bytes, long long want_bb, size_t unit_bytes, size_t lvl_extra) {
+BatchPlan auto_batch(gpslc_ctx* c, int64_t S, int L, size_t per_sample_bytes, size_t unit_bytes, size_t lvl_extra) {
     // enough matrices in flight that the per-step diagonal-block kernel (one workgroup per matrix) and the
     // launch quantisation of the late, small trailing updates are amortised: 1024 at N = 4096 (82 GB of the
     // 288 GB; measured 2013 / 2040 / 2055 / 2064 samples/s at batch 256 / 512 / 1024 / 2048)
@@ -727,10 +701,16 @@ BatchPlan auto_batch(gpslc_ctx* c, int64_t S, int L, size_t per_sample_bytes, lo
     long long b = 1048576LL / ((long long)c->nt * c->nt);
     b = std::max<long long>(32, std::min<long long>(b, 16384));
     if (c->max_batch > 0) b = c->max_batch;
+    // unit-B sub-batch (unit_bytes > 0): 128 units at N = 4096 (203 MB each, 26 GB).  Round 5, 256 units of 8 samples x 32 levels
+    // on one box (profiles/r05_ab_experiments.md §3): 16 / 32 / 64 / 128 / 256 per sub-batch -> 322 / 349 / 364 / 372 / 373
+    // units/s — the late columns of a factorisation have (nt - k) x sub-batch items for 512 workgroup slots; flat from 128 on
+    long long want_bb = std::max<long long>(1, std::min<long long>(128, 131072LL / ((long long)c->nt * c->nt)));
+    static const int bb_env = diag_env("GPSLC_UNITB_BATCH", 0);      // measurement switch: the sub-batch curve (profiles/r05)
+    if (bb_env > 0) want_bb = bb_env;
     size_t free_b = 0, tot_b = 0;
     HC(hipMemGetInfo(&free_b, &tot_b));
     size_t have = 0;
-    for (auto& a : c->arenas) have += a.bytes;
+    for (auto& sl : c->slots) have += sl.arena.bytes;
     // the AUTOMATIC chunk also stays under 30 % of the device's memory (arenas never shrink, and the host process usually
     // shares the device: torch's caching allocator under sharded.py / bench.py, other contexts of gpslc_predict_multi on one
     // GPU); 1,024 matrices at N = 4096 are 28 %.  gpslc_set_tuning(max_batch) may ask for more: then only what is free counts.
@@ -738,6 +718,307 @@ BatchPlan auto_batch(gpslc_ctx* c, int64_t S, int L, size_t per_sample_bytes, lo
                                    c->max_batch <= 0);
     if (!p.ok) throw std::bad_alloc();
     return p;
+}
+
+// what one run_predict call computes and the sizes that follow from it (the same for all of its chunks)
+struct PredictShape {
+    int n, nt, L, naug, ntot;
+    long long Np, tiles_per, nlow;   // padded N, tiles of A with its augmented rows, tiles of an nt x nt triangle
+    bool with_sums, want_cov, want_draws, want_mean, unitB;     // unitB: full ITE covariance (CovITE, draws)
+    PredictShape(const gpslc_ctx* c, const PredictIO& io)
+        : n((int)c->n), nt(c->nt), L(io.L), naug((L + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug), Np((long long)nt * GP_TS),
+          tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2), with_sums(io.meanSATE || io.varSATE),
+          want_cov(io.CovITEs != nullptr), want_draws(io.ite_draws != nullptr), want_mean(io.meanITE || io.MeanITEs || want_draws),
+          unitB(want_cov || want_draws) {}
+};
+
+// one chunk of a call: samples s0 .. s0 + nb - 1 on one stream slot, and the buffers carve_chunk takes for it from the slot's arena
+struct Chunk {
+    StreamSlot* s = nullptr;
+    int64_t s0 = 0;
+    int nb = 0;
+    TRef M{};                        // the tile matrices of A over `tiles`
+    double *tiles = nullptr, *inv = nullptr, *part = nullptr, *bsum = nullptr, *ksum = nullptr, *sumdelta = nullptr;
+    double *vpart = nullptr, *zwork = nullptr, *znode = nullptr;
+    // unit B: a sub-batch of gs_max samples x lc_max levels; W, CovITE, the draws' normals, level-sweep staging, failure codes
+    int lc_max = 0, gs_max = 0;
+    double *Wt = nullptr, *Ct = nullptr, *zgen = nullptr, *zt = nullptr, *dtmp = nullptr;
+    int* pinfo = nullptr;
+};
+
+struct ChunkBytes { size_t per_sample = 1024, per_pair = 0, per_level = 0; };    // 1 KiB: the 256-byte alignment of each buffer
+
+// Carves a chunk's buffers from its slot's arena (nb samples, sub-batches of Bb pairs) and counts, beside each buffer, the bytes
+// auto_batch reserves for it: per sample, per (sample, level) pair of a unit-B sub-batch, and per level of a sweep beyond the
+// sub-batch (the level-sweep staging).  ch == nullptr: the counts only.
+ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chunk* ch) {
+    ChunkBytes by;
+    Chunk none;
+    Chunk& b = ch ? *ch : none;
+    Arena* ar = ch ? &ch->s->arena : nullptr;
+    auto take = [&](size_t per_sample) -> double* {
+        by.per_sample += per_sample * 8;
+        return ar ? ar->take<double>((size_t)b.nb * per_sample) : nullptr;
+    };
+    const int n = sh.n, nt = sh.nt, L = sh.L;
+    // spp <= 128: the streaming draw kernel reads the unit's normals (caller's or Philox) from an operand image of 16 Np doubles
+    // per block of 16 draws (DrawArgs::zt); per unit: 1 / 2 / 4 / 8 blocks of 16 draws (draws_nq, k_solve.hip: the stream
+    // kernel's template parameter)
+    const bool zimage = sh.want_draws && io.spp <= 128;
+    const size_t zimage_doubles = zimage ? (size_t)16 * (io.spp <= 16 ? 1 : io.spp <= 32 ? 2 : io.spp <= 64 ? 4 : 8) * sh.Np : 0;
+    b.tiles = take(sh.tiles_per * GP_TSQ);
+    b.inv = take((size_t)nt * GP_TSQ);
+    if (sh.with_sums) b.part = take(2 * nt * sh.Np);
+    b.bsum = take(sh.Np); b.ksum = take(sh.Np);
+    b.sumdelta = take(std::max(L, 1));
+    if (io.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
+    b.zwork = take(2 * sh.Np);                                          // zwork + alpha
+    if (io.ndraw) b.znode = take(16 * sh.Np);                           // operand image of the node draw's normals
+    b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
+    if (!sh.unitB) return by;
+    by.per_pair = (size_t)((long long)nt * nt + sh.nlow) * GP_TSQ * 8;
+    if (sh.want_draws) {
+        by.per_pair += (zimage ? zimage_doubles * 8 + 256 : (io.z ? 0 : (size_t)io.spp * n * 8 + 256)) +
+                       (L > 1 ? (size_t)io.spp * n * 8 + 256 : 0) + sizeof(int) + 256;
+        by.per_level = (size_t)io.spp * n * 8;
+    }
+    if (!ar) return by;
+    b.lc_max = std::min(L, Bb);                      // levels per sub-batch
+    b.gs_max = std::max(1, Bb / b.lc_max);           // samples per sub-batch
+    b.Wt = ar->take<double>((size_t)Bb * nt * nt * GP_TSQ);
+    b.Ct = ar->take<double>((size_t)Bb * sh.nlow * GP_TSQ);
+    // draws: the library's own normals of one sub-batch (generated once per unit), and for a level sweep the staging buffer
+    // [sample][level][d][i] that is rearranged into the level-fastest tensor sample group by group (per unit of the sub-batch:
+    // max(1, Bb / L) samples x L levels <= Bb pairs, or one sample's L > Bb levels — per_level)
+    if (sh.want_draws && !io.z && !zimage) b.zgen = ar->take<double>((size_t)Bb * io.spp * n);
+    if (zimage) b.zt = ar->take<double>((size_t)Bb * zimage_doubles);
+    if (sh.want_draws && L > 1) b.dtmp = ar->take<double>((size_t)b.gs_max * L * io.spp * n);
+    // failure codes of the CovITE factors, one per pair of a sub-batch (folded into io.info after each sub-batch)
+    if (sh.want_draws) b.pinfo = ar->take<int>((size_t)Bb);
+    return by;
+}
+
+// the vector-level kernels' arguments of a chunk (doT is n x L: level l at doT + n*l)
+VecArgs vec_args(const gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    VecArgs va{};
+    va.X = io.X; va.T = c->dT; va.p = io.p; va.s0 = ch.s0;
+    va.n = sh.n; va.nX = io.nX; va.nU = io.nU; va.nt = sh.nt; va.L = sh.L; va.doT = io.doT;
+    va.M = ch.M; va.part = ch.vpart; va.sumdelta = ch.sumdelta;
+    va.Y = io.Y; va.y_sstride = io.y_sstride;
+    return va;
+}
+
+// unit A of a chunk: Gram build, right-hand sides, vector sums, factorisation, epilogue and node draw.  Returns whether the
+// factorisation delivered the back-substitution alpha.
+bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    hipStream_t st = ch.s->st;
+    const int n = sh.n, nt = sh.nt, nb = ch.nb;
+    const int64_t s0 = ch.s0;
+    GramArgs ga{};
+    ga.X = io.X; ga.T = c->dT; ga.p = io.p; ga.s0 = s0;
+    ga.n = n; ga.nX = io.nX; ga.nU = io.nU; ga.nt = nt; ga.M = ch.M; ga.part = ch.part;
+    ga.with_sums = sh.with_sums ? 1 : 0;
+#ifdef GPSLC_DIAG
+    static const int gram_dbg = diag_env("GPSLC_GRAM_DBG", 0);
+    static bool gram_dbg_done = false;
+    DevBuf gdbg;
+    if (gram_dbg && !gram_dbg_done) {
+        const size_t words = (size_t)8 * nb * (nt * (nt + 1) / 2);
+        gdbg.alloc(words * 8);
+        HC(hipMemset(gdbg.p, 0, words * 8));
+        ga.dbg = gdbg.as<unsigned long long>();
+    }
+#endif
+    ga.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
+    ga.binary_t = (c->binary_t && io.nU == c->nU && io.nX == c->nX && io.Y == c->dY) ? 1 : 0;   // ctx data only
+    launch_gram(ga, nb, st);
+#ifdef GPSLC_DIAG
+    if (ga.dbg) {      // GPSLC_GRAM_DBG: dump the first launch's per-workgroup stamps
+        HC(hipStreamSynchronize(st));
+        const size_t words = (size_t)8 * nb * (nt * (nt + 1) / 2);
+        std::vector<unsigned long long> h(words);
+        HC(hipMemcpy(h.data(), ga.dbg, words * 8, hipMemcpyDeviceToHost));
+        FILE* f = fopen("gpurun_out/gram_dbg.bin", "wb");
+        if (f) { fwrite(h.data(), 8, words, f); fclose(f); }
+        gram_dbg_done = true;
+    }
+#endif
+    RhsArgs ra{};
+    ra.T = c->dT; ra.Y = io.Y; ra.y_sstride = io.y_sstride; ra.tyLS = io.p.tyLS; ra.doT = io.doT; ra.s0 = s0;
+    // vector levels: rhs_tiles writes zeros into the level rows and rhs_prepare no level sums (L = 0 here); launch_vec_sums
+    // fills both below
+    ra.n = n; ra.nt = nt; ra.naug = sh.naug; ra.L = (sh.with_sums && !io.vec) ? sh.L : 0; ra.with_sums = sh.with_sums ? 1 : 0;
+    ra.part = ch.part; ra.bsum = ch.bsum; ra.ksum = ch.ksum; ra.sumdelta = ch.sumdelta; ra.M = ch.M;
+    static const int epi_rows_on = diag_env("GPSLC_EPI_ROWS", 1);      // measurement switch (A/B of the extra tile update)
+    const bool epi_rows = (sh.naug == 1) && epi_rows_on;     // single augmented tile row: the epilogue sums from the rows of R
+    const int live = (sh.with_sums ? sh.L : 0) + 1;          // right-hand sides: Y and one c_l per level
+    ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
+    launch_rhs(ra, nb, st);
+    if (io.vec && sh.with_sums) launch_vec_sums(vec_args(c, io, sh, ch), nb, st);
+    // NB: the MeanITE pass takes K alpha as Y - yNoise alpha (k_solve.hip, ite_mean_kernel): it relies on alpha solving EXACTLY
+    // (K_gram + yNoise I) alpha = Y.  Any future jitter, robust fallback or different right-hand side in this factorisation must
+    // be reflected there (tests: test_mean_ite_tiny_noise_and_near_coincident_levels).
+    const long long inv_bs = (long long)nt * GP_TSQ;
+    const int short_rows = sh.naug == 1 ? live : 0;
+    bool back_done = false;
+    if (potrf_tasks_ok(c, nt, sh.ntot, short_rows, epi_rows, nb, ch.inv)) {
+        // small tile counts: the whole factorisation (and the back-substitution) as ONE persistent launch of tile tasks
+        potrf_tasks(c, *ch.s, ch.M, nt, ch.inv, inv_bs, io.info + s0, 0, nb, short_rows,
+                    sh.want_mean ? ch.zwork + (long long)nb * sh.Np : nullptr);
+        back_done = sh.want_mean;
+    } else {
+        factor_panels(c, *ch.s, ch.M, nt, sh.ntot, ch.inv, inv_bs, io.info + s0, 0, nb, live, epi_rows, 0);
+    }
+    EpiArgs ea{};
+    ea.M = ch.M; ea.n = n; ea.nt = nt; ea.naug = sh.naug; ea.L = sh.with_sums ? sh.L : 0; ea.s0 = s0; ea.S = io.S;
+    ea.sumdelta = ch.sumdelta; ea.pred_noise = io.pred_noise;
+    ea.meanSATE = io.meanSATE; ea.varSATE = io.varSATE; ea.logdet = io.logdet; ea.quad = io.quad;
+    ea.from_rows = epi_rows ? 1 : 0;
+    launch_epilogue(ea, nb, st);
+    if (io.ndraw) {
+        // one draw from N(0, A_s) per parameter set with the caller's normals: L_s z_s on the factor just computed — Gen's
+        // mvnormal(zeros(n), cov) of an elliptical slice's auxiliary vector (src/inference.jl:225-232) and of the :logitT prior
+        // draw (src/model_likelihood.jl:25-33) — the predictive-draw kernel streaming L once
+        DrawArgs dr{};
+        dr.Lc = ch.M; dr.n = n; dr.nt = nt; dr.s0 = s0; dr.S = io.S; dr.l = 0; dr.lc = 1; dr.L = 1; dr.spp = 1;
+        dr.mean = io.nzero; dr.z = io.nz; dr.zt = ch.znode; dr.out = io.ndraw;
+        dr.obase = (long long)n * s0; dr.osb = n; dr.osl = 0; dr.osi = 1; dr.osd = n;
+        launch_draws(dr, nb, st);
+    }
+    return back_done;
+}
+
+// MeanITE of a chunk: the back-substitution (unless the factorisation delivered alpha) and the ITE-mean kernels, once per output
+// layout asked for: meanITE n x S x L, MeanITEs S x n (the reference layout, single level)
+void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch, bool back_done) {
+    hipStream_t st = ch.s->st;
+    const int n = sh.n, nb = ch.nb;
+    BackArgs ba{};
+    ba.M = ch.M; ba.inv = ch.inv; ba.inv_bstride = (long long)sh.nt * GP_TSQ; ba.nt = sh.nt; ba.naug = sh.naug; ba.zwork = ch.zwork;
+    if (!back_done) launch_backsolve(ba, nb, st);
+    const double* alpha = ch.zwork + (long long)nb * sh.Np;
+    const struct { double* out; long long si, ss, sl; } outs[2] = {{io.meanITE, 1, n, (long long)n * io.S}, {io.MeanITEs, io.S, 1, 0}};
+    if (io.vec) {
+        VecArgs va = vec_args(c, io, sh, ch);
+        va.alpha = alpha;
+        for (const auto& o : outs)
+            if (o.out) { va.meanITE = o.out; va.si = o.si; va.ss = o.ss; va.sl = o.sl; launch_vec_mean(va, nb, st); }
+        return;
+    }
+    IteMeanArgs ia{};
+    ia.X = io.X; ia.T = c->dT; ia.p = io.p; ia.s0 = ch.s0; ia.S = io.S;
+    ia.n = n; ia.nX = io.nX; ia.nU = io.nU; ia.nt = sh.nt; ia.L = sh.L; ia.doT = io.doT; ia.alpha = alpha;
+    ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.p.yNoise;
+    ia.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
+    for (const auto& o : outs)
+        if (o.out) { ia.meanITE = o.out; ia.si = o.si; ia.ss = o.ss; ia.sl = o.sl; launch_ite_mean(ia, nb, st); }
+}
+
+// unit B's W <- D L^-T for ub (sample, level) pairs, left-looking over tile columns: the panel product with inv(L_kk)^T is
+// applied by the same work item that finishes the column update (the tile makes one HBM round trip, as in the factorisation),
+// column 0 has no update and takes the panel product alone. Left-looking over the whole width (every column update in the strip
+// kernel).  GPSLC_W_PANEL = w > 0 (measurement build) blocks it like the factorisation instead — left-looking inside panels of w
+// tile columns, one right-looking update of everything to the right of a panel on the quadrant kernel.  Measured in round 4
+// (profiles/r04_ab_experiments.md §7): w = 4 / 8 / 16 -> 354 / 360 / 363.5 units/s against 363 unblocked: with a deep K loop the
+// strip kernel is as fast as the quadrant kernel's rectangle update plus the extra pass over W.  Not the default.
+void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const TRef& invref, int nt, int ub) {
+    static const int wpw_env = diag_env("GPSLC_W_PANEL", 0);
+    const int wpw = wpw_env <= 0 ? nt : wpw_env;
+    // fused up to a K depth of w_fuse_maxk tiles (measurement switch; +0.7 % fused at every depth)
+    static const int w_fuse_maxk = diag_env("GPSLC_FUSE_W_MAXK", 32);
+    for (int k = 0; k < nt; ++k) {
+        const int ka = (k / wpw) * wpw;
+        const int kend = std::min(ka + wpw, nt);
+        GemmArgs g{};
+        g.A = W; g.C = W;
+        g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1; g.nbatch = ub; g.ntiles = nt;
+        if (k - ka <= w_fuse_maxk && fuse_mode()) {      // k == ka: empty K range, the panel product alone (round 5)
+            g.B = Ls; g.k0 = ka; g.k1 = k; g.accumulate = 1;
+            g.fuse = 1; g.F = invref; g.fk = k;
+            gemm(c, g, s, 3);
+        } else {
+            if (k > ka) {
+                g.B = Ls; g.k0 = ka; g.k1 = k; g.accumulate = 1;
+                gemm(c, g, s, 3);
+            }
+            g.B = invref; g.k0 = k; g.k1 = k + 1; g.accumulate = 0;
+            gemm(c, g, s, 3);
+        }
+        if (k == kend - 1 && kend < nt) {      // the panel is solved: update everything to its right
+            GemmArgs t{};
+            t.A = W; t.B = Ls; t.C = W;
+            t.shape = 1; t.i0 = 0; t.j0 = kend; t.mi = nt; t.mj = nt - kend;
+            t.k0 = ka; t.k1 = kend; t.accumulate = 1; t.nbatch = ub; t.ntiles = t.mi * t.mj;
+            gemm(c, t, s, 3);
+        }
+    }
+}
+
+// Unit B of a chunk batches over (posterior sample, level) PAIRS: a sub-batch is gs samples x lc levels (gs * lc <= Bb), batch
+// element b = (sample b / lc, level l0 + b % lc).  Every pair has its own W / CovITE workspace; the factor of A and its inverted
+// diagonal blocks are shared by a sample's levels (TRef::bdiv = lc) — the shape of predictCounterfactualEffects
+// (src/prediction.jl:30-33): few samples, ~100 levels.
+void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    hipStream_t st = ch.s->st;
+    const int n = sh.n, nt = sh.nt, L = sh.L, nb = ch.nb;
+    const int64_t s0 = ch.s0;
+    const long long bstride = sh.tiles_per * GP_TSQ, inv_bs = (long long)nt * GP_TSQ;
+    const TRef W = rect_ref(ch.Wt, (long long)nt * nt * GP_TSQ, nt), Cm = lower_ref(ch.Ct, sh.nlow * GP_TSQ);
+    for (int g0 = 0; g0 < nb; g0 += ch.gs_max) {
+        const int gs = std::min(ch.gs_max, nb - g0);
+        for (int l0 = 0; l0 < L; l0 += ch.lc_max) {
+            const int lc = std::min(ch.lc_max, L - l0);
+            const int ub = gs * lc;                           // (sample, level) pairs of this sub-batch
+            TRef Ls = lower_ref(ch.tiles + (long long)g0 * bstride, bstride);
+            Ls.bdiv = lc;
+            DtArgs da{};
+            da.X = io.X; da.T = c->dT; da.p = io.p; da.s0 = s0 + g0;
+            da.n = n; da.nX = io.nX; da.nU = io.nU; da.nt = nt; da.doT = io.doT; da.l0 = l0; da.lc = lc;
+            da.vec = io.vec ? 1 : 0;
+            da.pred_noise = io.pred_noise; da.W = W; da.Cm = Cm;
+            launch_dt_build(da, ub, st);
+            TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
+            invref.bdiv = lc;
+            w_solve(c, *ch.s, W, Ls, invref, nt, ub);
+            GemmArgs g{};            // CovITE (+ jitter) = Delta - W W^T, lower tiles
+            g.A = W; g.B = W; g.C = Cm;
+            g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt; g.sym = sym_mode();
+            g.k0 = 0; g.k1 = nt; g.accumulate = 1; g.nbatch = ub; g.ntiles = (int)sh.nlow;
+            g.order = tri_order(c, nt);
+            gemm(c, g, *ch.s, 3);
+            if (sh.want_cov) {       // ITEDistributions: single level (lc == 1)
+                GatherCovArgs gc{};
+                gc.Cm = Cm; gc.n = n; gc.nt = nt; gc.s0 = s0 + g0; gc.S = io.S; gc.out = io.CovITEs;
+                launch_gather_cov(gc, ub, st);
+            }
+            if (sh.want_draws) {
+                // one failure code per pair, then per sample the code of its lowest-index failing level (the reference's loop
+                // order, src/prediction.jl:30-33): a shared word per sample would let the lc levels of a diagonal launch race,
+                // and the lowest failing tile column win across launches
+                HC(hipMemsetAsync(ch.pinfo, 0, sizeof(int) * ub, st));
+                factor_robust(c, *ch.s, Cm, nt, ch.pinfo, n, ub, 3);
+                launch_fold_pair_info(ch.pinfo, io.info + s0 + g0, gs, lc, st);
+                DrawArgs dr{};
+                dr.Lc = Cm; dr.n = n; dr.nt = nt; dr.s0 = s0 + g0; dr.S = io.S; dr.l = l0; dr.lc = lc; dr.L = L;
+                dr.spp = io.spp; dr.mean = io.meanITE; dr.z = io.z; dr.zgen = ch.zgen; dr.zt = ch.zt; dr.seed = io.seed;
+                const int64_t eS = io.ens_S > 0 ? io.ens_S : c->ens_S, eo = io.ens_S > 0 ? io.ens_off : c->ens_off;
+                dr.rs0 = dr.s0 + (eS > 0 ? eo : 0); dr.rS = eS > 0 ? eS : io.S;
+                if (L == 1) {     // the reference tensor directly: n x (S*spp), instance fastest
+                    dr.out = io.ite_draws;
+                    dr.obase = (long long)n * io.spp * (s0 + g0); dr.osb = (long long)n * io.spp; dr.osl = 0;
+                    dr.osi = 1; dr.osd = n;
+                } else {          // staging [sample][level][d][i]
+                    dr.out = ch.dtmp;
+                    dr.obase = (long long)l0 * io.spp * n; dr.osb = (long long)L * io.spp * n;
+                    dr.osl = (long long)io.spp * n; dr.osi = 1; dr.osd = n;
+                }
+                ProfScope ps(c, 2, (double)ub * io.spp, st);     // unit C: work = draws
+                launch_draws(dr, ub, st);
+            }
+        }
+        if (sh.want_draws && L > 1)
+            launch_draws_scatter(ch.dtmp, io.ite_draws, n, L, io.spp, s0 + g0, gs, st);
+    }
 }
 
 // the chunked ensemble driver (device pointers everywhere)
@@ -749,317 +1030,32 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     if (io.p.u_sstride == 0 && io.nU > 0 && io.p.U != nullptr && !io.p_shared_u) io.p.u_sstride = (long long)c->n * io.nU;
     reset_stale_task_timeouts(c);
     ensure_streams(c);
-    const int n = (int)c->n, nt = c->nt;
-    const int L = io.L;
-    const int naug = (L + 1 + GP_TS - 1) / GP_TS;
-    const int ntot = nt + naug;
-    const long long Np = (long long)nt * GP_TS;
-    const long long tiles_per = (long long)ntot * (ntot + 1) / 2;
-    const bool want_sate = io.meanSATE || io.varSATE;
-    const bool want_cov = io.CovITEs != nullptr;
-    const bool want_draws = io.ite_draws != nullptr;
-    const bool want_mean = io.meanITE || io.MeanITEs || want_draws;
-    const bool with_sums = want_sate;
-    const long long nlow = (long long)nt * (nt + 1) / 2;
-
-    // unit-B sub-batch (full ITE covariance): W (nt^2 tiles) + Cm (nlow tiles) + inv (nt tiles)
-    const bool unitB = want_cov || want_draws;
-    const size_t unitB_per = unitB ? (size_t)((long long)nt * nt + nlow) * GP_TSQ * 8 : 0;
-
-    size_t per = (size_t)tiles_per * GP_TSQ * 8      // tiles
-               + (size_t)nt * GP_TSQ * 8             // inv
-               + (size_t)(with_sums ? 2 * nt * Np * 8 : 0)
-               + (size_t)(2 * Np * 8)                // bsum, ksum
-               + (size_t)(std::max(L, 1) * 8)        // sumdelta
-               + (size_t)(io.vec && with_sums ? (size_t)L * nt * 8 : 0)   // vector levels: per-tile shares of sum(Delta)
-               + (size_t)(2 * Np * 8)                // zwork + alpha
-               + (size_t)(io.ndraw ? 16 * Np * 8 : 0)   // operand image of the node draw's normals
-               + 1024;
-    int Bb_target = 0;
-    if (unitB) {
-        // unit-B sub-batch: 128 units at N = 4096 (203 MB each, 26 GB).  Round 5, 256 units of 8 samples x 32 levels on one box
-        // (profiles/r05_ab_experiments.md §3): 16 / 32 / 64 / 128 / 256 per sub-batch -> 322 / 349 / 364 / 372 / 373 units/s —
-        // the late columns of a factorisation have (nt - k) x sub-batch items for 512 workgroup slots; flat from 128 on
-        Bb_target = (int)std::max<long long>(1, std::min<long long>(128, 131072LL / ((long long)nt * nt)));
-        static const int bb_env = diag_env("GPSLC_UNITB_BATCH", 0);      // measurement switch: the sub-batch curve (profiles/r05)
-        if (bb_env > 0) Bb_target = bb_env;
-    }
-    // draws: normals workspace of one level of the sub-batch + the level-sweep staging buffer (see the unit-B loop)
-    // (per unit of the sub-batch: the staging buffer holds max(1, Bb / L) samples x L levels <= Bb pairs, or one sample's
-    // L > Bb levels — sized below through the extra term)
-    // spp <= 128: the streaming draw kernel reads the unit's normals (caller's or Philox) from an operand image of
-    // 16 Np doubles per block of 16 draws (DrawArgs::zt) instead
-    const bool zimage = want_draws && io.spp <= 128;
-    // per unit: 1 / 2 / 4 / 8 blocks of 16 draws (draws_nq, k_solve.hip: the stream kernel's template parameter)
-    const size_t zimage_doubles = zimage ? (size_t)16 * (io.spp <= 16 ? 1 : io.spp <= 32 ? 2 : io.spp <= 64 ? 4 : 8) * Np : 0;
-    const size_t draws_per = want_draws ? ((zimage ? zimage_doubles * 8 + 256 : (io.z ? 0 : (size_t)io.spp * n * 8 + 256)) +
-                                           (L > 1 ? (size_t)io.spp * n * 8 + 256 : 0) + sizeof(int) + 256) : 0;
-    const size_t unitB_all = unitB_per + draws_per;
+    const PredictShape sh(c, io);
     // chunk size and sub-batch from what the device has (the sub-batch's workspace is sized from the pairs the call
     // really has, and the 30 % rule of the automatic chunk covers its per-sample part only)
-    const BatchPlan plan = auto_batch(c, io.S, L, per, Bb_target, unitB_all, want_draws ? (size_t)io.spp * n * 8 : 0);
-    const int Bt = (int)plan.Bt;
-    const int Bb = (int)plan.Bb;      // (sample, level) pairs per unit-B sub-batch: no more than the call has
-    const size_t need = (size_t)Bt * per + plan.fixed;
-    for (int i = 0; i < c->nstreams; ++i) arena_reserve(c, c->arenas[i], need);
-
+    const ChunkBytes by = carve_chunk(sh, io, 0, nullptr);
+    const BatchPlan plan = auto_batch(c, io.S, sh.L, by.per_sample, by.per_pair, by.per_level);
+    const int Bt = (int)plan.Bt, Bb = (int)plan.Bb;      // Bb: (sample, level) pairs per unit-B sub-batch, no more than the call has
+    const size_t need = (size_t)Bt * by.per_sample + plan.fixed;
+    for (int i = 0; i < c->nstreams; ++i) arena_reserve(c, c->slots[i].arena, need);
     // internal MeanITE buffer when the caller did not ask for it but the draws need it
-    double* meanITE = io.meanITE;
-    if (want_draws && !meanITE) {
-        arena_reserve(c, c->scratch, std::max(c->scratch.bytes, (size_t)n * io.S * L * 8 + (1 << 16)));
+    if (sh.want_draws && !io.meanITE) {
+        arena_reserve(c, c->scratch, std::max(c->scratch.bytes, (size_t)sh.n * io.S * sh.L * 8 + (1 << 16)));
         c->scratch.reset();
-        meanITE = c->scratch.take<double>((size_t)n * io.S * L);
+        io.meanITE = c->scratch.take<double>((size_t)sh.n * io.S * sh.L);
     }
-
-    HC(hipMemsetAsync(io.info, 0, sizeof(int) * io.S, c->streams[0]));
-    HC(hipStreamSynchronize(c->streams[0]));
-
+    HC(hipMemsetAsync(io.info, 0, sizeof(int) * io.S, c->slots[0].st));
+    HC(hipStreamSynchronize(c->slots[0].st));
     int chunk = 0;
     for (int64_t s0 = 0; s0 < io.S; s0 += Bt, ++chunk) {
-        const int nb = (int)std::min<int64_t>(Bt, io.S - s0);
-        const int slot = chunk % c->nstreams;
-        hipStream_t st = c->streams[slot];
-        Arena& ar = c->arenas[slot];
-        ar.reset();
-        double* tiles = ar.take<double>((size_t)nb * tiles_per * GP_TSQ);
-        double* inv = ar.take<double>((size_t)nb * nt * GP_TSQ);
-        double* part = with_sums ? ar.take<double>((size_t)nb * 2 * nt * Np) : nullptr;
-        double* bsum = ar.take<double>((size_t)nb * Np);
-        double* ksum = ar.take<double>((size_t)nb * Np);
-        double* sumdelta = ar.take<double>((size_t)nb * std::max(L, 1));
-        double* vpart = (io.vec && with_sums) ? ar.take<double>((size_t)nb * L * nt) : nullptr;
-        double* zwork = ar.take<double>((size_t)2 * nb * Np);
-        const long long bstride = tiles_per * GP_TSQ;
-        const long long inv_bs = (long long)nt * GP_TSQ;
-        TRef M = lower_ref(tiles, bstride);
-
-        GramArgs ga{};
-        ga.X = io.X; ga.T = c->dT; ga.p = io.p; ga.s0 = s0;
-        ga.n = n; ga.nX = io.nX; ga.nU = io.nU; ga.nt = nt; ga.M = M; ga.part = part;
-        ga.with_sums = with_sums ? 1 : 0;
-#ifdef GPSLC_DIAG
-        static const int gram_dbg = diag_env("GPSLC_GRAM_DBG", 0);
-        static bool gram_dbg_done = false;
-        DevBuf gdbg;
-        if (gram_dbg && !gram_dbg_done) {
-            const size_t words = (size_t)8 * nb * (nt * (nt + 1) / 2);
-            gdbg.alloc(words * 8);
-            HC(hipMemset(gdbg.p, 0, words * 8));
-            ga.dbg = gdbg.as<unsigned long long>();
-        }
-#endif
-        ga.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
-        ga.binary_t = (c->binary_t && io.nU == c->nU && io.nX == c->nX && io.Y == c->dY) ? 1 : 0;   // ctx data only
-        launch_gram(ga, nb, st);
-#ifdef GPSLC_DIAG
-        if (ga.dbg) {      // GPSLC_GRAM_DBG: dump the first launch's per-workgroup stamps
-            HC(hipStreamSynchronize(st));
-            const size_t words = (size_t)8 * nb * (nt * (nt + 1) / 2);
-            std::vector<unsigned long long> h(words);
-            HC(hipMemcpy(h.data(), ga.dbg, words * 8, hipMemcpyDeviceToHost));
-            FILE* f = fopen("gpurun_out/gram_dbg.bin", "wb");
-            if (f) { fwrite(h.data(), 8, words, f); fclose(f); }
-            gram_dbg_done = true;
-        }
-#endif
-
-        RhsArgs ra{};
-        ra.T = c->dT; ra.Y = io.Y; ra.y_sstride = io.y_sstride; ra.tyLS = io.p.tyLS; ra.doT = io.doT; ra.s0 = s0;
-        // vector levels: rhs_tiles writes zeros into the level rows and rhs_prepare no level sums (L = 0 here); launch_vec_sums
-        // fills both below
-        ra.n = n; ra.nt = nt; ra.naug = naug; ra.L = (with_sums && !io.vec) ? L : 0; ra.with_sums = with_sums ? 1 : 0;
-        ra.part = part; ra.bsum = bsum; ra.ksum = ksum; ra.sumdelta = sumdelta; ra.M = M;
-        static const int epi_rows_on = diag_env("GPSLC_EPI_ROWS", 1);      // measurement switch (A/B of the extra tile update)
-        const bool epi_rows = (naug == 1) && epi_rows_on;
-        {
-            const int live = (with_sums ? L : 0) + 1;                         // right-hand sides: Y and one c_l per level
-            ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
-        }
-        launch_rhs(ra, nb, st);
-        VecArgs va{};
-        if (io.vec) {
-            va.X = io.X; va.T = c->dT; va.p = io.p; va.s0 = s0;
-            va.n = n; va.nX = io.nX; va.nU = io.nU; va.nt = nt; va.L = L; va.doT = io.doT;
-            va.M = M; va.part = vpart; va.sumdelta = sumdelta;
-            va.Y = io.Y; va.y_sstride = io.y_sstride;
-            if (with_sums) launch_vec_sums(va, nb, st);
-        }
-
-        // NB: the MeanITE pass takes K alpha as Y - yNoise alpha (k_solve.hip, ite_mean_kernel): it relies on alpha solving
-        // EXACTLY (K_gram + yNoise I) alpha = Y.  Any future jitter, robust fallback or different right-hand side in this
-        // factorisation must be reflected there (tests: test_mean_ite_tiny_noise_and_near_coincident_levels).
-        const bool back_done = potrf_tiles(c, M, nt, ntot, inv, inv_bs, io.info + s0, 0, nb, st, (with_sums ? L : 0) + 1, 0, false, 1,
-                                           epi_rows, /*tasks=*/true, want_mean ? zwork + (long long)nb * Np : nullptr);
-
-        EpiArgs ea{};
-        ea.M = M; ea.n = n; ea.nt = nt; ea.naug = naug; ea.L = with_sums ? L : 0; ea.s0 = s0; ea.S = io.S;
-        ea.sumdelta = sumdelta; ea.pred_noise = io.pred_noise;
-        ea.meanSATE = io.meanSATE; ea.varSATE = io.varSATE; ea.logdet = io.logdet; ea.quad = io.quad;
-        ea.from_rows = epi_rows ? 1 : 0;
-        launch_epilogue(ea, nb, st);
-
-        if (io.ndraw) {
-            // one draw from N(0, A_s) per parameter set with the caller's normals: L_s z_s on the factor just computed —
-            // Gen's mvnormal(zeros(n), cov) of an elliptical slice's auxiliary vector (src/inference.jl:225-232) and of the
-            // :logitT prior draw (src/model_likelihood.jl:25-33) — the predictive-draw kernel streaming L once
-            double* zt = ar.take<double>((size_t)nb * 16 * Np);
-            DrawArgs dr{};
-            dr.Lc = M; dr.n = n; dr.nt = nt; dr.s0 = s0; dr.S = io.S; dr.l = 0; dr.lc = 1; dr.L = 1; dr.spp = 1;
-            dr.mean = io.nzero; dr.z = io.nz; dr.zt = zt; dr.out = io.ndraw;
-            dr.obase = (long long)n * s0; dr.osb = n; dr.osl = 0; dr.osi = 1; dr.osd = n;
-            launch_draws(dr, nb, st);
-        }
-
-        if (want_mean) {
-            BackArgs ba{};
-            ba.M = M; ba.inv = inv; ba.inv_bstride = inv_bs; ba.nt = nt; ba.naug = naug; ba.zwork = zwork;
-            if (!back_done) launch_backsolve(ba, nb, st);
-            const double* alpha = zwork + (long long)nb * Np;
-            if (io.vec) {
-                va.alpha = alpha;
-                if (meanITE) {
-                    va.meanITE = meanITE; va.si = 1; va.ss = n; va.sl = (long long)n * io.S;
-                    launch_vec_mean(va, nb, st);
-                }
-                if (io.MeanITEs) {   // reference layout S x n (single level)
-                    va.meanITE = io.MeanITEs; va.si = io.S; va.ss = 1; va.sl = 0;
-                    launch_vec_mean(va, nb, st);
-                }
-            }
-            IteMeanArgs ia{};
-            ia.X = io.X; ia.T = c->dT; ia.p = io.p; ia.s0 = s0; ia.S = io.S;
-            ia.n = n; ia.nX = io.nX; ia.nU = io.nU; ia.nt = nt; ia.L = L; ia.doT = io.doT; ia.alpha = alpha;
-            ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.p.yNoise;
-            ia.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
-            if (meanITE && !io.vec) {
-                ia.meanITE = meanITE; ia.si = 1; ia.ss = n; ia.sl = (long long)n * io.S;
-                launch_ite_mean(ia, nb, st);
-            }
-            if (io.MeanITEs && !io.vec) {   // reference layout S x n (single level)
-                ia.meanITE = io.MeanITEs; ia.si = io.S; ia.ss = 1; ia.sl = 0;
-                launch_ite_mean(ia, nb, st);
-            }
-        }
-
-        if (unitB) {
-            // Unit B batches over (posterior sample, level) PAIRS: a sub-batch is gs samples x lc levels (gs * lc <= Bb),
-            // batch element b = (sample b / lc, level l0 + b % lc).  Every pair has its own W / CovITE workspace; the
-            // factor of A and its inverted diagonal blocks are shared by a sample's levels (TRef::bdiv = lc) — the shape of
-            // predictCounterfactualEffects (src/prediction.jl:30-33): few samples, ~100 levels.
-            double* Wt = ar.take<double>((size_t)Bb * nt * nt * GP_TSQ);
-            double* Ct = ar.take<double>((size_t)Bb * nlow * GP_TSQ);
-            const int lc_max = std::min(L, Bb);                   // levels per sub-batch
-            const int gs_max = std::max(1, Bb / lc_max);          // samples per sub-batch
-            // draws: the library's own normals of one sub-batch (generated once per unit), and for a level sweep the
-            // staging buffer [sample][level][d][i] that is rearranged into the level-fastest tensor sample group by group
-            double* zgen = (want_draws && !io.z && !zimage) ? ar.take<double>((size_t)Bb * io.spp * n) : nullptr;
-            double* zt = zimage ? ar.take<double>((size_t)Bb * zimage_doubles) : nullptr;
-            double* dtmp = (want_draws && L > 1) ? ar.take<double>((size_t)gs_max * L * io.spp * n) : nullptr;
-            // failure codes of the CovITE factors, one per pair of a sub-batch (folded into io.info after each sub-batch)
-            int* pinfo = want_draws ? ar.take<int>((size_t)Bb) : nullptr;
-            const long long wbs = (long long)nt * nt * GP_TSQ, cbs = nlow * GP_TSQ;
-            for (int g0 = 0; g0 < nb; g0 += gs_max) {
-                const int gs = std::min(gs_max, nb - g0);
-                for (int l0 = 0; l0 < L; l0 += lc_max) {
-                    const int lc = std::min(lc_max, L - l0);
-                    const int ub = gs * lc;                           // (sample, level) pairs of this sub-batch
-                    TRef W = rect_ref(Wt, wbs, nt);
-                    TRef Cm = lower_ref(Ct, cbs);
-                    TRef Ls = lower_ref(tiles + (long long)g0 * bstride, bstride);
-                    Ls.bdiv = lc;
-                    DtArgs da{};
-                    da.X = io.X; da.T = c->dT; da.p = io.p; da.s0 = s0 + g0;
-                    da.n = n; da.nX = io.nX; da.nU = io.nU; da.nt = nt; da.doT = io.doT; da.l0 = l0; da.lc = lc;
-                    da.vec = io.vec ? 1 : 0;
-                    da.pred_noise = io.pred_noise; da.W = W; da.Cm = Cm;
-                    launch_dt_build(da, ub, st);
-                    // W <- D L^-T, left-looking over tile columns; the panel product with inv(L_kk)^T is applied by the
-                    // same work item that finishes the column update (the tile makes one HBM round trip, as in the
-                    // factorisation), column 0 has no update and takes the panel product alone
-                    TRef invref = TRef{inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
-                    invref.bdiv = lc;
-                    // Left-looking over the whole width (every column update in the strip kernel).  GPSLC_W_PANEL = w > 0
-                    // (measurement build) blocks it like the factorisation instead — left-looking inside panels of w tile
-                    // columns, one right-looking update of everything to the right of a panel on the quadrant kernel.
-                    // Measured in round 4 (profiles/r04_ab_experiments.md §7): w = 4 / 8 / 16 -> 354 / 360 / 363.5 units/s
-                    // against 363 unblocked: with a deep K loop the strip kernel is as fast as the quadrant kernel's
-                    // rectangle update plus the extra pass over W.  Not the default.
-                    static const int wpw_env = diag_env("GPSLC_W_PANEL", 0);
-                    const int wpw = wpw_env <= 0 ? nt : wpw_env;
-                    for (int k = 0; k < nt; ++k) {
-                        const int ka = (k / wpw) * wpw;
-                        const int kend = std::min(ka + wpw, nt);
-                        GemmArgs g{};
-                        g.A = W; g.C = W;
-                        g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1; g.nbatch = ub; g.ntiles = nt;
-                        // fused up to a K depth of w_fuse_maxk tiles (measurement switch; +0.7 % fused at every depth)
-                        static const int w_fuse_maxk = diag_env("GPSLC_FUSE_W_MAXK", 32);
-                        if (k - ka <= w_fuse_maxk && fuse_mode()) {      // k == ka: empty K range, the panel product alone (round 5)
-                            g.B = Ls; g.k0 = ka; g.k1 = k; g.accumulate = 1;
-                            g.fuse = 1; g.F = invref; g.fk = k;
-                            gemm(c, g, st, 3);
-                        } else {
-                            if (k > ka) {
-                                g.B = Ls; g.k0 = ka; g.k1 = k; g.accumulate = 1;
-                                gemm(c, g, st, 3);
-                            }
-                            g.B = invref; g.k0 = k; g.k1 = k + 1; g.accumulate = 0;
-                            gemm(c, g, st, 3);
-                        }
-                        if (k == kend - 1 && kend < nt) {      // the panel is solved: update everything to its right
-                            GemmArgs t{};
-                            t.A = W; t.B = Ls; t.C = W;
-                            t.shape = 1; t.i0 = 0; t.j0 = kend; t.mi = nt; t.mj = nt - kend;
-                            t.k0 = ka; t.k1 = kend; t.accumulate = 1; t.nbatch = ub; t.ntiles = t.mi * t.mj;
-                            gemm(c, t, st, 3);
-                        }
-                    }
-                    {   // CovITE (+ jitter) = Delta - W W^T, lower tiles
-                        GemmArgs g{};
-                        g.A = W; g.B = W; g.C = Cm;
-                        g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt; g.sym = sym_mode();
-                        g.k0 = 0; g.k1 = nt; g.accumulate = 1; g.nbatch = ub; g.ntiles = (int)nlow;
-                        g.order = tri_order(c, nt);
-                        gemm(c, g, st, 3);
-                    }
-                    if (want_cov) {       // ITEDistributions: single level (lc == 1)
-                        GatherCovArgs gc{};
-                        gc.Cm = Cm; gc.n = n; gc.nt = nt; gc.s0 = s0 + g0; gc.S = io.S; gc.out = io.CovITEs;
-                        launch_gather_cov(gc, ub, st);
-                    }
-                    if (want_draws) {
-                        // one failure code per pair, then per sample the code of its lowest-index failing level (the
-                        // reference's loop order, src/prediction.jl:30-33): a shared word per sample would let the lc levels
-                        // of a diagonal launch race, and the lowest failing tile column win across launches
-                        HC(hipMemsetAsync(pinfo, 0, sizeof(int) * ub, st));
-                        potrf_tiles(c, Cm, nt, nt, nullptr, 0, pinfo, n, ub, st, 0, 3, /*robust=*/true, /*info_div=*/1);
-                        launch_fold_pair_info(pinfo, io.info + s0 + g0, gs, lc, st);
-                        DrawArgs dr{};
-                        dr.Lc = Cm; dr.n = n; dr.nt = nt; dr.s0 = s0 + g0; dr.S = io.S; dr.l = l0; dr.lc = lc; dr.L = L;
-                        dr.spp = io.spp; dr.mean = meanITE; dr.z = io.z; dr.zgen = zgen; dr.zt = zt; dr.seed = io.seed;
-                        {
-                            const int64_t eS = io.ens_S > 0 ? io.ens_S : c->ens_S, eo = io.ens_S > 0 ? io.ens_off : c->ens_off;
-                            dr.rs0 = dr.s0 + (eS > 0 ? eo : 0); dr.rS = eS > 0 ? eS : io.S;
-                        }
-                        if (L == 1) {     // the reference tensor directly: n x (S*spp), instance fastest
-                            dr.out = io.ite_draws;
-                            dr.obase = (long long)n * io.spp * (s0 + g0); dr.osb = (long long)n * io.spp; dr.osl = 0;
-                            dr.osi = 1; dr.osd = n;
-                        } else {          // staging [sample][level][d][i]
-                            dr.out = dtmp;
-                            dr.obase = (long long)l0 * io.spp * n; dr.osb = (long long)L * io.spp * n;
-                            dr.osl = (long long)io.spp * n; dr.osi = 1; dr.osd = n;
-                        }
-                        ProfScope ps(c, 2, (double)ub * io.spp, st);     // unit C: work = draws
-                        launch_draws(dr, ub, st);
-                    }
-                }
-                if (want_draws && L > 1)
-                    launch_draws_scatter(dtmp, io.ite_draws, n, L, io.spp, s0 + g0, gs, st);
-            }
-        }
+        Chunk ch{&c->slots[chunk % c->nstreams], s0, (int)std::min<int64_t>(Bt, io.S - s0)};
+        ch.s->arena.reset();
+        carve_chunk(sh, io, Bb, &ch);
+        const bool back_done = unit_a(c, io, sh, ch);
+        if (sh.want_mean) mean_ite(c, io, sh, ch, back_done);
+        if (sh.unitB) unit_b(c, io, sh, ch);
     }
-    for (auto st : c->streams) HC(hipStreamSynchronize(st));
+    for (auto& s : c->slots) HC(hipStreamSynchronize(s.st));
     HC(hipGetLastError());
     check_task_timeout(c);
     if (c->flags & GPSLC_FLAG_PROFILE) prof_collect(c);
@@ -1208,7 +1204,7 @@ void copy_out_large(gpslc_ctx* c, void* dst, const void* src_dev, size_t bytes) 
             }
             c->bounce[i] = static_cast<char*>(p);
         }
-    hipStream_t st = c->streams[0];
+    hipStream_t st = c->slots[0].st;
     const size_t nchunk = (bytes + kBounceBytes - 1) / kBounceBytes;
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     const unsigned nthr = std::min(8u, hw);
@@ -1260,7 +1256,7 @@ void copy_out_rows(gpslc_ctx* c, void* dst, size_t dpitch, const void* src_dev, 
             }
     }
     if (plain) { HC(hipMemcpy2D(dst, dpitch, src_dev, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost)); return; }
-    hipStream_t st = c->streams[0];
+    hipStream_t st = c->slots[0].st;
     const size_t nchunk = (bytes + kBounceBytes - 1) / kBounceBytes;
     const unsigned nthr = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
     auto chunk_bytes = [&](size_t k) { return std::min(kBounceBytes, bytes - k * kBounceBytes); };
@@ -1358,7 +1354,7 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
     static const int want_stamps = diag_env("GPSLC_SMALL_STAMPS", 0);
     if (want_stamps) a.stamps = a.out + 4 * (size_t)count;
 #endif
-    hipStream_t st = c->streams[0];
+    hipStream_t st = c->slots[0].st;
     if (in_lds) launch_small_gp(a, count, nF_max, st);
     else launch_mid_gp(a, count, nF_max, st);
     HC(hipGetLastError());
@@ -1441,10 +1437,11 @@ int gpslc_destroy(gpslc_ctx* c) {
     if (!c) return GPSLC_OK;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (auto s : c->streams) (void)hipStreamDestroy(s);
-    for (auto& a : c->arenas) if (a.base) (void)hipFree(a.base);
-    for (int* q : c->queues) if (q) (void)hipFree(q);
-    for (int* q : c->task_sync) if (q) (void)hipFree(q);
+    for (auto& s : c->slots) {
+        if (s.st) (void)hipStreamDestroy(s.st);
+        (void)hipFree(s.arena.base); (void)hipFree(s.queue); (void)hipFree(s.sync);     // hipFree(nullptr) is a no-op
+    }
+    if (c->task_timeout) (void)hipFree(c->task_timeout);
     for (auto& t : c->task_lists) if (t.dev) (void)hipFree(t.dev);
     if (c->scratch.base) (void)hipFree(c->scratch.base);
     c->io.release();
@@ -1543,9 +1540,9 @@ int gpslc_rbf_log_dev(gpslc_ctx* c, const double* X1, const double* X2, int64_t 
     if (rc) return rc;
     return guarded(c, [&]() {
         ensure_streams(c);
-        launch_rbf_log(X1, X2, n, d, ls, ls_len, out, c->streams[0]);
+        launch_rbf_log(X1, X2, n, d, ls, ls_len, out, c->slots[0].st);
         HC(hipGetLastError());
-        HC(hipStreamSynchronize(c->streams[0]));
+        HC(hipStreamSynchronize(c->slots[0].st));
         return GPSLC_OK;
     });
 }
@@ -1561,9 +1558,9 @@ int gpslc_rbf_log(gpslc_ctx* c, const double* X1, const double* X2, int64_t n, i
         double* dB = up(c, X2, (size_t)n * d);
         double* dl = up(c, ls, (size_t)ls_len);
         double* o = c->io.take<double>((size_t)n * n);
-        launch_rbf_log(dA, dB, n, d, dl, ls_len, o, c->streams[0]);
+        launch_rbf_log(dA, dB, n, d, dl, ls_len, o, c->slots[0].st);
         HC(hipGetLastError());
-        HC(hipStreamSynchronize(c->streams[0]));
+        HC(hipStreamSynchronize(c->slots[0].st));
         copy_out_large(c, out, o, sizeof(double) * (size_t)n * n);
         return GPSLC_OK;
     });
@@ -1576,9 +1573,9 @@ int gpslc_process_cov_dev(gpslc_ctx* c, const double* logcov, int64_t n, double 
     if (!out) return bad_arg(c, 6, "out is NULL");
     return guarded(c, [&]() {
         ensure_streams(c);
-        launch_process_cov(logcov, n, scale, noise, out, c->streams[0]);
+        launch_process_cov(logcov, n, scale, noise, out, c->slots[0].st);
         HC(hipGetLastError());
-        HC(hipStreamSynchronize(c->streams[0]));
+        HC(hipStreamSynchronize(c->slots[0].st));
         return GPSLC_OK;
     });
 }
@@ -1593,9 +1590,9 @@ int gpslc_process_cov(gpslc_ctx* c, const double* logcov, int64_t n, double scal
         c->io.reset();
         double* dA = up(c, logcov, (size_t)n * n);
         double* o = c->io.take<double>((size_t)n * n);
-        launch_process_cov(dA, n, scale, noise, o, c->streams[0]);
+        launch_process_cov(dA, n, scale, noise, o, c->slots[0].st);
         HC(hipGetLastError());
-        HC(hipStreamSynchronize(c->streams[0]));
+        HC(hipStreamSynchronize(c->slots[0].st));
         copy_out_large(c, out, o, sizeof(double) * (size_t)n * n);
         return GPSLC_OK;
     });
@@ -1975,8 +1972,8 @@ static int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* 
         ensure_streams(c);
         ddraw = c->io.take<double>(n * (size_t)S);
         double* zero_mean = c->io.take<double>(n * (size_t)S);
-        HC(hipMemsetAsync(zero_mean, 0, n * (size_t)S * sizeof(double), c->streams[0]));
-        HC(hipStreamSynchronize(c->streams[0]));
+        HC(hipMemsetAsync(zero_mean, 0, n * (size_t)S * sizeof(double), c->slots[0].st));
+        HC(hipStreamSynchronize(c->slots[0].st));
         io.nz = dtg; io.nzero = zero_mean; io.ndraw = ddraw;
     }
     run_predict(c, io);
@@ -2126,7 +2123,8 @@ static void mvn_factor_tiles(gpslc_ctx* c, const double* dcov) {
     ensure_streams(c);
     const int nt = c->nt;
     const long long nlow = (long long)nt * (nt + 1) / 2;
-    hipStream_t st = c->streams[0];
+    StreamSlot& slot = c->slots[0];
+    hipStream_t st = slot.st;
     c->mvn_tiles_gen = 0;
     if (!c->mvn_tiles) HC(hipMalloc((void**)&c->mvn_tiles, (size_t)nlow * GP_TSQ * 8));
     DevBuf old, oq, info;
@@ -2134,7 +2132,7 @@ static void mvn_factor_tiles(gpslc_ctx* c, const double* dcov) {
     HC(hipMemsetAsync(info.p, 0, sizeof(int), st));
     TRef M = lower_ref(c->mvn_tiles, nlow * GP_TSQ);
     launch_dense_load(DenseLoadArgs{dcov, (int)c->n, nt, M}, st);
-    potrf_tiles(c, M, nt, nt, nullptr, 0, info.as<int>(), 0, 1, st, 0, 0, /*robust=*/true);
+    factor_robust(c, slot, M, nt, info.as<int>(), 0, 1, 0);
     launch_quad_rows(QuadRowsArgs{M, (int)c->n, nt, 0, 0, old.as<double>(), oq.as<double>()}, st);
     HC(hipStreamSynchronize(st));
     HC(hipGetLastError());
@@ -2211,7 +2209,8 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
         ensure_streams(c);
         const int n = (int)c->n, nt = c->nt;
         const long long nlow = (long long)nt * (nt + 1) / 2;
-        hipStream_t st = c->streams[0];
+        StreamSlot& slot = c->slots[0];
+        hipStream_t st = slot.st;
         if (cov) mvn_cache(c, cov, false);   // factor once, keep L in the context
         else mvn_tiles_current(c);
         c->last_info.assign((size_t)S, c->mvn_info);
@@ -2239,7 +2238,7 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
                 u.shape = 1; u.i0 = 0; u.j0 = k + 1; u.mi = naug; u.mj = nt - k - 1;
                 u.k0 = k; u.k1 = k + 1; u.accumulate = 1; u.nbatch = 1; u.ntiles = naug * (nt - k - 1);
                 u.short_row0 = 0; u.short_rows = short_rows;
-                gemm(c, u, st);
+                gemm(c, u, slot, 0);
             }
         }
         launch_row_norms(RowNormArgs{W, nt, naug, S, oq}, st);
@@ -2290,7 +2289,7 @@ int gpslc_mvn_draw(gpslc_ctx* c, int64_t S, const double* cov, const double* cov
         }
         // tiled: L z on the predictive-draw kernel (every unit streams the ONE cached factor: batch stride 0), scaled on the host
         ensure_streams(c);
-        hipStream_t st = c->streams[0];
+        hipStream_t st = c->slots[0].st;
         const int nt = c->nt;
         const long long Np = (long long)nt * GP_TS;
         c->io.reset();
@@ -2324,7 +2323,8 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
     const double ty = tyLS, ysc = yScale, yno = yNoise;
     return guarded(c, [&]() {
         ensure_streams(c);
-        hipStream_t st = c->streams[0];
+        StreamSlot& slot = c->slots[0];
+        hipStream_t st = slot.st;
         const int n = (int)c->n, nt = c->nt;
         const long long nlow = (long long)nt * (nt + 1) / 2, nsq = (long long)nt * nt;
         DevBuf bU, buy, bxy, bty, bys, byn, bdo, info, tiles, inv, part, rect, outb;
@@ -2351,7 +2351,7 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
         ga.X = c->dX; ga.T = c->dT; ga.p = sp; ga.s0 = 0; ga.n = n; ga.nX = c->nX; ga.nU = c->nU; ga.nt = nt;
         ga.M = M; ga.part = nullptr; ga.with_sums = 0; ga.f32 = 0;
         launch_gram(ga, 1, st);
-        potrf_tiles(c, M, nt, nt, inv.as<double>(), (long long)nt * GP_TSQ, info.as<int>(), 0, 1, st);
+        factor_panels(c, slot, M, nt, nt, inv.as<double>(), (long long)nt * GP_TSQ, info.as<int>(), 0, 1, 0, false, 0);
         LdBuildArgs la{c->dX, c->dT, sp, 0, n, c->nX, c->nU, nt, doT, Kt, Kst, KsTt, Ksst};
         if (doTv) la.doTv = up(bdo, doTv, (size_t)n);
         launch_ld_build(la, st);
@@ -2376,13 +2376,13 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
                         g.A = *Wp; g.B = M; g.C = *Wp;
                         g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1;
                         g.k0 = 0; g.k1 = k; g.accumulate = 1; g.nbatch = 1; g.ntiles = nt;
-                        gemm(c, g, st);
+                        gemm(c, g, slot, 0);
                     }
                     GemmArgs g{};
                     g.A = *Wp; g.B = invref; g.C = *Wp;
                     g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1;
                     g.k0 = k; g.k1 = k + 1; g.accumulate = 0; g.nbatch = 1; g.ntiles = nt;
-                    gemm(c, g, st);
+                    gemm(c, g, slot, 0);
                 }
             }
             // C11 = K - W1 W1', C12 = Ks - W1 W2', C21 = Ks' - W2 W1', C22 = Kss - W2 W2'   (src/likelihood.jl:46-49)
@@ -2392,7 +2392,7 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
                 g.A = Wa; g.B = Wb; g.C = Cm;
                 g.shape = 1; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt;
                 g.k0 = 0; g.k1 = nt; g.accumulate = 1; g.nbatch = 1; g.ntiles = nt * nt;
-                gemm(c, g, st);
+                gemm(c, g, slot, 0);
                 emit(Cm, host, 0.0);
             };
             block(Kt, W1, W1, CovC11);      // K, Ks, Ks', Kss are consumed in place: emitted above already
@@ -2439,8 +2439,8 @@ static int summarize_impl(gpslc_ctx* c, const double* dx, int64_t n, int64_t m, 
     while (mpad < m && mpad < 16384) mpad <<= 1;      // (longer rows: radix select, no image)
     const double lowerQ = (1.0 - ci) / 2.0;          // src/driver.jl:130-131
     const double upperQ = 1.0 - lowerQ;
-    launch_summarize(SummArgs{dx, rs, cs, (int)n, (int)m, mpad, lowerQ, upperQ, dmean, dlo, dhi}, c->streams[0]);
-    HC(hipStreamSynchronize(c->streams[0]));
+    launch_summarize(SummArgs{dx, rs, cs, (int)n, (int)m, mpad, lowerQ, upperQ, dmean, dlo, dhi}, c->slots[0].st);
+    HC(hipStreamSynchronize(c->slots[0].st));
     HC(hipGetLastError());
     return GPSLC_OK;
 }

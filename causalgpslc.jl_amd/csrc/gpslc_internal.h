@@ -147,9 +147,10 @@ struct PotrfTaskArgs {
     GemmArgs g;             // A = B = C = the tile matrix, F = the inverted diagonal blocks, k0 = 0, short_row0 = nt, short_rows,
                             // sym = 3 with an augmented row riding along, info / info_base, nbatch
     const unsigned* list;   // TASK_LIST_HDR header words, then the descriptors of the eight queues
-    int* sync;              // TASK_SYNC_HDR + TASK_SYNC_STRIDE * nbatch ints: the launcher's caller zeroes all of them when it allocates
-                            // the buffer and all but the time-out word [8] before every launch; [8] is read and cleared once per
-                            // call, after every chunk has drained (check_task_timeout), so that no later chunk can wipe a time-out
+    int* sync;              // TASK_SYNC_HDR + TASK_SYNC_STRIDE * nbatch ints (ticket heads, progress words), all zeroed before every
+                            // launch by the launcher's caller
+    int* timeout;           // set by a poll that exceeds its bound; one word per context, outside `sync`, so that no later launch
+                            // can wipe it: read and cleared once per call, after every chunk has drained (check_task_timeout)
     int nt;
     double* alpha;          // non-null: the list ends every matrix with its back-substitution, alpha = L^-T z -> alpha[b][nt 128]
     int fence_mode;         // measurement build only (0 = release / acquire as documented)
@@ -165,7 +166,7 @@ void launch_diag(const TRef& M, int k, double* inv, long long inv_bstride, int* 
                  int info_base, int nbatch, hipStream_t st);
 void launch_gram(const GramArgs& g, int nbatch, hipStream_t st);
 // substitution-based (backward-stable) diagonal-tile factorisation and panel solve for near-singular matrices (k_robust.hip)
-void launch_diag_robust(const TRef& M, int k, int* info, int info_base, int nbatch, hipStream_t st, int info_div = 1);
+void launch_diag_robust(const TRef& M, int k, int* info, int info_base, int nbatch, hipStream_t st);
 void launch_trsm_robust(const TRef& X, const TRef& L, int k, int i0, int count, int nbatch, hipStream_t st);
 // info[g] (if still 0) <- the first nonzero of pair_info[g*lc .. g*lc + lc - 1], g < gs (k_robust.hip)
 void launch_fold_pair_info(const int* pair_info, int* info, int gs, int lc, hipStream_t st);
@@ -188,7 +189,7 @@ struct EpiArgs {
     double* meanSATE; double* varSATE;   // S x L or null
     double* logdet; double* quad;        // S or null
     int from_rows;   // 1 (single augmented tile row): z.z, z.w_l, w_l.w_l are summed from the rows of R themselves — the
-                     // augmented diagonal tile is then never updated (potrf_tiles(..., skip_aug_diag))
+                     // augmented diagonal tile is then never updated (factor_panels(..., skip_aug_diag))
 };
 void launch_epilogue(const EpiArgs& e, int nbatch, hipStream_t st);
 

@@ -26,7 +26,7 @@
 #define RB_NSB (GP_TS / SB)       // 8 sub-block rows / columns per tile
 
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void diag_potrf_robust_kernel(TRef M, int k, int* info, int info_base, int info_div) {
+__global__ __launch_bounds__(256) void diag_potrf_robust_kernel(TRef M, int k, int* info, int info_base) {
     extern __shared__ __attribute__((aligned(16))) double P[];        // 36 packed blocks + [4 waves][16] broadcast lines
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // scalar: branches on it are scalar branches
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void diag_potrf_robust_kernel(TRef M, int k, i
         }
         __syncthreads();
     }
-    if (tid == 0 && bad != 0) atomicCAS(&info[b / info_div], 0, info_base + GP_TS * k + bad);   // info per posterior sample
+    if (tid == 0 && bad != 0) atomicCAS(&info[b], 0, info_base + GP_TS * k + bad);   // info per matrix
     // factor back to the tile: lower blocks, zeros in the strictly-upper sub-blocks
     for (int bi = 0; bi < RB_NSB; ++bi)
         for (int bj = 0; bj < RB_NSB; ++bj)
@@ -181,11 +181,11 @@ __global__ __launch_bounds__(256) void tile_trsm_robust_kernel(TRef X, TRef L, i
     }
 }
 
-void launch_diag_robust(const TRef& M, int k, int* info, int info_base, int nbatch, hipStream_t st, int info_div) {
+void launch_diag_robust(const TRef& M, int k, int* info, int info_base, int nbatch, hipStream_t st) {
     const int bytes = (36 * 256 + 4 * SB) * 8;
     static DeviceOnce once;
     lds_opt_in(once, (const void*)diag_potrf_robust_kernel, bytes);
-    hipLaunchKernelGGL(diag_potrf_robust_kernel, dim3(nbatch), dim3(256), bytes, st, M, k, info, info_base, info_div < 1 ? 1 : info_div);
+    hipLaunchKernelGGL(diag_potrf_robust_kernel, dim3(nbatch), dim3(256), bytes, st, M, k, info, info_base);
 }
 
 // X(i, k) <- X(i, k) L_kk^-T for the tiles i = i0 .. i0 + count - 1 of tile column k of X (X may be the factor's own
@@ -200,7 +200,7 @@ void launch_trsm_robust(const TRef& X, const TRef& L, int k, int i0, int count, 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Failure codes of a unit-B sub-batch (gs samples x lc levels, pair b = sample b / lc, level b % lc): the robust factor
-// writes one code per pair (info_div = 1); sample g keeps the code of its lowest-index failing level, unless it already
+// writes one code per pair; sample g keeps the code of its lowest-index failing level, unless it already
 // holds one (its A factorisation or an earlier level chunk, run before on the same stream).  src/prediction.jl:30-33
 // visits the levels in order and stops at the first PosDefException.
 __global__ __launch_bounds__(64) void fold_pair_info_kernel(const int* __restrict__ pair_info, int* __restrict__ info,

@@ -919,7 +919,7 @@ __global__ __launch_bounds__(256, 2) void potrf_tasks_kernel(PotrfTaskArgs a) {
         unsigned long long stf = 0;
         if (GP_DBG_ON(a)) stf = __builtin_amdgcn_s_memtime();
         if (tid == 0) {
-            int* const tmo = a.sync + 8;
+            int* const tmo = a.timeout;
             const unsigned d = s_next;
             if (d != TASK_NONE) {
                 const int nt = a.nt;

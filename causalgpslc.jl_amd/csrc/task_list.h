@@ -12,7 +12,7 @@
 
 #define TASK_NONE 0xFFFFFFFFu
 #define TASK_LIST_HDR 32          // words: [0, 8) first descriptor of queue x, [8, 16) descriptors of queue x
-#define TASK_SYNC_HDR 32          // ints: [0, 8) ticket heads, [8] time-out word, [9] tasks finished
+#define TASK_SYNC_HDR 32          // ints: [0, 8) ticket heads, [8] unused (the time-out word is PotrfTaskArgs::timeout), [9] tasks finished
 #define TASK_SYNC_STRIDE 40       // ints per matrix: [0] diagonal tiles finished, [1 + i] finished tiles of tile row i (i <= nt)
 #define TASK_MAX_NT 32
 // descriptor: bits 0..16 batch element, 17..18 (strips) number of consecutive tile rows of the column the task covers minus 1,
