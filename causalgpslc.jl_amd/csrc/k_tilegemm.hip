@@ -70,6 +70,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #define LROW 144                      // padded k-row (doubles)
 #define OPER_LDS (KS * LROW)          // doubles per operand per stage
 #define GEMM_LDS_BYTES (2 * 2 * OPER_LDS * 8)
+#define STRIP_LDS_BYTES (2 * OPER_LDS * 8)     // strip kernel: two stages of the B operand only
 #ifndef SYRK_PF
 #define SYRK_PF 2                      // staging depth (register sets = slabs in flight) of the diagonal-tile update loops
 #endif
@@ -401,13 +402,31 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
     }
 }
 
+// a pointer every lane of the wave holds the same value of, moved to scalar registers (the base of a buffer descriptor)
+typedef const __attribute__((address_space(1))) char* gcptr;      // global address space: never a flat_load
+__device__ __forceinline__ gcptr wave_uniform(const void* p) {
+    const unsigned long long x = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)x);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(x >> 32));
+    return (gcptr)(((unsigned long long)hi << 32) | lo);
+}
+// two consecutive rows of one column of an output tile, 16 bytes.  WT (task launch): write-through (sc1), the 16-byte form of
+// out_store<true> (MI355X_MICROARCH.md "inter-workgroup visibility", R1), through a buffer descriptor of the tile — an offset
+// beyond the tile would be dropped by the hardware; else non-temporal.
+typedef unsigned u4 __attribute__((ext_vector_type(4)));
+template <bool WT>
+__device__ __forceinline__ void strip_store2(__amdgpu_buffer_rsrc_t rs, double* tile_lane, int lane_bytes, int col_doubles, d2 v) {
+    if (WT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), rs, lane_bytes + col_doubles * 8, 0, /*sc1*/ 16);
+    else __builtin_nontemporal_store(v, reinterpret_cast<d2*>(tile_lane + col_doubles));
+}
+
 // ---------------------------------------------------------------------------------------
 // In-panel column update fused with the panel solve, STRIP layout (round 3).
 //     X = C(i,k) - sum_kk A(i,kk) B(k,kk)^T          (K loop, X stays in the accumulators)
 //     L(i,k) = X * inv(L_kk)^T                          (second phase, GemmArgs::F = the inverted diagonal blocks)
 // Wave w owns the 32-row strip [32 w, 32 w + 32) x ALL 128 columns of the tile: acc[m][n][v] =
-// X[32 w + 16 m + (lane & 15)][16 n + 4 v + (lane >> 4)] (2 x 8 accumulators, the same 128 registers as a 64 x 64
-// quadrant).  A lane's accumulator registers are exactly its k-operands of an MFMA over the columns of X, so the
+// X[32 w + 2 (lane & 15) + m][16 n + 4 v + (lane >> 4)] (2 x 8 accumulators, the same 128 registers as a 64 x 64
+// quadrant; the two 16-row blocks interleaved since round 7, see strip_item).  A lane's accumulator registers are exactly its k-operands of an MFMA over the columns of X, so the
 // second product needs nothing but the wave's own registers and the fragments of inv(L_kk) (L2-resident, shared by the
 // launch): 36 live 16 x 16 blocks of the lower-triangular inverse x 4 k-steps x 2 row blocks = 288 MFMAs on EVERY wave,
 // no LDS hand-over and no barrier.  (With 64 x 64 quadrants the product X(:, 0:64) inv(L)(64:128, 0:64)^T crossed from
@@ -425,10 +444,18 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
 // its column — the tile diag(tj) has already updated — instead of that tile being a work item of its own: all four waves load
 // its live rows, wave w computes the column blocks w and 7 - w.  Per output element the same MFMA chain as the stand-alone
 // item (ascending column block of X, then v): bit-identical.
+// Operands of the K loop (round 7).  Wave w multiplies rows [32 w, 32 w + 32) of A(i, kk) and nobody else reads them, so the A
+// operand never touches LDS: with the strip's two 16-row blocks INTERLEAVED — acc[m][n][v] of lane (li, lg) holds row
+// 32 w + 2 li + m, column 16 n + 4 v + lg — the lane's two A fragments of a k-step are two consecutive doubles of one tile
+// column, one 16-byte non-temporal load (16 lanes = 256 contiguous bytes) straight into the MFMA operand registers, requested
+// two slabs ahead.  LDS holds the B slabs only (shared by the four waves), double-buffered as before.  The same interleave
+// makes the C tile's loads and the L tile's stores 16-byte accesses.  Rows are independent in both phases, so every output
+// element keeps its MFMA chain and order: bit-identical to the 16 m + li layout.  Both operands' row strips are contiguous
+// runs of tiles ((i, k0) .. (i, k1 - 1) are consecutive in both TRef layouts): slab s is at base + s * KS * GP_TS doubles.
 template <int WD, bool AUGEP = false, bool WT = false>
 __device__ __forceinline__ void strip_item(const GemmArgs& g, const int b, const int ti, const int tj, const bool no_update,
-                                           const int nslab, double* lA, double* lB, const int tid, const int lane,
-                                           const int wave, const int li, const int lg, const int frow_a, const int frow_b,
+                                           const int nslab, double* lB, const int tid, const int lane,
+                                           const int wave, const int li, const int lg, const int frow_b,
                                            const int (&loff)[4], const long long item, const bool with_aug = false) {
     double* __restrict__ Ct = tref_tile(g.C, b, ti, tj);
     // augmented right-hand-side tiles hold `short_rows` live rows: a wave whose strip lies below them only helps
@@ -436,78 +463,117 @@ __device__ __forceinline__ void strip_item(const GemmArgs& g, const int b, const
     const bool live = !(g.short_rows > 0 && ti >= g.short_row0 && 32 * wave >= g.short_rows);
     unsigned long long st0 = 0, st1 = 0, st2 = 0;
     if (GP_DBG_ON(g)) st0 = __builtin_amdgcn_s_memtime();
+    const int lane_off = lg * GP_TS + 32 * wave + 2 * li;       // (row pair, column lg) of this lane inside a tile
 
     d4 acc[2][8];
     if (live) {
-        const double* __restrict__ Cl = Ct + (lg * GP_TS + 32 * wave + li);
+        const double* __restrict__ Cl = Ct + lane_off;
 #pragma unroll
         for (int n = 0; n < 8; ++n)
 #pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-                    acc[m][n][v] = __builtin_nontemporal_load(Cl + (16 * n + 4 * v) * GP_TS + 16 * m);
+            for (int v = 0; v < 4; ++v) {
+                const d2 c = __builtin_nontemporal_load(reinterpret_cast<const d2*>(Cl + (16 * n + 4 * v) * GP_TS));
+                acc[0][n][v] = c[0];
+                acc[1][n][v] = c[1];
+            }
     }
 
     if (nslab > 0 && !no_update) {
-        d2 ra[4], rb[4], ra2[4], rb2[4];
-        auto gload = [&](int s, d2 (&xa)[4], d2 (&xb)[4]) {
-            const int kk = g.k0 + (s >> 3);
-            const int so = (s & 7) * (KS * GP_TS);
-            const double* pa = tref_tile(g.A, b, ti, kk) + so;
-            const double* pb = tref_tile(g.B, b, tj, kk) + so;
+        constexpr int SLAB = KS * GP_TS * 8;       // bytes per slab and operand
+        // each operand's row strip as ONE buffer: scalar descriptor + scalar slab offset + a constant lane offset per load, no
+        // address arithmetic in the loop but one scalar add per slab; an offset beyond the strip would read zeros
+        const int nsl = __builtin_amdgcn_readfirstlane(nslab);
+        const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(unsigned long long)wave_uniform(tref_tile(g.A, b, ti, g.k0)), 0, nsl * SLAB, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(unsigned long long)wave_uniform(tref_tile(g.B, b, tj, g.k0)), 0, nsl * SLAB, 0x00020000);
+        int voa[4], vob[4];                        // lane offsets (bytes) of the four A fragments / B chunks of a slab
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                xa[u] = __builtin_nontemporal_load(reinterpret_cast<const d2*>(pa + (tid + 256 * u) * 2));
-                xb[u] = *reinterpret_cast<const d2*>(pb + (tid + 256 * u) * 2);
-            }
-        };
-        auto lstore = [&](int buf, const d2 (&xa)[4], const d2 (&xb)[4]) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                *reinterpret_cast<d2*>(lA + buf * OPER_LDS + loff[u]) = xa[u];
-                *reinterpret_cast<d2*>(lB + buf * OPER_LDS + loff[u]) = xb[u];
-            }
-        };
-        auto compute = [&](int buf) {
-            if (!live) return;
-            const double* pa = lA + buf * OPER_LDS + frow_a;
-            const double* pb = lB + buf * OPER_LDS + frow_b;
-#pragma unroll
-            for (int ks = 0; ks < KS / 4; ++ks) {
-                double af[2], bf[8];
-#pragma unroll
-                for (int m = 0; m < 2; ++m) af[m] = pa[ks * 4 * LROW + 16 * m];
-#pragma unroll
-                for (int n = 0; n < 8; ++n) bf[n] = pb[ks * 4 * LROW + 16 * n];
-#pragma unroll
-                for (int n = 0; n < 8; ++n)
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) acc[m][n] = mfma_step<1>(bf[n], af[m], acc[m][n]);
-            }
-        };
-        gload(0, ra, rb);
-        lstore(0, ra, rb);
-        gload(1, ra, rb);          // nslab is a multiple of 8
-        __syncthreads();
-        if (GP_DBG_ON(g)) st1 = __builtin_amdgcn_s_memtime();
-        for (int s = 0; s < nslab; s += 2) {
-            if (s + 2 < nslab) gload(s + 2, ra2, rb2);
-            compute(0);
-            lstore(1, ra, rb);
-            KLOOP_BARRIER;
-            if (s + 3 < nslab) gload(s + 3, ra, rb);
-            compute(1);
-            if (s + 2 < nslab) lstore(0, ra2, rb2);
-            KLOOP_BARRIER;
+        for (int u = 0; u < 4; ++u) {
+            voa[u] = (4 * u * GP_TS + lane_off) * 8;
+            vob[u] = (tid + 256 * u) * 16;
         }
+        const std::true_type yes;
+        const std::false_type no;
+        // the whole loop once per kind of wave (a wave below the live rows of an augmented tile stages B and meets the barriers,
+        // nothing else), so that neither copy has a branch inside a slab
+        auto kloop = [&](auto lv) {
+            constexpr bool LIVE = decltype(lv)::value;
+            d2 rb[4], rb2[4];      // B staging sets: loads run two slabs ahead of the MFMAs
+            d2 a0[4], a1[4];       // A fragments of the even / odd slabs: a k-step's register is re-requested as soon as it is used
+            auto bload1 = [&](int so, int u) { return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rB, vob[u], so, 0)); };
+            auto bload = [&](int so, d2 (&xb)[4]) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) xb[u] = bload1(so, u);
+            };
+            auto aload = [&](int so, int ks) {      // non-temporal: streamed once per launch
+                return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rA, voa[ks], so, /*nt*/ 2));
+            };
+            auto lstore = [&](int buf, const d2 (&xb)[4]) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) *reinterpret_cast<d2*>(lB + buf * OPER_LDS + loff[u]) = xb[u];
+            };
+            // one slab: 64 MFMAs.  PF: the slab two ahead exists — per k-step one A fragment and one B chunk of it are requested and
+            // one chunk of the staged B slab `wb` is deposited, each k-step's share behind its own 16 MFMAs.  (Placing them by hand
+            // between the MFMAs, fragments read one k-step ahead, measured the same: profiles/r07_ab_experiments.md §2.)
+            auto slab = [&](auto pf, int buf, d2 (&aa)[4], int so, d2 (&lb)[4], auto ws, int wbuf,
+                            const d2 (&wb)[4]) {
+                constexpr bool PF = decltype(pf)::value;
+                constexpr bool WS = decltype(ws)::value;
+                const double* pb = lB + buf * OPER_LDS + frow_b;
+#pragma unroll
+                for (int ks = 0; ks < KS / 4; ++ks) {
+                    if (LIVE) {
+                        double bf[8];
+#pragma unroll
+                        for (int n = 0; n < 8; ++n) bf[n] = pb[ks * 4 * LROW + 16 * n];
+                        const d2 a = aa[ks];
+#pragma unroll
+                        for (int n = 0; n < 8; ++n)
+#pragma unroll
+                            for (int m = 0; m < 2; ++m) acc[m][n] = mfma_step<1>(bf[n], a[m], acc[m][n]);
+                        if (PF) aa[ks] = aload(so, ks);
+                    }
+                    if (PF) lb[ks] = bload1(so, ks);
+                    if (WS) *reinterpret_cast<d2*>(lB + wbuf * OPER_LDS + loff[ks]) = wb[ks];
+                }
+            };
+            bload(0, rb);
+            if (LIVE) {
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) a0[ks] = aload(0, ks);
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) a1[ks] = aload(SLAB, ks);
+            }
+            lstore(0, rb);
+            bload(SLAB, rb);          // nslab is a multiple of 8
+            KLOOP_BARRIER;                 // LDS only: the slabs in flight stay in flight
+            if (GP_DBG_ON(g)) st1 = __builtin_amdgcn_s_memtime();
+            // unrolled by two, the staging sets swapping roles: rb holds slab s + 1 while slab s + 2 streams into rb2.  The last
+            // two slabs (nothing left to request) are peeled, so that the steady-state body is straight-line code.  The barrier
+            // that ends the last slab also protects the LDS buffers against the next work item's first lstore.
+            int so = 2 * SLAB;         // byte offset of the slab two ahead inside both strips
+            for (int s = 0; s + 2 < nsl; s += 2) {
+                slab(yes, 0, a0, so, rb2, yes, 1, rb);
+                KLOOP_BARRIER;
+                slab(yes, 1, a1, so + SLAB, rb, yes, 0, rb2);
+                KLOOP_BARRIER;
+                so += 2 * SLAB;
+            }
+            slab(no, 0, a0, 0, rb2, yes, 1, rb);
+            KLOOP_BARRIER;
+            slab(no, 1, a1, 0, rb, no, 0, rb2);
+            KLOOP_BARRIER;
+        };
+        if (live) kloop(yes); else kloop(no);
     }
     if (GP_DBG_ON(g)) st2 = __builtin_amdgcn_s_memtime();
 
     if (live) {
         // fragment (nc, n, v) of W = inv(L_kk): W[16 nc + li][16 n + 4 v + lg], element (c, c') at c' * 128 + c
         const double* __restrict__ Wl = tref_tile(g.F, b, 0, g.fk) + (lg * GP_TS + li);
-        double* __restrict__ Co = Ct + (lg * GP_TS + 32 * wave + li);
+        double* __restrict__ Co = Ct + lane_off;
+        const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc((void*)(unsigned long long)wave_uniform(Ct), 0, GP_TSQ * 8, 0x00020000);
         // the 144 live fragments in the order of use, WD groups (WD x 128 MFMA clocks) ahead through a register ring
         double wn[WD];
         int pc = 0, pn = 0, pv = 0;        // next fragment to request (compile-time after unrolling)
@@ -537,16 +603,10 @@ __device__ __forceinline__ void strip_item(const GemmArgs& g, const int b, const
                         st[1] = mfma_step<0>(w, acc[1][n][v], st[1]);
                     }
                 }
+            // task launch: write-through, so that the consumer workgroup needs no L2 write-back (out_store)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                if (WT) {       // task launch: write-through, so that the consumer workgroup needs no L2 write-back (out_store)
-                    out_store<true>(Co + (16 * nc + 4 * v) * GP_TS, st[0][v]);
-                    out_store<true>(Co + (16 * nc + 4 * v) * GP_TS + 16, st[1][v]);
-                } else {
-                    __builtin_nontemporal_store(st[0][v], Co + (16 * nc + 4 * v) * GP_TS);
-                    __builtin_nontemporal_store(st[1][v], Co + (16 * nc + 4 * v) * GP_TS + 16);
-                }
-            }
+            for (int v = 0; v < 4; ++v)
+                strip_store2<WT>(crs, Co, lane_off * 8, (16 * nc + 4 * v) * GP_TS, (d2){st[0][v], st[1][v]});
         }
     }
     if (AUGEP && with_aug) {
@@ -615,8 +675,7 @@ __global__ __launch_bounds__(256, 2) void tile_fused_strip_kernel(GemmArgs g) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
-    double* lA = smem;                       // [2][KS][LROW]
-    double* lB = smem + 2 * OPER_LDS;        // [2][KS][LROW]
+    double* lB = smem;                       // [2][KS][LROW]: the B slabs; the A operand goes from HBM to registers (strip_item)
 
     const long long W = (long long)g.ntiles * g.nbatch;
     const int G = gridDim.x;
@@ -626,7 +685,6 @@ __global__ __launch_bounds__(256, 2) void tile_fused_strip_kernel(GemmArgs g) {
     const long long x0 = xcd * wq + (xcd < wrm ? xcd : wrm);
     const long long xc = wq + (xcd < wrm ? 1 : 0);
 
-    const int frow_a = lg * LROW + 32 * wave + li;     // + 16 m
     const int frow_b = lg * LROW + li;                 // + 16 n
     int loff[4];
 #pragma unroll
@@ -652,7 +710,7 @@ __global__ __launch_bounds__(256, 2) void tile_fused_strip_kernel(GemmArgs g) {
         if (g.sym >= 2 && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) break;   // tile_syrk_diag_kernel's
         // sym == 3: the augmented tile was already updated (it rode with the diagonal item); panel product only
         const bool no_update = g.sym == 3 && g.short_rows > 0 && ti >= g.short_row0 && tj < g.short_row0;
-        strip_item<WD>(g, b, ti, tj, no_update, nslab, lA, lB, tid, lane, wave, li, lg, frow_a, frow_b, loff, item);
+        strip_item<WD>(g, b, ti, tj, no_update, nslab, lB, tid, lane, wave, li, lg, frow_b, loff, item);
         } while (0);
         if (g.queue) {
             if (tid == 0) s_ticket = ticket;
@@ -1010,13 +1068,12 @@ __global__ __launch_bounds__(256, 2) void potrf_tasks_kernel(PotrfTaskArgs a) {
             // `rows` consecutive tiles of the column, one after the other: they stream the same B panel, and the task's fetch,
             // acquire and release are paid once
             if (diag_then_strip)
-                strip_item<FUSE_WD, (MT > 0), WT>(gl, b, k + 1, k, false, 8 * k, smem, smem + 2 * OPER_LDS, tid, lane, wave, li, lg,
-                                              lg * LROW + 32 * wave + li, lg * LROW + li, loff, 0, true);
+                strip_item<FUSE_WD, (MT > 0), WT>(gl, b, k + 1, k, false, 8 * k, smem, tid, lane, wave, li, lg, lg * LROW + li, loff, 0,
+                                              true);
             else
                 for (int r = 0; r < rows; ++r)
-                    strip_item<FUSE_WD, (MT > 0), WT>(gl, b, i + r, k, /*no_update=*/MT > 0 && i >= a.nt, 8 * k, smem, smem + 2 * OPER_LDS, tid,
-                                                  lane, wave, li, lg, lg * LROW + 32 * wave + li, lg * LROW + li, loff, 0,
-                                                  with_aug && r == 0);
+                    strip_item<FUSE_WD, (MT > 0), WT>(gl, b, i + r, k, /*no_update=*/MT > 0 && i >= a.nt, 8 * k, smem, tid, lane, wave, li, lg,
+                                                  lg * LROW + li, loff, 0, with_aug && r == 0);
         }
         // publish: every wave's stores have left the CU, then one lane releases and moves the matrix's progress word(s)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1297,8 +1354,8 @@ void launch_tile_gemm(const GemmArgs& g, hipStream_t st) {
 #endif
     if (g.fuse && g.accumulate) {
         static DeviceOnce once;
-        lds_opt_in(once, (const void*)tile_fused_strip_kernel<FUSE_WD>, GEMM_LDS_BYTES);
-        hipLaunchKernelGGL((tile_fused_strip_kernel<FUSE_WD>), dim3(grid), dim3(256), GEMM_LDS_BYTES, st, g);
+        lds_opt_in(once, (const void*)tile_fused_strip_kernel<FUSE_WD>, STRIP_LDS_BYTES);
+        hipLaunchKernelGGL((tile_fused_strip_kernel<FUSE_WD>), dim3(grid), dim3(256), STRIP_LDS_BYTES, st, g);
     } else {
         if (g.accumulate) launch_one<1, 0>(g, grid, st); else launch_one<0, 0>(g, grid, st);
     }
