@@ -56,6 +56,18 @@ def _intervention(doT, n):
     raise ValueError(f"doT must be a scalar or a vector of length n = {n}, got an array of shape {a.shape}")
 
 
+def _baseline(baseline, L):
+    """The ``baseline=`` of a contrast (gpslc_predict_contrast) for L scalar levels -> (L,) float64: a scalar (Bool -> 0/1)
+    is every level's baseline, a 1-D sequence gives each level its own.  Any other shape raises ValueError before anything
+    runs on a device."""
+    b = np.asarray(baseline, dtype=np.float64)
+    if b.ndim == 0:
+        return np.full(L, float(b))
+    if b.ndim == 1 and b.shape[0] == L:
+        return np.ascontiguousarray(b)
+    raise ValueError(f"baseline must be a scalar or one value per level (L = {L}), got an array of shape {b.shape}")
+
+
 class Context:
     """RAII wrapper of gpslc_ctx (one per GPU and data set)."""
 
@@ -362,13 +374,19 @@ def conditionalITE(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT):
     return M[0], Cv[0]
 
 
-def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True):
+def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=None):
     n, S = g.getN(), g.getNumPosteriorSamples()
     x, d = _intervention(doT, n)
+    if baseline is not None:
+        if d is not None:
+            raise ValueError("baseline= needs a scalar doT: contrasts of per-individual intervention vectors are not supported")
+        base = float(_baseline(baseline, 1)[0])
     ctx = g.ctx()
     M = np.empty((S, n), order="F")
     Cv = np.empty((S, n, n), order="F") if want_cov else None
-    if d is None:
+    if baseline is not None:
+        st = ctx.lib.gpslc_ite_distributions_contrast(ctx.h, S, *g._params(), x, base, float(pred_noise), _p(M), _p(Cv))
+    elif d is None:
         st = ctx.lib.gpslc_ite_distributions(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
     else:
         st = ctx.lib.gpslc_ite_distributions_vec(ctx.h, S, *g._params(), _p(d), float(pred_noise), _p(M), _p(Cv))
@@ -376,9 +394,10 @@ def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True):
     return M, Cv
 
 
-def ITEDistributions(g: GPSLCObject, doT):
-    """MeanITEs (S, n), CovITEs (S, n, n) incl. + I*predictionCovarianceNoise (src/estimation.jl:66-86)."""
-    return _ite_distributions(g, doT, g.hyperparams.predictionCovarianceNoise)
+def ITEDistributions(g: GPSLCObject, doT, baseline=None):
+    """MeanITEs (S, n), CovITEs (S, n, n) incl. + I*predictionCovarianceNoise (src/estimation.jl:66-86).  ``baseline`` = a
+    scalar b: the contrast f(doT) - f(b) of two scalar levels instead of f(doT) - f(T) (gpslc_ite_distributions_contrast)."""
+    return _ite_distributions(g, doT, g.hyperparams.predictionCovarianceNoise, baseline=baseline)
 
 
 def conditionalSATE(MeanITE, CovITE):
@@ -387,10 +406,10 @@ def conditionalSATE(MeanITE, CovITE):
     return float(np.sum(MeanITE) / n), float(np.sum(CovITE) / n ** 2)
 
 
-def SATEDistributions(g: GPSLCObject, doT):
+def SATEDistributions(g: GPSLCObject, doT, baseline=None):
     """MeanSATEs (S,), VarSATEs (S,) (src/estimation.jl:127-140) — O(N^2) per sample on the GPU,
-    without materialising CovITE."""
-    m, v, _ = predict(g, _levels(g, doT))
+    without materialising CovITE.  ``baseline`` = a scalar b: the contrast doT against b (see predict)."""
+    m, v, _ = predict(g, _levels(g, doT), baseline=baseline)
     return m[:, 0].copy(), v[:, 0].copy()
 
 
@@ -415,11 +434,14 @@ def _levels(g: GPSLCObject, doT):
 
 
 def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
-            want_draws=False, devices: Optional[Sequence[int]] = None):
+            want_draws=False, devices: Optional[Sequence[int]] = None, baseline=None):
     """The ensemble entry point (gpslc_predict): returns MeanSATE (S, L), VarSATE (S, L) and, when
     asked, MeanITE (n, S, L) / draws (L, n, S*spp).  ``doTs``: L scalar levels (1-D), or an (L, n) array of L per-individual
     intervention vectors (gpslc_predict_vec).  ``devices`` = a list of GPU indices shards the posterior samples
-    over one context per entry through ``gpslc_predict_multi`` (same results, bit for bit; scalar levels only)."""
+    over one context per entry through ``gpslc_predict_multi`` (same results, bit for bit; scalar levels only).
+    ``baseline`` = a scalar or L values b: level l becomes the contrast f(doTs[l]) - f(b[l]) between two scalar levels
+    (gpslc_predict_contrast: "treatment a against treatment b", with its own covariance and draws) instead of
+    f(doTs[l]) - f(T); ``None`` is the plain call.  Scalar levels and one GPU only."""
     n, S = g.getN(), g.getNumPosteriorSamples()
     doTs = np.asarray(doTs, dtype=np.float64)
     vec = doTs.ndim == 2
@@ -428,9 +450,14 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
                          f"got an array of shape {doTs.shape}")
     if vec and devices is not None:
         raise NotImplementedError("vector interventions are not sharded over devices: call predict without devices=")
+    if baseline is not None and vec:
+        raise ValueError("baseline= needs scalar levels: contrasts of per-individual intervention vectors are not supported")
+    if baseline is not None and devices is not None:
+        raise NotImplementedError("contrasts are not sharded over devices: call predict without devices=")
     # vector levels: n x L column-major, doT[i + n*l]
     doTs = np.asfortranarray(doTs.T) if vec else np.ascontiguousarray(np.atleast_1d(doTs))
     L = doTs.shape[1] if vec else doTs.shape[0]
+    base = None if baseline is None else _baseline(baseline, L)
     ctx = g.ctx() if devices is None else g.ctxs(devices)[0]
     ms = np.empty((S, L), order="F")
     vs = np.empty((S, L), order="F")
@@ -441,7 +468,11 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
         zz = _f(z)
         if zz.shape != (n, spp, S, L):
             raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
-    if devices is None:
+    if base is not None:
+        st = ctx.lib.gpslc_predict_contrast(ctx.h, S, *g._params(), L, _p(doTs), _p(base),
+                                            float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
+                                            _p(ms), _p(vs), _p(mi), _p(dr))
+    elif devices is None:
         fn = ctx.lib.gpslc_predict_vec if vec else ctx.lib.gpslc_predict
         st = fn(ctx.h, S, *g._params(), L, _p(doTs), float(g.hyperparams.predictionCovarianceNoise),
                 int(spp), int(seed), _p(zz), _p(ms), _p(vs), _p(mi), _p(dr))
@@ -457,16 +488,17 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
     return ms, vs, mi
 
 
-def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0):
+def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, baseline=None):
     """ITEsamples: n x (S*spp) draws, column order sample-outer / draw-inner (src/estimation.jl:95-109).
-    Called as ITEsamples(g, doT, spp): the factor of CovITE + jitter is computed once per sample on the GPU."""
+    Called as ITEsamples(g, doT, spp): the factor of CovITE + jitter is computed once per sample on the GPU.
+    ``baseline`` = a scalar b: draws of the contrast doT against b (see predict)."""
     g, doT = g_or_means, doT_or_covs
     zz = None
     if z is not None:   # z given in the reference's (n, S*spp) column order
         n, S = g.getN(), g.getNumPosteriorSamples()
         # column j*spp + d  ->  [i, d, j] under a column-major reshape
         zz = np.asarray(z, dtype=np.float64).reshape(n, nSamplesPerMixture, S, order="F")[:, :, :, None]
-    _, _, _, dr = predict(g, _levels(g, doT), spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True)
+    _, _, _, dr = predict(g, _levels(g, doT), spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True, baseline=baseline)
     return np.asfortranarray(dr[0])
 
 
@@ -474,14 +506,16 @@ def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0):
 # src/driver.jl, src/prediction.jl
 # ------------------------------------------------------------------------------------------
 
-def sampleITE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0):
-    """sampleITE(g, doT; samplesPerPosterior=10) -> n x (S*spp) (src/driver.jl:86-89)."""
-    return ITEsamples(g, doT, samplesPerPosterior, z=z, seed=seed)
+def sampleITE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None):
+    """sampleITE(g, doT; samplesPerPosterior=10) -> n x (S*spp) (src/driver.jl:86-89); ``baseline``: the contrast doT
+    against that scalar level."""
+    return ITEsamples(g, doT, samplesPerPosterior, z=z, seed=seed, baseline=baseline)
 
 
-def sampleSATE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0):
-    """sampleSATE(g, doT; samplesPerPosterior=10) -> (S*spp,) (src/driver.jl:108-111)."""
-    m, v = SATEDistributions(g, doT)
+def sampleSATE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None):
+    """sampleSATE(g, doT; samplesPerPosterior=10) -> (S*spp,) (src/driver.jl:108-111); ``baseline``: the contrast doT
+    against that scalar level."""
+    m, v = SATEDistributions(g, doT, baseline=baseline)
     return SATEsamples(m, v, samplesPerPosterior, z=z, seed=seed)
 
 

@@ -669,6 +669,7 @@ struct PredictIO {
     int L = 0;
     const double* doT = nullptr;
     bool vec = false;                // vector levels: doT is n x L (level l at doT + n*l), not L scalars
+    const double* base = nullptr;    // contrasts (device, L): level l is doT[l] against base[l] (scalar levels only)
     double pred_noise = 0;
     int spp = 0;
     uint64_t seed = 0;
@@ -849,6 +850,7 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     // fills both below
     ra.n = n; ra.nt = nt; ra.naug = sh.naug; ra.L = (sh.with_sums && !io.vec) ? sh.L : 0; ra.with_sums = sh.with_sums ? 1 : 0;
     ra.part = ch.part; ra.bsum = ch.bsum; ra.ksum = ch.ksum; ra.sumdelta = ch.sumdelta; ra.M = ch.M;
+    ra.doT_base = io.base;
     static const int epi_rows_on = diag_env("GPSLC_EPI_ROWS", 1);      // measurement switch (A/B of the extra tile update)
     const bool epi_rows = (sh.naug == 1) && epi_rows_on;     // single augmented tile row: the epilogue sums from the rows of R
     const int live = (sh.with_sums ? sh.L : 0) + 1;          // right-hand sides: Y and one c_l per level
@@ -910,6 +912,7 @@ void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
     ia.n = n; ia.nX = io.nX; ia.nU = io.nU; ia.nt = sh.nt; ia.L = sh.L; ia.doT = io.doT; ia.alpha = alpha;
     ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.p.yNoise;
     ia.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
+    ia.doT_base = io.base;
     for (const auto& o : outs)
         if (o.out) { ia.meanITE = o.out; ia.si = o.si; ia.ss = o.ss; ia.sl = o.sl; launch_ite_mean(ia, nb, st); }
 }
@@ -975,6 +978,7 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
             da.X = io.X; da.T = c->dT; da.p = io.p; da.s0 = s0 + g0;
             da.n = n; da.nX = io.nX; da.nU = io.nU; da.nt = nt; da.doT = io.doT; da.l0 = l0; da.lc = lc;
             da.vec = io.vec ? 1 : 0;
+            da.doT_base = io.base;
             da.pred_noise = io.pred_noise; da.W = W; da.Cm = Cm;
             launch_dt_build(da, ub, st);
             TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
@@ -1024,6 +1028,8 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
 // the chunked ensemble driver (device pointers everywhere)
 void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     PredictIO io = io_in;
+    if (io.base && io.vec) throw std::runtime_error("a contrast baseline cannot be combined with vector levels");
+    if (io.base && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("contrasts need an fp64 context");
     if (io.nU < 0) io.nU = c->nU;
     if (io.nX < 0) io.nX = c->nX;
     if (!io.Y) { io.Y = c->dY; io.y_sstride = 0; }
@@ -1624,10 +1630,10 @@ static int predict_dev_inner(gpslc_ctx* c, int64_t S, const double* U, const dou
                              const double* tyLS, const double* yScale, const double* yNoise, int32_t L,
                              const double* doT, double pred_noise, int32_t spp, uint64_t seed, const double* z,
                              double* meanSATE, double* varSATE, double* meanITE, double* ite_draws,
-                             int64_t ens_off = 0, int64_t ens_S = 0, bool vec = false) {
+                             int64_t ens_off = 0, int64_t ens_S = 0, bool vec = false, const double* base = nullptr) {
     PredictIO io;
     io.S = S; io.p = SampleParams{U, uyLS, xyLS, tyLS, yScale, yNoise}; io.X = c->dX;
-    io.L = L; io.doT = doT; io.vec = vec; io.pred_noise = pred_noise; io.spp = spp; io.seed = seed; io.z = z;
+    io.L = L; io.doT = doT; io.vec = vec; io.base = base; io.pred_noise = pred_noise; io.spp = spp; io.seed = seed; io.z = z;
     io.meanSATE = meanSATE; io.varSATE = varSATE; io.meanITE = meanITE; io.ite_draws = ite_draws;
     io.ens_off = ens_off; io.ens_S = ens_S;
     io.info = c->io.take<int>((size_t)S);
@@ -1663,7 +1669,7 @@ struct HostPlacement {
 static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
                         const double* yScale, const double* yNoise, int32_t L, const double* doT, double pred_noise, int32_t spp,
                         uint64_t seed, const double* z, double* meanSATE, double* varSATE, double* meanITE, double* ite_draws,
-                        const HostPlacement& pl, bool vec = false) {
+                        const HostPlacement& pl, bool vec = false, const double* base = nullptr) {
     return guarded(c, [&]() {
         const size_t n = (size_t)c->n;
         const size_t s0 = (size_t)pl.s0, St = (size_t)pl.S_total;
@@ -1675,6 +1681,7 @@ static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* 
         const double* dys = up(c, yScale + s0, S);
         const double* dyn = up(c, yNoise + s0, S);
         const double* ddo = up(c, doT, vec ? n * L : (size_t)L);     // vector levels: n x L
+        const double* dba = base ? up(c, base, (size_t)L) : nullptr;  // contrasts: the L baselines
         const double* dz = nullptr;
         if (z && ite_draws) {      // caller's normals n x spp x S_total x L: level l of the shard is one run of n spp S doubles
             double* d = c->io.take<double>(n * spp * S * L);
@@ -1687,7 +1694,7 @@ static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* 
         double* omi = meanITE ? c->io.take<double>(n * S * L) : nullptr;
         double* odr = ite_draws ? c->io.take<double>((size_t)L * n * S * spp) : nullptr;
         int st = predict_dev_inner(c, S, dU, duy, dxy, dty, dys, dyn, L, ddo, pred_noise, spp, seed, dz,
-                                   oms, ovs, omi, odr, pl.ens_off, pl.ens_S, vec);
+                                   oms, ovs, omi, odr, pl.ens_off, pl.ens_S, vec, dba);
         if (st < 0) return st;
         const size_t sb = (size_t)S * sizeof(double);
         if (meanSATE) HC(hipMemcpy2D(meanSATE + s0, St * sizeof(double), oms, sb, sb, (size_t)L, hipMemcpyDeviceToHost));
@@ -1741,6 +1748,40 @@ int gpslc_predict_vec(gpslc_ctx* c, int64_t S, const double* U, const double* uy
     pl.S_total = S;
     return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE, varSATE, meanITE,
                         ite_draws, pl, /*vec=*/true);
+}
+
+// contrasts (gpslc_*_contrast): level l is the pair (doT[l], doT_base[l]) of finite scalars; fp64 contexts only
+static int contrast_levels_check(gpslc_ctx* c, const double* v, int64_t count, int argk, const char* name) {
+    char what[64];
+    if (!v) { snprintf(what, sizeof what, "%s is NULL", name); return bad_arg(c, argk, what); }
+    for (int64_t i = 0; i < count; ++i)
+        if (!std::isfinite(v[i])) { snprintf(what, sizeof what, "%s has a non-finite entry", name); return bad_arg(c, argk, what); }
+    return 0;
+}
+static int contrast_mode_check(gpslc_ctx* c) {
+    if (c->flags & GPSLC_FLAG_FP32_KERNEL) {
+        set_err(c, "contrasts are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
+        return GPSLC_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+
+int gpslc_predict_contrast(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                           const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
+                           const double* doT_base, double pred_noise, int32_t spp, uint64_t seed, const double* z,
+                           double* meanSATE, double* varSATE, double* meanITE, double* ite_draws) {
+    // gpslc_predict's checks up to doT (#10); doT_base is #11 here, so spp is #13
+    int rc = predict_check(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, nullptr);
+    if (rc) return rc;
+    if ((rc = contrast_levels_check(c, doT, L, 10, "doT"))) return rc;
+    if ((rc = contrast_levels_check(c, doT_base, L, 11, "doT_base"))) return rc;
+    if (ite_draws && spp < 1) return bad_arg(c, 13, "spp < 1 with ite_draws requested");
+    if ((rc = contrast_mode_check(c))) return rc;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    HostPlacement pl;
+    pl.S_total = S;
+    return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE, varSATE, meanITE,
+                        ite_draws, pl, /*vec=*/false, doT_base);
 }
 
 int gpslc_shard_range(int64_t S, int32_t nblocks, int32_t k, int64_t* s0, int64_t* s1) {
@@ -1835,10 +1876,10 @@ int gpslc_predict_multi(int32_t nctx, gpslc_ctx* const* ctxs, int64_t S, const d
     }
 }
 
-// doT: one level (host), a scalar (vec = false) or n values (vec = true)
+// doT: one level (host), a scalar (vec = false) or n values (vec = true); base: non-null = the contrast doT against *base
 static int ite_distributions_impl(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
                                   const double* tyLS, const double* yScale, const double* yNoise, const double* doT, bool vec,
-                                  double pred_noise, double* MeanITEs, double* CovITEs) {
+                                  double pred_noise, double* MeanITEs, double* CovITEs, const double* base = nullptr) {
     return guarded(c, [&]() {
         const size_t n = (size_t)c->n;
         c->io.reset();
@@ -1849,11 +1890,12 @@ static int ite_distributions_impl(gpslc_ctx* c, int64_t S, const double* U, cons
         const double* dys = up(c, yScale, S);
         const double* dyn = up(c, yNoise, S);
         const double* ddo = up(c, doT, vec ? n : 1);
+        const double* dba = base ? up(c, base, 1) : nullptr;
         double* om = MeanITEs ? c->io.take<double>((size_t)S * n) : nullptr;
         double* oc = CovITEs ? c->io.take<double>((size_t)S * n * n) : nullptr;
         PredictIO io;
         io.S = S; io.p = SampleParams{dU, duy, dxy, dty, dys, dyn}; io.X = c->dX;
-        io.L = 1; io.doT = ddo; io.vec = vec; io.pred_noise = pred_noise;
+        io.L = 1; io.doT = ddo; io.vec = vec; io.base = dba; io.pred_noise = pred_noise;
         io.MeanITEs = om; io.CovITEs = oc; io.info = c->io.take<int>((size_t)S);
         run_predict(c, io);
         if (MeanITEs) HC(hipMemcpy(MeanITEs, om, sizeof(double) * S * n, hipMemcpyDeviceToHost));
@@ -1880,6 +1922,18 @@ int gpslc_ite_distributions_vec(gpslc_ctx* c, int64_t S, const double* U, const 
     if ((rc = vec_mode_check(c))) return rc;
     if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
     return ite_distributions_impl(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, doT, true, pred_noise, MeanITEs, CovITEs);
+}
+
+int gpslc_ite_distributions_contrast(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                                     const double* tyLS, const double* yScale, const double* yNoise, double doT,
+                                     double doT_base, double pred_noise, double* MeanITEs, double* CovITEs) {
+    int rc = check_common(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise);
+    if (rc) return rc;
+    if ((rc = contrast_levels_check(c, &doT, 1, 9, "doT"))) return rc;
+    if ((rc = contrast_levels_check(c, &doT_base, 1, 10, "doT_base"))) return rc;
+    if ((rc = contrast_mode_check(c))) return rc;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return ite_distributions_impl(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, &doT, false, pred_noise, MeanITEs, CovITEs, &doT_base);
 }
 
 // logpdf[s] = -(n log 2pi + logdet_s + quad_s) / 2 from the device-side epilogue values

@@ -180,6 +180,8 @@ struct RhsArgs {
     int live_rows;   // > 0 (single augmented tile row of <= 32 right-hand sides, epilogue sums from the rows of R): only the
                      // first 32 rows of the augmented tiles are written (right-hand sides, then zeros) and the augmented
                      // diagonal tile not at all — every reader of those tiles touches the live 16- / 32-row blocks only
+    const double* doT_base;   // non-null: contrasts — level l is the pair (doT[l], doT_base[l]), c_l = (r^a - r^b) .* bsum and
+                              // sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B
 };
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
 
@@ -209,6 +211,8 @@ struct IteMeanArgs {
     double* meanITE;       // element (i, s, l) at i*si + s*ss + l*sl
     long long si, ss, sl;
     int f32;
+    const double* doT_base;   // non-null (fp64 only): contrasts, MeanITE_i(l) = sum_j B_ij (r^a_j - r^b_j) alpha_j for the pair
+                              // (a, b) = (doT[l], doT_base[l])
 };
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st);
 
@@ -241,6 +245,8 @@ struct DtArgs {
     double pred_noise;
     TRef W;    // nt x nt rectangular: receives D (rows = i, cols = j), D_ij = B_ij (r_j - e_ij)
     TRef Cm;   // lower packed nt: receives Delta + pred_noise*I (identity on the padding)
+    const double* doT_base;   // non-null (scalar levels only): contrasts, D_ij = B_ij (r^a_j - r^b_j) and
+                              // Delta_ij = B_ij ((1 - rho) + (1 - rho)) for the pair (doT[l], doT_base[l])
 };
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st);
 

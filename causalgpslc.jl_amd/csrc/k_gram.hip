@@ -4,7 +4,8 @@
 //                      src/likelihood.jl:24-32; src/model_likelihood.jl:83-120), lower tiles only,
 //                      fused with the per-tile partial column sums of B = yScale*exp(Lu+Lx) and
 //                      K = B.*E that the SATE path needs.
-//   rhs_prepare/tiles  column sums -> augmented right-hand sides [Y, c(1..L)] and sum(Delta).
+//   rhs_prepare/tiles  column sums -> augmented right-hand sides [Y, c(1..L)] and sum(Delta).  CON: the contrast form of
+//                      both (level l = the pair (doT[l], doT_base[l])).
 //   epilogue           Schur complement of the augmented block -> MeanSATE, VarSATE, logdet, quad.
 //   rbf_log / process_cov  the two src/kernel.jl entry points as stand-alone dense kernels.
 #include "gpslc_internal.h"
@@ -258,7 +259,11 @@ void launch_gram(const GramArgs& g, int nbatch, hipStream_t st) {
 // ---------------------------------------------------------------------------------------
 // rhs_prepare: per sample, reduce the per-tile partial sums in a fixed order, form the totals and
 // sum(Delta_l) = sum K - 2 r.bsum + sum B for every level.  One workgroup per sample.
+// CON (contrast of the levels a = doT[l] and b = doT_base[l]): the prior block Kss_aa - Kss_ab - Kss_ba + Kss_bb is
+// B ((1 - rho) + (1 - rho)) with rho = exp(-(a - b)^2 / tyLS^2), so sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B: no sum
+// over the columns, and exactly 0.0 when a == b.
 // ---------------------------------------------------------------------------------------
+template <bool CON>
 __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
     __shared__ double red[4];
     const int tid = threadIdx.x;
@@ -283,6 +288,14 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
     const double ktot = block_sum_256(tk, red);
     const double tl = a.tyLS[s];
     const double wt = 1.0 / (tl * tl);
+    if (CON) {
+        for (int l = tid; l < a.L; l += 256) {
+            const double dab = a.doT[l] - a.doT_base[l];
+            const double rho = gp_exp_neg(-((dab * dab) * wt));
+            a.sumdelta[(long long)b * a.L + l] = ((1.0 - rho) + (1.0 - rho)) * btot;
+        }
+        return;
+    }
     for (int l = 0; l < a.L; ++l) {
         const double dot = a.doT[l];
         double acc = 0.0;
@@ -299,7 +312,20 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
 
 // rhs_tiles: write the augmented row tiles: row q of the augmented block is right-hand side q
 // (q = 0: Y, q = 1 + l: c_l = r_l .* bsum - ksum), zero elsewhere; zero the aug x aug tiles.
+// CON: c_l = (r^a - r^b) .* bsum for the pair (a, b) = (doT[l], doT_base[l]) — the e_ij of the ordinary level cancels, and
+// a == b gives r^a == r^b bit for bit: an exact zero row.
 // grid (nt + naug, naug, batch): tile (nt + a, j) with j = blockIdx.x, a = blockIdx.y (j <= nt + a).
+template <bool CON>
+__device__ __forceinline__ double rhs_level_value(const RhsArgs& a, int l, int gj, double wt, const double* bs, const double* ks) {
+    const double dt = a.T[gj] - a.doT[l];
+    const double r = gp_exp_neg(-((dt * dt) * wt));
+    if (CON) {
+        const double db = a.T[gj] - a.doT_base[l];
+        return (r - gp_exp_neg(-((db * db) * wt))) * bs[gj];
+    }
+    return r * bs[gj] - ks[gj];
+}
+template <bool CON>
 __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
     const int tid = threadIdx.x;
     const int j = blockIdx.x, au = blockIdx.y, b = blockIdx.z;
@@ -329,11 +355,7 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
             double v = 0.0;
             if (gj < a.n) {
                 if (q == 0) v = a.Y[s * a.y_sstride + gj];
-                else if (q <= a.L) {
-                    const double dt = a.T[gj] - a.doT[q - 1];
-                    const double r = gp_exp_neg(-((dt * dt) * wt));
-                    v = r * bs[gj] - ks[gj];
-                }
+                else if (q <= a.L) v = rhs_level_value<CON>(a, q - 1, gj, wt, bs, ks);
             }
             tile[c * GP_TS + q] = v;
         }
@@ -346,19 +368,20 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
         double v = 0.0;
         if (gj < a.n) {
             if (gq == 0) v = a.Y[s * a.y_sstride + gj];
-            else if (gq <= a.L) {
-                const double dt = a.T[gj] - a.doT[gq - 1];
-                const double r = gp_exp_neg(-((dt * dt) * wt));
-                v = r * bs[gj] - ks[gj];
-            }
+            else if (gq <= a.L) v = rhs_level_value<CON>(a, gq - 1, gj, wt, bs, ks);
         }
         tile[idx] = v;
     }
 }
 
+template <bool CON>
+static void launch_rhs_t(const RhsArgs& r, int nbatch, hipStream_t st) {
+    if (r.with_sums) hipLaunchKernelGGL(rhs_prepare_kernel<CON>, dim3(nbatch), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(rhs_tiles_kernel<CON>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
+}
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.with_sums) hipLaunchKernelGGL(rhs_prepare_kernel, dim3(nbatch), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(rhs_tiles_kernel, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
+    if (r.doT_base) launch_rhs_t<true>(r, nbatch, st);
+    else launch_rhs_t<false>(r, nbatch, st);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -73,8 +73,12 @@ void launch_backsolve(const BackArgs& a, int nbatch, hipStream_t st) {
 // (T_i - T_j)^2 are then the same square, so Ks'_ij == K_ij bit for bit): the reference returns an exact 0.0 for such an
 // instance (test/estimation.jl:6-66 is the n = 1 case) and so does this kernel.
 // One workgroup per (row block, sample); levels are processed LCT at a time.
+// CON (contrast of the levels a = doT[l] and b = doT_base[l]): D = Ks_a' - Ks_b', the K of the ordinary level
+// cancels, so  MeanITE_i(l) = sum_j B_ij ((r^a_j - r^b_j) alpha_j)  with no K alpha term; a == b stages exact zeros (r^a == r^b
+// bit for bit) and every row returns 0.0.  Only what is staged per column block and the epilogue differ: the pair loop is
+// the same code.
 // ---------------------------------------------------------------------------------------
-template <int FREG, int LCT, typename RT, int RB>
+template <int FREG, int LCT, typename RT, int RB, bool CON = false>
 __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
@@ -128,7 +132,13 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
                 double v = 0.0;
                 if (ll < nl && g < n) {
                     const RT dt = (RT)a.T[g] - (RT)a.doT[l0 + ll];
-                    v = (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab) * alpha[g];
+                    if (CON) {
+                        const RT db = (RT)a.T[g] - (RT)a.doT_base[l0 + ll];
+                        v = ((double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab) -
+                             (double)RbfMath<RT>::exp_neg_t(-((db * db) * wtq), etab)) * alpha[g];
+                    } else {
+                        v = (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab) * alpha[g];
+                    }
                 }
                 rl[idx] = v;
             }
@@ -168,6 +178,16 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 #pragma unroll
             for (int q = 0; q < RB; ++q) {
                 if (gi[q] >= n) continue;
+                if (CON) {
+#pragma unroll
+                    for (int ll = 0; ll < LCT; ++ll)
+                        if (ll < nl) {
+                            const double v = acc[q][ll] + red[(q * GP_TS + r) * LCT + ll];
+                            a.meanITE[(long long)gi[q] * a.si + s * a.ss + (long long)(l0 + ll) * a.sl] =
+                                (a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : v;
+                        }
+                    continue;
+                }
                 // (K alpha)_i = Y_i - yNoise alpha_i: alpha solves (K + yNoise I) alpha = Y
                 const double ka = a.Y[s * a.y_sstride + gi[q]] - a.yNoise[s] * alpha[gi[q]];
                 const double ti = a.T[gi[q]];
@@ -193,6 +213,7 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 // Instances with T_i == doT_l get the reference's exact 0.0 (row i of Ks' - K is identically zero there).
 // One workgroup = 128 rows x up to 64 levels; wave w owns rows 32w..32w+31 (2 row sub-tiles x 4 level
 // sub-tiles = 8 accumulators).
+// CON: contrasts as in ite_mean_kernel — R[j, l] = (r^a_j - r^b_j) alpha_j, no K alpha term, 0.0 for a level with a == b.
 // ---------------------------------------------------------------------------------------
 typedef double d4s __attribute__((ext_vector_type(4)));
 typedef double d2s __attribute__((ext_vector_type(2)));
@@ -200,7 +221,7 @@ typedef double d2s __attribute__((ext_vector_type(2)));
 #define IM_RLD 80         // padded row of the R chunk (doubles): conflict-free ds_read_b64 across k rows
 #define IM_NL 64          // levels per pass
 
-template <int FREG>   // FREG > 0: this lane's two rows' features live in registers (F <= FREG); 0: read from LDS
+template <int FREG, bool CON = false>   // FREG > 0: this lane's two rows' features live in registers (F <= FREG); 0: read from LDS
 __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
@@ -264,7 +285,12 @@ __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
                 double v = 0.0;
                 if (ll < nl && g < n) {
                     const double dt = a.T[g] - a.doT[l0 + ll];
-                    v = gp_exp_neg_tab(-((dt * dt) * wt), etab) * alpha[g];
+                    if (CON) {
+                        const double db = a.T[g] - a.doT_base[l0 + ll];
+                        v = (gp_exp_neg_tab(-((dt * dt) * wt), etab) - gp_exp_neg_tab(-((db * db) * wt), etab)) * alpha[g];
+                    } else {
+                        v = gp_exp_neg_tab(-((dt * dt) * wt), etab) * alpha[g];
+                    }
                 }
                 R[cc * IM_RLD + ll] = v;
             }
@@ -306,7 +332,19 @@ __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const int gi = ib * GP_TS + 32 * wave + 16 * m + li;
-            if (gi < n) {
+            if (CON) {
+                if (gi < n) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) {
+                            const int ll = 16 * q + lq + 4 * v;
+                            if (ll < nl)
+                                a.meanITE[(long long)gi * a.si + s * a.ss + (long long)(l0 + ll) * a.sl] =
+                                    (a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : acc[m][q][v];
+                        }
+                }
+            } else if (gi < n) {
                 const double ka = a.Y[s * a.y_sstride + gi] - a.yNoise[s] * alpha[gi];     // (K alpha)_i from A alpha = Y
                 const double ti = a.T[gi];
 #pragma unroll
@@ -323,57 +361,63 @@ __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
     }
 }
 
-template <int FREG>
+template <int FREG, bool CON>
 static void launch_ite_mean_mfma_t(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     const int F = a.nU + a.nX;
     const int FS = FREG > F ? FREG : F;
     const int bytes = (GP_EXP_TAB_DOUBLES + F * GP_TS + FS * IM_CC + IM_CC * IM_RLD) * 8;
     static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)ite_mean_mfma_kernel<FREG>, (GP_EXP_TAB_DOUBLES + MAXF * GP_TS + MAXF * IM_CC + IM_CC * IM_RLD) * 8);
-    hipLaunchKernelGGL((ite_mean_mfma_kernel<FREG>), dim3(a.nt, nbatch), dim3(256), bytes, st, a);
+    lds_opt_in(attr_set, (const void*)ite_mean_mfma_kernel<FREG, CON>, (GP_EXP_TAB_DOUBLES + MAXF * GP_TS + MAXF * IM_CC + IM_CC * IM_RLD) * 8);
+    hipLaunchKernelGGL((ite_mean_mfma_kernel<FREG, CON>), dim3(a.nt, nbatch), dim3(256), bytes, st, a);
 }
+template <bool CON>
 static void launch_ite_mean_mfma(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     const int F = a.nU + a.nX;
-    if (F <= 4) launch_ite_mean_mfma_t<4>(a, nbatch, st);
-    else if (F <= 6) launch_ite_mean_mfma_t<6>(a, nbatch, st);
-    else if (F <= 8) launch_ite_mean_mfma_t<8>(a, nbatch, st);
-    else if (F <= 10) launch_ite_mean_mfma_t<10>(a, nbatch, st);
-    else if (F <= 12) launch_ite_mean_mfma_t<12>(a, nbatch, st);
-    else launch_ite_mean_mfma_t<0>(a, nbatch, st);
+    if (F <= 4) launch_ite_mean_mfma_t<4, CON>(a, nbatch, st);
+    else if (F <= 6) launch_ite_mean_mfma_t<6, CON>(a, nbatch, st);
+    else if (F <= 8) launch_ite_mean_mfma_t<8, CON>(a, nbatch, st);
+    else if (F <= 10) launch_ite_mean_mfma_t<10, CON>(a, nbatch, st);
+    else if (F <= 12) launch_ite_mean_mfma_t<12, CON>(a, nbatch, st);
+    else launch_ite_mean_mfma_t<0, CON>(a, nbatch, st);
 }
 
-template <int FREG, int LCT, typename RT>
+template <int FREG, int LCT, typename RT, bool CON>
 static void launch_ite_mean_t(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     constexpr int RB = 1;     // row blocks per workgroup (2 measured slower: occupancy)
     const int bytes = (GP_EXP_TAB_DOUBLES + (1 + RB) * LCT * GP_TS) * 8 + (FREG * GP_TS) * (int)sizeof(RT);
     static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)ite_mean_kernel<FREG, LCT, RT, RB>, bytes);
-    hipLaunchKernelGGL((ite_mean_kernel<FREG, LCT, RT, RB>), dim3((a.nt + RB - 1) / RB, nbatch), dim3(256), bytes, st, a);
+    lds_opt_in(attr_set, (const void*)ite_mean_kernel<FREG, LCT, RT, RB, CON>, bytes);
+    hipLaunchKernelGGL((ite_mean_kernel<FREG, LCT, RT, RB, CON>), dim3((a.nt + RB - 1) / RB, nbatch), dim3(256), bytes, st, a);
 }
-template <int FREG, typename RT>
+template <int FREG, typename RT, bool CON>
 static void launch_ite_mean_f(const IteMeanArgs& a, int nbatch, hipStream_t st) {
-    if (a.L <= 1) launch_ite_mean_t<FREG, 1, RT>(a, nbatch, st);
-    else if (a.L <= 4) launch_ite_mean_t<FREG, 4, RT>(a, nbatch, st);
-    else launch_ite_mean_t<FREG, 16, RT>(a, nbatch, st);
+    if (a.L <= 1) launch_ite_mean_t<FREG, 1, RT, CON>(a, nbatch, st);
+    else if (a.L <= 4) launch_ite_mean_t<FREG, 4, RT, CON>(a, nbatch, st);
+    else if (!CON) launch_ite_mean_t<FREG, 16, RT, false>(a, nbatch, st);     // contrasts (fp64): L > 4 is the MFMA kernel's
 }
-template <typename RT>
+template <typename RT, bool CON = false>
 static void launch_ite_mean_r(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     const int F = a.nU + a.nX;
     // exact register counts for the common feature widths: the pass is fp64-VALU bound (2 instructions per
     // feature per element), a padded feature is paid in full
-    if (F <= 4) launch_ite_mean_f<4, RT>(a, nbatch, st);
-    else if (F <= 5) launch_ite_mean_f<5, RT>(a, nbatch, st);      // BASELINE config 2: nU + nX = 1 + 4
-    else if (F <= 6) launch_ite_mean_f<6, RT>(a, nbatch, st);
-    else if (F <= 8) launch_ite_mean_f<8, RT>(a, nbatch, st);
-    else if (F <= 10) launch_ite_mean_f<10, RT>(a, nbatch, st);
-    else if (F <= 12) launch_ite_mean_f<12, RT>(a, nbatch, st);
-    else if (F <= 16) launch_ite_mean_f<16, RT>(a, nbatch, st);
-    else if (F <= 20) launch_ite_mean_f<20, RT>(a, nbatch, st);
-    else launch_ite_mean_f<32, RT>(a, nbatch, st);
+    if (F <= 4) launch_ite_mean_f<4, RT, CON>(a, nbatch, st);
+    else if (F <= 5) launch_ite_mean_f<5, RT, CON>(a, nbatch, st);      // BASELINE config 2: nU + nX = 1 + 4
+    else if (F <= 6) launch_ite_mean_f<6, RT, CON>(a, nbatch, st);
+    else if (F <= 8) launch_ite_mean_f<8, RT, CON>(a, nbatch, st);
+    else if (F <= 10) launch_ite_mean_f<10, RT, CON>(a, nbatch, st);
+    else if (F <= 12) launch_ite_mean_f<12, RT, CON>(a, nbatch, st);
+    else if (F <= 16) launch_ite_mean_f<16, RT, CON>(a, nbatch, st);
+    else if (F <= 20) launch_ite_mean_f<20, RT, CON>(a, nbatch, st);
+    else launch_ite_mean_f<32, RT, CON>(a, nbatch, st);
 }
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     // many levels: the (B R) product belongs on the matrix cores (fp64 path; the fp32 mode keeps the VALU kernel)
-    if (!a.f32 && a.L > 4) { launch_ite_mean_mfma(a, nbatch, st); return; }
+    if (a.doT_base) {       // contrasts: fp64 contexts only (the entry points refuse the fp32 kernel mode)
+        if (a.L > 4) launch_ite_mean_mfma<true>(a, nbatch, st);
+        else launch_ite_mean_r<double, true>(a, nbatch, st);
+        return;
+    }
+    if (!a.f32 && a.L > 4) { launch_ite_mean_mfma<false>(a, nbatch, st); return; }
     if (a.f32) launch_ite_mean_r<float>(a, nbatch, st);
     else launch_ite_mean_r<double>(a, nbatch, st);
 }
@@ -384,8 +428,10 @@ void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
 // CovWW - CovWWs - CovWWs' + CovWsWs, src/likelihood.jl:46-49 / estimation.jl:47, :82) into Cm.
 // VEC (per-individual intervention d, k_vec.hip): r_i, r_j become g_ij = exp(-(T_i - d_j)^2 / tyLS^2), g_ji, and the 1 of
 // CovWsWs becomes h_ij = exp(-(d_i - d_j)^2 / tyLS^2); the staged rr_ / rc_ hold d of the row / column block instead of r.
+// CON (contrast of the scalar levels a = doT[l], b = doT_base[l]): D_ij = B_ij (r^a_j - r^b_j) (rc_ holds the
+// difference) and Delta_ij = B_ij ((1 - rho) + (1 - rho)), rho = exp(-(a - b)^2 / tyLS^2) — exactly 0 when a == b.
 // ---------------------------------------------------------------------------------------
-template <bool VEC>
+template <bool VEC, bool CON = false>
 __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
@@ -404,6 +450,13 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
     const int gi0 = ti * GP_TS, gj0 = tj * GP_TS;
     const double tl = a.p.tyLS[s];
     const double wt = 1.0 / (tl * tl);
+    const double doTb = CON ? a.doT_base[a.l0 + (int)(b % a.lc)] : 0.0;
+    double kss = 0.0;       // CON: (1 - rho) + (1 - rho)
+    if (CON) {
+        const double dab = doT - doTb;
+        const double rho = gp_exp_neg(-((dab * dab) * wt));
+        kss = (1.0 - rho) + (1.0 - rho);
+    }
     for (int idx = tid; idx < F * GP_TS; idx += 256) {
         const int f = idx >> 7, r = idx & 127;
         const double* src = (f < a.nU) ? a.p.U + s * a.p.u_sstride + (long long)f * n
@@ -419,6 +472,9 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
         if (VEC) {
             rr_[tid] = (gi0 + tid < n) ? dv[gi0 + tid] : 0.0;
             rc_[tid] = (gj0 + tid < n) ? dv[gj0 + tid] : 0.0;
+        } else if (CON) {
+            const double d2 = t2 - doT, b2 = t2 - doTb;
+            rc_[tid] = gp_exp_neg(-((d2 * d2) * wt)) - gp_exp_neg(-((b2 * b2) * wt));
         } else {
             const double d1 = t1 - doT, d2 = t2 - doT;
             rr_[tid] = gp_exp_neg(-((d1 * d1) * wt));
@@ -459,6 +515,9 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
                 const double Gij = gp_exp_neg(-((gij * gij) * wt)), Gji = gp_exp_neg(-((gji * gji) * wt));
                 Dv = Bv * (Gji - Ev);
                 Cv = Bv * (((Ev - Gij) - Gji) + gp_exp_neg(-((hij * hij) * wt)));
+            } else if (CON) {
+                Dv = Bv * rj;
+                Cv = Bv * kss;
             } else {
                 const double ri = rr_[rp];
                 Dv = Bv * (rj - Ev);
@@ -474,14 +533,15 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
 }
 #define DT_LDS_BYTES(F) ((2 * (F) * GP_TS + 4 * GP_TS) * 8)
 
-template <bool VEC>
+template <bool VEC, bool CON = false>
 static void launch_dt_build_t(const DtArgs& a, int nbatch, hipStream_t st) {
     static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)dt_build_kernel<VEC>, DT_LDS_BYTES(MAXF));
-    hipLaunchKernelGGL(dt_build_kernel<VEC>, dim3(a.nt * a.nt, nbatch), dim3(256), DT_LDS_BYTES(a.nU + a.nX), st, a);
+    lds_opt_in(attr_set, (const void*)dt_build_kernel<VEC, CON>, DT_LDS_BYTES(MAXF));
+    hipLaunchKernelGGL((dt_build_kernel<VEC, CON>), dim3(a.nt * a.nt, nbatch), dim3(256), DT_LDS_BYTES(a.nU + a.nX), st, a);
 }
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st) {
-    if (a.vec) launch_dt_build_t<true>(a, nbatch, st);
+    if (a.doT_base) launch_dt_build_t<false, true>(a, nbatch, st);
+    else if (a.vec) launch_dt_build_t<true>(a, nbatch, st);
     else launch_dt_build_t<false>(a, nbatch, st);
 }
 

@@ -243,6 +243,30 @@ int gpslc_predict_vec(gpslc_ctx* ctx, int64_t S, const double* U, const double* 
                       int32_t spp, uint64_t seed, const double* z_or_null,
                       double* meanSATE, double* varSATE, double* meanITE, double* ite_draws);
 
+/* Contrasts between two intervention levels: level l is the PAIR (a, b) = (doT[l], doT_base[l]) of scalars and the estimand is
+ * "everybody at a" against "everybody at b",
+ *     ITE_i(a, b) = f_i(a) - f_i(b)        (gpslc_predict's is f_i(doT) - f_i(T_i): the case "b = the observed treatments"),
+ * for a binary treatment with (a, b) = (1, 0) the effect whose average is the ATE E[Y(1) - Y(0)].  With B = yScale exp(Lu + Lx),
+ * r^x_j = exp(-(T_j - x)^2 / tyLS^2), rho = exp(-(a - b)^2 / tyLS^2), alpha = (K + yNoise I)^-1 Y:
+ *     D = CovWWs_a' - CovWWs_b',  D_ij = B_ij (r^a_j - r^b_j);    MeanITE = D alpha;
+ *     CovITE = B ((1 - rho) + (1 - rho)) - D (K + yNoise I)^-1 D',  + pred_noise*I after symmetrisation (src/estimation.jl:82);
+ *     meanSATE, varSATE = conditionalSATE of these (src/estimation.jl:116-121).
+ * The mean is the difference of two gpslc_predict means; the covariance, varSATE and the draws are NOT obtainable from two
+ * gpslc_predict levels (those share the factual term and the whole GP, and draw independently).  doT and doT_base are L host
+ * values each, all finite (else -10 / -11, "argument #10 / #11 is invalid").  Everything else — the other arguments, outputs
+ * and layouts, NULL conventions, the normals (z layout, Philox stream s + S*l, gpslc_set_ensemble placement), chunking, the
+ * schedule and gpslc_last_info — is gpslc_predict's; a contrast level costs what a scalar level costs (no pass over the pairs
+ * is added).  Exact identities: a level with a == b gives MeanITE == 0.0 for every individual, meanSATE == 0.0, varSATE ==
+ * n*pred_noise/n^2 and CovITE == pred_noise*I, bit for bit.  Accuracy: for |a - b| far below tyLS both r^a - r^b and 1 - rho
+ * cancel, so such a pair loses relative accuracy in the mean and, more so, in the variance (1 - rho ~ (a - b)^2 / tyLS^2; the
+ * pred_noise jitter then dominates CovITE).  fp64 only: a ctx created with GPSLC_FLAG_FP32_KERNEL returns
+ * GPSLC_ERR_UNSUPPORTED.  Not sharded (gpslc_predict_multi keeps gpslc_predict's estimand). */
+int gpslc_predict_contrast(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                           const double* xyLS, const double* tyLS, const double* yScale,
+                           const double* yNoise, int32_t L, const double* doT, const double* doT_base,
+                           double pred_noise, int32_t spp, uint64_t seed, const double* z_or_null,
+                           double* meanSATE, double* varSATE, double* meanITE, double* ite_draws);
+
 /* The same call sharded over several GPUs of one node: what the loop of predictCounterfactualEffects (src/prediction.jl:30-33)
  * over the posterior samples (src/estimation.jl:78-84) becomes when the ensemble is partitioned.  ctxs[0..nctx) are
  * DISTINCT contexts created with the same (n, nX, nU), one per device (gpslc_create(&ctx_k, device_k, ...)), each holding the data
@@ -281,6 +305,14 @@ int gpslc_ite_distributions_vec(gpslc_ctx* ctx, int64_t S, const double* U, cons
                                 const double* xyLS, const double* tyLS, const double* yScale,
                                 const double* yNoise, const double* doT, double pred_noise,
                                 double* MeanITEs, double* CovITEs);
+
+/* ITEDistributions for the contrast of the scalar levels doT against doT_base (see gpslc_predict_contrast): same outputs and
+ * layouts as gpslc_ite_distributions, CovITEs with its + pred_noise*I.  A non-finite doT returns -9, a non-finite doT_base -10.
+ * doT == doT_base: MeanITEs all 0.0 and CovITEs == pred_noise*I exactly.  GPSLC_FLAG_FP32_KERNEL: GPSLC_ERR_UNSUPPORTED. */
+int gpslc_ite_distributions_contrast(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                                     const double* xyLS, const double* tyLS, const double* yScale,
+                                     const double* yNoise, double doT, double doT_base, double pred_noise,
+                                     double* MeanITEs, double* CovITEs);
 
 /* likelihoodDistribution(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT) (src/likelihood.jl:8-52 and
  * its three reduced methods :55-94, :97-136, :139-174) for ONE parameter set, as the reference exports it:

@@ -271,6 +271,28 @@ function predict_vec(c::Ctx, p::Pack, doT::Matrix{Float64}, pred_noise::Float64;
     mS, vS, mI, dr
 end
 
+"""`predict` for contrasts between two scalar levels: level l is `doT[l]` against `doT_base[l]`, the estimand f(a) − f(b)
+("everybody at a" against "everybody at b"; for a binary treatment (1, 0) is the effect whose average is the ATE) with its own
+covariance, varSATE and draws (gpslc_predict_contrast).  Same keywords and return value as `predict`; a pair with a == b gives
+exact zeros."""
+function predict_contrast(c::Ctx, p::Pack, doT::Vector{Float64}, doT_base::Vector{Float64}, pred_noise::Float64; spp::Integer=0,
+                          seed::Integer=0, z=nothing, want_mean_ite::Bool=false, want_draws::Bool=false)
+    S, L, n = length(p.tyLS), length(doT), c.n
+    length(doT_base) == L || throw(DimensionMismatch("doT_base has length $(length(doT_base)), L = $L"))
+    mS, vS = Matrix{Float64}(undef, S, L), Matrix{Float64}(undef, S, L)
+    mI = want_mean_ite ? Array{Float64}(undef, n, S, L) : nothing
+    dr = want_draws ? Array{Float64}(undef, L, n, S * spp) : nothing
+    zf = f64(z)
+    GC.@preserve p doT doT_base zf mS vS mI dr check(c, ccall((:gpslc_predict_contrast, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Ptr{Float64}, Ptr{Float64}, Float64, Int32, UInt64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        L, pointer(doT), pointer(doT_base), pred_noise, spp, seed, ptr(zf),
+        pointer(mS), pointer(vS), ptr(mI), ptr(dr)))
+    mS, vS, mI, dr
+end
+
 """`predict` sharded over several GPUs of one node — `cs` = one context per device (`Ctx(n, nX, nU; device=k)`, each with
 the data: `set_data!` on every one), the posterior samples split into contiguous blocks, one host thread per context inside the
 library, every device copying its block of the results into these host arrays.  Same results as `predict(cs[1], …)` over all S
@@ -338,6 +360,19 @@ function ite_distributions_vec(c::Ctx, p::Pack, doT::Vector{Float64}, pred_noise
          Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}),
         c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
         pointer(doT), pred_noise, pointer(M), ptr(Cv)))
+    M, Cv
+end
+
+"""`ite_distributions` for the contrast of the scalar levels `doT` against `doT_base`: gpslc_ite_distributions_contrast."""
+function ite_distributions_contrast(c::Ctx, p::Pack, doT::Float64, doT_base::Float64, pred_noise::Float64; want_cov::Bool=true)
+    S, n = length(p.tyLS), c.n
+    M = Matrix{Float64}(undef, S, n)
+    Cv = want_cov ? Array{Float64}(undef, S, n, n) : nothing
+    GC.@preserve p M Cv check(c, ccall((:gpslc_ite_distributions_contrast, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        doT, doT_base, pred_noise, pointer(M), ptr(Cv)))
     M, Cv
 end
 
@@ -682,6 +717,17 @@ function _predict(g::GPSLCObject, devices, doT::Matrix{Float64}; kw...)
     GPSLCHip.predict_vec(ctx(g), posterior_pack(g), doT, g.hyperparams.predictionCovarianceNoise; kw...)
 end
 
+# `baseline=` of the estimation methods below: nothing = the reference's estimand f(doT) - f(T); a scalar level b (Bool -> 0 / 1)
+# = the contrast f(doT) - f(b) between two scalar levels (gpslc_predict_contrast / gpslc_ite_distributions_contrast), one GPU only
+_baseline(b::Real) = Float64(b)
+_level_predict(g::GPSLCObject, devices, lv, baseline::Nothing; kw...) = _predict(g, devices, lv; kw...)
+function _level_predict(g::GPSLCObject, devices, lv, baseline; kw...)
+    lv isa Vector{Float64} || throw(ArgumentError("baseline= needs a scalar doT: contrasts of per-individual intervention vectors are not supported"))
+    devices === nothing || throw(ArgumentError("contrasts are not sharded over devices: pass devices=nothing"))
+    GPSLCHip.predict_contrast(ctx(g), posterior_pack(g), lv, fill(_baseline(baseline), length(lv)),
+                              g.hyperparams.predictionCovarianceNoise; kw...)
+end
+
 """ctx(g): the device context holding g.X, g.T, g.Y (src/types.jl:249-258), created on first use."""
 ctx(g::GPSLCObject) = _device_side(g).ctx
 
@@ -793,12 +839,15 @@ function conditionalITE(g::GPSLCObject, psindex::Int64, doT::Intervention)      
     conditionalITE(uyLS, xyLS, tyLS, yNoise, yScale, U, g.X, g.T, g.Y, doT)
 end
 
-function ITEDistributions(g::GPSLCObject, doT::Intervention)                                                       # :66-86
-    _ite_dists(ctx(g), posterior_pack(g), _dot(doT, getN(g)), g.hyperparams.predictionCovarianceNoise)
+function ITEDistributions(g::GPSLCObject, doT::Intervention; baseline=nothing)                                     # :66-86
+    d, pn = _dot(doT, getN(g)), g.hyperparams.predictionCovarianceNoise
+    baseline === nothing && return _ite_dists(ctx(g), posterior_pack(g), d, pn)
+    d isa Float64 || throw(ArgumentError("baseline= needs a scalar doT: contrasts of per-individual intervention vectors are not supported"))
+    GPSLCHip.ite_distributions_contrast(ctx(g), posterior_pack(g), d, _baseline(baseline), pn)
 end
 
-function SATEDistributions(g::GPSLCObject, doT::Intervention; devices=nothing)                                    # :127-140
-    mS, vS, _, _ = _predict(g, devices, _levels(_dot(doT, getN(g))))
+function SATEDistributions(g::GPSLCObject, doT::Intervention; devices=nothing, baseline=nothing)                  # :127-140
+    mS, vS, _, _ = _level_predict(g, devices, _levels(_dot(doT, getN(g))), baseline)
     mS[:, 1], vS[:, 1]          # O(N^2) per posterior sample: the N x N covariance is never formed
 end
 
@@ -816,16 +865,16 @@ function _normals(n, spp, S, L, seed)
 end
 
 function sampleITE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64=10,
-                   seed::Union{Nothing,Integer}=nothing, devices=nothing)                                          # :86-89
+                   seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing)                        # :86-89
     n, S = getN(g), getNumPosteriorSamples(g)
     sd, z = _normals(n, samplesPerPosterior, S, 1, seed)
-    _, _, _, ite = _predict(g, devices, _levels(_dot(doT, n)); spp=samplesPerPosterior, seed=sd, z=z, want_draws=true)
+    _, _, _, ite = _level_predict(g, devices, _levels(_dot(doT, n)), baseline; spp=samplesPerPosterior, seed=sd, z=z, want_draws=true)
     ite[1, :, :]                                                          # n x (S * spp), sample outer / draw inner (:100-107)
 end
 
 function sampleSATE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64=10,
-                    seed::Union{Nothing,Integer}=nothing, devices=nothing)                                         # :108-111
-    MeanSATEs, VarSATEs = SATEDistributions(g, doT; devices=devices)
+                    seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing)                       # :108-111
+    MeanSATEs, VarSATEs = SATEDistributions(g, doT; devices=devices, baseline=baseline)
     seed === nothing || return GPSLCHip.sate_samples(MeanSATEs, VarSATEs, samplesPerPosterior; seed=UInt64(seed))
     z = randn(length(MeanSATEs) * samplesPerPosterior)
     GPSLCHip.sate_samples(MeanSATEs, VarSATEs, samplesPerPosterior; z=z)  # normal(mean, var): variance as sigma (:159)
