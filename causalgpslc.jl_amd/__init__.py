@@ -8,7 +8,7 @@ from ._lib import GPSLCError, GPSLCLibraryError, PosDefException, load as load_l
 from .api import (  # noqa: F401
     Context, GPSLCObject, HyperParameters, PREDICTION_COVARIANCE_NOISE,
     rbfKernelLog, rbfKernelLogScalar, logit, expit, processCov, likelihoodDistribution, extractParameters, conditionalITE, ITEDistributions, ITEsamples, conditionalSATE,
-    SATEDistributions, SATEsamples, sampleITE, sampleSATE, predictCounterfactualEffects,
+    SATEDistributions, SATEsamples, sampleITE, sampleSATE, predictCounterfactualEffects, groupWeights,
     summarizeEstimates, yLogpdf, gpLogpdf, nodesLogpdf, nodesDraw, mvnLogpdf, mvnDraw, predict, doTRange, getN, getNX, getNU, getNumPosteriorSamples,
 )
 from . import synth  # noqa: F401

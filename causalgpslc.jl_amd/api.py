@@ -68,6 +68,52 @@ def _baseline(baseline, L):
     raise ValueError(f"baseline must be a scalar or one value per level (L = {L}), got an array of shape {b.shape}")
 
 
+def _weight_row(w, n):
+    """One weight vector for n individuals -> (n,) float64.  Float (or integer) values are used as given; a Bool vector is a
+    group mask and becomes that group's average, ``mask / mask.sum()`` (an empty mask raises ValueError)."""
+    a = np.asarray(w)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError(f"weights must be a vector of length n = {n} or a (G, n) array, got a row of shape {a.shape}")
+    if a.dtype == np.bool_:
+        k = int(a.sum())
+        if k == 0:
+            raise ValueError("weights has an empty group mask: the average over nobody is undefined")
+        return a.astype(np.float64) / k
+    a = a.astype(np.float64)
+    if not np.all(np.isfinite(a)):
+        raise ValueError("weights has a non-finite entry")
+    return a
+
+
+def _weights(weights, n):
+    """The ``weights=`` of predict / SATEDistributions / sampleSATE -> ((G, n) float64 C-contiguous, is_vector): a length-n
+    vector (one weight column, results without a group axis) or a (G, n) array / a sequence of G rows, each row parsed by
+    ``_weight_row`` (Float rows as given, Bool rows as group masks).  Raises ValueError before anything runs on a device."""
+    if isinstance(weights, (list, tuple)) and len(weights) > 0 and np.ndim(weights[0]) == 1:
+        return np.ascontiguousarray(np.stack([_weight_row(r, n) for r in weights])), False
+    a = np.asarray(weights)
+    if a.ndim == 1:
+        return np.ascontiguousarray(_weight_row(a, n)[None, :]), True
+    if a.ndim == 2 and a.shape[0] >= 1 and a.shape[1] == n:
+        return np.ascontiguousarray(np.stack([_weight_row(r, n) for r in a])), False
+    raise ValueError(f"weights must be a vector of length n = {n} or a (G, n) array, got an array of shape {a.shape}")
+
+
+def groupWeights(labels):
+    """Group-average weights for a labelling of the n individuals (object labels of the hierarchy, strata, a treatment
+    indicator): returns (the sorted distinct labels (G,), W (G, n)) with W[g] = 1_{labels == label_g} / |group g| — the
+    ``weights=`` of predict / SATEDistributions / sampleSATE.  The groups partition the sample, so
+    sum_g (n_g / n) * mean_g is the meanSATE of the plain call."""
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.shape[0] == 0:
+        raise ValueError(f"labels must be a non-empty vector (one label per individual), got an array of shape {lab.shape}")
+    keys, inv = np.unique(lab, return_inverse=True)
+    W = np.zeros((keys.shape[0], lab.shape[0]))
+    W[inv, np.arange(lab.shape[0])] = 1.0
+    W /= W.sum(axis=1, keepdims=True)
+    return keys, W
+
+
 class Context:
     """RAII wrapper of gpslc_ctx (one per GPU and data set)."""
 
@@ -406,10 +452,12 @@ def conditionalSATE(MeanITE, CovITE):
     return float(np.sum(MeanITE) / n), float(np.sum(CovITE) / n ** 2)
 
 
-def SATEDistributions(g: GPSLCObject, doT, baseline=None):
+def SATEDistributions(g: GPSLCObject, doT, baseline=None, weights=None):
     """MeanSATEs (S,), VarSATEs (S,) (src/estimation.jl:127-140) — O(N^2) per sample on the GPU,
-    without materialising CovITE.  ``baseline`` = a scalar b: the contrast doT against b (see predict)."""
-    m, v, _ = predict(g, _levels(g, doT), baseline=baseline)
+    without materialising CovITE.  ``baseline`` = a scalar b: the contrast doT against b (see predict).  ``weights`` = a
+    length-n vector: the weighted effect w' ITE instead of the average over everybody, same shapes; a (G, n) array: (S, G)
+    each (see predict)."""
+    m, v, _ = predict(g, _levels(g, doT), baseline=baseline, weights=weights)
     return m[:, 0].copy(), v[:, 0].copy()
 
 
@@ -434,14 +482,21 @@ def _levels(g: GPSLCObject, doT):
 
 
 def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
-            want_draws=False, devices: Optional[Sequence[int]] = None, baseline=None):
+            want_draws=False, devices: Optional[Sequence[int]] = None, baseline=None, weights=None):
     """The ensemble entry point (gpslc_predict): returns MeanSATE (S, L), VarSATE (S, L) and, when
     asked, MeanITE (n, S, L) / draws (L, n, S*spp).  ``doTs``: L scalar levels (1-D), or an (L, n) array of L per-individual
     intervention vectors (gpslc_predict_vec).  ``devices`` = a list of GPU indices shards the posterior samples
     over one context per entry through ``gpslc_predict_multi`` (same results, bit for bit; scalar levels only).
     ``baseline`` = a scalar or L values b: level l becomes the contrast f(doTs[l]) - f(b[l]) between two scalar levels
     (gpslc_predict_contrast: "treatment a against treatment b", with its own covariance and draws) instead of
-    f(doTs[l]) - f(T); ``None`` is the plain call.  Scalar levels and one GPU only."""
+    f(doTs[l]) - f(T); ``None`` is the plain call.  Scalar levels and one GPU only.
+    ``weights`` = a length-n vector or a (G, n) array: the first two results become the weighted effects tau_w = w' ITE —
+    mean w' MeanITE and variance w' (CovITE + predictionCovarianceNoise I) w, the weights used as given (gpslc_predict_weighted;
+    no n x n covariance is formed) — of shape (S, L) for a vector and (S, L, G) for an array.  Float rows are taken as they are
+    (1/n everywhere is the SATE, a difference of two group averages the difference of two groups with its correct variance);
+    a Bool row is a group mask and means that group's average (``groupWeights`` builds them from labels).  With ``baseline``
+    the weighted contrast: a binary treatment, ``predict(g, [1.0], baseline=0.0, weights=(T == 1))`` is the ATT.  MeanITE and
+    the draws are unchanged.  Scalar levels and one GPU only."""
     n, S = g.getN(), g.getNumPosteriorSamples()
     doTs = np.asarray(doTs, dtype=np.float64)
     vec = doTs.ndim == 2
@@ -454,6 +509,13 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
         raise ValueError("baseline= needs scalar levels: contrasts of per-individual intervention vectors are not supported")
     if baseline is not None and devices is not None:
         raise NotImplementedError("contrasts are not sharded over devices: call predict without devices=")
+    Wm = wvec = None
+    if weights is not None:
+        if vec:
+            raise ValueError("weights= needs scalar levels: weighted effects of per-individual intervention vectors are not supported")
+        if devices is not None:
+            raise NotImplementedError("weighted effects are not sharded over devices: call predict without devices=")
+        Wm, wvec = _weights(weights, n)
     # vector levels: n x L column-major, doT[i + n*l]
     doTs = np.asfortranarray(doTs.T) if vec else np.ascontiguousarray(np.atleast_1d(doTs))
     L = doTs.shape[1] if vec else doTs.shape[0]
@@ -468,7 +530,16 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
         zz = _f(z)
         if zz.shape != (n, spp, S, L):
             raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
-    if base is not None:
+    if Wm is not None:
+        G = Wm.shape[0]
+        ms = np.empty((S, L, G), order="F")
+        vs = np.empty((S, L, G), order="F")
+        st = ctx.lib.gpslc_predict_weighted(ctx.h, S, *g._params(), L, _p(doTs), _p(base), G, _p(Wm),     # (G, n) C order =
+                                            float(g.hyperparams.predictionCovarianceNoise), int(spp),     # weights[i + n*g]
+                                            int(seed), _p(zz), _p(ms), _p(vs), _p(mi), _p(dr))
+        if wvec:
+            ms, vs = ms[:, :, 0], vs[:, :, 0]
+    elif base is not None:
         st = ctx.lib.gpslc_predict_contrast(ctx.h, S, *g._params(), L, _p(doTs), _p(base),
                                             float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
                                             _p(ms), _p(vs), _p(mi), _p(dr))
@@ -512,11 +583,17 @@ def sampleITE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, basel
     return ITEsamples(g, doT, samplesPerPosterior, z=z, seed=seed, baseline=baseline)
 
 
-def sampleSATE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None):
+def sampleSATE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None):
     """sampleSATE(g, doT; samplesPerPosterior=10) -> (S*spp,) (src/driver.jl:108-111); ``baseline``: the contrast doT
-    against that scalar level."""
-    m, v = SATEDistributions(g, doT, baseline=baseline)
-    return SATEsamples(m, v, samplesPerPosterior, z=z, seed=seed)
+    against that scalar level.  ``weights`` = a length-n vector: samples of the weighted effect, (S*spp,); a (G, n) array:
+    (G, S*spp), row g from SATEsamples of group g's means and variances with ``z[g]`` (``z``: (G, S*spp), or (S*spp,) shared
+    by every group) or the Philox seed ``seed + g``."""
+    m, v = SATEDistributions(g, doT, baseline=baseline, weights=weights)
+    if m.ndim == 1:
+        return SATEsamples(m, v, samplesPerPosterior, z=z, seed=seed)
+    zz = None if z is None else np.broadcast_to(np.asarray(z, dtype=np.float64), (m.shape[1], m.shape[0] * samplesPerPosterior))
+    return np.stack([SATEsamples(m[:, k], v[:, k], samplesPerPosterior, z=None if zz is None else zz[k], seed=seed + k)
+                     for k in range(m.shape[1])])
 
 
 def doTRange(minDoT, maxDoT, fidelity):

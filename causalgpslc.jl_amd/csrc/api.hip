@@ -670,6 +670,10 @@ struct PredictIO {
     const double* doT = nullptr;
     bool vec = false;                // vector levels: doT is n x L (level l at doT + n*l), not L scalars
     const double* base = nullptr;    // contrasts (device, L): level l is doT[l] against base[l] (scalar levels only)
+    // weighted effects: G weight columns (device, column fastest: W[g + G*j]); meanSATE / varSATE are then
+    // S x L x G — element (s, l, g) at s + S*(l + L*g) — of tau_w = w_g' ITE_l, the weights used as given (scalar levels only)
+    const double* W = nullptr;
+    int G = 0;
     double pred_noise = 0;
     int spp = 0;
     uint64_t seed = 0;
@@ -723,11 +727,11 @@ BatchPlan auto_batch(gpslc_ctx* c, int64_t S, int L, size_t per_sample_bytes, si
 
 // what one run_predict call computes and the sizes that follow from it (the same for all of its chunks)
 struct PredictShape {
-    int n, nt, L, naug, ntot;
+    int n, nt, L, R, naug, ntot;      // R: right-hand sides beside Y — one per level, or L*G with weight columns
     long long Np, tiles_per, nlow;   // padded N, tiles of A with its augmented rows, tiles of an nt x nt triangle
     bool with_sums, want_cov, want_draws, want_mean, unitB;     // unitB: full ITE covariance (CovITE, draws)
     PredictShape(const gpslc_ctx* c, const PredictIO& io)
-        : n((int)c->n), nt(c->nt), L(io.L), naug((L + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug), Np((long long)nt * GP_TS),
+        : n((int)c->n), nt(c->nt), L(io.L), R(io.W ? io.L * io.G : io.L), naug((R + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug), Np((long long)nt * GP_TS),
           tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2), with_sums(io.meanSATE || io.varSATE),
           want_cov(io.CovITEs != nullptr), want_draws(io.ite_draws != nullptr), want_mean(io.meanITE || io.MeanITEs || want_draws),
           unitB(want_cov || want_draws) {}
@@ -741,6 +745,7 @@ struct Chunk {
     TRef M{};                        // the tile matrices of A over `tiles`
     double *tiles = nullptr, *inv = nullptr, *part = nullptr, *bsum = nullptr, *ksum = nullptr, *sumdelta = nullptr;
     double *vpart = nullptr, *zwork = nullptr, *znode = nullptr;
+    double *bw = nullptr, *kw = nullptr, *wnorm2 = nullptr;      // weighted effects: B W, K W [nb][G][Np], w_g . w_g [nb][G]
     // unit B: a sub-batch of gs_max samples x lc_max levels; W, CovITE, the draws' normals, level-sweep staging, failure codes
     int lc_max = 0, gs_max = 0;
     double *Wt = nullptr, *Ct = nullptr, *zgen = nullptr, *zt = nullptr, *dtmp = nullptr;
@@ -769,9 +774,14 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     const size_t zimage_doubles = zimage ? (size_t)16 * (io.spp <= 16 ? 1 : io.spp <= 32 ? 2 : io.spp <= 64 ? 4 : 8) * sh.Np : 0;
     b.tiles = take(sh.tiles_per * GP_TSQ);
     b.inv = take((size_t)nt * GP_TSQ);
-    if (sh.with_sums) b.part = take(2 * nt * sh.Np);
+    if (sh.with_sums && !io.W) b.part = take(2 * nt * sh.Np);
     b.bsum = take(sh.Np); b.ksum = take(sh.Np);
-    b.sumdelta = take(std::max(L, 1));
+    b.sumdelta = take(std::max(sh.R, 1));
+    if (io.W) {      // the contrast form needs no K W
+        b.bw = take((size_t)io.G * sh.Np);
+        b.kw = io.base ? b.bw : take((size_t)io.G * sh.Np);
+        b.wnorm2 = take(io.G);
+    }
     if (io.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
     if (io.ndraw) b.znode = take(16 * sh.Np);                           // operand image of the node draw's normals
@@ -818,7 +828,7 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     GramArgs ga{};
     ga.X = io.X; ga.T = c->dT; ga.p = io.p; ga.s0 = s0;
     ga.n = n; ga.nX = io.nX; ga.nU = io.nU; ga.nt = nt; ga.M = ch.M; ga.part = ch.part;
-    ga.with_sums = sh.with_sums ? 1 : 0;
+    ga.with_sums = (sh.with_sums && !io.W) ? 1 : 0;      // weighted: the column sums come from launch_wsum instead
 #ifdef GPSLC_DIAG
     static const int gram_dbg = diag_env("GPSLC_GRAM_DBG", 0);
     static bool gram_dbg_done = false;
@@ -832,6 +842,13 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
 #endif
     ga.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
     ga.binary_t = (c->binary_t && io.nU == c->nU && io.nX == c->nX && io.Y == c->dY) ? 1 : 0;   // ctx data only
+    if (io.W) {      // weighted effects: B W and K W, one pass over the pairs for all columns and levels (independent of the tiles)
+        WsumArgs wa{};
+        wa.X = io.X; wa.T = c->dT; wa.p = io.p; wa.s0 = s0;
+        wa.n = n; wa.nX = io.nX; wa.nU = io.nU; wa.nt = nt; wa.G = io.G; wa.W = io.W;
+        wa.bw = ch.bw; wa.kw = ch.kw; wa.with_k = io.base ? 0 : 1; wa.binary_t = ga.binary_t;
+        launch_wsum(wa, nb, st);
+    }
     launch_gram(ga, nb, st);
 #ifdef GPSLC_DIAG
     if (ga.dbg) {      // GPSLC_GRAM_DBG: dump the first launch's per-workgroup stamps
@@ -853,9 +870,14 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     ra.doT_base = io.base;
     static const int epi_rows_on = diag_env("GPSLC_EPI_ROWS", 1);      // measurement switch (A/B of the extra tile update)
     const bool epi_rows = (sh.naug == 1) && epi_rows_on;     // single augmented tile row: the epilogue sums from the rows of R
-    const int live = (sh.with_sums ? sh.L : 0) + 1;          // right-hand sides: Y and one c_l per level
+    const int live = (sh.with_sums ? sh.R : 0) + 1;          // right-hand sides: Y and one c_l per level (and weight column)
     ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
-    launch_rhs(ra, nb, st);
+    if (io.W) {
+        ra.W = io.W; ra.G = io.G; ra.bw = ch.bw; ra.kw = ch.kw; ra.wnorm2 = ch.wnorm2;
+        launch_rhs_weighted(ra, nb, st);
+    } else {
+        launch_rhs(ra, nb, st);
+    }
     if (io.vec && sh.with_sums) launch_vec_sums(vec_args(c, io, sh, ch), nb, st);
     // NB: the MeanITE pass takes K alpha as Y - yNoise alpha (k_solve.hip, ite_mean_kernel): it relies on alpha solving EXACTLY
     // (K_gram + yNoise I) alpha = Y.  Any future jitter, robust fallback or different right-hand side in this factorisation must
@@ -872,11 +894,17 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
         factor_panels(c, *ch.s, ch.M, nt, sh.ntot, ch.inv, inv_bs, io.info + s0, 0, nb, live, epi_rows, 0);
     }
     EpiArgs ea{};
-    ea.M = ch.M; ea.n = n; ea.nt = nt; ea.naug = sh.naug; ea.L = sh.with_sums ? sh.L : 0; ea.s0 = s0; ea.S = io.S;
+    ea.M = ch.M; ea.n = n; ea.nt = nt; ea.naug = sh.naug; ea.L = sh.with_sums ? sh.R : 0; ea.s0 = s0; ea.S = io.S;
     ea.sumdelta = ch.sumdelta; ea.pred_noise = io.pred_noise;
     ea.meanSATE = io.meanSATE; ea.varSATE = io.varSATE; ea.logdet = io.logdet; ea.quad = io.quad;
     ea.from_rows = epi_rows ? 1 : 0;
-    launch_epilogue(ea, nb, st);
+    if (io.W) {      // weighted: mean / var from the weighted kernel; the plain one (no levels) keeps logdet and quad
+        launch_epilogue_weighted(ea, ch.wnorm2, sh.L, nb, st);
+        ea.L = 0; ea.meanSATE = nullptr; ea.varSATE = nullptr;
+        if (ea.logdet || ea.quad) launch_epilogue(ea, nb, st);
+    } else {
+        launch_epilogue(ea, nb, st);
+    }
     if (io.ndraw) {
         // one draw from N(0, A_s) per parameter set with the caller's normals: L_s z_s on the factor just computed — Gen's
         // mvnormal(zeros(n), cov) of an elliptical slice's auxiliary vector (src/inference.jl:225-232) and of the :logitT prior
@@ -1030,6 +1058,10 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     PredictIO io = io_in;
     if (io.base && io.vec) throw std::runtime_error("a contrast baseline cannot be combined with vector levels");
     if (io.base && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("contrasts need an fp64 context");
+    if (io.W && io.vec) throw std::runtime_error("weights cannot be combined with vector levels");
+    if (io.W && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("weighted effects need an fp64 context");
+    if (io.W && io.G < 1) throw std::runtime_error("weights without a weight column");
+    if (io.W && !io.meanSATE && !io.varSATE) { io.W = nullptr; io.G = 0; }      // nothing weighted is asked for
     if (io.nU < 0) io.nU = c->nU;
     if (io.nX < 0) io.nX = c->nX;
     if (!io.Y) { io.Y = c->dY; io.y_sstride = 0; }
@@ -1630,12 +1662,14 @@ static int predict_dev_inner(gpslc_ctx* c, int64_t S, const double* U, const dou
                              const double* tyLS, const double* yScale, const double* yNoise, int32_t L,
                              const double* doT, double pred_noise, int32_t spp, uint64_t seed, const double* z,
                              double* meanSATE, double* varSATE, double* meanITE, double* ite_draws,
-                             int64_t ens_off = 0, int64_t ens_S = 0, bool vec = false, const double* base = nullptr) {
+                             int64_t ens_off = 0, int64_t ens_S = 0, bool vec = false, const double* base = nullptr,
+                             int G = 0, const double* W = nullptr) {
     PredictIO io;
     io.S = S; io.p = SampleParams{U, uyLS, xyLS, tyLS, yScale, yNoise}; io.X = c->dX;
     io.L = L; io.doT = doT; io.vec = vec; io.base = base; io.pred_noise = pred_noise; io.spp = spp; io.seed = seed; io.z = z;
     io.meanSATE = meanSATE; io.varSATE = varSATE; io.meanITE = meanITE; io.ite_draws = ite_draws;
     io.ens_off = ens_off; io.ens_S = ens_S;
+    io.W = W; io.G = G;
     io.info = c->io.take<int>((size_t)S);
     run_predict(c, io);
     return first_info(c);
@@ -1669,9 +1703,11 @@ struct HostPlacement {
 static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
                         const double* yScale, const double* yNoise, int32_t L, const double* doT, double pred_noise, int32_t spp,
                         uint64_t seed, const double* z, double* meanSATE, double* varSATE, double* meanITE, double* ite_draws,
-                        const HostPlacement& pl, bool vec = false, const double* base = nullptr) {
+                        const HostPlacement& pl, bool vec = false, const double* base = nullptr, int G = 0,
+                        const double* weights = nullptr) {
     return guarded(c, [&]() {
         const size_t n = (size_t)c->n;
+        const size_t LR = weights ? (size_t)L * G : (size_t)L;     // meanSATE / varSATE columns: levels, or levels x weight columns
         const size_t s0 = (size_t)pl.s0, St = (size_t)pl.S_total;
         c->io.reset();
         const double* dU = c->nU ? up(c, U + n * c->nU * s0, n * c->nU * S) : nullptr;
@@ -1682,6 +1718,13 @@ static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* 
         const double* dyn = up(c, yNoise + s0, S);
         const double* ddo = up(c, doT, vec ? n * L : (size_t)L);     // vector levels: n x L
         const double* dba = base ? up(c, base, (size_t)L) : nullptr;  // contrasts: the L baselines
+        const double* dW = nullptr;
+        if (weights) {             // n x G host (weights[i + n*g]) -> column fastest on the device (W[g + G*i]: the kernels' layout)
+            std::vector<double> wt(n * (size_t)G);
+            for (size_t i = 0; i < n; ++i)
+                for (int g = 0; g < G; ++g) wt[(size_t)g + (size_t)G * i] = weights[i + n * (size_t)g];
+            dW = up(c, wt.data(), wt.size());
+        }
         const double* dz = nullptr;
         if (z && ite_draws) {      // caller's normals n x spp x S_total x L: level l of the shard is one run of n spp S doubles
             double* d = c->io.take<double>(n * spp * S * L);
@@ -1689,16 +1732,16 @@ static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* 
             HC(hipMemcpy2D(d, run, z + n * spp * s0, n * spp * St * sizeof(double), run, (size_t)L, hipMemcpyHostToDevice));
             dz = d;
         }
-        double* oms = meanSATE ? c->io.take<double>((size_t)S * L) : nullptr;
-        double* ovs = varSATE ? c->io.take<double>((size_t)S * L) : nullptr;
+        double* oms = meanSATE ? c->io.take<double>((size_t)S * LR) : nullptr;
+        double* ovs = varSATE ? c->io.take<double>((size_t)S * LR) : nullptr;
         double* omi = meanITE ? c->io.take<double>(n * S * L) : nullptr;
         double* odr = ite_draws ? c->io.take<double>((size_t)L * n * S * spp) : nullptr;
         int st = predict_dev_inner(c, S, dU, duy, dxy, dty, dys, dyn, L, ddo, pred_noise, spp, seed, dz,
-                                   oms, ovs, omi, odr, pl.ens_off, pl.ens_S, vec, dba);
+                                   oms, ovs, omi, odr, pl.ens_off, pl.ens_S, vec, dba, G, dW);
         if (st < 0) return st;
         const size_t sb = (size_t)S * sizeof(double);
-        if (meanSATE) HC(hipMemcpy2D(meanSATE + s0, St * sizeof(double), oms, sb, sb, (size_t)L, hipMemcpyDeviceToHost));
-        if (varSATE) HC(hipMemcpy2D(varSATE + s0, St * sizeof(double), ovs, sb, sb, (size_t)L, hipMemcpyDeviceToHost));
+        if (meanSATE) HC(hipMemcpy2D(meanSATE + s0, St * sizeof(double), oms, sb, sb, LR, hipMemcpyDeviceToHost));
+        if (varSATE) HC(hipMemcpy2D(varSATE + s0, St * sizeof(double), ovs, sb, sb, LR, hipMemcpyDeviceToHost));
         if (meanITE) copy_out_rows(c, meanITE + n * s0, n * St * sizeof(double), omi, n * sb, (size_t)L);
         // level-fastest tensor L x n x (S_total spp): a sample's columns are one contiguous run
         if (ite_draws) copy_out_large(c, ite_draws + (size_t)L * n * spp * s0, odr, sizeof(double) * (size_t)L * n * S * spp);
@@ -1782,6 +1825,30 @@ int gpslc_predict_contrast(gpslc_ctx* c, int64_t S, const double* U, const doubl
     pl.S_total = S;
     return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE, varSATE, meanITE,
                         ite_draws, pl, /*vec=*/false, doT_base);
+}
+
+// weighted effects (gpslc_predict_weighted): G >= 1 columns of n finite host weights each; scalar levels, fp64 contexts only
+int gpslc_predict_weighted(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                           const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
+                           const double* doT_base, int32_t G, const double* weights, double pred_noise, int32_t spp,
+                           uint64_t seed, const double* z, double* meanW, double* varW, double* meanITE, double* ite_draws) {
+    // gpslc_predict's checks up to doT (#10); doT_base_or_null is #11, G #12, weights #13, so spp is #15
+    int rc = predict_check(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, nullptr);
+    if (rc) return rc;
+    if ((rc = contrast_levels_check(c, doT, L, 10, "doT"))) return rc;
+    if (doT_base && (rc = contrast_levels_check(c, doT_base, L, 11, "doT_base"))) return rc;
+    if (G < 1) return bad_arg(c, 12, "G < 1");
+    if ((rc = contrast_levels_check(c, weights, c->n * (int64_t)G, 13, "weights"))) return rc;
+    if (ite_draws && spp < 1) return bad_arg(c, 15, "spp < 1 with ite_draws requested");
+    if (c->flags & GPSLC_FLAG_FP32_KERNEL) {
+        set_err(c, "weighted effects are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
+        return GPSLC_ERR_UNSUPPORTED;
+    }
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    HostPlacement pl;
+    pl.S_total = S;
+    return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanW, varW, meanITE,
+                        ite_draws, pl, /*vec=*/false, doT_base, G, weights);
 }
 
 int gpslc_shard_range(int64_t S, int32_t nblocks, int32_t k, int64_t* s0, int64_t* s1) {

@@ -182,8 +182,24 @@ struct RhsArgs {
                      // diagonal tile not at all — every reader of those tiles touches the live 16- / 32-row blocks only
     const double* doT_base;   // non-null: contrasts — level l is the pair (doT[l], doT_base[l]), c_l = (r^a - r^b) .* bsum and
                               // sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B
+    // weighted effects (launch_rhs_weighted only): G weight columns, right-hand side 1 + l + L*g is level l
+    // of column g; bw / kw [b][G][Np] from launch_wsum replace bsum / ksum, sumdelta is [b][L*G], wnorm2 [b][G] = w_g . w_g
+    const double* W; int G;   // device, column g fastest: W[g + G*j]
+    const double* bw; const double* kw; double* wnorm2;
 };
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
+void launch_rhs_weighted(const RhsArgs& r, int nbatch, hipStream_t st);
+
+// weighted column sums BW = B W, KW = K W of a chunk (k_wsum.hip): one pass over the pairs per sample for all G columns
+struct WsumArgs {
+    const double* X; const double* T; SampleParams p; long long s0;
+    int n, nX, nU, nt, G;
+    const double* W;       // device, column g fastest: W[g + G*j]
+    double* bw; double* kw;   // [b][G][Np]; kw is not written when with_k == 0 (contrasts need BW only)
+    int with_k;
+    int binary_t;          // as GramArgs::binary_t: the e_ij of the K that is factorised
+};
+void launch_wsum(const WsumArgs& a, int nbatch, hipStream_t st);
 
 struct EpiArgs {
     TRef M; int n, nt, naug, L; long long s0; long long S;
@@ -194,6 +210,9 @@ struct EpiArgs {
                      // augmented diagonal tile is then never updated (factor_panels(..., skip_aug_diag))
 };
 void launch_epilogue(const EpiArgs& e, int nbatch, hipStream_t st);
+// weighted effects: e.L counts the wL levels x G right-hand sides (row 1 + l + wL*g), meanSATE / varSATE receive
+// mean = z.v and var = (sumdelta - v.v) + pred_noise * wnorm2[b][g] — no division by n; logdet / quad are not written
+void launch_epilogue_weighted(const EpiArgs& e, const double* wnorm2, int wL, int nbatch, hipStream_t st);
 
 struct BackArgs {
     TRef M; const double* inv; long long inv_bstride; int nt; int naug;

@@ -6,7 +6,8 @@
 //                      K = B.*E that the SATE path needs.
 //   rhs_prepare/tiles  column sums -> augmented right-hand sides [Y, c(1..L)] and sum(Delta).  CON: the contrast form of
 //                      both (level l = the pair (doT[l], doT_base[l])).
-//   epilogue           Schur complement of the augmented block -> MeanSATE, VarSATE, logdet, quad.
+//   rhs_w_prepare/tiles the same for weighted effects: G weight columns x L levels from bw = B w, kw = K w (k_wsum.hip).
+//   epilogue           Schur complement of the augmented block -> MeanSATE, VarSATE, logdet, quad; epilogue_w: the weighted form.
 //   rbf_log / process_cov  the two src/kernel.jl entry points as stand-alone dense kernels.
 #include "gpslc_internal.h"
 #include "gp_math.h"
@@ -385,6 +386,102 @@ void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Weighted effects tau_w = w' ITE: G weight columns, right-hand side q = 1 + l + L*g is level l of column g.
+// With bw = B w, kw = K w from launch_wsum (B, K symmetric):
+//   c = D' w,  c_j = r_j bw_j - kw_j            w' Delta w = sum_j w_j ((kw_j - 2 r_j bw_j) + bw_j)
+//   CON: c_j = (r^a_j - r^b_j) bw_j             w' Delta w = ((1 - rho) + (1 - rho)) sum_j w_j bw_j
+// rhs_w_prepare: one workgroup per (right-hand side, sample): sumdelta[b][l + L*g], and (l == 0) wnorm2[b][g] = w_g . w_g;
+// the sums run over the threads' strided j in a fixed tree.  r == 1 (every T equal to doT) and kw == bw give an exact 0.0
+// term by term; a == b gives rho == 1 and 0.0 * sum.
+// ---------------------------------------------------------------------------------------
+template <bool CON>
+__global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const int qq = blockIdx.x, b = blockIdx.y;
+    const int l = qq % a.L, g = qq / a.L;
+    const long long s = a.s0 + b;
+    const int Np = a.nt * GP_TS;
+    const double* bs = a.bw + ((long long)b * a.G + g) * Np;
+    const double* ks = a.kw + ((long long)b * a.G + g) * Np;
+    const double tl = a.tyLS[s];
+    const double wt = 1.0 / (tl * tl);
+    const double dot = a.doT[l];
+    double acc = 0.0, ww = 0.0;
+    for (int j = tid; j < a.n; j += 256) {
+        const double w = a.W[(long long)j * a.G + g];
+        ww = fma(w, w, ww);
+        if (CON) {
+            acc += w * bs[j];
+        } else {
+            const double dt = a.T[j] - dot;
+            const double r = gp_exp_neg(-((dt * dt) * wt));
+            acc += w * ((ks[j] - 2.0 * r * bs[j]) + bs[j]);
+        }
+    }
+    const double tot = block_sum_256(acc, red);
+    if (l == 0) {
+        const double w2 = block_sum_256(ww, red);
+        if (tid == 0) a.wnorm2[(long long)b * a.G + g] = w2;
+    }
+    if (tid != 0) return;
+    if (CON) {
+        const double dab = dot - a.doT_base[l];
+        const double rho = gp_exp_neg(-((dab * dab) * wt));
+        a.sumdelta[(long long)b * a.L * a.G + qq] = ((1.0 - rho) + (1.0 - rho)) * tot;
+    } else {
+        a.sumdelta[(long long)b * a.L * a.G + qq] = tot;
+    }
+}
+
+// rhs_w_tiles: the augmented row tiles of the weighted right-hand sides, in the three layouts of rhs_tiles_kernel (16 / 32 live
+// rows, a full augmented tile row, several tile rows); the level rows take rhs_level_value with column g's bw / kw.
+template <bool CON>
+__global__ __launch_bounds__(256) void rhs_w_tiles_kernel(RhsArgs a) {
+    const int tid = threadIdx.x;
+    const int j = blockIdx.x, au = blockIdx.y, b = blockIdx.z;
+    if (j > a.nt + au) return;
+    const long long s = a.s0 + b;
+    double* tile = tref_tile(a.M, b, a.nt + au, j);
+    if (j >= a.nt) {
+        if (a.live_rows > 0) return;
+        for (int idx = tid; idx < GP_TSQ; idx += 256) tile[idx] = 0.0;
+        return;
+    }
+    const int Np = a.nt * GP_TS;
+    const int R = a.L * a.G;
+    const double tl = a.tyLS[s];
+    const double wt = 1.0 / (tl * tl);
+    // live_rows > 0: all 32 rows of the live block are written (see rhs_tiles_kernel); else the whole tile
+    const int sh = a.live_rows > 0 ? 5 : 7;
+    for (int idx = tid; idx < (GP_TS << sh); idx += 256) {
+        const int c = idx >> sh, q = idx & ((1 << sh) - 1);
+        const int gq = au * GP_TS + q;        // right-hand side index
+        const int gj = j * GP_TS + c;         // instance index
+        double v = 0.0;
+        if (gj < a.n) {
+            if (gq == 0) v = a.Y[s * a.y_sstride + gj];
+            else if (gq <= R) {
+                const int l = (gq - 1) % a.L, g = (gq - 1) / a.L;
+                const long long o = ((long long)b * a.G + g) * Np;
+                v = rhs_level_value<CON>(a, l, gj, wt, a.bw + o, a.kw + o);
+            }
+        }
+        tile[c * GP_TS + q] = v;
+    }
+}
+
+template <bool CON>
+static void launch_rhs_w_t(const RhsArgs& r, int nbatch, hipStream_t st) {
+    hipLaunchKernelGGL(rhs_w_prepare_kernel<CON>, dim3(r.L * r.G, nbatch), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(rhs_w_tiles_kernel<CON>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
+}
+void launch_rhs_weighted(const RhsArgs& r, int nbatch, hipStream_t st) {
+    if (r.doT_base) launch_rhs_w_t<true>(r, nbatch, st);
+    else launch_rhs_w_t<false>(r, nbatch, st);
+}
+
+// ---------------------------------------------------------------------------------------
 // epilogue: after the augmented factorisation tile (nt+a, nt+a') holds G = -R R^T with
 // R = [z, w_1 .. w_L] (z = L^-1 Y, w_l = L^-1 c_l).  One workgroup per sample.
 // ---------------------------------------------------------------------------------------
@@ -480,6 +577,50 @@ __global__ __launch_bounds__(256) void epilogue_kernel(EpiArgs e) {
 
 void launch_epilogue(const EpiArgs& e, int nbatch, hipStream_t st) {
     hipLaunchKernelGGL(epilogue_kernel, dim3(nbatch), dim3(256), 0, st, e);
+}
+
+// The weighted form: right-hand side q = 1 + l + wL*g is level l of weight column g, and
+//   mean = z . v_q        var = (sumdelta_q - v_q . v_q) + pred_noise * wnorm2[g]
+// — the weights are used as given, nothing is divided by n.  from_rows: wave w sums q = 1 + w, 5 + w, ... from the rows of R
+// (lanes stride the columns, fixed butterfly); else from the Schur tiles -R R^T.  The plain epilogue, launched beside it with
+// L = 0, writes logdet and quad.
+__global__ __launch_bounds__(256) void epilogue_w_kernel(EpiArgs e, const double* wnorm2, int wL) {
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const long long s = e.s0 + b;
+    const int G = e.L / wL;
+    auto put = [&](int q, double zv, double vv) {
+        const int l = q - 1;
+        const double sd = e.sumdelta[(long long)b * e.L + l];
+        if (e.meanSATE) e.meanSATE[s + e.S * l] = zv;
+        if (e.varSATE) e.varSATE[s + e.S * l] = (sd - vv) + e.pred_noise * wnorm2[(long long)b * G + l / wL];
+    };
+    if (e.from_rows) {
+        const int lane = tid & 63, wave = tid >> 6;
+        const int ncol = e.nt * GP_TS;
+        for (int q = 1 + wave; q <= e.L; q += 4) {
+            double zv = 0.0, vv = 0.0;
+            for (int i = lane; i < ncol; i += 64) {
+                const double* col = tref_tile(e.M, b, e.nt, i >> 7) + (long long)(i & 127) * GP_TS;
+                const double z = col[0], v = col[q];
+                zv = fma(z, v, zv);
+                vv = fma(v, v, vv);
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) { zv += __shfl_xor(zv, o, 64); vv += __shfl_xor(vv, o, 64); }
+            if (lane == 0) put(q, zv, vv);
+        }
+        return;
+    }
+    for (int l = tid; l < e.L; l += 256) {
+        const int q = 1 + l, au = q >> 7, qq = q & 127;
+        const double zv = -tref_tile(e.M, b, e.nt + au, e.nt)[0 * GP_TS + qq];
+        const double vv = -tref_tile(e.M, b, e.nt + au, e.nt + au)[qq * GP_TS + qq];
+        put(q, zv, vv);
+    }
+}
+void launch_epilogue_weighted(const EpiArgs& e, const double* wnorm2, int wL, int nbatch, hipStream_t st) {
+    hipLaunchKernelGGL(epilogue_w_kernel, dim3(nbatch), dim3(256), 0, st, e, wnorm2, wL);
 }
 
 // ---------------------------------------------------------------------------------------

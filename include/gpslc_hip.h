@@ -267,6 +267,35 @@ int gpslc_predict_contrast(gpslc_ctx* ctx, int64_t S, const double* U, const dou
                            double pred_noise, int32_t spp, uint64_t seed, const double* z_or_null,
                            double* meanSATE, double* varSATE, double* meanITE, double* ite_draws);
 
+/* Weighted average effects over groups: tau_w = w' ITE for G weight columns w_g (n values each), the weights used AS GIVEN (no
+ * division by n): w = 1/n is the SATE, w = 1_A/|A| the average over a group A (the treated: the ATT; one object of the
+ * hierarchy; a stratum), w = 1_A/|A| - 1_B/|B| the difference of two groups with its correct variance (the two group effects
+ * are correlated), w = e_i one individual.  For every posterior sample s, level l and column g
+ *     meanW = w' MeanITE,    varW = w' (Symmetric(CovITE) + pred_noise*I) w        (src/estimation.jl:46-47, :82)
+ * without forming CovITE: with B = yScale exp(Lu + Lx), K = B .* E, bw = B w, kw = K w (one pass over the pairs per sample for all
+ * columns and levels), r_j = exp(-(T_j - doT)^2 / tyLS^2):
+ *     c = D' w, c_j = r_j bw_j - kw_j;   w' Delta w = sum_j w_j ((kw_j - 2 r_j bw_j) + bw_j);
+ *     v = L^-1 c (one more right-hand side of the factorisation of K + yNoise I = L L');
+ *     meanW = v . L^-1 Y,   varW = (w' Delta w - v . v) + pred_noise * (w . w).
+ * doT_base_or_null == NULL: the estimand of gpslc_predict, f_i(doT) - f_i(T_i).  Otherwise the contrast of gpslc_predict_contrast,
+ * f_i(a) - f_i(b) with (a, b) = (doT[l], doT_base[l]): c_j = (r^a_j - r^b_j) bw_j, w' Delta w = ((1 - rho) + (1 - rho)) sum_j w_j bw_j
+ * (no kw); a binary treatment, the pair (1, 0) and the mask of the treated give the ATT.
+ *   weights   n x G host, weights[i + n*g]; every entry finite (else -13), G >= 1 (else -12)
+ *   meanW, varW   S x L x G: element (s, l, g) at s + S*(l + L*g); either may be NULL
+ *   meanITE, ite_draws   what gpslc_predict / gpslc_predict_contrast return for the same levels (one call serves both)
+ * doT and doT_base are L finite host values each (else -10 / -11); ite_draws with spp < 1 is -15.  Everything else — the other
+ * arguments, the normals, chunking, the schedule and gpslc_last_info — is gpslc_predict's.  Exact identities: a zero column gives
+ * meanW == 0.0 and varW == 0.0; a level with a == b, or T_i == doT for every i, gives meanW == 0.0 and varW == pred_noise * (w . w).
+ * Results do not depend on chunking, streams or the schedule and are identical from run to run.  Scalar levels and fp64 only: a ctx
+ * created with GPSLC_FLAG_FP32_KERNEL returns GPSLC_ERR_UNSUPPORTED.  Not sharded (gpslc_predict_multi is unchanged).
+ *  */
+int gpslc_predict_weighted(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                           const double* xyLS, const double* tyLS, const double* yScale,
+                           const double* yNoise, int32_t L, const double* doT, const double* doT_base_or_null,
+                           int32_t G, const double* weights, double pred_noise, int32_t spp, uint64_t seed,
+                           const double* z_or_null, double* meanW, double* varW, double* meanITE,
+                           double* ite_draws);
+
 /* The same call sharded over several GPUs of one node: what the loop of predictCounterfactualEffects (src/prediction.jl:30-33)
  * over the posterior samples (src/estimation.jl:78-84) becomes when the ensemble is partitioned.  ctxs[0..nctx) are
  * DISTINCT contexts created with the same (n, nX, nU), one per device (gpslc_create(&ctx_k, device_k, ...)), each holding the data

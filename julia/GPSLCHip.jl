@@ -293,6 +293,31 @@ function predict_contrast(c::Ctx, p::Pack, doT::Vector{Float64}, doT_base::Vecto
     mS, vS, mI, dr
 end
 
+"""Weighted average effects over groups (gpslc_predict_weighted): column g of `weights` (n x G) is a weight vector w_g, used as
+given, and the first two results are S x L x G arrays of w_g' MeanITE and w_g' (CovITE + pred_noise I) w_g — w = 1/n is the SATE,
+1_A/|A| a group average (the treated: the ATT), a difference of two such the difference of two groups with its correct variance.
+`doT_base === nothing`: the estimand of `predict`; a vector: the contrast of `predict_contrast`.  MeanITE and the draws are
+those of `predict` / `predict_contrast` for the same levels."""
+function predict_weighted(c::Ctx, p::Pack, doT::Vector{Float64}, doT_base::Union{Nothing,Vector{Float64}}, weights::Matrix{Float64},
+                          pred_noise::Float64; spp::Integer=0, seed::Integer=0, z=nothing, want_mean_ite::Bool=false,
+                          want_draws::Bool=false)
+    S, L, n, G = length(p.tyLS), length(doT), c.n, size(weights, 2)
+    size(weights, 1) == n || throw(DimensionMismatch("weights has $(size(weights, 1)) rows, n = $n"))
+    doT_base === nothing || length(doT_base) == L || throw(DimensionMismatch("doT_base has length $(length(doT_base)), L = $L"))
+    mW, vW = Array{Float64}(undef, S, L, G), Array{Float64}(undef, S, L, G)
+    mI = want_mean_ite ? Array{Float64}(undef, n, S, L) : nothing
+    dr = want_draws ? Array{Float64}(undef, L, n, S * spp) : nothing
+    zf = f64(z)
+    GC.@preserve p doT doT_base weights zf mW vW mI dr check(c, ccall((:gpslc_predict_weighted, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Int32, UInt64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        L, pointer(doT), ptr(doT_base), G, pointer(weights), pred_noise, spp, seed, ptr(zf),
+        pointer(mW), pointer(vW), ptr(mI), ptr(dr)))
+    mW, vW, mI, dr
+end
+
 """`predict` sharded over several GPUs of one node — `cs` = one context per device (`Ctx(n, nX, nU; device=k)`, each with
 the data: `set_data!` on every one), the posterior samples split into contiguous blocks, one host thread per context inside the
 library, every device copying its block of the results into these host arrays.  Same results as `predict(cs[1], …)` over all S
@@ -728,6 +753,28 @@ function _level_predict(g::GPSLCObject, devices, lv, baseline; kw...)
                               g.hyperparams.predictionCovarianceNoise; kw...)
 end
 
+# `weights=` of SATEDistributions / sampleSATE: nothing = the average over everybody; a length-n vector or an n x G matrix of
+# weights used as given (a Bool vector / matrix is a mask: that group's average), gpslc_predict_weighted — scalar doT, one GPU only
+_weight_column(w::AbstractVector{Bool}) = (any(w) || throw(ArgumentError("weights= has an empty group mask")); Float64.(w) ./ count(w))
+_weight_column(w::AbstractVector{<:Real}) = Vector{Float64}(w)
+_weights(w::AbstractVector, n) = _weights(reshape(w, :, 1), n)
+function _weights(w::AbstractMatrix, n)
+    size(w, 1) == n || throw(ArgumentError("weights= needs one weight per individual: $(size(w, 1)) rows, n = $n"))
+    Wm = Matrix{Float64}(undef, n, size(w, 2))
+    for g in 1:size(w, 2)
+        Wm[:, g] = _weight_column(w[:, g])
+    end
+    Wm
+end
+function _weighted_predict(g::GPSLCObject, devices, lv, baseline, weights)
+    lv isa Vector{Float64} || throw(ArgumentError("weights= needs a scalar doT: weighted effects of per-individual intervention vectors are not supported"))
+    devices === nothing || throw(ArgumentError("weighted effects are not sharded over devices: pass devices=nothing"))
+    base = baseline === nothing ? nothing : fill(_baseline(baseline), length(lv))
+    mW, vW, _, _ = GPSLCHip.predict_weighted(ctx(g), posterior_pack(g), lv, base, _weights(weights, getN(g)),
+                                             g.hyperparams.predictionCovarianceNoise)
+    mW, vW
+end
+
 """ctx(g): the device context holding g.X, g.T, g.Y (src/types.jl:249-258), created on first use."""
 ctx(g::GPSLCObject) = _device_side(g).ctx
 
@@ -846,7 +893,11 @@ function ITEDistributions(g::GPSLCObject, doT::Intervention; baseline=nothing)  
     GPSLCHip.ite_distributions_contrast(ctx(g), posterior_pack(g), d, _baseline(baseline), pn)
 end
 
-function SATEDistributions(g::GPSLCObject, doT::Intervention; devices=nothing, baseline=nothing)                  # :127-140
+function SATEDistributions(g::GPSLCObject, doT::Intervention; devices=nothing, baseline=nothing, weights=nothing)  # :127-140
+    if weights !== nothing       # weighted average effects: (S,) for a weight vector, S x G for an n x G matrix
+        mW, vW = _weighted_predict(g, devices, _levels(_dot(doT, getN(g))), baseline, weights)
+        return weights isa AbstractVector ? (mW[:, 1, 1], vW[:, 1, 1]) : (mW[:, 1, :], vW[:, 1, :])
+    end
     mS, vS, _, _ = _level_predict(g, devices, _levels(_dot(doT, getN(g))), baseline)
     mS[:, 1], vS[:, 1]          # O(N^2) per posterior sample: the N x N covariance is never formed
 end
@@ -873,8 +924,15 @@ function sampleITE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64
 end
 
 function sampleSATE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64=10,
-                    seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing)                       # :108-111
-    MeanSATEs, VarSATEs = SATEDistributions(g, doT; devices=devices, baseline=baseline)
+                    seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing, weights=nothing)      # :108-111
+    MeanSATEs, VarSATEs = SATEDistributions(g, doT; devices=devices, baseline=baseline, weights=weights)
+    if MeanSATEs isa AbstractMatrix      # an n x G weight matrix: G x (S * spp), group g on the Philox seed `seed + g - 1`
+        G = size(MeanSATEs, 2)
+        rows = [seed === nothing ?
+                GPSLCHip.sate_samples(MeanSATEs[:, k], VarSATEs[:, k], samplesPerPosterior; z=randn(size(MeanSATEs, 1) * samplesPerPosterior)) :
+                GPSLCHip.sate_samples(MeanSATEs[:, k], VarSATEs[:, k], samplesPerPosterior; seed=UInt64(seed) + UInt64(k - 1)) for k in 1:G]
+        return permutedims(reduce(hcat, rows))
+    end
     seed === nothing || return GPSLCHip.sate_samples(MeanSATEs, VarSATEs, samplesPerPosterior; seed=UInt64(seed))
     z = randn(length(MeanSATEs) * samplesPerPosterior)
     GPSLCHip.sate_samples(MeanSATEs, VarSATEs, samplesPerPosterior; z=z)  # normal(mean, var): variance as sigma (:159)
