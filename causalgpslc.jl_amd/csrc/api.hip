@@ -662,23 +662,36 @@ void factor_panels(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int ntot,
     }
 }
 
-struct PredictIO {
+// One prediction call is described once, by three pieces: the extern "C" entry points fill them with the caller's pointers
+// (PredictRequest: host or device, as given) and run_predict reads them with device pointers (PredictIO).
+struct Posterior {                   // the S posterior samples of the call
     int64_t S = 0;
-    SampleParams p{};
-    const double* X = nullptr;   // device X to use (ctx or override)
+    SampleParams p{};                // the six per-sample arrays
+};
+struct Levels {
     int L = 0;
     const double* doT = nullptr;
     bool vec = false;                // vector levels: doT is n x L (level l at doT + n*l), not L scalars
-    const double* base = nullptr;    // contrasts (device, L): level l is doT[l] against base[l] (scalar levels only)
-    // weighted effects: G weight columns (device, column fastest: W[g + G*j]); meanSATE / varSATE are then
-    // S x L x G — element (s, l, g) at s + S*(l + L*g) — of tau_w = w_g' ITE_l, the weights used as given (scalar levels only)
-    const double* W = nullptr;
+    const double* base = nullptr;    // contrasts (L): level l is doT[l] against base[l] (scalar levels only)
+    // weighted effects: G weight columns — the caller's W[i + n*g] on the host, column fastest (W[g + G*j]) on the
+    // device; meanSATE / varSATE are then S x L x G — element (s, l, g) at s + S*(l + L*g) — of tau_w = w_g' ITE_l, the weights
+    // used as given (scalar levels only)
     int G = 0;
+    const double* W = nullptr;
+};
+struct DrawsAndOutputs {
     double pred_noise = 0;
     int spp = 0;
     uint64_t seed = 0;
     const double* z = nullptr;
     double *meanSATE = nullptr, *varSATE = nullptr, *meanITE = nullptr, *ite_draws = nullptr;
+};
+
+struct PredictIO {
+    Posterior post;
+    Levels lv;
+    DrawsAndOutputs out;
+    const double* X = nullptr;   // device X to use (ctx or override)
     double *logdet = nullptr, *quad = nullptr;
     // ITEDistributions-style outputs (single level): MeanITEs S x n, CovITEs S x n x n
     double *MeanITEs = nullptr, *CovITEs = nullptr;
@@ -731,10 +744,10 @@ struct PredictShape {
     long long Np, tiles_per, nlow;   // padded N, tiles of A with its augmented rows, tiles of an nt x nt triangle
     bool with_sums, want_cov, want_draws, want_mean, unitB;     // unitB: full ITE covariance (CovITE, draws)
     PredictShape(const gpslc_ctx* c, const PredictIO& io)
-        : n((int)c->n), nt(c->nt), L(io.L), R(io.W ? io.L * io.G : io.L), naug((R + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug), Np((long long)nt * GP_TS),
-          tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2), with_sums(io.meanSATE || io.varSATE),
-          want_cov(io.CovITEs != nullptr), want_draws(io.ite_draws != nullptr), want_mean(io.meanITE || io.MeanITEs || want_draws),
-          unitB(want_cov || want_draws) {}
+        : n((int)c->n), nt(c->nt), L(io.lv.L), R(io.lv.W ? io.lv.L * io.lv.G : io.lv.L), naug((R + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug),
+          Np((long long)nt * GP_TS), tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2),
+          with_sums(io.out.meanSATE || io.out.varSATE), want_cov(io.CovITEs != nullptr), want_draws(io.out.ite_draws != nullptr),
+          want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws) {}
 };
 
 // one chunk of a call: samples s0 .. s0 + nb - 1 on one stream slot, and the buffers carve_chunk takes for it from the slot's arena
@@ -750,6 +763,7 @@ struct Chunk {
     int lc_max = 0, gs_max = 0;
     double *Wt = nullptr, *Ct = nullptr, *zgen = nullptr, *zt = nullptr, *dtmp = nullptr;
     int* pinfo = nullptr;
+    SampleGrid grid{};               // the chunk's samples and feature blocks, as every RBF-evaluating kernel takes them
 };
 
 struct ChunkBytes { size_t per_sample = 1024, per_pair = 0, per_level = 0; };    // 1 KiB: the 256-byte alignment of each buffer
@@ -770,28 +784,28 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     // spp <= 128: the streaming draw kernel reads the unit's normals (caller's or Philox) from an operand image of 16 Np doubles
     // per block of 16 draws (DrawArgs::zt); per unit: 1 / 2 / 4 / 8 blocks of 16 draws (draws_nq, k_solve.hip: the stream
     // kernel's template parameter)
-    const bool zimage = sh.want_draws && io.spp <= 128;
-    const size_t zimage_doubles = zimage ? (size_t)16 * (io.spp <= 16 ? 1 : io.spp <= 32 ? 2 : io.spp <= 64 ? 4 : 8) * sh.Np : 0;
+    const bool zimage = sh.want_draws && io.out.spp <= 128;
+    const size_t zimage_doubles = zimage ? (size_t)16 * (io.out.spp <= 16 ? 1 : io.out.spp <= 32 ? 2 : io.out.spp <= 64 ? 4 : 8) * sh.Np : 0;
     b.tiles = take(sh.tiles_per * GP_TSQ);
     b.inv = take((size_t)nt * GP_TSQ);
-    if (sh.with_sums && !io.W) b.part = take(2 * nt * sh.Np);
+    if (sh.with_sums && !io.lv.W) b.part = take(2 * nt * sh.Np);
     b.bsum = take(sh.Np); b.ksum = take(sh.Np);
     b.sumdelta = take(std::max(sh.R, 1));
-    if (io.W) {      // the contrast form needs no K W
-        b.bw = take((size_t)io.G * sh.Np);
-        b.kw = io.base ? b.bw : take((size_t)io.G * sh.Np);
-        b.wnorm2 = take(io.G);
+    if (io.lv.W) {      // the contrast form needs no K W
+        b.bw = take((size_t)io.lv.G * sh.Np);
+        b.kw = io.lv.base ? b.bw : take((size_t)io.lv.G * sh.Np);
+        b.wnorm2 = take(io.lv.G);
     }
-    if (io.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
+    if (io.lv.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
     if (io.ndraw) b.znode = take(16 * sh.Np);                           // operand image of the node draw's normals
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
     if (!sh.unitB) return by;
     by.per_pair = (size_t)((long long)nt * nt + sh.nlow) * GP_TSQ * 8;
     if (sh.want_draws) {
-        by.per_pair += (zimage ? zimage_doubles * 8 + 256 : (io.z ? 0 : (size_t)io.spp * n * 8 + 256)) +
-                       (L > 1 ? (size_t)io.spp * n * 8 + 256 : 0) + sizeof(int) + 256;
-        by.per_level = (size_t)io.spp * n * 8;
+        by.per_pair += (zimage ? zimage_doubles * 8 + 256 : (io.out.z ? 0 : (size_t)io.out.spp * n * 8 + 256)) +
+                       (L > 1 ? (size_t)io.out.spp * n * 8 + 256 : 0) + sizeof(int) + 256;
+        by.per_level = (size_t)io.out.spp * n * 8;
     }
     if (!ar) return by;
     b.lc_max = std::min(L, Bb);                      // levels per sub-batch
@@ -801,19 +815,18 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     // draws: the library's own normals of one sub-batch (generated once per unit), and for a level sweep the staging buffer
     // [sample][level][d][i] that is rearranged into the level-fastest tensor sample group by group (per unit of the sub-batch:
     // max(1, Bb / L) samples x L levels <= Bb pairs, or one sample's L > Bb levels — per_level)
-    if (sh.want_draws && !io.z && !zimage) b.zgen = ar->take<double>((size_t)Bb * io.spp * n);
+    if (sh.want_draws && !io.out.z && !zimage) b.zgen = ar->take<double>((size_t)Bb * io.out.spp * n);
     if (zimage) b.zt = ar->take<double>((size_t)Bb * zimage_doubles);
-    if (sh.want_draws && L > 1) b.dtmp = ar->take<double>((size_t)b.gs_max * L * io.spp * n);
+    if (sh.want_draws && L > 1) b.dtmp = ar->take<double>((size_t)b.gs_max * L * io.out.spp * n);
     // failure codes of the CovITE factors, one per pair of a sub-batch (folded into io.info after each sub-batch)
     if (sh.want_draws) b.pinfo = ar->take<int>((size_t)Bb);
     return by;
 }
 
 // the vector-level kernels' arguments of a chunk (doT is n x L: level l at doT + n*l)
-VecArgs vec_args(const gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
-    VecArgs va{};
-    va.X = io.X; va.T = c->dT; va.p = io.p; va.s0 = ch.s0;
-    va.n = sh.n; va.nX = io.nX; va.nU = io.nU; va.nt = sh.nt; va.L = sh.L; va.doT = io.doT;
+VecArgs vec_args(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    VecArgs va{ch.grid};
+    va.L = sh.L; va.doT = io.lv.doT;
     va.M = ch.M; va.part = ch.vpart; va.sumdelta = ch.sumdelta;
     va.Y = io.Y; va.y_sstride = io.y_sstride;
     return va;
@@ -825,10 +838,9 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     hipStream_t st = ch.s->st;
     const int n = sh.n, nt = sh.nt, nb = ch.nb;
     const int64_t s0 = ch.s0;
-    GramArgs ga{};
-    ga.X = io.X; ga.T = c->dT; ga.p = io.p; ga.s0 = s0;
-    ga.n = n; ga.nX = io.nX; ga.nU = io.nU; ga.nt = nt; ga.M = ch.M; ga.part = ch.part;
-    ga.with_sums = (sh.with_sums && !io.W) ? 1 : 0;      // weighted: the column sums come from launch_wsum instead
+    GramArgs ga{ch.grid};
+    ga.M = ch.M; ga.part = ch.part;
+    ga.with_sums = (sh.with_sums && !io.lv.W) ? 1 : 0;      // weighted: the column sums come from launch_wsum instead
 #ifdef GPSLC_DIAG
     static const int gram_dbg = diag_env("GPSLC_GRAM_DBG", 0);
     static bool gram_dbg_done = false;
@@ -842,11 +854,10 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
 #endif
     ga.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
     ga.binary_t = (c->binary_t && io.nU == c->nU && io.nX == c->nX && io.Y == c->dY) ? 1 : 0;   // ctx data only
-    if (io.W) {      // weighted effects: B W and K W, one pass over the pairs for all columns and levels (independent of the tiles)
-        WsumArgs wa{};
-        wa.X = io.X; wa.T = c->dT; wa.p = io.p; wa.s0 = s0;
-        wa.n = n; wa.nX = io.nX; wa.nU = io.nU; wa.nt = nt; wa.G = io.G; wa.W = io.W;
-        wa.bw = ch.bw; wa.kw = ch.kw; wa.with_k = io.base ? 0 : 1; wa.binary_t = ga.binary_t;
+    if (io.lv.W) {      // weighted effects: B W and K W, one pass over the pairs for all columns and levels (independent of the tiles)
+        WsumArgs wa{ch.grid};
+        wa.G = io.lv.G; wa.W = io.lv.W;
+        wa.bw = ch.bw; wa.kw = ch.kw; wa.with_k = io.lv.base ? 0 : 1; wa.binary_t = ga.binary_t;
         launch_wsum(wa, nb, st);
     }
     launch_gram(ga, nb, st);
@@ -862,23 +873,20 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     }
 #endif
     RhsArgs ra{};
-    ra.T = c->dT; ra.Y = io.Y; ra.y_sstride = io.y_sstride; ra.tyLS = io.p.tyLS; ra.doT = io.doT; ra.s0 = s0;
+    ra.T = c->dT; ra.Y = io.Y; ra.y_sstride = io.y_sstride; ra.tyLS = io.post.p.tyLS; ra.doT = io.lv.doT; ra.s0 = s0;
     // vector levels: rhs_tiles writes zeros into the level rows and rhs_prepare no level sums (L = 0 here); launch_vec_sums
     // fills both below
-    ra.n = n; ra.nt = nt; ra.naug = sh.naug; ra.L = (sh.with_sums && !io.vec) ? sh.L : 0; ra.with_sums = sh.with_sums ? 1 : 0;
+    ra.n = n; ra.nt = nt; ra.naug = sh.naug; ra.L = (sh.with_sums && !io.lv.vec) ? sh.L : 0; ra.with_sums = sh.with_sums ? 1 : 0;
     ra.part = ch.part; ra.bsum = ch.bsum; ra.ksum = ch.ksum; ra.sumdelta = ch.sumdelta; ra.M = ch.M;
-    ra.doT_base = io.base;
+    ra.doT_base = io.lv.base;
     static const int epi_rows_on = diag_env("GPSLC_EPI_ROWS", 1);      // measurement switch (A/B of the extra tile update)
     const bool epi_rows = (sh.naug == 1) && epi_rows_on;     // single augmented tile row: the epilogue sums from the rows of R
     const int live = (sh.with_sums ? sh.R : 0) + 1;          // right-hand sides: Y and one c_l per level (and weight column)
     ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
-    if (io.W) {
-        ra.W = io.W; ra.G = io.G; ra.bw = ch.bw; ra.kw = ch.kw; ra.wnorm2 = ch.wnorm2;
-        launch_rhs_weighted(ra, nb, st);
-    } else {
-        launch_rhs(ra, nb, st);
-    }
-    if (io.vec && sh.with_sums) launch_vec_sums(vec_args(c, io, sh, ch), nb, st);
+    ra.G = 1; ra.bw = ch.bsum; ra.kw = ch.ksum;       // the plain call: one column of level sums, the Gram build's
+    if (io.lv.W) { ra.W = io.lv.W; ra.G = io.lv.G; ra.bw = ch.bw; ra.kw = ch.kw; ra.wnorm2 = ch.wnorm2; }
+    launch_rhs(ra, nb, st);
+    if (io.lv.vec && sh.with_sums) launch_vec_sums(vec_args(io, sh, ch), nb, st);
     // NB: the MeanITE pass takes K alpha as Y - yNoise alpha (k_solve.hip, ite_mean_kernel): it relies on alpha solving EXACTLY
     // (K_gram + yNoise I) alpha = Y.  Any future jitter, robust fallback or different right-hand side in this factorisation must
     // be reflected there (tests: test_mean_ite_tiny_noise_and_near_coincident_levels).
@@ -894,23 +902,18 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
         factor_panels(c, *ch.s, ch.M, nt, sh.ntot, ch.inv, inv_bs, io.info + s0, 0, nb, live, epi_rows, 0);
     }
     EpiArgs ea{};
-    ea.M = ch.M; ea.n = n; ea.nt = nt; ea.naug = sh.naug; ea.L = sh.with_sums ? sh.R : 0; ea.s0 = s0; ea.S = io.S;
-    ea.sumdelta = ch.sumdelta; ea.pred_noise = io.pred_noise;
-    ea.meanSATE = io.meanSATE; ea.varSATE = io.varSATE; ea.logdet = io.logdet; ea.quad = io.quad;
+    ea.M = ch.M; ea.n = n; ea.nt = nt; ea.naug = sh.naug; ea.L = sh.with_sums ? sh.R : 0; ea.s0 = s0; ea.S = io.post.S;
+    ea.sumdelta = ch.sumdelta; ea.pred_noise = io.out.pred_noise;
+    ea.meanSATE = io.out.meanSATE; ea.varSATE = io.out.varSATE; ea.logdet = io.logdet; ea.quad = io.quad;
     ea.from_rows = epi_rows ? 1 : 0;
-    if (io.W) {      // weighted: mean / var from the weighted kernel; the plain one (no levels) keeps logdet and quad
-        launch_epilogue_weighted(ea, ch.wnorm2, sh.L, nb, st);
-        ea.L = 0; ea.meanSATE = nullptr; ea.varSATE = nullptr;
-        if (ea.logdet || ea.quad) launch_epilogue(ea, nb, st);
-    } else {
-        launch_epilogue(ea, nb, st);
-    }
+    if (io.lv.W) { ea.wnorm2 = ch.wnorm2; ea.wL = sh.L; }
+    launch_epilogue(ea, nb, st);
     if (io.ndraw) {
         // one draw from N(0, A_s) per parameter set with the caller's normals: L_s z_s on the factor just computed — Gen's
         // mvnormal(zeros(n), cov) of an elliptical slice's auxiliary vector (src/inference.jl:225-232) and of the :logitT prior
         // draw (src/model_likelihood.jl:25-33) — the predictive-draw kernel streaming L once
         DrawArgs dr{};
-        dr.Lc = ch.M; dr.n = n; dr.nt = nt; dr.s0 = s0; dr.S = io.S; dr.l = 0; dr.lc = 1; dr.L = 1; dr.spp = 1;
+        dr.Lc = ch.M; dr.n = n; dr.nt = nt; dr.s0 = s0; dr.S = io.post.S; dr.l = 0; dr.lc = 1; dr.L = 1; dr.spp = 1;
         dr.mean = io.nzero; dr.z = io.nz; dr.zt = ch.znode; dr.out = io.ndraw;
         dr.obase = (long long)n * s0; dr.osb = n; dr.osl = 0; dr.osi = 1; dr.osd = n;
         launch_draws(dr, nb, st);
@@ -927,20 +930,20 @@ void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
     ba.M = ch.M; ba.inv = ch.inv; ba.inv_bstride = (long long)sh.nt * GP_TSQ; ba.nt = sh.nt; ba.naug = sh.naug; ba.zwork = ch.zwork;
     if (!back_done) launch_backsolve(ba, nb, st);
     const double* alpha = ch.zwork + (long long)nb * sh.Np;
-    const struct { double* out; long long si, ss, sl; } outs[2] = {{io.meanITE, 1, n, (long long)n * io.S}, {io.MeanITEs, io.S, 1, 0}};
-    if (io.vec) {
-        VecArgs va = vec_args(c, io, sh, ch);
+    const long long S = io.post.S;
+    const struct { double* out; long long si, ss, sl; } outs[2] = {{io.out.meanITE, 1, n, (long long)n * S}, {io.MeanITEs, S, 1, 0}};
+    if (io.lv.vec) {
+        VecArgs va = vec_args(io, sh, ch);
         va.alpha = alpha;
         for (const auto& o : outs)
             if (o.out) { va.meanITE = o.out; va.si = o.si; va.ss = o.ss; va.sl = o.sl; launch_vec_mean(va, nb, st); }
         return;
     }
-    IteMeanArgs ia{};
-    ia.X = io.X; ia.T = c->dT; ia.p = io.p; ia.s0 = ch.s0; ia.S = io.S;
-    ia.n = n; ia.nX = io.nX; ia.nU = io.nU; ia.nt = sh.nt; ia.L = sh.L; ia.doT = io.doT; ia.alpha = alpha;
-    ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.p.yNoise;
+    IteMeanArgs ia{ch.grid};
+    ia.S = S; ia.L = sh.L; ia.doT = io.lv.doT; ia.alpha = alpha;
+    ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.post.p.yNoise;
     ia.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
-    ia.doT_base = io.base;
+    ia.doT_base = io.lv.base;
     for (const auto& o : outs)
         if (o.out) { ia.meanITE = o.out; ia.si = o.si; ia.ss = o.ss; ia.sl = o.sl; launch_ite_mean(ia, nb, st); }
 }
@@ -1002,12 +1005,12 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
             const int ub = gs * lc;                           // (sample, level) pairs of this sub-batch
             TRef Ls = lower_ref(ch.tiles + (long long)g0 * bstride, bstride);
             Ls.bdiv = lc;
-            DtArgs da{};
-            da.X = io.X; da.T = c->dT; da.p = io.p; da.s0 = s0 + g0;
-            da.n = n; da.nX = io.nX; da.nU = io.nU; da.nt = nt; da.doT = io.doT; da.l0 = l0; da.lc = lc;
-            da.vec = io.vec ? 1 : 0;
-            da.doT_base = io.base;
-            da.pred_noise = io.pred_noise; da.W = W; da.Cm = Cm;
+            DtArgs da{ch.grid};
+            da.s0 = s0 + g0;
+            da.doT = io.lv.doT; da.l0 = l0; da.lc = lc;
+            da.vec = io.lv.vec ? 1 : 0;
+            da.doT_base = io.lv.base;
+            da.pred_noise = io.out.pred_noise; da.W = W; da.Cm = Cm;
             launch_dt_build(da, ub, st);
             TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
             invref.bdiv = lc;
@@ -1020,7 +1023,7 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
             gemm(c, g, *ch.s, 3);
             if (sh.want_cov) {       // ITEDistributions: single level (lc == 1)
                 GatherCovArgs gc{};
-                gc.Cm = Cm; gc.n = n; gc.nt = nt; gc.s0 = s0 + g0; gc.S = io.S; gc.out = io.CovITEs;
+                gc.Cm = Cm; gc.n = n; gc.nt = nt; gc.s0 = s0 + g0; gc.S = io.post.S; gc.out = io.CovITEs;
                 launch_gather_cov(gc, ub, st);
             }
             if (sh.want_draws) {
@@ -1031,64 +1034,65 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
                 factor_robust(c, *ch.s, Cm, nt, ch.pinfo, n, ub, 3);
                 launch_fold_pair_info(ch.pinfo, io.info + s0 + g0, gs, lc, st);
                 DrawArgs dr{};
-                dr.Lc = Cm; dr.n = n; dr.nt = nt; dr.s0 = s0 + g0; dr.S = io.S; dr.l = l0; dr.lc = lc; dr.L = L;
-                dr.spp = io.spp; dr.mean = io.meanITE; dr.z = io.z; dr.zgen = ch.zgen; dr.zt = ch.zt; dr.seed = io.seed;
+                dr.Lc = Cm; dr.n = n; dr.nt = nt; dr.s0 = s0 + g0; dr.S = io.post.S; dr.l = l0; dr.lc = lc; dr.L = L;
+                dr.spp = io.out.spp; dr.mean = io.out.meanITE; dr.z = io.out.z; dr.zgen = ch.zgen; dr.zt = ch.zt; dr.seed = io.out.seed;
                 const int64_t eS = io.ens_S > 0 ? io.ens_S : c->ens_S, eo = io.ens_S > 0 ? io.ens_off : c->ens_off;
-                dr.rs0 = dr.s0 + (eS > 0 ? eo : 0); dr.rS = eS > 0 ? eS : io.S;
+                dr.rs0 = dr.s0 + (eS > 0 ? eo : 0); dr.rS = eS > 0 ? eS : io.post.S;
                 if (L == 1) {     // the reference tensor directly: n x (S*spp), instance fastest
-                    dr.out = io.ite_draws;
-                    dr.obase = (long long)n * io.spp * (s0 + g0); dr.osb = (long long)n * io.spp; dr.osl = 0;
+                    dr.out = io.out.ite_draws;
+                    dr.obase = (long long)n * io.out.spp * (s0 + g0); dr.osb = (long long)n * io.out.spp; dr.osl = 0;
                     dr.osi = 1; dr.osd = n;
                 } else {          // staging [sample][level][d][i]
                     dr.out = ch.dtmp;
-                    dr.obase = (long long)l0 * io.spp * n; dr.osb = (long long)L * io.spp * n;
-                    dr.osl = (long long)io.spp * n; dr.osi = 1; dr.osd = n;
+                    dr.obase = (long long)l0 * io.out.spp * n; dr.osb = (long long)L * io.out.spp * n;
+                    dr.osl = (long long)io.out.spp * n; dr.osi = 1; dr.osd = n;
                 }
-                ProfScope ps(c, 2, (double)ub * io.spp, st);     // unit C: work = draws
+                ProfScope ps(c, 2, (double)ub * io.out.spp, st);     // unit C: work = draws
                 launch_draws(dr, ub, st);
             }
         }
         if (sh.want_draws && L > 1)
-            launch_draws_scatter(ch.dtmp, io.ite_draws, n, L, io.spp, s0 + g0, gs, st);
+            launch_draws_scatter(ch.dtmp, io.out.ite_draws, n, L, io.out.spp, s0 + g0, gs, st);
     }
 }
 
 // the chunked ensemble driver (device pointers everywhere)
 void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     PredictIO io = io_in;
-    if (io.base && io.vec) throw std::runtime_error("a contrast baseline cannot be combined with vector levels");
-    if (io.base && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("contrasts need an fp64 context");
-    if (io.W && io.vec) throw std::runtime_error("weights cannot be combined with vector levels");
-    if (io.W && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("weighted effects need an fp64 context");
-    if (io.W && io.G < 1) throw std::runtime_error("weights without a weight column");
-    if (io.W && !io.meanSATE && !io.varSATE) { io.W = nullptr; io.G = 0; }      // nothing weighted is asked for
+    if (io.lv.base && io.lv.vec) throw std::runtime_error("a contrast baseline cannot be combined with vector levels");
+    if (io.lv.base && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("contrasts need an fp64 context");
+    if (io.lv.W && io.lv.vec) throw std::runtime_error("weights cannot be combined with vector levels");
+    if (io.lv.W && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("weighted effects need an fp64 context");
+    if (io.lv.W && io.lv.G < 1) throw std::runtime_error("weights without a weight column");
+    if (io.lv.W && !io.out.meanSATE && !io.out.varSATE) { io.lv.W = nullptr; io.lv.G = 0; }      // nothing weighted is asked for
     if (io.nU < 0) io.nU = c->nU;
     if (io.nX < 0) io.nX = c->nX;
     if (!io.Y) { io.Y = c->dY; io.y_sstride = 0; }
-    if (io.p.u_sstride == 0 && io.nU > 0 && io.p.U != nullptr && !io.p_shared_u) io.p.u_sstride = (long long)c->n * io.nU;
+    if (io.post.p.u_sstride == 0 && io.nU > 0 && io.post.p.U != nullptr && !io.p_shared_u) io.post.p.u_sstride = (long long)c->n * io.nU;
     reset_stale_task_timeouts(c);
     ensure_streams(c);
     const PredictShape sh(c, io);
     // chunk size and sub-batch from what the device has (the sub-batch's workspace is sized from the pairs the call
     // really has, and the 30 % rule of the automatic chunk covers its per-sample part only)
     const ChunkBytes by = carve_chunk(sh, io, 0, nullptr);
-    const BatchPlan plan = auto_batch(c, io.S, sh.L, by.per_sample, by.per_pair, by.per_level);
+    const BatchPlan plan = auto_batch(c, io.post.S, sh.L, by.per_sample, by.per_pair, by.per_level);
     const int Bt = (int)plan.Bt, Bb = (int)plan.Bb;      // Bb: (sample, level) pairs per unit-B sub-batch, no more than the call has
     const size_t need = (size_t)Bt * by.per_sample + plan.fixed;
     for (int i = 0; i < c->nstreams; ++i) arena_reserve(c, c->slots[i].arena, need);
     // internal MeanITE buffer when the caller did not ask for it but the draws need it
-    if (sh.want_draws && !io.meanITE) {
-        arena_reserve(c, c->scratch, std::max(c->scratch.bytes, (size_t)sh.n * io.S * sh.L * 8 + (1 << 16)));
+    if (sh.want_draws && !io.out.meanITE) {
+        arena_reserve(c, c->scratch, std::max(c->scratch.bytes, (size_t)sh.n * io.post.S * sh.L * 8 + (1 << 16)));
         c->scratch.reset();
-        io.meanITE = c->scratch.take<double>((size_t)sh.n * io.S * sh.L);
+        io.out.meanITE = c->scratch.take<double>((size_t)sh.n * io.post.S * sh.L);
     }
-    HC(hipMemsetAsync(io.info, 0, sizeof(int) * io.S, c->slots[0].st));
+    HC(hipMemsetAsync(io.info, 0, sizeof(int) * io.post.S, c->slots[0].st));
     HC(hipStreamSynchronize(c->slots[0].st));
     int chunk = 0;
-    for (int64_t s0 = 0; s0 < io.S; s0 += Bt, ++chunk) {
-        Chunk ch{&c->slots[chunk % c->nstreams], s0, (int)std::min<int64_t>(Bt, io.S - s0)};
+    for (int64_t s0 = 0; s0 < io.post.S; s0 += Bt, ++chunk) {
+        Chunk ch{&c->slots[chunk % c->nstreams], s0, (int)std::min<int64_t>(Bt, io.post.S - s0)};
         ch.s->arena.reset();
         carve_chunk(sh, io, Bb, &ch);
+        ch.grid = SampleGrid{io.X, c->dT, io.post.p, s0, sh.n, io.nX, io.nU, sh.nt};
         const bool back_done = unit_a(c, io, sh, ch);
         if (sh.want_mean) mean_ite(c, io, sh, ch, back_done);
         if (sh.unitB) unit_b(c, io, sh, ch);
@@ -1097,8 +1101,8 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     HC(hipGetLastError());
     check_task_timeout(c);
     if (c->flags & GPSLC_FLAG_PROFILE) prof_collect(c);
-    c->last_info.resize(io.S);
-    HC(hipMemcpy(c->last_info.data(), io.info, sizeof(int) * io.S, hipMemcpyDeviceToHost));
+    c->last_info.resize(io.post.S);
+    HC(hipMemcpy(c->last_info.data(), io.info, sizeof(int) * io.post.S, hipMemcpyDeviceToHost));
 }
 
 int first_info(const gpslc_ctx* c) {
@@ -1168,17 +1172,6 @@ double* up(gpslc_ctx* c, const double* host, size_t count) {
     double* d = c->io.take<double>(count);
     if (count) HC(hipMemcpy(d, host, count * sizeof(double), hipMemcpyHostToDevice));
     return d;
-}
-
-int check_common(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
-                 const double* tyLS, const double* yScale, const double* yNoise) {
-    if (!c) return -1;
-    if (!c->has_data) { set_err(c, "gpslc_set_data has not been called"); return GPSLC_ERR_NODATA; }
-    if (S < 0) return bad_arg(c, 2, "S < 0");
-    if (c->nU > 0 && S > 0 && (!U || !uyLS)) return bad_arg(c, 3, "U / uyLS must not be NULL when nU > 0");
-    if (c->nX > 0 && S > 0 && !xyLS) return bad_arg(c, 5, "xyLS must not be NULL when nX > 0");
-    if (S > 0 && (!tyLS || !yScale || !yNoise)) return bad_arg(c, 6, "tyLS / yScale / yNoise must not be NULL");
-    return 0;
 }
 
 // ---- single-launch small-n node scores ----------------------------------------------------------------------------
@@ -1636,59 +1629,6 @@ int gpslc_process_cov(gpslc_ctx* c, const double* logcov, int64_t n, double scal
     });
 }
 
-// argument checks of gpslc_predict / gpslc_predict_multi; argoff shifts the reported argument number (code AND message) to the
-// caller's own signature (gpslc_predict_multi has two more leading arguments than gpslc_predict: nctx, ctxs)
-static int predict_check(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
-                         const double* tyLS, const double* yScale, const double* yNoise, int32_t L,
-                         const double* doT, int32_t spp, const double* ite_draws, int argoff = 0) {
-    if (!c) return -1;
-    if (!c->has_data) { set_err(c, "gpslc_set_data has not been called"); return GPSLC_ERR_NODATA; }
-    if (S < 0) return bad_arg(c, 2 + argoff, "S < 0");
-    if (c->nU > 0 && S > 0 && (!U || !uyLS)) return bad_arg(c, 3 + argoff, "U / uyLS must not be NULL when nU > 0");
-    if (c->nX > 0 && S > 0 && !xyLS) return bad_arg(c, 5 + argoff, "xyLS must not be NULL when nX > 0");
-    if (S > 0 && (!tyLS || !yScale || !yNoise)) return bad_arg(c, 6 + argoff, "tyLS / yScale / yNoise must not be NULL");
-    if (L < 1) return bad_arg(c, 9 + argoff, "L < 1");
-    if (!doT) return bad_arg(c, 10 + argoff, "doT is NULL");
-    if (ite_draws && spp < 1) return bad_arg(c, 12 + argoff, "spp < 1 with ite_draws requested");
-    // a placement left over from an earlier, smaller call would make the stream ids (off + s) + S_total * l of this call's last
-    // samples collide with the next level's streams: refuse instead of drawing correlated normals
-    if (c->ens_S > 0 && c->ens_off + S > c->ens_S)
-        return bad_arg(c, 2 + argoff, "S exceeds the room gpslc_set_ensemble left: sample_offset + S > S_total");
-    return 0;
-}
-
-// device pointers everywhere; the info words come from the staging pool (the caller has reset it)
-static int predict_dev_inner(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
-                             const double* tyLS, const double* yScale, const double* yNoise, int32_t L,
-                             const double* doT, double pred_noise, int32_t spp, uint64_t seed, const double* z,
-                             double* meanSATE, double* varSATE, double* meanITE, double* ite_draws,
-                             int64_t ens_off = 0, int64_t ens_S = 0, bool vec = false, const double* base = nullptr,
-                             int G = 0, const double* W = nullptr) {
-    PredictIO io;
-    io.S = S; io.p = SampleParams{U, uyLS, xyLS, tyLS, yScale, yNoise}; io.X = c->dX;
-    io.L = L; io.doT = doT; io.vec = vec; io.base = base; io.pred_noise = pred_noise; io.spp = spp; io.seed = seed; io.z = z;
-    io.meanSATE = meanSATE; io.varSATE = varSATE; io.meanITE = meanITE; io.ite_draws = ite_draws;
-    io.ens_off = ens_off; io.ens_S = ens_S;
-    io.W = W; io.G = G;
-    io.info = c->io.take<int>((size_t)S);
-    run_predict(c, io);
-    return first_info(c);
-}
-
-int gpslc_predict_dev(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
-                      const double* tyLS, const double* yScale, const double* yNoise, int32_t L,
-                      const double* doT, double pred_noise, int32_t spp, uint64_t seed, const double* z,
-                      double* meanSATE, double* varSATE, double* meanITE, double* ite_draws) {
-    int rc = predict_check(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, ite_draws);
-    if (rc) return rc;
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return guarded(c, [&]() {
-        c->io.reset();
-        return predict_dev_inner(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z,
-                                 meanSATE, varSATE, meanITE, ite_draws);
-    });
-}
-
 // Where a host-pointer prediction over the samples [s0, s0 + S) of S_total sits in the caller's arrays (gpslc_predict_multi:
 // one shard; gpslc_predict: s0 = 0, S_total = S).  Per-sample inputs and the outputs are addressed in the caller's FULL
 // arrays: element (s, l) of an S_total x L array at (s0 + s) + S_total l, block (s, l) of an n x S_total x L array at
@@ -1698,53 +1638,163 @@ struct HostPlacement {
     int64_t ens_off = 0, ens_S = 0;     // Philox stream placement of the shard (ens_S > 0), else the ctx's
 };
 
-// gpslc_predict's body: uploads, run_predict, delivery — every level's run of a shard goes from the device straight to its place
-// in the caller's array (no host staging)
-static int predict_host(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
-                        const double* yScale, const double* yNoise, int32_t L, const double* doT, double pred_noise, int32_t spp,
-                        uint64_t seed, const double* z, double* meanSATE, double* varSATE, double* meanITE, double* ite_draws,
-                        const HostPlacement& pl, bool vec = false, const double* base = nullptr, int G = 0,
-                        const double* weights = nullptr) {
+// what an extern "C" prediction or ITE-distribution function was asked for, with the caller's pointers as given
+struct PredictRequest {
+    Posterior post;
+    Levels lv;
+    DrawsAndOutputs out;
+    double *MeanITEs = nullptr, *CovITEs = nullptr;     // gpslc_ite_distributions*: S x n, S x n x n
+    HostPlacement pl;                                   // host calls
+};
+static PredictRequest make_request(int64_t S, const SampleParams& samples, int32_t L, const double* doT) {
+    PredictRequest rq;
+    rq.post.S = S; rq.post.p = samples;
+    rq.lv.L = L; rq.lv.doT = doT;
+    rq.pl.S_total = S;
+    return rq;
+}
+
+// The position of each checked argument in one entry point's signature (0: it has no such argument): the k of the status -k
+// and of the message's "argument #k".  fp64_only: the entry point refuses a GPSLC_FLAG_FP32_KERNEL context (the fp32 kernel
+// mode covers scalar levels without baseline or weights only).
+struct ArgPos { int S, U, xyLS, tyLS, L, doT, base, G, W, spp; bool fp64_only; };
+static const ArgPos kPredictArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, false}, kPredictVecArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, true},
+    kPredictContrastArgs{2, 3, 5, 6, 9, 10, 11, 0, 0, 13, true}, kPredictWeightedArgs{2, 3, 5, 6, 9, 10, 11, 12, 13, 15, true},
+    kPredictMultiArgs{3, 4, 6, 7, 10, 11, 0, 0, 0, 13, false},      // two more leading arguments: nctx, ctxs
+    kSamplesArgs{2, 3, 5, 6, 0, 0, 0, 0, 0, 0, false},      // gpslc_ite_distributions, gpslc_y_logpdf, gpslc_likelihood_distribution
+    kIteVecArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true}, kIteContrastArgs{2, 3, 5, 6, 0, 9, 10, 0, 0, 0, true},
+    kLikelihoodVecArgs{2, 3, 5, 6, 0, 8, 0, 0, 0, 0, false};
+
+// `count` host values: all there and all finite
+static int finite_check(gpslc_ctx* c, const double* v, int64_t count, int argk, const char* name) {
+    char what[64];
+    if (!v) { snprintf(what, sizeof what, "%s is NULL", name); return bad_arg(c, argk, what); }
+    for (int64_t i = 0; i < count; ++i)
+        if (!std::isfinite(v[i])) { snprintf(what, sizeof what, "%s has a non-finite entry", name); return bad_arg(c, argk, what); }
+    return 0;
+}
+
+// The argument checks of every prediction and ITE-distribution entry point, in the order of the arguments.  Levels given as
+// host values beyond the plain L scalars (vector levels: n x L; pairs with a baseline; weight columns: n x G) must be finite.
+static int validate(gpslc_ctx* c, const PredictRequest& rq, const ArgPos& k) {
+    const Posterior& po = rq.post;
+    const Levels& lv = rq.lv;
+    if (!c) return -1;
+    if (!c->has_data) { set_err(c, "gpslc_set_data has not been called"); return GPSLC_ERR_NODATA; }
+    if (po.S < 0) return bad_arg(c, k.S, "S < 0");
+    if (c->nU > 0 && po.S > 0 && (!po.p.U || !po.p.uyLS)) return bad_arg(c, k.U, "U / uyLS must not be NULL when nU > 0");
+    if (c->nX > 0 && po.S > 0 && !po.p.xyLS) return bad_arg(c, k.xyLS, "xyLS must not be NULL when nX > 0");
+    if (po.S > 0 && (!po.p.tyLS || !po.p.yScale || !po.p.yNoise)) return bad_arg(c, k.tyLS, "tyLS / yScale / yNoise must not be NULL");
+    const bool no_spp = rq.out.ite_draws && rq.out.spp < 1;
+    int rc = 0;
+    if (k.L) {
+        if (lv.L < 1) return bad_arg(c, k.L, "L < 1");
+        if (!lv.doT) return bad_arg(c, k.doT, "doT is NULL");
+        if (no_spp && !k.base) return bad_arg(c, k.spp, "spp < 1 with ite_draws requested");      // spp follows doT
+        // a placement left over from an earlier, smaller call would make the stream ids (off + s) + S_total * l of this call's
+        // last samples collide with the next level's streams: refuse instead of drawing correlated normals
+        if (c->ens_S > 0 && c->ens_off + po.S > c->ens_S)
+            return bad_arg(c, k.S, "S exceeds the room gpslc_set_ensemble left: sample_offset + S > S_total");
+    }
+    if (lv.vec || k.base) {
+        if ((rc = finite_check(c, lv.doT, lv.vec ? c->n * (int64_t)lv.L : lv.L, k.doT, "doT"))) return rc;
+        // the baselines are optional beside weights
+        if (k.base && (lv.base || !k.W) && (rc = finite_check(c, lv.base, lv.L, k.base, "doT_base"))) return rc;
+    }
+    if (k.W) {
+        if (lv.G < 1) return bad_arg(c, k.G, "G < 1");
+        if ((rc = finite_check(c, lv.W, c->n * (int64_t)lv.G, k.W, "weights"))) return rc;
+    }
+    if (no_spp && k.base) return bad_arg(c, k.spp, "spp < 1 with ite_draws requested");
+    if (k.fp64_only && (c->flags & GPSLC_FLAG_FP32_KERNEL)) {
+        set_err(c, "vector levels, contrasts and weighted effects are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
+        return GPSLC_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// the samples [s0, s0 + S) of a host posterior block, uploaded into the staging pool
+static SampleParams upload_samples(gpslc_ctx* c, const SampleParams& h, size_t s0, size_t S) {
+    const size_t n = (size_t)c->n, nU = (size_t)c->nU, nX = (size_t)c->nX;
+    SampleParams d{};
+    d.U = nU ? up(c, h.U + n * nU * s0, n * nU * S) : nullptr;
+    d.uyLS = nU ? up(c, h.uyLS + nU * s0, nU * S) : nullptr;
+    d.xyLS = nX ? up(c, h.xyLS + nX * s0, nX * S) : nullptr;
+    d.tyLS = up(c, h.tyLS + s0, S);
+    d.yScale = up(c, h.yScale + s0, S);
+    d.yNoise = up(c, h.yNoise + s0, S);
+    return d;
+}
+
+// device pointers everywhere; the info words come from the staging pool (the caller has reset it)
+static int predict_dev_inner(gpslc_ctx* c, const PredictRequest& rq) {
+    PredictIO io;
+    io.post = rq.post; io.lv = rq.lv; io.out = rq.out; io.X = c->dX;
+    io.MeanITEs = rq.MeanITEs; io.CovITEs = rq.CovITEs;
+    io.ens_off = rq.pl.ens_off; io.ens_S = rq.pl.ens_S;
+    io.info = c->io.take<int>((size_t)rq.post.S);
+    run_predict(c, io);
+    return first_info(c);
+}
+
+int gpslc_predict_dev(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                      const double* tyLS, const double* yScale, const double* yNoise, int32_t L,
+                      const double* doT, double pred_noise, int32_t spp, uint64_t seed, const double* z,
+                      double* meanSATE, double* varSATE, double* meanITE, double* ite_draws) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanSATE, varSATE, meanITE, ite_draws};
+    int rc = validate(c, rq, kPredictArgs);
+    if (rc) return rc;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
     return guarded(c, [&]() {
-        const size_t n = (size_t)c->n;
-        const size_t LR = weights ? (size_t)L * G : (size_t)L;     // meanSATE / varSATE columns: levels, or levels x weight columns
-        const size_t s0 = (size_t)pl.s0, St = (size_t)pl.S_total;
         c->io.reset();
-        const double* dU = c->nU ? up(c, U + n * c->nU * s0, n * c->nU * S) : nullptr;
-        const double* duy = c->nU ? up(c, uyLS + (size_t)c->nU * s0, (size_t)c->nU * S) : nullptr;
-        const double* dxy = c->nX ? up(c, xyLS + (size_t)c->nX * s0, (size_t)c->nX * S) : nullptr;
-        const double* dty = up(c, tyLS + s0, S);
-        const double* dys = up(c, yScale + s0, S);
-        const double* dyn = up(c, yNoise + s0, S);
-        const double* ddo = up(c, doT, vec ? n * L : (size_t)L);     // vector levels: n x L
-        const double* dba = base ? up(c, base, (size_t)L) : nullptr;  // contrasts: the L baselines
-        const double* dW = nullptr;
-        if (weights) {             // n x G host (weights[i + n*g]) -> column fastest on the device (W[g + G*i]: the kernels' layout)
-            std::vector<double> wt(n * (size_t)G);
+        return predict_dev_inner(c, rq);
+    });
+}
+
+// The body of the host-pointer entry points (an empty call returns here, after its checks): uploads, run_predict, delivery —
+// every level's run of a shard goes from the device straight to its place in the caller's array (no host staging, VERDICT r05
+// item 2)
+static int predict_host(gpslc_ctx* c, const PredictRequest& rq) {
+    const int64_t S = rq.post.S;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        const Levels& lv = rq.lv;
+        const DrawsAndOutputs& o = rq.out;
+        const size_t n = (size_t)c->n, L = (size_t)lv.L;
+        const size_t LR = lv.W ? L * lv.G : L;     // meanSATE / varSATE columns: levels, or levels x weight columns
+        const size_t s0 = (size_t)rq.pl.s0, St = (size_t)rq.pl.S_total;
+        c->io.reset();
+        PredictRequest d = rq;             // the same request with device pointers
+        d.post.p = upload_samples(c, rq.post.p, s0, (size_t)S);
+        d.lv.doT = up(c, lv.doT, lv.vec ? n * L : L);                 // vector levels: n x L
+        d.lv.base = lv.base ? up(c, lv.base, L) : nullptr;            // contrasts: the L baselines
+        if (lv.W) {                // n x G host (weights[i + n*g]) -> column fastest on the device (W[g + G*i]: the kernels' layout)
+            const size_t G = (size_t)lv.G;
+            std::vector<double> wt(n * G);
             for (size_t i = 0; i < n; ++i)
-                for (int g = 0; g < G; ++g) wt[(size_t)g + (size_t)G * i] = weights[i + n * (size_t)g];
-            dW = up(c, wt.data(), wt.size());
+                for (size_t g = 0; g < G; ++g) wt[g + G * i] = lv.W[i + n * g];
+            d.lv.W = up(c, wt.data(), wt.size());
         }
-        const double* dz = nullptr;
-        if (z && ite_draws) {      // caller's normals n x spp x S_total x L: level l of the shard is one run of n spp S doubles
-            double* d = c->io.take<double>(n * spp * S * L);
-            const size_t run = n * spp * (size_t)S * sizeof(double);
-            HC(hipMemcpy2D(d, run, z + n * spp * s0, n * spp * St * sizeof(double), run, (size_t)L, hipMemcpyHostToDevice));
-            dz = d;
+        d.out.z = nullptr;
+        if (o.z && o.ite_draws) {  // caller's normals n x spp x S_total x L: level l of the shard is one run of n spp S doubles
+            double* dz = c->io.take<double>(n * o.spp * S * L);
+            const size_t run = n * o.spp * (size_t)S * sizeof(double);
+            HC(hipMemcpy2D(dz, run, o.z + n * o.spp * s0, n * o.spp * St * sizeof(double), run, L, hipMemcpyHostToDevice));
+            d.out.z = dz;
         }
-        double* oms = meanSATE ? c->io.take<double>((size_t)S * LR) : nullptr;
-        double* ovs = varSATE ? c->io.take<double>((size_t)S * LR) : nullptr;
-        double* omi = meanITE ? c->io.take<double>(n * S * L) : nullptr;
-        double* odr = ite_draws ? c->io.take<double>((size_t)L * n * S * spp) : nullptr;
-        int st = predict_dev_inner(c, S, dU, duy, dxy, dty, dys, dyn, L, ddo, pred_noise, spp, seed, dz,
-                                   oms, ovs, omi, odr, pl.ens_off, pl.ens_S, vec, dba, G, dW);
+        double* oms = d.out.meanSATE = o.meanSATE ? c->io.take<double>((size_t)S * LR) : nullptr;
+        double* ovs = d.out.varSATE = o.varSATE ? c->io.take<double>((size_t)S * LR) : nullptr;
+        double* omi = d.out.meanITE = o.meanITE ? c->io.take<double>(n * S * L) : nullptr;
+        double* odr = d.out.ite_draws = o.ite_draws ? c->io.take<double>(L * n * S * o.spp) : nullptr;
+        int st = predict_dev_inner(c, d);
         if (st < 0) return st;
         const size_t sb = (size_t)S * sizeof(double);
-        if (meanSATE) HC(hipMemcpy2D(meanSATE + s0, St * sizeof(double), oms, sb, sb, LR, hipMemcpyDeviceToHost));
-        if (varSATE) HC(hipMemcpy2D(varSATE + s0, St * sizeof(double), ovs, sb, sb, LR, hipMemcpyDeviceToHost));
-        if (meanITE) copy_out_rows(c, meanITE + n * s0, n * St * sizeof(double), omi, n * sb, (size_t)L);
+        if (o.meanSATE) HC(hipMemcpy2D(o.meanSATE + s0, St * sizeof(double), oms, sb, sb, LR, hipMemcpyDeviceToHost));
+        if (o.varSATE) HC(hipMemcpy2D(o.varSATE + s0, St * sizeof(double), ovs, sb, sb, LR, hipMemcpyDeviceToHost));
+        if (o.meanITE) copy_out_rows(c, o.meanITE + n * s0, n * St * sizeof(double), omi, n * sb, L);
         // level-fastest tensor L x n x (S_total spp): a sample's columns are one contiguous run
-        if (ite_draws) copy_out_large(c, ite_draws + (size_t)L * n * spp * s0, odr, sizeof(double) * (size_t)L * n * S * spp);
+        if (o.ite_draws) copy_out_large(c, o.ite_draws + L * n * o.spp * s0, odr, sizeof(double) * L * n * S * o.spp);
         return st;
     });
 }
@@ -1753,102 +1803,46 @@ int gpslc_predict(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, 
                   const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
                   double pred_noise, int32_t spp, uint64_t seed, const double* z, double* meanSATE,
                   double* varSATE, double* meanITE, double* ite_draws) {
-    int rc = predict_check(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, ite_draws);
-    if (rc) return rc;
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    HostPlacement pl;
-    pl.S_total = S;
-    return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE, varSATE, meanITE,
-                        ite_draws, pl);
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanSATE, varSATE, meanITE, ite_draws};
+    int rc = validate(c, rq, kPredictArgs);
+    return rc ? rc : predict_host(c, rq);
 }
 
-// vector levels (gpslc_*_vec): every entry of the n x L host array doT must be finite; the fp32 kernel mode covers the
-// scalar levels only
-static int vec_levels_check(gpslc_ctx* c, const double* doT, int64_t count, int argk) {
-    if (!doT) return bad_arg(c, argk, "doT is NULL");
-    for (int64_t i = 0; i < count; ++i)
-        if (!std::isfinite(doT[i])) return bad_arg(c, argk, "doT has a non-finite entry");
-    return 0;
-}
-static int vec_mode_check(gpslc_ctx* c) {
-    if (c->flags & GPSLC_FLAG_FP32_KERNEL) {
-        set_err(c, "vector interventions are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
-        return GPSLC_ERR_UNSUPPORTED;
-    }
-    return 0;
-}
-
+// vector levels: every entry of the n x L host array doT must be finite
 int gpslc_predict_vec(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
                       const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
                       double pred_noise, int32_t spp, uint64_t seed, const double* z, double* meanSATE,
                       double* varSATE, double* meanITE, double* ite_draws) {
-    int rc = predict_check(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, ite_draws);
-    if (rc) return rc;
-    if ((rc = vec_levels_check(c, doT, c->n * (int64_t)L, 10))) return rc;
-    if ((rc = vec_mode_check(c))) return rc;
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    HostPlacement pl;
-    pl.S_total = S;
-    return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE, varSATE, meanITE,
-                        ite_draws, pl, /*vec=*/true);
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.lv.vec = true;
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanSATE, varSATE, meanITE, ite_draws};
+    int rc = validate(c, rq, kPredictVecArgs);
+    return rc ? rc : predict_host(c, rq);
 }
 
-// contrasts (gpslc_*_contrast): level l is the pair (doT[l], doT_base[l]) of finite scalars; fp64 contexts only
-static int contrast_levels_check(gpslc_ctx* c, const double* v, int64_t count, int argk, const char* name) {
-    char what[64];
-    if (!v) { snprintf(what, sizeof what, "%s is NULL", name); return bad_arg(c, argk, what); }
-    for (int64_t i = 0; i < count; ++i)
-        if (!std::isfinite(v[i])) { snprintf(what, sizeof what, "%s has a non-finite entry", name); return bad_arg(c, argk, what); }
-    return 0;
-}
-static int contrast_mode_check(gpslc_ctx* c) {
-    if (c->flags & GPSLC_FLAG_FP32_KERNEL) {
-        set_err(c, "contrasts are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
-        return GPSLC_ERR_UNSUPPORTED;
-    }
-    return 0;
-}
-
+// contrasts: level l is the pair (doT[l], doT_base[l]) of finite scalars
 int gpslc_predict_contrast(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
                            const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
                            const double* doT_base, double pred_noise, int32_t spp, uint64_t seed, const double* z,
                            double* meanSATE, double* varSATE, double* meanITE, double* ite_draws) {
-    // gpslc_predict's checks up to doT (#10); doT_base is #11 here, so spp is #13
-    int rc = predict_check(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, nullptr);
-    if (rc) return rc;
-    if ((rc = contrast_levels_check(c, doT, L, 10, "doT"))) return rc;
-    if ((rc = contrast_levels_check(c, doT_base, L, 11, "doT_base"))) return rc;
-    if (ite_draws && spp < 1) return bad_arg(c, 13, "spp < 1 with ite_draws requested");
-    if ((rc = contrast_mode_check(c))) return rc;
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    HostPlacement pl;
-    pl.S_total = S;
-    return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE, varSATE, meanITE,
-                        ite_draws, pl, /*vec=*/false, doT_base);
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.lv.base = doT_base;
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanSATE, varSATE, meanITE, ite_draws};
+    int rc = validate(c, rq, kPredictContrastArgs);
+    return rc ? rc : predict_host(c, rq);
 }
 
-// weighted effects (gpslc_predict_weighted): G >= 1 columns of n finite host weights each; scalar levels, fp64 contexts only
+// weighted effects: G >= 1 columns of n finite host weights each; scalar levels, with or without baselines
 int gpslc_predict_weighted(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
                            const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
                            const double* doT_base, int32_t G, const double* weights, double pred_noise, int32_t spp,
                            uint64_t seed, const double* z, double* meanW, double* varW, double* meanITE, double* ite_draws) {
-    // gpslc_predict's checks up to doT (#10); doT_base_or_null is #11, G #12, weights #13, so spp is #15
-    int rc = predict_check(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, nullptr);
-    if (rc) return rc;
-    if ((rc = contrast_levels_check(c, doT, L, 10, "doT"))) return rc;
-    if (doT_base && (rc = contrast_levels_check(c, doT_base, L, 11, "doT_base"))) return rc;
-    if (G < 1) return bad_arg(c, 12, "G < 1");
-    if ((rc = contrast_levels_check(c, weights, c->n * (int64_t)G, 13, "weights"))) return rc;
-    if (ite_draws && spp < 1) return bad_arg(c, 15, "spp < 1 with ite_draws requested");
-    if (c->flags & GPSLC_FLAG_FP32_KERNEL) {
-        set_err(c, "weighted effects are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
-        return GPSLC_ERR_UNSUPPORTED;
-    }
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    HostPlacement pl;
-    pl.S_total = S;
-    return predict_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanW, varW, meanITE,
-                        ite_draws, pl, /*vec=*/false, doT_base, G, weights);
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.lv.base = doT_base; rq.lv.G = G; rq.lv.W = weights;
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws};
+    int rc = validate(c, rq, kPredictWeightedArgs);
+    return rc ? rc : predict_host(c, rq);
 }
 
 int gpslc_shard_range(int64_t S, int32_t nblocks, int32_t k, int64_t* s0, int64_t* s1) {
@@ -1890,8 +1884,9 @@ int gpslc_predict_multi(int32_t nctx, gpslc_ctx* const* ctxs, int64_t S, const d
             return bad_arg(c0, 2, "the contexts differ in GPSLC_FLAG_FP32_KERNEL");
         if (!ctxs[k]->has_data) { set_err(c0, "gpslc_set_data has not been called on every ctx"); return GPSLC_ERR_NODATA; }
     }
-    // argument numbers of THIS signature, in the code and in the message (S is #3, ...)
-    int rc0 = predict_check(c0, S, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, spp, ite_draws, /*argoff=*/1);
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanSATE, varSATE, meanITE, ite_draws};
+    int rc0 = validate(c0, rq, kPredictMultiArgs);      // argument numbers of THIS signature, in the code and in the message
     if (rc0) return rc0;
     if (S == 0) { for (int k = 0; k < nctx; ++k) ctxs[k]->last_info.clear(); return GPSLC_OK; }
     try {
@@ -1907,10 +1902,10 @@ int gpslc_predict_multi(int32_t nctx, gpslc_ctx* const* ctxs, int64_t S, const d
         auto work = [&](int k) {
             Shard& h = sh[(size_t)k];
             if (h.Sr == 0) { ctxs[k]->last_info.clear(); return; }
-            HostPlacement pl;
-            pl.s0 = h.s0; pl.S_total = S; pl.ens_off = base_off + h.s0; pl.ens_S = total;
-            h.rc = predict_host(ctxs[k], h.Sr, U, uyLS, xyLS, tyLS, yScale, yNoise, L, doT, pred_noise, spp, seed, z, meanSATE,
-                                varSATE, meanITE, ite_draws, pl);
+            PredictRequest part = rq;                // the shard's samples, placed in the caller's full arrays
+            part.post.S = h.Sr;
+            part.pl = HostPlacement{h.s0, S, base_off + h.s0, total};
+            h.rc = predict_host(ctxs[k], part);
         };
         std::vector<std::thread> pool;
         for (int k = 1; k < nctx; ++k) {
@@ -1943,64 +1938,53 @@ int gpslc_predict_multi(int32_t nctx, gpslc_ctx* const* ctxs, int64_t S, const d
     }
 }
 
-// doT: one level (host), a scalar (vec = false) or n values (vec = true); base: non-null = the contrast doT against *base
-static int ite_distributions_impl(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
-                                  const double* tyLS, const double* yScale, const double* yNoise, const double* doT, bool vec,
-                                  double pred_noise, double* MeanITEs, double* CovITEs, const double* base = nullptr) {
+// gpslc_ite_distributions*'s body: one level (host) — a scalar, n values (vec) or the contrast of two scalars (base)
+static int ite_distributions_host(gpslc_ctx* c, const PredictRequest& rq) {
+    const int64_t S = rq.post.S;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
     return guarded(c, [&]() {
         const size_t n = (size_t)c->n;
         c->io.reset();
-        const double* dU = c->nU ? up(c, U, n * c->nU * S) : nullptr;
-        const double* duy = c->nU ? up(c, uyLS, (size_t)c->nU * S) : nullptr;
-        const double* dxy = c->nX ? up(c, xyLS, (size_t)c->nX * S) : nullptr;
-        const double* dty = up(c, tyLS, S);
-        const double* dys = up(c, yScale, S);
-        const double* dyn = up(c, yNoise, S);
-        const double* ddo = up(c, doT, vec ? n : 1);
-        const double* dba = base ? up(c, base, 1) : nullptr;
-        double* om = MeanITEs ? c->io.take<double>((size_t)S * n) : nullptr;
-        double* oc = CovITEs ? c->io.take<double>((size_t)S * n * n) : nullptr;
-        PredictIO io;
-        io.S = S; io.p = SampleParams{dU, duy, dxy, dty, dys, dyn}; io.X = c->dX;
-        io.L = 1; io.doT = ddo; io.vec = vec; io.base = dba; io.pred_noise = pred_noise;
-        io.MeanITEs = om; io.CovITEs = oc; io.info = c->io.take<int>((size_t)S);
-        run_predict(c, io);
-        if (MeanITEs) HC(hipMemcpy(MeanITEs, om, sizeof(double) * S * n, hipMemcpyDeviceToHost));
-        if (CovITEs) copy_out_large(c, CovITEs, oc, sizeof(double) * (size_t)S * n * n);
-        return first_info(c);
+        PredictRequest d = rq;             // the same request with device pointers
+        d.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
+        d.lv.doT = up(c, rq.lv.doT, rq.lv.vec ? n : 1);
+        d.lv.base = rq.lv.base ? up(c, rq.lv.base, 1) : nullptr;
+        d.MeanITEs = rq.MeanITEs ? c->io.take<double>((size_t)S * n) : nullptr;
+        d.CovITEs = rq.CovITEs ? c->io.take<double>((size_t)S * n * n) : nullptr;
+        const int st = predict_dev_inner(c, d);
+        if (rq.MeanITEs) HC(hipMemcpy(rq.MeanITEs, d.MeanITEs, sizeof(double) * S * n, hipMemcpyDeviceToHost));
+        if (rq.CovITEs) copy_out_large(c, rq.CovITEs, d.CovITEs, sizeof(double) * (size_t)S * n * n);
+        return st;
     });
 }
 
 int gpslc_ite_distributions(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
                             const double* tyLS, const double* yScale, const double* yNoise, double doT,
                             double pred_noise, double* MeanITEs, double* CovITEs) {
-    int rc = check_common(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise);
-    if (rc) return rc;
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return ite_distributions_impl(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, &doT, false, pred_noise, MeanITEs, CovITEs);
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, &doT);
+    rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
+    int rc = validate(c, rq, kSamplesArgs);
+    return rc ? rc : ite_distributions_host(c, rq);
 }
 
 int gpslc_ite_distributions_vec(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
                                 const double* tyLS, const double* yScale, const double* yNoise, const double* doT,
                                 double pred_noise, double* MeanITEs, double* CovITEs) {
-    int rc = check_common(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise);
-    if (rc) return rc;
-    if ((rc = vec_levels_check(c, doT, c->n, 9))) return rc;
-    if ((rc = vec_mode_check(c))) return rc;
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return ite_distributions_impl(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, doT, true, pred_noise, MeanITEs, CovITEs);
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, doT);
+    rq.lv.vec = true;
+    rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
+    int rc = validate(c, rq, kIteVecArgs);
+    return rc ? rc : ite_distributions_host(c, rq);
 }
 
 int gpslc_ite_distributions_contrast(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
                                      const double* tyLS, const double* yScale, const double* yNoise, double doT,
                                      double doT_base, double pred_noise, double* MeanITEs, double* CovITEs) {
-    int rc = check_common(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise);
-    if (rc) return rc;
-    if ((rc = contrast_levels_check(c, &doT, 1, 9, "doT"))) return rc;
-    if ((rc = contrast_levels_check(c, &doT_base, 1, 10, "doT_base"))) return rc;
-    if ((rc = contrast_mode_check(c))) return rc;
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return ite_distributions_impl(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, &doT, false, pred_noise, MeanITEs, CovITEs, &doT_base);
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, &doT);
+    rq.lv.base = &doT_base;
+    rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
+    int rc = validate(c, rq, kIteContrastArgs);
+    return rc ? rc : ite_distributions_host(c, rq);
 }
 
 // logpdf[s] = -(n log 2pi + logdet_s + quad_s) / 2 from the device-side epilogue values
@@ -2015,7 +1999,8 @@ static void finish_logpdf(gpslc_ctx* c, int64_t S, const double* d_logdet, const
 int gpslc_y_logpdf(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
                    const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale,
                    const double* yNoise, double* logpdf) {
-    int rc = check_common(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise);
+    const PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 0, nullptr);
+    int rc = validate(c, rq, kSamplesArgs);
     if (rc) return rc;
     if (!logpdf) return bad_arg(c, 11, "logpdf is NULL");
     if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
@@ -2041,22 +2026,16 @@ int gpslc_y_logpdf(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_
     return guarded(c, [&]() {
         const size_t n = (size_t)c->n;
         c->io.reset();
-        const double* dU = c->nU ? up(c, U, n * c->nU * S) : nullptr;
         const double* dX = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
         const double* dYo = Y_or_null ? up(c, Y_or_null, n) : nullptr;
-        const double* duy = c->nU ? up(c, uyLS, (size_t)c->nU * S) : nullptr;
-        const double* dxy = c->nX ? up(c, xyLS, (size_t)c->nX * S) : nullptr;
-        const double* dty = up(c, tyLS, S);
-        const double* dys = up(c, yScale, S);
-        const double* dyn = up(c, yNoise, S);
         const double zero = 0.0;
         const double* ddo = up(c, &zero, 1);
         double* old = c->io.take<double>((size_t)S);
         double* oq = c->io.take<double>((size_t)S);
         PredictIO io;
-        io.S = S; io.p = SampleParams{dU, duy, dxy, dty, dys, dyn}; io.X = dX;
+        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S); io.X = dX;
         if (dYo) { io.Y = dYo; io.y_sstride = 0; }    // the value being scored (Gen passes it to logpdf), else the ctx's Y
-        io.L = 0; io.doT = ddo; io.logdet = old; io.quad = oq; io.info = c->io.take<int>((size_t)S);
+        io.lv.L = 0; io.lv.doT = ddo; io.logdet = old; io.quad = oq; io.info = c->io.take<int>((size_t)S);
         run_predict(c, io);
         finish_logpdf(c, S, old, oq, logpdf);
         return first_info(c);
@@ -2082,12 +2061,12 @@ static int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* 
     double* old = c->io.take<double>((size_t)S);
     double* oq = c->io.take<double>((size_t)S);
     PredictIO io;
-    io.S = S;
-    io.p = SampleParams{dF, dls, nullptr, dty, dsc, dno, f_shared ? 0 : (long long)n * nF};
+    io.post.S = S;
+    io.post.p = SampleParams{dF, dls, nullptr, dty, dsc, dno, f_shared ? 0 : (long long)n * nF};
     io.p_shared_u = f_shared != 0;
     io.X = nullptr; io.nU = nF; io.nX = 0;
     io.Y = dtg; io.y_sstride = t_shared ? 0 : (long long)n;
-    io.L = 0; io.doT = ddo; io.logdet = old; io.quad = oq; io.info = c->io.take<int>((size_t)S);
+    io.lv.L = 0; io.lv.doT = ddo; io.logdet = old; io.quad = oq; io.info = c->io.take<int>((size_t)S);
     double* ddraw = nullptr;
     if (draws_or_null) {
         ensure_streams(c);
@@ -2448,14 +2427,10 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
         hipStream_t st = slot.st;
         const int n = (int)c->n, nt = c->nt;
         const long long nlow = (long long)nt * (nt + 1) / 2, nsq = (long long)nt * nt;
-        DevBuf bU, buy, bxy, bty, bys, byn, bdo, info, tiles, inv, part, rect, outb;
-        const double* dU = c->nU ? up(bU, U, (size_t)n * c->nU) : nullptr;
-        const double* duy = c->nU ? up(buy, uyLS, c->nU) : nullptr;
-        const double* dxy = c->nX ? up(bxy, xyLS, c->nX) : nullptr;
-        const double* dty = up(bty, &ty, 1);
-        const double* dys = up(bys, &ysc, 1);
-        const double* dyn = up(byn, &yno, 1);
-        SampleParams sp{dU, duy, dxy, dty, dys, dyn, (long long)n * c->nU};
+        DevBuf bdo, info, tiles, inv, part, rect, outb;
+        c->io.reset();
+        SampleParams sp = upload_samples(c, SampleParams{U, uyLS, xyLS, &ty, &ysc, &yno}, 0, 1);
+        sp.u_sstride = (long long)n * c->nU;
         info.alloc(sizeof(int));
         HC(hipMemsetAsync(info.p, 0, sizeof(int), st));
         tiles.alloc((size_t)nlow * GP_TSQ * 8);
@@ -2468,12 +2443,12 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
              Ksst = rect_ref(rb + 3 * rs, rs, nt), W1 = rect_ref(rb + 4 * rs, rs, nt), W2 = rect_ref(rb + 5 * rs, rs, nt);
         TRef M = lower_ref(tiles.as<double>(), nlow * GP_TSQ);
         // A = K + yNoise I (lower tiles) and its factor
-        GramArgs ga{};
-        ga.X = c->dX; ga.T = c->dT; ga.p = sp; ga.s0 = 0; ga.n = n; ga.nX = c->nX; ga.nU = c->nU; ga.nt = nt;
+        const SampleGrid grid{c->dX, c->dT, sp, 0, n, c->nX, c->nU, nt};
+        GramArgs ga{grid};
         ga.M = M; ga.part = nullptr; ga.with_sums = 0; ga.f32 = 0;
         launch_gram(ga, 1, st);
         factor_panels(c, slot, M, nt, nt, inv.as<double>(), (long long)nt * GP_TSQ, info.as<int>(), 0, 1, 0, false, 0);
-        LdBuildArgs la{c->dX, c->dT, sp, 0, n, c->nX, c->nU, nt, doT, Kt, Kst, KsTt, Ksst};
+        LdBuildArgs la{grid, doT, Kt, Kst, KsTt, Ksst};
         if (doTv) la.doTv = up(bdo, doTv, (size_t)n);
         launch_ld_build(la, st);
         auto emit = [&](const TRef& R, double* host, double diag_add) {
@@ -2534,8 +2509,7 @@ int gpslc_likelihood_distribution(gpslc_ctx* c, const double* U, const double* u
                                   double tyLS, double yScale, double yNoise, double doT, double* CovWW,
                                   double* CovWWs, double* CovWWp, double* CovC11, double* CovC12,
                                   double* CovC21, double* CovC22) {
-    const double ty = tyLS, ysc = yScale, yno = yNoise;
-    int rc = check_common(c, 1, U, uyLS, xyLS, &ty, &ysc, &yno);
+    int rc = validate(c, make_request(1, {U, uyLS, xyLS, &tyLS, &yScale, &yNoise}, 0, nullptr), kSamplesArgs);
     if (rc) return rc;
     return likelihood_distribution_impl(c, U, uyLS, xyLS, tyLS, yScale, yNoise, doT, nullptr, CovWW, CovWWs, CovWWp, CovC11,
                                         CovC12, CovC21, CovC22);
@@ -2545,10 +2519,10 @@ int gpslc_likelihood_distribution_vec(gpslc_ctx* c, const double* U, const doubl
                                       double tyLS, double yScale, double yNoise, const double* doT, double* CovWW,
                                       double* CovWWs, double* CovWWp, double* CovC11, double* CovC12,
                                       double* CovC21, double* CovC22) {
-    const double ty = tyLS, ysc = yScale, yno = yNoise;
-    int rc = check_common(c, 1, U, uyLS, xyLS, &ty, &ysc, &yno);
+    PredictRequest rq = make_request(1, {U, uyLS, xyLS, &tyLS, &yScale, &yNoise}, 1, doT);
+    rq.lv.vec = true;
+    int rc = validate(c, rq, kLikelihoodVecArgs);
     if (rc) return rc;
-    if ((rc = vec_levels_check(c, doT, c->n, 8))) return rc;
     return likelihood_distribution_impl(c, U, uyLS, xyLS, tyLS, yScale, yNoise, 0.0, doT, CovWW, CovWWs, CovWWp, CovC11,
                                         CovC12, CovC21, CovC22);
 }

@@ -120,12 +120,23 @@ struct SampleParams {
     long long u_sstride;   // doubles between the U blocks of consecutive samples (n*nU; 0 = shared)
 };
 
-struct GramArgs {
+// The samples of a chunk and their feature blocks [U_s | X]: what every kernel that evaluates the RBF kernel starts from.  The
+// two members carry address arithmetic and one load only; the callers keep their own 1.0 / ls and multiplication order.
+struct SampleGrid {
     const double* X;   // n x nX (ctx or override)
     const double* T;   // n
     SampleParams p;
     long long s0;      // first sample of this chunk
     int n, nX, nU, nt;
+    __host__ __device__ const double* column(long long s, int f) const {      // feature f of sample s: n values
+        return f < nU ? p.U + s * p.u_sstride + (long long)f * n : X + (long long)(f - nU) * n;
+    }
+    __host__ __device__ double lengthscale(long long s, int f) const {
+        return f < nU ? p.uyLS[s * nU + f] : p.xyLS[s * nX + (f - nU)];
+    }
+};
+
+struct GramArgs : SampleGrid {
     TRef M;            // lower-packed tile matrix of the chunk
     double* part;      // [b][2][nt][Np] partial column sums of B (0) and K (1)
     int with_sums;
@@ -182,18 +193,17 @@ struct RhsArgs {
                      // diagonal tile not at all — every reader of those tiles touches the live 16- / 32-row blocks only
     const double* doT_base;   // non-null: contrasts — level l is the pair (doT[l], doT_base[l]), c_l = (r^a - r^b) .* bsum and
                               // sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B
-    // weighted effects (launch_rhs_weighted only): G weight columns, right-hand side 1 + l + L*g is level l
-    // of column g; bw / kw [b][G][Np] from launch_wsum replace bsum / ksum, sumdelta is [b][L*G], wnorm2 [b][G] = w_g . w_g
+    // G columns of level sums, right-hand side 1 + l + L*g is level l of column g, rows from bw / kw [b][G][Np].  The plain call
+    // is G = 1 with bw = bsum, kw = ksum and W null; weighted effects (W non-null) have G weight columns, bw / kw
+    // from launch_wsum, sumdelta [b][L*G] and wnorm2 [b][G] = w_g . w_g
     const double* W; int G;   // device, column g fastest: W[g + G*j]
     const double* bw; const double* kw; double* wnorm2;
 };
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
-void launch_rhs_weighted(const RhsArgs& r, int nbatch, hipStream_t st);
 
 // weighted column sums BW = B W, KW = K W of a chunk (k_wsum.hip): one pass over the pairs per sample for all G columns
-struct WsumArgs {
-    const double* X; const double* T; SampleParams p; long long s0;
-    int n, nX, nU, nt, G;
+struct WsumArgs : SampleGrid {
+    int G;
     const double* W;       // device, column g fastest: W[g + G*j]
     double* bw; double* kw;   // [b][G][Np]; kw is not written when with_k == 0 (contrasts need BW only)
     int with_k;
@@ -208,11 +218,11 @@ struct EpiArgs {
     double* logdet; double* quad;        // S or null
     int from_rows;   // 1 (single augmented tile row): z.z, z.w_l, w_l.w_l are summed from the rows of R themselves — the
                      // augmented diagonal tile is then never updated (factor_panels(..., skip_aug_diag))
+    // weighted effects (null / 0 = the plain form): L counts the wL levels x G right-hand sides (row 1 + l + wL*g),
+    // meanSATE / varSATE receive mean = z.v and var = (sumdelta - v.v) + pred_noise * wnorm2[b][g] — no division by n
+    const double* wnorm2; int wL;
 };
 void launch_epilogue(const EpiArgs& e, int nbatch, hipStream_t st);
-// weighted effects: e.L counts the wL levels x G right-hand sides (row 1 + l + wL*g), meanSATE / varSATE receive
-// mean = z.v and var = (sumdelta - v.v) + pred_noise * wnorm2[b][g] — no division by n; logdet / quad are not written
-void launch_epilogue_weighted(const EpiArgs& e, const double* wnorm2, int wL, int nbatch, hipStream_t st);
 
 struct BackArgs {
     TRef M; const double* inv; long long inv_bstride; int nt; int naug;
@@ -220,9 +230,9 @@ struct BackArgs {
 };
 void launch_backsolve(const BackArgs& a, int nbatch, hipStream_t st);
 
-struct IteMeanArgs {
-    const double* X; const double* T; SampleParams p; long long s0; long long S;
-    int n, nX, nU, nt, L; const double* doT;
+struct IteMeanArgs : SampleGrid {
+    long long S;
+    int L; const double* doT;
     const double* alpha;   // [b][Np]
     const double* Y;       // right-hand side alpha solves for: A alpha = Y (sample s at Y + s*y_sstride)
     long long y_sstride;
@@ -236,9 +246,8 @@ struct IteMeanArgs {
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st);
 
 // vector levels (per-individual interventions, k_vec.hip): the level sums and MeanITE as passes over the pairs
-struct VecArgs {
-    const double* X; const double* T; SampleParams p; long long s0;
-    int n, nX, nU, nt, L;
+struct VecArgs : SampleGrid {
+    int L;
     const double* doT;     // n x L: d_l[i] at doT[i + n*l]
     // launch_vec_sums: c_l into row 1 + l of the augmented tiles of M, 1' Delta_l 1 into sumdelta [b][L] (part: [b][L][nt])
     TRef M; double* part; double* sumdelta;
@@ -255,9 +264,7 @@ void launch_process_cov(const double* in, long long n, double scale, double nois
                         hipStream_t st);
 
 // unit B (full ITE covariance) helpers
-struct DtArgs {
-    const double* X; const double* T; SampleParams p; long long s0;
-    int n, nX, nU, nt;
+struct DtArgs : SampleGrid {
     const double* doT;     // device: intervention levels; batch element b = (sample s0 + b / lc, level l0 + b % lc)
     int l0, lc;
     int vec;               // vector levels: doT is n x L (level l at doT + n*l), g_ij / g_ji / h_ij per pair
@@ -305,9 +312,8 @@ void launch_row_norms(const RowNormArgs& a, hipStream_t st);
 void launch_quad_rows(const QuadRowsArgs& a, hipStream_t st);
 
 // likelihoodDistribution (src/likelihood.jl:8-174): dense blocks as rectangular tile matrices
-struct LdBuildArgs {
-    const double* X; const double* T; SampleParams p; long long s0;
-    int n, nX, nU, nt; double doT;
+struct LdBuildArgs : SampleGrid {
+    double doT;
     TRef K, Ks, KsT, Kss;   // nt x nt rectangular each: CovWW, CovWWs, CovWWs', CovWsWs
     const double* doTv;     // non-null: per-individual intervention d (n, device) instead of the scalar doT
 };

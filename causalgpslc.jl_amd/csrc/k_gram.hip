@@ -6,8 +6,9 @@
 //                      K = B.*E that the SATE path needs.
 //   rhs_prepare/tiles  column sums -> augmented right-hand sides [Y, c(1..L)] and sum(Delta).  CON: the contrast form of
 //                      both (level l = the pair (doT[l], doT_base[l])).
-//   rhs_w_prepare/tiles the same for weighted effects: G weight columns x L levels from bw = B w, kw = K w (k_wsum.hip).
-//   epilogue           Schur complement of the augmented block -> MeanSATE, VarSATE, logdet, quad; epilogue_w: the weighted form.
+//   rhs_w_prepare      the level sums of weighted effects: G weight columns x L levels from bw = B w, kw = K w (k_wsum.hip,
+//                      DESIGN.md §13); rhs_tiles writes their rows.
+//   epilogue           Schur complement of the augmented block -> MeanSATE, VarSATE (plain or weighted), logdet, quad.
 //   rbf_log / process_cov  the two src/kernel.jl entry points as stand-alone dense kernels.
 #include "gpslc_internal.h"
 #include "gp_math.h"
@@ -71,10 +72,8 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
         for (int k = 0; k < NIT; ++k) {
             const int idx = tid + 256 * k;
             const int f = min(idx >> 7, FT - 1), r = idx & 127;
-            const bool isu = f < g.nU;
-            const double* src = isu ? g.p.U + s * g.p.u_sstride + (long long)f * n : g.X + (long long)(f - g.nU) * n;
-            const double* lp = isu ? g.p.uyLS + s * g.nU + f : g.p.xyLS + s * g.nX + (f - g.nU);
-            lv[k] = *lp;
+            const double* src = g.column(s, f);
+            lv[k] = g.lengthscale(s, f);
             av[k] = src[min(gi0 + r, n - 1)];
             cv[k] = src[min(gj0 + r, n - 1)];
         }
@@ -91,11 +90,8 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
     } else {
         for (int idx = tid; idx < F * GP_TS; idx += 256) {
             const int f = idx >> 7, r = idx & 127;
-            const double* src;
-            double l;
-            if (f < g.nU) { src = g.p.U + s * g.p.u_sstride + (long long)f * n; l = g.p.uyLS[s * g.nU + f]; }
-            else { src = g.X + (long long)(f - g.nU) * n; l = g.p.xyLS[s * g.nX + (f - g.nU)]; }
-            const double il = 1.0 / l;
+            const double* src = g.column(s, f);
+            const double il = 1.0 / g.lengthscale(s, f);
             fr[f * GP_TS + r] = (RT)((gi0 + r < n) ? src[gi0 + r] * il : 0.0);
             fc[f * GP_TS + r] = (RT)((gj0 + r < n) ? src[gj0 + r] * il : 0.0);
         }
@@ -312,8 +308,8 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
 }
 
 // rhs_tiles: write the augmented row tiles: row q of the augmented block is right-hand side q
-// (q = 0: Y, q = 1 + l: c_l = r_l .* bsum - ksum), zero elsewhere; zero the aug x aug tiles.
-// CON: c_l = (r^a - r^b) .* bsum for the pair (a, b) = (doT[l], doT_base[l]) — the e_ij of the ordinary level cancels, and
+// (q = 0: Y, q = 1 + l + L*g: c_l = r_l .* bw_g - kw_g of column g), zero elsewhere; zero the aug x aug tiles.
+// CON: c_l = (r^a - r^b) .* bw_g for the pair (a, b) = (doT[l], doT_base[l]) — the e_ij of the ordinary level cancels, and
 // a == b gives r^a == r^b bit for bit: an exact zero row.
 // grid (nt + naug, naug, batch): tile (nt + a, j) with j = blockIdx.x, a = blockIdx.y (j <= nt + a).
 template <bool CON>
@@ -339,50 +335,31 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
         return;
     }
     const int Np = a.nt * GP_TS;
-    const double* bs = a.bsum + (long long)b * Np;
-    const double* ks = a.ksum + (long long)b * Np;
+    const int R = a.L * a.G;
     const double tl = a.tyLS[s];
     const double wt = 1.0 / (tl * tl);
-    // element (row q, col c) at c*128 + q; thread -> consecutive q for coalescing
-    if (a.live_rows > 0) {
-        // 32 live rows at most: 32 x 128 elements, 256 contiguous bytes per column.  ALL 32 rows are written (zeros beyond
-        // the last right-hand side): the strip and trailing kernels handle these tiles in 32-row units, so wave 0 loads,
-        // multiplies and stores rows 16..31 even when only 16 are live — they must not hold what a reused arena left there
-        // (NaN / Inf).  The other 96 rows keep whatever the workspace held: no kernel touches them, and a row of an MFMA
-        // product depends on its own row only.
-        for (int idx = tid; idx < 32 * GP_TS; idx += 256) {
-            const int c = idx >> 5, q = idx & 31;
-            const int gj = j * GP_TS + c;
-            double v = 0.0;
-            if (gj < a.n) {
-                if (q == 0) v = a.Y[s * a.y_sstride + gj];
-                else if (q <= a.L) v = rhs_level_value<CON>(a, q - 1, gj, wt, bs, ks);
-            }
-            tile[c * GP_TS + q] = v;
-        }
-        return;
-    }
-    for (int idx = tid; idx < GP_TSQ; idx += 256) {
-        const int c = idx >> 7, q = idx & 127;
+    // element (row q, col c) at c*128 + q; thread -> consecutive q for coalescing.
+    // live_rows > 0: 32 live rows at most: 32 x 128 elements, 256 contiguous bytes per column.  ALL 32 rows are written (zeros
+    // beyond the last right-hand side): the strip and trailing kernels handle these tiles in 32-row units, so wave 0 loads,
+    // multiplies and stores rows 16..31 even when only 16 are live — they must not hold what a reused arena left there
+    // (NaN / Inf).  The other 96 rows keep whatever the workspace held: no kernel touches them, and a row of an MFMA
+    // product depends on its own row only.  Else the whole tile.
+    const int sh = a.live_rows > 0 ? 5 : 7;
+    for (int idx = tid; idx < (GP_TS << sh); idx += 256) {
+        const int c = idx >> sh, q = idx & ((1 << sh) - 1);
         const int gq = au * GP_TS + q;        // right-hand side index
         const int gj = j * GP_TS + c;         // instance index
         double v = 0.0;
         if (gj < a.n) {
             if (gq == 0) v = a.Y[s * a.y_sstride + gj];
-            else if (gq <= a.L) v = rhs_level_value<CON>(a, gq - 1, gj, wt, bs, ks);
+            else if (gq <= R) {
+                const int g = a.G > 1 ? (gq - 1) / a.L : 0, l = gq - 1 - a.L * g;
+                const long long o = ((long long)b * a.G + g) * Np;
+                v = rhs_level_value<CON>(a, l, gj, wt, a.bw + o, a.kw + o);
+            }
         }
-        tile[idx] = v;
+        tile[c * GP_TS + q] = v;
     }
-}
-
-template <bool CON>
-static void launch_rhs_t(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.with_sums) hipLaunchKernelGGL(rhs_prepare_kernel<CON>, dim3(nbatch), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(rhs_tiles_kernel<CON>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
-}
-void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.doT_base) launch_rhs_t<true>(r, nbatch, st);
-    else launch_rhs_t<false>(r, nbatch, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -434,56 +411,24 @@ __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
     }
 }
 
-// rhs_w_tiles: the augmented row tiles of the weighted right-hand sides, in the three layouts of rhs_tiles_kernel (16 / 32 live
-// rows, a full augmented tile row, several tile rows); the level rows take rhs_level_value with column g's bw / kw.
+// the plain and the weighted prepare kernels reduce in different orders (both are part of the results); the tiles are one kernel
 template <bool CON>
-__global__ __launch_bounds__(256) void rhs_w_tiles_kernel(RhsArgs a) {
-    const int tid = threadIdx.x;
-    const int j = blockIdx.x, au = blockIdx.y, b = blockIdx.z;
-    if (j > a.nt + au) return;
-    const long long s = a.s0 + b;
-    double* tile = tref_tile(a.M, b, a.nt + au, j);
-    if (j >= a.nt) {
-        if (a.live_rows > 0) return;
-        for (int idx = tid; idx < GP_TSQ; idx += 256) tile[idx] = 0.0;
-        return;
-    }
-    const int Np = a.nt * GP_TS;
-    const int R = a.L * a.G;
-    const double tl = a.tyLS[s];
-    const double wt = 1.0 / (tl * tl);
-    // live_rows > 0: all 32 rows of the live block are written (see rhs_tiles_kernel); else the whole tile
-    const int sh = a.live_rows > 0 ? 5 : 7;
-    for (int idx = tid; idx < (GP_TS << sh); idx += 256) {
-        const int c = idx >> sh, q = idx & ((1 << sh) - 1);
-        const int gq = au * GP_TS + q;        // right-hand side index
-        const int gj = j * GP_TS + c;         // instance index
-        double v = 0.0;
-        if (gj < a.n) {
-            if (gq == 0) v = a.Y[s * a.y_sstride + gj];
-            else if (gq <= R) {
-                const int l = (gq - 1) % a.L, g = (gq - 1) / a.L;
-                const long long o = ((long long)b * a.G + g) * Np;
-                v = rhs_level_value<CON>(a, l, gj, wt, a.bw + o, a.kw + o);
-            }
-        }
-        tile[c * GP_TS + q] = v;
-    }
+static void launch_rhs_t(const RhsArgs& r, int nbatch, hipStream_t st) {
+    if (r.W) hipLaunchKernelGGL(rhs_w_prepare_kernel<CON>, dim3(r.L * r.G, nbatch), dim3(256), 0, st, r);
+    else if (r.with_sums) hipLaunchKernelGGL(rhs_prepare_kernel<CON>, dim3(nbatch), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(rhs_tiles_kernel<CON>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
 }
-
-template <bool CON>
-static void launch_rhs_w_t(const RhsArgs& r, int nbatch, hipStream_t st) {
-    hipLaunchKernelGGL(rhs_w_prepare_kernel<CON>, dim3(r.L * r.G, nbatch), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(rhs_w_tiles_kernel<CON>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
-}
-void launch_rhs_weighted(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.doT_base) launch_rhs_w_t<true>(r, nbatch, st);
-    else launch_rhs_w_t<false>(r, nbatch, st);
+void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st) {
+    if (r.doT_base) launch_rhs_t<true>(r, nbatch, st);
+    else launch_rhs_t<false>(r, nbatch, st);
 }
 
 // ---------------------------------------------------------------------------------------
 // epilogue: after the augmented factorisation tile (nt+a, nt+a') holds G = -R R^T with
 // R = [z, w_1 .. w_L] (z = L^-1 Y, w_l = L^-1 c_l).  One workgroup per sample.
+// The weighted form (e.wnorm2): right-hand side q = 1 + l + wL*g is level l of weight column g, and
+//   mean = z . v_q        var = (sumdelta_q - v_q . v_q) + pred_noise * wnorm2[g]
+// — the weights are used as given, nothing is divided by n.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void epilogue_kernel(EpiArgs e) {
     __shared__ double red[4];
@@ -499,6 +444,17 @@ __global__ __launch_bounds__(256) void epilogue_kernel(EpiArgs e) {
     }
     const double ld = 2.0 * block_sum_256(acc, red);
     const double nn = (double)e.n;
+    // level q - 1 from z . w (zw) and w . w (ww)
+    auto put_level = [&](int l, double zw, double ww) {
+        const double sd = e.sumdelta[(long long)b * e.L + l];
+        if (e.wnorm2) {
+            if (e.meanSATE) e.meanSATE[s + e.S * l] = zw;
+            if (e.varSATE) e.varSATE[s + e.S * l] = (sd - ww) + e.pred_noise * e.wnorm2[(long long)b * (e.L / e.wL) + l / e.wL];
+            return;
+        }
+        if (e.meanSATE) e.meanSATE[s + e.S * l] = zw / nn;
+        if (e.varSATE) e.varSATE[s + e.S * l] = ((sd - ww) + nn * e.pred_noise) / (nn * nn);
+    };
     if (e.from_rows) {
         // The Schur block -R R^T used to come from one more tile update (an item streaming two full operand panels for
         // (L + 1)^2 live entries: 1.9 % of the GPU time at N = 1024) of which only z.z, z.w_l and w_l.w_l are read.  Here
@@ -511,10 +467,7 @@ __global__ __launch_bounds__(256) void epilogue_kernel(EpiArgs e) {
         if (tid == 0 && e.logdet) e.logdet[s] = ld;
         auto put = [&](int q, double zw, double ww) {
             if (q == 0) { if (e.quad) e.quad[s] = ww; return; }
-            const int l = q - 1;
-            const double sd = e.sumdelta[(long long)b * e.L + l];
-            if (e.meanSATE) e.meanSATE[s + e.S * l] = zw / nn;
-            if (e.varSATE) e.varSATE[s + e.S * l] = ((sd - ww) + nn * e.pred_noise) / (nn * nn);
+            put_level(q - 1, zw, ww);
         };
         if (nq >= 16) {
             // Level sweeps: a lane reads 16 CONSECUTIVE right-hand sides of its column with each visit (one full 128-byte line)
@@ -569,58 +522,12 @@ __global__ __launch_bounds__(256) void epilogue_kernel(EpiArgs e) {
         const int q = 1 + l, au = q >> 7, qq = q & 127;
         const double wz = -tref_tile(e.M, b, e.nt + au, e.nt)[0 * GP_TS + qq];
         const double ww = -tref_tile(e.M, b, e.nt + au, e.nt + au)[qq * GP_TS + qq];
-        const double sd = e.sumdelta[(long long)b * e.L + l];
-        if (e.meanSATE) e.meanSATE[s + e.S * l] = wz / nn;
-        if (e.varSATE) e.varSATE[s + e.S * l] = ((sd - ww) + nn * e.pred_noise) / (nn * nn);
+        put_level(l, wz, ww);
     }
 }
 
 void launch_epilogue(const EpiArgs& e, int nbatch, hipStream_t st) {
     hipLaunchKernelGGL(epilogue_kernel, dim3(nbatch), dim3(256), 0, st, e);
-}
-
-// The weighted form: right-hand side q = 1 + l + wL*g is level l of weight column g, and
-//   mean = z . v_q        var = (sumdelta_q - v_q . v_q) + pred_noise * wnorm2[g]
-// — the weights are used as given, nothing is divided by n.  from_rows: wave w sums q = 1 + w, 5 + w, ... from the rows of R
-// (lanes stride the columns, fixed butterfly); else from the Schur tiles -R R^T.  The plain epilogue, launched beside it with
-// L = 0, writes logdet and quad.
-__global__ __launch_bounds__(256) void epilogue_w_kernel(EpiArgs e, const double* wnorm2, int wL) {
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x;
-    const long long s = e.s0 + b;
-    const int G = e.L / wL;
-    auto put = [&](int q, double zv, double vv) {
-        const int l = q - 1;
-        const double sd = e.sumdelta[(long long)b * e.L + l];
-        if (e.meanSATE) e.meanSATE[s + e.S * l] = zv;
-        if (e.varSATE) e.varSATE[s + e.S * l] = (sd - vv) + e.pred_noise * wnorm2[(long long)b * G + l / wL];
-    };
-    if (e.from_rows) {
-        const int lane = tid & 63, wave = tid >> 6;
-        const int ncol = e.nt * GP_TS;
-        for (int q = 1 + wave; q <= e.L; q += 4) {
-            double zv = 0.0, vv = 0.0;
-            for (int i = lane; i < ncol; i += 64) {
-                const double* col = tref_tile(e.M, b, e.nt, i >> 7) + (long long)(i & 127) * GP_TS;
-                const double z = col[0], v = col[q];
-                zv = fma(z, v, zv);
-                vv = fma(v, v, vv);
-            }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) { zv += __shfl_xor(zv, o, 64); vv += __shfl_xor(vv, o, 64); }
-            if (lane == 0) put(q, zv, vv);
-        }
-        return;
-    }
-    for (int l = tid; l < e.L; l += 256) {
-        const int q = 1 + l, au = q >> 7, qq = q & 127;
-        const double zv = -tref_tile(e.M, b, e.nt + au, e.nt)[0 * GP_TS + qq];
-        const double vv = -tref_tile(e.M, b, e.nt + au, e.nt + au)[qq * GP_TS + qq];
-        put(q, zv, vv);
-    }
-}
-void launch_epilogue_weighted(const EpiArgs& e, const double* wnorm2, int wL, int nbatch, hipStream_t st) {
-    hipLaunchKernelGGL(epilogue_w_kernel, dim3(nbatch), dim3(256), 0, st, e, wnorm2, wL);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -91,12 +91,8 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
     const long long b = blockIdx.y, s = a.s0 + b;
     const int n = a.n, Np = a.nt * GP_TS;
 
-    auto feat_src = [&](int f) -> const double* {
-        return (f < a.nU) ? a.p.U + s * a.p.u_sstride + (long long)f * n : a.X + (long long)(f - a.nU) * n;
-    };
-    auto feat_il = [&](int f) -> double {
-        return 1.0 / ((f < a.nU) ? a.p.uyLS[s * a.nU + f] : a.p.xyLS[s * a.nX + (f - a.nU)]);
-    };
+    auto feat_src = [&](int f) { return a.column(s, f); };
+    auto feat_il = [&](int f) { return 1.0 / a.lengthscale(s, f); };
     int gi[RB];
     RT af[RB][FREG];   // this thread's rows' features / LS
 #pragma unroll
@@ -236,12 +232,8 @@ __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
     const long long b = blockIdx.y, s = a.s0 + b;
     const int n = a.n, Np = a.nt * GP_TS;
 
-    auto feat_src = [&](int f) -> const double* {
-        return (f < a.nU) ? a.p.U + s * a.p.u_sstride + (long long)f * n : a.X + (long long)(f - a.nU) * n;
-    };
-    auto feat_il = [&](int f) -> double {
-        return 1.0 / ((f < a.nU) ? a.p.uyLS[s * a.nU + f] : a.p.xyLS[s * a.nX + (f - a.nU)]);
-    };
+    auto feat_src = [&](int f) { return a.column(s, f); };
+    auto feat_il = [&](int f) { return 1.0 / a.lengthscale(s, f); };
     for (int idx = tid; idx < F * GP_TS; idx += 256) {
         const int f = idx >> 7, rr = idx & 127;
         const int g = ib * GP_TS + rr;
@@ -459,9 +451,8 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
     }
     for (int idx = tid; idx < F * GP_TS; idx += 256) {
         const int f = idx >> 7, r = idx & 127;
-        const double* src = (f < a.nU) ? a.p.U + s * a.p.u_sstride + (long long)f * n
-                                       : a.X + (long long)(f - a.nU) * n;
-        const double il = 1.0 / ((f < a.nU) ? a.p.uyLS[s * a.nU + f] : a.p.xyLS[s * a.nX + (f - a.nU)]);
+        const double* src = a.column(s, f);
+        const double il = 1.0 / a.lengthscale(s, f);
         fr[idx] = (gi0 + r < n) ? src[gi0 + r] * il : 0.0;
         fc[idx] = (gj0 + r < n) ? src[gj0 + r] * il : 0.0;
     }
@@ -991,9 +982,8 @@ __global__ __launch_bounds__(256) void ld_build_kernel(LdBuildArgs a) {
     const double wt = 1.0 / (tl * tl);
     for (int idx = tid; idx < F * GP_TS; idx += 256) {
         const int f = idx >> 7, r = idx & 127;
-        const double* src = (f < a.nU) ? a.p.U + s * a.p.u_sstride + (long long)f * n
-                                       : a.X + (long long)(f - a.nU) * n;
-        const double il = 1.0 / ((f < a.nU) ? a.p.uyLS[s * a.nU + f] : a.p.xyLS[s * a.nX + (f - a.nU)]);
+        const double* src = a.column(s, f);
+        const double il = 1.0 / a.lengthscale(s, f);
         fr[idx] = (gi0 + r < n) ? src[gi0 + r] * il : 0.0;
         fc[idx] = (gj0 + r < n) ? src[gj0 + r] * il : 0.0;
     }

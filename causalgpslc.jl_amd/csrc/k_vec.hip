@@ -43,8 +43,8 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
     const bool own_in = go < n;
 
     auto feat = [&](int f, int i) -> double {
-        const double* src = (f < a.nU) ? a.p.U + s * a.p.u_sstride + (long long)f * n : a.X + (long long)(f - a.nU) * n;
-        const double il = 1.0 / ((f < a.nU) ? a.p.uyLS[s * a.nU + f] : a.p.xyLS[s * a.nX + (f - a.nU)]);
+        const double* src = a.column(s, f);
+        const double il = 1.0 / a.lengthscale(s, f);
         return src[i] * il;
     };
     for (int idx = tid; idx < F * GP_TS; idx += 256) {

@@ -41,12 +41,8 @@ __global__ __launch_bounds__(256, 2) void wsum_mfma_kernel(WsumArgs a) {
     const long long b = blockIdx.y, s = a.s0 + b;
     const int n = a.n, Np = a.nt * GP_TS, G = a.G;
 
-    auto feat_src = [&](int f) -> const double* {
-        return (f < a.nU) ? a.p.U + s * a.p.u_sstride + (long long)f * n : a.X + (long long)(f - a.nU) * n;
-    };
-    auto feat_il = [&](int f) -> double {
-        return 1.0 / ((f < a.nU) ? a.p.uyLS[s * a.nU + f] : a.p.xyLS[s * a.nX + (f - a.nU)]);
-    };
+    auto feat_src = [&](int f) { return a.column(s, f); };
+    auto feat_il = [&](int f) { return 1.0 / a.lengthscale(s, f); };
     for (int idx = tid; idx < F * GP_TS; idx += 256) {
         const int f = idx >> 7, rr = idx & 127;
         const int g = ib * GP_TS + rr;
