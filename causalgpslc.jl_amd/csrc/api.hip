@@ -101,6 +101,7 @@ struct ProfRec {
     int cls;     // kernel class, see gpslc_profile_get_class (include/gpslc_hip.h)
 };
 constexpr int kProfClasses = 5;
+constexpr int kOrderBlock = 8;     // super-block edge (tiles) of the L2-blocked visiting order of a trailing update (tri_order)
 
 // device-resident task list of one (tile count, augmented row, batch size, group size) shape of the persistent
 // factorisation launch (potrf_tasks_kernel); built once per shape and kept (see task_list_for)
@@ -179,7 +180,6 @@ struct gpslc_ctx {
     bool mvn_valid = false;
     // L2-blocked visiting orders of the lower-triangular tile sets, keyed by the triangle size m
     std::vector<unsigned short*> tri_order;
-    int order_block = 8;
     // profiling of the dominant kernel
     std::vector<ProfRec> prof;
     size_t prof_used = 0;
@@ -258,39 +258,10 @@ void ensure_streams(gpslc_ctx* c) {
 void rearm_queue(StreamSlot& s) { HC(hipMemsetAsync(s.queue, 0, 16 * sizeof(int), s.st)); }
 
 // ---- profiled launch of the accumulate-mode tile kernel ---------------------------------
-// GPSLC_SYRK_DIAG=0 keeps the diagonal tiles in the general kernel (A/B switch for measurements)
-static int sym_mode() {
-    static const int m = diag_env("GPSLC_SYRK_DIAG", 1) == 0 ? 1 : 2;
-    return m;
-}
-
-static int col_sym_mode() {
-    // the one diagonal tile of an in-panel column update also goes to the lower-triangle kernel (+0.2 %, measured)
-    static const int m = diag_env("GPSLC_SYRK_DIAG_COL", 1) == 0 ? 1 : sym_mode();
-    return m;
-}
-
-// with a single short augmented tile row, its off-diagonal tiles ride with the diagonal items (GemmArgs::sym == 3)
-static int aug_sym(int sym, int short_rows) {
-    static const int on = diag_env("GPSLC_SYRK_AUG", 1) == 0 ? 0 : 1;
-    // up to 32 live rows (31 levels): beyond that the diagonal kernel runs out of registers and the augmented
-    // tiles carry enough real work to stay ordinary items
-    return (sym == 2 && short_rows > 0 && short_rows <= 32 && on) ? 3 : sym;
-}
-
-// GPSLC_FUSE_PANEL=0: separate panel-product launches for every column (measurement switch)
-static int fuse_mode() {
-    static const int m = diag_env("GPSLC_FUSE_PANEL", 1) == 0 ? 0 : 1;
-    return m;
-}
-
-// the diagonal tile (and, with sym == 3, the augmented-row tile) of a symmetric column update, on its own
-static void launch_sym_diag_tiles(const GemmArgs& g, hipStream_t st) {
-    GemmArgs d = g;
-    const int cand = g.shape == 0 ? g.mi : 1;
-    d.mi = g.short_rows > 0 ? std::max(0, std::min(cand, g.short_row0 - g.i0)) : cand;
-    launch_syrk_diag(d, g.sym == 3 && g.short_rows > 0, st);
-}
+// GemmArgs::sym of a symmetric launch of the factorisation of A: with a single short augmented tile row, its off-diagonal tiles
+// ride with the diagonal items (3).  Up to 32 live rows (31 levels): beyond that the diagonal kernel runs out of registers and
+// the augmented tiles carry enough real work to stay ordinary items
+static int aug_sym(int short_rows) { return (short_rows > 0 && short_rows <= 32) ? 3 : 2; }
 
 // prof_base: the kernel class of the profiled launches (0 = class 0 or 1 by the launch's shape)
 void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
@@ -298,10 +269,7 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
     GemmArgs g = g0;
     g.diag_skip = 0;
     g.dbg = nullptr;
-    static const int nt_c = diag_env("GPSLC_NT_C", 0);
-    g.nt_c = (nt_c && g.shape == 0) ? 1 : 0;      // trailing updates only
-    static const int use_queue = diag_env("GPSLC_GEMM_QUEUE", 1);
-    g.queue = use_queue ? s.queue : nullptr;
+    g.queue = s.queue;
     if (g.ntiles <= 0 || g.nbatch <= 0 || (g.k1 <= g.k0 && g.accumulate && !g.fuse)) return;     // fuse with an empty K range: panel product only
 #ifdef GPSLC_DIAG
     // measurement build only: timing-only kernel variants (results are garbage by construction) and in-kernel
@@ -323,10 +291,10 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
         dbg_done = true;
     }
 #endif
-    // sym == 2: the full-size diagonal tiles (those above the augmented rows) go to the lower-triangle kernel
+    // symmetric launches: the full-size diagonal tiles (those above the augmented rows) go to the lower-triangle kernel
     auto launch_diag_tiles = [&]() {
-        if (g.fuse) return;     // factor_panels launched them before the diagonal-block kernel (launch_sym_diag_tiles)
-        if (g.sym >= 2 && g.i0 == g.j0 && (g.diag_skip == 0 || g.diag_skip == 3)) {
+        if (g.fuse) return;     // factor_panels updated the diagonal tile before this launch (launch_diag_update_potrf)
+        if (g.sym && g.i0 == g.j0 && (g.diag_skip == 0 || g.diag_skip == 3)) {
             GemmArgs d = g;
             const int cand = g.shape == 0 ? g.mi : 1;      // a column update holds one diagonal tile
             d.mi = g.short_rows > 0 ? std::max(0, std::min(cand, g.short_row0 - g.i0)) : cand;
@@ -348,9 +316,10 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
         double diag_items = 0.0;
         if (g.sym && g.i0 == g.j0) diag_items = (g.shape == 0) ? (double)g.mi : 1.0;
         if (short_items > 0 && g.shape == 0) diag_items -= 1.0;
-        // sym == 2: this kernel does not run the full-size diagonal tiles at all (launch_syrk_diag does, outside the
-        // timed bracket, so that the HIP-event average equals rocprofv3's average for the dominant kernel)
-        const double diag_out = (g.sym >= 2 && g.i0 == g.j0 && (g.diag_skip == 0 || g.diag_skip == 3)) ? 1.0 : 0.5;
+        // this kernel does not run the full-size diagonal tiles at all (launch_syrk_diag does, outside the timed bracket, so
+        // that the HIP-event average equals rocprofv3's average for the dominant kernel); the timing-only variants
+        // (GPSLC_GEMM_DIAG = 1 / 2) keep them as half a tile product each
+        const double diag_out = (g.diag_skip == 0 || g.diag_skip == 3) ? 1.0 : 0.5;
         // sym == 3: the off-diagonal augmented-row tiles are not this kernel's either (they ride with the diagonal items)
         double short_exec = short_items;
         if (g.sym == 3 && short_items > 0) short_exec = (g.shape == 0) ? 1.0 : 0.0;
@@ -401,8 +370,8 @@ void prof_collect(gpslc_ctx* c) {
 // G + G operand tile rows together and share them in that XCD's L2 instead of each streaming its own
 // copy from HBM (operand traffic / ~G).
 const unsigned short* tri_order(gpslc_ctx* c, int m) {
-    const int G = c->order_block;
-    if (G <= 1 || m <= 2) return nullptr;
+    constexpr int G = kOrderBlock;
+    if (m <= 2) return nullptr;
     if ((int)c->tri_order.size() <= m) c->tri_order.resize(m + 1, nullptr);
     if (c->tri_order[m]) return c->tri_order[m];
     std::vector<unsigned short> h;
@@ -438,8 +407,7 @@ const TaskList& task_list_for(gpslc_ctx* c, int nt, int back, int nb, int G, int
     }
     TaskList t;
     t.nt = nt; t.back = back; t.nb = nb; t.G = G; t.rows = rows; t.aug_full = aug_full;
-    static const int merge_diag = diag_env("GPSLC_TASK_MERGE", 1);      // measurement switch: 0 = strip(k + 1, k) as a task of its own
-    std::vector<unsigned> h = build_task_list(nt, back, nb, G, rows, aug_full, &t.ntasks, merge_diag);
+    std::vector<unsigned> h = build_task_list(nt, back, nb, G, rows, aug_full, &t.ntasks, /*merge_diag=*/1);
     HC(hipMalloc((void**)&t.dev, h.size() * sizeof(unsigned)));
     HC(hipMemcpy(t.dev, h.data(), h.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     t.used = ++c->task_clock;
@@ -451,11 +419,10 @@ const TaskList& task_list_for(gpslc_ctx* c, int nt, int back, int nb, int G, int
 // factorisation, ONE short augmented row whose tiles ride with the diagonal tasks and whose diagonal tile nobody reads
 // (EpiArgs::from_rows) — the shape of run_predict's factorisation of A at N <= 128 task_max_nt
 bool potrf_tasks_ok(const gpslc_ctx* c, int nt, int ntot, int short_rows, bool skip_aug_diag, int nb, const double* inv) {
-    static const int on = diag_env("GPSLC_TASKS", 1);
     // one left-looking panel only: a panel width given through gpslc_set_tuning keeps its meaning (nt beyond it takes the panel
     // schedule); with the default width the persistent launch factorises the whole matrix as ONE panel up to task_max_nt
     const int pmax = c->panel_set ? std::max(1, c->panel) : TASK_MAX_NT;
-    if (!on || !inv || nt < std::max(2, c->task_min_nt) || nt > std::min(std::min(c->task_max_nt, TASK_MAX_NT), pmax) ||
+    if (!inv || nt < std::max(2, c->task_min_nt) || nt > std::min(std::min(c->task_max_nt, TASK_MAX_NT), pmax) ||
         nb >= TASK_MAX_BATCH || nb < c->task_min_batch)
         return false;
     return ntot == nt + 1 && short_rows > 0 && short_rows <= GP_TS && skip_aug_diag;
@@ -478,10 +445,8 @@ void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv
         HC(hipMalloc((void**)&s.sync, ints * sizeof(int)));
         s.sync_ints = ints;
     }
-    static const int g_env = diag_env("GPSLC_TASK_G", 0);
-    static const int r_env = diag_env("GPSLC_TASK_ROWS", 0);
-    const TaskList& tl = task_list_for(c, nt, back_alpha ? 1 : 0, nb, g_env > 0 ? g_env : c->task_group,
-                                       std::max(1, std::min(4, r_env > 0 ? r_env : (nt > 8 ? 1 : c->task_rows))), short_rows > 32);
+    const TaskList& tl = task_list_for(c, nt, back_alpha ? 1 : 0, nb, c->task_group,
+                                       std::max(1, std::min(4, nt > 8 ? 1 : c->task_rows)), short_rows > 32);
     HC(hipMemsetAsync(s.sync, 0, ints * sizeof(int), st));
     PotrfTaskArgs a{};
     a.g.A = M; a.g.B = M; a.g.C = M;
@@ -563,7 +528,7 @@ void factor_robust(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int* info
         if (k > ka) {
             GemmArgs g{};
             g.A = M; g.B = M; g.C = M;
-            g.shape = 1; g.i0 = k; g.j0 = k; g.mi = nt - k; g.mj = 1; g.sym = col_sym_mode();
+            g.shape = 1; g.i0 = k; g.j0 = k; g.mi = nt - k; g.mj = 1; g.sym = 2;
             g.k0 = ka; g.k1 = k; g.accumulate = 1; g.nbatch = nb; g.ntiles = g.mi;
             gemm(c, g, s, prof_base);
         }
@@ -573,7 +538,7 @@ void factor_robust(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int* info
             GemmArgs g{};
             g.A = M; g.B = M; g.C = M;
             const int m = nt - kend;
-            g.shape = 0; g.i0 = kend; g.j0 = kend; g.mi = m; g.mj = m; g.sym = sym_mode();
+            g.shape = 0; g.i0 = kend; g.j0 = kend; g.mi = m; g.mj = m; g.sym = 2;
             g.k0 = ka; g.k1 = kend; g.accumulate = 1; g.nbatch = nb; g.ntiles = m * (m + 1) / 2;
             g.order = tri_order(c, m);
             gemm(c, g, s, prof_base);
@@ -598,66 +563,51 @@ void factor_panels(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int ntot,
     for (int k = 0; k < nt; ++k) {
         const int ka = (k / pw) * pw;
         const int kend = std::min(ka + pw, nt);
-        bool fused = false;
-        if (k > ka) {   // column update inside the panel: tile(i,k) -= sum_{kk in [ka,k)} tile(i,kk) tile(k,kk)^T
-            GemmArgs g{};
-            g.A = M; g.B = M; g.C = M;
-            g.shape = 1; g.i0 = k; g.j0 = k; g.mi = ntot - k; g.mj = 1; g.sym = aug_sym(col_sym_mode(), short_rows);
-            g.k0 = ka; g.k1 = k; g.accumulate = 1; g.nbatch = nb; g.ntiles = g.mi;
-            g.short_row0 = nt; g.short_rows = short_rows;
-            if (g.sym >= 2 && fuse_mode() && ntot - k - 1 > 0) {
-                // diagonal tile first, then its factor + inverse, then ONE pass over the column: update and panel
-                // product of every tile below the diagonal (the column makes one HBM round trip instead of two)
-                // GPSLC_DIAG_FOLD (measurement switch, default on): update + factorisation of the diagonal tile in ONE
-                // launch (diag_update_potrf_kernel) instead of tile_syrk_diag_kernel followed by diag_potrf_inv_la_kernel
-                static const int fold = diag_env("GPSLC_DIAG_FOLD", 1);
-                if (fold) {
-                    GemmArgs d = g;
-                    d.F = invref; d.info = info; d.info_base = info_base;
-                    launch_diag_update_potrf(d, g.sym == 3 && short_rows > 0, st);
-                } else {
-                    launch_sym_diag_tiles(g, st);
-                    launch_diag(M, k, inv, inv_bstride, info, info_base, nb, st);
-                }
-                g.fuse = 1; g.F = invref; g.fk = k;
-                gemm(c, g, s, prof_base);
-                fused = true;
-            } else {
-                gemm(c, g, s, prof_base);
-            }
-        }
-        if (!fused) launch_diag(M, k, inv, inv_bstride, info, info_base, nb, st);
-        if (!fused && ntot - k - 1 > 0) {   // panel: tile(i,k) = tile(i,k) * inv(L_kk)^T
-            // GPSLC_PANEL0_STRIP (measurement switch, default on, round 5): the first column of a panel has no column update — its
-            // panel product runs as the strip kernel's second phase alone (empty K range: the tile goes from HBM into the
-            // accumulators, the fragments of inv(L_kk) from L2 into registers, no LDS staging), same summation order as the
-            // general product it replaces (tile_gemm_nt_kernel<0, 0>)
-            static const int p0strip = diag_env("GPSLC_PANEL0_STRIP", 1);
-            GemmArgs g{};
-            g.A = M; g.C = M;
-            g.shape = 1; g.i0 = k + 1; g.j0 = k; g.mi = ntot - k - 1; g.mj = 1;
-            g.nbatch = nb; g.ntiles = g.mi;
-            g.short_row0 = nt; g.short_rows = short_rows;
-            if (p0strip && fuse_mode()) {
-                g.B = M; g.k0 = k; g.k1 = k; g.accumulate = 1; g.fuse = 1; g.F = invref; g.fk = k;
-            } else {
-                g.B = invref; g.k0 = k; g.k1 = k + 1; g.accumulate = 0;
-            }
+        const int below = ntot - k - 1;      // tiles of column k below the diagonal
+        GemmArgs g{};                        // the column's strip launch: update over the panel columns [ka, k) + panel product
+                                             // (F / fk are read by the fused launches only: strip_item's panel product)
+        g.A = M; g.B = M; g.C = M; g.F = invref; g.fk = k;
+        g.shape = 1; g.j0 = k; g.mj = 1; g.k1 = k; g.accumulate = 1; g.nbatch = nb;
+        g.short_row0 = nt; g.short_rows = short_rows;
+        if (k > ka && below > 0) {
+            // in-panel update: the diagonal tile first — update, factor and inverse in ONE launch — then ONE pass over the column:
+            // tile(i,k) -= sum_{kk in [ka,k)} tile(i,kk) tile(k,kk)^T and tile(i,k) *= inv(L_kk)^T for every tile below the
+            // diagonal (the column makes one HBM round trip instead of two)
+            g.i0 = k; g.mi = ntot - k; g.ntiles = g.mi; g.k0 = ka; g.sym = aug_sym(short_rows);
+            GemmArgs d = g;
+            d.info = info; d.info_base = info_base;
+            launch_diag_update_potrf(d, g.sym == 3, st);
+            g.fuse = 1;
             gemm(c, g, s, prof_base);
+        } else {
+            if (k > ka) {
+                // the last column of a matrix without augmented rows (ntot == nt: likelihood_distribution_impl) inside a panel:
+                // nothing lies below the diagonal, the column update holds the diagonal tile alone
+                g.i0 = k; g.mi = 1; g.ntiles = 1; g.k0 = ka; g.sym = 2;
+                gemm(c, g, s, prof_base);
+            }
+            launch_diag(M, k, inv, inv_bstride, info, info_base, nb, st);
+            if (below > 0) {
+                // the first column of a panel has no column update: its panel product tile(i,k) *= inv(L_kk)^T runs as the strip
+                // kernel's second phase alone (empty K range: the tile goes from HBM into the accumulators, the fragments of
+                // inv(L_kk) from L2 into registers, no LDS staging)
+                g.i0 = k + 1; g.mi = below; g.ntiles = below; g.k0 = k; g.sym = 0; g.fuse = 1;
+                gemm(c, g, s, prof_base);
+            }
         }
         // skip_aug_diag (single short augmented row, epilogue sums from the rows of R): the augmented diagonal tile is
         // never updated — after the last panel it would be the launch's only item
         const bool skip_gd = skip_aug_diag && short_rows > 0;
         if (k == kend - 1 && ntot - kend > (skip_gd ? 1 : 0)) {   // trailing update with the whole panel
-            GemmArgs g{};
-            g.A = M; g.B = M; g.C = M;
+            GemmArgs t{};
+            t.A = M; t.B = M; t.C = M;
             const int m = ntot - kend;
-            g.skip_gdiag = skip_gd ? 1 : 0;
-            g.shape = 0; g.i0 = kend; g.j0 = kend; g.mi = m; g.mj = m; g.sym = aug_sym(sym_mode(), short_rows);
-            g.k0 = ka; g.k1 = kend; g.accumulate = 1; g.nbatch = nb; g.ntiles = m * (m + 1) / 2;
-            g.order = tri_order(c, m);
-            g.short_row0 = nt; g.short_rows = short_rows;
-            gemm(c, g, s, prof_base);
+            t.skip_gdiag = skip_gd ? 1 : 0;
+            t.shape = 0; t.i0 = kend; t.j0 = kend; t.mi = m; t.mj = m; t.sym = aug_sym(short_rows);
+            t.k0 = ka; t.k1 = kend; t.accumulate = 1; t.nbatch = nb; t.ntiles = m * (m + 1) / 2;
+            t.order = tri_order(c, m);
+            t.short_row0 = nt; t.short_rows = short_rows;
+            gemm(c, t, s, prof_base);
         }
     }
 }
@@ -722,9 +672,7 @@ BatchPlan auto_batch(gpslc_ctx* c, int64_t S, int L, size_t per_sample_bytes, si
     // unit-B sub-batch (unit_bytes > 0): 128 units at N = 4096 (203 MB each, 26 GB).  Round 5, 256 units of 8 samples x 32 levels
     // on one box (profiles/r05_ab_experiments.md §3): 16 / 32 / 64 / 128 / 256 per sub-batch -> 322 / 349 / 364 / 372 / 373
     // units/s — the late columns of a factorisation have (nt - k) x sub-batch items for 512 workgroup slots; flat from 128 on
-    long long want_bb = std::max<long long>(1, std::min<long long>(128, 131072LL / ((long long)c->nt * c->nt)));
-    static const int bb_env = diag_env("GPSLC_UNITB_BATCH", 0);      // measurement switch: the sub-batch curve (profiles/r05)
-    if (bb_env > 0) want_bb = bb_env;
+    const long long want_bb = std::max<long long>(1, std::min<long long>(128, 131072LL / ((long long)c->nt * c->nt)));
     size_t free_b = 0, tot_b = 0;
     HC(hipMemGetInfo(&free_b, &tot_b));
     size_t have = 0;
@@ -879,8 +827,7 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     ra.n = n; ra.nt = nt; ra.naug = sh.naug; ra.L = (sh.with_sums && !io.lv.vec) ? sh.L : 0; ra.with_sums = sh.with_sums ? 1 : 0;
     ra.part = ch.part; ra.bsum = ch.bsum; ra.ksum = ch.ksum; ra.sumdelta = ch.sumdelta; ra.M = ch.M;
     ra.doT_base = io.lv.base;
-    static const int epi_rows_on = diag_env("GPSLC_EPI_ROWS", 1);      // measurement switch (A/B of the extra tile update)
-    const bool epi_rows = (sh.naug == 1) && epi_rows_on;     // single augmented tile row: the epilogue sums from the rows of R
+    const bool epi_rows = (sh.naug == 1);                    // single augmented tile row: the epilogue sums from the rows of R
     const int live = (sh.with_sums ? sh.R : 0) + 1;          // right-hand sides: Y and one c_l per level (and weight column)
     ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
     ra.G = 1; ra.bw = ch.bsum; ra.kw = ch.ksum;       // the plain call: one column of level sums, the Gram build's
@@ -948,43 +895,16 @@ void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
         if (o.out) { ia.meanITE = o.out; ia.si = o.si; ia.ss = o.ss; ia.sl = o.sl; launch_ite_mean(ia, nb, st); }
 }
 
-// unit B's W <- D L^-T for ub (sample, level) pairs, left-looking over tile columns: the panel product with inv(L_kk)^T is
-// applied by the same work item that finishes the column update (the tile makes one HBM round trip, as in the factorisation),
-// column 0 has no update and takes the panel product alone. Left-looking over the whole width (every column update in the strip
-// kernel).  GPSLC_W_PANEL = w > 0 (measurement build) blocks it like the factorisation instead — left-looking inside panels of w
-// tile columns, one right-looking update of everything to the right of a panel on the quadrant kernel.  Measured in round 4
-// (profiles/r04_ab_experiments.md §7): w = 4 / 8 / 16 -> 354 / 360 / 363.5 units/s against 363 unblocked: with a deep K loop the
-// strip kernel is as fast as the quadrant kernel's rectangle update plus the extra pass over W.  Not the default.
+// unit B's W <- D L^-T for ub (sample, level) pairs, left-looking over the whole width: one strip launch per tile column (column
+// update + panel product with inv(L_kk)^T in the same work item; column 0 takes the panel product alone), which measured level
+// with blocking it like the factorisation (profiles/r04_ab_experiments.md §7).
 void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const TRef& invref, int nt, int ub) {
-    static const int wpw_env = diag_env("GPSLC_W_PANEL", 0);
-    const int wpw = wpw_env <= 0 ? nt : wpw_env;
-    // fused up to a K depth of w_fuse_maxk tiles (measurement switch; +0.7 % fused at every depth)
-    static const int w_fuse_maxk = diag_env("GPSLC_FUSE_W_MAXK", 32);
     for (int k = 0; k < nt; ++k) {
-        const int ka = (k / wpw) * wpw;
-        const int kend = std::min(ka + wpw, nt);
         GemmArgs g{};
-        g.A = W; g.C = W;
+        g.A = W; g.B = Ls; g.C = W; g.F = invref; g.fk = k;
         g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1; g.nbatch = ub; g.ntiles = nt;
-        if (k - ka <= w_fuse_maxk && fuse_mode()) {      // k == ka: empty K range, the panel product alone (round 5)
-            g.B = Ls; g.k0 = ka; g.k1 = k; g.accumulate = 1;
-            g.fuse = 1; g.F = invref; g.fk = k;
-            gemm(c, g, s, 3);
-        } else {
-            if (k > ka) {
-                g.B = Ls; g.k0 = ka; g.k1 = k; g.accumulate = 1;
-                gemm(c, g, s, 3);
-            }
-            g.B = invref; g.k0 = k; g.k1 = k + 1; g.accumulate = 0;
-            gemm(c, g, s, 3);
-        }
-        if (k == kend - 1 && kend < nt) {      // the panel is solved: update everything to its right
-            GemmArgs t{};
-            t.A = W; t.B = Ls; t.C = W;
-            t.shape = 1; t.i0 = 0; t.j0 = kend; t.mi = nt; t.mj = nt - kend;
-            t.k0 = ka; t.k1 = kend; t.accumulate = 1; t.nbatch = ub; t.ntiles = t.mi * t.mj;
-            gemm(c, t, s, 3);
-        }
+        g.k0 = 0; g.k1 = k; g.accumulate = 1; g.fuse = 1;
+        gemm(c, g, s, 3);
     }
 }
 
@@ -1017,7 +937,7 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
             w_solve(c, *ch.s, W, Ls, invref, nt, ub);
             GemmArgs g{};            // CovITE (+ jitter) = Delta - W W^T, lower tiles
             g.A = W; g.B = W; g.C = Cm;
-            g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt; g.sym = sym_mode();
+            g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt; g.sym = 2;
             g.k0 = 0; g.k1 = nt; g.accumulate = 1; g.nbatch = ub; g.ntiles = (int)sh.nlow;
             g.order = tri_order(c, nt);
             gemm(c, g, *ch.s, 3);
@@ -1440,7 +1360,6 @@ int gpslc_create(gpslc_ctx** out, int device, int64_t n, int32_t nX, int32_t nU,
     if (!c) return GPSLC_ERR_NOMEM;
     c->device = device; c->n = n; c->nX = nX; c->nU = nU; c->flags = flags;
     c->nt = (int)((n + GP_TS - 1) / GP_TS);
-    c->order_block = diag_env("GPSLC_ORDER_BLOCK", c->order_block);
     int rc = guarded(c, [&]() {
         hipDeviceProp_t prop;
         HC(hipGetDeviceProperties(&prop, device));

@@ -46,9 +46,11 @@ inline int device_cus() {
     }
     return v;
 }
-// Measurement switches (tile visiting order, grid sizes, timing-only kernels, in-kernel stamps) exist only in the
-// -DGPSLC_DIAG build that tools/ and the profiling scripts use (libgpslc_hip_diag.so).  In the production library
-// the environment cannot change a result or a schedule: every switch reads as its default.
+// Measurement switches exist only in the -DGPSLC_DIAG build that tools/ and the profiling scripts use (libgpslc_hip_diag.so):
+// the timing-only kernel variants (GPSLC_GEMM_DIAG), the in-kernel stamps (GPSLC_GEMM_DBG, GPSLC_GEMM_DBG_FUSEK, GPSLC_GRAM_DBG,
+// GPSLC_TASK_DBG, GPSLC_SMALL_STAMPS) and the hand-off variants of the persistent launch (GPSLC_TASK_FENCE).  They are
+// instruments, not schedules: the A/B switches of rounds 1-7 are settled and gone ("Retired switches").  In the
+// production library the environment cannot change a result or a schedule: every switch reads as its default.
 inline int diag_env(const char* name, int dflt) {
 #ifdef GPSLC_DIAG
     const char* e = getenv(name);
@@ -89,10 +91,10 @@ struct GemmArgs {
     int ntiles;       // output tiles per batch element
     int short_row0;   // output tile rows >= short_row0 (augmented right-hand-side rows) carry only
     int short_rows;   // `short_rows` live rows: dead 16-row sub-tiles are skipped (0 = feature off)
-    int sym;          // A and B are the same tile matrix and C(t, t) needs only its lower triangle.  1: noted for
-                      // the flop accounting only; 2: launch_tile_gemm skips the full-size diagonal tiles, which
-                      // launch_syrk_diag (36 of 64 sub-tile products, 9 per wave) computes instead; 3: as 2, and
-                      // the augmented-row tiles (short_row0, j) of those columns ride with the diagonal items too
+    int sym;          // 0 / 2 / 3.  Nonzero: A and B are the same tile matrix and C(t, t) needs only its lower triangle.
+                      // 2: launch_tile_gemm skips the full-size diagonal tiles, which launch_syrk_diag (36 of 64 sub-tile
+                      // products, 9 per wave) or launch_diag_update_potrf computes instead; 3: as 2, and the
+                      // augmented-row tiles (short_row0, j) of those columns ride with the diagonal items too
     int fuse;         // 1 (accumulate launches of one tile column, mj == 1): each item also applies the panel
     TRef F;           //    product with tile (0, fk) of F = the inverted diagonal blocks (see k_tilegemm.hip)
     int fk;
@@ -100,11 +102,9 @@ struct GemmArgs {
                       // reads -R R^T (EpiArgs::from_rows)
     int* info;        // launch_diag_update_potrf: per-batch-element info words and the code base of tile row 0 (launch_diag's)
     int info_base;
-    int* queue;       // optional: 16 zero-initialised ints (per-XCD ticket counters [0..8), exit counters [8..16))
-                      // owned by the launching stream; the kernel leaves them zeroed again.  null = static stride
+    int* queue;       // launch_tile_gemm: 16 zero-initialised ints (per-XCD ticket counters [0..8), exit counters [8..16))
+                      // owned by the launching stream; the kernel leaves them zeroed again
     const unsigned short* order;  // optional (ii, jj) pairs: output-tile visiting order (L2-blocked), or null
-    int nt_c;                     // C tiles are loaded / stored with the non-temporal hint (streamed once per launch:
-                                  // they should not displace the operand slabs the co-resident workgroups share in L2)
     int diag_skip;                // DIAGNOSTIC ONLY (GPSLC_GEMM_DIAG): 1 = skip in-loop global loads, 2 = also LDS writes
     unsigned long long* dbg;      // diagnostic builds only: per-workgroup s_memtime stamps, or null
 };

@@ -123,15 +123,14 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
     const int nslab = (g.k1 - g.k0) * (GP_TS / KS);
 
     // Work distribution inside the XCD's run: the first item of a workgroup is `local`; the following ones come
-    // from a per-XCD ticket counter (GemmArgs::queue) when the launch provides one — items differ in cost
-    // (augmented-row tiles, skipped diagonal tiles), a static stride leaves the slowest workgroup ~5 items
-    // behind the mean — or from the static stride otherwise.  The ticket for the NEXT item is requested at the
-    // start of the current one, so its latency hides behind the tile.
+    // from a per-XCD ticket counter (GemmArgs::queue) — items differ in cost (augmented-row tiles, skipped
+    // diagonal tiles), a static stride leaves the slowest workgroup ~5 items behind the mean.  The ticket for
+    // the NEXT item is requested at the start of the current one, so its latency hides behind the tile.
     __shared__ int s_ticket;
     long long it = local;
     while (it < xc) {
         int ticket = 0;
-        if (g.queue && tid == 0) ticket = atomicAdd(&g.queue[xcd], 1);
+        if (tid == 0) ticket = atomicAdd(&g.queue[xcd], 1);
         do {
         const long long item = x0 + it;
         const int b = (int)(item / g.ntiles);
@@ -141,8 +140,8 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
         else if (g.shape == 0) tri_decode(t, ii, jj);
         else { ii = t / g.mj; jj = t - ii * g.mj; }
         const int ti = g.i0 + ii, tj = g.j0 + jj;
-        // sym == 2: the full-size diagonal tiles of this launch belong to tile_syrk_diag_kernel
-        if (g.sym >= 2 && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) break;
+        // symmetric launch: its full-size diagonal tiles belong to tile_syrk_diag_kernel
+        if (g.sym && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) break;
         // sym == 3: the augmented-row tiles of the columns that have a full-size diagonal tile ride with it
         if (g.sym == 3 && g.short_rows > 0 && ti >= g.short_row0 && tj < g.short_row0) break;
         if (g.skip_gdiag && ti == tj && g.short_rows > 0 && ti >= g.short_row0) break;   // -R R^T is not needed (EpiArgs::from_rows)
@@ -171,23 +170,13 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
         d4 acc[4][4];
         if (ACC) {
             const double* __restrict__ Cl = Ct + (ccol * GP_TS + crow);
-            if (g.nt_c) {
 #pragma unroll
-                for (int n = 0; n < 4; ++n)
+            for (int n = 0; n < 4; ++n)
 #pragma unroll
-                    for (int v = 0; v < 4; ++v)
+                for (int v = 0; v < 4; ++v)
 #pragma unroll
-                        for (int m = 0; m < 4; ++m)
-                            acc[m][n][v] = __builtin_nontemporal_load(Cl + (16 * n + 4 * v) * GP_TS + 16 * m);
-            } else {
-#pragma unroll
-                for (int n = 0; n < 4; ++n)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-#pragma unroll
-                        for (int m = 0; m < 4; ++m)
-                            acc[m][n][v] = Cl[(16 * n + 4 * v) * GP_TS + 16 * m];
-            }
+                    for (int m = 0; m < 4; ++m)
+                        acc[m][n][v] = Cl[(16 * n + 4 * v) * GP_TS + 16 * m];
         } else {
 #pragma unroll
             for (int m = 0; m < 4; ++m)
@@ -348,26 +337,16 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
                     }
                 }
         } else {
-        int soff = ccol * GP_TS + crow;
-        asm volatile("" : "+v"(soff));
-        double* __restrict__ Cs = Ct + soff;
-        if (g.nt_c) {
+            int soff = ccol * GP_TS + crow;
+            asm volatile("" : "+v"(soff));
+            double* __restrict__ Cs = Ct + soff;
 #pragma unroll
             for (int n = 0; n < 4; ++n)
 #pragma unroll
                 for (int v = 0; v < 4; ++v)
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
-                        __builtin_nontemporal_store(acc[m][n][v], Cs + (16 * n + 4 * v) * GP_TS + 16 * m);
-        } else {
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-                    Cs[(16 * n + 4 * v) * GP_TS + 16 * m] = acc[m][n][v];
-        }
+                        Cs[(16 * n + 4 * v) * GP_TS + 16 * m] = acc[m][n][v];
         }
         }
         if (GP_DBG_ON(g)) {   // diagnostic stamps: go to a buffer nothing else reads
@@ -383,17 +362,13 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
             }
         }
         } while (0);
-        if (g.queue) {
-            if (tid == 0) s_ticket = ticket;
-            __syncthreads();
-            it = (long long)gx + s_ticket;
-            __syncthreads();
-        } else {
-            it += gx;
-        }
+        if (tid == 0) s_ticket = ticket;
+        __syncthreads();
+        it = (long long)gx + s_ticket;
+        __syncthreads();
     }
     // the last workgroup of the XCD to leave re-arms the counters for the next launch on this stream
-    if (g.queue && tid == 0) {
+    if (tid == 0) {
         __threadfence();
         if (atomicAdd(&g.queue[8 + xcd], 1) == gx - 1) {
             g.queue[xcd] = 0;
@@ -698,7 +673,7 @@ __global__ __launch_bounds__(256, 2) void tile_fused_strip_kernel(GemmArgs g) {
     long long it = local;
     while (it < xc) {
         int ticket = 0;
-        if (g.queue && tid == 0) ticket = atomicAdd(&g.queue[xcd], 1);
+        if (tid == 0) ticket = atomicAdd(&g.queue[xcd], 1);
         do {
         const long long item = x0 + it;
         const int b = (int)(item / g.ntiles);
@@ -707,21 +682,17 @@ __global__ __launch_bounds__(256, 2) void tile_fused_strip_kernel(GemmArgs g) {
         if (g.shape == 0) tri_decode(t, ii, jj);
         else { ii = t / g.mj; jj = t - ii * g.mj; }
         const int ti = g.i0 + ii, tj = g.j0 + jj;
-        if (g.sym >= 2 && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) break;   // tile_syrk_diag_kernel's
+        if (g.sym && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) break;   // the diagonal-tile kernel's
         // sym == 3: the augmented tile was already updated (it rode with the diagonal item); panel product only
         const bool no_update = g.sym == 3 && g.short_rows > 0 && ti >= g.short_row0 && tj < g.short_row0;
         strip_item<WD>(g, b, ti, tj, no_update, nslab, lB, tid, lane, wave, li, lg, frow_b, loff, item);
         } while (0);
-        if (g.queue) {
-            if (tid == 0) s_ticket = ticket;
-            __syncthreads();
-            it = (long long)gx + s_ticket;
-            __syncthreads();
-        } else {
-            it += gx;
-        }
+        if (tid == 0) s_ticket = ticket;
+        __syncthreads();
+        it = (long long)gx + s_ticket;
+        __syncthreads();
     }
-    if (g.queue && tid == 0) {
+    if (tid == 0) {
         __threadfence();
         if (atomicAdd(&g.queue[8 + xcd], 1) == gx - 1) {
             g.queue[xcd] = 0;
@@ -1128,10 +1099,7 @@ static void launch_potrf_tasks_t(const PotrfTaskArgs& a, unsigned grid, hipStrea
 // row of the task list, strip(nt, k) with its own column update over the live rows, as in the per-column launches
 void launch_potrf_tasks(const PotrfTaskArgs& a, long long ntasks, int mt, hipStream_t st) {
     if (ntasks <= 0) return;
-    int slots = 2 * device_cus();
-#ifdef GPSLC_DIAG
-    slots = diag_env("GPSLC_GEMM_SLOTS", slots);
-#endif
+    const int slots = 2 * device_cus();
     const unsigned grid = (unsigned)(ntasks < slots ? ntasks : slots);
 #ifdef GPSLC_DIAG
     if (a.fence_mode & 2) {      // measurement build, GPSLC_TASK_FENCE bit 1: plain / nt payload stores + an agent-scope release fence
@@ -1313,10 +1281,7 @@ static void launch_syrk_diag_t(const GemmArgs& g, unsigned grid, hipStream_t st)
 // carry_aug: the items also update the augmented-row tiles (short_row0, i0 + t) (live rows g.short_rows).
 void launch_syrk_diag(const GemmArgs& g, int carry_aug, hipStream_t st) {
     if (g.mi <= 0 || g.nbatch <= 0 || g.k1 <= g.k0) return;
-    int slots = 2 * device_cus();
-#ifdef GPSLC_DIAG
-    slots = diag_env("GPSLC_GEMM_SLOTS", slots);
-#endif
+    const int slots = 2 * device_cus();
     const long long Wk = (long long)g.mi * g.nbatch;
     const unsigned grid = (unsigned)(Wk < slots ? Wk : slots);
     const int mt = carry_aug ? (g.short_rows + 15) / 16 : 0;   // callers pass carry_aug only for mt <= 2
@@ -1334,13 +1299,8 @@ static void launch_one(const GemmArgs& g, unsigned grid, hipStream_t st) {
 
 void launch_tile_gemm(const GemmArgs& g, hipStream_t st) {
     if (g.ntiles <= 0 || g.nbatch <= 0) return;
-    int slots = 2 * device_cus();   // 2 workgroups per CU (227 VGPRs, 72 KiB LDS each)
+    const int slots = 2 * device_cus();   // 2 workgroups per CU (227 VGPRs, 72 KiB LDS each)
     const long long W = (long long)g.ntiles * g.nbatch;
-#ifdef GPSLC_DIAG
-    slots = diag_env("GPSLC_GEMM_SLOTS", slots);
-    const int panel_slots = diag_env("GPSLC_PANEL_SLOTS", 0);
-    if (!g.accumulate && panel_slots > 0) slots = panel_slots;
-#endif
     const unsigned grid = (unsigned)(W < slots ? W : slots);
 #ifdef GPSLC_DIAG
     if (g.diag_skip == 1) {        // timing-only diagnostics (GPSLC_GEMM_DIAG), separate instantiations
