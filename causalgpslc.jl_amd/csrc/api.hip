@@ -780,6 +780,18 @@ VecArgs vec_args(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     return va;
 }
 
+// One draw per unit from N(0, L L^T): unit b streams the factor Lc of batch element b (batch stride 0: ONE factor for all) and
+// multiplies it with column s0 + b of the normals z (n x S); `zero` is n x S zeros (the draw kernel's mean), zt the operand
+// image workspace, out n x S.
+DrawArgs zero_mean_draw(TRef Lc, int n, int nt, long long s0, long long S, const double* zero, const double* z, double* zt,
+                        double* out) {
+    DrawArgs dr{};
+    dr.Lc = Lc; dr.n = n; dr.nt = nt; dr.s0 = s0; dr.S = S; dr.l = 0; dr.lc = 1; dr.L = 1; dr.spp = 1;
+    dr.mean = zero; dr.z = z; dr.zt = zt; dr.out = out;
+    dr.obase = (long long)n * s0; dr.osb = n; dr.osl = 0; dr.osi = 1; dr.osd = n;
+    return dr;
+}
+
 // unit A of a chunk: Gram build, right-hand sides, vector sums, factorisation, epilogue and node draw.  Returns whether the
 // factorisation delivered the back-substitution alpha.
 bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
@@ -859,11 +871,7 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
         // one draw from N(0, A_s) per parameter set with the caller's normals: L_s z_s on the factor just computed — Gen's
         // mvnormal(zeros(n), cov) of an elliptical slice's auxiliary vector (src/inference.jl:225-232) and of the :logitT prior
         // draw (src/model_likelihood.jl:25-33) — the predictive-draw kernel streaming L once
-        DrawArgs dr{};
-        dr.Lc = ch.M; dr.n = n; dr.nt = nt; dr.s0 = s0; dr.S = io.post.S; dr.l = 0; dr.lc = 1; dr.L = 1; dr.spp = 1;
-        dr.mean = io.nzero; dr.z = io.nz; dr.zt = ch.znode; dr.out = io.ndraw;
-        dr.obase = (long long)n * s0; dr.osb = n; dr.osl = 0; dr.osi = 1; dr.osd = n;
-        launch_draws(dr, nb, st);
+        launch_draws(zero_mean_draw(ch.M, n, nt, s0, io.post.S, io.nzero, io.nz, ch.znode, io.ndraw), nb, st);
     }
     return back_done;
 }
@@ -1110,6 +1118,33 @@ struct HostNode {            // host view of one node (gpslc_node with plain poi
     double covscale;
 };
 
+// The three kinds of node view.  An RBF node: K = scale exp(-sum_f ((x_if - x_jf) / ls_f)^2) + noise I over nF feature columns
+HostNode rbf_node(int nF, const double* F, const double* ls, double scale, double noise, const double* target) {
+    HostNode h{};
+    h.nF = nF; h.F[0] = nF ? F : nullptr; h.nFpart[0] = nF; h.ls[0] = nF ? ls : nullptr;
+    h.scale = scale; h.noise = noise; h.target = target;
+    return h;
+}
+// the :Y node: the same over the feature parts U | X | T (T one column with the scalar lengthscale tyLS)
+HostNode y_node(int nU, const double* U, const double* uyLS, int nX, const double* X, const double* xyLS, const double* T,
+                double tyLS, double scale, double noise, const double* target) {
+    HostNode h = rbf_node(nU, U, uyLS, scale, noise, target);
+    h.nF = nU + nX + 1;
+    h.F[1] = nX ? X : nullptr; h.nFpart[1] = nX; h.ls[1] = nX ? xyLS : nullptr;
+    h.col = T; h.ls_col = tyLS;
+    return h;
+}
+// a dense-covariance node: K = covscale dev_cov (n x n, device)
+HostNode dense_node(const double* dev_cov, double covscale, const double* target) {
+    HostNode h{};
+    h.dev_cov = dev_cov; h.covscale = covscale; h.target = target;
+    return h;
+}
+
+// log N(x; 0, K) of an n-vector from log det K and the quadratic form x' K^-1 x
+constexpr double kLog2Pi = 1.8378770664093454835606594728112;
+inline double gauss_logpdf(size_t n, double logdet, double quad) { return -0.5 * ((double)n * kLog2Pi + logdet + quad); }
+
 void pin_reserve(gpslc_ctx* c, size_t bytes) {
     if (c->pin_bytes >= bytes) return;
     if (c->pin) { HC(hipDeviceSynchronize()); HC(hipHostFree(c->pin)); c->pin = nullptr; c->pin_bytes = 0; }
@@ -1136,77 +1171,37 @@ bool fast_path_ok(const gpslc_ctx* c, int nF_max, int64_t count) {
 // threads: 1.1 GB in 77 ms instead of 110 (a huge-page hint on the destination changed nothing: NumPy's large arrays
 // already carry it).  Small results keep the plain call; a caller who hands over a PINNED buffer gets the DMA rate.
 constexpr size_t kBounceBytes = size_t(64) << 20;
-void copy_out_large(gpslc_ctx* c, void* dst, const void* src_dev, size_t bytes) {
+// The source is `rows` runs of row_bytes, CONTIGUOUS ON THE DEVICE, that land `dpitch` bytes apart in the caller's array: a
+// shard's block of an (n x S x L) array of a level sweep — level l of the shard is one run of n S_r doubles at n (s0 + S l) of
+// the caller's array (gpslc_predict_multi).  The device side is DMA'd chunk by chunk whatever the rows; each host thread
+// scatters its slice of a chunk to the rows it covers.  rows == 1 or dpitch == row_bytes is one run: one memcpy per slice.
+void copy_out_rows(gpslc_ctx* c, void* dst, size_t dpitch, const void* src_dev, size_t row_bytes, size_t rows) {
+    if (rows == 0 || row_bytes == 0) return;
+    const size_t bytes = row_bytes * rows;
+    const bool strided = rows > 1 && dpitch != row_bytes;
+    const size_t run = strided ? row_bytes : bytes;
+    auto direct = [&]() {
+        if (strided) HC(hipMemcpy2D(dst, dpitch, src_dev, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost));
+        else HC(hipMemcpy(dst, src_dev, bytes, hipMemcpyDeviceToHost));
+    };
     bool plain = bytes < 2 * kBounceBytes;
     if (!plain) {                                     // a pinned (registered) destination takes the DMA directly
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, dst) == hipSuccess) plain = at.type == hipMemoryTypeHost;
         else (void)hipGetLastError();                 // ordinary pageable memory: not known to the runtime
     }
-    if (plain) { HC(hipMemcpy(dst, src_dev, bytes, hipMemcpyDeviceToHost)); return; }
+    if (plain) { direct(); return; }
     ensure_streams(c);
     for (int i = 0; i < 2; ++i)
         if (!c->bounce[i]) {
             void* p = nullptr;
             if (hipHostMalloc(&p, kBounceBytes, hipHostMallocDefault) != hipSuccess) {
                 (void)hipGetLastError();
-                HC(hipMemcpy(dst, src_dev, bytes, hipMemcpyDeviceToHost));      // no pinned memory to be had: the plain way
+                direct();                             // no pinned memory to be had: the plain way
                 return;
             }
             c->bounce[i] = static_cast<char*>(p);
         }
-    hipStream_t st = c->slots[0].st;
-    const size_t nchunk = (bytes + kBounceBytes - 1) / kBounceBytes;
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned nthr = std::min(8u, hw);
-    auto chunk_bytes = [&](size_t k) { return std::min(kBounceBytes, bytes - k * kBounceBytes); };
-    HC(hipMemcpyAsync(c->bounce[0], src_dev, chunk_bytes(0), hipMemcpyDeviceToHost, st));
-    for (size_t k = 0; k < nchunk; ++k) {
-        HC(hipStreamSynchronize(st));                                           // chunk k has landed in bounce[k & 1]
-        if (k + 1 < nchunk)
-            HC(hipMemcpyAsync(c->bounce[(k + 1) & 1], static_cast<const char*>(src_dev) + (k + 1) * kBounceBytes,
-                              chunk_bytes(k + 1), hipMemcpyDeviceToHost, st));
-        const size_t cb = chunk_bytes(k);
-        char* d = static_cast<char*>(dst) + k * kBounceBytes;
-        const char* b = c->bounce[k & 1];
-        const size_t per = ((cb + nthr - 1) / nthr + 4095) & ~size_t(4095);
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < nthr; ++t) {
-            const size_t o = (size_t)t * per;
-            if (o >= cb) break;
-            const size_t len = std::min(per, cb - o);
-            try { pool.emplace_back([=]() { memcpy(d + o, b + o, len); }); }
-            catch (...) { memcpy(d + o, b + o, len); }        // no thread to be had: copy this slice here
-        }
-        memcpy(d, b, std::min(per, cb));
-        for (auto& th : pool) th.join();
-    }
-}
-
-// The same hand-over for a result whose rows are CONTIGUOUS ON THE DEVICE (rows x row_bytes) and `dpitch` bytes apart in the
-// caller's array: a shard's block of an (n x S x L) array of a level sweep — level l of the shard is one run of n S_r doubles
-// at n (s0 + S l) of the caller's array (gpslc_predict_multi).  The device side is DMA'd in 64 MiB chunks as above; the host
-// threads scatter a chunk to its rows.  Small results: one hipMemcpy2D.
-void copy_out_rows(gpslc_ctx* c, void* dst, size_t dpitch, const void* src_dev, size_t row_bytes, size_t rows) {
-    if (rows == 0 || row_bytes == 0) return;
-    if (rows == 1 || dpitch == row_bytes) { copy_out_large(c, dst, src_dev, row_bytes * rows); return; }
-    const size_t bytes = row_bytes * rows;
-    bool plain = bytes < 2 * kBounceBytes;
-    if (!plain) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, dst) == hipSuccess) plain = at.type == hipMemoryTypeHost;
-        else (void)hipGetLastError();
-    }
-    if (!plain) {
-        ensure_streams(c);
-        for (int i = 0; i < 2 && !plain; ++i)
-            if (!c->bounce[i]) {
-                void* p = nullptr;
-                if (hipHostMalloc(&p, kBounceBytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); plain = true; }
-                else c->bounce[i] = static_cast<char*>(p);
-            }
-    }
-    if (plain) { HC(hipMemcpy2D(dst, dpitch, src_dev, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost)); return; }
     hipStream_t st = c->slots[0].st;
     const size_t nchunk = (bytes + kBounceBytes - 1) / kBounceBytes;
     const unsigned nthr = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
@@ -1214,15 +1209,15 @@ void copy_out_rows(gpslc_ctx* c, void* dst, size_t dpitch, const void* src_dev, 
     // bytes [o, o + len) of the device block -> their rows of the caller's array
     auto scatter = [=](const char* b, size_t o, size_t len) {
         while (len > 0) {
-            const size_t row = o / row_bytes, within = o - row * row_bytes;
-            const size_t m = std::min(len, row_bytes - within);
+            const size_t row = o / run, within = o - row * run;
+            const size_t m = std::min(len, run - within);
             memcpy(static_cast<char*>(dst) + row * dpitch + within, b, m);
             b += m; o += m; len -= m;
         }
     };
     HC(hipMemcpyAsync(c->bounce[0], src_dev, chunk_bytes(0), hipMemcpyDeviceToHost, st));
     for (size_t k = 0; k < nchunk; ++k) {
-        HC(hipStreamSynchronize(st));
+        HC(hipStreamSynchronize(st));                                           // chunk k has landed in bounce[k & 1]
         if (k + 1 < nchunk)
             HC(hipMemcpyAsync(c->bounce[(k + 1) & 1], static_cast<const char*>(src_dev) + (k + 1) * kBounceBytes,
                               chunk_bytes(k + 1), hipMemcpyDeviceToHost, st));
@@ -1235,15 +1230,16 @@ void copy_out_rows(gpslc_ctx* c, void* dst, size_t dpitch, const void* src_dev, 
             if (o >= cb) break;
             const size_t len = std::min(per, cb - o);
             try { pool.emplace_back([=]() { scatter(b + o, o0 + o, len); }); }
-            catch (...) { scatter(b + o, o0 + o, len); }
+            catch (...) { scatter(b + o, o0 + o, len); }        // no thread to be had: copy this slice here
         }
         scatter(b, o0, std::min(per, cb));
         for (auto& th : pool) th.join();
     }
 }
+void copy_out_large(gpslc_ctx* c, void* dst, const void* src_dev, size_t bytes) { copy_out_rows(c, dst, bytes, src_dev, bytes, 1); }
 
 // scores `count` nodes in ONE launch; logdet/quad/info per node come back through the pinned buffer.
-// Returns the first failing pivot (0 = all fine); logpdf[i] = -(n log 2pi + logdet_i + quad_i) / 2.
+// Returns the first failing pivot (0 = all fine); logpdf[i] = gauss_logpdf(n, logdet_i, quad_i).
 // draw_out (optional, host, n x count): node i also returns chol(K_i) * target_i.
 int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* logpdf, double* draw_out = nullptr) {
     ensure_streams(c);
@@ -1328,14 +1324,13 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
     }
 #endif
     if (draw_out) memcpy(draw_out, c->pin + off_draw, (size_t)count * n * sizeof(double));
-    const double l2pi = 1.8378770664093454835606594728112;
     int first = 0;
     c->last_info.resize((size_t)count);
     for (int i = 0; i < count; ++i) {
         const int info = (int)hout[4 * i + 2];
         c->last_info[i] = info;
         if (info != 0 && first == 0) first = info;
-        logpdf[i] = -0.5 * ((double)n * l2pi + hout[4 * i] + hout[4 * i + 1]);
+        logpdf[i] = gauss_logpdf(n, hout[4 * i], hout[4 * i + 1]);
     }
     return first;
 }
@@ -1497,22 +1492,21 @@ int gpslc_rbf_log_dev(gpslc_ctx* c, const double* X1, const double* X2, int64_t 
     });
 }
 
+// the host forms: upload, run what the _dev form runs, copy out
+
 int gpslc_rbf_log(gpslc_ctx* c, const double* X1, const double* X2, int64_t n, int32_t d, const double* ls,
                   int32_t ls_len, double* out) {
     int rc = rbf_log_check(c, X1, X2, n, d, ls, ls_len, out);
     if (rc) return rc;
     return guarded(c, [&]() {
-        ensure_streams(c);
         c->io.reset();
         double* dA = up(c, X1, (size_t)n * d);
         double* dB = up(c, X2, (size_t)n * d);
         double* dl = up(c, ls, (size_t)ls_len);
         double* o = c->io.take<double>((size_t)n * n);
-        launch_rbf_log(dA, dB, n, d, dl, ls_len, o, c->slots[0].st);
-        HC(hipGetLastError());
-        HC(hipStreamSynchronize(c->slots[0].st));
-        copy_out_large(c, out, o, sizeof(double) * (size_t)n * n);
-        return GPSLC_OK;
+        const int st = gpslc_rbf_log_dev(c, dA, dB, n, d, dl, ls_len, o);
+        if (st == GPSLC_OK) copy_out_large(c, out, o, sizeof(double) * (size_t)n * n);
+        return st;
     });
 }
 
@@ -1536,15 +1530,12 @@ int gpslc_process_cov(gpslc_ctx* c, const double* logcov, int64_t n, double scal
     if (n < 1) return bad_arg(c, 3, "n < 1");
     if (!out) return bad_arg(c, 6, "out is NULL");
     return guarded(c, [&]() {
-        ensure_streams(c);
         c->io.reset();
         double* dA = up(c, logcov, (size_t)n * n);
         double* o = c->io.take<double>((size_t)n * n);
-        launch_process_cov(dA, n, scale, noise, o, c->slots[0].st);
-        HC(hipGetLastError());
-        HC(hipStreamSynchronize(c->slots[0].st));
-        copy_out_large(c, out, o, sizeof(double) * (size_t)n * n);
-        return GPSLC_OK;
+        const int st = gpslc_process_cov_dev(c, dA, n, scale, noise, o);
+        if (st == GPSLC_OK) copy_out_large(c, out, o, sizeof(double) * (size_t)n * n);
+        return st;
     });
 }
 
@@ -1906,66 +1897,32 @@ int gpslc_ite_distributions_contrast(gpslc_ctx* c, int64_t S, const double* U, c
     return rc ? rc : ite_distributions_host(c, rq);
 }
 
-// logpdf[s] = -(n log 2pi + logdet_s + quad_s) / 2 from the device-side epilogue values
-static void finish_logpdf(gpslc_ctx* c, int64_t S, const double* d_logdet, const double* d_quad, double* logpdf) {
-    std::vector<double> ld(S), q(S);
-    HC(hipMemcpy(ld.data(), d_logdet, sizeof(double) * S, hipMemcpyDeviceToHost));
-    HC(hipMemcpy(q.data(), d_quad, sizeof(double) * S, hipMemcpyDeviceToHost));
-    const double l2pi = 1.8378770664093454835606594728112;
-    for (int64_t s = 0; s < S; ++s) logpdf[s] = -0.5 * ((double)c->n * l2pi + ld[s] + q[s]);
-}
+}  // extern "C"
 
-int gpslc_y_logpdf(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
-                   const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale,
-                   const double* yNoise, double* logpdf) {
-    const PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 0, nullptr);
-    int rc = validate(c, rq, kSamplesArgs);
-    if (rc) return rc;
-    if (!logpdf) return bad_arg(c, 11, "logpdf is NULL");
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    if (fast_path_ok(c, c->nU + c->nX + 1, S)) {
-        // small n: every parameter set is one workgroup of ONE launch (k_small.hip); T enters as a feature column
-        return guarded(c, [&]() {
-            const size_t n = (size_t)c->n;
-            std::vector<HostNode> hn((size_t)S);
-            for (int64_t s = 0; s < S; ++s) {
-                HostNode& h = hn[s];
-                h = HostNode{};
-                h.nF = c->nU + c->nX + 1;
-                h.F[0] = c->nU ? U + s * n * c->nU : nullptr; h.nFpart[0] = c->nU; h.ls[0] = c->nU ? uyLS + s * c->nU : nullptr;
-                h.F[1] = c->nX ? (X_or_null ? X_or_null : c->hX.data()) : nullptr; h.nFpart[1] = c->nX;
-                h.ls[1] = c->nX ? xyLS + s * c->nX : nullptr;
-                h.col = c->hT.data(); h.ls_col = tyLS[s];
-                h.scale = yScale[s]; h.noise = yNoise[s];
-                h.target = Y_or_null ? Y_or_null : c->hY.data();
-            }
-            return small_nodes_logpdf(c, (int)S, hn.data(), logpdf);
-        });
-    }
-    return guarded(c, [&]() {
-        const size_t n = (size_t)c->n;
-        c->io.reset();
-        const double* dX = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
-        const double* dYo = Y_or_null ? up(c, Y_or_null, n) : nullptr;
-        const double zero = 0.0;
-        const double* ddo = up(c, &zero, 1);
-        double* old = c->io.take<double>((size_t)S);
-        double* oq = c->io.take<double>((size_t)S);
-        PredictIO io;
-        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S); io.X = dX;
-        if (dYo) { io.Y = dYo; io.y_sstride = 0; }    // the value being scored (Gen passes it to logpdf), else the ctx's Y
-        io.lv.L = 0; io.lv.doT = ddo; io.logdet = old; io.quad = oq; io.info = c->io.take<int>((size_t)S);
-        run_predict(c, io);
-        finish_logpdf(c, S, old, oq, logpdf);
-        return first_info(c);
-    });
+// ---- node scores: the six entry points of the chain's inner loop and what they share --------------------------------
+namespace {
+
+// The tiled score of the S parameter sets of `io`: the caller has filled in the samples, the features, the right-hand side
+// (the value being scored) and, for gpslc_nodes_draw, the node draw.  This adds "no level, score only", runs the prediction
+// pass and turns the epilogue's logdet / quad into log-densities.  Returns the first failing pivot.
+int tiled_score(gpslc_ctx* c, PredictIO& io, double* logpdf) {
+    const size_t S = (size_t)io.post.S;
+    const double zero = 0.0;
+    io.lv.L = 0; io.lv.doT = up(c, &zero, 1);
+    io.logdet = c->io.take<double>(S); io.quad = c->io.take<double>(S); io.info = c->io.take<int>(S);
+    run_predict(c, io);
+    std::vector<double> ld(S), q(S);
+    HC(hipMemcpy(ld.data(), io.logdet, sizeof(double) * S, hipMemcpyDeviceToHost));
+    HC(hipMemcpy(q.data(), io.quad, sizeof(double) * S, hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < S; ++s) logpdf[s] = gauss_logpdf((size_t)c->n, ld[s], q[s]);
+    return first_info(c);
 }
 
 // general (tiled, multi-launch) path of gpslc_gp_logpdf; arguments already validated
 // draws_or_null (host, n x S; needs t_shared == 0): also chol(K_s) target_s — the targets are then standard normals
-static int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_t f_shared, const double* ls,
-                             const double* scale, const double* noise, const double* target, int32_t t_shared,
-                             double* logpdf, double* draws_or_null = nullptr) {
+int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_t f_shared, const double* ls,
+                      const double* scale, const double* noise, const double* target, int32_t t_shared, double* logpdf,
+                      double* draws_or_null = nullptr) {
     const size_t n = (size_t)c->n;
     c->io.reset();
     const double* dF = nF ? up(c, F, n * nF * (f_shared ? 1 : S)) : nullptr;
@@ -1975,17 +1932,12 @@ static int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* 
     const double* dtg = up(c, target, n * (t_shared ? 1 : S));
     std::vector<double> inf(S, INFINITY);        // tyLS = inf switches the treatment term off: e_ij = exp(-0) = 1
     const double* dty = up(c, inf.data(), S);
-    const double zero = 0.0;
-    const double* ddo = up(c, &zero, 1);
-    double* old = c->io.take<double>((size_t)S);
-    double* oq = c->io.take<double>((size_t)S);
     PredictIO io;
     io.post.S = S;
     io.post.p = SampleParams{dF, dls, nullptr, dty, dsc, dno, f_shared ? 0 : (long long)n * nF};
     io.p_shared_u = f_shared != 0;
     io.X = nullptr; io.nU = nF; io.nX = 0;
     io.Y = dtg; io.y_sstride = t_shared ? 0 : (long long)n;
-    io.lv.L = 0; io.lv.doT = ddo; io.logdet = old; io.quad = oq; io.info = c->io.take<int>((size_t)S);
     double* ddraw = nullptr;
     if (draws_or_null) {
         ensure_streams(c);
@@ -1995,44 +1947,14 @@ static int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* 
         HC(hipStreamSynchronize(c->slots[0].st));
         io.nz = dtg; io.nzero = zero_mean; io.ndraw = ddraw;
     }
-    run_predict(c, io);
-    if (logpdf) finish_logpdf(c, S, old, oq, logpdf);
+    const int st = tiled_score(c, io, logpdf);
     if (draws_or_null) HC(hipMemcpy(draws_or_null, ddraw, n * (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
-    return first_info(c);
-}
-
-int gpslc_gp_logpdf(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_t f_shared, const double* ls,
-                    const double* scale, const double* noise, const double* target, int32_t t_shared,
-                    double* logpdf) {
-    if (!c) return -1;
-    if (S < 0) return bad_arg(c, 2, "S < 0");
-    if (nF < 0 || nF > 32) return bad_arg(c, 3, "nF must be in 0..32");
-    if (nF > 0 && (!F || !ls)) return bad_arg(c, 4, "F / ls must not be NULL when nF > 0");
-    if (S > 0 && (!scale || !noise)) return bad_arg(c, 7, "scale / noise must not be NULL");
-    if (S > 0 && !target) return bad_arg(c, 9, "target is NULL");
-    if (!logpdf) return bad_arg(c, 11, "logpdf is NULL");
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return guarded(c, [&]() {
-        const size_t n = (size_t)c->n;
-        if (fast_path_ok(c, nF, S)) {
-            std::vector<HostNode> hn((size_t)S);
-            for (int64_t s = 0; s < S; ++s) {
-                HostNode& h = hn[s];
-                h = HostNode{};
-                h.nF = nF;
-                h.F[0] = nF ? F + (f_shared ? 0 : s * n * nF) : nullptr; h.nFpart[0] = nF; h.ls[0] = nF ? ls + s * nF : nullptr;
-                h.scale = scale[s]; h.noise = noise[s];
-                h.target = target + (t_shared ? 0 : s * n);
-            }
-            return small_nodes_logpdf(c, (int)S, hn.data(), logpdf);
-        }
-        return gp_logpdf_general(c, S, nF, F, f_shared, ls, scale, noise, target, t_shared, logpdf);
-    });
+    return st;
 }
 
 // ONE batched pass of the general tiled path over all nodes of a call (S = count parameter sets with per-set feature blocks
 // and per-set targets); draws_or_null: also chol(K_i) target_i per node (gpslc_nodes_draw)
-static int nodes_general(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, int nF_max, double* logpdf, double* draws_or_null) {
+int nodes_general(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, int nF_max, double* logpdf, double* draws_or_null) {
     // Nodes with fewer than nF_max feature columns are padded with zero
     // columns of lengthscale 1: a padding column adds (0 * 1 - 0 * 1)^2 = +0.0 to every squared distance, so a
     // node's Gram matrix — and its score — is bit-identical to the one its own feature count would give.
@@ -2068,11 +1990,13 @@ static int nodes_general(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, i
     return gp_logpdf_general(c, count, nF_max, Fsrc, same_f ? 1 : 0, nF_max ? lsp : nullptr, sc, no, tg, 0, logpdf, draws_or_null);
 }
 
-int gpslc_nodes_logpdf(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, double* logpdf) {
+// The argument checks of the fused node calls (`out`: the output the call must deliver, argument 4 of both signatures):
+// the largest feature count of the nodes, or the negative status
+int nodes_check(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, const double* out, const char* out_is_null) {
     if (!c) return -1;
     if (count < 0) return bad_arg(c, 2, "count < 0");
     if (count > 0 && !nodes) return bad_arg(c, 3, "nodes is NULL");
-    if (count > 0 && !logpdf) return bad_arg(c, 4, "logpdf is NULL");
+    if (count > 0 && !out) return bad_arg(c, 4, out_is_null);
     int nF_max = 0;
     for (int i = 0; i < count; ++i) {
         const gpslc_node& q = nodes[i];
@@ -2080,65 +2004,34 @@ int gpslc_nodes_logpdf(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, dou
             return bad_arg(c, 3, "node with nF outside 0..32 or a NULL feature / lengthscale / target pointer");
         nF_max = std::max(nF_max, (int)q.nF);
     }
-    if (count == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return guarded(c, [&]() {
-        if (fast_path_ok(c, nF_max, count)) {
-            std::vector<HostNode> hn((size_t)count);
-            for (int i = 0; i < count; ++i) {
-                HostNode& h = hn[i];
-                h = HostNode{};
-                h.nF = nodes[i].nF;
-                h.F[0] = nodes[i].F; h.nFpart[0] = nodes[i].nF; h.ls[0] = nodes[i].ls;
-                h.scale = nodes[i].scale; h.noise = nodes[i].noise; h.target = nodes[i].target;
-            }
-            return small_nodes_logpdf(c, count, hn.data(), logpdf);
-        }
-        return nodes_general(c, count, nodes, nF_max, logpdf, nullptr);
-    });
+    return nF_max;
 }
 
-int gpslc_nodes_draw(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, double* draws, double* logpdf_or_null) {
-    if (!c) return -1;
-    if (count < 0) return bad_arg(c, 2, "count < 0");
-    if (count > 0 && !nodes) return bad_arg(c, 3, "nodes is NULL");
-    if (count > 0 && !draws) return bad_arg(c, 4, "draws is NULL");
-    int nF_max = 0;
-    for (int i = 0; i < count; ++i) {
-        const gpslc_node& q = nodes[i];
-        if (q.nF < 0 || q.nF > 32 || (q.nF > 0 && (!q.F || !q.ls)) || !q.target)
-            return bad_arg(c, 3, "node with nF outside 0..32 or a NULL feature / lengthscale / target pointer");
-        nF_max = std::max(nF_max, (int)q.nF);
-    }
+// The body of the fused node calls: every node one workgroup of ONE launch, or — beyond the single-workgroup kernels (n > 640,
+// many nodes, fp32 kernel mode) — the batched tiled factorisation of every node's covariance; with draws_or_null also
+// chol(K_i) target_i per node (the small kernels' draw mode; L z on the predictive-draw kernel, round 6)
+int nodes_score(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, int nF_max, double* logpdf_or_null, double* draws_or_null) {
     if (count == 0) { c->last_info.clear(); return GPSLC_OK; }
     return guarded(c, [&]() {
-        std::vector<double> lp((size_t)count);
-        int st;
-        if (fast_path_ok(c, nF_max, count)) {
-            std::vector<HostNode> hn((size_t)count);
-            for (int i = 0; i < count; ++i) {
-                HostNode& h = hn[i];
-                h = HostNode{};
-                h.nF = nodes[i].nF;
-                h.F[0] = nodes[i].F; h.nFpart[0] = nodes[i].nF; h.ls[0] = nodes[i].ls;
-                h.scale = nodes[i].scale; h.noise = nodes[i].noise; h.target = nodes[i].target;
-            }
-            st = small_nodes_logpdf(c, count, hn.data(), lp.data(), draws);
-        } else {
-            // beyond the single-workgroup kernels (n > 640, many nodes, fp32 kernel mode): the batched tiled factorisation of
-            // every node's covariance, then L z on the predictive-draw kernel (round 6)
-            st = nodes_general(c, count, nodes, nF_max, lp.data(), draws);
+        std::vector<double> lp;                      // the scores are computed either way: kept only when the caller asks
+        if (!logpdf_or_null) { lp.resize((size_t)count); logpdf_or_null = lp.data(); }
+        if (!fast_path_ok(c, nF_max, count)) return nodes_general(c, count, nodes, nF_max, logpdf_or_null, draws_or_null);
+        std::vector<HostNode> hn;
+        hn.reserve((size_t)count);
+        for (int i = 0; i < count; ++i) {
+            const gpslc_node& q = nodes[i];
+            hn.push_back(rbf_node(q.nF, q.F, q.ls, q.scale, q.noise, q.target));
         }
-        if (logpdf_or_null) memcpy(logpdf_or_null, lp.data(), (size_t)count * sizeof(double));
-        return st;
+        return small_nodes_logpdf(c, count, hn.data(), logpdf_or_null, draws_or_null);
     });
 }
 
 // both paths of gpslc_mvn_logpdf / gpslc_mvn_draw can run on this ctx (n <= 640): then the dense covariance is always kept
-static bool mvn_dual(const gpslc_ctx* c) { return fast_path_ok(c, 0, 1); }
+bool mvn_dual(const gpslc_ctx* c) { return fast_path_ok(c, 0, 1); }
 
 // the tiled factor of the device covariance dcov (substitution-based: SigmaU * uNoise is near-singular by construction, 1e-13
 // jitter, src/utils.jl:17-33); mvn_logdet / mvn_info from it, and it now stands for hand-over mvn_gen
-static void mvn_factor_tiles(gpslc_ctx* c, const double* dcov) {
+void mvn_factor_tiles(gpslc_ctx* c, const double* dcov) {
     ensure_streams(c);
     const int nt = c->nt;
     const long long nlow = (long long)nt * (nt + 1) / 2;
@@ -2162,7 +2055,7 @@ static void mvn_factor_tiles(gpslc_ctx* c, const double* dcov) {
 
 // hands a covariance over: n <= 640 keeps the dense matrix (and validates it on the single-workgroup kernel when the call takes
 // that path), the tiled path factorises it; mvn_info = its LAPACK-style info
-static void mvn_cache(gpslc_ctx* c, const double* cov, bool small) {
+void mvn_cache(gpslc_ctx* c, const double* cov, bool small) {
     const size_t n = (size_t)c->n;
     c->mvn_valid = false;
     ++c->mvn_gen;
@@ -2177,8 +2070,7 @@ static void mvn_cache(gpslc_ctx* c, const double* cov, bool small) {
     if (small) {
         // validate once (as the tiled path does when it factorises): info of cov itself
         std::vector<double> zeros(n, 0.0);
-        HostNode probe{};
-        probe.dev_cov = c->mvn_dense; probe.covscale = 1.0; probe.target = zeros.data();
+        const HostNode probe = dense_node(c->mvn_dense, 1.0, zeros.data());
         double dummy = 0.0;
         c->mvn_info = small_nodes_logpdf(c, 1, &probe, &dummy);
     } else {
@@ -2189,54 +2081,125 @@ static void mvn_cache(gpslc_ctx* c, const double* cov, bool small) {
 
 // before a cov = NULL call on the tiled path: the factor of the latest hand-over (rebuilt from the dense copy when an earlier
 // hand-over went to the single-workgroup path)
-static void mvn_tiles_current(gpslc_ctx* c) {
+void mvn_tiles_current(gpslc_ctx* c) {
     if (c->mvn_tiles && c->mvn_tiles_gen == c->mvn_gen) return;
     mvn_factor_tiles(c, c->mvn_dense);
 }
 
-int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* covscale, const double* x,
-                     double* logpdf) {
+// What gpslc_mvn_logpdf and gpslc_mvn_draw do before they differ (`in`: x / z, argument 5; `out`: the result, argument 6):
+// the pointer checks, then — small: the call runs on the single-workgroup kernels — the covariance is handed over, or the tiled
+// factor brought up to date when the call runs tiled and gave none, and every vector's info is that of the covariance.
+// `body(small)` goes on from there; mvn_info != 0 and S == 0 are its to answer (the two calls differ there).
+template <class Body>
+int mvn_call(gpslc_ctx* c, int64_t S, const double* cov, const double* in, const char* in_is_null, const double* out,
+             const char* out_is_null, Body&& body) {
     if (!c) return -1;
     if (S < 0) return bad_arg(c, 2, "S < 0");
     if (!cov && !c->mvn_valid) return bad_arg(c, 3, "cov is NULL and no factor is cached");
-    if (S > 0 && !x) return bad_arg(c, 5, "x is NULL");
-    if (S > 0 && !logpdf) return bad_arg(c, 6, "logpdf is NULL");
-    if (fast_path_ok(c, 0, std::max<int64_t>(S, 1))) {
-        // small n: keep the dense matrix on the device; every evaluation is one workgroup that scales, factorises
-        // and solves in LDS (k_small.hip) — cheaper than the tiled forward solve against a cached factor
-        return guarded(c, [&]() {
-            const size_t n = (size_t)c->n;
-            if (cov) mvn_cache(c, cov, true);
-            c->last_info.assign((size_t)S, c->mvn_info);
-            if (S == 0 || c->mvn_info != 0) {
-                for (int64_t s = 0; s < S; ++s) logpdf[s] = NAN;
-                return c->mvn_info;
-            }
-            std::vector<HostNode> hn((size_t)S);
-            for (int64_t s = 0; s < S; ++s) {
-                hn[s] = HostNode{};
-                hn[s].dev_cov = c->mvn_dense;
-                hn[s].covscale = covscale ? covscale[s] : 1.0;
-                hn[s].target = x + s * n;
-            }
+    if (S > 0 && !in) return bad_arg(c, 5, in_is_null);
+    if (S > 0 && !out) return bad_arg(c, 6, out_is_null);
+    const bool small = fast_path_ok(c, 0, std::max<int64_t>(S, 1));
+    return guarded(c, [&]() {
+        if (cov) mvn_cache(c, cov, small);   // factor once, keep it in the context
+        else if (!small) mvn_tiles_current(c);
+        c->last_info.assign((size_t)S, c->mvn_info);
+        return body(small);
+    });
+}
+
+// the S dense-covariance nodes of the single-workgroup path: covscale_s times the cached covariance, target column s
+std::vector<HostNode> mvn_nodes(const gpslc_ctx* c, int64_t S, const double* covscale, const double* target) {
+    std::vector<HostNode> hn;
+    hn.reserve((size_t)S);
+    for (int64_t s = 0; s < S; ++s) hn.push_back(dense_node(c->mvn_dense, covscale ? covscale[s] : 1.0, target + s * c->n));
+    return hn;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpslc_y_logpdf(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                   const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale,
+                   const double* yNoise, double* logpdf) {
+    const PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 0, nullptr);
+    int rc = validate(c, rq, kSamplesArgs);
+    if (rc) return rc;
+    if (!logpdf) return bad_arg(c, 11, "logpdf is NULL");
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        const size_t n = (size_t)c->n;
+        if (fast_path_ok(c, c->nU + c->nX + 1, S)) {
+            // small n: every parameter set is one workgroup of ONE launch (k_small.hip); T enters as a feature column
+            std::vector<HostNode> hn;
+            hn.reserve((size_t)S);
+            for (int64_t s = 0; s < S; ++s)
+                hn.push_back(y_node(c->nU, U + s * n * c->nU, uyLS + s * c->nU, c->nX, X_or_null ? X_or_null : c->hX.data(),
+                                    xyLS + s * c->nX, c->hT.data(), tyLS[s], yScale[s], yNoise[s],
+                                    Y_or_null ? Y_or_null : c->hY.data()));
+            return small_nodes_logpdf(c, (int)S, hn.data(), logpdf);
+        }
+        c->io.reset();
+        PredictIO io;
+        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
+        io.X = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
+        if (Y_or_null) { io.Y = up(c, Y_or_null, n); io.y_sstride = 0; }    // the value being scored (Gen passes it to logpdf), else the ctx's Y
+        return tiled_score(c, io, logpdf);
+    });
+}
+
+int gpslc_gp_logpdf(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_t f_shared, const double* ls,
+                    const double* scale, const double* noise, const double* target, int32_t t_shared,
+                    double* logpdf) {
+    if (!c) return -1;
+    if (S < 0) return bad_arg(c, 2, "S < 0");
+    if (nF < 0 || nF > 32) return bad_arg(c, 3, "nF must be in 0..32");
+    if (nF > 0 && (!F || !ls)) return bad_arg(c, 4, "F / ls must not be NULL when nF > 0");
+    if (S > 0 && (!scale || !noise)) return bad_arg(c, 7, "scale / noise must not be NULL");
+    if (S > 0 && !target) return bad_arg(c, 9, "target is NULL");
+    if (!logpdf) return bad_arg(c, 11, "logpdf is NULL");
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        const size_t n = (size_t)c->n;
+        if (!fast_path_ok(c, nF, S)) return gp_logpdf_general(c, S, nF, F, f_shared, ls, scale, noise, target, t_shared, logpdf);
+        std::vector<HostNode> hn;
+        hn.reserve((size_t)S);
+        for (int64_t s = 0; s < S; ++s)
+            hn.push_back(rbf_node(nF, F + (f_shared ? 0 : s * n * nF), ls + s * nF, scale[s], noise[s], target + (t_shared ? 0 : s * n)));
+        return small_nodes_logpdf(c, (int)S, hn.data(), logpdf);
+    });
+}
+
+int gpslc_nodes_logpdf(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, double* logpdf) {
+    const int nF_max = nodes_check(c, count, nodes, logpdf, "logpdf is NULL");
+    return nF_max < 0 ? nF_max : nodes_score(c, count, nodes, nF_max, logpdf, nullptr);
+}
+
+int gpslc_nodes_draw(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, double* draws, double* logpdf_or_null) {
+    const int nF_max = nodes_check(c, count, nodes, draws, "draws is NULL");
+    return nF_max < 0 ? nF_max : nodes_score(c, count, nodes, nF_max, logpdf_or_null, draws);
+}
+
+int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* covscale, const double* x,
+                     double* logpdf) {
+    return mvn_call(c, S, cov, x, "x is NULL", logpdf, "logpdf is NULL", [&](bool small) {
+        if (S == 0 || c->mvn_info != 0) {
+            for (int64_t s = 0; s < S; ++s) logpdf[s] = NAN;
+            return c->mvn_info;
+        }
+        if (small) {
+            // small n: the dense matrix stays on the device; every evaluation is one workgroup that scales, factorises
+            // and solves in LDS (k_small.hip) — cheaper than the tiled forward solve against a cached factor
+            const std::vector<HostNode> hn = mvn_nodes(c, S, covscale, x);
             const int st = small_nodes_logpdf(c, (int)S, hn.data(), logpdf);
             if (st > 0) for (int64_t s = 0; s < S; ++s) if (c->last_info[s] != 0) logpdf[s] = NAN;
             return st;
-        });
-    }
-    return guarded(c, [&]() {
+        }
         ensure_streams(c);
         const int n = (int)c->n, nt = c->nt;
         const long long nlow = (long long)nt * (nt + 1) / 2;
         StreamSlot& slot = c->slots[0];
         hipStream_t st = slot.st;
-        if (cov) mvn_cache(c, cov, false);   // factor once, keep L in the context
-        else mvn_tiles_current(c);
-        c->last_info.assign((size_t)S, c->mvn_info);
-        if (S == 0 || c->mvn_info != 0) {
-            for (int64_t s = 0; s < S; ++s) logpdf[s] = NAN;
-            return c->mvn_info;
-        }
         // z_s = L^-1 x_s for all S vectors: rows of W = X^T L^-T, tile-level left-looking solve
         const int naug = (int)((S + GP_TS - 1) / GP_TS);
         c->io.reset();
@@ -2266,10 +2229,9 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
         if (c->flags & GPSLC_FLAG_PROFILE) prof_collect(c);
         std::vector<double> q(S);
         HC(hipMemcpy(q.data(), oq, sizeof(double) * S, hipMemcpyDeviceToHost));
-        const double l2pi = 1.8378770664093454835606594728112;
         for (int64_t s = 0; s < S; ++s) {
             const double sc = covscale ? covscale[s] : 1.0;
-            logpdf[s] = -0.5 * ((double)n * l2pi + (double)n * std::log(sc) + c->mvn_logdet + q[s] / sc);
+            logpdf[s] = -0.5 * ((double)n * kLog2Pi + (double)n * std::log(sc) + c->mvn_logdet + q[s] / sc);
         }
         return GPSLC_OK;
     });
@@ -2279,30 +2241,15 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
 // elliptical_slice(trace, :U => k => :U, zeros(n), uCov) (src/inference.jl:48-54) and the prior draw generateUfromSigmaU
 // (src/model_likelihood.jl:4-10) — from the covariance gpslc_mvn_logpdf caches (chol(s C) = sqrt(s) chol(C))
 int gpslc_mvn_draw(gpslc_ctx* c, int64_t S, const double* cov, const double* covscale, const double* z, double* draws) {
-    if (!c) return -1;
-    if (S < 0) return bad_arg(c, 2, "S < 0");
-    if (!cov && !c->mvn_valid) return bad_arg(c, 3, "cov is NULL and no factor is cached");
-    if (S > 0 && !z) return bad_arg(c, 5, "z is NULL");
-    if (S > 0 && !draws) return bad_arg(c, 6, "draws is NULL");
-    const bool small = fast_path_ok(c, 0, std::max<int64_t>(S, 1));
-    return guarded(c, [&]() {
+    return mvn_call(c, S, cov, z, "z is NULL", draws, "draws is NULL", [&](bool small) {
         const size_t n = (size_t)c->n;
-        if (cov) mvn_cache(c, cov, small);
-        else if (!small) mvn_tiles_current(c);
-        c->last_info.assign((size_t)S, c->mvn_info);
-        if (S == 0) return GPSLC_OK;
+        if (S == 0) return GPSLC_OK;        // a hand-over alone answers GPSLC_OK here; the covariance's info is in last_info
         if (c->mvn_info != 0) {
             for (size_t e = 0; e < n * (size_t)S; ++e) draws[e] = NAN;
             return c->mvn_info;
         }
         if (small) {
-            std::vector<HostNode> hn((size_t)S);
-            for (int64_t s = 0; s < S; ++s) {
-                hn[s] = HostNode{};
-                hn[s].dev_cov = c->mvn_dense;
-                hn[s].covscale = covscale ? covscale[s] : 1.0;
-                hn[s].target = z + s * n;
-            }
+            const std::vector<HostNode> hn = mvn_nodes(c, S, covscale, z);
             std::vector<double> lp((size_t)S);
             return small_nodes_logpdf(c, (int)S, hn.data(), lp.data(), draws);
         }
@@ -2317,11 +2264,7 @@ int gpslc_mvn_draw(gpslc_ctx* c, int64_t S, const double* cov, const double* cov
         double* out = c->io.take<double>(n * (size_t)S);
         double* zt = c->io.take<double>((size_t)S * 16 * Np);
         HC(hipMemsetAsync(zero_mean, 0, n * (size_t)S * sizeof(double), st));
-        DrawArgs dr{};
-        dr.Lc = lower_ref(c->mvn_tiles, 0); dr.n = (int)n; dr.nt = nt; dr.s0 = 0; dr.S = S; dr.l = 0; dr.lc = 1; dr.L = 1; dr.spp = 1;
-        dr.mean = zero_mean; dr.z = dz; dr.zt = zt; dr.out = out;
-        dr.obase = 0; dr.osb = (long long)n; dr.osl = 0; dr.osi = 1; dr.osd = (long long)n;
-        launch_draws(dr, (int)S, st);
+        launch_draws(zero_mean_draw(lower_ref(c->mvn_tiles, 0), (int)n, nt, 0, S, zero_mean, dz, zt, out), (int)S, st);
         HC(hipStreamSynchronize(st));
         HC(hipGetLastError());
         HC(hipMemcpy(draws, out, n * (size_t)S * sizeof(double), hipMemcpyDeviceToHost));

@@ -51,6 +51,33 @@ def test_multi_multi_tile_matrix_and_more_contexts_than_samples(gp):
         _same(a, b)
 
 
+def test_multi_mean_ite_block_large_enough_for_the_chunked_strided_delivery(gp):
+    """A shard whose MeanITE block takes the pinned, double-buffered delivery with strided rows: n = 150, S = 1400 over two
+    contexts, 160 levels.  Each shard's block is 150 x 700 x 160 doubles = 134,400,000 bytes: at least two 64 MiB chunks and
+    no multiple of one (the last chunk is partial); its rows (one level: 840,000 bytes) do not divide 64 MiB, so rows
+    straddle chunk boundaries and the slices of the copying threads.  The single-context call delivers the same 268.8 MB as
+    one contiguous run through the same chunks.  Both must agree bit for bit; and, independent of that delivery, the mean
+    over the individuals of every MeanITE[:, s, l] must be meanSATE[s, l], which arrives by a plain small copy (the bound of
+    test_ite_distributions_large_hand_over_n2048 for the same identity)."""
+    n, S, L = 150, 1400, 160
+    g = cases.gpslc_object(gp, cases.make_case(n, "UX", False, S=S, seed=31))
+    doT = np.linspace(-0.8, 0.8, L)
+    ms1, vs1, mi1 = gp.predict(g, doT, want_mean_ite=True)
+    ms2, vs2, mi2 = gp.predict(g, doT, want_mean_ite=True, devices=[0, 0])
+    try:
+        _same(ms1, ms2)
+        _same(vs1, vs2)
+        assert mi1.shape == mi2.shape == (n, S, L)
+        assert np.array_equal(mi1, mi2)
+        err = np.abs(mi2.mean(axis=0) - ms2)
+        bound = 1e-9 * np.abs(ms2) + 1e-12
+        print("mean_i MeanITE against meanSATE: worst error / bound =", float(np.max(err / bound)),
+              "worst absolute error =", float(err.max()))
+        assert np.all(err <= bound), float(np.max(err / bound))
+    finally:
+        del mi1, mi2                                            # 269 MB each
+
+
 def test_predict_counterfactual_effects_over_devices(gp):
     c = cases.make_case(150, "U", False, S=4, seed=8)
     g = cases.gpslc_object(gp, c)
