@@ -2406,8 +2406,10 @@ int gpslc_summarize_dev(gpslc_ctx* c, const double* samples, int64_t n, int64_t 
                         int64_t col_stride, double credible_interval, double* mean, double* lower, double* upper) {
     if (!c) return -1;
     if (!samples) return bad_arg(c, 2, "samples is NULL");
-    if (n < 1) return bad_arg(c, 3, "n < 1");
+    if (n < 1 || n > 2147483647LL) return bad_arg(c, 3, "n must be in 1..2^31-1");
     if (m < 1 || m > 2147483647LL) return bad_arg(c, 4, "m must be in 1..2^31-1");
+    if (row_stride < 1) return bad_arg(c, 5, "row_stride < 1");
+    if (col_stride < 1) return bad_arg(c, 6, "col_stride < 1");
     if (!(credible_interval > 0.0 && credible_interval < 1.0)) return bad_arg(c, 7, "credible_interval not in (0,1)");
     if (!mean || !lower || !upper) return bad_arg(c, 8, "output is NULL");
     return guarded(c, [&]() { return summarize_impl(c, samples, n, m, row_stride, col_stride, credible_interval,
@@ -2418,7 +2420,7 @@ int gpslc_summarize(gpslc_ctx* c, const double* samples, int64_t n, int64_t m, d
                     double* mean, double* lower, double* upper) {
     if (!c) return -1;
     if (!samples) return bad_arg(c, 2, "samples is NULL");
-    if (n < 1) return bad_arg(c, 3, "n < 1");
+    if (n < 1 || n > 2147483647LL) return bad_arg(c, 3, "n must be in 1..2^31-1");
     if (m < 1 || m > 2147483647LL) return bad_arg(c, 4, "m must be in 1..2^31-1");
     if (!(credible_interval > 0.0 && credible_interval < 1.0)) return bad_arg(c, 5, "credible_interval not in (0,1)");
     if (!mean || !lower || !upper) return bad_arg(c, 6, "output is NULL");

@@ -62,7 +62,8 @@ typedef struct gpslc_ctx gpslc_ctx;
 int gpslc_create(gpslc_ctx** out, int device, int64_t n, int32_t nX, int32_t nU, uint32_t flags);
 int gpslc_destroy(gpslc_ctx* ctx);
 
-/* g.X (n x nX, may be NULL when nX == 0), g.T (n), g.Y (n): src/types.jl:249-258. */
+/* g.X (n x nX, may be NULL when nX == 0), g.T (n), g.Y (n): src/types.jl:249-258.  The arrays are copied; the caller
+ * may free or reuse its arrays after the call (host pointers, or device pointers for _dev). */
 int gpslc_set_data(gpslc_ctx* ctx, const double* X, const double* T, const double* Y);
 int gpslc_set_data_dev(gpslc_ctx* ctx, const double* X, const double* T, const double* Y);
 
@@ -371,7 +372,9 @@ int gpslc_sate_samples(const double* meanSATE, const double* varSATE, int64_t S,
  * posterior) go through an exact radix select.  The _dev variant reads device memory with explicit strides
  * (sample (i, j) at samples[i*row_stride + j*col_stride]) so that level l of gpslc_predict_dev's ite_draws
  * (L x n x M, level fastest) is summarised in place with samples = draws + l, row_stride = L,
- * col_stride = L*n, and writes device outputs: the draw tensor never leaves HBM. */
+ * col_stride = L*n, and writes device outputs: the draw tensor never leaves HBM.  Both strides count doubles and must be
+ * at least 1: row_stride < 1 returns -5, col_stride < 1 returns -6.  n and m are at most 2^31 - 1 (else -3 / -4), for both
+ * entry points. */
 int gpslc_summarize(gpslc_ctx* ctx, const double* samples, int64_t n, int64_t m, double credible_interval,
                     double* mean, double* lower, double* upper);
 int gpslc_summarize_dev(gpslc_ctx* ctx, const double* samples, int64_t n, int64_t m, int64_t row_stride,

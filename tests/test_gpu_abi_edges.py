@@ -12,6 +12,7 @@ import pytest
 
 import cases
 import gpslc_oracle as orc
+from devmem import Hip as _Hip
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,38 +34,6 @@ def test_y_logpdf_scores_the_value_it_is_given(gp):
     assert not np.allclose(lp_other, lp_data)
     # and the override does not stick
     assert np.array_equal(gp.yLogpdf(g), lp_data)
-
-
-class _Hip:
-    """hipMalloc / hipMemcpy through ctypes on the HIP runtime the library itself uses (no torch needed)."""
-
-    def __init__(self):
-        self.rt = C.CDLL("libamdhip64.so.7")      # already loaded by libgpslc_hip.so: same instance
-        self.rt.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.rt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.rt.hipFree.argtypes = [C.c_void_p]
-        self.bufs = []
-
-    def up(self, x):
-        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, order="F"))
-        p = self.empty(x.size)
-        assert self.rt.hipMemcpy(p, x.ctypes.data_as(C.c_void_p), x.nbytes, 1) == 0
-        return p
-
-    def empty(self, count):
-        p = C.c_void_p()
-        assert self.rt.hipMalloc(C.byref(p), 8 * count) == 0
-        self.bufs.append(p)
-        return p
-
-    def down(self, p, count):
-        out = np.empty(count)
-        assert self.rt.hipMemcpy(out.ctypes.data_as(C.c_void_p), p, 8 * count, 2) == 0
-        return out
-
-    def free(self):
-        for p in self.bufs:
-            self.rt.hipFree(p)
 
 
 def test_rbf_log_and_process_cov_device_pointer_forms(gp):
