@@ -11,7 +11,6 @@
 #include "sm_blocks.h"
 #include <type_traits>
 
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 #define NSB (GP_TS / SB)
 

@@ -14,6 +14,12 @@
 #define GP_TS 128
 #define GP_TSQ (GP_TS * GP_TS)
 
+// MFMA accumulators (v_mfma_f64_16x16x4_f64: four doubles per lane) and 16-byte accesses, for every kernel file
+typedef double d4 __attribute__((ext_vector_type(4)));
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+#define MAXF 32   // max nU + nX of the kernels that hold the features of a tile's rows in LDS (k_gram.hip, k_solve.hip)
+
 // ---------------------------------------------------------------------------------------
 // Per-device launch state.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device only
 // and one process may hold a ctx per GPU, each driven by its own thread: every kernel

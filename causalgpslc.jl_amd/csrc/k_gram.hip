@@ -14,8 +14,6 @@
 #include "gp_math.h"
 #include <type_traits>
 
-#define MAXF 32   // max nU + nX handled by the fused Gram kernel
-
 // block-wide sum with a fixed reduction tree (deterministic); result valid in every thread
 __device__ __forceinline__ double block_sum_256(double v, double* red /* >= 4 doubles */) {
 #pragma unroll

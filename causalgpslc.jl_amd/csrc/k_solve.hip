@@ -4,8 +4,6 @@
 #include "gp_math.h"
 #include "back_block.h"
 
-#define MAXF 32
-
 // ---------------------------------------------------------------------------------------
 // Back-substitution L^T alpha = z, right-looking over tile rows i = nt-1 .. 0, two launches per row:
 // alpha_i = inv(L_ii)^T z_i (one workgroup per matrix), then z_k -= L(i,k)^T alpha_i for every k < i
@@ -211,8 +209,6 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 // sub-tiles = 8 accumulators).
 // CON: contrasts as in ite_mean_kernel — R[j, l] = (r^a_j - r^b_j) alpha_j, no K alpha term, 0.0 for a level with a == b.
 // ---------------------------------------------------------------------------------------
-typedef double d4s __attribute__((ext_vector_type(4)));
-typedef double d2s __attribute__((ext_vector_type(2)));
 #define IM_CC 64          // columns per staged chunk
 #define IM_RLD 80         // padded row of the R chunk (doubles): conflict-free ds_read_b64 across k rows
 #define IM_NL 64          // levels per pass
@@ -258,11 +254,11 @@ __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
     for (int l0 = 0; l0 < a.L; l0 += IM_NL) {
         const int nl = min(IM_NL, a.L - l0);
         const int nq = (nl + 15) >> 4;          // live 16-level sub-tiles of this pass (wave-uniform)
-        d4s acc[2][4];
+        d4 acc[2][4];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[m][q] = (d4s){0.0, 0.0, 0.0, 0.0};
+            for (int q = 0; q < 4; ++q) acc[m][q] = (d4){0.0, 0.0, 0.0, 0.0};
         for (int c0 = 0; c0 < Np; c0 += IM_CC) {
             __syncthreads();
             const int FS = FREG > F ? FREG : F;      // staged feature rows (zero beyond F)
@@ -639,11 +635,11 @@ __global__ __launch_bounds__(256) void draws_mfma_kernel(DrawArgs a) {
 
     for (int d0 = 0; d0 < a.spp; d0 += ND) {
         const int nd = min(ND, a.spp - d0);
-        d4s acc[2][NQ];
+        d4 acc[2][NQ];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) acc[m][q] = (d4s){0.0, 0.0, 0.0, 0.0};
+            for (int q = 0; q < NQ; ++q) acc[m][q] = (d4){0.0, 0.0, 0.0, 0.0};
         // (rounds 2-4 ran 1..128 draws through this kernel, with a software-pipelined form for <= 16: since round 5 it serves units of
         // more than 128 draws only — several passes over L_c; profiles/r05_draws_lds_kernel.patch has the removed branches)
         for (int jt = 0; jt <= ib; ++jt) {
@@ -651,10 +647,10 @@ __global__ __launch_bounds__(256) void draws_mfma_kernel(DrawArgs a) {
 #pragma unroll 1
             for (int kc = 0; kc < GP_TS / DR_KC; ++kc) {
                 // this lane's rows of the 16 column groups of the chunk: 16 independent 16-byte loads in flight
-                d2s lv[DR_KC / 4];
+                d2 lv[DR_KC / 4];
 #pragma unroll
                 for (int kk = 0; kk < DR_KC / 4; ++kk)
-                    lv[kk] = *reinterpret_cast<const d2s*>(t + (kc * DR_KC + 4 * kk + lq) * GP_TS);
+                    lv[kk] = *reinterpret_cast<const d2*>(t + (kc * DR_KC + 4 * kk + lq) * GP_TS);
                 __syncthreads();
                 for (int idx = tid; idx < DR_KC * ND; idx += 256) {
                     const int k = idx & (DR_KC - 1), dd = idx / DR_KC;
@@ -696,7 +692,7 @@ __global__ __launch_bounds__(256) void draws_mfma_kernel(DrawArgs a) {
                         double* o = ob + (long long)(d0 + dd) * a.osd;
                         const double x0 = mu0 + acc[0][q][v], x1 = mu1 + acc[1][q][v];
                         if (a.osi == 1 && gi + 1 < n && ((reinterpret_cast<unsigned long long>(o) & 15ull) == 0)) {
-                            *reinterpret_cast<d2s*>(o) = (d2s){x0, x1};
+                            *reinterpret_cast<d2*>(o) = (d2){x0, x1};
                         } else {
                             o[0] = x0;
                             if (gi + 1 < n) o[a.osi] = x1;
@@ -787,7 +783,7 @@ __global__ __launch_bounds__(256) void draws_zstage_kernel(DrawArgs a) {
             if (g1 < n) v1 = philox_normal(a.seed, stream, (unsigned long long)(g1 + n * d));
         }
     }
-    *reinterpret_cast<d2s*>(a.zt + b * Np * 16 * nq + 2 * t) = (d2s){v0, v1};
+    *reinterpret_cast<d2*>(a.zt + b * Np * 16 * nq + 2 * t) = (d2){v0, v1};
 }
 
 // CC columns per chunk (CC / 4 k groups of the 16x16x4 MFMA), NS register sets in rotation, WPE waves per SIMD the
@@ -812,23 +808,23 @@ __global__ __launch_bounds__(256, WPE) void draws_stream_kernel(DrawArgs a) {
         // the tiles (ib, 0..ib) of a row are contiguous in both tile layouts
         const double* __restrict__ Lrow = tref_tile(a.Lc, b, ib, 0) + r0 + lq * GP_TS;
         const int nch = (GP_TS / CC) * ib + (32 / CC) * wave + 32 / CC;   // chunks up to and including the wave's diagonal block
-        d4s acc0[NQ], acc1[NQ];
+        d4 acc0[NQ], acc1[NQ];
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) { acc0[q] = (d4s){0.0, 0.0, 0.0, 0.0}; acc1[q] = acc0[q]; }
-        d2s lv[NS][NL], zv[NS][NQ * NZ];
-        auto load = [&](int c, d2s (&l)[NL], d2s (&z)[NQ * NZ]) {
+        for (int q = 0; q < NQ; ++q) { acc0[q] = (d4){0.0, 0.0, 0.0, 0.0}; acc1[q] = acc0[q]; }
+        d2 lv[NS][NL], zv[NS][NQ * NZ];
+        auto load = [&](int c, d2 (&l)[NL], d2 (&z)[NQ * NZ]) {
             c = min(c, nch - 1);                         // past the end: the last chunk again (keeps the loop body branch-free)
             const double* __restrict__ zp = zt + (long long)c * (CC * 16);
 #pragma unroll
             for (int q = 0; q < NQ; ++q)
 #pragma unroll
-                for (int m = 0; m < NZ; ++m) z[q * NZ + m] = *reinterpret_cast<const d2s*>(zp + q * (16 * Np) + m * 128);
+                for (int m = 0; m < NZ; ++m) z[q * NZ + m] = *reinterpret_cast<const d2*>(zp + q * (16 * Np) + m * 128);
             const double* __restrict__ lp = Lrow + (long long)c * (CC * GP_TS);
 #pragma unroll
             for (int kk = 0; kk < NL; ++kk)
-                l[kk] = __builtin_nontemporal_load(reinterpret_cast<const d2s*>(lp + kk * 4 * GP_TS));
+                l[kk] = __builtin_nontemporal_load(reinterpret_cast<const d2*>(lp + kk * 4 * GP_TS));
         };
-        auto compute = [&](const d2s (&l)[NL], const d2s (&z)[NQ * NZ]) {
+        auto compute = [&](const d2 (&l)[NL], const d2 (&z)[NQ * NZ]) {
 #pragma unroll
             for (int kk = 0; kk < NL; ++kk)
 #pragma unroll
@@ -839,7 +835,7 @@ __global__ __launch_bounds__(256, WPE) void draws_stream_kernel(DrawArgs a) {
                 }
         };
         // the chunks of the wave's own 32 x 32 diagonal block: only the lower triangle belongs to L_c
-        auto mask_diag = [&](d2s (&l)[NL], int c) {
+        auto mask_diag = [&](d2 (&l)[NL], int c) {
             const int cb = (c * CC) & 31;                // first column of the chunk relative to the wave's first row
 #pragma unroll
             for (int kk = 0; kk < NL; ++kk) {
@@ -883,7 +879,7 @@ __global__ __launch_bounds__(256, WPE) void draws_stream_kernel(DrawArgs a) {
                     double* o = ob + (long long)dd * a.osd;
                     const double x0 = mu0 + acc0[q][v], x1 = mu1 + acc1[q][v];
                     if (a.osi == 1 && gi + 1 < n && ((reinterpret_cast<unsigned long long>(o) & 15ull) == 0)) {
-                        *reinterpret_cast<d2s*>(o) = (d2s){x0, x1};
+                        *reinterpret_cast<d2*>(o) = (d2){x0, x1};
                     } else {
                         o[0] = x0;
                         if (gi + 1 < n) o[a.osi] = x1;

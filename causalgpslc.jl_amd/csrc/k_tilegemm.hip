@@ -32,9 +32,6 @@
 #include "diag_block.h"
 #include "back_block.h"
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 // measurement-only paths (in-kernel stamps, timing-only variants) exist in the -DGPSLC_DIAG build only
 #ifdef GPSLC_DIAG
 #define GP_DBG_ON(g) ((g).dbg != nullptr)
@@ -57,7 +54,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // staging instructions.  Measured (profiles/r04_ab_experiments.md §11, three alternating pairs): trailing update 66.4 ->
 // 67.2 TFLOP/s, unit A +0.55 %; priority 3 the same; on the strip kernel -0.3 % (its second phase wants the partner's
 // staging to proceed) -> applied to tile_gemm_nt_kernel only.
-// K-loop barriers of the trailing and strip kernels order LDS traffic only: __syncthreads() carries a fence that also waits
+// K-loop barriers of every kernel here (trailing, strip, diagonal-tile update) order LDS traffic only: __syncthreads() carries a fence that also waits
 // vmcnt(0), i.e. for the slab requested at the top of the iteration — the register staging then ran ONE slab ahead, not two.
 // The barrier needs exactly two things, both LDS: this wave's ds_writes of the next slab have landed (lgkmcnt(0)) and every
 // wave has issued the MFMAs that consumed its ds_reads of the buffer about to be overwritten (program order before s_barrier).
@@ -91,6 +88,63 @@ __device__ __forceinline__ d4 mfma_step(double a, double b, d4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, NEG);
 }
 
+// staging: a slab of one operand is 16 KiB = 1024 16-byte chunks, contiguous in HBM, 4 per thread (chunk q = tid + 256 u);
+// loff[u] = where chunk q goes in the padded LDS slab (k-row q >> 6, row pair q & 63)
+__device__ __forceinline__ void stage_offsets(int tid, int (&loff)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int q = tid + 256 * u;
+        loff[u] = (q >> 6) * LROW + (q & 63) * 2;
+    }
+}
+
+// Persistent, XCD-aware work split: XCD x (blockIdx % 8) owns the x-th contiguous run of the launch's W work items.
+struct XcdSplit {
+    int xcd, local;      // this workgroup's XCD and its rank among the XCD's workgroups
+    int gx;              // workgroups on this XCD
+    long long x0, xc;    // first item of this XCD's run, items in the run
+};
+__device__ __forceinline__ XcdSplit xcd_split(long long W) {
+    const int G = gridDim.x;
+    XcdSplit x;
+    x.xcd = blockIdx.x & 7;
+    x.local = blockIdx.x >> 3;
+    x.gx = (G >> 3) + (x.xcd < (G & 7) ? 1 : 0);
+    const long long wq = W >> 3, wrm = W & 7;
+    x.x0 = x.xcd * wq + (x.xcd < wrm ? x.xcd : wrm);
+    x.xc = wq + (x.xcd < wrm ? 1 : 0);
+    return x;
+}
+
+// Work distribution inside the XCD's run: the first item of a workgroup is `local`; the following ones come from a per-XCD
+// ticket counter (GemmArgs::queue) — items differ in cost (augmented-row tiles, skipped diagonal tiles), a static stride
+// leaves the slowest workgroup ~5 items behind the mean.  The ticket for the NEXT item is requested at the start of the
+// current one, so its latency hides behind the tile.  item_body(item) runs one work item (a tile of a batch element); the
+// barrier that ends an item's last slab protects the LDS buffers, the two here the ticket word.
+template <class Body>
+__device__ __forceinline__ void ticket_loop(const GemmArgs& g, long long W, int tid, Body&& item_body) {
+    const XcdSplit x = xcd_split(W);
+    __shared__ int s_ticket;
+    long long it = x.local;
+    while (it < x.xc) {
+        int ticket = 0;
+        if (tid == 0) ticket = atomicAdd(&g.queue[x.xcd], 1);
+        item_body(x.x0 + it);
+        if (tid == 0) s_ticket = ticket;
+        __syncthreads();
+        it = (long long)x.gx + s_ticket;
+        __syncthreads();
+    }
+    // the last workgroup of the XCD to leave re-arms the counters for the next launch on this stream
+    if (tid == 0) {
+        __threadfence();
+        if (atomicAdd(&g.queue[8 + x.xcd], 1) == x.gx - 1) {
+            g.queue[x.xcd] = 0;
+            g.queue[8 + x.xcd] = 0;
+        }
+    }
+}
+
 template <int ACC, int DIAG>
 __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -101,38 +155,15 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
     double* lA = smem;                       // [2][KS][LROW]
     double* lB = smem + 2 * OPER_LDS;        // [2][KS][LROW]
 
-    // ---- persistent, XCD-aware work split
-    const long long W = (long long)g.ntiles * g.nbatch;
-    const int G = gridDim.x;
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int gx = (G >> 3) + (xcd < (G & 7) ? 1 : 0);                 // workgroups on this XCD
-    const long long wq = W >> 3, wrm = W & 7;
-    const long long x0 = xcd * wq + (xcd < wrm ? xcd : wrm);           // first item of this XCD's run
-    const long long xc = wq + (xcd < wrm ? 1 : 0);                     // items in the run
-
     const int crow = wr * 64 + (lane & 15);
     const int ccol = wc * 64 + (lane >> 4);
     const int frow_a = (lane >> 4) * LROW + wr * 64 + (lane & 15);
     const int frow_b = (lane >> 4) * LROW + wc * 64 + (lane & 15);
     int loff[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int q = tid + 256 * u;
-        loff[u] = (q >> 6) * LROW + (q & 63) * 2;
-    }
+    stage_offsets(tid, loff);
     const int nslab = (g.k1 - g.k0) * (GP_TS / KS);
 
-    // Work distribution inside the XCD's run: the first item of a workgroup is `local`; the following ones come
-    // from a per-XCD ticket counter (GemmArgs::queue) — items differ in cost (augmented-row tiles, skipped
-    // diagonal tiles), a static stride leaves the slowest workgroup ~5 items behind the mean.  The ticket for
-    // the NEXT item is requested at the start of the current one, so its latency hides behind the tile.
-    __shared__ int s_ticket;
-    long long it = local;
-    while (it < xc) {
-        int ticket = 0;
-        if (tid == 0) ticket = atomicAdd(&g.queue[xcd], 1);
-        do {
-        const long long item = x0 + it;
+    ticket_loop(g, (long long)g.ntiles * g.nbatch, tid, [&](const long long item) {
         const int b = (int)(item / g.ntiles);
         const int t = (int)(item - (long long)b * g.ntiles);
         int ii, jj;
@@ -141,11 +172,11 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
         else { ii = t / g.mj; jj = t - ii * g.mj; }
         const int ti = g.i0 + ii, tj = g.j0 + jj;
         // symmetric launch: its full-size diagonal tiles belong to tile_syrk_diag_kernel
-        if (g.sym && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) break;
+        if (g.sym && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) return;
         // sym == 3: the augmented-row tiles of the columns that have a full-size diagonal tile ride with it
-        if (g.sym == 3 && g.short_rows > 0 && ti >= g.short_row0 && tj < g.short_row0) break;
-        if (g.skip_gdiag && ti == tj && g.short_rows > 0 && ti >= g.short_row0) break;   // -R R^T is not needed (EpiArgs::from_rows)
-        if (GP_DIAG_SKIP(g) == 3 && g.short_rows > 0 && ti >= g.short_row0) break;   // timing-only: price of the short tiles
+        if (g.sym == 3 && g.short_rows > 0 && ti >= g.short_row0 && tj < g.short_row0) return;
+        if (g.skip_gdiag && ti == tj && g.short_rows > 0 && ti >= g.short_row0) return;   // -R R^T is not needed (EpiArgs::from_rows)
+        if (GP_DIAG_SKIP(g) == 3 && g.short_rows > 0 && ti >= g.short_row0) return;   // timing-only: price of the short tiles
 
         double* __restrict__ Ct = tref_tile(g.C, b, ti, tj);
         // augmented right-hand-side rows hold only `short_rows` live rows: this wave's number of live
@@ -361,20 +392,7 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
                 d[7] = blockIdx.x;
             }
         }
-        } while (0);
-        if (tid == 0) s_ticket = ticket;
-        __syncthreads();
-        it = (long long)gx + s_ticket;
-        __syncthreads();
-    }
-    // the last workgroup of the XCD to leave re-arms the counters for the next launch on this stream
-    if (tid == 0) {
-        __threadfence();
-        if (atomicAdd(&g.queue[8 + xcd], 1) == gx - 1) {
-            g.queue[xcd] = 0;
-            g.queue[8 + xcd] = 0;
-        }
-    }
+    });
 }
 
 // a pointer every lane of the wave holds the same value of, moved to scalar registers (the base of a buffer descriptor)
@@ -652,85 +670,54 @@ __global__ __launch_bounds__(256, 2) void tile_fused_strip_kernel(GemmArgs g) {
     const int li = lane & 15, lg = lane >> 4;
     double* lB = smem;                       // [2][KS][LROW]: the B slabs; the A operand goes from HBM to registers (strip_item)
 
-    const long long W = (long long)g.ntiles * g.nbatch;
-    const int G = gridDim.x;
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int gx = (G >> 3) + (xcd < (G & 7) ? 1 : 0);
-    const long long wq = W >> 3, wrm = W & 7;
-    const long long x0 = xcd * wq + (xcd < wrm ? xcd : wrm);
-    const long long xc = wq + (xcd < wrm ? 1 : 0);
-
     const int frow_b = lg * LROW + li;                 // + 16 n
     int loff[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int q = tid + 256 * u;
-        loff[u] = (q >> 6) * LROW + (q & 63) * 2;
-    }
+    stage_offsets(tid, loff);
     const int nslab = (g.k1 - g.k0) * (GP_TS / KS);
 
-    __shared__ int s_ticket;
-    long long it = local;
-    while (it < xc) {
-        int ticket = 0;
-        if (tid == 0) ticket = atomicAdd(&g.queue[xcd], 1);
-        do {
-        const long long item = x0 + it;
+    ticket_loop(g, (long long)g.ntiles * g.nbatch, tid, [&](const long long item) {
         const int b = (int)(item / g.ntiles);
         const int t = (int)(item - (long long)b * g.ntiles);
         int ii, jj;
         if (g.shape == 0) tri_decode(t, ii, jj);
         else { ii = t / g.mj; jj = t - ii * g.mj; }
         const int ti = g.i0 + ii, tj = g.j0 + jj;
-        if (g.sym && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) break;   // the diagonal-tile kernel's
+        if (g.sym && ti == tj && !(g.short_rows > 0 && ti >= g.short_row0)) return;   // the diagonal-tile kernel's
         // sym == 3: the augmented tile was already updated (it rode with the diagonal item); panel product only
         const bool no_update = g.sym == 3 && g.short_rows > 0 && ti >= g.short_row0 && tj < g.short_row0;
         strip_item<WD>(g, b, ti, tj, no_update, nslab, lB, tid, lane, wave, li, lg, frow_b, loff, item);
-        } while (0);
-        if (tid == 0) s_ticket = ticket;
-        __syncthreads();
-        it = (long long)gx + s_ticket;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        __threadfence();
-        if (atomicAdd(&g.queue[8 + xcd], 1) == gx - 1) {
-            g.queue[xcd] = 0;
-            g.queue[8 + xcd] = 0;
-        }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------
-// Update of a diagonal tile INSIDE a panel, one wave's share: tile (td, td) -= sum_{kk in [g.k0, kd1)} A(td, kk) A(td, kk)^T,
-// lower triangle, 9 sub-tiles per wave, the augmented right-hand-side rows (MT row blocks) riding along — and the result left
-// as the PACKED LDS IMAGE the factorisation of diag_block.h works on, so that diag_update_potrf_kernel below goes from the
-// update to the Cholesky + inverse without the tile's HBM round trip.  Same arithmetic and summation order as
-// tile_syrk_diag_kernel (syrk_diag_wave below): the factor is bit-identical to the two-launch form.
-// (The round-4 experiment that chained this INTO the strip kernel's launch — one launch per column, measured slower at every
-// size — lives in profiles/r04_chain_experiment.patch, not in the sources.)
+// Update of ONE diagonal tile, one wave's share:  C(t, t) -= sum_kk A(t, kk) A(t, kk)^T over the nslab slabs (nslab / 8 tile
+// columns) from tile column g.k0, lower triangle only.  Wave W owns sub-tile rows W and 7 - W of the 8 x 8 grid of 16 x 16
+// sub-tiles: (W, 0..W) and (7 - W, 0..7 - W), 9 sub-tiles, 9 accumulators — 36 of the 64 sub-tile products of a full tile.  Both
+// MFMA operands come from the one staged A slab.  The strictly-upper sub-tiles of C are never touched (the diagonal-block code
+// reads the lower triangle only).
+//
+// MT > 0: the augmented (right-hand-side) row of the column rides along,
+//     C(aug, t) -= sum_kk A(aug, kk) A(t, kk)^T      for the first 16 MT rows of the tile (aug = g.short_row0),
+// because this update streams exactly the operand that one needs (A(t, kk)): as work items of the general kernel the
+// augmented-row tiles cost 3.9 % of its time (measured, GPSLC_GEMM_DIAG=3) for 0.1 % of the flops — each one streams two full
+// operand panels for two live rows.  Wave W takes column blocks W and 7 - W of those rows.
+//
+// The accumulators go back to the caller, which decides where the result lives: a0c[cb] / a1c[cb] = sub-tiles (W, cb) /
+// (7 - W, cb), ag[m][0 / 1] = row block m, column blocks W / 7 - W of the augmented tile; [v] of lane (li, lg) = element
+// (li, lg + 4 v) of the 16 x 16 block.  This is the ONE copy of the MFMA order — per output element ascending k — so the in-panel
+// form (syrk_chain_wave: packed LDS image) and the trailing-update form (syrk_diag_wave: back to HBM) give the same bits.
+// The four waves of a workgroup call it together with the same (b, t, nslab): they share the staging and its barriers.
+// smem: two slabs of A(t, .) and, MT > 0, two of the augmented rows (DG_LDS_BYTES); dead after the return (last barrier).
 // ---------------------------------------------------------------------------------------
-template <int W, int MT, bool WT = false>
-__device__ __forceinline__ void syrk_chain_wave(const GemmArgs& g, const int b, const int td, const int kd1, double* smem,
-                                                const int tid, const int lane) {
-    // diagonal tile (td, td) -= sum_{kk in [g.k0, kd1)} A(td, kk) A(td, kk)^T -> packed LDS image (smem); augmented tile
-    // (g.short_row0, td) likewise -> HBM.  Layouts and MFMA order: syrk_diag_wave below.
+template <int W, int MT>
+__device__ __forceinline__ void diag_tile_update(const GemmArgs& g, const int b, const int t, const int nslab, double* smem,
+                                                 const int tid, const int lane, d4 (&a0c)[W + 1], d4 (&a1c)[8 - W],
+                                                 d4 (&ag)[MT > 0 ? MT : 1][2]) {
     double* lA = smem;
-    double* lG = smem + 2 * OPER_LDS;
-    int loff[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int q = tid + 256 * u;
-        loff[u] = (q >> 6) * LROW + (q & 63) * 2;
-    }
-    const bool glive = MT > 0 && tid < 128 * MT;     // one row pair of the augmented slab per thread
-    const int nslab = (kd1 - g.k0) * (GP_TS / KS);
+    double* lG = smem + 2 * OPER_LDS;      // augmented-row slabs (MT > 0)
     const int li = lane & 15, lg = lane >> 4;
     const int fbase = lg * LROW + li;
-    double* __restrict__ Cd = tref_tile(g.C, b, td, td) + (lg * GP_TS + li);
-    double* __restrict__ Cg = MT > 0 ? tref_tile(g.C, b, g.short_row0, td) + (lg * GP_TS + li) : nullptr;
-
-    d4 a0c[W + 1], a1c[8 - W];     // sub-tiles (W, cb) and (7 - W, cb)
+    const double* __restrict__ Cd = tref_tile(g.C, b, t, t) + (lg * GP_TS + li);
 #pragma unroll
     for (int cb = 0; cb <= W; ++cb)
 #pragma unroll
@@ -739,8 +726,8 @@ __device__ __forceinline__ void syrk_chain_wave(const GemmArgs& g, const int b, 
     for (int cb = 0; cb < 8 - W; ++cb)
 #pragma unroll
         for (int v = 0; v < 4; ++v) a1c[cb][v] = Cd[(16 * cb + 4 * v) * GP_TS + 16 * (7 - W)];
-    d4 ag[MT > 0 ? MT : 1][2];
     if (MT > 0) {
+        const double* __restrict__ Cg = tref_tile(g.C, b, g.short_row0, t) + (lg * GP_TS + li);
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -749,17 +736,21 @@ __device__ __forceinline__ void syrk_chain_wave(const GemmArgs& g, const int b, 
                 ag[m][1][v] = Cg[(16 * (7 - W) + 4 * v) * GP_TS + 16 * m];
             }
     }
+    if (nslab <= 0) return;      // an empty K range leaves the tile as loaded (no launcher asks for one)
     // Staging: SYRK_PF register sets, loads SYRK_PF slabs ahead of the MFMAs.  A slab of this update is 9 MFMAs per wave and
     // k-step — 576 pipe clocks — so its loads need more than one slab time to arrive; the barriers order LDS traffic only
     // (__syncthreads() waits vmcnt(0): with it the "two slabs ahead" of round 3 was in fact less than one).  The augmented
-    // rows' loads travel with their slab (vmcnt counts in order), one row pair per thread.  Measured (profiles/
-    // r04_ab_experiments.md §12): 2 sets + LDS-only barriers +1.1..2.0 % at N = 1024, 4 sets no better, 8 sets spill.
+    // rows' loads travel with their slab (vmcnt counts in order).  Measured (profiles/r04_ab_experiments.md §12): 2 sets +
+    // LDS-only barriers +1.1..2.0 % at N = 1024, 4 sets no better, 8 sets spill.
+    int loff[4];
+    stage_offsets(tid, loff);
     // augmented slab: 16 k-columns x 16 MT live rows = 128 MT row pairs, ONE per thread (tid < 128 MT)
-    d2 rs[SYRK_PF][4], rgs[MT > 0 ? SYRK_PF : 1];
+    const bool glive = MT > 0 && tid < 128 * MT;
     const int gcol = tid / (8 * (MT > 0 ? MT : 1)), grp = tid % (8 * (MT > 0 ? MT : 1));
+    d2 rs[SYRK_PF][4], rgs[MT > 0 ? SYRK_PF : 1];
     auto gload = [&](int s, int set) {
         const int kk = g.k0 + (s >> 3);
-        const double* pa = tref_tile(g.A, b, td, kk) + (s & 7) * (KS * GP_TS);
+        const double* pa = tref_tile(g.A, b, t, kk) + (s & 7) * (KS * GP_TS);
 #pragma unroll
         for (int u = 0; u < 4; ++u) rs[set][u] = *reinterpret_cast<const d2*>(pa + (tid + 256 * u) * 2);
         if (MT > 0 && glive) {
@@ -773,7 +764,6 @@ __device__ __forceinline__ void syrk_chain_wave(const GemmArgs& g, const int b, 
         if (MT > 0 && glive)
             *reinterpret_cast<d2*>(lG + buf * OPER_LDS + gcol * LROW + 2 * grp) = rgs[MT > 0 ? set : 0];
     };
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     auto compute = [&](int buf) {
         const double* pa = lA + buf * OPER_LDS + fbase;
         const double* pg = lG + buf * OPER_LDS + fbase;
@@ -801,29 +791,44 @@ __device__ __forceinline__ void syrk_chain_wave(const GemmArgs& g, const int b, 
 #pragma unroll
     for (int u = 0; u < SYRK_PF; ++u) gload(u, u);          // nslab is a multiple of 8 >= SYRK_PF
     lstore(0, 0);
-    lds_barrier();
+    KLOOP_BARRIER;
     for (int s = 0; s < nslab; s += SYRK_PF) {
 #pragma unroll
         for (int u = 0; u < SYRK_PF; ++u) {                  // slab s + u sits in LDS buffer u & 1
             if (s + u + SYRK_PF < nslab) gload(s + u + SYRK_PF, u);      // set u went to LDS one step ago
             compute(u & 1);
             if (s + u + 1 < nslab) lstore((u + 1) & 1, (u + 1) % SYRK_PF);
-            lds_barrier();
+            KLOOP_BARRIER;
         }
     }
-    {
-        // the staging buffers are dead (last barrier): the updated lower blocks become the packed image of the factorisation
-        // — block (i, j) at ((i (i + 1) / 2 + j) << 8), element (r, c) at c * 16 + r; acc[v] = element (li, lg + 4 v)
+}
+
+// ---------------------------------------------------------------------------------------
+// Update of a diagonal tile INSIDE a panel, one wave's share: tile (td, td) over the tile columns [g.k0, kd1) with the augmented
+// rows (MT row blocks) riding along -> HBM (WT: write-through, the task launch's hand-off) — and the tile itself left as the
+// PACKED LDS IMAGE the factorisation of diag_block.h works on, so that diag_update_potrf_kernel and the diagonal tasks of
+// potrf_tasks_kernel go from the update to the Cholesky + inverse without the tile's HBM round trip.
+// (The round-4 experiment that chained this INTO the strip kernel's launch — one launch per column, measured slower at every
+// size — lives in profiles/r04_chain_experiment.patch, not in the sources.)
+// ---------------------------------------------------------------------------------------
+template <int W, int MT, bool WT = false>
+__device__ __forceinline__ void syrk_chain_wave(const GemmArgs& g, const int b, const int td, const int kd1, double* smem,
+                                                const int tid, const int lane) {
+    d4 a0c[W + 1], a1c[8 - W], ag[MT > 0 ? MT : 1][2];
+    diag_tile_update<W, MT>(g, b, td, (kd1 - g.k0) * (GP_TS / KS), smem, tid, lane, a0c, a1c, ag);
+    const int li = lane & 15, lg = lane >> 4;
+    // the updated lower blocks become the packed image of the factorisation — block (i, j) at ((i (i + 1) / 2 + j) << 8),
+    // element (r, c) at c * 16 + r
 #pragma unroll
-        for (int cb = 0; cb <= W; ++cb)
+    for (int cb = 0; cb <= W; ++cb)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) smem[(((W * (W + 1)) / 2 + cb) << 8) + (lg + 4 * v) * 16 + li] = a0c[cb][v];
+        for (int v = 0; v < 4; ++v) smem[(((W * (W + 1)) / 2 + cb) << 8) + (lg + 4 * v) * 16 + li] = a0c[cb][v];
 #pragma unroll
-        for (int cb = 0; cb < 8 - W; ++cb)
+    for (int cb = 0; cb < 8 - W; ++cb)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) smem[((((7 - W) * (8 - W)) / 2 + cb) << 8) + (lg + 4 * v) * 16 + li] = a1c[cb][v];
-    }
+        for (int v = 0; v < 4; ++v) smem[((((7 - W) * (8 - W)) / 2 + cb) << 8) + (lg + 4 * v) * 16 + li] = a1c[cb][v];
     if (MT > 0) {
+        double* __restrict__ Cg = tref_tile(g.C, b, g.short_row0, td) + (lg * GP_TS + li);
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -857,6 +862,19 @@ __global__ __launch_bounds__(256, 2) void diag_update_potrf_kernel(GemmArgs g) {
                            tid, true);
 }
 
+// grid of a persistent launch over `work` items: 2 workgroups per CU (the kernels' launch bounds), never more than items
+static unsigned persistent_grid(long long work) {
+    const int slots = 2 * device_cus();
+    return (unsigned)(work < slots ? work : slots);
+}
+// mt = 16-row blocks of the augmented row that ride with the diagonal tiles (0, 1 or 2) -> launch(integral_constant<int, MT>)
+template <class F>
+static void dispatch_mt(int mt, F&& launch) {
+    if (mt == 0) launch(std::integral_constant<int, 0>());
+    else if (mt == 1) launch(std::integral_constant<int, 1>());
+    else launch(std::integral_constant<int, 2>());
+}
+
 template <int MT>
 static void launch_diag_update_potrf_t(const GemmArgs& g, hipStream_t st) {
     static DeviceOnce once;
@@ -869,10 +887,8 @@ static void launch_diag_update_potrf_t(const GemmArgs& g, hipStream_t st) {
 // info_base as for launch_diag, short_row0 / short_rows = the augmented row when carry_aug
 void launch_diag_update_potrf(const GemmArgs& g, int carry_aug, hipStream_t st) {
     if (g.nbatch <= 0) return;
-    const int mt = carry_aug ? (g.short_rows + 15) / 16 : 0;
-    if (mt == 0) launch_diag_update_potrf_t<0>(g, st);
-    else if (mt == 1) launch_diag_update_potrf_t<1>(g, st);
-    else launch_diag_update_potrf_t<2>(g, st);
+    dispatch_mt(carry_aug ? (g.short_rows + 15) / 16 : 0,
+                [&](auto mt) { launch_diag_update_potrf_t<decltype(mt)::value>(g, st); });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1028,11 +1044,7 @@ __global__ __launch_bounds__(256, 2) void potrf_tasks_kernel(PotrfTaskArgs a) {
         if ((!is_diag && !is_back) || diag_then_strip) {
             const int li = lane & 15, lg = lane >> 4;
             int loff[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int q = tid + 256 * u;
-                loff[u] = (q >> 6) * LROW + (q & 63) * 2;
-            }
+            stage_offsets(tid, loff);
             GemmArgs gl = a.g;
             gl.k1 = k;
             gl.fk = k;
@@ -1099,144 +1111,36 @@ static void launch_potrf_tasks_t(const PotrfTaskArgs& a, unsigned grid, hipStrea
 // row of the task list, strip(nt, k) with its own column update over the live rows, as in the per-column launches
 void launch_potrf_tasks(const PotrfTaskArgs& a, long long ntasks, int mt, hipStream_t st) {
     if (ntasks <= 0) return;
-    const int slots = 2 * device_cus();
-    const unsigned grid = (unsigned)(ntasks < slots ? ntasks : slots);
+    const unsigned grid = persistent_grid(ntasks);
 #ifdef GPSLC_DIAG
     if (a.fence_mode & 2) {      // measurement build, GPSLC_TASK_FENCE bit 1: plain / nt payload stores + an agent-scope release fence
-        if (mt == 0) launch_potrf_tasks_t<0, false>(a, grid, st);
-        else if (mt <= 1) launch_potrf_tasks_t<1, false>(a, grid, st);
-        else launch_potrf_tasks_t<2, false>(a, grid, st);
+        dispatch_mt(mt, [&](auto m) { launch_potrf_tasks_t<decltype(m)::value, false>(a, grid, st); });
         return;
     }
 #endif
-    if (mt == 0) launch_potrf_tasks_t<0, true>(a, grid, st);
-    else if (mt <= 1) launch_potrf_tasks_t<1, true>(a, grid, st);
-    else launch_potrf_tasks_t<2, true>(a, grid, st);
+    dispatch_mt(mt, [&](auto m) { launch_potrf_tasks_t<decltype(m)::value, true>(a, grid, st); });
 }
 
 // ---------------------------------------------------------------------------------------
-// Diagonal tiles of a symmetric update:  C(t, t) -= sum_kk A(t, kk) A(t, kk)^T, lower triangle only.
-// Work item = (diagonal tile t in [0, mi), batch element).  Wave w owns sub-tile rows w and 7 - w of the
-// 8 x 8 grid of 16 x 16 sub-tiles: (w, 0..w) and (7 - w, 0..7 - w), 9 sub-tiles, 9 accumulators.  Both MFMA
-// operands come from the one staged A slab.  The strictly-upper sub-tiles of C are never touched (the
-// diagonal-block kernel reads the lower triangle only).
-//
-// MT > 0: the item also carries the augmented (right-hand-side) row of its column,
-//     C(aug, t) -= sum_kk A(aug, kk) A(t, kk)^T      for the first 16 MT rows of the tile,
-// because it streams exactly the operand that update needs (A(t, kk)): as work items of the general kernel the
-// augmented-row tiles cost 3.9 % of its time (measured, GPSLC_GEMM_DIAG=3) for 0.1 % of the flops — each one
-// streams two full operand panels for two live rows.  Wave w takes column blocks w and 7 - w of those rows.
+// Diagonal tiles of a symmetric (trailing) update: diag_tile_update above on every full-size diagonal tile of the launch, result
+// back to HBM.  Work item = (diagonal tile t in [0, mi), batch element), XCD-aware split as in the general kernel but a static
+// stride inside the XCD's run: the items cost the same, so there is no ticket queue.  MT > 0: the items also carry the
+// augmented-row tiles (short_row0, i0 + t).
 // ---------------------------------------------------------------------------------------
 #define DG_LDS_BYTES(MT) ((2 * OPER_LDS + ((MT) > 0 ? 2 * OPER_LDS : 0)) * 8)
 
 template <int W, int MT>
-__device__ __forceinline__ void syrk_diag_wave(const GemmArgs& g, double* lA, int tid, int lane) {
-    double* lG = lA + 2 * OPER_LDS;      // augmented-row slabs (MT > 0)
-    const long long Wk = (long long)g.mi * g.nbatch;
-    const int G = gridDim.x;
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int gx = (G >> 3) + (xcd < (G & 7) ? 1 : 0);
-    const long long wq = Wk >> 3, wrm = Wk & 7;
-    const long long x0 = xcd * wq + (xcd < wrm ? xcd : wrm);
-    const long long xc = wq + (xcd < wrm ? 1 : 0);
-    int loff[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int q = tid + 256 * u;
-        loff[u] = (q >> 6) * LROW + (q & 63) * 2;
-    }
-    // rows [0, 16 MT) of an augmented slab: the chunks of this thread whose row pair is live
-    const bool glive = MT > 0 && tid < 128 * MT;     // one row pair of the augmented slab per thread
+__device__ __forceinline__ void syrk_diag_wave(const GemmArgs& g, double* smem, int tid, int lane) {
+    const XcdSplit x = xcd_split((long long)g.mi * g.nbatch);
     const int nslab = (g.k1 - g.k0) * (GP_TS / KS);
-    const int fbase = (lane >> 4) * LROW + (lane & 15);
-
-    for (long long it = local; it < xc; it += gx) {
-        const long long item = x0 + it;
+    const int li = lane & 15, lg = lane >> 4;
+    for (long long it = x.local; it < x.xc; it += x.gx) {
+        const long long item = x.x0 + it;
         const int b = (int)(item / g.mi);
-        const int t = (int)(item - (long long)b * g.mi);
-        const int ti = g.i0 + t;
-        double* __restrict__ Cd = tref_tile(g.C, b, ti, ti) + ((lane >> 4) * GP_TS + (lane & 15));
-        double* __restrict__ Cg = MT > 0 ? tref_tile(g.C, b, g.short_row0, ti) + ((lane >> 4) * GP_TS + (lane & 15)) : nullptr;
-
-        d4 a0c[W + 1], a1c[8 - W];     // sub-tiles (W, cb) and (7 - W, cb)
-#pragma unroll
-        for (int cb = 0; cb <= W; ++cb)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) a0c[cb][v] = Cd[(16 * cb + 4 * v) * GP_TS + 16 * W];
-#pragma unroll
-        for (int cb = 0; cb < 8 - W; ++cb)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) a1c[cb][v] = Cd[(16 * cb + 4 * v) * GP_TS + 16 * (7 - W)];
-        d4 ag[MT > 0 ? MT : 1][2];     // augmented rows: row block m, column blocks W (0) and 7 - W (1)
-        if (MT > 0) {
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    ag[m][0][v] = Cg[(16 * W + 4 * v) * GP_TS + 16 * m];
-                    ag[m][1][v] = Cg[(16 * (7 - W) + 4 * v) * GP_TS + 16 * m];
-                }
-        }
-
-        // staging as in syrk_chain_wave above: SYRK_PF register sets, LDS-only barriers
-        d2 rs[SYRK_PF][4], rgs[MT > 0 ? SYRK_PF : 1];
-        const int gcol = tid / (8 * (MT > 0 ? MT : 1)), grp = tid % (8 * (MT > 0 ? MT : 1));
-        auto gload = [&](int s, int set) {
-            const int kk = g.k0 + (s >> 3);
-            const double* pa = tref_tile(g.A, b, ti, kk) + (s & 7) * (KS * GP_TS);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) rs[set][u] = *reinterpret_cast<const d2*>(pa + (tid + 256 * u) * 2);
-            if (MT > 0 && glive) {
-                const double* pg = tref_tile(g.A, b, g.short_row0, kk) + (s & 7) * (KS * GP_TS);
-                rgs[MT > 0 ? set : 0] = *reinterpret_cast<const d2*>(pg + gcol * GP_TS + 2 * grp);
-            }
-        };
-        auto lstore = [&](int buf, int set) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) *reinterpret_cast<d2*>(lA + buf * OPER_LDS + loff[u]) = rs[set][u];
-            if (MT > 0 && glive)
-                *reinterpret_cast<d2*>(lG + buf * OPER_LDS + gcol * LROW + 2 * grp) = rgs[MT > 0 ? set : 0];
-        };
-        auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-        auto compute = [&](int buf) {
-            const double* pa = lA + buf * OPER_LDS + fbase;
-            const double* pg = lG + buf * OPER_LDS + fbase;
-#pragma unroll
-            for (int ks = 0; ks < KS / 4; ++ks) {
-                double bf[8 - W];
-#pragma unroll
-                for (int cb = 0; cb < 8 - W; ++cb) bf[cb] = pa[ks * 4 * LROW + 16 * cb];
-                const double r0 = pa[ks * 4 * LROW + 16 * W];
-                const double r1 = pa[ks * 4 * LROW + 16 * (7 - W)];
-#pragma unroll
-                for (int cb = 0; cb <= W; ++cb) a0c[cb] = mfma_step<1>(bf[cb], r0, a0c[cb]);
-#pragma unroll
-                for (int cb = 0; cb < 8 - W; ++cb) a1c[cb] = mfma_step<1>(bf[cb], r1, a1c[cb]);
-                if (MT > 0) {
-#pragma unroll
-                    for (int m = 0; m < MT; ++m) {
-                        const double gf = pg[ks * 4 * LROW + 16 * m];
-                        ag[m][0] = mfma_step<1>(bf[W], gf, ag[m][0]);
-                        ag[m][1] = mfma_step<1>(bf[7 - W], gf, ag[m][1]);
-                    }
-                }
-            }
-        };
-        if (nslab > 0) {
-#pragma unroll
-            for (int u = 0; u < SYRK_PF; ++u) gload(u, u);          // nslab is a multiple of 8 >= SYRK_PF
-            lstore(0, 0);
-            lds_barrier();
-            for (int s = 0; s < nslab; s += SYRK_PF) {
-#pragma unroll
-                for (int u = 0; u < SYRK_PF; ++u) {
-                    if (s + u + SYRK_PF < nslab) gload(s + u + SYRK_PF, u);
-                    compute(u & 1);
-                    if (s + u + 1 < nslab) lstore((u + 1) & 1, (u + 1) % SYRK_PF);
-                    lds_barrier();
-                }
-            }
-        }
+        const int ti = g.i0 + (int)(item - (long long)b * g.mi);
+        d4 a0c[W + 1], a1c[8 - W], ag[MT > 0 ? MT : 1][2];
+        diag_tile_update<W, MT>(g, b, ti, nslab, smem, tid, lane, a0c, a1c, ag);
+        double* __restrict__ Cd = tref_tile(g.C, b, ti, ti) + (lg * GP_TS + li);
 #pragma unroll
         for (int cb = 0; cb <= W; ++cb)
 #pragma unroll
@@ -1246,6 +1150,7 @@ __device__ __forceinline__ void syrk_diag_wave(const GemmArgs& g, double* lA, in
 #pragma unroll
             for (int v = 0; v < 4; ++v) Cd[(16 * cb + 4 * v) * GP_TS + 16 * (7 - W)] = a1c[cb][v];
         if (MT > 0) {
+            double* __restrict__ Cg = tref_tile(g.C, b, g.short_row0, ti) + (lg * GP_TS + li);
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -1281,13 +1186,9 @@ static void launch_syrk_diag_t(const GemmArgs& g, unsigned grid, hipStream_t st)
 // carry_aug: the items also update the augmented-row tiles (short_row0, i0 + t) (live rows g.short_rows).
 void launch_syrk_diag(const GemmArgs& g, int carry_aug, hipStream_t st) {
     if (g.mi <= 0 || g.nbatch <= 0 || g.k1 <= g.k0) return;
-    const int slots = 2 * device_cus();
-    const long long Wk = (long long)g.mi * g.nbatch;
-    const unsigned grid = (unsigned)(Wk < slots ? Wk : slots);
-    const int mt = carry_aug ? (g.short_rows + 15) / 16 : 0;   // callers pass carry_aug only for mt <= 2
-    if (mt == 0) launch_syrk_diag_t<0>(g, grid, st);
-    else if (mt == 1) launch_syrk_diag_t<1>(g, grid, st);
-    else launch_syrk_diag_t<2>(g, grid, st);
+    const unsigned grid = persistent_grid((long long)g.mi * g.nbatch);
+    dispatch_mt(carry_aug ? (g.short_rows + 15) / 16 : 0,      // callers pass carry_aug only for up to 32 live rows
+                [&](auto mt) { launch_syrk_diag_t<decltype(mt)::value>(g, grid, st); });
 }
 
 template <int ACC, int DIAG>
@@ -1299,9 +1200,7 @@ static void launch_one(const GemmArgs& g, unsigned grid, hipStream_t st) {
 
 void launch_tile_gemm(const GemmArgs& g, hipStream_t st) {
     if (g.ntiles <= 0 || g.nbatch <= 0) return;
-    const int slots = 2 * device_cus();   // 2 workgroups per CU (227 VGPRs, 72 KiB LDS each)
-    const long long W = (long long)g.ntiles * g.nbatch;
-    const unsigned grid = (unsigned)(W < slots ? W : slots);
+    const unsigned grid = persistent_grid((long long)g.ntiles * g.nbatch);
 #ifdef GPSLC_DIAG
     if (g.diag_skip == 1) {        // timing-only diagnostics (GPSLC_GEMM_DIAG), separate instantiations
         if (g.accumulate) launch_one<1, 1>(g, grid, st); else launch_one<0, 1>(g, grid, st);

@@ -19,7 +19,6 @@
 #include "gpslc_internal.h"
 #include "gp_math.h"
 
-typedef double d4w __attribute__((ext_vector_type(4)));
 #define WS_CC 64          // columns per staged chunk
 #define WS_RLD 80         // padded row of the W chunk (doubles): conflict-free ds_read_b64 across the four k rows
 #define WS_NL 64          // weight columns per pass
@@ -69,13 +68,13 @@ __global__ __launch_bounds__(256, 2) void wsum_mfma_kernel(WsumArgs a) {
     for (int g0 = 0; g0 < G; g0 += WS_NL) {
         const int ng = min(WS_NL, G - g0);
         const int nq = (ng + 15) >> 4;          // live 16-column sub-tiles of this pass (wave-uniform)
-        d4w accB[2][4], accK[WK ? 2 : 1][WK ? 4 : 1];
+        d4 accB[2][4], accK[WK ? 2 : 1][WK ? 4 : 1];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                accB[m][q] = (d4w){0.0, 0.0, 0.0, 0.0};
-                if constexpr (WK) accK[m][q] = (d4w){0.0, 0.0, 0.0, 0.0};
+                accB[m][q] = (d4){0.0, 0.0, 0.0, 0.0};
+                if constexpr (WK) accK[m][q] = (d4){0.0, 0.0, 0.0, 0.0};
             }
         for (int c0 = 0; c0 < Np; c0 += WS_CC) {
             __syncthreads();

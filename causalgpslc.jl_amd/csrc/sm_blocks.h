@@ -4,7 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-typedef double d4 __attribute__((ext_vector_type(4)));
+#include "gpslc_internal.h"     // d4, d2
 
 #define SB 16
 #define SM_THREADS 512
@@ -51,7 +51,6 @@ __device__ __forceinline__ double sm_rsqrt(double d) {
 // lane's earlier loads for the lanes that did not store).
 __device__ __forceinline__ void sm_factor_rows_lds(double (&r)[SB], int li, int lane, int base, int& bad, double& lcc,
                                                    double* bc /* this wave's 16-double LDS line, 16-byte aligned */) {
-    typedef double d2v __attribute__((ext_vector_type(2)));
     double dsave = 1.0, ysave = 1.0;
     double d = sm_readlane(r[0], 0);
     double y = sm_rsqrt(d);
@@ -88,7 +87,7 @@ __device__ __forceinline__ void sm_factor_rows_lds(double (&r)[SB], int li, int 
         if (c + 3 < SB) {                                        // fetch this pivot's far multipliers: j >= c + 3
 #pragma unroll
             for (int j0 = (c + 3) & ~1; j0 < SB; j0 += 2) {
-                const d2v m = *reinterpret_cast<const d2v*>(bc + j0);
+                const d2 m = *reinterpret_cast<const d2*>(bc + j0);
                 mp[j0] = m[0];
                 mp[j0 + 1] = m[1];
             }

@@ -81,6 +81,29 @@ def test_task_launch_with_a_level_sweep_of_more_than_32_right_hand_sides(gp, n, 
         _same(x, y)
 
 
+@pytest.mark.parametrize("n", [400, 512])
+@pytest.mark.parametrize("L", [1, 20, 40])
+def test_narrow_panels_at_four_tiles_equal_the_task_launch_bit_for_bit(gp, n, L):
+    """The smallest shapes that reach every instantiation of the trailing updates' diagonal kernel: nt = 4 (n = 400: the last tile
+    short, n = 512: four full tiles) with panels of 1, 2 and 3 tile columns, so that the diagonal tiles of columns 1 to 3 are
+    updated by tile_syrk_diag_kernel over K ranges of 1, 2 and 3 tiles, split across several launches; L = 1 / 20 / 40: one and
+    two blocks of augmented rows riding along (MT = 1, 2), and more than 32 right-hand sides (MT = 0, the augmented row an
+    ordinary tile row).  The task launch updates the same tiles in one panel through syrk_chain_wave — the same MFMA chain per
+    tile, ascending k: bit-identical, MeanITE included."""
+    c = cases.make_case(n, "UX", False, S=3, seed=n + L)
+    doT = np.linspace(-0.5, 0.7, L)
+    out = []
+    for tiles, panel in ((32, 0), (0, 1), (0, 2), (0, 3)):
+        g = cases.gpslc_object(gp, c)
+        g.ctx().set_task_schedule(2, tiles, 1, 0)
+        if panel:
+            g.ctx().set_tuning(0, panel, 0)
+        out.append(gp.predict(g, doT, want_mean_ite=True))
+    for other in out[1:]:
+        for x, y in zip(out[0], other):
+            _same(x, y)
+
+
 @pytest.mark.parametrize("group", [1, 3, 64])
 def test_task_order_group_size_and_chunking_do_not_change_results(gp, group):
     """Group size 1 puts a task right behind its producer in the queue (consumers really wait on the progress words);
