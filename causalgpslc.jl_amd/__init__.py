@@ -9,6 +9,7 @@ from .api import (  # noqa: F401
     Context, GPSLCObject, HyperParameters, PREDICTION_COVARIANCE_NOISE,
     rbfKernelLog, rbfKernelLogScalar, logit, expit, processCov, likelihoodDistribution, extractParameters, conditionalITE, ITEDistributions, ITEsamples, conditionalSATE,
     SATEDistributions, SATEsamples, sampleITE, sampleSATE, predictCounterfactualEffects, groupWeights,
+    effectCurve, sampleEffectCurve, curveSamples,
     summarizeEstimates, yLogpdf, gpLogpdf, nodesLogpdf, nodesDraw, mvnLogpdf, mvnDraw, predict, doTRange, getN, getNX, getNU, getNumPosteriorSamples,
 )
 from . import synth  # noqa: F401

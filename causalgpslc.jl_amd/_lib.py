@@ -79,6 +79,8 @@ SIGNATURES = {
                                          C.c_int32, C.c_uint64, _D, _D, _D, _D, _D]),
     "gpslc_predict_weighted": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, C.c_int32, _D, _D, C.c_int32, _D,
                                          C.c_double, C.c_int32, C.c_uint64, _D, _D, _D, _D, _D]),
+    "gpslc_predict_curve": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, C.c_int32, _D, _D, C.c_int32, _D,
+                                      C.c_double, C.c_int32, C.c_uint64, _D, _D, _D, _D, _D, _D]),
     "gpslc_shard_range": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),
     "gpslc_ite_distributions": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, C.c_double,
                                           C.c_double, _D, _D]),
@@ -93,6 +95,7 @@ SIGNATURES = {
     "gpslc_summarize": (C.c_int, [C.c_void_p, _D, C.c_int64, C.c_int64, C.c_double, _D, _D, _D]),
     "gpslc_summarize_dev": (C.c_int, [C.c_void_p, _D, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, _D, _D, _D]),
     "gpslc_sate_samples": (C.c_int, [_D, _D, C.c_int64, C.c_int32, C.c_uint64, _D, _D]),
+    "gpslc_curve_samples": (C.c_int, [_D, _D, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _D, _D]),
     "gpslc_last_info": (C.c_int, [C.c_void_p, c_int32_p, C.c_int64]),
     "gpslc_profile_reset": (C.c_int, [C.c_void_p]),
     "gpslc_profile_get": (C.c_int, [C.c_void_p, c_int64_p, c_double_p, c_double_p]),

@@ -559,6 +559,89 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
     return ms, vs, mi
 
 
+def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_ite=False, spp=0, z=None, seed=0,
+                   want_draws=False, want_cov=True, devices=None):
+    """gpslc_predict_curve: (meanW (S, L, G), varW (S, L, G), covW (S, L, L, G) or None, MeanITE or None, draws or None) and
+    whether ``weights`` was a single vector.  ``weights=None`` is 1/n for everybody."""
+    n, S = g.getN(), g.getNumPosteriorSamples()
+    doTs = np.asarray(doTs, dtype=np.float64)
+    if doTs.ndim > 1:
+        raise ValueError("an effect curve needs scalar levels: per-individual intervention vectors are not supported")
+    if devices is not None:
+        raise NotImplementedError("effect curves are not sharded over devices: call without devices=")
+    Wm, wvec = (np.full((1, n), 1.0 / n), True) if weights is None else _weights(weights, n)
+    doTs = np.ascontiguousarray(np.atleast_1d(doTs))
+    L, G = doTs.shape[0], Wm.shape[0]
+    base = None if baseline is None else _baseline(baseline, L)
+    ctx = g.ctx()
+    mw = np.empty((S, L, G), order="F")
+    vw = np.empty((S, L, G), order="F")
+    cw = np.empty((S, L, L, G), order="F") if want_cov else None
+    mi = np.empty((n, S, L), order="F") if want_mean_ite else None
+    dr = np.empty((L, n, S * spp), order="F") if want_draws else None
+    zz = None
+    if z is not None:
+        zz = _f(z)
+        if zz.shape != (n, spp, S, L):
+            raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
+    st = ctx.lib.gpslc_predict_curve(ctx.h, S, *g._params(), L, _p(doTs), _p(base), G, _p(Wm),
+                                     float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
+                                     _p(mw), _p(vw), _p(cw), _p(mi), _p(dr))
+    ctx.check(st)
+    return (mw, vw, cw, mi, dr), wvec
+
+
+def effectCurve(g: GPSLCObject, doTs, baseline=None, weights=None, devices=None):
+    """The weighted effect over a sweep of L scalar levels as ONE Gaussian: mean (S, L[, G]) and the joint covariance
+    cov (S, L, L[, G]) of tau_l = w' ITE_l across the levels, per posterior sample (gpslc_predict_curve).  The diagonal of
+    ``cov`` is the ``var`` of ``predict`` to the bits; the off-diagonal blocks are what simultaneous bands, comparisons of
+    two levels and functionals of the curve (slope, maximum, area) need.  ``weights=None`` means 1/n, the SATE curve; a
+    length-n vector or a (G, n) array as in ``predict`` (a (G, n) array adds the trailing group axis); ``baseline`` as in
+    ``predict``.  Scalar levels and one GPU only."""
+    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices)
+    if wvec:
+        return mw[:, :, 0], cw[:, :, :, 0]
+    return mw, cw
+
+
+def curveSamples(mean, cov, samplesPerPosterior, z=None, seed=0):
+    """Joint draws of curves from ``effectCurve``'s (mean (S, L, G), cov (S, L, L, G)): (L, spp, S, G), draw d of sample s and
+    group g at [:, d, s, g] (gpslc_curve_samples: pivoted Cholesky per block, semi-definite blocks allowed).  ``z``: (L, spp,
+    S, G) standard normals, else the library's Philox stream ``seed``."""
+    lib = _lib.load()
+    m, c = _f(mean), _f(cov)
+    if m.ndim != 3 or c.shape != (m.shape[0], m.shape[1], m.shape[1], m.shape[2]):
+        raise ValueError(f"mean must be (S, L, G) and cov (S, L, L, G), got {m.shape} and {c.shape}")
+    S, L, G = m.shape
+    spp = int(samplesPerPosterior)
+    zz = None
+    if z is not None:
+        zz = _f(z)
+        if zz.shape != (L, spp, S, G):
+            raise ValueError(f"z must be (L, spp, S, G) = {(L, spp, S, G)}, got {zz.shape}")
+    out = np.empty((L, spp, S, G), order="F")
+    st = lib.gpslc_curve_samples(_p(m), _p(c), S, L, G, spp, int(seed), _p(zz), _p(out))
+    if st != 0:
+        raise GPSLCError(st, "gpslc_curve_samples")
+    return out
+
+
+def sampleEffectCurve(g: GPSLCObject, doTs, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None, devices=None):
+    """Joint draws of the effect curve over the L levels: (L, S*spp), column order sample-outer / draw-inner as sampleSATE, or
+    (G, L, S*spp) for a (G, n) weight array.  Unlike sampleSATE per level, the L values of a column are ONE draw of the curve
+    (they share the Gaussian process).  ``z``: (L, spp, S[, G]) standard normals, else the Philox stream ``seed``."""
+    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices)
+    S, L, G = mw.shape
+    spp = int(samplesPerPosterior)
+    if z is not None:
+        z = np.asarray(z, dtype=np.float64)
+        if wvec and z.ndim == 3:
+            z = z[:, :, :, None]
+    dr = curveSamples(mw, cw, spp, z=z, seed=seed)                      # (L, spp, S, G)
+    out = np.transpose(dr.reshape(L, spp * S, G, order="F"), (2, 0, 1))     # column d + spp*s
+    return np.ascontiguousarray(out[0]) if wvec else np.ascontiguousarray(out)
+
+
 def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, baseline=None):
     """ITEsamples: n x (S*spp) draws, column order sample-outer / draw-inner (src/estimation.jl:95-109).
     Called as ITEsamples(g, doT, spp): the factor of CovITE + jitter is computed once per sample on the GPU.

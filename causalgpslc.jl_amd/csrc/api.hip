@@ -635,6 +635,9 @@ struct DrawsAndOutputs {
     uint64_t seed = 0;
     const double* z = nullptr;
     double *meanSATE = nullptr, *varSATE = nullptr, *meanITE = nullptr, *ite_draws = nullptr;
+    // weighted calls only: the joint covariance of the L levels per weight column, S x L x L x G — element
+    // (s, l, l', g) at s + S*(l + L*(l' + L*g)); needs varSATE, whose values are its diagonal
+    double* covW = nullptr;
 };
 
 struct PredictIO {
@@ -694,7 +697,7 @@ struct PredictShape {
     PredictShape(const gpslc_ctx* c, const PredictIO& io)
         : n((int)c->n), nt(c->nt), L(io.lv.L), R(io.lv.W ? io.lv.L * io.lv.G : io.lv.L), naug((R + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug),
           Np((long long)nt * GP_TS), tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2),
-          with_sums(io.out.meanSATE || io.out.varSATE), want_cov(io.CovITEs != nullptr), want_draws(io.out.ite_draws != nullptr),
+          with_sums(io.out.meanSATE || io.out.varSATE || io.out.covW), want_cov(io.CovITEs != nullptr), want_draws(io.out.ite_draws != nullptr),
           want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws) {}
 };
 
@@ -707,6 +710,7 @@ struct Chunk {
     double *tiles = nullptr, *inv = nullptr, *part = nullptr, *bsum = nullptr, *ksum = nullptr, *sumdelta = nullptr;
     double *vpart = nullptr, *zwork = nullptr, *znode = nullptr;
     double *bw = nullptr, *kw = nullptr, *wnorm2 = nullptr;      // weighted effects: B W, K W [nb][G][Np], w_g . w_g [nb][G]
+    double* cprior = nullptr;        // joint covariance across the levels: beta, kappa, gamma_l [nb][G][L + 2]
     // unit B: a sub-batch of gs_max samples x lc_max levels; W, CovITE, the draws' normals, level-sweep staging, failure codes
     int lc_max = 0, gs_max = 0;
     double *Wt = nullptr, *Ct = nullptr, *zgen = nullptr, *zt = nullptr, *dtmp = nullptr;
@@ -743,6 +747,7 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
         b.bw = take((size_t)io.lv.G * sh.Np);
         b.kw = io.lv.base ? b.bw : take((size_t)io.lv.G * sh.Np);
         b.wnorm2 = take(io.lv.G);
+        if (io.out.covW) b.cprior = take((size_t)io.lv.G * (L + 2));
     }
     if (io.lv.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
@@ -867,6 +872,14 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     ea.from_rows = epi_rows ? 1 : 0;
     if (io.lv.W) { ea.wnorm2 = ch.wnorm2; ea.wL = sh.L; }
     launch_epilogue(ea, nb, st);
+    if (io.out.covW) {      // the levels' joint covariance per weight column: Gram matrix of the rows the factorisation carried
+        CurveArgs ca{};
+        ca.M = ch.M; ca.n = n; ca.nt = nt; ca.L = sh.L; ca.G = io.lv.G; ca.s0 = s0; ca.S = io.post.S;
+        ca.T = c->dT; ca.tyLS = io.post.p.tyLS; ca.doT = io.lv.doT; ca.doT_base = io.lv.base;
+        ca.W = io.lv.W; ca.bw = ch.bw; ca.kw = ch.kw; ca.prior = ch.cprior;
+        ca.varW = io.out.varSATE; ca.covW = io.out.covW;
+        launch_curve(ca, nb, st);
+    }
     if (io.ndraw) {
         // one draw from N(0, A_s) per parameter set with the caller's normals: L_s z_s on the factor just computed — Gen's
         // mvnormal(zeros(n), cov) of an elliptical slice's auxiliary vector (src/inference.jl:225-232) and of the :logitT prior
@@ -992,6 +1005,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     if (io.lv.W && io.lv.vec) throw std::runtime_error("weights cannot be combined with vector levels");
     if (io.lv.W && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("weighted effects need an fp64 context");
     if (io.lv.W && io.lv.G < 1) throw std::runtime_error("weights without a weight column");
+    if (io.out.covW && (!io.lv.W || !io.out.varSATE)) throw std::runtime_error("the joint covariance needs weights and varW");
     if (io.lv.W && !io.out.meanSATE && !io.out.varSATE) { io.lv.W = nullptr; io.lv.G = 0; }      // nothing weighted is asked for
     if (io.nU < 0) io.nU = c->nU;
     if (io.nX < 0) io.nX = c->nX;
@@ -1694,7 +1708,9 @@ static int predict_host(gpslc_ctx* c, const PredictRequest& rq) {
             d.out.z = dz;
         }
         double* oms = d.out.meanSATE = o.meanSATE ? c->io.take<double>((size_t)S * LR) : nullptr;
-        double* ovs = d.out.varSATE = o.varSATE ? c->io.take<double>((size_t)S * LR) : nullptr;
+        // the joint covariance takes its diagonal from the device's varW, asked for or not
+        double* ovs = d.out.varSATE = (o.varSATE || o.covW) ? c->io.take<double>((size_t)S * LR) : nullptr;
+        double* ocv = d.out.covW = o.covW ? c->io.take<double>((size_t)S * LR * L) : nullptr;
         double* omi = d.out.meanITE = o.meanITE ? c->io.take<double>(n * S * L) : nullptr;
         double* odr = d.out.ite_draws = o.ite_draws ? c->io.take<double>(L * n * S * o.spp) : nullptr;
         int st = predict_dev_inner(c, d);
@@ -1702,6 +1718,7 @@ static int predict_host(gpslc_ctx* c, const PredictRequest& rq) {
         const size_t sb = (size_t)S * sizeof(double);
         if (o.meanSATE) HC(hipMemcpy2D(o.meanSATE + s0, St * sizeof(double), oms, sb, sb, LR, hipMemcpyDeviceToHost));
         if (o.varSATE) HC(hipMemcpy2D(o.varSATE + s0, St * sizeof(double), ovs, sb, sb, LR, hipMemcpyDeviceToHost));
+        if (o.covW) copy_out_rows(c, o.covW + s0, St * sizeof(double), ocv, sb, LR * L);
         if (o.meanITE) copy_out_rows(c, o.meanITE + n * s0, n * St * sizeof(double), omi, n * sb, L);
         // level-fastest tensor L x n x (S_total spp): a sample's columns are one contiguous run
         if (o.ite_draws) copy_out_large(c, o.ite_draws + L * n * o.spp * s0, odr, sizeof(double) * L * n * S * o.spp);
@@ -1751,6 +1768,19 @@ int gpslc_predict_weighted(gpslc_ctx* c, int64_t S, const double* U, const doubl
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
     rq.lv.base = doT_base; rq.lv.G = G; rq.lv.W = weights;
     rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws};
+    int rc = validate(c, rq, kPredictWeightedArgs);
+    return rc ? rc : predict_host(c, rq);
+}
+
+// the same call with the joint covariance of the levels per weight column as one more output
+int gpslc_predict_curve(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                        const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
+                        const double* doT_base, int32_t G, const double* weights, double pred_noise, int32_t spp,
+                        uint64_t seed, const double* z, double* meanW, double* varW, double* covW, double* meanITE,
+                        double* ite_draws) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.lv.base = doT_base; rq.lv.G = G; rq.lv.W = weights;
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws, covW};
     int rc = validate(c, rq, kPredictWeightedArgs);
     return rc ? rc : predict_host(c, rq);
 }
@@ -2449,6 +2479,70 @@ int gpslc_sate_samples(const double* meanSATE, const double* varSATE, int64_t S,
             const int64_t i = j * spp + d;
             const double zz = z ? z[i] : philox_normal_host(seed, (1ull << 40) + (uint64_t)j, (uint64_t)d);
             out[i] = meanSATE[j] + varSATE[j] * zz;   // variance used as sigma: src/estimation.jl:159
+        }
+    return GPSLC_OK;
+}
+
+// Joint draws of the curve from the (s, g) blocks of gpslc_predict_curve: diagonally pivoted Cholesky of each L x L block,
+// stopped at the first pivot <= L eps max diag (the remaining columns of the factor stay zero), mapped back to level order
+int gpslc_curve_samples(const double* meanW, const double* covW, int64_t S, int32_t L, int32_t G, int32_t spp, uint64_t seed,
+                        const double* z, double* out) {
+    if (!meanW) return -1;
+    if (!covW) return -2;
+    if (S < 0) return -3;
+    if (L < 1) return -4;
+    if (G < 1) return -5;
+    if (spp < 0) return -6;
+    if (!out) return -9;
+    const size_t Ls = (size_t)L;
+    std::vector<double> Cb(Ls * Ls), F(Ls * Ls), dk(Ls);      // dk[i]: the remaining diagonal of level piv[i]
+    std::vector<int32_t> piv(Ls);
+    for (int32_t g = 0; g < G; ++g)
+        for (int64_t s = 0; s < S; ++s) {
+            // block (s, g), lower triangle read; Cb and F are indexed in level order, column-major
+            double dmax = 0.0;
+            for (size_t lp = 0; lp < Ls; ++lp)
+                for (size_t l = lp; l < Ls; ++l) {
+                    Cb[l + Ls * lp] = covW[(size_t)s + (size_t)S * (l + Ls * (lp + Ls * (size_t)g))];
+                    if (l == lp) dmax = std::max(dmax, Cb[l + Ls * lp]);
+                }
+            std::fill(F.begin(), F.end(), 0.0);
+            for (size_t l = 0; l < Ls; ++l) piv[l] = (int32_t)l;
+            const double stop = (double)L * 2.220446049250313e-16 * dmax;
+            auto c_at = [&](size_t i, size_t j) { return i >= j ? Cb[i + Ls * j] : Cb[j + Ls * i]; };
+            for (size_t i = 0; i < Ls; ++i) dk[i] = c_at(i, i);
+            size_t rank = 0;
+            for (size_t k = 0; k < Ls; ++k) {
+                size_t m = k;
+                for (size_t i = k + 1; i < Ls; ++i)
+                    if (dk[i] > dk[m]) m = i;      // first largest
+                if (!(dk[m] > stop)) break;
+                std::swap(piv[k], piv[m]);
+                std::swap(dk[k], dk[m]);
+                const size_t pk = (size_t)piv[k];
+                const double lkk = std::sqrt(dk[k]);
+                F[pk + Ls * k] = lkk;
+                for (size_t i = k + 1; i < Ls; ++i) {
+                    const size_t pi = (size_t)piv[i];
+                    double v = c_at(pi, pk);
+                    for (size_t j = 0; j < k; ++j) v -= F[pi + Ls * j] * F[pk + Ls * j];
+                    v /= lkk;
+                    F[pi + Ls * k] = v;
+                    dk[i] -= v * v;
+                }
+                rank = k + 1;
+            }
+            for (int32_t d = 0; d < spp; ++d) {
+                const size_t base = Ls * ((size_t)d + (size_t)spp * ((size_t)s + (size_t)S * (size_t)g));
+                double* o = out + base;
+                for (size_t l = 0; l < Ls; ++l) o[l] = meanW[(size_t)s + (size_t)S * (l + Ls * (size_t)g)];
+                for (size_t k = 0; k < rank; ++k) {
+                    const double zz = z ? z[base + k]
+                                        : philox_normal_host(seed, (1ull << 41) + (uint64_t)s + (uint64_t)S * (uint64_t)g,
+                                                             (uint64_t)k + (uint64_t)L * (uint64_t)d);
+                    for (size_t l = 0; l < Ls; ++l) o[l] += F[l + Ls * k] * zz;
+                }
+            }
         }
     return GPSLC_OK;
 }

@@ -230,6 +230,19 @@ struct EpiArgs {
 };
 void launch_epilogue(const EpiArgs& e, int nbatch, hipStream_t st);
 
+// joint covariance of the weighted effects across the levels of a call (k_curve.hip); runs after the epilogue
+struct CurveArgs {
+    TRef M; int n, nt, L, G; long long s0; long long S;
+    const double* T; const double* tyLS; const double* doT;
+    const double* doT_base;   // non-null: contrasts (level l is the pair (doT[l], doT_base[l]))
+    const double* W;          // device, column g fastest: W[g + G*j]
+    const double* bw; const double* kw;   // [b][G][Np] (launch_wsum); kw is not read for contrasts
+    double* prior;            // [b][G][L + 2]: beta = w . bw, kappa = w . kw, gamma_l = sum_j w_j r^l_j bw_j
+    const double* varW;       // S x L x G, as the epilogue stored it: the diagonal
+    double* covW;             // S x L x L x G: element (s, l, l', g) at s + S*(l + L*(l' + L*g))
+};
+void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st);
+
 struct BackArgs {
     TRef M; const double* inv; long long inv_bstride; int nt; int naug;
     double* zwork;   // [b][Np] in: z (copied from the augmented row), out: alpha

@@ -1,0 +1,147 @@
+// Joint covariance of the weighted effects of one call across its levels: for weight column w_g, posterior
+// sample s and levels l, l' with tau_l = w_g' ITE_l,
+//
+//     Cov(tau_l, tau_l') = P_ll' - v_l . v_l' + [l == l'] pred_noise (w . w)
+//
+// v_q = L^-1 c_q are the right-hand-side rows the factorisation has carried (row q = 1 + l + L*g of the augmented tiles) and
+// P the prior term: with bw = B w, kw = K w (k_wsum.hip), beta = w . bw, kappa = w . kw, gamma_l = sum_j w_j r^l_j bw_j and
+// rho(x, y) = exp(-(x - y)^2 / tyLS^2)
+//     ordinary, f(d_l) - f(T):    P_ll' = rho(d_l, d_l') beta - gamma_l - gamma_l' + kappa
+//     contrast, f(a_l) - f(b_l):  P_ll' = [(rho(a_l, a_l') - rho(a_l, b_l')) - (rho(b_l, a_l') - rho(b_l, b_l'))] beta
+//
+//   curve_prior_kernel   beta, kappa, gamma_l per (sample, weight column): fixed trees over the threads' strided j
+//   curve_gram_kernel    one workgroup per (16 x 16 block of right-hand-side pairs, sample): v_q . v_q' with
+//                        v_mfma_f64_16x16x4_f64 straight from the augmented rows, then P - Gram for l' < l, written to both
+//                        triangles; the diagonal is the value the epilogue stored as varW
+#include "gpslc_internal.h"
+#include "gp_math.h"
+
+// block-wide sum with a fixed reduction tree (deterministic); result valid in every thread
+__device__ __forceinline__ double curve_block_sum(double v, double* red /* 4 doubles */) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__device__ __forceinline__ double curve_rho(double x, double y, double wt) {
+    const double d = x - y;
+    return gp_exp_neg(-((d * d) * wt));
+}
+
+// grid (G, batch).  prior[b][g][0] = beta, [1] = kappa, [2 + l] = gamma_l; the contrast form needs beta alone (kw is not
+// computed for it and is not read)
+template <bool CON>
+__global__ __launch_bounds__(256) void curve_prior_kernel(CurveArgs a) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const int g = blockIdx.x, b = blockIdx.y;
+    const long long s = a.s0 + b;
+    const int Np = a.nt * GP_TS;
+    const double* bs = a.bw + ((long long)b * a.G + g) * Np;
+    const double* ks = a.kw + ((long long)b * a.G + g) * Np;
+    double* out = a.prior + ((long long)b * a.G + g) * (a.L + 2);
+    double ab = 0.0, ak = 0.0;
+    for (int j = tid; j < a.n; j += 256) {
+        const double w = a.W[(long long)j * a.G + g];
+        ab = fma(w, bs[j], ab);
+        if (!CON) ak = fma(w, ks[j], ak);
+    }
+    const double beta = curve_block_sum(ab, red);
+    const double kappa = CON ? 0.0 : curve_block_sum(ak, red);
+    if (tid == 0) { out[0] = beta; out[1] = kappa; }
+    if (CON) return;
+    const double tl = a.tyLS[s];
+    const double wt = 1.0 / (tl * tl);
+    for (int l = 0; l < a.L; ++l) {
+        const double dot = a.doT[l];
+        double acc = 0.0;
+        for (int j = tid; j < a.n; j += 256) {
+            const double w = a.W[(long long)j * a.G + g];
+            acc = fma(w * curve_rho(a.T[j], dot, wt), bs[j], acc);
+        }
+        const double gam = curve_block_sum(acc, red);
+        if (tid == 0) out[2 + l] = gam;
+    }
+}
+
+// grid (nblk (nblk + 1) / 2, batch), nblk = ceil((R + 1) / 16) blocks of 16 right-hand sides, R = L G.  Workgroup p is the block
+// pair (A, Bk), Bk <= A.  Right-hand side q of column i sits at tile (nt + q / 128, i / 128)[(i % 128) * 128 + q % 128]: the 16
+// q of a block are one 128-byte line per column, so lane (r = lane & 15, k = lane >> 4) loads its MFMA operand — row 16 A + r,
+// column 4 kg + k of column group kg — straight from global memory.  Only rows below 16 nblk are read: with <= 32 live rows
+// the rest of the augmented tile is undefined (rhs_tiles_kernel).  Wave w takes the column groups w, w + 4, ... of every tile
+// column in ascending order, alternating between two accumulators; the four waves' sums meet in LDS as (w0 + w1) + (w2 + w3).
+// Accumulator v of a lane is the pair (qa = 16 A + (lane >> 4) + 4 v, qb = 16 Bk + (lane & 15)) (diag_block.h: mma).
+template <bool CON>
+__global__ __launch_bounds__(256) void curve_gram_kernel(CurveArgs a) {
+    __shared__ double part[4][4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y;
+    const long long s = a.s0 + b;
+    const int R = a.L * a.G;
+    int A = 0;
+    while ((A + 1) * (A + 2) / 2 <= (int)blockIdx.x) ++A;
+    const int Bk = (int)blockIdx.x - A * (A + 1) / 2;
+    // no pair of the same weight column in this block pair: the columns of block A start beyond the last column of block Bk
+    const int ga_lo = (max(16 * A, 1) - 1) / a.L, gb_hi = (min(16 * Bk + 15, R) - 1) / a.L;
+    if (gb_hi < ga_lo) return;
+    const int lane_off = (lane & 15) + (lane >> 4) * GP_TS;
+    d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+    for (int tj = 0; tj < a.nt; ++tj) {
+        const double* pa = tref_tile(a.M, b, a.nt + (A >> 3), tj) + (A & 7) * 16 + lane_off;
+        const double* pb = tref_tile(a.M, b, a.nt + (Bk >> 3), tj) + (Bk & 7) * 16 + lane_off;
+        double av[8], bv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int col = 4 * (wave + 4 * u);
+            av[u] = pa[col * GP_TS];
+            bv[u] = pb[col * GP_TS];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u += 2) {
+            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u + 1], bv[u + 1], acc1, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) part[wave][v][lane] = acc0[v] + acc1[v];
+    __syncthreads();
+    // thread -> one pair of the block: v = tid >> 6 of lane tid & 63
+    const int qa = 16 * A + (lane >> 4) + 4 * wave, qb = 16 * Bk + (lane & 15);
+    if (qa < 1 || qb < 1 || qa > R || qb > qa) return;
+    const int g = (qa - 1) / a.L, l = (qa - 1) - a.L * g;
+    if ((qb - 1) / a.L != g) return;
+    const int lp = (qb - 1) - a.L * g;                      // l' <= l
+    double* cov = a.covW + s + a.S * ((long long)a.L * a.L * g);
+    if (lp == l) {
+        cov[a.S * ((long long)l + (long long)a.L * l)] = a.varW[s + a.S * ((long long)l + (long long)a.L * g)];
+        return;
+    }
+    const double gram = (part[0][wave][lane] + part[1][wave][lane]) + (part[2][wave][lane] + part[3][wave][lane]);
+    const double* pr = a.prior + ((long long)b * a.G + g) * (a.L + 2);
+    const double tl = a.tyLS[s];
+    const double wt = 1.0 / (tl * tl);
+    double P;
+    if (CON) {
+        const double x = a.doT[l], y = a.doT_base[l], xp = a.doT[lp], yp = a.doT_base[lp];
+        P = ((curve_rho(x, xp, wt) - curve_rho(x, yp, wt)) - (curve_rho(y, xp, wt) - curve_rho(y, yp, wt))) * pr[0];
+    } else {
+        P = ((curve_rho(a.doT[l], a.doT[lp], wt) * pr[0] - pr[2 + l]) - pr[2 + lp]) + pr[1];
+    }
+    const double val = P - gram;
+    cov[a.S * ((long long)l + (long long)a.L * lp)] = val;
+    cov[a.S * ((long long)lp + (long long)a.L * l)] = val;
+}
+
+template <bool CON>
+static void launch_curve_t(const CurveArgs& a, int nbatch, hipStream_t st) {
+    const int nblk = (a.L * a.G + 1 + 15) / 16;
+    hipLaunchKernelGGL(curve_prior_kernel<CON>, dim3(a.G, nbatch), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(curve_gram_kernel<CON>, dim3(nblk * (nblk + 1) / 2, nbatch), dim3(256), 0, st, a);
+}
+void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st) {
+    if (a.doT_base) launch_curve_t<true>(a, nbatch, st);
+    else launch_curve_t<false>(a, nbatch, st);
+}

@@ -297,6 +297,33 @@ int gpslc_predict_weighted(gpslc_ctx* ctx, int64_t S, const double* U, const dou
                            const double* z_or_null, double* meanW, double* varW, double* meanITE,
                            double* ite_draws);
 
+/* The joint covariance of the weighted effects across the levels of one call: gpslc_predict_weighted with one more output.  A
+ * sweep of levels is a dose-response curve; its values tau_l = w_g' ITE_l share one Gaussian process, and simultaneous bands,
+ * comparisons of every pair of levels and functionals of the curve (slope, maximum, area) need the L x L covariance of the sweep,
+ * which the per-level varW does not give.  With v_l = L^-1 c_l the right-hand sides the weighted call has solved for anyway,
+ * bw = B w, kw = K w, beta = w . bw, kappa = w . kw, gamma_l = sum_j w_j r^l_j bw_j and rho(x, y) = exp(-(x - y)^2 / tyLS^2):
+ *     Cov(tau_l, tau_l') = P_ll' - v_l . v_l' + [l == l'] pred_noise (w . w)           (the jitter of src/estimation.jl:82 is per level)
+ *     ordinary estimand:  P_ll' = rho(d_l, d_l') beta - gamma_l - gamma_l' + kappa
+ *     contrast:           P_ll' = [(rho(a_l, a_l') - rho(a_l, b_l')) - (rho(b_l, a_l') - rho(b_l, b_l'))] beta
+ * The factorisation is untouched: one Gram pass over the solved rows and O(n L + L^2) prior terms per sample and column.
+ *   covW   S x L x L x G host: element (s, l, l', g) at s + S*(l + L*(l' + L*g)); may be NULL (then the call IS
+ *          gpslc_predict_weighted: the same kernels are launched)
+ * Arguments, layouts, NULL conventions, error codes (-10 / -11 / -12 / -13 / -15, GPSLC_ERR_UNSUPPORTED on a
+ * GPSLC_FLAG_FP32_KERNEL ctx), chunking, the schedule and gpslc_last_info are gpslc_predict_weighted's.  Guarantees: every
+ * (s, g) block is exactly symmetric (one value is written to both triangles); the diagonal covW[s, l, l, g] is bit-identical
+ * to varW[s, l, g] of the same call; meanW, varW, meanITE and ite_draws are bit-identical to gpslc_predict_weighted's with the
+ * same arguments; a zero weight column gives an all-0.0 block; a contrast level with a_l == b_l gives row and column l exactly
+ * 0.0 off the diagonal; results do not depend on chunking, streams or the factorisation schedule and are identical from run to
+ * run.  Near-coincident levels give a block that is semi-definite to rounding (gpslc_curve_samples takes such blocks).
+ * Out of scope: cross-covariances between different weight columns (a difference of groups is a weight column), vector levels,
+ * the fp32-kernel mode, sharding through gpslc_predict_multi, device-pointer variants.   */
+int gpslc_predict_curve(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                        const double* xyLS, const double* tyLS, const double* yScale,
+                        const double* yNoise, int32_t L, const double* doT, const double* doT_base_or_null,
+                        int32_t G, const double* weights, double pred_noise, int32_t spp, uint64_t seed,
+                        const double* z_or_null, double* meanW, double* varW, double* covW, double* meanITE,
+                        double* ite_draws);
+
 /* The same call sharded over several GPUs of one node: what the loop of predictCounterfactualEffects (src/prediction.jl:30-33)
  * over the posterior samples (src/estimation.jl:78-84) becomes when the ensemble is partitioned.  ctxs[0..nctx) are
  * DISTINCT contexts created with the same (n, nX, nU), one per device (gpslc_create(&ctx_k, device_k, ...)), each holding the data
@@ -365,6 +392,17 @@ int gpslc_likelihood_distribution_vec(gpslc_ctx* ctx, const double* U, const dou
  * arithmetic; z_or_null (S*spp) or Philox stream `seed`, stream id 2^40 + j. */
 int gpslc_sate_samples(const double* meanSATE, const double* varSATE, int64_t S, int32_t spp,
                        uint64_t seed, const double* z_or_null, double* out /* S*spp */);
+
+/* Joint draws of a curve from gpslc_predict_curve's outputs (meanW S x L x G, covW S x L x L x G; the lower triangle of each
+ * block is read): out[l + L*(d + spp*(s + S*g))] = meanW[s, l, g] + (F z)_l, F F' = the (s, g) block.  F is the factor of a
+ * diagonally pivoted Cholesky mapped back to level order; the factorisation stops at the first pivot <= L * eps * max diag and
+ * leaves the remaining columns of F zero, so a semi-definite or slightly indefinite block (near-coincident levels on a smooth
+ * curve, repeated levels) is a normal input, not an error.  z_or_null: L x spp x S x G standard normals, z[k + L*(d + spp*(s +
+ * S*g))] multiplying column k of F (pivot order), or the library's Philox stream `seed`: stream id 2^41 + s + S*g, element
+ * k + L*d.  Host-only arithmetic (no ctx, no GPU).  Errors: meanW / covW NULL -1 / -2, S < 0 -3, L < 1 -4, G < 1 -5, spp < 0 -6,
+ * out NULL -9. */
+int gpslc_curve_samples(const double* meanW, const double* covW, int64_t S, int32_t L, int32_t G,
+                        int32_t spp, uint64_t seed, const double* z_or_null, double* out /* L*spp*S*G */);
 
 /* summarizeEstimates(samples; credible_interval) (src/driver.jl:129-149): per-individual Mean and the
  * (1-ci)/2 and 1-(1-ci)/2 quantiles (Julia's Statistics.quantile, type 7) of an n x m sample matrix

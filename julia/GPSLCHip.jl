@@ -318,6 +318,31 @@ function predict_weighted(c::Ctx, p::Pack, doT::Vector{Float64}, doT_base::Union
     mW, vW, mI, dr
 end
 
+"""The weighted call with the joint covariance of its L levels as one more result (gpslc_predict_curve): covW is S x L x L x G,
+covW[s, l, l', g] = Cov(w_g' ITE_l, w_g' ITE_l') of posterior sample s — the covariance of a dose-response curve over a sweep of
+levels.  Its diagonal is vW to the bits, every (s, g) block is exactly symmetric; mW, vW, MeanITE and the draws are
+`predict_weighted`'s.  Returns (mW, vW, covW, meanITE | nothing, ite | nothing)."""
+function predict_curve(c::Ctx, p::Pack, doT::Vector{Float64}, doT_base::Union{Nothing,Vector{Float64}}, weights::Matrix{Float64},
+                       pred_noise::Float64; spp::Integer=0, seed::Integer=0, z=nothing, want_mean_ite::Bool=false,
+                       want_draws::Bool=false)
+    S, L, n, G = length(p.tyLS), length(doT), c.n, size(weights, 2)
+    size(weights, 1) == n || throw(DimensionMismatch("weights has $(size(weights, 1)) rows, n = $n"))
+    doT_base === nothing || length(doT_base) == L || throw(DimensionMismatch("doT_base has length $(length(doT_base)), L = $L"))
+    mW, vW = Array{Float64}(undef, S, L, G), Array{Float64}(undef, S, L, G)
+    cW = Array{Float64}(undef, S, L, L, G)
+    mI = want_mean_ite ? Array{Float64}(undef, n, S, L) : nothing
+    dr = want_draws ? Array{Float64}(undef, L, n, S * spp) : nothing
+    zf = f64(z)
+    GC.@preserve p doT doT_base weights zf mW vW cW mI dr check(c, ccall((:gpslc_predict_curve, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Int32, UInt64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        L, pointer(doT), ptr(doT_base), G, pointer(weights), pred_noise, spp, seed, ptr(zf),
+        pointer(mW), pointer(vW), pointer(cW), ptr(mI), ptr(dr)))
+    mW, vW, cW, mI, dr
+end
+
 """`predict` sharded over several GPUs of one node — `cs` = one context per device (`Ctx(n, nX, nU; device=k)`, each with
 the data: `set_data!` on every one), the posterior samples split into contiguous blocks, one host thread per context inside the
 library, every device copying its block of the results into these host arrays.  Same results as `predict(cs[1], …)` over all S
@@ -441,6 +466,25 @@ function sate_samples(meanSATE::Vector{Float64}, varSATE::Vector{Float64}, spp::
             (Ptr{Float64}, Ptr{Float64}, Int64, Int32, UInt64, Ptr{Float64}, Ptr{Float64}),
             pointer(meanSATE), pointer(varSATE), S, spp, seed, ptr(zf), pointer(out))
         st == 0 || error("gpslc_sate_samples: status $st")
+    end
+    out
+end
+
+"""Joint draws of curves from `predict_curve`'s meanW (S x L x G) and covW (S x L x L x G): L x spp x S x G, draw d of sample s
+and column g at [:, d, s, g] = mean + F z with F F' the (s, g) block (diagonally pivoted Cholesky, stopped at the first pivot
+<= L eps max diag: semi-definite blocks — repeated or near-coincident levels — are normal inputs).  `z`: L x spp x S x G standard
+normals, else the library's Philox stream `seed`."""
+function curve_samples(meanW::Array{Float64,3}, covW::Array{Float64,4}, spp::Integer; seed::Integer=0, z=nothing)
+    S, L, G = size(meanW)
+    size(covW) == (S, L, L, G) || throw(DimensionMismatch("covW is $(size(covW)), expected $((S, L, L, G))"))
+    out = Array{Float64}(undef, L, spp, S, G)
+    zf = f64(z)
+    zf === nothing || size(zf) == (L, spp, S, G) || throw(DimensionMismatch("z is $(size(zf)), expected $((L, spp, S, G))"))
+    GC.@preserve meanW covW zf out begin
+        st = ccall((:gpslc_curve_samples, lib), Cint,
+            (Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int32, Int32, UInt64, Ptr{Float64}, Ptr{Float64}),
+            pointer(meanW), pointer(covW), S, L, G, spp, seed, ptr(zf), pointer(out))
+        st == 0 || error("gpslc_curve_samples: status $st")
     end
     out
 end
@@ -936,6 +980,42 @@ function sampleSATE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int6
     seed === nothing || return GPSLCHip.sate_samples(MeanSATEs, VarSATEs, samplesPerPosterior; seed=UInt64(seed))
     z = randn(length(MeanSATEs) * samplesPerPosterior)
     GPSLCHip.sate_samples(MeanSATEs, VarSATEs, samplesPerPosterior; z=z)  # normal(mean, var): variance as sigma (:159)
+end
+
+# ---- the effect over a sweep of levels as one Gaussian (gpslc_predict_curve; not in the reference) ---------------------------
+# `weights = nothing`: 1/n, the SATE curve; a length-n vector or an n x G matrix as in SATEDistributions.  `baseline`: nothing,
+# one scalar for every level, or one per level.  Scalar levels and one GPU only.
+_curve_baseline(b::Nothing, L) = nothing
+_curve_baseline(b::Real, L) = fill(Float64(b), L)
+_curve_baseline(b::AbstractVector{<:Real}, L) =
+    (length(b) == L || throw(ArgumentError("baseline= needs one value per level: $(length(b)) values, L = $L")); Vector{Float64}(b))
+function _curve(g::GPSLCObject, doTs::AbstractVector{<:Real}, baseline, weights, devices)
+    devices === nothing || throw(ArgumentError("effect curves are not sharded over devices: pass devices=nothing"))
+    n = getN(g)
+    lv = Vector{Float64}(doTs)
+    Wm = weights === nothing ? fill(1.0 / n, n, 1) : _weights(weights, n)
+    mW, _, cW, _, _ = GPSLCHip.predict_curve(ctx(g), posterior_pack(g), lv, _curve_baseline(baseline, length(lv)), Wm,
+                                             g.hyperparams.predictionCovarianceNoise)
+    mW, cW, !(weights isa AbstractMatrix)
+end
+
+"""effectCurve(g, doTs; baseline, weights) -> (mean S x L [x G], cov S x L x L [x G]): the weighted effect over the L scalar
+levels `doTs` and its joint covariance across the levels, per posterior sample."""
+function effectCurve(g::GPSLCObject, doTs::AbstractVector{<:Real}; baseline=nothing, weights=nothing, devices=nothing)
+    mW, cW, vec = _curve(g, doTs, baseline, weights, devices)
+    vec ? (mW[:, :, 1], cW[:, :, :, 1]) : (mW, cW)
+end
+
+"""sampleEffectCurve(g, doTs; samplesPerPosterior, seed, baseline, weights) -> L x (S * spp) [G x L x (S * spp)] joint draws of
+the curve, column order sample-outer / draw-inner: every column is ONE curve over the L levels."""
+function sampleEffectCurve(g::GPSLCObject, doTs::AbstractVector{<:Real}; samplesPerPosterior::Int64=10,
+                           seed::Union{Nothing,Integer}=nothing, baseline=nothing, weights=nothing, devices=nothing)
+    mW, cW, vec = _curve(g, doTs, baseline, weights, devices)
+    S, L, G = size(mW)
+    dr = seed === nothing ? GPSLCHip.curve_samples(mW, cW, samplesPerPosterior; z=randn(L, samplesPerPosterior, S, G)) :
+                            GPSLCHip.curve_samples(mW, cW, samplesPerPosterior; seed=UInt64(seed))
+    out = permutedims(reshape(dr, L, samplesPerPosterior * S, G), (3, 1, 2))
+    vec ? out[1, :, :] : out
 end
 
 function summarizeEstimates(samples; savetofile::String="", credible_interval::Float64=0.90)                        # :129-149
