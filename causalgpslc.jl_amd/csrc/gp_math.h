@@ -2,6 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+// sum over a workgroup of 256 threads with a fixed reduction tree (deterministic); result valid in every thread
+__device__ __forceinline__ double block_sum_256(double v, double* red /* >= 4 doubles */) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // exp(x) for x <= 0 (the only domain the RBF path needs; x is clamped at -800 where exp underflows
 // to 0).  Cody-Waite reduction x = k ln2 + r, |r| <= ln2/2, degree-13 Taylor polynomial in Horner form
 // (truncation 4e-18 relative), v_ldexp_f64 scaling: < 1 ulp from the polynomial's rounding, about

@@ -16,16 +16,6 @@
 #include "gpslc_internal.h"
 #include "gp_math.h"
 
-// block-wide sum with a fixed reduction tree (deterministic); result valid in every thread
-__device__ __forceinline__ double curve_block_sum(double v, double* red /* 4 doubles */) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __device__ __forceinline__ double curve_rho(double x, double y, double wt) {
     const double d = x - y;
     return gp_exp_neg(-((d * d) * wt));
@@ -49,8 +39,8 @@ __global__ __launch_bounds__(256) void curve_prior_kernel(CurveArgs a) {
         ab = fma(w, bs[j], ab);
         if (!CON) ak = fma(w, ks[j], ak);
     }
-    const double beta = curve_block_sum(ab, red);
-    const double kappa = CON ? 0.0 : curve_block_sum(ak, red);
+    const double beta = block_sum_256(ab, red);
+    const double kappa = CON ? 0.0 : block_sum_256(ak, red);
     if (tid == 0) { out[0] = beta; out[1] = kappa; }
     if (CON) return;
     const double tl = a.tyLS[s];
@@ -62,7 +52,7 @@ __global__ __launch_bounds__(256) void curve_prior_kernel(CurveArgs a) {
             const double w = a.W[(long long)j * a.G + g];
             acc = fma(w * curve_rho(a.T[j], dot, wt), bs[j], acc);
         }
-        const double gam = curve_block_sum(acc, red);
+        const double gam = block_sum_256(acc, red);
         if (tid == 0) out[2 + l] = gam;
     }
 }

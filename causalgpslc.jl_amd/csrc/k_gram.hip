@@ -14,16 +14,6 @@
 #include "gp_math.h"
 #include <type_traits>
 
-// block-wide sum with a fixed reduction tree (deterministic); result valid in every thread
-__device__ __forceinline__ double block_sum_256(double v, double* red /* >= 4 doubles */) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // ---------------------------------------------------------------------------------------
 // Gram build: one workgroup per lower tile (ti >= tj) per posterior sample.
 // Thread (tx = tid>>4, ty = tid&15) owns rows ty + 16p and columns 8 tx + q, p, q = 0..7.

@@ -3,6 +3,7 @@
 #include "gpslc_internal.h"
 #include "gp_math.h"
 #include "back_block.h"
+#include "pair_mfma.h"
 
 // ---------------------------------------------------------------------------------------
 // Back-substitution L^T alpha = z, right-looking over tile rows i = nt-1 .. 0, two launches per row:
@@ -202,171 +203,51 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 //   MeanITE[i, l] = sum_j B_ij (r_j(l) alpha_j)  -  (Y_i - yNoise alpha_i)
 // = (B R)[i, l] - (K alpha)[i],  R[j, l] = r_j(l) alpha_j  — a (128 x N)(N x 64) product per row block; K alpha from
 // the solve itself (A alpha = Y; see ite_mean_kernel), so the pair loop evaluates one exp (B_ij) and no e_ij.
-// No operand tile goes through LDS: the f64 16x16x4 MFMA wants one element per lane, and each lane computes exactly its
-// own B_rc (row = 16m + lane&15, column = 4kk + lane>>4) from the staged features; R is staged per 64-column chunk.
-// Instances with T_i == doT_l get the reference's exact 0.0 (row i of Ks' - K is identically zero there).
-// One workgroup = 128 rows x up to 64 levels; wave w owns rows 32w..32w+31 (2 row sub-tiles x 4 level
-// sub-tiles = 8 accumulators).
-// CON: contrasts as in ite_mean_kernel — R[j, l] = (r^a_j - r^b_j) alpha_j, no K alpha term, 0.0 for a level with a == b.
+// The product is the pair-product body this kernel shares with wsum_mfma_kernel (pair_mfma.h: no operand tile of B goes
+// through LDS, each lane computes its own B_rc, R is staged per 64-column chunk, fixed summation order, and why the FREG
+// rung that serves an F cannot change a bit).  This kernel supplies the two things the body asks of a caller:
+//   - what is staged: R[j, l] = r_j(l) alpha_j; CON (contrasts as in ite_mean_kernel): (r^a_j - r^b_j) alpha_j;
+//   - the store, per 16-row sub-tile: rows i < n only, (K alpha)_i and T_i loaded once; instances with T_i == doT_l get the
+//     reference's exact 0.0 (row i of Ks' - K is identically zero there).  CON: no K alpha term, 0.0 for a level with a == b.
 // ---------------------------------------------------------------------------------------
-#define IM_CC 64          // columns per staged chunk
-#define IM_RLD 80         // padded row of the R chunk (doubles): conflict-free ds_read_b64 across k rows
-#define IM_NL 64          // levels per pass
-
 template <int FREG, bool CON = false>   // FREG > 0: this lane's two rows' features live in registers (F <= FREG); 0: read from LDS
 __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int F = a.nU + a.nX;
-    double* etab = sm;                       // [32] 2^(j/32): table-driven exp (gp_math.h)
-    double* fr = etab + GP_EXP_TAB_DOUBLES;  // [F][128] row features / LS
-    const int FSL = FREG > F ? FREG : F;
-    double* fc = fr + F * GP_TS;             // [max(F, FREG)][IM_CC] column features / LS
-    double* R = fc + FSL * IM_CC;            // [IM_CC][IM_RLD]  r_j(l) * alpha_j
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, lq = lane >> 4;
-    const int ib = blockIdx.x;
     const long long b = blockIdx.y, s = a.s0 + b;
-    const int n = a.n, Np = a.nt * GP_TS;
-
-    auto feat_src = [&](int f) { return a.column(s, f); };
-    auto feat_il = [&](int f) { return 1.0 / a.lengthscale(s, f); };
-    for (int idx = tid; idx < F * GP_TS; idx += 256) {
-        const int f = idx >> 7, rr = idx & 127;
-        const int g = ib * GP_TS + rr;
-        fr[idx] = (g < n) ? feat_src(f)[g] * feat_il(f) : 0.0;
-    }
-    const double ys = a.p.yScale[s];
-    const double tl = a.p.tyLS[s];
-    const double wt = 1.0 / (tl * tl);
-    const double* alpha = a.alpha + b * Np;
-    gp_exp_tab_stage(etab, tid);
-    const int r0 = 32 * wave + li;           // this lane's rows: r0 and r0 + 16
-    __syncthreads();
-    double af0[FREG > 0 ? FREG : 1], af1[FREG > 0 ? FREG : 1];
-    if (FREG > 0) {
-#pragma unroll
-        for (int f = 0; f < FREG; ++f) {
-            af0[f] = (f < F) ? fr[f * GP_TS + r0] : 0.0;
-            af1[f] = (f < F) ? fr[f * GP_TS + r0 + 16] : 0.0;
-        }
-    }
-
-    for (int l0 = 0; l0 < a.L; l0 += IM_NL) {
-        const int nl = min(IM_NL, a.L - l0);
-        const int nq = (nl + 15) >> 4;          // live 16-level sub-tiles of this pass (wave-uniform)
-        d4 acc[2][4];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[m][q] = (d4){0.0, 0.0, 0.0, 0.0};
-        for (int c0 = 0; c0 < Np; c0 += IM_CC) {
-            __syncthreads();
-            const int FS = FREG > F ? FREG : F;      // staged feature rows (zero beyond F)
-            for (int idx = tid; idx < FS * IM_CC; idx += 256) {
-                const int f = idx / IM_CC, cc = idx - f * IM_CC;
-                const int g = c0 + cc;
-                fc[idx] = (f < F && g < n) ? feat_src(f)[g] * feat_il(f) : 0.0;
-            }
-            for (int idx = tid; idx < IM_CC * IM_NL; idx += 256) {
-                const int cc = idx >> 6, ll = idx & 63;      // consecutive threads -> consecutive levels
-                const int g = c0 + cc;
-                double v = 0.0;
-                if (ll < nl && g < n) {
-                    const double dt = a.T[g] - a.doT[l0 + ll];
-                    if (CON) {
-                        const double db = a.T[g] - a.doT_base[l0 + ll];
-                        v = (gp_exp_neg_tab(-((dt * dt) * wt), etab) - gp_exp_neg_tab(-((db * db) * wt), etab)) * alpha[g];
-                    } else {
-                        v = gp_exp_neg_tab(-((dt * dt) * wt), etab) * alpha[g];
-                    }
-                }
-                R[cc * IM_RLD + ll] = v;
-            }
-            __syncthreads();
-#pragma unroll 2
-            for (int kk = 0; kk < IM_CC / 4; ++kk) {
-                const int cc = 4 * kk + lq;            // this lane's column inside the chunk
-                double lux0 = 0.0, lux1 = 0.0;
-                if (FREG > 0) {
-#pragma unroll
-                    for (int f = 0; f < FREG; ++f) {       // fc rows beyond F are zero-filled
-                        const double cf = fc[f * IM_CC + cc];
-                        const double d0 = af0[f] - cf, d1 = af1[f] - cf;
-                        lux0 = fma(d0, d0, lux0);
-                        lux1 = fma(d1, d1, lux1);
-                    }
-                } else {
-                    for (int f = 0; f < F; ++f) {
-                        const double cf = fc[f * IM_CC + cc];
-                        const double d0 = fr[f * GP_TS + r0] - cf;
-                        const double d1 = fr[f * GP_TS + r0 + 16] - cf;
-                        lux0 = fma(d0, d0, lux0);
-                        lux1 = fma(d1, d1, lux1);
-                    }
-                }
-                const double B0 = ys * gp_exp_neg_tab(-lux0, etab), B1 = ys * gp_exp_neg_tab(-lux1, etab);
-                const double* Rrow = R + cc * IM_RLD + li;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (q < nq) {
-                        const double rf = Rrow[16 * q];
-                        acc[0][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(rf, B0, acc[0][q], 0, 0, 0);
-                        acc[1][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(rf, B1, acc[1][q], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        // acc[m][q][v] = (B R)[row 32w + 16m + li][level 16q + lq + 4v]
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int gi = ib * GP_TS + 32 * wave + 16 * m + li;
+    const double* alpha = a.alpha + b * (a.nt * GP_TS);
+    pair_mfma_body<FREG, false, 0>(
+        a, s, a.L, sm,
+        [&](int j, int l, double wt, const double* etab) {
+            const double dt = a.T[j] - a.doT[l];
             if (CON) {
-                if (gi < n) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) {
-                            const int ll = 16 * q + lq + 4 * v;
-                            if (ll < nl)
-                                a.meanITE[(long long)gi * a.si + s * a.ss + (long long)(l0 + ll) * a.sl] =
-                                    (a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : acc[m][q][v];
-                        }
-                }
-            } else if (gi < n) {
-                const double ka = a.Y[s * a.y_sstride + gi] - a.yNoise[s] * alpha[gi];     // (K alpha)_i from A alpha = Y
-                const double ti = a.T[gi];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int ll = 16 * q + lq + 4 * v;
-                        if (ll < nl)
-                            a.meanITE[(long long)gi * a.si + s * a.ss + (long long)(l0 + ll) * a.sl] =
-                                (ti == a.doT[l0 + ll]) ? 0.0 : acc[m][q][v] - ka;
-                    }
+                const double db = a.T[j] - a.doT_base[l];
+                return (gp_exp_neg_tab(-((dt * dt) * wt), etab) - gp_exp_neg_tab(-((db * db) * wt), etab)) * alpha[j];
             }
-        }
-    }
+            return gp_exp_neg_tab(-((dt * dt) * wt), etab) * alpha[j];
+        },
+        [&](int gi, int l0, int nl, const d4* acc, const d4*) {
+            if (gi >= a.n) return;
+            double* out = a.meanITE + (long long)gi * a.si + s * a.ss;
+            if (CON) {
+                pair_mfma_each_column(nl, [&](int q, int v, int ll) {
+                    out[(long long)(l0 + ll) * a.sl] = (a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : acc[q][v];
+                });
+                return;
+            }
+            const double ka = a.Y[s * a.y_sstride + gi] - a.yNoise[s] * alpha[gi];     // (K alpha)_i from A alpha = Y
+            const double ti = a.T[gi];
+            pair_mfma_each_column(nl, [&](int q, int v, int ll) {
+                out[(long long)(l0 + ll) * a.sl] = (ti == a.doT[l0 + ll]) ? 0.0 : acc[q][v] - ka;
+            });
+        });
 }
 
-template <int FREG, bool CON>
-static void launch_ite_mean_mfma_t(const IteMeanArgs& a, int nbatch, hipStream_t st) {
-    const int F = a.nU + a.nX;
-    const int FS = FREG > F ? FREG : F;
-    const int bytes = (GP_EXP_TAB_DOUBLES + F * GP_TS + FS * IM_CC + IM_CC * IM_RLD) * 8;
-    static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)ite_mean_mfma_kernel<FREG, CON>, (GP_EXP_TAB_DOUBLES + MAXF * GP_TS + MAXF * IM_CC + IM_CC * IM_RLD) * 8);
-    hipLaunchKernelGGL((ite_mean_mfma_kernel<FREG, CON>), dim3(a.nt, nbatch), dim3(256), bytes, st, a);
-}
 template <bool CON>
 static void launch_ite_mean_mfma(const IteMeanArgs& a, int nbatch, hipStream_t st) {
-    const int F = a.nU + a.nX;
-    if (F <= 4) launch_ite_mean_mfma_t<4, CON>(a, nbatch, st);
-    else if (F <= 6) launch_ite_mean_mfma_t<6, CON>(a, nbatch, st);
-    else if (F <= 8) launch_ite_mean_mfma_t<8, CON>(a, nbatch, st);
-    else if (F <= 10) launch_ite_mean_mfma_t<10, CON>(a, nbatch, st);
-    else if (F <= 12) launch_ite_mean_mfma_t<12, CON>(a, nbatch, st);
-    else launch_ite_mean_mfma_t<0, CON>(a, nbatch, st);
+    pair_mfma_freg_ladder(a.nU + a.nX, [&](auto freg) {
+        constexpr int FREG = decltype(freg)::value;
+        pair_mfma_launch<ite_mean_mfma_kernel<FREG, CON>, FREG, false>(a, nbatch, st);
+    });
 }
 
 template <int FREG, int LCT, typename RT, bool CON>
