@@ -4,6 +4,7 @@
 #include "../../include/gpslc_hip.h"
 #include "gpslc_internal.h"
 #include "batch_plan.h"
+#include "philox.h"
 
 #include <algorithm>
 #include <cmath>
@@ -713,7 +714,7 @@ struct Chunk {
     double* cprior = nullptr;        // joint covariance across the levels: beta, kappa, gamma_l [nb][G][L + 2]
     // unit B: a sub-batch of gs_max samples x lc_max levels; W, CovITE, the draws' normals, level-sweep staging, failure codes
     int lc_max = 0, gs_max = 0;
-    double *Wt = nullptr, *Ct = nullptr, *zgen = nullptr, *zt = nullptr, *dtmp = nullptr;
+    double *Wt = nullptr, *Ct = nullptr, *zt = nullptr, *dtmp = nullptr;
     int* pinfo = nullptr;
     SampleGrid grid{};               // the chunk's samples and feature blocks, as every RBF-evaluating kernel takes them
 };
@@ -733,11 +734,8 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
         return ar ? ar->take<double>((size_t)b.nb * per_sample) : nullptr;
     };
     const int n = sh.n, nt = sh.nt, L = sh.L;
-    // spp <= 128: the streaming draw kernel reads the unit's normals (caller's or Philox) from an operand image of 16 Np doubles
-    // per block of 16 draws (DrawArgs::zt); per unit: 1 / 2 / 4 / 8 blocks of 16 draws (draws_nq, k_solve.hip: the stream
-    // kernel's template parameter)
-    const bool zimage = sh.want_draws && io.out.spp <= 128;
-    const size_t zimage_doubles = zimage ? (size_t)16 * (io.out.spp <= 16 ? 1 : io.out.spp <= 32 ? 2 : io.out.spp <= 64 ? 4 : 8) * sh.Np : 0;
+    // the streaming draw kernel reads a pass's normals (caller's or Philox) from the unit's operand image (DrawArgs::zt)
+    const size_t zimage_doubles = sh.want_draws ? draws_image_doubles(io.out.spp, sh.Np) : 0;
     b.tiles = take(sh.tiles_per * GP_TSQ);
     b.inv = take((size_t)nt * GP_TSQ);
     if (sh.with_sums && !io.lv.W) b.part = take(2 * nt * sh.Np);
@@ -751,13 +749,12 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     }
     if (io.lv.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
-    if (io.ndraw) b.znode = take(16 * sh.Np);                           // operand image of the node draw's normals
+    if (io.ndraw) b.znode = take(draws_image_doubles(1, sh.Np));        // operand image of the node draw's normals
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
     if (!sh.unitB) return by;
     by.per_pair = (size_t)((long long)nt * nt + sh.nlow) * GP_TSQ * 8;
     if (sh.want_draws) {
-        by.per_pair += (zimage ? zimage_doubles * 8 + 256 : (io.out.z ? 0 : (size_t)io.out.spp * n * 8 + 256)) +
-                       (L > 1 ? (size_t)io.out.spp * n * 8 + 256 : 0) + sizeof(int) + 256;
+        by.per_pair += zimage_doubles * 8 + 256 + (L > 1 ? (size_t)io.out.spp * n * 8 + 256 : 0) + sizeof(int) + 256;
         by.per_level = (size_t)io.out.spp * n * 8;
     }
     if (!ar) return by;
@@ -765,11 +762,10 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     b.gs_max = std::max(1, Bb / b.lc_max);           // samples per sub-batch
     b.Wt = ar->take<double>((size_t)Bb * nt * nt * GP_TSQ);
     b.Ct = ar->take<double>((size_t)Bb * sh.nlow * GP_TSQ);
-    // draws: the library's own normals of one sub-batch (generated once per unit), and for a level sweep the staging buffer
+    // draws: the operand images of one sub-batch, and for a level sweep the staging buffer
     // [sample][level][d][i] that is rearranged into the level-fastest tensor sample group by group (per unit of the sub-batch:
     // max(1, Bb / L) samples x L levels <= Bb pairs, or one sample's L > Bb levels — per_level)
-    if (sh.want_draws && !io.out.z && !zimage) b.zgen = ar->take<double>((size_t)Bb * io.out.spp * n);
-    if (zimage) b.zt = ar->take<double>((size_t)Bb * zimage_doubles);
+    if (sh.want_draws) b.zt = ar->take<double>((size_t)Bb * zimage_doubles);
     if (sh.want_draws && L > 1) b.dtmp = ar->take<double>((size_t)b.gs_max * L * io.out.spp * n);
     // failure codes of the CovITE factors, one per pair of a sub-batch (folded into io.info after each sub-batch)
     if (sh.want_draws) b.pinfo = ar->take<int>((size_t)Bb);
@@ -976,7 +972,7 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
                 launch_fold_pair_info(ch.pinfo, io.info + s0 + g0, gs, lc, st);
                 DrawArgs dr{};
                 dr.Lc = Cm; dr.n = n; dr.nt = nt; dr.s0 = s0 + g0; dr.S = io.post.S; dr.l = l0; dr.lc = lc; dr.L = L;
-                dr.spp = io.out.spp; dr.mean = io.out.meanITE; dr.z = io.out.z; dr.zgen = ch.zgen; dr.zt = ch.zt; dr.seed = io.out.seed;
+                dr.spp = io.out.spp; dr.mean = io.out.meanITE; dr.z = io.out.z; dr.zt = ch.zt; dr.seed = io.out.seed;
                 const int64_t eS = io.ens_S > 0 ? io.ens_S : c->ens_S, eo = io.ens_S > 0 ? io.ens_off : c->ens_off;
                 dr.rs0 = dr.s0 + (eS > 0 ? eo : 0); dr.rS = eS > 0 ? eS : io.post.S;
                 if (L == 1) {     // the reference tensor directly: n x (S*spp), instance fastest
@@ -1077,31 +1073,6 @@ int bad_arg(gpslc_ctx* c, int k, const char* what) {
     snprintf(buf, sizeof buf, "argument #%d is invalid: %s", k, what);
     set_err(c, buf);
     return -k;
-}
-
-// host-side Philox (same stream definition as the device code / the oracle)
-void philox_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t o[4]) {
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-double philox_normal_host(uint64_t seed, uint64_t stream, uint64_t e) {
-    uint32_t w[4];
-    const uint64_t pair = e >> 1;
-    philox_host((uint32_t)pair, (uint32_t)(pair >> 32), (uint32_t)stream, (uint32_t)(stream >> 32),
-                (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    const uint64_t A = ((uint64_t)w[0] << 21) ^ ((uint64_t)w[1] >> 11);
-    const uint64_t B = ((uint64_t)w[2] << 21) ^ ((uint64_t)w[3] >> 11);
-    const double u1 = ((double)A + 0.5) * (1.0 / 9007199254740992.0);
-    const double u2 = ((double)B + 0.5) * (1.0 / 9007199254740992.0);
-    const double rad = std::sqrt(-2.0 * std::log(u1));
-    const double ang = 6.283185307179586476925286766559 * u2;
-    return (e & 1) ? rad * std::sin(ang) : rad * std::cos(ang);
 }
 
 double* up(DevBuf& b, const double* host, size_t count) {
@@ -2292,7 +2263,7 @@ int gpslc_mvn_draw(gpslc_ctx* c, int64_t S, const double* cov, const double* cov
         const double* dz = up(c, z, n * (size_t)S);
         double* zero_mean = c->io.take<double>(n * (size_t)S);
         double* out = c->io.take<double>(n * (size_t)S);
-        double* zt = c->io.take<double>((size_t)S * 16 * Np);
+        double* zt = c->io.take<double>((size_t)S * draws_image_doubles(1, Np));
         HC(hipMemsetAsync(zero_mean, 0, n * (size_t)S * sizeof(double), st));
         launch_draws(zero_mean_draw(lower_ref(c->mvn_tiles, 0), (int)n, nt, 0, S, zero_mean, dz, zt, out), (int)S, st);
         HC(hipStreamSynchronize(st));
@@ -2477,7 +2448,7 @@ int gpslc_sate_samples(const double* meanSATE, const double* varSATE, int64_t S,
     for (int64_t j = 0; j < S; ++j)
         for (int32_t d = 0; d < spp; ++d) {
             const int64_t i = j * spp + d;
-            const double zz = z ? z[i] : philox_normal_host(seed, (1ull << 40) + (uint64_t)j, (uint64_t)d);
+            const double zz = z ? z[i] : philox_normal(seed, (1ull << 40) + (uint64_t)j, (uint64_t)d);
             out[i] = meanSATE[j] + varSATE[j] * zz;   // variance used as sigma: src/estimation.jl:159
         }
     return GPSLC_OK;
@@ -2538,7 +2509,7 @@ int gpslc_curve_samples(const double* meanW, const double* covW, int64_t S, int3
                 for (size_t l = 0; l < Ls; ++l) o[l] = meanW[(size_t)s + (size_t)S * (l + Ls * (size_t)g)];
                 for (size_t k = 0; k < rank; ++k) {
                     const double zz = z ? z[base + k]
-                                        : philox_normal_host(seed, (1ull << 41) + (uint64_t)s + (uint64_t)S * (uint64_t)g,
+                                        : philox_normal(seed, (1ull << 41) + (uint64_t)s + (uint64_t)S * (uint64_t)g,
                                                              (uint64_t)k + (uint64_t)L * (uint64_t)d);
                     for (size_t l = 0; l < Ls; ++l) o[l] += F[l + Ls * k] * zz;
                 }

@@ -300,14 +300,20 @@ struct GatherCovArgs {
 };
 void launch_gather_cov(const GatherCovArgs& a, int nbatch, hipStream_t st);
 
+// blocks of 16 draws the streaming draw kernel works on in a pass of nd <= 128 draws: its template parameter NQ
+__host__ __device__ inline int draws_nq(int nd) { return nd <= 16 ? 1 : nd <= 32 ? 2 : nd <= 64 ? 4 : 8; }
+// doubles of a unit's operand image (DrawArgs::zt) for spp draws per unit: 16 Np per block of 16 draws of its widest pass
+inline size_t draws_image_doubles(int spp, long long Np) { return (size_t)16 * draws_nq(spp < 128 ? spp : 128) * Np; }
+
 struct DrawArgs {
     TRef Lc; int n, nt; long long s0, S; int l, L, spp;   // batch element b = (sample s0 + b / lc, level l + b % lc)
     int lc;
+    int d0, nd;           // set by launch_draws, one launch pair per pass: the pass's first draw and its count (<= 128).  spp stays
+                          // the unit's total: the stride of z, of the Philox element index and of out
     const double* mean;   // meanITE n x S x L
-    const double* z;      // caller's normals, n x spp x S x L, or null
-    double* zgen;         // z == null, spp > 128: workspace [nbatch][spp][n] the library's Philox normals are generated into
-    double* zt;           // spp <= 128: workspace [nbatch][1 | 2 | 4 | 8 blocks of 16 draws][16 nt 128] — the unit's normals (caller's or Philox) in
-                          // the MFMA operand image the streaming draw kernel reads (draws_zt_index, k_solve.hip), zero-padded
+    const double* z;      // caller's normals, n x spp x S x L, or null: the library's Philox normals (philox.h)
+    double* zt;           // workspace [nbatch][draws_image_doubles(spp, 128 nt)] — the normals of one pass (caller's or Philox) in the
+                          // MFMA operand image the streaming draw kernel reads (draws_zt_index, k_draws.hip), zero-padded
     unsigned long long seed;
     long long rs0, rS;    // Philox stream of batch element b: (rs0 + b / lc) + rS * (l + b % lc) (gpslc_set_ensemble)
     // element (instance i, sample offset sb = b / lc, level offset lb = b % lc, draw d) of this launch goes to

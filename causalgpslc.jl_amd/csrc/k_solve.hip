@@ -1,5 +1,6 @@
 // O(N^2) kernels around the factor: back-substitution for alpha = A^-1 Y, the MeanITE pass,
-// construction of D / Delta for the full ITE covariance, CovITE gather and the predictive draws.
+// construction of D / Delta for the full ITE covariance, CovITE gather, the likelihood blocks and summarize (the predictive
+// draws: k_draws.hip).
 #include "gpslc_internal.h"
 #include "gp_math.h"
 #include "back_block.h"
@@ -436,403 +437,6 @@ __global__ __launch_bounds__(256) void gather_cov_kernel(GatherCovArgs a) {
 }
 void launch_gather_cov(const GatherCovArgs& a, int nbatch, hipStream_t st) {
     hipLaunchKernelGGL(gather_cov_kernel, dim3(a.nt * (a.nt + 1) / 2, nbatch), dim3(256), 0, st, a);
-}
-
-// ---------------------------------------------------------------------------------------
-// Predictive draws: ite[l, i, s*spp + d] = MeanITE_i + (L_c z)_i  (src/estimation.jl:95-109 with the
-// factor computed once per (sample, level) instead of once per draw).
-// Philox4x32-10 + Box-Muller, restated in oracle/gpslc_oracle.py:philox_normals.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                              unsigned k0, unsigned k1, unsigned out[4]) {
-#pragma unroll
-    for (int rd = 0; rd < 10; ++rd) {
-        const unsigned long long p0 = 0xD2511F53ull * c0;
-        const unsigned long long p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-        const unsigned n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        const unsigned n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ double philox_normal(unsigned long long seed, unsigned long long stream,
-                                                unsigned long long e) {
-    unsigned w[4];
-    const unsigned long long pair = e >> 1;
-    philox4x32_10((unsigned)pair, (unsigned)(pair >> 32), (unsigned)stream, (unsigned)(stream >> 32),
-                  (unsigned)seed, (unsigned)(seed >> 32), w);
-    const unsigned long long A = ((unsigned long long)w[0] << 21) ^ ((unsigned long long)w[1] >> 11);
-    const unsigned long long Bq = ((unsigned long long)w[2] << 21) ^ ((unsigned long long)w[3] >> 11);
-    const double u1 = ((double)A + 0.5) * (1.0 / 9007199254740992.0);
-    const double u2 = ((double)Bq + 0.5) * (1.0 / 9007199254740992.0);
-    const double rad = sqrt(-2.0 * log(u1));
-    const double ang = 6.283185307179586476925286766559 * u2;
-    return (e & 1ull) ? rad * sin(ang) : rad * cos(ang);
-}
-
-// One standard normal per (instance, draw) of every unit of the sub-batch, generated ONCE per unit into a
-// workspace laid out like the caller-supplied form (z[g + n*d] per unit): thread = one Philox counter = the
-// pair of elements (2p, 2p + 1) -> (cos, sin) branch of one Box-Muller transform, exactly the values
-// philox_normal() returns for those two elements.
-__global__ __launch_bounds__(256) void normals_kernel(unsigned long long seed, long long s0, long long S, int l, int lc,
-                                                      long long n, int spp, double* out) {
-    const long long b = blockIdx.y;             // (sample s0 + b / lc, level l + b % lc)
-    const unsigned long long stream = (unsigned long long)(s0 + b / lc + S * (long long)(l + b % lc));
-    const long long total = n * spp;                       // elements of this unit
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (2 * p >= total) return;
-    double* o = out + b * total;
-    o[2 * p] = philox_normal(seed, stream, (unsigned long long)(2 * p));
-    if (2 * p + 1 < total) o[2 * p + 1] = philox_normal(seed, stream, (unsigned long long)(2 * p + 1));
-}
-
-// The draws of one unit as a triangular matrix product on the f64 MFMA:  out[:, d] = mu + L_c z[:, d] for ALL
-// draws d of the unit in one pass over L_c (16 NQ draws per pass; spp <= 128 -> the factor is read exactly once).
-// One workgroup = one tile row of L_c (128 instances); wave w owns rows 32w..32w+31 as two row sets
-// {32w + 2j} and {32w + 2j + 1}, j = lane & 15: a lane fetches its two rows of a column with ONE 16-byte load
-// straight from HBM (every element of L_c is used by exactly one wave, so it never goes through LDS) and stores
-// its two results with one 16-byte store (16 lanes -> 256 contiguous bytes).  MFMA operands: A = z (draw index
-// = lane & 15), B = L_c (row = lane & 15), k = lane >> 4, so D[draw = 4v + (lane >> 4)][row = lane & 15].
-// z (64 columns x 16 NQ draws) is staged in LDS per half tile.  HBM-bound while 16 NQ <= 32 (one 128 KiB tile
-// per 0.5 NQ MFMA-microseconds), MFMA-bound beyond.
-#define DR_KC 64
-template <int NQ>
-__global__ __launch_bounds__(256) void draws_mfma_kernel(DrawArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double zs[];      // [DR_KC][ZLD]
-    constexpr int ND = 16 * NQ;
-    constexpr int ZLD = ND + 1;          // odd row stride: conflict-free column-wise staging writes
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, lq = lane >> 4;
-    const int ib = a.nt - 1 - (int)blockIdx.x;          // longest tile rows first
-    const long long b = blockIdx.y, sb = b / a.lc, lb = b % a.lc;      // batch element = (sample, level) pair
-    const long long s = a.s0 + sb, lev = a.l + lb;
-    const long long n = a.n;
-    const double* __restrict__ zu = a.z ? a.z + n * a.spp * (s + a.S * lev) : a.zgen + n * a.spp * b;
-    const int r0 = 32 * wave + 2 * li;                  // this lane's two rows inside the tile: r0, r0 + 1
-    const long long gi = (long long)ib * GP_TS + r0;
-
-    for (int d0 = 0; d0 < a.spp; d0 += ND) {
-        const int nd = min(ND, a.spp - d0);
-        d4 acc[2][NQ];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) acc[m][q] = (d4){0.0, 0.0, 0.0, 0.0};
-        // (rounds 2-4 ran 1..128 draws through this kernel, with a software-pipelined form for <= 16: since round 5 it serves units of
-        // more than 128 draws only — several passes over L_c; profiles/r05_draws_lds_kernel.patch has the removed branches)
-        for (int jt = 0; jt <= ib; ++jt) {
-            const double* __restrict__ t = tref_tile(a.Lc, b, ib, jt) + r0;
-#pragma unroll 1
-            for (int kc = 0; kc < GP_TS / DR_KC; ++kc) {
-                // this lane's rows of the 16 column groups of the chunk: 16 independent 16-byte loads in flight
-                d2 lv[DR_KC / 4];
-#pragma unroll
-                for (int kk = 0; kk < DR_KC / 4; ++kk)
-                    lv[kk] = *reinterpret_cast<const d2*>(t + (kc * DR_KC + 4 * kk + lq) * GP_TS);
-                __syncthreads();
-                for (int idx = tid; idx < DR_KC * ND; idx += 256) {
-                    const int k = idx & (DR_KC - 1), dd = idx / DR_KC;
-                    const long long g = (long long)jt * GP_TS + kc * DR_KC + k;
-                    zs[k * ZLD + dd] = (dd < nd && g < n) ? zu[g + n * (d0 + dd)] : 0.0;
-                }
-                __syncthreads();
-                if (jt == ib) {     // diagonal tile: only the lower triangle belongs to L_c
-#pragma unroll
-                    for (int kk = 0; kk < DR_KC / 4; ++kk) {
-                        const int c = kc * DR_KC + 4 * kk + lq;
-                        if (c > r0) lv[kk].x = 0.0;
-                        if (c > r0 + 1) lv[kk].y = 0.0;
-                    }
-                }
-#pragma unroll
-                for (int kk = 0; kk < DR_KC / 4; ++kk) {
-                    const double* zr = zs + (4 * kk + lq) * ZLD + li;
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) {
-                        const double zf = zr[16 * q];
-                        acc[0][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(zf, lv[kk].x, acc[0][q], 0, 0, 0);
-                        acc[1][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(zf, lv[kk].y, acc[1][q], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        // acc[m][q][v]: row r0 + m, draw d0 + 16 q + 4 v + lq
-        if (gi < n) {
-            const double mu0 = a.mean[gi + n * (s + a.S * lev)];
-            const double mu1 = (gi + 1 < n) ? a.mean[gi + 1 + n * (s + a.S * lev)] : 0.0;
-            double* __restrict__ ob = a.out + a.obase + sb * a.osb + lb * a.osl + gi * a.osi;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int dd = 16 * q + 4 * v + lq;
-                    if (dd < nd) {
-                        double* o = ob + (long long)(d0 + dd) * a.osd;
-                        const double x0 = mu0 + acc[0][q][v], x1 = mu1 + acc[1][q][v];
-                        if (a.osi == 1 && gi + 1 < n && ((reinterpret_cast<unsigned long long>(o) & 15ull) == 0)) {
-                            *reinterpret_cast<d2*>(o) = (d2){x0, x1};
-                        } else {
-                            o[0] = x0;
-                            if (gi + 1 < n) o[a.osi] = x1;
-                        }
-                    }
-                }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// Round 5: the draws of a unit with spp <= 128 (the reference's default is 10; NQ = 1, 2, 4 or 8 blocks of 16 draws per pass;
-// more than 128 draws keep the LDS-staged multi-pass kernel above) as a PURE STREAM of L_c.
-// What the LDS kernel above left on the table (4.3 of the ~6 TB/s a read-only sweep reaches on this chip): its 4 waves
-// meet at two barriers per 64 columns (one wave's late line stalls four), its work items span 1..nt tiles (the last long
-// row runs alone at the end of the launch), and the diagonal tile is read whole.  Here
-//   * the unit's normals are laid out ONCE, by draws_zstage_kernel, as the MFMA A-operand image zt: the 16-byte word of
-//     lane (lq, li) for the column groups (2m, 2m + 1) of a 32-column chunk sits at lane-contiguous addresses, so a wave
-//     fetches its z operands with four fully coalesced 1 KiB loads per chunk — no LDS, no barrier, no dependence
-//     between the waves of a workgroup (draws 10..15 and columns >= n are zeros in the image);
-//   * a workgroup owns the tile-row PAIR (nt-1-p, p): every item streams nt + 1 tiles, whatever p;
-//   * wave w reads only the columns of the diagonal tile at or left of its own 32 rows (8 (w + 1) of the 32 groups);
-//   * three register sets of 4 factor loads + 2 z loads each (16-column chunks) in rotation, the next two chunks in flight
-//     under the current chunk's MFMAs, 104 VGPRs -> four workgroups per CU; factor loads carry the non-temporal hint (each
-//     line is used exactly once).  Measured (same box, 64 units x 10 draws at N = 4096): 4.30 -> 6.04 TB/s of factor stream;
-//     32-column chunks with two sets 5.6, and the number of workgroups per CU (2 / 3 / 4) does not matter;
-// MFMA operands, accumulators and the order of the k groups along a row are those of draws_mfma_kernel<1>: the chains
-// are the same, so the draws are bit-identical (skipped groups of the diagonal tile only ever added +-0).
-// ---------------------------------------------------------------------------------------
-// blocks of 16 draws the stream kernel works on for spp draws per unit: its template parameter NQ
-__host__ __device__ inline int draws_nq(int spp) { return spp <= 16 ? 1 : spp <= 32 ? 2 : spp <= 64 ? 4 : 8; }
-// index of z[column g][draw d] in a unit's operand image (16 * Np doubles)
-__host__ __device__ inline long long draws_zt_index(long long g, int d) {
-    return ((g >> 3) << 7) + ((g & 3) << 5) + ((long long)d << 1) + ((g >> 2) & 1);
-}
-
-// one thread = one 16-byte word of the image: columns g0 = 8 blk + lq and g0 + 4, draw d
-__global__ __launch_bounds__(256) void draws_zstage_kernel(DrawArgs a) {
-    const long long b = blockIdx.y, sb = b / a.lc, lb = b % a.lc;
-    const long long s = a.s0 + sb, lev = a.l + lb;
-    const long long n = a.n, Np = (long long)a.nt * GP_TS;
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;      // word t of the image; block q of 16 draws = words [q 8 Np, ...)
-    const int nq = draws_nq(a.spp);              // the stream kernel's NQ: every one of its blocks is written (zeros beyond spp)
-    if (t >= Np * 8 * nq) return;
-    const long long tq = t % (Np * 8);
-    const int d = (int)(tq & 15) + 16 * (int)(t / (Np * 8)), lq = (int)(tq >> 4) & 3;
-    const long long g0 = ((tq >> 6) << 3) + lq, g1 = g0 + 4;
-    double v0 = 0.0, v1 = 0.0;
-    if (d < a.spp) {
-        if (a.z) {
-            const double* __restrict__ zu = a.z + n * a.spp * (s + a.S * lev);
-            if (g0 < n) v0 = zu[g0 + n * d];
-            if (g1 < n) v1 = zu[g1 + n * d];
-        } else if ((n & 1) == 0) {
-            // n even: the elements e = g + n d and e ^ 1 of a unit's stream share one Philox counter and one Box-Muller
-            // transform (even -> cos, odd -> sin), and the lane that holds column g ^ 1 of the same draw is lane ^ 16 (lq ^ 1).
-            // The even-lq lane evaluates the pair of g0, the odd-lq lane the pair of g1 = g0 + 4, and they swap the halves:
-            // one counter, one log, one sqrt, one sincos per lane instead of two of each — the same values philox_normal()
-            // returns element by element.  (Whole waves reach this point together: Np * 8 * nq is a multiple of 64.)
-            const unsigned long long stream = (unsigned long long)((a.rs0 + sb) + a.rS * lev);
-            const bool odd = (lq & 1) != 0;
-            const long long ge = odd ? (g1 & ~1ll) : g0;            // the even column of the pair this lane evaluates
-            double c = 0.0, sn = 0.0;
-            if (d < a.spp && ge < n) {
-                unsigned w[4];
-                const unsigned long long pair = (unsigned long long)(ge + n * d) >> 1;
-                philox4x32_10((unsigned)pair, (unsigned)(pair >> 32), (unsigned)stream, (unsigned)(stream >> 32),
-                              (unsigned)a.seed, (unsigned)(a.seed >> 32), w);
-                const unsigned long long A = ((unsigned long long)w[0] << 21) ^ ((unsigned long long)w[1] >> 11);
-                const unsigned long long Bq = ((unsigned long long)w[2] << 21) ^ ((unsigned long long)w[3] >> 11);
-                const double u1 = ((double)A + 0.5) * (1.0 / 9007199254740992.0);
-                const double u2 = ((double)Bq + 0.5) * (1.0 / 9007199254740992.0);
-                const double rad = sqrt(-2.0 * log(u1));
-                const double ang = 6.283185307179586476925286766559 * u2;
-                c = rad * cos(ang);
-                sn = rad * sin(ang);
-            }
-            // even-lq lane: keeps cos as its v0 (column g0), sends sin to the partner's v0 (column g0 + 1);
-            // odd-lq lane: keeps sin as its v1 (column g1), sends cos to the partner's v1 (column g1 - 1)
-            const double give = odd ? c : sn;
-            const double got = __shfl_xor(give, 16, 64);
-            if (odd) { v0 = got; v1 = sn; } else { v0 = c; v1 = got; }
-            if (g0 >= n) v0 = 0.0;
-            if (g1 >= n) v1 = 0.0;
-        } else {
-            const unsigned long long stream = (unsigned long long)((a.rs0 + sb) + a.rS * lev);
-            if (g0 < n) v0 = philox_normal(a.seed, stream, (unsigned long long)(g0 + n * d));
-            if (g1 < n) v1 = philox_normal(a.seed, stream, (unsigned long long)(g1 + n * d));
-        }
-    }
-    *reinterpret_cast<d2*>(a.zt + b * Np * 16 * nq + 2 * t) = (d2){v0, v1};
-}
-
-// CC columns per chunk (CC / 4 k groups of the 16x16x4 MFMA), NS register sets in rotation, WPE waves per SIMD the
-// register allocation is held to
-template <int CC, int NS, int WPE, int NQ = 1>
-__global__ __launch_bounds__(256, WPE) void draws_stream_kernel(DrawArgs a) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, lq = lane >> 4;
-    const long long b = blockIdx.y, sb = b / a.lc, lb = b % a.lc;      // batch element = (sample, level) pair
-    const long long s = a.s0 + sb, lev = a.l + lb;
-    const long long n = a.n;
-    const long long Np = (long long)a.nt * GP_TS;
-    const double* __restrict__ zt = a.zt + b * Np * 16 * NQ + 2 * lane;      // block q of 16 draws: + q * 16 Np
-    const int r0 = 32 * wave + 2 * li;                  // this lane's two rows inside the tile: r0, r0 + 1
-    const int p = blockIdx.x;
-    constexpr int NL = CC / 4, NZ = CC / 8;             // 16-byte factor / z loads per chunk and lane
-
-    for (int half = 0; half < 2; ++half) {
-        const int ib = half == 0 ? a.nt - 1 - p : p;
-        if (half == 1 && 2 * p == a.nt - 1) break;      // odd nt: the middle row has no partner
-        // the tiles (ib, 0..ib) of a row are contiguous in both tile layouts
-        const double* __restrict__ Lrow = tref_tile(a.Lc, b, ib, 0) + r0 + lq * GP_TS;
-        const int nch = (GP_TS / CC) * ib + (32 / CC) * wave + 32 / CC;   // chunks up to and including the wave's diagonal block
-        d4 acc0[NQ], acc1[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) { acc0[q] = (d4){0.0, 0.0, 0.0, 0.0}; acc1[q] = acc0[q]; }
-        d2 lv[NS][NL], zv[NS][NQ * NZ];
-        auto load = [&](int c, d2 (&l)[NL], d2 (&z)[NQ * NZ]) {
-            c = min(c, nch - 1);                         // past the end: the last chunk again (keeps the loop body branch-free)
-            const double* __restrict__ zp = zt + (long long)c * (CC * 16);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q)
-#pragma unroll
-                for (int m = 0; m < NZ; ++m) z[q * NZ + m] = *reinterpret_cast<const d2*>(zp + q * (16 * Np) + m * 128);
-            const double* __restrict__ lp = Lrow + (long long)c * (CC * GP_TS);
-#pragma unroll
-            for (int kk = 0; kk < NL; ++kk)
-                l[kk] = __builtin_nontemporal_load(reinterpret_cast<const d2*>(lp + kk * 4 * GP_TS));
-        };
-        auto compute = [&](const d2 (&l)[NL], const d2 (&z)[NQ * NZ]) {
-#pragma unroll
-            for (int kk = 0; kk < NL; ++kk)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const double zf = (kk & 1) ? z[q * NZ + (kk >> 1)].y : z[q * NZ + (kk >> 1)].x;
-                    acc0[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(zf, l[kk].x, acc0[q], 0, 0, 0);
-                    acc1[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(zf, l[kk].y, acc1[q], 0, 0, 0);
-                }
-        };
-        // the chunks of the wave's own 32 x 32 diagonal block: only the lower triangle belongs to L_c
-        auto mask_diag = [&](d2 (&l)[NL], int c) {
-            const int cb = (c * CC) & 31;                // first column of the chunk relative to the wave's first row
-#pragma unroll
-            for (int kk = 0; kk < NL; ++kk) {
-                const int cc = cb + 4 * kk + lq;
-                if (cc > 2 * li) l[kk].x = 0.0;
-                if (cc > 2 * li + 1) l[kk].y = 0.0;
-            }
-        };
-        constexpr int ND = 32 / CC;                      // chunks of the diagonal block (1 or 2)
-#pragma unroll
-        for (int i = 0; i < NS; ++i) load(i, lv[i], zv[i]);
-        int c = 0;
-        for (; c + NS + ND - 1 < nch; c += NS) {         // chunks c .. c + NS - 1 are all left of the diagonal block
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                compute(lv[i], zv[i]);
-                load(c + NS + i, lv[i], zv[i]);
-            }
-        }
-        const int rem = nch - c;                         // ND .. NS + ND - 1 chunks left; the first min(rem, NS) are loaded
-#pragma unroll
-        for (int i = 0; i < NS + ND - 1; ++i) {
-            if (i < rem) {
-                if (i >= NS) load(c + i, lv[i % NS], zv[i % NS]);
-                if (i >= rem - ND) mask_diag(lv[i % NS], c + i);
-                compute(lv[i % NS], zv[i % NS]);
-            }
-        }
-        // acc{0,1}[q][v]: row r0 + {0,1}, draw 16 q + 4 v + lq
-        const long long gi = (long long)ib * GP_TS + r0;
-        if (gi < n) {
-            const double mu0 = a.mean[gi + n * (s + a.S * lev)];
-            const double mu1 = (gi + 1 < n) ? a.mean[gi + 1 + n * (s + a.S * lev)] : 0.0;
-            double* __restrict__ ob = a.out + a.obase + sb * a.osb + lb * a.osl + gi * a.osi;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int dd = 16 * q + 4 * v + lq;
-                if (dd < a.spp) {
-                    double* o = ob + (long long)dd * a.osd;
-                    const double x0 = mu0 + acc0[q][v], x1 = mu1 + acc1[q][v];
-                    if (a.osi == 1 && gi + 1 < n && ((reinterpret_cast<unsigned long long>(o) & 15ull) == 0)) {
-                        *reinterpret_cast<d2*>(o) = (d2){x0, x1};
-                    } else {
-                        o[0] = x0;
-                        if (gi + 1 < n) o[a.osi] = x1;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// Level sweep (L > 1): the draws of the sub-batch are produced level by level into tmp[b][l][d][i] (instance
-// fastest: coalesced stores) and rearranged ONCE into the reference's level-fastest tensor
-// ite[l + L*(i + n*(s*spp + d))] (src/prediction.jl:30-33) through LDS, so that both the reads (1 KiB runs along i)
-// and the writes (runs along l) are contiguous.
-#define SC_LC 32
-__global__ __launch_bounds__(256) void draws_scatter_kernel(const double* __restrict__ tmp, double* __restrict__ out,
-                                                            long long n, int L, int spp, long long s0) {
-    __shared__ double tl[SC_LC][GP_TS + 1];
-    const int tid = threadIdx.x;
-    const long long i0 = (long long)blockIdx.x * GP_TS;
-    const int d = blockIdx.y;
-    const long long b = blockIdx.z;
-    const double* src = tmp + ((b * L) * spp + d) * n;                                // + l*spp*n + i
-    double* dst = out + (long long)L * n * ((s0 + b) * spp + d);                       // + l + L*i
-    for (int l0 = 0; l0 < L; l0 += SC_LC) {
-        const int nl = min(SC_LC, L - l0);
-        __syncthreads();
-        for (int idx = tid; idx < SC_LC * GP_TS; idx += 256) {
-            const int ll = idx >> 7, ii = idx & 127;
-            if (ll < nl && i0 + ii < n) tl[ll][ii] = src[(long long)(l0 + ll) * spp * n + i0 + ii];
-        }
-        __syncthreads();
-        for (int idx = tid; idx < SC_LC * GP_TS; idx += 256) {
-            const int ll = idx & (SC_LC - 1), ii = idx / SC_LC;
-            if (ll < nl && i0 + ii < n) dst[(l0 + ll) + (long long)L * (i0 + ii)] = tl[ll][ii];
-        }
-    }
-}
-
-template <int NQ>
-static void launch_draws_t(const DrawArgs& a, int nbatch, hipStream_t st) {
-    const int bytes = DR_KC * (16 * NQ + 1) * 8;
-    static DeviceOnce once;
-    lds_opt_in(once, (const void*)draws_mfma_kernel<NQ>, bytes);
-    hipLaunchKernelGGL((draws_mfma_kernel<NQ>), dim3(a.nt, nbatch), dim3(256), bytes, st, a);
-}
-void launch_draws(const DrawArgs& a, int nbatch, hipStream_t st) {
-    if (a.spp <= 128 && a.zt) {    // up to 128 draws = one pass over L_c: the barrier-free stream of L_c (round 5)
-        const long long words = (long long)a.nt * GP_TS * 8 * draws_nq(a.spp);
-        hipLaunchKernelGGL(draws_zstage_kernel, dim3((unsigned)((words + 255) / 256), nbatch), dim3(256), 0, st, a);
-        const dim3 grid((a.nt + 1) / 2, nbatch);
-        // more than 16 draws: NQ z blocks and accumulator pairs per wave.  HBM-bound up to 32 draws, MFMA-bound beyond (the
-        // factor is still read exactly once): fewer, fatter waves
-        if (a.spp > 64) { hipLaunchKernelGGL((draws_stream_kernel<16, 2, 1, 8>), grid, dim3(256), 0, st, a); return; }
-        if (a.spp > 32) { hipLaunchKernelGGL((draws_stream_kernel<16, 3, 2, 4>), grid, dim3(256), 0, st, a); return; }
-        if (a.spp > 16) { hipLaunchKernelGGL((draws_stream_kernel<16, 3, 3, 2>), grid, dim3(256), 0, st, a); return; }
-        // register-set arrangements tried (profiles/r05_ab_experiments.md §1): <32,2,2> 5.62-5.65 TB/s, <32,2,3> 5.59, <32,3,2> 5.55,
-        // <16,4,3> 5.60, <16,4,4> 6.02, <16,3,4> 6.04 (this one) on one box; 5.5-5.6 for every one of them on another
-        hipLaunchKernelGGL((draws_stream_kernel<16, 3, 4>), grid, dim3(256), 0, st, a);
-        return;
-    }
-    if (!a.z) {     // the library's own stream: every normal of the unit is generated exactly once
-        const long long pairs = ((long long)a.n * a.spp + 1) / 2;
-        hipLaunchKernelGGL(normals_kernel, dim3((unsigned)((pairs + 255) / 256), nbatch), dim3(256), 0, st, a.seed, a.rs0,
-                           a.rS, a.l, a.lc, (long long)a.n, a.spp, a.zgen);
-    }
-    launch_draws_t<8>(a, nbatch, st);      // more than 128 draws per unit: passes of 128
-}
-void launch_draws_scatter(const double* tmp, double* out, long long n, int L, int spp, long long s0, int nbatch,
-                          hipStream_t st) {
-    hipLaunchKernelGGL(draws_scatter_kernel, dim3((unsigned)((n + GP_TS - 1) / GP_TS), spp, nbatch), dim3(256), 0, st,
-                       tmp, out, n, L, spp, s0);
 }
 
 // ---------------------------------------------------------------------------------------

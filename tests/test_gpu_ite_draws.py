@@ -4,8 +4,8 @@ changes hands:
 
 - odd tile counts (nt = 3, 5, 7: the streaming draw kernel pairs tile rows (nt-1-p, p) and leaves the middle row alone) and
   ragged last tiles, both parities of n;
-- every draw kernel (spp <= 16, the 2 / 4 / 8 block variants, the MFMA kernel with its own normals beyond 128) at odd nt;
-- the library's Philox normals at size (odd n: the element-wise branch of the operand staging; spp > 128: normals_kernel);
+- every draw kernel (spp <= 16, the 2 / 4 / 8 block variants, a second pass of the stream kernel beyond 128) at odd nt;
+- the library's Philox normals at size (odd n: the element-wise branch of the operand staging; spp > 128: the staging of a second pass);
 - sub-batches of (sample, level) pairs beyond the first: sample groups at g0 > 0, level chunks at l0 > 0, the 32-level chunks
   of the level-sweep scatter, a gpslc_set_ensemble placement, and the chunking of gpslc_set_tuning (bit for bit);
 - the documented example's call (NEEC: 91 samples x 101 levels x 2 draws, jitter 1e-10);
@@ -105,8 +105,8 @@ SPPS = (1, 16, 17, 32, 33, 64, 65, 128, 129, 130)
 
 @pytest.mark.parametrize("n", [639, 384])
 def test_every_draw_kernel_at_an_odd_tile_count(gp, n):
-    """spp across the five draw kernels (<= 16, <= 32, <= 64, <= 128: the streaming kernel's block variants; > 128: the MFMA
-    kernel with normals_kernel) at nt = 5 (ragged) and nt = 3 (full tiles), L = 1, every draw.  One host factor per pair
+    """spp across the draw kernels (<= 16, <= 32, <= 64, <= 128: the streaming kernel's block variants; > 128: a second pass
+    of one or two draws) at nt = 5 (ragged) and nt = 3 (full tiles), L = 1, every draw.  One host factor per pair
     serves every spp (the reference draws with all columns of z at once)."""
     S = 2
     c = cases.make_case(n, "UX", False, S=S, seed=3 * n)
@@ -137,7 +137,7 @@ def test_every_draw_kernel_at_an_odd_tile_count(gp, n):
 @pytest.mark.parametrize("spp", [10, 130])
 def test_philox_draws_at_size(gp, n, spp):
     """Seeded draws = the same call with z from orc.philox_normals(seed, s + S*l, n*spp) (1e-12 of max |draw|: host and device
-    libm may differ by an ulp) and = the host reference; odd and even n, the staged image (spp <= 128) and normals_kernel."""
+    libm may differ by an ulp) and = the host reference; odd and even n, the staged image of one pass (spp <= 128) and of two."""
     S, L, seed = 2, 2, 20 + n + spp
     c = cases.make_case(n, "UX", False, S=S, seed=n + spp)
     doTs = np.array([-0.2, 0.5])
@@ -147,6 +147,35 @@ def test_philox_draws_at_size(gp, n, spp):
     _, _, _, dr_z = gp.predict(g, doTs, spp=spp, z=z, want_draws=True)
     assert np.max(np.abs(dr_p - dr_z)) <= 1e-12 * np.max(np.abs(dr_z))
     _check_draws(dr_p, c, doTs, _all_pairs(S, L), z)
+
+
+# ---- draws per unit do not change a draw ---------------------------------------------------------------------------------
+
+SPP_PAIRS = ((128, 130), (128, 257), (130, 257))
+
+
+@pytest.mark.parametrize("n", [129, 256, 383])
+def test_draw_bits_do_not_depend_on_spp(gp, n):
+    """The same case and seed with spp = 128, 130 and 257 draws per unit (one pass over the factor, a second pass of two draws,
+    two full passes and one draw): column s*spp + d of a shorter call equals column s*spp' + d of a longer one BIT FOR BIT,
+    for every d both have — seeded (element e = g + n d and the Philox stream do not depend on spp) and with the caller's z
+    (the shorter call's z is the longer call's leading draw columns): a draw's column depends only on its z column and on
+    the factor.  n = 129: odd, one live row in tile 2; 256: even, two full tiles (the pair branch of the staging);
+    383: nt = 3, the middle tile row has no partner."""
+    S, seed = 2, 900 + n
+    c = cases.make_case(n, "UX", False, S=S, seed=n)
+    g = _obj(gp, c)
+    doTs = np.array([0.3])
+    z_all = np.random.default_rng(n).standard_normal((n, 257, S, 1))
+    seeded, given = {}, {}
+    for spp in (128, 130, 257):
+        seeded[spp] = gp.predict(g, doTs, spp=spp, seed=seed, want_draws=True)[3]
+        given[spp] = gp.predict(g, doTs, spp=spp, z=np.asfortranarray(z_all[:, :spp]), want_draws=True)[3]
+        assert seeded[spp].shape == (1, n, S * spp)
+    for form, dr in (("seeded", seeded), ("z", given)):
+        for a, b in SPP_PAIRS:
+            for s in range(S):
+                assert np.array_equal(dr[a][0][:, s * a:(s + 1) * a], dr[b][0][:, s * b:s * b + a]), (form, n, a, b, s)
 
 
 # ---- sub-batch splits at nt >= 3 -----------------------------------------------------------------------------------------

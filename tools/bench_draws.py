@@ -2,7 +2,7 @@
 """Unit C of SURVEY.md §8d on its own clock: HIP-event time of the predictive-draw launches (gpslc profile class 2) for
 `samples x levels` units of `spp` draws at size N, as TB/s of factor stream (4 N^2 B per unit, SURVEY's algorithmic figure),
 plus a SHA-256 of the draw tensor — two builds that claim bit-identical draws must print the same digest.
-Usage: bench_draws.py [--diag-lib] [N samples levels spp reps]"""
+Usage: bench_draws.py [--diag-lib | --lib PATH] [N samples levels spp reps]   (--lib: another build of the library, for an A/B)"""
 import ctypes as C
 import hashlib
 import os
@@ -17,6 +17,10 @@ from causalgpslc_jl_amd import synth    # noqa: E402
 if "--diag-lib" in sys.argv:      # measurement build (GPSLC_* switches live there only)
     sys.argv.remove("--diag-lib")
     gp._lib.LIB_PATH = gp._lib.LIB_PATH.replace("libgpslc_hip.so", "libgpslc_hip_diag.so")
+if "--lib" in sys.argv:           # measurement only: this build of the library instead
+    i = sys.argv.index("--lib")
+    gp._lib.LIB_PATH = os.path.abspath(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 n, S, L, spp, reps = (int(a) for a in (sys.argv[1:6] + ["4096", "8", "8", "10", "3"][len(sys.argv) - 1:]))
 D, K = 8, 2
 X, T, Y, obj = synth.make_dataset(n, D)
