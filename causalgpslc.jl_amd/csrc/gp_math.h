@@ -39,6 +39,12 @@ __device__ __forceinline__ double gp_exp_neg(double x) {
     return ldexp(p, (int)k);
 }
 
+// The treatment kernel exp(-(x - y)^2 / tyLS^2), wt = 1 / tyLS^2, of every fp64 site outside the table-driven pair loops.  The
+// exact-zero identities (doT == T, d == T, a == b) need equal arguments to give equal values: the same square into the same exp.
+__device__ __forceinline__ double gp_rho(double x, double y, double wt) {
+    const double d = x - y;
+    return gp_exp_neg(-((d * d) * wt));
+}
 
 // Table-driven variant for the two fp64-VALU-bound kernels of unit A (Gram build, MeanITE pass): x = (32 e + j) ln2/32 + r,
 // |r| <= ln2/64, exp(x) = 2^e * T[j] * (1 + q(r)) with T[j] = 2^(j/32) (32 correctly rounded doubles staged in LDS: a 256-byte

@@ -127,7 +127,7 @@ struct SampleParams {
 };
 
 // The samples of a chunk and their feature blocks [U_s | X]: what every kernel that evaluates the RBF kernel starts from.  The
-// two members carry address arithmetic and one load only; the callers keep their own 1.0 / ls and multiplication order.
+// two members carry address arithmetic and one load only; stage_scaled_features below is the one place that divides by ls.
 struct SampleGrid {
     const double* X;   // n x nX (ctx or override)
     const double* T;   // n
@@ -141,6 +141,25 @@ struct SampleGrid {
         return f < nU ? p.uyLS[s * nU + f] : p.xyLS[s * nX + (f - nU)];
     }
 };
+
+// Features / lengthscale of COUNT consecutive individuals from g0 into LDS, by a workgroup of 256 threads: FS >= F rows of
+// COUNT, zeros beyond n and in the rows F .. FS - 1.  (x - x')^2 / ls^2 = (x / ls - x' / ls)^2, and every kernel that
+// evaluates B_ij forms x / ls as x * (1.0 / ls): the same product everywhere, so the same B_ij everywhere.
+template <int COUNT, typename RT>
+__device__ __forceinline__ void stage_scaled_features(const SampleGrid& a, long long s, int F, int FS, int g0, RT* dst) {
+    for (int idx = threadIdx.x; idx < FS * COUNT; idx += 256) {
+        const int f = idx / COUNT, r = idx % COUNT;
+        dst[idx] = (RT)((f < F && g0 + r < a.n) ? a.column(s, f)[g0 + r] * (1.0 / a.lengthscale(s, f)) : 0.0);
+    }
+}
+
+// lower-packed tile index t = ii (ii + 1) / 2 + jj, 0 <= jj <= ii, back to (ii, jj)
+__host__ __device__ __forceinline__ void tri_decode(int t, int& ii, int& jj) {
+    int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((long long)(r + 1) * (r + 2) / 2 <= t) ++r;
+    while ((long long)r * (r + 1) / 2 > t) --r;
+    ii = r; jj = t - (int)((unsigned)r * (unsigned)(r + 1) / 2u);     // r (r + 1) leaves 32 bits from t = 2^30 on
+}
 
 struct GramArgs : SampleGrid {
     TRef M;            // lower-packed tile matrix of the chunk

@@ -16,11 +16,6 @@
 #include "gpslc_internal.h"
 #include "gp_math.h"
 
-__device__ __forceinline__ double curve_rho(double x, double y, double wt) {
-    const double d = x - y;
-    return gp_exp_neg(-((d * d) * wt));
-}
-
 // grid (G, batch).  prior[b][g][0] = beta, [1] = kappa, [2 + l] = gamma_l; the contrast form needs beta alone (kw is not
 // computed for it and is not read)
 template <bool CON>
@@ -50,7 +45,7 @@ __global__ __launch_bounds__(256) void curve_prior_kernel(CurveArgs a) {
         double acc = 0.0;
         for (int j = tid; j < a.n; j += 256) {
             const double w = a.W[(long long)j * a.G + g];
-            acc = fma(w * curve_rho(a.T[j], dot, wt), bs[j], acc);
+            acc = fma(w * gp_rho(a.T[j], dot, wt), bs[j], acc);
         }
         const double gam = block_sum_256(acc, red);
         if (tid == 0) out[2 + l] = gam;
@@ -116,9 +111,9 @@ __global__ __launch_bounds__(256) void curve_gram_kernel(CurveArgs a) {
     double P;
     if (CON) {
         const double x = a.doT[l], y = a.doT_base[l], xp = a.doT[lp], yp = a.doT_base[lp];
-        P = ((curve_rho(x, xp, wt) - curve_rho(x, yp, wt)) - (curve_rho(y, xp, wt) - curve_rho(y, yp, wt))) * pr[0];
+        P = ((gp_rho(x, xp, wt) - gp_rho(x, yp, wt)) - (gp_rho(y, xp, wt) - gp_rho(y, yp, wt))) * pr[0];
     } else {
-        P = ((curve_rho(a.doT[l], a.doT[lp], wt) * pr[0] - pr[2 + l]) - pr[2 + lp]) + pr[1];
+        P = ((gp_rho(a.doT[l], a.doT[lp], wt) * pr[0] - pr[2 + l]) - pr[2 + lp]) + pr[1];
     }
     const double val = P - gram;
     cov[a.S * ((long long)l + (long long)a.L * lp)] = val;

@@ -38,13 +38,7 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
     const unsigned long long dr0 = g.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
 #endif
     int ti, tj;
-    {
-        const int t = blockIdx.x;
-        int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while ((long long)(r + 1) * (r + 2) / 2 <= t) ++r;
-        while ((long long)r * (r + 1) / 2 > t) --r;
-        ti = r; tj = t - r * (r + 1) / 2;
-    }
+    tri_decode(blockIdx.x, ti, tj);
     const int n = g.n;
     const int gi0 = ti * GP_TS, gj0 = tj * GP_TS;
 
@@ -76,13 +70,8 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
             }
         }
     } else {
-        for (int idx = tid; idx < F * GP_TS; idx += 256) {
-            const int f = idx >> 7, r = idx & 127;
-            const double* src = g.column(s, f);
-            const double il = 1.0 / g.lengthscale(s, f);
-            fr[f * GP_TS + r] = (RT)((gi0 + r < n) ? src[gi0 + r] * il : 0.0);
-            fc[f * GP_TS + r] = (RT)((gj0 + r < n) ? src[gj0 + r] * il : 0.0);
-        }
+        stage_scaled_features<GP_TS>(g, s, F, F, gi0, fr);
+        stage_scaled_features<GP_TS>(g, s, F, F, gj0, fc);
     }
     if (tid < GP_TS) {
         tr[tid] = (RT)((gi0 + tid < n) ? g.T[gi0 + tid] : 0.0);
@@ -275,8 +264,7 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
     const double wt = 1.0 / (tl * tl);
     if (CON) {
         for (int l = tid; l < a.L; l += 256) {
-            const double dab = a.doT[l] - a.doT_base[l];
-            const double rho = gp_exp_neg(-((dab * dab) * wt));
+            const double rho = gp_rho(a.doT[l], a.doT_base[l], wt);
             a.sumdelta[(long long)b * a.L + l] = ((1.0 - rho) + (1.0 - rho)) * btot;
         }
         return;
@@ -286,8 +274,7 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
         double acc = 0.0;
         for (int j = tid; j < Np; j += 256) {
             // same thread -> j assignment and the same tree as btot, so r == 1 reproduces btot bit for bit
-            const double dt = (j < a.n ? a.T[j] : 0.0) - dot;
-            const double r = gp_exp_neg(-((dt * dt) * wt));
+            const double r = gp_rho(j < a.n ? a.T[j] : 0.0, dot, wt);
             acc += r * bs[j];
         }
         const double rb = block_sum_256(acc, red);
@@ -302,12 +289,8 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
 // grid (nt + naug, naug, batch): tile (nt + a, j) with j = blockIdx.x, a = blockIdx.y (j <= nt + a).
 template <bool CON>
 __device__ __forceinline__ double rhs_level_value(const RhsArgs& a, int l, int gj, double wt, const double* bs, const double* ks) {
-    const double dt = a.T[gj] - a.doT[l];
-    const double r = gp_exp_neg(-((dt * dt) * wt));
-    if (CON) {
-        const double db = a.T[gj] - a.doT_base[l];
-        return (r - gp_exp_neg(-((db * db) * wt))) * bs[gj];
-    }
+    const double r = gp_rho(a.T[gj], a.doT[l], wt);
+    if (CON) return (r - gp_rho(a.T[gj], a.doT_base[l], wt)) * bs[gj];
     return r * bs[gj] - ks[gj];
 }
 template <bool CON>
@@ -379,8 +362,7 @@ __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
         if (CON) {
             acc += w * bs[j];
         } else {
-            const double dt = a.T[j] - dot;
-            const double r = gp_exp_neg(-((dt * dt) * wt));
+            const double r = gp_rho(a.T[j], dot, wt);
             acc += w * ((ks[j] - 2.0 * r * bs[j]) + bs[j]);
         }
     }
@@ -391,8 +373,7 @@ __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
     }
     if (tid != 0) return;
     if (CON) {
-        const double dab = dot - a.doT_base[l];
-        const double rho = gp_exp_neg(-((dab * dab) * wt));
+        const double rho = gp_rho(dot, a.doT_base[l], wt);
         a.sumdelta[(long long)b * a.L * a.G + qq] = ((1.0 - rho) + (1.0 - rho)) * tot;
     } else {
         a.sumdelta[(long long)b * a.L * a.G + qq] = tot;
@@ -566,13 +547,7 @@ void launch_process_cov(const double* in, long long n, double scale, double nois
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dense_load_kernel(DenseLoadArgs a) {
     int ti, tj;
-    {
-        const int t = blockIdx.x;
-        int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while ((long long)(r + 1) * (r + 2) / 2 <= t) ++r;
-        while ((long long)r * (r + 1) / 2 > t) --r;
-        ti = r; tj = t - r * (r + 1) / 2;
-    }
+    tri_decode(blockIdx.x, ti, tj);
     double* tile = tref_tile(a.M, 0, ti, tj);
     for (int idx = threadIdx.x; idx < GP_TSQ; idx += 256) {
         const int c = idx >> 7, r = idx & 127;

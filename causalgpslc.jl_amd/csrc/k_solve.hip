@@ -117,11 +117,7 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
             for (int ll = 0; ll < LCT; ++ll) acc[q][ll] = 0.0;
         for (int jt = 0; jt < a.nt; ++jt) {
             __syncthreads();
-            for (int idx = tid; idx < FREG * GP_TS; idx += 256) {
-                const int f = idx >> 7, cc = idx & 127;
-                const int g = jt * GP_TS + cc;
-                fc[idx] = (RT)((f < F && g < n) ? feat_src(f)[g] * feat_il(f) : 0.0);
-            }
+            stage_scaled_features<GP_TS>(a, s, F, FREG, jt * GP_TS, fc);
             for (int idx = tid; idx < LCT * GP_TS; idx += 256) {
                 const int ll = idx >> 7, cc = idx & 127;
                 const int g = jt * GP_TS + cc;
@@ -293,68 +289,59 @@ void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------
-// dt_build: tiles of D (D_ij = B_ij (r_j - e_ij), src/estimation.jl:46 "CovWWs' - CovWW") into the
-// rectangular matrix W and Delta + pred_noise*I (Delta_ij = B_ij (e_ij - r_i - r_j + 1) =
-// CovWW - CovWWs - CovWWs' + CovWsWs, src/likelihood.jl:46-49 / estimation.jl:47, :82) into Cm.
-// VEC (per-individual intervention d, k_vec.hip): r_i, r_j become g_ij = exp(-(T_i - d_j)^2 / tyLS^2), g_ji, and the 1 of
-// CovWsWs becomes h_ij = exp(-(d_i - d_j)^2 / tyLS^2); the staged rr_ / rc_ hold d of the row / column block instead of r.
-// CON (contrast of the scalar levels a = doT[l], b = doT_base[l], DESIGN.md §12): D_ij = B_ij (r^a_j - r^b_j) (rc_ holds the
-// difference) and Delta_ij = B_ij ((1 - rho) + (1 - rho)), rho = exp(-(a - b)^2 / tyLS^2) — exactly 0 when a == b.
+// The tile builders: one workgroup fills one 128 x 128 tile of every matrix whose element (i, j) is B_ij times a function of the
+// treatment kernel's values at the pair — D / Delta of the full ITE covariance (dt_build_kernel) and the four likelihood blocks
+// (ld_build_kernel).  tile_build_body is what they share: the LDS layout, the staging, the thread mapping (thread (ty, tx) owns
+// rows ty + 16p and columns 8 tx + q, as gram_kernel), (x/l - x'/l)^2 summed by fma in feature order, B_ij = yScale exp(-lux).
+// With rho(x, y) = exp(-(x - y)^2 / tyLS^2) (gp_rho) an element's level terms are
+//     e = rho(T_i, T_j)      g_ij = rho(T_i, d_j)      g_ji = rho(T_j, d_i)      h = rho(d_i, d_j)
+// for a per-individual intervention d (LEVEL_VECTOR; rr_ / rc_ hold d of the row / column block), and a scalar level doT is the
+// case g_ij = r_i, g_ji = r_j, h = 1 with r_i = rho(T_i, doT) staged in rr_ / rc_ (LEVEL_SCALAR).  LEVEL_NONE (contrasts) stages
+// the column block's values only, hands them over as g_ji and evaluates neither e nor the other terms.  A kernel supplies
+//   stage_level(g, t, wt)   what rr_ / rc_ hold for individual g (any g: the kernel decides what the padding gets) with
+//                           T_g = t (0.0 on the padding), wt = 1 / tyLS^2
+//   emit(rp, cq, inside, diag, Bv, terms)   element (row rp, column cq) of the tile: inside = both individuals < n, diag = on the
+//                           matrix diagonal, padding included; with level terms, Bv and the terms of an element outside
+//                           arrive as 0.0 (g_ji as staged).  Every element depends on its own row and column only.
 // ---------------------------------------------------------------------------------------
-template <bool VEC, bool CON = false>
-__global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
+enum { LEVEL_NONE, LEVEL_SCALAR, LEVEL_VECTOR };
+struct LevelTerms { double e, gij, gji, h; };
+template <bool VEC>
+__device__ __forceinline__ LevelTerms level_terms(double ti, double tj, double xi, double xj, double wt) {
+    const double e = gp_rho(ti, tj, wt);
+    if (VEC) return {e, gp_rho(ti, xj, wt), gp_rho(tj, xi, wt), gp_rho(xi, xj, wt)};
+    return {e, xi, xj, 1.0};
+}
+// LDS (doubles): fr [F][128] | fc [F][128] row / column features / LS | tr [128] | tc [128] T | rr_ [128] | rc_ [128]
+constexpr int tile_build_lds_bytes(int F) { return (2 * F * GP_TS + 4 * GP_TS) * 8; }
+
+template <int LEVEL, typename StageLevel, typename Emit>
+__device__ __forceinline__ void tile_build_body(const SampleGrid& a, long long s, int ti, int tj, double* sm,
+                                                StageLevel&& stage_level, Emit&& emit) {
     const int F = a.nU + a.nX;
     double* fr = sm;
     double* fc = fr + F * GP_TS;
     double* tr = fc + F * GP_TS;
     double* tc = tr + GP_TS;
-    double* rr_ = tc + GP_TS;   // r_i of the row block
-    double* rc_ = rr_ + GP_TS;  // r_j of the column block
+    double* rr_ = tc + GP_TS;
+    double* rc_ = rr_ + GP_TS;
     const int tid = threadIdx.x;
-    const int ti = blockIdx.x / a.nt, tj = blockIdx.x % a.nt;
-    const long long b = blockIdx.y, s = a.s0 + b / a.lc;       // batch element = (sample, level) pair
     const int n = a.n;
-    const double doT = VEC ? 0.0 : a.doT[a.l0 + (int)(b % a.lc)];
-    const double* dv = VEC ? a.doT + (long long)n * (a.l0 + (int)(b % a.lc)) : nullptr;
     const int gi0 = ti * GP_TS, gj0 = tj * GP_TS;
     const double tl = a.p.tyLS[s];
     const double wt = 1.0 / (tl * tl);
-    const double doTb = CON ? a.doT_base[a.l0 + (int)(b % a.lc)] : 0.0;
-    double kss = 0.0;       // CON: (1 - rho) + (1 - rho)
-    if (CON) {
-        const double dab = doT - doTb;
-        const double rho = gp_exp_neg(-((dab * dab) * wt));
-        kss = (1.0 - rho) + (1.0 - rho);
-    }
-    for (int idx = tid; idx < F * GP_TS; idx += 256) {
-        const int f = idx >> 7, r = idx & 127;
-        const double* src = a.column(s, f);
-        const double il = 1.0 / a.lengthscale(s, f);
-        fr[idx] = (gi0 + r < n) ? src[gi0 + r] * il : 0.0;
-        fc[idx] = (gj0 + r < n) ? src[gj0 + r] * il : 0.0;
-    }
+    stage_scaled_features<GP_TS>(a, s, F, F, gi0, fr);
+    stage_scaled_features<GP_TS>(a, s, F, F, gj0, fc);
     if (tid < GP_TS) {
         const double t1 = (gi0 + tid < n) ? a.T[gi0 + tid] : 0.0;
         const double t2 = (gj0 + tid < n) ? a.T[gj0 + tid] : 0.0;
         tr[tid] = t1; tc[tid] = t2;
-        if (VEC) {
-            rr_[tid] = (gi0 + tid < n) ? dv[gi0 + tid] : 0.0;
-            rc_[tid] = (gj0 + tid < n) ? dv[gj0 + tid] : 0.0;
-        } else if (CON) {
-            const double d2 = t2 - doT, b2 = t2 - doTb;
-            rc_[tid] = gp_exp_neg(-((d2 * d2) * wt)) - gp_exp_neg(-((b2 * b2) * wt));
-        } else {
-            const double d1 = t1 - doT, d2 = t2 - doT;
-            rr_[tid] = gp_exp_neg(-((d1 * d1) * wt));
-            rc_[tid] = gp_exp_neg(-((d2 * d2) * wt));
-        }
+        if (LEVEL != LEVEL_NONE) rr_[tid] = stage_level(gi0 + tid, t1, wt);
+        rc_[tid] = stage_level(gj0 + tid, t2, wt);
     }
     __syncthreads();
     const double ys = a.p.yScale[s];
     const int ty = tid & 15, tx = tid >> 4;
-    double* wt_tile = tref_tile(a.W, b, ti, tj);
-    double* c_tile = (ti >= tj) ? tref_tile(a.Cm, b, ti, tj) : nullptr;
 #pragma unroll 1
     for (int q = 0; q < 8; ++q) {
         const int cq = 8 * tx + q;
@@ -370,43 +357,77 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
                 lux[p] = fma(d, d, lux[p]);
             }
         }
-        const double tcq = tc[cq], rj = rc_[cq];
+        const double tcq = tc[cq], xj = rc_[cq];
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             const int rp = ty + 16 * p;
             const int gi = gi0 + rp;
-            const double dt = tr[rp] - tcq;
-            const double Bv = ys * gp_exp_neg(-lux[p]);
-            const double Ev = gp_exp_neg(-((dt * dt) * wt));
-            double Dv, Cv;
-            if (VEC) {
-                const double di = rr_[rp], gij = tr[rp] - rj, gji = tcq - di, hij = di - rj;
-                const double Gij = gp_exp_neg(-((gij * gij) * wt)), Gji = gp_exp_neg(-((gji * gji) * wt));
-                Dv = Bv * (Gji - Ev);
-                Cv = Bv * (((Ev - Gij) - Gji) + gp_exp_neg(-((hij * hij) * wt)));
-            } else if (CON) {
-                Dv = Bv * rj;
-                Cv = Bv * kss;
-            } else {
-                const double ri = rr_[rp];
-                Dv = Bv * (rj - Ev);
-                Cv = Bv * (((Ev - ri) - rj) + 1.0);
-            }
             const bool inside = (gi < n) && (gj < n);
-            if (!inside) { Dv = 0.0; Cv = (gi == gj) ? 1.0 : 0.0; }
-            else if (gi == gj) Cv += a.pred_noise;
-            wt_tile[cq * GP_TS + rp] = Dv;
-            if (c_tile) c_tile[cq * GP_TS + rp] = Cv;
+            double Bv = 0.0;
+            LevelTerms t{0.0, 0.0, xj, 0.0};
+            // The level terms stay under this branch: evaluated unconditionally, the eight rows' exp chains of a column
+            // interleave and the kernel no longer fits 8 waves per SIMD.  Contrasts (one exp per element) fit without it.
+            if (LEVEL == LEVEL_NONE || inside) {
+                Bv = ys * gp_exp_neg(-lux[p]);
+                if constexpr (LEVEL != LEVEL_NONE) t = level_terms<LEVEL == LEVEL_VECTOR>(tr[rp], tcq, rr_[rp], xj, wt);
+            }
+            emit(rp, cq, inside, gi == gj, Bv, t);
         }
     }
 }
-#define DT_LDS_BYTES(F) ((2 * (F) * GP_TS + 4 * GP_TS) * 8)
+
+// ---------------------------------------------------------------------------------------
+// dt_build: tiles of D (D_ij = B_ij (r_j - e_ij), src/estimation.jl:46 "CovWWs' - CovWW") into the
+// rectangular matrix W and Delta + pred_noise*I (Delta_ij = B_ij (e_ij - r_i - r_j + 1) =
+// CovWW - CovWWs - CovWWs' + CovWsWs, src/likelihood.jl:46-49 / estimation.jl:47, :82) into Cm, with the identity on the padding.
+// VEC (per-individual intervention d, k_vec.hip): D_ij = B_ij (g_ji - e_ij), Delta_ij = B_ij (e_ij - g_ij - g_ji + h_ij).
+// CON (contrast of the scalar levels a = doT[l], b = doT_base[l], DESIGN.md §12): D_ij = B_ij (r^a_j - r^b_j) (rc_ holds the
+// difference) and Delta_ij = B_ij ((1 - rho) + (1 - rho)), rho = exp(-(a - b)^2 / tyLS^2) — exactly 0 when a == b.
+// ---------------------------------------------------------------------------------------
+template <bool VEC, bool CON = false>
+__global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int ti = blockIdx.x / a.nt, tj = blockIdx.x % a.nt;
+    const long long b = blockIdx.y, s = a.s0 + b / a.lc;       // batch element = (sample, level) pair
+    const int l = a.l0 + (int)(b % a.lc), n = a.n;
+    const double doT = VEC ? 0.0 : a.doT[l], doTb = CON ? a.doT_base[l] : 0.0;
+    const double* dv = VEC ? a.doT + (long long)n * l : nullptr;
+    double kss = 0.0;       // CON: (1 - rho) + (1 - rho)
+    if (CON) {
+        const double tl = a.p.tyLS[s];
+        const double rho = gp_rho(doT, doTb, 1.0 / (tl * tl));
+        kss = (1.0 - rho) + (1.0 - rho);
+    }
+    double* wt_tile = tref_tile(a.W, b, ti, tj);
+    double* c_tile = (ti >= tj) ? tref_tile(a.Cm, b, ti, tj) : nullptr;
+    tile_build_body<CON ? LEVEL_NONE : VEC ? LEVEL_VECTOR : LEVEL_SCALAR>(
+        a, s, ti, tj, sm,
+        [&](int g, double t, double wt) {
+            if constexpr (VEC) return g < n ? dv[g] : 0.0;
+            else if constexpr (CON) return gp_rho(t, doT, wt) - gp_rho(t, doTb, wt);
+            else return gp_rho(t, doT, wt);
+        },
+        [&](int rp, int cq, bool inside, bool diag, double Bv, const LevelTerms& t) {
+            double Dv, Cv;
+            if (CON) {
+                Dv = Bv * t.gji;
+                Cv = Bv * kss;
+            } else {
+                Dv = Bv * (t.gji - t.e);
+                Cv = Bv * (((t.e - t.gij) - t.gji) + t.h);
+            }
+            if (!inside) { Dv = 0.0; Cv = diag ? 1.0 : 0.0; }
+            else if (diag) Cv += a.pred_noise;
+            wt_tile[cq * GP_TS + rp] = Dv;
+            if (c_tile) c_tile[cq * GP_TS + rp] = Cv;
+        });
+}
 
 template <bool VEC, bool CON = false>
 static void launch_dt_build_t(const DtArgs& a, int nbatch, hipStream_t st) {
     static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)dt_build_kernel<VEC, CON>, DT_LDS_BYTES(MAXF));
-    hipLaunchKernelGGL((dt_build_kernel<VEC, CON>), dim3(a.nt * a.nt, nbatch), dim3(256), DT_LDS_BYTES(a.nU + a.nX), st, a);
+    lds_opt_in(attr_set, (const void*)dt_build_kernel<VEC, CON>, tile_build_lds_bytes(MAXF));
+    hipLaunchKernelGGL((dt_build_kernel<VEC, CON>), dim3(a.nt * a.nt, nbatch), dim3(256), tile_build_lds_bytes(a.nU + a.nX), st, a);
 }
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st) {
     if (a.doT_base) launch_dt_build_t<false, true>(a, nbatch, st);
@@ -417,13 +438,7 @@ void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st) {
 // CovITEs[s + S*(i + n*j)] (src/estimation.jl:75, :82 layout: sample index fastest), both triangles
 __global__ __launch_bounds__(256) void gather_cov_kernel(GatherCovArgs a) {
     int ti, tj;
-    {
-        const int t = blockIdx.x;
-        int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while ((long long)(r + 1) * (r + 2) / 2 <= t) ++r;
-        while ((long long)r * (r + 1) / 2 > t) --r;
-        ti = r; tj = t - r * (r + 1) / 2;
-    }
+    tri_decode(blockIdx.x, ti, tj);
     const long long b = blockIdx.y, s = a.s0 + b;
     const double* t = tref_tile(a.Cm, b, ti, tj);
     for (int idx = threadIdx.x; idx < GP_TSQ; idx += 256) {
@@ -441,87 +456,41 @@ void launch_gather_cov(const GatherCovArgs& a, int nbatch, hipStream_t st) {
 
 // ---------------------------------------------------------------------------------------
 // likelihoodDistribution blocks (src/likelihood.jl:24-39): K = B.*E, Ks = diag(r) B, Ks' = B diag(r), Kss = B
-// VEC (per-individual intervention d): Ks = B.*G, Ks' = B.*G', Kss = B.*H with G_ij = exp(-(T_i - d_j)^2 / tyLS^2),
-// H_ij = exp(-(d_i - d_j)^2 / tyLS^2); rr_ / rc_ then hold d of the row / column block
+// VEC (per-individual intervention d): Ks = B.*G, Ks' = B.*G', Kss = B.*H with G_ij = g_ij, H_ij = h_ij of tile_build_body.
+// Zeros on the padding.
 // ---------------------------------------------------------------------------------------
 template <bool VEC>
 __global__ __launch_bounds__(256) void ld_build_kernel(LdBuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int F = a.nU + a.nX;
-    double* fr = sm;
-    double* fc = fr + F * GP_TS;
-    double* tr = fc + F * GP_TS;
-    double* tc = tr + GP_TS;
-    double* rr_ = tc + GP_TS;
-    double* rc_ = rr_ + GP_TS;
-    const int tid = threadIdx.x;
     const int ti = blockIdx.x / a.nt, tj = blockIdx.x % a.nt;
-    const long long s = a.s0;
     const int n = a.n;
-    const int gi0 = ti * GP_TS, gj0 = tj * GP_TS;
-    const double tl = a.p.tyLS[s];
-    const double wt = 1.0 / (tl * tl);
-    for (int idx = tid; idx < F * GP_TS; idx += 256) {
-        const int f = idx >> 7, r = idx & 127;
-        const double* src = a.column(s, f);
-        const double il = 1.0 / a.lengthscale(s, f);
-        fr[idx] = (gi0 + r < n) ? src[gi0 + r] * il : 0.0;
-        fc[idx] = (gj0 + r < n) ? src[gj0 + r] * il : 0.0;
-    }
-    if (tid < GP_TS) {
-        const double t1 = (gi0 + tid < n) ? a.T[gi0 + tid] : 0.0;
-        const double t2 = (gj0 + tid < n) ? a.T[gj0 + tid] : 0.0;
-        tr[tid] = t1; tc[tid] = t2;
-        if (VEC) {
-            rr_[tid] = (gi0 + tid < n) ? a.doTv[gi0 + tid] : 0.0;
-            rc_[tid] = (gj0 + tid < n) ? a.doTv[gj0 + tid] : 0.0;
-        } else {
-            const double d1 = t1 - a.doT, d2 = t2 - a.doT;
-            rr_[tid] = gp_exp_neg(-((d1 * d1) * wt));
-            rc_[tid] = gp_exp_neg(-((d2 * d2) * wt));
-        }
-    }
-    __syncthreads();
-    const double ys = a.p.yScale[s];
     double* tK = tref_tile(a.K, 0, ti, tj);
     double* tKs = tref_tile(a.Ks, 0, ti, tj);
     double* tKsT = tref_tile(a.KsT, 0, ti, tj);
     double* tKss = tref_tile(a.Kss, 0, ti, tj);
-    for (int idx = tid; idx < GP_TSQ; idx += 256) {
-        const int c = idx >> 7, r = idx & 127;
-        double lux = 0.0;
-        for (int f = 0; f < F; ++f) {
-            const double d = fr[f * GP_TS + r] - fc[f * GP_TS + c];
-            lux = fma(d, d, lux);
-        }
-        const double dt = tr[r] - tc[c];
-        double Bv = ys * gp_exp_neg(-lux);
-        double Ev = gp_exp_neg(-((dt * dt) * wt));
-        if (gi0 + r >= n || gj0 + c >= n) { Bv = 0.0; Ev = 0.0; }
-        tK[idx] = Bv * Ev;
-        if (VEC) {
-            const double gij = tr[r] - rc_[c], gji = tc[c] - rr_[r], hij = rr_[r] - rc_[c];
-            tKs[idx] = gp_exp_neg(-((gij * gij) * wt)) * Bv;
-            tKsT[idx] = Bv * gp_exp_neg(-((gji * gji) * wt));
-            tKss[idx] = Bv * gp_exp_neg(-((hij * hij) * wt));
-        } else {
-            tKs[idx] = rr_[r] * Bv;
-            tKsT[idx] = Bv * rc_[c];
-            tKss[idx] = Bv;
-        }
-    }
+    tile_build_body<VEC ? LEVEL_VECTOR : LEVEL_SCALAR>(
+        a, a.s0, ti, tj, sm,
+        [&](int g, double t, double wt) {
+            if constexpr (VEC) return g < n ? a.doTv[g] : 0.0;
+            else return gp_rho(t, a.doT, wt);
+        },
+        [&](int rp, int cq, bool inside, bool, double Bv, const LevelTerms& t) {
+            const int idx = cq * GP_TS + rp;
+            tK[idx] = inside ? Bv * t.e : 0.0;
+            tKs[idx] = inside ? t.gij * Bv : 0.0;
+            tKsT[idx] = inside ? Bv * t.gji : 0.0;
+            tKss[idx] = inside ? Bv * t.h : 0.0;
+        });
+}
+template <bool VEC>
+static void launch_ld_build_t(const LdBuildArgs& a, hipStream_t st) {
+    static DeviceOnce attr_set;
+    lds_opt_in(attr_set, (const void*)ld_build_kernel<VEC>, tile_build_lds_bytes(MAXF));
+    hipLaunchKernelGGL(ld_build_kernel<VEC>, dim3(a.nt * a.nt), dim3(256), tile_build_lds_bytes(a.nU + a.nX), st, a);
 }
 void launch_ld_build(const LdBuildArgs& a, hipStream_t st) {
-    const int F = a.nU + a.nX;
-    const int bytes = (2 * F * GP_TS + 4 * GP_TS) * 8;
-    static DeviceOnce attr_set, attr_set_v;
-    if (a.doTv) {
-        lds_opt_in(attr_set_v, (const void*)ld_build_kernel<true>, (2 * MAXF * GP_TS + 4 * GP_TS) * 8);
-        hipLaunchKernelGGL(ld_build_kernel<true>, dim3(a.nt * a.nt), dim3(256), bytes, st, a);
-        return;
-    }
-    lds_opt_in(attr_set, (const void*)ld_build_kernel<false>, (2 * MAXF * GP_TS + 4 * GP_TS) * 8);
-    hipLaunchKernelGGL(ld_build_kernel<false>, dim3(a.nt * a.nt), dim3(256), bytes, st, a);
+    if (a.doTv) launch_ld_build_t<true>(a, st);
+    else launch_ld_build_t<false>(a, st);
 }
 
 __global__ __launch_bounds__(256) void rect_gather_kernel(RectGatherArgs a) {

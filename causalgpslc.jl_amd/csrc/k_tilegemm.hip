@@ -73,15 +73,6 @@
 #endif
 #define FUSE_WD 8                      // inv(L) fragments in flight ahead of their MFMAs (strip kernel)
 
-__device__ __forceinline__ void tri_decode(int t, int& ii, int& jj) {
-    // t = ii(ii+1)/2 + jj, 0 <= jj <= ii
-    int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((long long)(r + 1) * (r + 2) / 2 <= t) ++r;
-    while ((long long)r * (r + 1) / 2 > t) --r;
-    ii = r;
-    jj = t - r * (r + 1) / 2;
-}
-
 template <int NEG>
 __device__ __forceinline__ d4 mfma_step(double a, double b, d4 c) {
     // blgp bit 0 = negate the MFMA A operand (f64 MFMA re-uses BLGP as NEG[2:0])

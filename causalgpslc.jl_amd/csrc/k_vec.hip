@@ -42,15 +42,7 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
     const int go = ot * GP_TS + o;
     const bool own_in = go < n;
 
-    auto feat = [&](int f, int i) -> double {
-        const double* src = a.column(s, f);
-        const double il = 1.0 / a.lengthscale(s, f);
-        return src[i] * il;
-    };
-    for (int idx = tid; idx < F * GP_TS; idx += 256) {
-        const int f = idx >> 7, r = idx & 127, g = ot * GP_TS + r;
-        fo[idx] = g < n ? feat(f, g) : 0.0;
-    }
+    stage_scaled_features<GP_TS>(a, s, F, F, ot * GP_TS, fo);
     gp_exp_tab_stage(etab, tid);
 
     const double ys = a.p.yScale[s];
@@ -68,10 +60,7 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
     for (int kt = 0; kt < a.nt; ++kt) {
         const int k0 = kt * GP_TS;
         __syncthreads();
-        for (int idx = tid; idx < F * GP_TS; idx += 256) {
-            const int f = idx >> 7, r = idx & 127;
-            fk[idx] = k0 + r < n ? feat(f, k0 + r) : 0.0;
-        }
+        stage_scaled_features<GP_TS>(a, s, F, F, k0, fk);
         if (tid < GP_TS) tk[tid] = k0 + tid < n ? a.T[k0 + tid] : 0.0;
         if (SUMS) {
             for (int idx = tid; idx < LB * GP_TS; idx += 256) {
@@ -176,7 +165,7 @@ static void launch_vec_t(const VecArgs& a, int nbatch, hipStream_t st) {
     const int bytes = (GP_EXP_TAB_DOUBLES + 2 * F * GP_TS + GP_TS + LB * GP_TS + 2 * LB * GP_TS) * 8;
     static DeviceOnce attr_set;
     lds_opt_in(attr_set, (const void*)vec_pair_kernel<LB, SUMS>,
-               (GP_EXP_TAB_DOUBLES + 2 * 32 * GP_TS + GP_TS + 3 * LB * GP_TS) * 8);
+               (GP_EXP_TAB_DOUBLES + 2 * MAXF * GP_TS + GP_TS + 3 * LB * GP_TS) * 8);
     hipLaunchKernelGGL((vec_pair_kernel<LB, SUMS>), dim3(a.nt, (a.L + LB - 1) / LB, nbatch), dim3(256), bytes, st, a);
 }
 template <bool SUMS>

@@ -84,13 +84,7 @@ __device__ __forceinline__ void pair_mfma_body(const SampleGrid& a, long long s,
     const int ib = blockIdx.x;
     const int n = a.n, Np = a.nt * GP_TS;
 
-    auto feat_src = [&](int f) { return a.column(s, f); };
-    auto feat_il = [&](int f) { return 1.0 / a.lengthscale(s, f); };
-    for (int idx = tid; idx < F * GP_TS; idx += 256) {
-        const int f = idx >> 7, rr = idx & 127;
-        const int g = ib * GP_TS + rr;
-        fr[idx] = (g < n) ? feat_src(f)[g] * feat_il(f) : 0.0;
-    }
+    stage_scaled_features<GP_TS>(a, s, F, F, ib * GP_TS, fr);
     const double ys = a.p.yScale[s];
     const double tl = a.p.tyLS[s];
     const double wt = 1.0 / (tl * tl);
@@ -122,11 +116,7 @@ __device__ __forceinline__ void pair_mfma_body(const SampleGrid& a, long long s,
             }
         for (int c0 = 0; c0 < Np; c0 += PM_CC) {
             __syncthreads();
-            for (int idx = tid; idx < FS * PM_CC; idx += 256) {
-                const int f = idx / PM_CC, cc = idx - f * PM_CC;
-                const int g = c0 + cc;
-                fc[idx] = (f < F && g < n) ? feat_src(f)[g] * feat_il(f) : 0.0;
-            }
+            stage_scaled_features<PM_CC>(a, s, F, FS, c0, fc);
             if (WK && tid < PM_CC) tc[tid] = (c0 + tid < n) ? a.T[c0 + tid] : 0.0;
             for (int idx = tid; idx < PM_CC * PM_NL; idx += 256) {
                 const int cc = idx >> 6, ll = idx & 63;      // consecutive threads -> consecutive right-operand columns
