@@ -28,6 +28,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // ---------------------------------------------------------------------------------------
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 struct DeviceOnce {
     std::atomic<unsigned long long> mask{0};
 };
@@ -142,14 +143,26 @@ struct SampleGrid {
     }
 };
 
+// Element i of a column (a feature, or T) as the RT arithmetic stages it.  fp32 (GPSLC_FLAG_FP32_KERNEL): minus the column's
+// first element, subtracted in fp64 BEFORE the value is scaled and rounded to fp32 — the RBF model sees differences only, and
+// rounding x / ls itself would cost eps32 |x| / ls per difference, which grows with the distance of the data from the origin
+// (a column of calendar years: 1e-4).  One centre per (sample, column), the same in every kernel: the same B_ij everywhere.
+// fp64: the value itself, the code it always was (eps64 |x| / ls is 1e-13 at |x| / ls = 1000).
+template <typename RT>
+__device__ __forceinline__ double centred_value(const double* col, int i) {
+    if constexpr (std::is_same<RT, float>::value) return col[i] - col[0];
+    else return col[i];
+}
+
 // Features / lengthscale of COUNT consecutive individuals from g0 into LDS, by a workgroup of 256 threads: FS >= F rows of
 // COUNT, zeros beyond n and in the rows F .. FS - 1.  (x - x')^2 / ls^2 = (x / ls - x' / ls)^2, and every kernel that
-// evaluates B_ij forms x / ls as x * (1.0 / ls): the same product everywhere, so the same B_ij everywhere.
+// evaluates B_ij forms x / ls as x * (1.0 / ls): the same product everywhere, so the same B_ij everywhere.  RT = float:
+// (x - x_0) * (1.0 / ls), centred_value above.
 template <int COUNT, typename RT>
 __device__ __forceinline__ void stage_scaled_features(const SampleGrid& a, long long s, int F, int FS, int g0, RT* dst) {
     for (int idx = threadIdx.x; idx < FS * COUNT; idx += 256) {
         const int f = idx / COUNT, r = idx % COUNT;
-        dst[idx] = (RT)((f < F && g0 + r < a.n) ? a.column(s, f)[g0 + r] * (1.0 / a.lengthscale(s, f)) : 0.0);
+        dst[idx] = (RT)((f < F && g0 + r < a.n) ? centred_value<RT>(a.column(s, f), g0 + r) * (1.0 / a.lengthscale(s, f)) : 0.0);
     }
 }
 

@@ -42,14 +42,16 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
     const int n = g.n;
     const int gi0 = ti * GP_TS, gj0 = tj * GP_TS;
 
-    // stage features scaled by 1/LS (zeros on the padding): (x - x')^2 / LS^2 = (x/LS - x'/LS)^2
+    // stage features scaled by 1/LS (zeros on the padding): (x - x')^2 / LS^2 = (x/LS - x'/LS)^2; fp32: centred per column first
     if (FT > 0) {
         // exact feature count: ALL loads of the staging (lengthscale, row value, column value per (feature, instance)
         // pair of this thread) are issued before the first is used — branch-free, clamped addresses.  As a loop with
         // guarded loads every iteration waited for its own round trips: in-kernel stamps showed 17.7 k clocks of staging
         // per workgroup, a quarter of its life.
         constexpr int NIT = (FT * GP_TS + 255) / 256;
+        constexpr bool CENTRE = std::is_same<RT, float>::value;    // fp32: centred_value (gpslc_internal.h), one more load per column
         double lv[NIT > 0 ? NIT : 1], av[NIT > 0 ? NIT : 1], cv[NIT > 0 ? NIT : 1];
+        [[maybe_unused]] double x0[CENTRE && NIT > 0 ? NIT : 1];
 #pragma unroll
         for (int k = 0; k < NIT; ++k) {
             const int idx = tid + 256 * k;
@@ -58,6 +60,7 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
             lv[k] = g.lengthscale(s, f);
             av[k] = src[min(gi0 + r, n - 1)];
             cv[k] = src[min(gj0 + r, n - 1)];
+            if constexpr (CENTRE) x0[k] = src[0];
         }
 #pragma unroll
         for (int k = 0; k < NIT; ++k) {
@@ -65,6 +68,7 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
             if (idx < FT * GP_TS) {
                 const int f = idx >> 7, r = idx & 127;
                 const double il = 1.0 / lv[k];
+                if constexpr (CENTRE) { av[k] -= x0[k]; cv[k] -= x0[k]; }
                 fr[f * GP_TS + r] = (RT)((gi0 + r < n) ? av[k] * il : 0.0);
                 fc[f * GP_TS + r] = (RT)((gj0 + r < n) ? cv[k] * il : 0.0);
             }
@@ -74,8 +78,8 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
         stage_scaled_features<GP_TS>(g, s, F, F, gj0, fc);
     }
     if (tid < GP_TS) {
-        tr[tid] = (RT)((gi0 + tid < n) ? g.T[gi0 + tid] : 0.0);
-        tc[tid] = (RT)((gj0 + tid < n) ? g.T[gj0 + tid] : 0.0);
+        tr[tid] = (RT)((gi0 + tid < n) ? centred_value<RT>(g.T, gi0 + tid) : 0.0);     // a binary T stays in {-1, 0, 1}
+        tc[tid] = (RT)((gj0 + tid < n) ? centred_value<RT>(g.T, gj0 + tid) : 0.0);
     }
     gp_exp_tab_stage(etab, tid);
     __syncthreads();

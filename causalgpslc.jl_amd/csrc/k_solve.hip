@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
     for (int q = 0; q < RB; ++q) {
         gi[q] = (ib * RB + q) * GP_TS + r;
 #pragma unroll
-        for (int f = 0; f < FREG; ++f) af[q][f] = (RT)((f < F && gi[q] < n) ? feat_src(f)[gi[q]] * feat_il(f) : 0.0);
+        for (int f = 0; f < FREG; ++f) af[q][f] = (RT)((f < F && gi[q] < n) ? centred_value<RT>(feat_src(f), gi[q]) * feat_il(f) : 0.0);
     }
     const double ys = a.p.yScale[s];
     const double tl = a.p.tyLS[s];
@@ -123,9 +123,10 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
                 const int g = jt * GP_TS + cc;
                 double v = 0.0;
                 if (ll < nl && g < n) {
-                    const RT dt = (RT)a.T[g] - (RT)a.doT[l0 + ll];
+                    // the difference in fp64, then ONE rounding (fp32 mode): its error does not grow with |T|
+                    const RT dt = (RT)(a.T[g] - a.doT[l0 + ll]);
                     if (CON) {
-                        const RT db = (RT)a.T[g] - (RT)a.doT_base[l0 + ll];
+                        const RT db = (RT)(a.T[g] - a.doT_base[l0 + ll]);
                         v = ((double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab) -
                              (double)RbfMath<RT>::exp_neg_t(-((db * db) * wtq), etab)) * alpha[g];
                     } else {
