@@ -258,7 +258,7 @@ void ensure_streams(gpslc_ctx* c) {
 // error in an earlier call) can never make a later one skip work items
 void rearm_queue(StreamSlot& s) { HC(hipMemsetAsync(s.queue, 0, 16 * sizeof(int), s.st)); }
 
-// ---- profiled launch of the accumulate-mode tile kernel ---------------------------------
+// ---- profiled launch of the tile kernels ------------------------------------------------
 // GemmArgs::sym of a symmetric launch of the factorisation of A: with a single short augmented tile row, its off-diagonal tiles
 // ride with the diagonal items (3).  Up to 32 live rows (31 levels): beyond that the diagonal kernel runs out of registers and
 // the augmented tiles carry enough real work to stay ordinary items
@@ -271,7 +271,7 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
     g.diag_skip = 0;
     g.dbg = nullptr;
     g.queue = s.queue;
-    if (g.ntiles <= 0 || g.nbatch <= 0 || (g.k1 <= g.k0 && g.accumulate && !g.fuse)) return;     // fuse with an empty K range: panel product only
+    if (g.ntiles <= 0 || g.nbatch <= 0 || (g.k1 <= g.k0 && !g.fuse)) return;     // fuse with an empty K range: panel product only
 #ifdef GPSLC_DIAG
     // measurement build only: timing-only kernel variants (results are garbage by construction) and in-kernel
     // stamps of one trailing update, written to gpurun_out/gemm_dbg.bin
@@ -283,7 +283,7 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
     size_t dbg_words = 0;
     // GPSLC_GEMM_DBG_FUSEK=<K>: the first FUSED in-panel launch whose K loop is K tiles deep instead
     static const int dbg_fk = diag_env("GPSLC_GEMM_DBG_FUSEK", -1);
-    const bool dbg_fused = dbg_fk >= 0 && g.fuse && g.accumulate && (g.k1 - g.k0) == dbg_fk;
+    const bool dbg_fused = dbg_fk >= 0 && g.fuse && (g.k1 - g.k0) == dbg_fk;
     if (!dbg_done && ((dbg_fk < 0 && dbg_m > 0 && g.shape == 0 && g.mi == dbg_m) || dbg_fused)) {
         dbg_words = (size_t)g.ntiles * g.nbatch * 8;
         dbg_buf.alloc(dbg_words * 8);
@@ -302,7 +302,7 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
             launch_syrk_diag(d, g.sym == 3 && g.short_rows > 0 && g.diag_skip == 0, st);
         }
     };
-    const bool prof = (c->flags & GPSLC_FLAG_PROFILE) && g.accumulate;
+    const bool prof = (c->flags & GPSLC_FLAG_PROFILE) != 0;
     if (prof) {
         // algorithmic flop: full tiles count 2*128^3 per K tile, items in the (single) augmented row only
         // their live right-hand-side rows
@@ -452,7 +452,7 @@ void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv
     PotrfTaskArgs a{};
     a.g.A = M; a.g.B = M; a.g.C = M;
     a.g.F = TRef{inv, inv_bstride, 1, 0, 0, 0};
-    a.g.shape = 1; a.g.k0 = 0; a.g.accumulate = 1; a.g.fuse = 1; a.g.nbatch = nb;
+    a.g.shape = 1; a.g.k0 = 0; a.g.fuse = 1; a.g.nbatch = nb;
     a.g.short_row0 = nt; a.g.short_rows = short_rows; a.g.sym = 3;
     a.g.info = info; a.g.info_base = info_base;
     a.list = tl.dev; a.sync = s.sync; a.timeout = c->task_timeout; a.nt = nt; a.alpha = back_alpha;
@@ -530,7 +530,7 @@ void factor_robust(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int* info
             GemmArgs g{};
             g.A = M; g.B = M; g.C = M;
             g.shape = 1; g.i0 = k; g.j0 = k; g.mi = nt - k; g.mj = 1; g.sym = 2;
-            g.k0 = ka; g.k1 = k; g.accumulate = 1; g.nbatch = nb; g.ntiles = g.mi;
+            g.k0 = ka; g.k1 = k; g.nbatch = nb; g.ntiles = g.mi;
             gemm(c, g, s, prof_base);
         }
         launch_diag_robust(M, k, info, info_base, nb, s.st);
@@ -540,7 +540,7 @@ void factor_robust(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int* info
             g.A = M; g.B = M; g.C = M;
             const int m = nt - kend;
             g.shape = 0; g.i0 = kend; g.j0 = kend; g.mi = m; g.mj = m; g.sym = 2;
-            g.k0 = ka; g.k1 = kend; g.accumulate = 1; g.nbatch = nb; g.ntiles = m * (m + 1) / 2;
+            g.k0 = ka; g.k1 = kend; g.nbatch = nb; g.ntiles = m * (m + 1) / 2;
             g.order = tri_order(c, m);
             gemm(c, g, s, prof_base);
         }
@@ -568,7 +568,7 @@ void factor_panels(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int ntot,
         GemmArgs g{};                        // the column's strip launch: update over the panel columns [ka, k) + panel product
                                              // (F / fk are read by the fused launches only: strip_item's panel product)
         g.A = M; g.B = M; g.C = M; g.F = invref; g.fk = k;
-        g.shape = 1; g.j0 = k; g.mj = 1; g.k1 = k; g.accumulate = 1; g.nbatch = nb;
+        g.shape = 1; g.j0 = k; g.mj = 1; g.k1 = k; g.nbatch = nb;
         g.short_row0 = nt; g.short_rows = short_rows;
         if (k > ka && below > 0) {
             // in-panel update: the diagonal tile first — update, factor and inverse in ONE launch — then ONE pass over the column:
@@ -605,7 +605,7 @@ void factor_panels(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int ntot,
             const int m = ntot - kend;
             t.skip_gdiag = skip_gd ? 1 : 0;
             t.shape = 0; t.i0 = kend; t.j0 = kend; t.mi = m; t.mj = m; t.sym = aug_sym(short_rows);
-            t.k0 = ka; t.k1 = kend; t.accumulate = 1; t.nbatch = nb; t.ntiles = m * (m + 1) / 2;
+            t.k0 = ka; t.k1 = kend; t.nbatch = nb; t.ntiles = m * (m + 1) / 2;
             t.order = tri_order(c, m);
             t.short_row0 = nt; t.short_rows = short_rows;
             gemm(c, t, s, prof_base);
@@ -920,7 +920,7 @@ void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const T
         GemmArgs g{};
         g.A = W; g.B = Ls; g.C = W; g.F = invref; g.fk = k;
         g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1; g.nbatch = ub; g.ntiles = nt;
-        g.k0 = 0; g.k1 = k; g.accumulate = 1; g.fuse = 1;
+        g.k0 = 0; g.k1 = k; g.fuse = 1;
         gemm(c, g, s, 3);
     }
 }
@@ -955,7 +955,7 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
             GemmArgs g{};            // CovITE (+ jitter) = Delta - W W^T, lower tiles
             g.A = W; g.B = W; g.C = Cm;
             g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt; g.sym = 2;
-            g.k0 = 0; g.k1 = nt; g.accumulate = 1; g.nbatch = ub; g.ntiles = (int)sh.nlow;
+            g.k0 = 0; g.k1 = nt; g.nbatch = ub; g.ntiles = (int)sh.nlow;
             g.order = tri_order(c, nt);
             gemm(c, g, *ch.s, 3);
             if (sh.want_cov) {       // ITEDistributions: single level (lc == 1)
@@ -2219,7 +2219,7 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
                 GemmArgs u{};
                 u.A = W; u.B = Ls; u.C = W;
                 u.shape = 1; u.i0 = 0; u.j0 = k + 1; u.mi = naug; u.mj = nt - k - 1;
-                u.k0 = k; u.k1 = k + 1; u.accumulate = 1; u.nbatch = 1; u.ntiles = naug * (nt - k - 1);
+                u.k0 = k; u.k1 = k + 1; u.nbatch = 1; u.ntiles = naug * (nt - k - 1);
                 u.short_row0 = 0; u.short_rows = short_rows;
                 gemm(c, u, slot, 0);
             }
@@ -2324,33 +2324,19 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
         emit(Kst, CovWWs, 0.0);
         emit(Kt, CovWWp, yno);
         if (CovC11 || CovC12 || CovC21 || CovC22) {
-            // W1 = K L^-T, W2 = Ks' L^-T  (copies, then the tile-level left-looking solve)
+            // W1 = K L^-T, W2 = Ks' L^-T  (copies, then unit B's tile-level left-looking solve)
             HC(hipMemcpyAsync(W1.base, Kt.base, (size_t)rs * 8, hipMemcpyDeviceToDevice, st));
             HC(hipMemcpyAsync(W2.base, KsTt.base, (size_t)rs * 8, hipMemcpyDeviceToDevice, st));
             TRef invref = TRef{inv.as<double>(), (long long)nt * GP_TSQ, 1, 0, 0, 0};
-            for (TRef* Wp : {&W1, &W2}) {
-                for (int k = 0; k < nt; ++k) {
-                    if (k > 0) {
-                        GemmArgs g{};
-                        g.A = *Wp; g.B = M; g.C = *Wp;
-                        g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1;
-                        g.k0 = 0; g.k1 = k; g.accumulate = 1; g.nbatch = 1; g.ntiles = nt;
-                        gemm(c, g, slot, 0);
-                    }
-                    GemmArgs g{};
-                    g.A = *Wp; g.B = invref; g.C = *Wp;
-                    g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1;
-                    g.k0 = k; g.k1 = k + 1; g.accumulate = 0; g.nbatch = 1; g.ntiles = nt;
-                    gemm(c, g, slot, 0);
-                }
-            }
+            w_solve(c, slot, W1, M, invref, nt, 1);
+            w_solve(c, slot, W2, M, invref, nt, 1);
             // C11 = K - W1 W1', C12 = Ks - W1 W2', C21 = Ks' - W2 W1', C22 = Kss - W2 W2'   (src/likelihood.jl:46-49)
             auto block = [&](const TRef& Cm, const TRef& Wa, const TRef& Wb, double* host) {
                 if (!host) return;
                 GemmArgs g{};
                 g.A = Wa; g.B = Wb; g.C = Cm;
                 g.shape = 1; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt;
-                g.k0 = 0; g.k1 = nt; g.accumulate = 1; g.nbatch = 1; g.ntiles = nt * nt;
+                g.k0 = 0; g.k1 = nt; g.nbatch = 1; g.ntiles = nt * nt;
                 gemm(c, g, slot, 0);
                 emit(Cm, host, 0.0);
             };

@@ -86,14 +86,14 @@ __host__ __device__ inline double* tref_tile(const TRef& t, long long b, int i, 
     return t.base + b * t.bstride + tref_index(t, i, j) * (long long)GP_TSQ;
 }
 
-// C(i, j) (-)= sum_{kk in [k0, k1)} A(i, kk) * B(j, kk)^T over a set of output tiles.
+// C(i, j) -= sum_{kk in [k0, k1)} A(i, kk) * B(j, kk)^T over a set of output tiles.
 struct GemmArgs {
     TRef A, B, C;
     int shape;        // 0: lower triangle (incl. diagonal) of an mi x mi tile square, 1: mi x mj rectangle
     int i0, j0;       // output tile (i, j) = (i0 + ii, j0 + jj)
     int mi, mj;
     int k0, k1;
-    int accumulate;   // 1: C -= A B^T, 0: C = A B^T
+    int diag_skip;    // DIAGNOSTIC ONLY (GPSLC_GEMM_DIAG): 1 = skip in-loop global loads, 2 = also LDS writes
     int nbatch;
     int ntiles;       // output tiles per batch element
     int short_row0;   // output tile rows >= short_row0 (augmented right-hand-side rows) carry only
@@ -102,7 +102,7 @@ struct GemmArgs {
                       // 2: launch_tile_gemm skips the full-size diagonal tiles, which launch_syrk_diag (36 of 64 sub-tile
                       // products, 9 per wave) or launch_diag_update_potrf computes instead; 3: as 2, and the
                       // augmented-row tiles (short_row0, j) of those columns ride with the diagonal items too
-    int fuse;         // 1 (accumulate launches of one tile column, mj == 1): each item also applies the panel
+    int fuse;         // 1 (launches of one tile column, mj == 1; k1 == k0 allowed): each item also applies the panel
     TRef F;           //    product with tile (0, fk) of F = the inverted diagonal blocks (see k_tilegemm.hip)
     int fk;
     int skip_gdiag;   // the (short) augmented diagonal tile (short_row0, short_row0) is not an item of this launch: nobody
@@ -112,7 +112,6 @@ struct GemmArgs {
     int* queue;       // launch_tile_gemm: 16 zero-initialised ints (per-XCD ticket counters [0..8), exit counters [8..16))
                       // owned by the launching stream; the kernel leaves them zeroed again
     const unsigned short* order;  // optional (ii, jj) pairs: output-tile visiting order (L2-blocked), or null
-    int diag_skip;                // DIAGNOSTIC ONLY (GPSLC_GEMM_DIAG): 1 = skip in-loop global loads, 2 = also LDS writes
     unsigned long long* dbg;      // diagnostic builds only: per-workgroup s_memtime stamps, or null
 };
 

@@ -31,19 +31,6 @@
 
 #include "sm_blocks.h"
 
-// one Gram entry: scale * exp(-sum_f (x_f/l_f - x'_f/l_f)^2) (+ noise on the diagonal); identity on the padding
-__device__ __forceinline__ double sm_gram_entry(const double* fs, int NP, int nF, int n, int i, int j, double scale,
-                                                double noise) {
-    if (i >= n || j >= n) return (i == j) ? 1.0 : 0.0;
-    double lux = 0.0;
-    for (int f = 0; f < nF; ++f) {
-        const double d = fs[f * NP + i] - fs[f * NP + j];
-        lux = fma(d, d, lux);
-    }
-    const double v = scale * gp_exp_neg(-lux);
-    return (i == j) ? v + noise : v;
-}
-
 __global__ __launch_bounds__(SM_THREADS) void small_gp_logpdf_kernel(SmallArgs a) {
     extern __shared__ __attribute__((aligned(16))) double P[];
     const unsigned long long tstart = a.stamps ? __builtin_amdgcn_s_memtime() : 0;

@@ -1,8 +1,16 @@
 // f64-MFMA tile update:  C(i,j) (-)= sum_kk A(i,kk) * B(j,kk)^T   on 128 x 128 fp64 tiles.
 //
-// This one kernel carries every O(N^3) term of the path: the Cholesky panel multiply by the
-// inverted diagonal block, the left-looking column update inside a panel, the trailing SYRK
-// update, the "D L^-T" solve of the ITE covariance and its SYRK.
+// The kernels of this file carry every O(N^3) term of the path:
+//   tile_gemm_nt_kernel       the plain update above: the trailing update of the blocked Cholesky, the SYRK of the ITE
+//                             covariance, the conditional blocks of the likelihood distribution;
+//   tile_fused_strip_kernel   one tile column: the left-looking column update and, in the same work item, the panel product
+//                             with the inverted diagonal block (strip_item) — the panels of the factorisation and the
+//                             "D L^-T" solves (w_solve, api.hip);
+//   tile_syrk_diag_kernel,    the diagonal tiles of a symmetric update (lower triangle only), alone or followed by the
+//   diag_update_potrf_kernel  tile's Cholesky and inverse;
+//   potrf_tasks_kernel        a whole factorisation as tile tasks of one persistent launch (strip_item and the diagonal-tile
+//                             update again).
+// The mapping below is tile_gemm_nt_kernel's; the others say where they differ.
 //
 // CDNA4 mapping
 //   * PERSISTENT workgroups: 2 per CU are launched once and each walks its share of the output
@@ -136,7 +144,7 @@ __device__ __forceinline__ void ticket_loop(const GemmArgs& g, long long W, int 
     }
 }
 
-template <int ACC, int DIAG>
+template <int DIAG>
 __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int tid = threadIdx.x;
@@ -177,20 +185,12 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
             const int mt = (g.short_rows + 15) >> 4;
             mlive = min(4, max(0, mt - 4 * wr));
         }
-        // Panel product (ACC == 0): B = inv(L_kk) is lower triangular, so output column block cb needs only the
-        // slabs s <= cb.  With the quadrant layout the two right-hand waves carry 416 of the 1152 live MFMAs
-        // each (critical path 81 % of a full tile for 56 % of its work); here every wave owns ALL 8 row
-        // blocks of the column blocks pw and 7 - pw instead: 32 x ((pw + 1) + (8 - pw)) = 288 MFMAs per wave.
-        // acc[m >> 1][2 (m & 1) + n]: row block m, column block n ? 7 - pw : pw.
-        const int pw = __builtin_amdgcn_readfirstlane(wave);
-        int prow = 8;                                     // live 16-row blocks of this tile
-        if (!ACC && g.short_rows > 0 && ti >= g.short_row0) prow = min(8, (g.short_rows + 15) >> 4);
         unsigned long long st0 = 0, st1 = 0, st2 = 0;
         if (GP_DBG_ON(g)) st0 = __builtin_amdgcn_s_memtime();
 
         // ---- accumulators: acc[m][n][v] = C[wr*64 + 16m + (lane&15)][wc*64 + 16n + (lane>>4) + 4v]
         d4 acc[4][4];
-        if (ACC) {
+        {
             const double* __restrict__ Cl = Ct + (ccol * GP_TS + crow);
 #pragma unroll
             for (int n = 0; n < 4; ++n)
@@ -199,11 +199,6 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
                         acc[m][n][v] = Cl[(16 * n + 4 * v) * GP_TS + 16 * m];
-        } else {
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = (d4){0.0, 0.0, 0.0, 0.0};
         }
 
         if (nslab > 0) {
@@ -215,9 +210,7 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
                 const int so = (s & 7) * (KS * GP_TS);
                 const double* pa = tref_tile(g.A, b, ti, kk) + so;
                 const double* pb = tref_tile(g.B, b, tj, kk) + so;
-                // panel product of a short (augmented-row) tile: the chunks of A below its live rows are never
-                // used — point them at chunk 0 of their k-column's line instead of streaming zeros
-                const int ao = (!ACC && ((tid & 63) * 2) >= 16 * prow) ? (tid & ~63) * 2 : tid * 2;
+                const int ao = tid * 2;      // (pa + ao + 512 u, not (tid + 256 u) * 2 as for B: the compiler schedules that form differently)
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     xa[u] = *reinterpret_cast<const d2*>(pa + ao + 512 * u);
@@ -231,16 +224,12 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
                     *reinterpret_cast<d2*>(lB + buf * OPER_LDS + loff[u]) = xb[u];
                 }
             };
-            auto compute = [&](int buf, int s) {
+            auto compute = [&](int buf) {
                 const double* pa = lA + buf * OPER_LDS + frow_a;
                 const double* pb = lB + buf * OPER_LDS + frow_b;
-                // Panel product (ACC == 0): B is the lower-triangular inverse inv(L_kk)[c][c'], zero for
-                // c' > c.  Slab s carries c' in [16 (s&7), 16 (s&7) + 16), so only the output column
-                // sub-tiles n with 64 wc + 16 n + 15 >= 16 (s&7) contribute: 44 % fewer MFMAs.
-                const int nlo = ACC ? 0 : min(4, max(0, (s & 7) - 4 * wc));
                 // trailing updates (no second phase, registers to spare): the fragments of k-step ks + 1 are read from LDS
                 // before the 16 MFMAs of k-step ks are issued, so that a wave never starts a k-step with an LDS round trip
-                constexpr bool PIPE = ACC && DIAG == 0;
+                constexpr bool PIPE = DIAG == 0;
                 double afn[4], bfn[4];
                 if (PIPE) {
 #pragma unroll
@@ -266,43 +255,20 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
 #pragma unroll
                         for (int n = 0; n < 4; ++n) bf[n] = pb[ks * 4 * LROW + 16 * n];
                     }
-                    if (mlive == 4 && nlo == 0) {
+                    if (mlive == 4) {
 #pragma unroll
                         for (int m = 0; m < 4; ++m)
 #pragma unroll
                             for (int n = 0; n < 4; ++n)
-                                acc[m][n] = mfma_step<ACC>(bf[n], af[m], acc[m][n]);
+                                acc[m][n] = mfma_step<1>(bf[n], af[m], acc[m][n]);
                     } else {
 #pragma unroll
                         for (int m = 0; m < 4; ++m)
                             if (m < mlive) {
 #pragma unroll
-                                for (int n = 0; n < 4; ++n)
-                                    if (n >= nlo) acc[m][n] = mfma_step<ACC>(bf[n], af[m], acc[m][n]);
+                                for (int n = 0; n < 4; ++n) acc[m][n] = mfma_step<1>(bf[n], af[m], acc[m][n]);
                             }
                     }
-                }
-            };
-
-            auto compute_p = [&](int buf, int s) {
-                const int sl = s & 7;
-                if (sl > 7 - pw) return;                   // neither column block needs this slab
-                const bool use0 = sl <= pw;
-                const double* pa = lA + buf * OPER_LDS + (lane >> 4) * LROW + (lane & 15);
-                const double* pb = lB + buf * OPER_LDS + (lane >> 4) * LROW + (lane & 15);
-#pragma unroll
-                for (int ks = 0; ks < KS / 4; ++ks) {
-                    const double b0 = pb[ks * 4 * LROW + 16 * pw];
-                    const double b1 = pb[ks * 4 * LROW + 16 * (7 - pw)];
-                    double af[8];
-#pragma unroll
-                    for (int m = 0; m < 8; ++m) af[m] = pa[ks * 4 * LROW + 16 * m];
-#pragma unroll
-                    for (int m = 0; m < 8; ++m)
-                        if (m < prow) {
-                            if (use0) acc[m >> 1][2 * (m & 1)] = mfma_step<0>(b0, af[m], acc[m >> 1][2 * (m & 1)]);
-                            acc[m >> 1][2 * (m & 1) + 1] = mfma_step<0>(b1, af[m], acc[m >> 1][2 * (m & 1) + 1]);
-                        }
                 }
             };
 
@@ -318,23 +284,23 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
                 for (int s = 0; s < nslab; s += 2) {
                     if (s + 2 < nslab) gload(s + 2, ra2, rb2);
                     MFMA_PRIO_UP;
-                    if (ACC) compute(0, s); else compute_p(0, s);
+                    compute(0);
                     MFMA_PRIO_DOWN;
                     lstore(1, ra, rb);
                     KLOOP_BARRIER;
                     if (s + 3 < nslab) gload(s + 3, ra, rb);
                     MFMA_PRIO_UP;
-                    if (ACC) compute(1, s + 1); else compute_p(1, s + 1);
+                    compute(1);
                     MFMA_PRIO_DOWN;
                     if (s + 2 < nslab) lstore(0, ra2, rb2);
                     KLOOP_BARRIER;
                 }
             } else {   // timing-only diagnostic: same MFMA / ds_read stream, operand traffic removed
                 for (int s = 0; s < nslab; s += 2) {
-                    compute(0, s);
+                    compute(0);
                     if (DIAG == 1) lstore(1, ra, rb);
                     __syncthreads();
-                    compute(1, s + 1);
+                    compute(1);
                     if (DIAG == 1) lstore(0, ra, rb);
                     __syncthreads();
                 }
@@ -343,22 +309,8 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
         if (GP_DBG_ON(g)) st2 = __builtin_amdgcn_s_memtime();
 
         {
-        // recompute the store addresses from one opaque offset instead of keeping the 64 preload
-        // addresses alive (and spilled) across the K loop
-        if (!ACC) {
-            // panel layout: row block m, column blocks pw (n = 0) and 7 - pw (n = 1); dead rows of a short tile
-            // hold zeros (never accumulated, never written)
-            double* __restrict__ Cp = Ct + ((lane >> 4) * GP_TS + (lane & 15));
-#pragma unroll
-            for (int m = 0; m < 8; ++m)
-                if (m < prow) {     // the dead row blocks of a short tile keep their zeros
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        Cp[(16 * pw + 4 * v) * GP_TS + 16 * m] = acc[m >> 1][2 * (m & 1)][v];
-                        Cp[(16 * (7 - pw) + 4 * v) * GP_TS + 16 * m] = acc[m >> 1][2 * (m & 1) + 1][v];
-                    }
-                }
-        } else {
+            // recompute the store addresses from one opaque offset instead of keeping the 64 preload
+            // addresses alive (and spilled) across the K loop
             int soff = ccol * GP_TS + crow;
             asm volatile("" : "+v"(soff));
             double* __restrict__ Cs = Ct + soff;
@@ -369,7 +321,6 @@ __global__ __launch_bounds__(256, 2) void tile_gemm_nt_kernel(GemmArgs g) {
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
                         Cs[(16 * n + 4 * v) * GP_TS + 16 * m] = acc[m][n][v];
-        }
         }
         if (GP_DBG_ON(g)) {   // diagnostic stamps: go to a buffer nothing else reads
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1182,31 +1133,26 @@ void launch_syrk_diag(const GemmArgs& g, int carry_aug, hipStream_t st) {
                 [&](auto mt) { launch_syrk_diag_t<decltype(mt)::value>(g, grid, st); });
 }
 
-template <int ACC, int DIAG>
+template <int DIAG>
 static void launch_one(const GemmArgs& g, unsigned grid, hipStream_t st) {
     static DeviceOnce once;
-    lds_opt_in(once, (const void*)tile_gemm_nt_kernel<ACC, DIAG>, GEMM_LDS_BYTES);
-    hipLaunchKernelGGL((tile_gemm_nt_kernel<ACC, DIAG>), dim3(grid), dim3(256), GEMM_LDS_BYTES, st, g);
+    lds_opt_in(once, (const void*)tile_gemm_nt_kernel<DIAG>, GEMM_LDS_BYTES);
+    hipLaunchKernelGGL((tile_gemm_nt_kernel<DIAG>), dim3(grid), dim3(256), GEMM_LDS_BYTES, st, g);
 }
 
 void launch_tile_gemm(const GemmArgs& g, hipStream_t st) {
     if (g.ntiles <= 0 || g.nbatch <= 0) return;
     const unsigned grid = persistent_grid((long long)g.ntiles * g.nbatch);
 #ifdef GPSLC_DIAG
-    if (g.diag_skip == 1) {        // timing-only diagnostics (GPSLC_GEMM_DIAG), separate instantiations
-        if (g.accumulate) launch_one<1, 1>(g, grid, st); else launch_one<0, 1>(g, grid, st);
-        return;
-    }
-    if (g.diag_skip == 2) {
-        if (g.accumulate) launch_one<1, 2>(g, grid, st); else launch_one<0, 2>(g, grid, st);
-        return;
-    }
+    // timing-only diagnostics (GPSLC_GEMM_DIAG), separate instantiations
+    if (g.diag_skip == 1) { launch_one<1>(g, grid, st); return; }
+    if (g.diag_skip == 2) { launch_one<2>(g, grid, st); return; }
 #endif
-    if (g.fuse && g.accumulate) {
+    if (g.fuse) {
         static DeviceOnce once;
         lds_opt_in(once, (const void*)tile_fused_strip_kernel<FUSE_WD>, STRIP_LDS_BYTES);
         hipLaunchKernelGGL((tile_fused_strip_kernel<FUSE_WD>), dim3(grid), dim3(256), STRIP_LDS_BYTES, st, g);
     } else {
-        if (g.accumulate) launch_one<1, 0>(g, grid, st); else launch_one<0, 0>(g, grid, st);
+        launch_one<0>(g, grid, st);
     }
 }

@@ -451,7 +451,7 @@ int gpslc_pack_load(const char* path, int64_t s0, int64_t s1, double* X, double*
 
 /* Accumulated HIP-event statistics since the last reset, recorded (on the launching stream) when the ctx was
  * created with GPSLC_FLAG_PROFILE: launches, total device milliseconds, total algorithmic work.  Kernel classes:
- *   0  tile_gemm_nt_kernel<1, 0> in the factorisation of A (trailing updates: the dominant kernel)   work = flop
+ *   0  tile_gemm_nt_kernel<0> in the factorisation of A (trailing updates: the dominant kernel)   work = flop
  *   1  tile_fused_strip_kernel in the factorisation of A (in-panel column update + panel solve)        work = flop
  *   2  the predictive-draw kernels of a launch_draws call (normal generation + triangular product)      work = draws
  *   3  every f64-MFMA tile-update launch of the full-ITE-covariance path (W solve, SYRK, factor)        work = flop
