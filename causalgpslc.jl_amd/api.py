@@ -68,6 +68,18 @@ def _baseline(baseline, L):
     raise ValueError(f"baseline must be a scalar or one value per level (L = {L}), got an array of shape {b.shape}")
 
 
+def _slope_refusals(slope, baseline, vec, devices):
+    """What ``slope=True`` (gpslc_predict_slope) cannot be combined with, refused before any device work."""
+    if not slope:
+        return
+    if baseline is not None:
+        raise ValueError("slope=True cannot be combined with baseline=: the slope is a derivative at one level, not a contrast")
+    if vec:
+        raise ValueError("slope=True needs scalar levels: slopes at per-individual intervention vectors are not supported")
+    if devices is not None:
+        raise ValueError("slope=True is not sharded over devices: call without devices=")
+
+
 def _weight_row(w, n):
     """One weight vector for n individuals -> (n,) float64.  Float (or integer) values are used as given; a Bool vector is a
     group mask and becomes that group's average, ``mask / mask.sum()`` (an empty mask raises ValueError)."""
@@ -420,9 +432,10 @@ def conditionalITE(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT):
     return M[0], Cv[0]
 
 
-def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=None):
+def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=None, slope=False):
     n, S = g.getN(), g.getNumPosteriorSamples()
     x, d = _intervention(doT, n)
+    _slope_refusals(slope, baseline, d is not None, None)
     if baseline is not None:
         if d is not None:
             raise ValueError("baseline= needs a scalar doT: contrasts of per-individual intervention vectors are not supported")
@@ -430,7 +443,9 @@ def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=
     ctx = g.ctx()
     M = np.empty((S, n), order="F")
     Cv = np.empty((S, n, n), order="F") if want_cov else None
-    if baseline is not None:
+    if slope:
+        st = ctx.lib.gpslc_ite_distributions_slope(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
+    elif baseline is not None:
         st = ctx.lib.gpslc_ite_distributions_contrast(ctx.h, S, *g._params(), x, base, float(pred_noise), _p(M), _p(Cv))
     elif d is None:
         st = ctx.lib.gpslc_ite_distributions(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
@@ -440,10 +455,11 @@ def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=
     return M, Cv
 
 
-def ITEDistributions(g: GPSLCObject, doT, baseline=None):
+def ITEDistributions(g: GPSLCObject, doT, baseline=None, slope=False):
     """MeanITEs (S, n), CovITEs (S, n, n) incl. + I*predictionCovarianceNoise (src/estimation.jl:66-86).  ``baseline`` = a
-    scalar b: the contrast f(doT) - f(b) of two scalar levels instead of f(doT) - f(T) (gpslc_ite_distributions_contrast)."""
-    return _ite_distributions(g, doT, g.hyperparams.predictionCovarianceNoise, baseline=baseline)
+    scalar b: the contrast f(doT) - f(b) of two scalar levels instead of f(doT) - f(T) (gpslc_ite_distributions_contrast).
+    ``slope=True``: the marginal effect d f_i(t) / dt at the scalar t = doT (gpslc_ite_distributions_slope; see predict)."""
+    return _ite_distributions(g, doT, g.hyperparams.predictionCovarianceNoise, baseline=baseline, slope=slope)
 
 
 def conditionalSATE(MeanITE, CovITE):
@@ -452,12 +468,12 @@ def conditionalSATE(MeanITE, CovITE):
     return float(np.sum(MeanITE) / n), float(np.sum(CovITE) / n ** 2)
 
 
-def SATEDistributions(g: GPSLCObject, doT, baseline=None, weights=None):
+def SATEDistributions(g: GPSLCObject, doT, baseline=None, weights=None, slope=False):
     """MeanSATEs (S,), VarSATEs (S,) (src/estimation.jl:127-140) — O(N^2) per sample on the GPU,
     without materialising CovITE.  ``baseline`` = a scalar b: the contrast doT against b (see predict).  ``weights`` = a
     length-n vector: the weighted effect w' ITE instead of the average over everybody, same shapes; a (G, n) array: (S, G)
-    each (see predict)."""
-    m, v, _ = predict(g, _levels(g, doT), baseline=baseline, weights=weights)
+    each (see predict).  ``slope=True``: the average marginal effect at the scalar doT (see predict)."""
+    m, v, _ = predict(g, _levels(g, doT), baseline=baseline, weights=weights, slope=slope)
     return m[:, 0].copy(), v[:, 0].copy()
 
 
@@ -482,7 +498,7 @@ def _levels(g: GPSLCObject, doT):
 
 
 def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
-            want_draws=False, devices: Optional[Sequence[int]] = None, baseline=None, weights=None):
+            want_draws=False, devices: Optional[Sequence[int]] = None, baseline=None, weights=None, slope=False):
     """The ensemble entry point (gpslc_predict): returns MeanSATE (S, L), VarSATE (S, L) and, when
     asked, MeanITE (n, S, L) / draws (L, n, S*spp).  ``doTs``: L scalar levels (1-D), or an (L, n) array of L per-individual
     intervention vectors (gpslc_predict_vec).  ``devices`` = a list of GPU indices shards the posterior samples
@@ -496,10 +512,15 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
     (1/n everywhere is the SATE, a difference of two group averages the difference of two groups with its correct variance);
     a Bool row is a group mask and means that group's average (``groupWeights`` builds them from labels).  With ``baseline``
     the weighted contrast: a binary treatment, ``predict(g, [1.0], baseline=0.0, weights=(T == 1))`` is the ATT.  MeanITE and
-    the draws are unchanged.  Scalar levels and one GPU only."""
+    the draws are unchanged.  Scalar levels and one GPU only.
+    ``slope=True``: level l becomes the marginal effect d f_i(t) / dt at t = doTs[l], everybody set to that dose
+    (gpslc_predict_slope) — MeanSATE / VarSATE its average over the population, the slope of the dose-response curve, MeanITE and
+    the draws the per-individual slope; exact (the derivative of the Gaussian process, nothing is differenced).  Combines with
+    ``weights``; ``baseline``, vector levels and ``devices`` raise ValueError."""
     n, S = g.getN(), g.getNumPosteriorSamples()
     doTs = np.asarray(doTs, dtype=np.float64)
     vec = doTs.ndim == 2
+    _slope_refusals(slope, baseline, vec, devices)
     if doTs.ndim > 2 or (vec and doTs.shape[1] != n):
         raise ValueError(f"doTs must be L scalar levels or an (L, n) array of intervention vectors with n = {n}, "
                          f"got an array of shape {doTs.shape}")
@@ -530,7 +551,17 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
         zz = _f(z)
         if zz.shape != (n, spp, S, L):
             raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
-    if Wm is not None:
+    if slope:
+        G = 0 if Wm is None else Wm.shape[0]
+        if Wm is not None:
+            ms = np.empty((S, L, G), order="F")
+            vs = np.empty((S, L, G), order="F")
+        st = ctx.lib.gpslc_predict_slope(ctx.h, S, *g._params(), L, _p(doTs), G, _p(Wm),
+                                         float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
+                                         _p(ms), _p(vs), None, _p(mi), _p(dr))
+        if wvec:
+            ms, vs = ms[:, :, 0], vs[:, :, 0]
+    elif Wm is not None:
         G = Wm.shape[0]
         ms = np.empty((S, L, G), order="F")
         vs = np.empty((S, L, G), order="F")
@@ -560,11 +591,13 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
 
 
 def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_ite=False, spp=0, z=None, seed=0,
-                   want_draws=False, want_cov=True, devices=None):
+                   want_draws=False, want_cov=True, devices=None, slope=False):
     """gpslc_predict_curve: (meanW (S, L, G), varW (S, L, G), covW (S, L, L, G) or None, MeanITE or None, draws or None) and
-    whether ``weights`` was a single vector.  ``weights=None`` is 1/n for everybody."""
+    whether ``weights`` was a single vector.  ``weights=None`` is 1/n for everybody.  ``slope=True``: gpslc_predict_slope's
+    weighted form."""
     n, S = g.getN(), g.getNumPosteriorSamples()
     doTs = np.asarray(doTs, dtype=np.float64)
+    _slope_refusals(slope, baseline, doTs.ndim > 1, devices)
     if doTs.ndim > 1:
         raise ValueError("an effect curve needs scalar levels: per-individual intervention vectors are not supported")
     if devices is not None:
@@ -584,21 +617,27 @@ def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_
         zz = _f(z)
         if zz.shape != (n, spp, S, L):
             raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
-    st = ctx.lib.gpslc_predict_curve(ctx.h, S, *g._params(), L, _p(doTs), _p(base), G, _p(Wm),
-                                     float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
-                                     _p(mw), _p(vw), _p(cw), _p(mi), _p(dr))
+    if slope:
+        st = ctx.lib.gpslc_predict_slope(ctx.h, S, *g._params(), L, _p(doTs), G, _p(Wm),
+                                         float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
+                                         _p(mw), _p(vw), _p(cw), _p(mi), _p(dr))
+    else:
+        st = ctx.lib.gpslc_predict_curve(ctx.h, S, *g._params(), L, _p(doTs), _p(base), G, _p(Wm),
+                                         float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
+                                         _p(mw), _p(vw), _p(cw), _p(mi), _p(dr))
     ctx.check(st)
     return (mw, vw, cw, mi, dr), wvec
 
 
-def effectCurve(g: GPSLCObject, doTs, baseline=None, weights=None, devices=None):
+def effectCurve(g: GPSLCObject, doTs, baseline=None, weights=None, devices=None, slope=False):
     """The weighted effect over a sweep of L scalar levels as ONE Gaussian: mean (S, L[, G]) and the joint covariance
     cov (S, L, L[, G]) of tau_l = w' ITE_l across the levels, per posterior sample (gpslc_predict_curve).  The diagonal of
     ``cov`` is the ``var`` of ``predict`` to the bits; the off-diagonal blocks are what simultaneous bands, comparisons of
     two levels and functionals of the curve (slope, maximum, area) need.  ``weights=None`` means 1/n, the SATE curve; a
     length-n vector or a (G, n) array as in ``predict`` (a (G, n) array adds the trailing group axis); ``baseline`` as in
-    ``predict``.  Scalar levels and one GPU only."""
-    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices)
+    ``predict``.  ``slope=True``: the curve of average marginal effects, tau_l = w' (d f / dt at doTs[l]) — the derivative of the
+    dose-response curve with its joint covariance (``weights=None`` is 1/n here too).  Scalar levels and one GPU only."""
+    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices, slope=slope)
     if wvec:
         return mw[:, :, 0], cw[:, :, :, 0]
     return mw, cw
@@ -626,11 +665,13 @@ def curveSamples(mean, cov, samplesPerPosterior, z=None, seed=0):
     return out
 
 
-def sampleEffectCurve(g: GPSLCObject, doTs, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None, devices=None):
+def sampleEffectCurve(g: GPSLCObject, doTs, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None, devices=None,
+                      slope=False):
     """Joint draws of the effect curve over the L levels: (L, S*spp), column order sample-outer / draw-inner as sampleSATE, or
     (G, L, S*spp) for a (G, n) weight array.  Unlike sampleSATE per level, the L values of a column are ONE draw of the curve
-    (they share the Gaussian process).  ``z``: (L, spp, S[, G]) standard normals, else the Philox stream ``seed``."""
-    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices)
+    (they share the Gaussian process).  ``z``: (L, spp, S[, G]) standard normals, else the Philox stream ``seed``.
+    ``slope=True``: draws of the curve of average marginal effects (see effectCurve)."""
+    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices, slope=slope)
     S, L, G = mw.shape
     spp = int(samplesPerPosterior)
     if z is not None:
@@ -642,17 +683,19 @@ def sampleEffectCurve(g: GPSLCObject, doTs, samplesPerPosterior=10, z=None, seed
     return np.ascontiguousarray(out[0]) if wvec else np.ascontiguousarray(out)
 
 
-def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, baseline=None):
+def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, baseline=None, slope=False):
     """ITEsamples: n x (S*spp) draws, column order sample-outer / draw-inner (src/estimation.jl:95-109).
     Called as ITEsamples(g, doT, spp): the factor of CovITE + jitter is computed once per sample on the GPU.
-    ``baseline`` = a scalar b: draws of the contrast doT against b (see predict)."""
+    ``baseline`` = a scalar b: draws of the contrast doT against b (see predict).  ``slope=True``: draws of the per-individual
+    marginal effect at the scalar doT (see predict)."""
     g, doT = g_or_means, doT_or_covs
     zz = None
     if z is not None:   # z given in the reference's (n, S*spp) column order
         n, S = g.getN(), g.getNumPosteriorSamples()
         # column j*spp + d  ->  [i, d, j] under a column-major reshape
         zz = np.asarray(z, dtype=np.float64).reshape(n, nSamplesPerMixture, S, order="F")[:, :, :, None]
-    _, _, _, dr = predict(g, _levels(g, doT), spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True, baseline=baseline)
+    _, _, _, dr = predict(g, _levels(g, doT), spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True, baseline=baseline,
+                          slope=slope)
     return np.asfortranarray(dr[0])
 
 
@@ -660,18 +703,18 @@ def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, base
 # src/driver.jl, src/prediction.jl
 # ------------------------------------------------------------------------------------------
 
-def sampleITE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None):
+def sampleITE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None, slope=False):
     """sampleITE(g, doT; samplesPerPosterior=10) -> n x (S*spp) (src/driver.jl:86-89); ``baseline``: the contrast doT
-    against that scalar level."""
-    return ITEsamples(g, doT, samplesPerPosterior, z=z, seed=seed, baseline=baseline)
+    against that scalar level; ``slope=True``: the marginal effect at the scalar doT."""
+    return ITEsamples(g, doT, samplesPerPosterior, z=z, seed=seed, baseline=baseline, slope=slope)
 
 
-def sampleSATE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None):
+def sampleSATE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None, slope=False):
     """sampleSATE(g, doT; samplesPerPosterior=10) -> (S*spp,) (src/driver.jl:108-111); ``baseline``: the contrast doT
     against that scalar level.  ``weights`` = a length-n vector: samples of the weighted effect, (S*spp,); a (G, n) array:
     (G, S*spp), row g from SATEsamples of group g's means and variances with ``z[g]`` (``z``: (G, S*spp), or (S*spp,) shared
-    by every group) or the Philox seed ``seed + g``."""
-    m, v = SATEDistributions(g, doT, baseline=baseline, weights=weights)
+    by every group) or the Philox seed ``seed + g``.  ``slope=True``: samples of the average marginal effect at the scalar doT."""
+    m, v = SATEDistributions(g, doT, baseline=baseline, weights=weights, slope=slope)
     if m.ndim == 1:
         return SATEsamples(m, v, samplesPerPosterior, z=z, seed=seed)
     zz = None if z is None else np.broadcast_to(np.asarray(z, dtype=np.float64), (m.shape[1], m.shape[0] * samplesPerPosterior))

@@ -624,6 +624,10 @@ struct Levels {
     const double* doT = nullptr;
     bool vec = false;                // vector levels: doT is n x L (level l at doT + n*l), not L scalars
     const double* base = nullptr;    // contrasts (L): level l is doT[l] against base[l] (scalar levels only)
+    bool slope = false;              // marginal effects: level l is d f_i(t) / dt at t = doT[l] (scalar levels only)
+    // the level form the kernels take (FORM_*): what multiplies B_ij outside the pair loops
+    int form() const { return slope ? FORM_SLOPE : base ? FORM_CONTRAST : FORM_ORDINARY; }
+    bool needs_kw() const { return form() == FORM_ORDINARY; }     // contrasts and slopes have no K W term
     // weighted effects: G weight columns — the caller's W[i + n*g] on the host, column fastest (W[g + G*j]) on the
     // device; meanSATE / varSATE are then S x L x G — element (s, l, g) at s + S*(l + L*g) — of tau_w = w_g' ITE_l, the weights
     // used as given (scalar levels only)
@@ -741,9 +745,9 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     if (sh.with_sums && !io.lv.W) b.part = take(2 * nt * sh.Np);
     b.bsum = take(sh.Np); b.ksum = take(sh.Np);
     b.sumdelta = take(std::max(sh.R, 1));
-    if (io.lv.W) {      // the contrast form needs no K W
+    if (io.lv.W) {      // the contrast and slope forms need no K W
         b.bw = take((size_t)io.lv.G * sh.Np);
-        b.kw = io.lv.base ? b.bw : take((size_t)io.lv.G * sh.Np);
+        b.kw = io.lv.needs_kw() ? take((size_t)io.lv.G * sh.Np) : b.bw;
         b.wnorm2 = take(io.lv.G);
         if (io.out.covW) b.cprior = take((size_t)io.lv.G * (L + 2));
     }
@@ -818,7 +822,7 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     if (io.lv.W) {      // weighted effects: B W and K W, one pass over the pairs for all columns and levels (independent of the tiles)
         WsumArgs wa{ch.grid};
         wa.G = io.lv.G; wa.W = io.lv.W;
-        wa.bw = ch.bw; wa.kw = ch.kw; wa.with_k = io.lv.base ? 0 : 1; wa.binary_t = ga.binary_t;
+        wa.bw = ch.bw; wa.kw = ch.kw; wa.with_k = io.lv.needs_kw() ? 1 : 0; wa.binary_t = ga.binary_t;
         launch_wsum(wa, nb, st);
     }
     launch_gram(ga, nb, st);
@@ -839,7 +843,7 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     // fills both below
     ra.n = n; ra.nt = nt; ra.naug = sh.naug; ra.L = (sh.with_sums && !io.lv.vec) ? sh.L : 0; ra.with_sums = sh.with_sums ? 1 : 0;
     ra.part = ch.part; ra.bsum = ch.bsum; ra.ksum = ch.ksum; ra.sumdelta = ch.sumdelta; ra.M = ch.M;
-    ra.doT_base = io.lv.base;
+    ra.doT_base = io.lv.base; ra.form = io.lv.form();
     const bool epi_rows = (sh.naug == 1);                    // single augmented tile row: the epilogue sums from the rows of R
     const int live = (sh.with_sums ? sh.R : 0) + 1;          // right-hand sides: Y and one c_l per level (and weight column)
     ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
@@ -871,7 +875,7 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     if (io.out.covW) {      // the levels' joint covariance per weight column: Gram matrix of the rows the factorisation carried
         CurveArgs ca{};
         ca.M = ch.M; ca.n = n; ca.nt = nt; ca.L = sh.L; ca.G = io.lv.G; ca.s0 = s0; ca.S = io.post.S;
-        ca.T = c->dT; ca.tyLS = io.post.p.tyLS; ca.doT = io.lv.doT; ca.doT_base = io.lv.base;
+        ca.T = c->dT; ca.tyLS = io.post.p.tyLS; ca.doT = io.lv.doT; ca.doT_base = io.lv.base; ca.form = io.lv.form();
         ca.W = io.lv.W; ca.bw = ch.bw; ca.kw = ch.kw; ca.prior = ch.cprior;
         ca.varW = io.out.varSATE; ca.covW = io.out.covW;
         launch_curve(ca, nb, st);
@@ -907,7 +911,7 @@ void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
     ia.S = S; ia.L = sh.L; ia.doT = io.lv.doT; ia.alpha = alpha;
     ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.post.p.yNoise;
     ia.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
-    ia.doT_base = io.lv.base;
+    ia.doT_base = io.lv.base; ia.form = io.lv.form();
     for (const auto& o : outs)
         if (o.out) { ia.meanITE = o.out; ia.si = o.si; ia.ss = o.ss; ia.sl = o.sl; launch_ite_mean(ia, nb, st); }
 }
@@ -946,7 +950,7 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
             da.s0 = s0 + g0;
             da.doT = io.lv.doT; da.l0 = l0; da.lc = lc;
             da.vec = io.lv.vec ? 1 : 0;
-            da.doT_base = io.lv.base;
+            da.doT_base = io.lv.base; da.form = io.lv.form();
             da.pred_noise = io.out.pred_noise; da.W = W; da.Cm = Cm;
             launch_dt_build(da, ub, st);
             TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
@@ -998,6 +1002,9 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     PredictIO io = io_in;
     if (io.lv.base && io.lv.vec) throw std::runtime_error("a contrast baseline cannot be combined with vector levels");
     if (io.lv.base && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("contrasts need an fp64 context");
+    if (io.lv.slope && io.lv.vec) throw std::runtime_error("slopes cannot be combined with vector levels");
+    if (io.lv.slope && io.lv.base) throw std::runtime_error("slopes cannot be combined with a contrast baseline");
+    if (io.lv.slope && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("slopes need an fp64 context");
     if (io.lv.W && io.lv.vec) throw std::runtime_error("weights cannot be combined with vector levels");
     if (io.lv.W && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("weighted effects need an fp64 context");
     if (io.lv.W && io.lv.G < 1) throw std::runtime_error("weights without a weight column");
@@ -1552,13 +1559,15 @@ static PredictRequest make_request(int64_t S, const SampleParams& samples, int32
 // The position of each checked argument in one entry point's signature (0: it has no such argument): the k of the status -k
 // and of the message's "argument #k".  fp64_only: the entry point refuses a GPSLC_FLAG_FP32_KERNEL context (the fp32 kernel
 // mode covers scalar levels without baseline or weights only).
-struct ArgPos { int S, U, xyLS, tyLS, L, doT, base, G, W, spp; bool fp64_only; };
+// covW: the joint covariance where the weights are optional (it needs them).
+struct ArgPos { int S, U, xyLS, tyLS, L, doT, base, G, W, spp; bool fp64_only; int covW = 0; };
 static const ArgPos kPredictArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, false}, kPredictVecArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, true},
     kPredictContrastArgs{2, 3, 5, 6, 9, 10, 11, 0, 0, 13, true}, kPredictWeightedArgs{2, 3, 5, 6, 9, 10, 11, 12, 13, 15, true},
     kPredictMultiArgs{3, 4, 6, 7, 10, 11, 0, 0, 0, 13, false},      // two more leading arguments: nctx, ctxs
     kSamplesArgs{2, 3, 5, 6, 0, 0, 0, 0, 0, 0, false},      // gpslc_ite_distributions, gpslc_y_logpdf, gpslc_likelihood_distribution
     kIteVecArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true}, kIteContrastArgs{2, 3, 5, 6, 0, 9, 10, 0, 0, 0, true},
-    kLikelihoodVecArgs{2, 3, 5, 6, 0, 8, 0, 0, 0, 0, false};
+    kLikelihoodVecArgs{2, 3, 5, 6, 0, 8, 0, 0, 0, 0, false},
+    kPredictSlopeArgs{2, 3, 5, 6, 9, 10, 0, 11, 12, 14, true, 19}, kIteSlopeArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true};
 
 // `count` host values: all there and all finite
 static int finite_check(gpslc_ctx* c, const double* v, int64_t count, int argk, const char* name) {
@@ -1570,7 +1579,8 @@ static int finite_check(gpslc_ctx* c, const double* v, int64_t count, int argk, 
 }
 
 // The argument checks of every prediction and ITE-distribution entry point, in the order of the arguments.  Levels given as
-// host values beyond the plain L scalars (vector levels: n x L; pairs with a baseline; weight columns: n x G) must be finite.
+// host values beyond the plain L scalars (vector levels: n x L; pairs with a baseline; slopes; weight columns: n x G) must be
+// finite.  The slope entry takes its weights or none (G == 0 and NULL: the plain 1/n average).
 static int validate(gpslc_ctx* c, const PredictRequest& rq, const ArgPos& k) {
     const Posterior& po = rq.post;
     const Levels& lv = rq.lv;
@@ -1585,24 +1595,29 @@ static int validate(gpslc_ctx* c, const PredictRequest& rq, const ArgPos& k) {
     if (k.L) {
         if (lv.L < 1) return bad_arg(c, k.L, "L < 1");
         if (!lv.doT) return bad_arg(c, k.doT, "doT is NULL");
-        if (no_spp && !k.base) return bad_arg(c, k.spp, "spp < 1 with ite_draws requested");      // spp follows doT
+        if (no_spp && !k.base && !k.W) return bad_arg(c, k.spp, "spp < 1 with ite_draws requested");      // spp follows doT
         // a placement left over from an earlier, smaller call would make the stream ids (off + s) + S_total * l of this call's
         // last samples collide with the next level's streams: refuse instead of drawing correlated normals
         if (c->ens_S > 0 && c->ens_off + po.S > c->ens_S)
             return bad_arg(c, k.S, "S exceeds the room gpslc_set_ensemble left: sample_offset + S > S_total");
     }
-    if (lv.vec || k.base) {
+    if (lv.vec || k.base || lv.slope) {
         if ((rc = finite_check(c, lv.doT, lv.vec ? c->n * (int64_t)lv.L : lv.L, k.doT, "doT"))) return rc;
         // the baselines are optional beside weights
         if (k.base && (lv.base || !k.W) && (rc = finite_check(c, lv.base, lv.L, k.base, "doT_base"))) return rc;
     }
-    if (k.W) {
+    if (k.W && k.covW) {       // optional weights
+        if (lv.G < 0) return bad_arg(c, k.G, "G < 0");
+        if (lv.G == 0 && lv.W) return bad_arg(c, k.G, "G == 0 with weights given");
+        if (lv.G > 0 && (rc = finite_check(c, lv.W, c->n * (int64_t)lv.G, k.W, "weights"))) return rc;
+    } else if (k.W) {
         if (lv.G < 1) return bad_arg(c, k.G, "G < 1");
         if ((rc = finite_check(c, lv.W, c->n * (int64_t)lv.G, k.W, "weights"))) return rc;
     }
-    if (no_spp && k.base) return bad_arg(c, k.spp, "spp < 1 with ite_draws requested");
+    if (no_spp && (k.base || k.W)) return bad_arg(c, k.spp, "spp < 1 with ite_draws requested");
+    if (k.covW && rq.out.covW && !lv.W) return bad_arg(c, k.covW, "covW needs weights");
     if (k.fp64_only && (c->flags & GPSLC_FLAG_FP32_KERNEL)) {
-        set_err(c, "vector levels, contrasts and weighted effects are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
+        set_err(c, "vector levels, contrasts, slopes and weighted effects are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
         return GPSLC_ERR_UNSUPPORTED;
     }
     return 0;
@@ -1756,6 +1771,19 @@ int gpslc_predict_curve(gpslc_ctx* c, int64_t S, const double* U, const double* 
     return rc ? rc : predict_host(c, rq);
 }
 
+// marginal effects: level l is the slope d f_i(t) / dt at the finite scalar t = doT[l].  G == 0 and NULL weights:
+// the plain 1/n average as gpslc_predict's (covW must be NULL); else G >= 1 weight columns as gpslc_predict_curve's
+int gpslc_predict_slope(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                        const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
+                        int32_t G, const double* weights, double pred_noise, int32_t spp, uint64_t seed, const double* z,
+                        double* meanW, double* varW, double* covW, double* meanITE, double* ite_draws) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.lv.slope = true; rq.lv.G = G; rq.lv.W = weights;
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws, covW};
+    int rc = validate(c, rq, kPredictSlopeArgs);
+    return rc ? rc : predict_host(c, rq);
+}
+
 int gpslc_shard_range(int64_t S, int32_t nblocks, int32_t k, int64_t* s0, int64_t* s1) {
     if (S < 0) return -1;
     if (nblocks < 1) return -2;
@@ -1849,7 +1877,7 @@ int gpslc_predict_multi(int32_t nctx, gpslc_ctx* const* ctxs, int64_t S, const d
     }
 }
 
-// gpslc_ite_distributions*'s body: one level (host) — a scalar, n values (vec) or the contrast of two scalars (base)
+// gpslc_ite_distributions*'s body: one level (host) — a scalar, n values (vec), the contrast of two scalars (base) or a slope
 static int ite_distributions_host(gpslc_ctx* c, const PredictRequest& rq) {
     const int64_t S = rq.post.S;
     if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
@@ -1895,6 +1923,16 @@ int gpslc_ite_distributions_contrast(gpslc_ctx* c, int64_t S, const double* U, c
     rq.lv.base = &doT_base;
     rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
     int rc = validate(c, rq, kIteContrastArgs);
+    return rc ? rc : ite_distributions_host(c, rq);
+}
+
+int gpslc_ite_distributions_slope(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                                  const double* tyLS, const double* yScale, const double* yNoise, double doT,
+                                  double pred_noise, double* MeanITEs, double* CovITEs) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, &doT);
+    rq.lv.slope = true;
+    rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
+    int rc = validate(c, rq, kIteSlopeArgs);
     return rc ? rc : ite_distributions_host(c, rq);
 }
 

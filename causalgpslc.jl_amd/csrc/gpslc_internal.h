@@ -219,6 +219,15 @@ void launch_trsm_robust(const TRef& X, const TRef& L, int k, int i0, int count, 
 // info[g] (if still 0) <- the first nonzero of pair_info[g*lc .. g*lc + lc - 1], g < gs (k_robust.hip)
 void launch_fold_pair_info(const int* pair_info, int* info, int gs, int lc, hipStream_t st);
 
+// The level form of a prediction call: what multiplies B_ij outside the pair loops.
+//   FORM_ORDINARY  f_i(doT_l) - f_i(T_i)
+//   FORM_CONTRAST  f_i(a_l) - f_i(b_l) for the pair (a, b) = (doT[l], doT_base[l])
+//   FORM_SLOPE     d f_i(t) / dt at t = doT[l]: cross term q^a_j = 2 (T_j - a) r^a_j / tyLS^2, prior term 2 / tyLS^2
+enum { FORM_ORDINARY = 0, FORM_CONTRAST = 1, FORM_SLOPE = 2 };
+
+// q^a_j of the slope form, wt = 1 / tyLS^2: the difference T_j - a is formed in fp64 by the caller's arguments
+__host__ __device__ inline double gp_slope_q(double dt, double r, double wt) { return (2.0 * dt) * wt * r; }
+
 struct RhsArgs {
     const double* T; const double* Y; const double* tyLS; const double* doT;
     long long y_sstride;   // right-hand side 0 of sample s is Y + s*y_sstride (0 = shared)
@@ -228,13 +237,14 @@ struct RhsArgs {
     int live_rows;   // > 0 (single augmented tile row of <= 32 right-hand sides, epilogue sums from the rows of R): only the
                      // first 32 rows of the augmented tiles are written (right-hand sides, then zeros) and the augmented
                      // diagonal tile not at all — every reader of those tiles touches the live 16- / 32-row blocks only
-    const double* doT_base;   // non-null: contrasts — level l is the pair (doT[l], doT_base[l]), c_l = (r^a - r^b) .* bsum and
+    const double* doT_base;   // form == FORM_CONTRAST: level l is the pair (doT[l], doT_base[l]), c_l = (r^a - r^b) .* bsum and
                               // sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B
     // G columns of level sums, right-hand side 1 + l + L*g is level l of column g, rows from bw / kw [b][G][Np].  The plain call
     // is G = 1 with bw = bsum, kw = ksum and W null; weighted effects (W non-null) have G weight columns, bw / kw
     // from launch_wsum, sumdelta [b][L*G] and wnorm2 [b][G] = w_g . w_g
     const double* W; int G;   // device, column g fastest: W[g + G*j]
     const double* bw; const double* kw; double* wnorm2;
+    int form;   // FORM_*.  Slope: c_l = q^a .* bw_g and sum(Delta_l) = (2 / tyLS^2) sum B (weighted: (2 / tyLS^2) w . bw), no kw
 };
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
 
@@ -242,7 +252,7 @@ void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
 struct WsumArgs : SampleGrid {
     int G;
     const double* W;       // device, column g fastest: W[g + G*j]
-    double* bw; double* kw;   // [b][G][Np]; kw is not written when with_k == 0 (contrasts need BW only)
+    double* bw; double* kw;   // [b][G][Np]; kw is not written when with_k == 0 (contrasts and slopes need BW only)
     int with_k;
     int binary_t;          // as GramArgs::binary_t: the e_ij of the K that is factorised
 };
@@ -265,12 +275,13 @@ void launch_epilogue(const EpiArgs& e, int nbatch, hipStream_t st);
 struct CurveArgs {
     TRef M; int n, nt, L, G; long long s0; long long S;
     const double* T; const double* tyLS; const double* doT;
-    const double* doT_base;   // non-null: contrasts (level l is the pair (doT[l], doT_base[l]))
+    const double* doT_base;   // form == FORM_CONTRAST (level l is the pair (doT[l], doT_base[l]))
     const double* W;          // device, column g fastest: W[g + G*j]
-    const double* bw; const double* kw;   // [b][G][Np] (launch_wsum); kw is not read for contrasts
+    const double* bw; const double* kw;   // [b][G][Np] (launch_wsum); kw is not read for contrasts and slopes
     double* prior;            // [b][G][L + 2]: beta = w . bw, kappa = w . kw, gamma_l = sum_j w_j r^l_j bw_j
     const double* varW;       // S x L x G, as the epilogue stored it: the diagonal
     double* covW;             // S x L x L x G: element (s, l, l', g) at s + S*(l + L*(l' + L*g))
+    int form;                 // FORM_*.  Slope: P_ll' = (2 wt - 4 (a_l - a_l')^2 wt^2) rho(a_l, a_l') beta, wt = 1 / tyLS^2; no kw
 };
 void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st);
 
@@ -290,8 +301,9 @@ struct IteMeanArgs : SampleGrid {
     double* meanITE;       // element (i, s, l) at i*si + s*ss + l*sl
     long long si, ss, sl;
     int f32;
-    const double* doT_base;   // non-null (fp64 only): contrasts, MeanITE_i(l) = sum_j B_ij (r^a_j - r^b_j) alpha_j for the pair
+    const double* doT_base;   // form == FORM_CONTRAST (fp64 only): MeanITE_i(l) = sum_j B_ij (r^a_j - r^b_j) alpha_j for the pair
                               // (a, b) = (doT[l], doT_base[l])
+    int form;                 // FORM_*.  Slope (fp64 only): MeanITE_i(l) = sum_j B_ij q^a_j alpha_j
 };
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st);
 
@@ -321,8 +333,9 @@ struct DtArgs : SampleGrid {
     double pred_noise;
     TRef W;    // nt x nt rectangular: receives D (rows = i, cols = j), D_ij = B_ij (r_j - e_ij)
     TRef Cm;   // lower packed nt: receives Delta + pred_noise*I (identity on the padding)
-    const double* doT_base;   // non-null (scalar levels only): contrasts, D_ij = B_ij (r^a_j - r^b_j) and
+    const double* doT_base;   // form == FORM_CONTRAST (scalar levels only): D_ij = B_ij (r^a_j - r^b_j) and
                               // Delta_ij = B_ij ((1 - rho) + (1 - rho)) for the pair (doT[l], doT_base[l])
+    int form;                 // FORM_*.  Slope (scalar levels only): D_ij = B_ij q^a_j and Delta_ij = B_ij 2 / tyLS^2
 };
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st);
 

@@ -5,7 +5,8 @@
 //                      fused with the per-tile partial column sums of B = yScale*exp(Lu+Lx) and
 //                      K = B.*E that the SATE path needs.
 //   rhs_prepare/tiles  column sums -> augmented right-hand sides [Y, c(1..L)] and sum(Delta).  CON: the contrast form of
-//                      both (level l = the pair (doT[l], doT_base[l])).
+//                      both (level l = the pair (doT[l], doT_base[l])).  SLP: the slope form (§15).
+//                      FORM is RhsArgs::form; CON / SLP name its two special values inside the kernels.
 //   rhs_w_prepare      the level sums of weighted effects: G weight columns x L levels from bw = B w, kw = K w (k_wsum.hip,
 //                      DESIGN.md §13); rhs_tiles writes their rows.
 //   epilogue           Schur complement of the augmented block -> MeanSATE, VarSATE (plain or weighted), logdet, quad.
@@ -240,9 +241,11 @@ void launch_gram(const GramArgs& g, int nbatch, hipStream_t st) {
 // CON (contrast of the levels a = doT[l] and b = doT_base[l]): the prior block Kss_aa - Kss_ab - Kss_ba + Kss_bb is
 // B ((1 - rho) + (1 - rho)) with rho = exp(-(a - b)^2 / tyLS^2), so sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B: no sum
 // over the columns, and exactly 0.0 when a == b.
+// SLP (slope at a = doT[l]): the prior block is B 2 / tyLS^2 for every level, so sum(Delta_l) = (2 / tyLS^2) sum B.
 // ---------------------------------------------------------------------------------------
-template <bool CON>
+template <int FORM>
 __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -273,6 +276,10 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
         }
         return;
     }
+    if (SLP) {
+        for (int l = tid; l < a.L; l += 256) a.sumdelta[(long long)b * a.L + l] = (2.0 * wt) * btot;
+        return;
+    }
     for (int l = 0; l < a.L; ++l) {
         const double dot = a.doT[l];
         double acc = 0.0;
@@ -289,15 +296,17 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
 // rhs_tiles: write the augmented row tiles: row q of the augmented block is right-hand side q
 // (q = 0: Y, q = 1 + l + L*g: c_l = r_l .* bw_g - kw_g of column g), zero elsewhere; zero the aug x aug tiles.
 // CON: c_l = (r^a - r^b) .* bw_g for the pair (a, b) = (doT[l], doT_base[l]) — the e_ij of the ordinary level cancels, and
-// a == b gives r^a == r^b bit for bit: an exact zero row.
+// a == b gives r^a == r^b bit for bit: an exact zero row.  SLP: c_l = q^a .* bw_g, q^a_j = 2 (T_j - a) r^a_j / tyLS^2, no e_ij either.
 // grid (nt + naug, naug, batch): tile (nt + a, j) with j = blockIdx.x, a = blockIdx.y (j <= nt + a).
-template <bool CON>
+template <int FORM>
 __device__ __forceinline__ double rhs_level_value(const RhsArgs& a, int l, int gj, double wt, const double* bs, const double* ks) {
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
     const double r = gp_rho(a.T[gj], a.doT[l], wt);
+    if (SLP) return gp_slope_q(a.T[gj] - a.doT[l], r, wt) * bs[gj];
     if (CON) return (r - gp_rho(a.T[gj], a.doT_base[l], wt)) * bs[gj];
     return r * bs[gj] - ks[gj];
 }
-template <bool CON>
+template <int FORM>
 __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
     const int tid = threadIdx.x;
     const int j = blockIdx.x, au = blockIdx.y, b = blockIdx.z;
@@ -330,7 +339,7 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
             else if (gq <= R) {
                 const int g = a.G > 1 ? (gq - 1) / a.L : 0, l = gq - 1 - a.L * g;
                 const long long o = ((long long)b * a.G + g) * Np;
-                v = rhs_level_value<CON>(a, l, gj, wt, a.bw + o, a.kw + o);
+                v = rhs_level_value<FORM>(a, l, gj, wt, a.bw + o, a.kw + o);
             }
         }
         tile[c * GP_TS + q] = v;
@@ -342,12 +351,14 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
 // With bw = B w, kw = K w from launch_wsum (B, K symmetric):
 //   c = D' w,  c_j = r_j bw_j - kw_j            w' Delta w = sum_j w_j ((kw_j - 2 r_j bw_j) + bw_j)
 //   CON: c_j = (r^a_j - r^b_j) bw_j             w' Delta w = ((1 - rho) + (1 - rho)) sum_j w_j bw_j
+//   SLP: c_j = q^a_j bw_j                       w' Delta w = (2 / tyLS^2) sum_j w_j bw_j
 // rhs_w_prepare: one workgroup per (right-hand side, sample): sumdelta[b][l + L*g], and (l == 0) wnorm2[b][g] = w_g . w_g;
 // the sums run over the threads' strided j in a fixed tree.  r == 1 (every T equal to doT) and kw == bw give an exact 0.0
 // term by term; a == b gives rho == 1 and 0.0 * sum.
 // ---------------------------------------------------------------------------------------
-template <bool CON>
+template <int FORM>
 __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int qq = blockIdx.x, b = blockIdx.y;
@@ -363,7 +374,7 @@ __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
     for (int j = tid; j < a.n; j += 256) {
         const double w = a.W[(long long)j * a.G + g];
         ww = fma(w, w, ww);
-        if (CON) {
+        if (CON || SLP) {
             acc += w * bs[j];
         } else {
             const double r = gp_rho(a.T[j], dot, wt);
@@ -379,21 +390,24 @@ __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
     if (CON) {
         const double rho = gp_rho(dot, a.doT_base[l], wt);
         a.sumdelta[(long long)b * a.L * a.G + qq] = ((1.0 - rho) + (1.0 - rho)) * tot;
+    } else if (SLP) {
+        a.sumdelta[(long long)b * a.L * a.G + qq] = (2.0 * wt) * tot;
     } else {
         a.sumdelta[(long long)b * a.L * a.G + qq] = tot;
     }
 }
 
 // the plain and the weighted prepare kernels reduce in different orders (both are part of the results); the tiles are one kernel
-template <bool CON>
+template <int FORM>
 static void launch_rhs_t(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.W) hipLaunchKernelGGL(rhs_w_prepare_kernel<CON>, dim3(r.L * r.G, nbatch), dim3(256), 0, st, r);
-    else if (r.with_sums) hipLaunchKernelGGL(rhs_prepare_kernel<CON>, dim3(nbatch), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(rhs_tiles_kernel<CON>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
+    if (r.W) hipLaunchKernelGGL(rhs_w_prepare_kernel<FORM>, dim3(r.L * r.G, nbatch), dim3(256), 0, st, r);
+    else if (r.with_sums) hipLaunchKernelGGL(rhs_prepare_kernel<FORM>, dim3(nbatch), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(rhs_tiles_kernel<FORM>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
 }
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.doT_base) launch_rhs_t<true>(r, nbatch, st);
-    else launch_rhs_t<false>(r, nbatch, st);
+    if (r.form == FORM_SLOPE) launch_rhs_t<FORM_SLOPE>(r, nbatch, st);
+    else if (r.form == FORM_CONTRAST) launch_rhs_t<FORM_CONTRAST>(r, nbatch, st);
+    else launch_rhs_t<FORM_ORDINARY>(r, nbatch, st);
 }
 
 // ---------------------------------------------------------------------------------------

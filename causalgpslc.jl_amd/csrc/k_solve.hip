@@ -77,9 +77,13 @@ void launch_backsolve(const BackArgs& a, int nbatch, hipStream_t st) {
 // cancels, so  MeanITE_i(l) = sum_j B_ij ((r^a_j - r^b_j) alpha_j)  with no K alpha term; a == b stages exact zeros (r^a == r^b
 // bit for bit) and every row returns 0.0.  Only what is staged per column block and the epilogue differ: the pair loop is
 // the same code.
+// SLP (slope at a = doT[l]): D_ij = B_ij q^a_j with q^a_j = 2 (T_j - a) r^a_j / tyLS^2, so
+// MeanITE_i(l) = sum_j B_ij (q^a_j alpha_j): no K alpha term as for CON, and no level gives an exact-zero row.
+// FORM is IteMeanArgs::form; CON / SLP name its two special values inside the kernels.
 // ---------------------------------------------------------------------------------------
-template <int FREG, int LCT, typename RT, int RB, bool CON = false>
+template <int FREG, int LCT, typename RT, int RB, int FORM = FORM_ORDINARY>
 __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
     double* etab = sm;                     // [32] 2^(j/32): table-driven exp (gp_math.h)
@@ -129,6 +133,8 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
                         const RT db = (RT)(a.T[g] - a.doT_base[l0 + ll]);
                         v = ((double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab) -
                              (double)RbfMath<RT>::exp_neg_t(-((db * db) * wtq), etab)) * alpha[g];
+                    } else if (SLP) {
+                        v = gp_slope_q(a.T[g] - a.doT[l0 + ll], (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab), wt) * alpha[g];
                     } else {
                         v = (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab) * alpha[g];
                     }
@@ -171,13 +177,13 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 #pragma unroll
             for (int q = 0; q < RB; ++q) {
                 if (gi[q] >= n) continue;
-                if (CON) {
+                if (CON || SLP) {
 #pragma unroll
                     for (int ll = 0; ll < LCT; ++ll)
                         if (ll < nl) {
                             const double v = acc[q][ll] + red[(q * GP_TS + r) * LCT + ll];
                             a.meanITE[(long long)gi[q] * a.si + s * a.ss + (long long)(l0 + ll) * a.sl] =
-                                (a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : v;
+                                (CON && a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : v;
                         }
                     continue;
                 }
@@ -207,12 +213,14 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 //   - what is staged: R[j, l] = r_j(l) alpha_j; CON (contrasts as in ite_mean_kernel): (r^a_j - r^b_j) alpha_j;
 //   - the store, per 16-row sub-tile: rows i < n only, (K alpha)_i and T_i loaded once; instances with T_i == doT_l get the
 //     reference's exact 0.0 (row i of Ks' - K is identically zero there).  CON: no K alpha term, 0.0 for a level with a == b.
+//     SLP: q^a_j alpha_j is staged, no K alpha term and no exact-zero case.
 // ---------------------------------------------------------------------------------------
-template <int FREG, bool CON = false>   // FREG > 0: this lane's two rows' features live in registers (F <= FREG); 0: read from LDS
+template <int FREG, int FORM = FORM_ORDINARY>   // FREG > 0: this lane's two rows' features live in registers (F <= FREG); 0: read from LDS
 __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const long long b = blockIdx.y, s = a.s0 + b;
     const double* alpha = a.alpha + b * (a.nt * GP_TS);
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
     pair_mfma_body<FREG, false, 0>(
         a, s, a.L, sm,
         [&](int j, int l, double wt, const double* etab) {
@@ -221,14 +229,15 @@ __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
                 const double db = a.T[j] - a.doT_base[l];
                 return (gp_exp_neg_tab(-((dt * dt) * wt), etab) - gp_exp_neg_tab(-((db * db) * wt), etab)) * alpha[j];
             }
+            if (SLP) return gp_slope_q(dt, gp_exp_neg_tab(-((dt * dt) * wt), etab), wt) * alpha[j];
             return gp_exp_neg_tab(-((dt * dt) * wt), etab) * alpha[j];
         },
         [&](int gi, int l0, int nl, const d4* acc, const d4*) {
             if (gi >= a.n) return;
             double* out = a.meanITE + (long long)gi * a.si + s * a.ss;
-            if (CON) {
+            if (CON || SLP) {
                 pair_mfma_each_column(nl, [&](int q, int v, int ll) {
-                    out[(long long)(l0 + ll) * a.sl] = (a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : acc[q][v];
+                    out[(long long)(l0 + ll) * a.sl] = (CON && a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : acc[q][v];
                 });
                 return;
             }
@@ -240,51 +249,54 @@ __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
         });
 }
 
-template <bool CON>
+template <int FORM>
 static void launch_ite_mean_mfma(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     pair_mfma_freg_ladder(a.nU + a.nX, [&](auto freg) {
         constexpr int FREG = decltype(freg)::value;
-        pair_mfma_launch<ite_mean_mfma_kernel<FREG, CON>, FREG, false>(a, nbatch, st);
+        pair_mfma_launch<ite_mean_mfma_kernel<FREG, FORM>, FREG, false>(a, nbatch, st);
     });
 }
 
-template <int FREG, int LCT, typename RT, bool CON>
+template <int FREG, int LCT, typename RT, int FORM>
 static void launch_ite_mean_t(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     constexpr int RB = 1;     // row blocks per workgroup (2 measured slower: occupancy)
     const int bytes = (GP_EXP_TAB_DOUBLES + (1 + RB) * LCT * GP_TS) * 8 + (FREG * GP_TS) * (int)sizeof(RT);
     static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)ite_mean_kernel<FREG, LCT, RT, RB, CON>, bytes);
-    hipLaunchKernelGGL((ite_mean_kernel<FREG, LCT, RT, RB, CON>), dim3((a.nt + RB - 1) / RB, nbatch), dim3(256), bytes, st, a);
+    lds_opt_in(attr_set, (const void*)ite_mean_kernel<FREG, LCT, RT, RB, FORM>, bytes);
+    hipLaunchKernelGGL((ite_mean_kernel<FREG, LCT, RT, RB, FORM>), dim3((a.nt + RB - 1) / RB, nbatch), dim3(256), bytes, st, a);
 }
-template <int FREG, typename RT, bool CON>
+template <int FREG, typename RT, int FORM>
 static void launch_ite_mean_f(const IteMeanArgs& a, int nbatch, hipStream_t st) {
-    if (a.L <= 1) launch_ite_mean_t<FREG, 1, RT, CON>(a, nbatch, st);
-    else if (a.L <= 4) launch_ite_mean_t<FREG, 4, RT, CON>(a, nbatch, st);
-    else if (!CON) launch_ite_mean_t<FREG, 16, RT, false>(a, nbatch, st);     // contrasts (fp64): L > 4 is the MFMA kernel's
+    if (a.L <= 1) launch_ite_mean_t<FREG, 1, RT, FORM>(a, nbatch, st);
+    else if (a.L <= 4) launch_ite_mean_t<FREG, 4, RT, FORM>(a, nbatch, st);
+    else if (FORM == FORM_ORDINARY) launch_ite_mean_t<FREG, 16, RT, FORM_ORDINARY>(a, nbatch, st);     // contrasts, slopes (fp64): L > 4 is the MFMA kernel's
 }
-template <typename RT, bool CON = false>
+template <typename RT, int FORM = FORM_ORDINARY>
 static void launch_ite_mean_r(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     const int F = a.nU + a.nX;
     // exact register counts for the common feature widths: the pass is fp64-VALU bound (2 instructions per
     // feature per element), a padded feature is paid in full
-    if (F <= 4) launch_ite_mean_f<4, RT, CON>(a, nbatch, st);
-    else if (F <= 5) launch_ite_mean_f<5, RT, CON>(a, nbatch, st);      // BASELINE config 2: nU + nX = 1 + 4
-    else if (F <= 6) launch_ite_mean_f<6, RT, CON>(a, nbatch, st);
-    else if (F <= 8) launch_ite_mean_f<8, RT, CON>(a, nbatch, st);
-    else if (F <= 10) launch_ite_mean_f<10, RT, CON>(a, nbatch, st);
-    else if (F <= 12) launch_ite_mean_f<12, RT, CON>(a, nbatch, st);
-    else if (F <= 16) launch_ite_mean_f<16, RT, CON>(a, nbatch, st);
-    else if (F <= 20) launch_ite_mean_f<20, RT, CON>(a, nbatch, st);
-    else launch_ite_mean_f<32, RT, CON>(a, nbatch, st);
+    if (F <= 4) launch_ite_mean_f<4, RT, FORM>(a, nbatch, st);
+    else if (F <= 5) launch_ite_mean_f<5, RT, FORM>(a, nbatch, st);      // BASELINE config 2: nU + nX = 1 + 4
+    else if (F <= 6) launch_ite_mean_f<6, RT, FORM>(a, nbatch, st);
+    else if (F <= 8) launch_ite_mean_f<8, RT, FORM>(a, nbatch, st);
+    else if (F <= 10) launch_ite_mean_f<10, RT, FORM>(a, nbatch, st);
+    else if (F <= 12) launch_ite_mean_f<12, RT, FORM>(a, nbatch, st);
+    else if (F <= 16) launch_ite_mean_f<16, RT, FORM>(a, nbatch, st);
+    else if (F <= 20) launch_ite_mean_f<20, RT, FORM>(a, nbatch, st);
+    else launch_ite_mean_f<32, RT, FORM>(a, nbatch, st);
+}
+// contrasts and slopes: fp64 contexts only (the entry points refuse the fp32 kernel mode)
+template <int FORM>
+static void launch_ite_mean_f64(const IteMeanArgs& a, int nbatch, hipStream_t st) {
+    if (a.L > 4) launch_ite_mean_mfma<FORM>(a, nbatch, st);
+    else launch_ite_mean_r<double, FORM>(a, nbatch, st);
 }
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
+    if (a.form == FORM_CONTRAST) { launch_ite_mean_f64<FORM_CONTRAST>(a, nbatch, st); return; }
+    if (a.form == FORM_SLOPE) { launch_ite_mean_f64<FORM_SLOPE>(a, nbatch, st); return; }
     // many levels: the (B R) product belongs on the matrix cores (fp64 path; the fp32 mode keeps the VALU kernel)
-    if (a.doT_base) {       // contrasts: fp64 contexts only (the entry points refuse the fp32 kernel mode)
-        if (a.L > 4) launch_ite_mean_mfma<true>(a, nbatch, st);
-        else launch_ite_mean_r<double, true>(a, nbatch, st);
-        return;
-    }
-    if (!a.f32 && a.L > 4) { launch_ite_mean_mfma<false>(a, nbatch, st); return; }
+    if (!a.f32 && a.L > 4) { launch_ite_mean_mfma<FORM_ORDINARY>(a, nbatch, st); return; }
     if (a.f32) launch_ite_mean_r<float>(a, nbatch, st);
     else launch_ite_mean_r<double>(a, nbatch, st);
 }
@@ -384,33 +396,41 @@ __device__ __forceinline__ void tile_build_body(const SampleGrid& a, long long s
 // VEC (per-individual intervention d, k_vec.hip): D_ij = B_ij (g_ji - e_ij), Delta_ij = B_ij (e_ij - g_ij - g_ji + h_ij).
 // CON (contrast of the scalar levels a = doT[l], b = doT_base[l]): D_ij = B_ij (r^a_j - r^b_j) (rc_ holds the
 // difference) and Delta_ij = B_ij ((1 - rho) + (1 - rho)), rho = exp(-(a - b)^2 / tyLS^2) — exactly 0 when a == b.
+// SLP (slope at the scalar level a = doT[l]): D_ij = B_ij q^a_j (rc_ holds q^a) and Delta_ij = B_ij 2 / tyLS^2.
+// FORM is DtArgs::form (FORM_ORDINARY with VEC).
 // ---------------------------------------------------------------------------------------
-template <bool VEC, bool CON = false>
+template <bool VEC, int FORM = FORM_ORDINARY>
 __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int ti = blockIdx.x / a.nt, tj = blockIdx.x % a.nt;
     const long long b = blockIdx.y, s = a.s0 + b / a.lc;       // batch element = (sample, level) pair
     const int l = a.l0 + (int)(b % a.lc), n = a.n;
     const double doT = VEC ? 0.0 : a.doT[l], doTb = CON ? a.doT_base[l] : 0.0;
     const double* dv = VEC ? a.doT + (long long)n * l : nullptr;
-    double kss = 0.0;       // CON: (1 - rho) + (1 - rho)
+    double kss = 0.0;       // CON: (1 - rho) + (1 - rho); SLP: 2 / tyLS^2
     if (CON) {
         const double tl = a.p.tyLS[s];
         const double rho = gp_rho(doT, doTb, 1.0 / (tl * tl));
         kss = (1.0 - rho) + (1.0 - rho);
     }
+    if (SLP) {
+        const double tl = a.p.tyLS[s];
+        kss = 2.0 * (1.0 / (tl * tl));
+    }
     double* wt_tile = tref_tile(a.W, b, ti, tj);
     double* c_tile = (ti >= tj) ? tref_tile(a.Cm, b, ti, tj) : nullptr;
-    tile_build_body<CON ? LEVEL_NONE : VEC ? LEVEL_VECTOR : LEVEL_SCALAR>(
+    tile_build_body<(CON || SLP) ? LEVEL_NONE : VEC ? LEVEL_VECTOR : LEVEL_SCALAR>(
         a, s, ti, tj, sm,
         [&](int g, double t, double wt) {
             if constexpr (VEC) return g < n ? dv[g] : 0.0;
             else if constexpr (CON) return gp_rho(t, doT, wt) - gp_rho(t, doTb, wt);
+            else if constexpr (SLP) return gp_slope_q(t - doT, gp_rho(t, doT, wt), wt);
             else return gp_rho(t, doT, wt);
         },
         [&](int rp, int cq, bool inside, bool diag, double Bv, const LevelTerms& t) {
             double Dv, Cv;
-            if (CON) {
+            if (CON || SLP) {
                 Dv = Bv * t.gji;
                 Cv = Bv * kss;
             } else {
@@ -424,14 +444,15 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
         });
 }
 
-template <bool VEC, bool CON = false>
+template <bool VEC, int FORM = FORM_ORDINARY>
 static void launch_dt_build_t(const DtArgs& a, int nbatch, hipStream_t st) {
     static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)dt_build_kernel<VEC, CON>, tile_build_lds_bytes(MAXF));
-    hipLaunchKernelGGL((dt_build_kernel<VEC, CON>), dim3(a.nt * a.nt, nbatch), dim3(256), tile_build_lds_bytes(a.nU + a.nX), st, a);
+    lds_opt_in(attr_set, (const void*)dt_build_kernel<VEC, FORM>, tile_build_lds_bytes(MAXF));
+    hipLaunchKernelGGL((dt_build_kernel<VEC, FORM>), dim3(a.nt * a.nt, nbatch), dim3(256), tile_build_lds_bytes(a.nU + a.nX), st, a);
 }
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st) {
-    if (a.doT_base) launch_dt_build_t<false, true>(a, nbatch, st);
+    if (a.form == FORM_SLOPE) launch_dt_build_t<false, FORM_SLOPE>(a, nbatch, st);
+    else if (a.form == FORM_CONTRAST) launch_dt_build_t<false, FORM_CONTRAST>(a, nbatch, st);
     else if (a.vec) launch_dt_build_t<true>(a, nbatch, st);
     else launch_dt_build_t<false>(a, nbatch, st);
 }

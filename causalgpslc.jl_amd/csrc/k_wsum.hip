@@ -10,7 +10,7 @@
 // change a bit).  This file supplies the two things the body asks of a caller:
 //   - what is staged: X[j, g] = W[j, g] (W is g-fastest: consecutive threads read consecutive weight columns);
 //   - the store: bw / kw are [b][G][Np], rows i >= n are written as 0.0.
-// WK = false (contrasts: c needs no KW): no e, no second MFMA, kw is not written.  BIN: binary treatments, e is 1 or
+// WK = false (contrasts and slopes: c needs no KW): no e, no second MFMA, kw is not written.  BIN: binary treatments, e is 1 or
 // exp(-1/tyLS^2).
 #include "pair_mfma.h"
 

@@ -326,6 +326,37 @@ int gpslc_predict_curve(gpslc_ctx* ctx, int64_t S, const double* U, const double
                         const double* z_or_null, double* meanW, double* varW, double* covW, double* meanITE,
                         double* ite_draws);
 
+/* Marginal effects: level l is the slope of individual i's response surface in the treatment at dose a = doT[l], everybody set
+ * to that dose,
+ *     g_i(a) = d f_i(t) / dt at t = a;
+ * its average over the population is the slope of the dose-response curve.  The derivative of a Gaussian process with an RBF
+ * kernel is a Gaussian process in closed form: with B = yScale exp(Lu + Lx), wt = 1 / tyLS^2, r^a_j = exp(-(T_j - a)^2 wt),
+ * q^a_j = 2 (T_j - a) wt r^a_j (T_j - a formed in fp64), alpha = (K + yNoise I)^-1 Y:
+ *     D_ij = Cov(g_i(a), Y_j) = B_ij q^a_j;    MeanITE = D alpha;
+ *     CovITE = 2 wt B - D (K + yNoise I)^-1 D',  + pred_noise*I after symmetrisation (src/estimation.jl:82).
+ * Nothing cancels (a finite difference of gpslc_predict_contrast loses its mean and, more so, its variance as the two levels
+ * approach each other), and a slope level costs what a scalar level costs: only what multiplies B_ij outside the pair loops
+ * differs.  doT: L finite host scalars (else -10).
+ *   weights_or_null == NULL and G == 0 (the plain form): meanW, varW are S x L with gpslc_predict's meanSATE / varSATE semantics,
+ *       the 1/n average: mean = w . z / n, var = (2 wt sum(B) - w . w + n pred_noise) / n^2 with w = L^-1 (q^a .* bsum); covW must be
+ *       NULL (else -19)
+ *   weights n x G, G >= 1 (the weighted form): meanW, varW S x L x G and covW S x L x L x G (or NULL) with the layouts and
+ *       guarantees of gpslc_predict_weighted / gpslc_predict_curve — c_j = q^a_j bw_j, w' Delta w = 2 wt (w . bw) (no kw), and across
+ *       the levels P_ll' = (2 wt - 4 (a_l - a_l')^2 wt^2) rho(a_l, a_l') beta; the block is exactly symmetric, its diagonal
+ *       bit-identical to varW, a zero weight column gives an all-0.0 block
+ *   meanITE n x S x L, ite_draws L x n x (S*spp): the per-individual slope; normals, Philox streams, gpslc_set_ensemble placement,
+ *       chunking and gpslc_last_info are gpslc_predict's
+ * Errors: G < 0, or G == 0 with weights given: -11; G > 0 with NULL weights, or a non-finite weight: -12; ite_draws with spp < 1:
+ * -14; covW without weights: -19.  Scalar levels and fp64 only: a ctx created with GPSLC_FLAG_FP32_KERNEL returns
+ * GPSLC_ERR_UNSUPPORTED.  Not sharded (gpslc_predict_multi is unchanged).  A treatment whose values are all equal to a gives a
+ * CovITE that is semi-definite to rounding; the draws factorise it robustly, as every CovITE.   */
+int gpslc_predict_slope(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                        const double* xyLS, const double* tyLS, const double* yScale,
+                        const double* yNoise, int32_t L, const double* doT, int32_t G,
+                        const double* weights_or_null, double pred_noise, int32_t spp, uint64_t seed,
+                        const double* z_or_null, double* meanW, double* varW, double* covW, double* meanITE,
+                        double* ite_draws);
+
 /* The same call sharded over several GPUs of one node: what the loop of predictCounterfactualEffects (src/prediction.jl:30-33)
  * over the posterior samples (src/estimation.jl:78-84) becomes when the ensemble is partitioned.  ctxs[0..nctx) are
  * DISTINCT contexts created with the same (n, nX, nU), one per device (gpslc_create(&ctx_k, device_k, ...)), each holding the data
@@ -372,6 +403,14 @@ int gpslc_ite_distributions_contrast(gpslc_ctx* ctx, int64_t S, const double* U,
                                      const double* xyLS, const double* tyLS, const double* yScale,
                                      const double* yNoise, double doT, double doT_base, double pred_noise,
                                      double* MeanITEs, double* CovITEs);
+
+/* ITEDistributions for the slope d f_i(t) / dt at the scalar level t = doT (see gpslc_predict_slope): same outputs and layouts as
+ * gpslc_ite_distributions, CovITEs with its + pred_noise*I.  A non-finite doT returns -9.  GPSLC_FLAG_FP32_KERNEL:
+ * GPSLC_ERR_UNSUPPORTED. */
+int gpslc_ite_distributions_slope(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                                  const double* xyLS, const double* tyLS, const double* yScale,
+                                  const double* yNoise, double doT, double pred_noise,
+                                  double* MeanITEs, double* CovITEs);
 
 /* likelihoodDistribution(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT) (src/likelihood.jl:8-52 and
  * its three reduced methods :55-94, :97-136, :139-174) for ONE parameter set, as the reference exports it:

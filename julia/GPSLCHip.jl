@@ -343,6 +343,33 @@ function predict_curve(c::Ctx, p::Pack, doT::Vector{Float64}, doT_base::Union{No
     mW, vW, cW, mI, dr
 end
 
+"""Marginal effects (gpslc_predict_slope): level l is the slope d f_i(t) / dt at t = `doT[l]`, everybody set to that dose — its
+average over the population is the slope of the dose-response curve.  `weights === nothing`: the plain 1/n average, mW and vW
+are S x L with `predict`'s meanSATE / varSATE semantics and covW is `nothing`.  An n x G matrix: mW, vW S x L x G and covW
+S x L x L x G as `predict_curve`'s (`want_cov=false` leaves covW out).  MeanITE and the draws are the per-individual slope.
+Returns (mW, vW, covW | nothing, meanITE | nothing, ite | nothing)."""
+function predict_slope(c::Ctx, p::Pack, doT::Vector{Float64}, weights::Union{Nothing,Matrix{Float64}}, pred_noise::Float64;
+                       spp::Integer=0, seed::Integer=0, z=nothing, want_mean_ite::Bool=false, want_draws::Bool=false,
+                       want_cov::Bool=true)
+    S, L, n = length(p.tyLS), length(doT), c.n
+    G = weights === nothing ? 0 : size(weights, 2)
+    weights === nothing || size(weights, 1) == n || throw(DimensionMismatch("weights has $(size(weights, 1)) rows, n = $n"))
+    mW = weights === nothing ? Array{Float64}(undef, S, L) : Array{Float64}(undef, S, L, G)
+    vW = similar(mW)
+    cW = (weights !== nothing && want_cov) ? Array{Float64}(undef, S, L, L, G) : nothing
+    mI = want_mean_ite ? Array{Float64}(undef, n, S, L) : nothing
+    dr = want_draws ? Array{Float64}(undef, L, n, S * spp) : nothing
+    zf = f64(z)
+    GC.@preserve p doT weights zf mW vW cW mI dr check(c, ccall((:gpslc_predict_slope, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Int32, UInt64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        L, pointer(doT), G, ptr(weights), pred_noise, spp, seed, ptr(zf),
+        pointer(mW), pointer(vW), ptr(cW), ptr(mI), ptr(dr)))
+    mW, vW, cW, mI, dr
+end
+
 """`predict` sharded over several GPUs of one node — `cs` = one context per device (`Ctx(n, nX, nU; device=k)`, each with
 the data: `set_data!` on every one), the posterior samples split into contiguous blocks, one host thread per context inside the
 library, every device copying its block of the results into these host arrays.  Same results as `predict(cs[1], …)` over all S
@@ -423,6 +450,19 @@ function ite_distributions_contrast(c::Ctx, p::Pack, doT::Float64, doT_base::Flo
          Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}),
         c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
         doT, doT_base, pred_noise, pointer(M), ptr(Cv)))
+    M, Cv
+end
+
+"""`ite_distributions` for the slope d f_i(t) / dt at the scalar level t = `doT`: gpslc_ite_distributions_slope."""
+function ite_distributions_slope(c::Ctx, p::Pack, doT::Float64, pred_noise::Float64; want_cov::Bool=true)
+    S, n = length(p.tyLS), c.n
+    M = Matrix{Float64}(undef, S, n)
+    Cv = want_cov ? Array{Float64}(undef, S, n, n) : nothing
+    GC.@preserve p M Cv check(c, ccall((:gpslc_ite_distributions_slope, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Float64, Float64, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        doT, pred_noise, pointer(M), ptr(Cv)))
     M, Cv
 end
 
@@ -797,6 +837,17 @@ function _level_predict(g::GPSLCObject, devices, lv, baseline; kw...)
                               g.hyperparams.predictionCovarianceNoise; kw...)
 end
 
+# `slope=true` of the estimation methods below: the marginal effect d f_i(t) / dt at the scalar level t = doT instead of a difference
+# of two settings (gpslc_predict_slope / gpslc_ite_distributions_slope); combines with `weights=`, not with `baseline=`, a
+# per-individual doT or `devices=`
+function _slope_predict(g::GPSLCObject, devices, lv, baseline, weights; kw...)
+    baseline === nothing || throw(ArgumentError("slope=true cannot be combined with baseline=: the slope is a derivative at one level, not a contrast"))
+    lv isa Vector{Float64} || throw(ArgumentError("slope=true needs a scalar doT: slopes at per-individual intervention vectors are not supported"))
+    devices === nothing || throw(ArgumentError("slope=true is not sharded over devices: pass devices=nothing"))
+    Wm = weights === nothing ? nothing : _weights(weights, getN(g))
+    GPSLCHip.predict_slope(ctx(g), posterior_pack(g), lv, Wm, g.hyperparams.predictionCovarianceNoise; kw...)
+end
+
 # `weights=` of SATEDistributions / sampleSATE: nothing = the average over everybody; a length-n vector or an n x G matrix of
 # weights used as given (a Bool vector / matrix is a mask: that group's average), gpslc_predict_weighted — scalar doT, one GPU only
 _weight_column(w::AbstractVector{Bool}) = (any(w) || throw(ArgumentError("weights= has an empty group mask")); Float64.(w) ./ count(w))
@@ -930,14 +981,25 @@ function conditionalITE(g::GPSLCObject, psindex::Int64, doT::Intervention)      
     conditionalITE(uyLS, xyLS, tyLS, yNoise, yScale, U, g.X, g.T, g.Y, doT)
 end
 
-function ITEDistributions(g::GPSLCObject, doT::Intervention; baseline=nothing)                                     # :66-86
+function ITEDistributions(g::GPSLCObject, doT::Intervention; baseline=nothing, slope::Bool=false)                  # :66-86
     d, pn = _dot(doT, getN(g)), g.hyperparams.predictionCovarianceNoise
+    if slope
+        baseline === nothing || throw(ArgumentError("slope=true cannot be combined with baseline=: the slope is a derivative at one level, not a contrast"))
+        d isa Float64 || throw(ArgumentError("slope=true needs a scalar doT: slopes at per-individual intervention vectors are not supported"))
+        return GPSLCHip.ite_distributions_slope(ctx(g), posterior_pack(g), d, pn)
+    end
     baseline === nothing && return _ite_dists(ctx(g), posterior_pack(g), d, pn)
     d isa Float64 || throw(ArgumentError("baseline= needs a scalar doT: contrasts of per-individual intervention vectors are not supported"))
     GPSLCHip.ite_distributions_contrast(ctx(g), posterior_pack(g), d, _baseline(baseline), pn)
 end
 
-function SATEDistributions(g::GPSLCObject, doT::Intervention; devices=nothing, baseline=nothing, weights=nothing)  # :127-140
+function SATEDistributions(g::GPSLCObject, doT::Intervention; devices=nothing, baseline=nothing, weights=nothing,
+                           slope::Bool=false)                                                                      # :127-140
+    if slope                     # the average marginal effect at doT; shapes as below
+        mW, vW, _, _, _ = _slope_predict(g, devices, _levels(_dot(doT, getN(g))), baseline, weights; want_cov=false)
+        weights === nothing && return mW[:, 1], vW[:, 1]
+        return weights isa AbstractVector ? (mW[:, 1, 1], vW[:, 1, 1]) : (mW[:, 1, :], vW[:, 1, :])
+    end
     if weights !== nothing       # weighted average effects: (S,) for a weight vector, S x G for an n x G matrix
         mW, vW = _weighted_predict(g, devices, _levels(_dot(doT, getN(g))), baseline, weights)
         return weights isa AbstractVector ? (mW[:, 1, 1], vW[:, 1, 1]) : (mW[:, 1, :], vW[:, 1, :])
@@ -960,16 +1022,22 @@ function _normals(n, spp, S, L, seed)
 end
 
 function sampleITE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64=10,
-                   seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing)                        # :86-89
+                   seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing, slope::Bool=false)     # :86-89
     n, S = getN(g), getNumPosteriorSamples(g)
     sd, z = _normals(n, samplesPerPosterior, S, 1, seed)
+    if slope
+        _, _, _, _, ite = _slope_predict(g, devices, _levels(_dot(doT, n)), baseline, nothing; spp=samplesPerPosterior, seed=sd, z=z,
+                                         want_draws=true)
+        return ite[1, :, :]
+    end
     _, _, _, ite = _level_predict(g, devices, _levels(_dot(doT, n)), baseline; spp=samplesPerPosterior, seed=sd, z=z, want_draws=true)
     ite[1, :, :]                                                          # n x (S * spp), sample outer / draw inner (:100-107)
 end
 
 function sampleSATE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64=10,
-                    seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing, weights=nothing)      # :108-111
-    MeanSATEs, VarSATEs = SATEDistributions(g, doT; devices=devices, baseline=baseline, weights=weights)
+                    seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing, weights=nothing,
+                    slope::Bool=false)                                                                             # :108-111
+    MeanSATEs, VarSATEs = SATEDistributions(g, doT; devices=devices, baseline=baseline, weights=weights, slope=slope)
     if MeanSATEs isa AbstractMatrix      # an n x G weight matrix: G x (S * spp), group g on the Philox seed `seed + g - 1`
         G = size(MeanSATEs, 2)
         rows = [seed === nothing ?
@@ -989,28 +1057,35 @@ _curve_baseline(b::Nothing, L) = nothing
 _curve_baseline(b::Real, L) = fill(Float64(b), L)
 _curve_baseline(b::AbstractVector{<:Real}, L) =
     (length(b) == L || throw(ArgumentError("baseline= needs one value per level: $(length(b)) values, L = $L")); Vector{Float64}(b))
-function _curve(g::GPSLCObject, doTs::AbstractVector{<:Real}, baseline, weights, devices)
-    devices === nothing || throw(ArgumentError("effect curves are not sharded over devices: pass devices=nothing"))
+function _curve(g::GPSLCObject, doTs::AbstractVector{<:Real}, baseline, weights, devices, slope::Bool=false)
     n = getN(g)
     lv = Vector{Float64}(doTs)
+    if slope                     # the curve of average marginal effects: gpslc_predict_slope's weighted form, 1/n included
+        mW, _, cW, _, _ = _slope_predict(g, devices, lv, baseline, weights === nothing ? fill(1.0 / n, n) : weights)
+        return mW, cW, !(weights isa AbstractMatrix)
+    end
+    devices === nothing || throw(ArgumentError("effect curves are not sharded over devices: pass devices=nothing"))
     Wm = weights === nothing ? fill(1.0 / n, n, 1) : _weights(weights, n)
     mW, _, cW, _, _ = GPSLCHip.predict_curve(ctx(g), posterior_pack(g), lv, _curve_baseline(baseline, length(lv)), Wm,
                                              g.hyperparams.predictionCovarianceNoise)
     mW, cW, !(weights isa AbstractMatrix)
 end
 
-"""effectCurve(g, doTs; baseline, weights) -> (mean S x L [x G], cov S x L x L [x G]): the weighted effect over the L scalar
-levels `doTs` and its joint covariance across the levels, per posterior sample."""
-function effectCurve(g::GPSLCObject, doTs::AbstractVector{<:Real}; baseline=nothing, weights=nothing, devices=nothing)
-    mW, cW, vec = _curve(g, doTs, baseline, weights, devices)
+"""effectCurve(g, doTs; baseline, weights, slope) -> (mean S x L [x G], cov S x L x L [x G]): the weighted effect over the L scalar
+levels `doTs` and its joint covariance across the levels, per posterior sample.  `slope=true`: the weighted marginal effects
+d f / dt at the levels — the derivative of the dose-response curve — instead."""
+function effectCurve(g::GPSLCObject, doTs::AbstractVector{<:Real}; baseline=nothing, weights=nothing, devices=nothing,
+                     slope::Bool=false)
+    mW, cW, vec = _curve(g, doTs, baseline, weights, devices, slope)
     vec ? (mW[:, :, 1], cW[:, :, :, 1]) : (mW, cW)
 end
 
 """sampleEffectCurve(g, doTs; samplesPerPosterior, seed, baseline, weights) -> L x (S * spp) [G x L x (S * spp)] joint draws of
 the curve, column order sample-outer / draw-inner: every column is ONE curve over the L levels."""
 function sampleEffectCurve(g::GPSLCObject, doTs::AbstractVector{<:Real}; samplesPerPosterior::Int64=10,
-                           seed::Union{Nothing,Integer}=nothing, baseline=nothing, weights=nothing, devices=nothing)
-    mW, cW, vec = _curve(g, doTs, baseline, weights, devices)
+                           seed::Union{Nothing,Integer}=nothing, baseline=nothing, weights=nothing, devices=nothing,
+                           slope::Bool=false)
+    mW, cW, vec = _curve(g, doTs, baseline, weights, devices, slope)
     S, L, G = size(mW)
     dr = seed === nothing ? GPSLCHip.curve_samples(mW, cW, samplesPerPosterior; z=randn(L, samplesPerPosterior, S, G)) :
                             GPSLCHip.curve_samples(mW, cW, samplesPerPosterior; seed=UInt64(seed))
