@@ -80,6 +80,23 @@ def _slope_refusals(slope, baseline, vec, devices):
         raise ValueError("slope=True is not sharded over devices: call without devices=")
 
 
+def _outcome_refusals(outcome, baseline, slope, vec, weights, devices):
+    """What ``outcome=True`` (gpslc_predict_outcome / gpslc_predict_outcome_vec) cannot be combined with, refused before any
+    device work.  Vector levels are allowed; weights with them are not."""
+    if not outcome:
+        return
+    if baseline is not None:
+        raise ValueError("outcome=True cannot be combined with baseline=: the contrast is the difference of two outcomes, "
+                         "f(a) - f(b); ask for the contrast, or for the outcomes at a and at b")
+    if slope:
+        raise ValueError("outcome=True cannot be combined with slope=True: the outcome is a level of the surface, the slope its derivative")
+    if devices is not None:
+        raise ValueError("outcome=True is not sharded over devices: call without devices=")
+    if weights is not None and vec:
+        raise ValueError("outcome=True with weights= needs scalar levels: weighted outcomes at per-individual intervention "
+                         "vectors are not supported")
+
+
 def _weight_row(w, n):
     """One weight vector for n individuals -> (n,) float64.  Float (or integer) values are used as given; a Bool vector is a
     group mask and becomes that group's average, ``mask / mask.sum()`` (an empty mask raises ValueError)."""
@@ -432,9 +449,10 @@ def conditionalITE(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT):
     return M[0], Cv[0]
 
 
-def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=None, slope=False):
+def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=None, slope=False, outcome=False):
     n, S = g.getN(), g.getNumPosteriorSamples()
     x, d = _intervention(doT, n)
+    _outcome_refusals(outcome, baseline, slope, d is not None, None, None)
     _slope_refusals(slope, baseline, d is not None, None)
     if baseline is not None:
         if d is not None:
@@ -443,7 +461,11 @@ def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=
     ctx = g.ctx()
     M = np.empty((S, n), order="F")
     Cv = np.empty((S, n, n), order="F") if want_cov else None
-    if slope:
+    if outcome and d is None:
+        st = ctx.lib.gpslc_ite_distributions_outcome(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
+    elif outcome:
+        st = ctx.lib.gpslc_ite_distributions_outcome_vec(ctx.h, S, *g._params(), _p(d), float(pred_noise), _p(M), _p(Cv))
+    elif slope:
         st = ctx.lib.gpslc_ite_distributions_slope(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
     elif baseline is not None:
         st = ctx.lib.gpslc_ite_distributions_contrast(ctx.h, S, *g._params(), x, base, float(pred_noise), _p(M), _p(Cv))
@@ -455,11 +477,13 @@ def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=
     return M, Cv
 
 
-def ITEDistributions(g: GPSLCObject, doT, baseline=None, slope=False):
+def ITEDistributions(g: GPSLCObject, doT, baseline=None, slope=False, outcome=False):
     """MeanITEs (S, n), CovITEs (S, n, n) incl. + I*predictionCovarianceNoise (src/estimation.jl:66-86).  ``baseline`` = a
     scalar b: the contrast f(doT) - f(b) of two scalar levels instead of f(doT) - f(T) (gpslc_ite_distributions_contrast).
-    ``slope=True``: the marginal effect d f_i(t) / dt at the scalar t = doT (gpslc_ite_distributions_slope; see predict)."""
-    return _ite_distributions(g, doT, g.hyperparams.predictionCovarianceNoise, baseline=baseline, slope=slope)
+    ``slope=True``: the marginal effect d f_i(t) / dt at the scalar t = doT (gpslc_ite_distributions_slope; see predict).
+    ``outcome=True``: the potential outcome f_i(doT) itself, doT a scalar or a per-individual vector — mean D alpha and covariance
+    CovC22 of src/likelihood.jl:49, + I*predictionCovarianceNoise (gpslc_ite_distributions_outcome[_vec]; see predict)."""
+    return _ite_distributions(g, doT, g.hyperparams.predictionCovarianceNoise, baseline=baseline, slope=slope, outcome=outcome)
 
 
 def conditionalSATE(MeanITE, CovITE):
@@ -468,12 +492,14 @@ def conditionalSATE(MeanITE, CovITE):
     return float(np.sum(MeanITE) / n), float(np.sum(CovITE) / n ** 2)
 
 
-def SATEDistributions(g: GPSLCObject, doT, baseline=None, weights=None, slope=False):
+def SATEDistributions(g: GPSLCObject, doT, baseline=None, weights=None, slope=False, outcome=False):
     """MeanSATEs (S,), VarSATEs (S,) (src/estimation.jl:127-140) — O(N^2) per sample on the GPU,
     without materialising CovITE.  ``baseline`` = a scalar b: the contrast doT against b (see predict).  ``weights`` = a
     length-n vector: the weighted effect w' ITE instead of the average over everybody, same shapes; a (G, n) array: (S, G)
-    each (see predict).  ``slope=True``: the average marginal effect at the scalar doT (see predict)."""
-    m, v, _ = predict(g, _levels(g, doT), baseline=baseline, weights=weights, slope=slope)
+    each (see predict).  ``slope=True``: the average marginal effect at the scalar doT (see predict).
+    ``outcome=True``: the average potential outcome — the dose-response function at the scalar doT, the value of the policy for
+    a per-individual doT (see predict)."""
+    m, v, _ = predict(g, _levels(g, doT), baseline=baseline, weights=weights, slope=slope, outcome=outcome)
     return m[:, 0].copy(), v[:, 0].copy()
 
 
@@ -498,7 +524,8 @@ def _levels(g: GPSLCObject, doT):
 
 
 def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
-            want_draws=False, devices: Optional[Sequence[int]] = None, baseline=None, weights=None, slope=False):
+            want_draws=False, devices: Optional[Sequence[int]] = None, baseline=None, weights=None, slope=False,
+            outcome=False):
     """The ensemble entry point (gpslc_predict): returns MeanSATE (S, L), VarSATE (S, L) and, when
     asked, MeanITE (n, S, L) / draws (L, n, S*spp).  ``doTs``: L scalar levels (1-D), or an (L, n) array of L per-individual
     intervention vectors (gpslc_predict_vec).  ``devices`` = a list of GPU indices shards the posterior samples
@@ -516,10 +543,20 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
     ``slope=True``: level l becomes the marginal effect d f_i(t) / dt at t = doTs[l], everybody set to that dose
     (gpslc_predict_slope) — MeanSATE / VarSATE its average over the population, the slope of the dose-response curve, MeanITE and
     the draws the per-individual slope; exact (the derivative of the Gaussian process, nothing is differenced).  Combines with
-    ``weights``; ``baseline``, vector levels and ``devices`` raise ValueError."""
+    ``weights``; ``baseline``, vector levels and ``devices`` raise ValueError.
+    ``outcome=True``: level l becomes the potential outcome mu_i = f_i(doTs[l]) itself, the response surface and not a difference
+    of it (gpslc_predict_outcome) — MeanSATE / VarSATE its average over the population, the average dose-response function mu(a)
+    (E[Y(1)], E[Y(0)] for a binary treatment), MeanITE and the draws the per-individual outcome.  With an (L, n) array of
+    per-individual levels (gpslc_predict_outcome_vec) MeanSATE / VarSATE are the value of the treatment policy doTs[l] and its
+    variance; doTs[l] = T gives the fitted surface.  The prior mean is zero as in the reference's model: far from the data the
+    outcome returns to 0, not to the sample mean of Y.  This is the latent surface; the predictive distribution of a new
+    observation adds yNoise to the diagonal, which is left to the caller.  Combines with ``weights`` for scalar levels;
+    ``baseline`` (the contrast IS the difference of two outcomes), ``slope``, ``devices`` and ``weights`` with vector levels
+    raise ValueError."""
     n, S = g.getN(), g.getNumPosteriorSamples()
     doTs = np.asarray(doTs, dtype=np.float64)
     vec = doTs.ndim == 2
+    _outcome_refusals(outcome, baseline, slope, vec, weights, devices)
     _slope_refusals(slope, baseline, vec, devices)
     if doTs.ndim > 2 or (vec and doTs.shape[1] != n):
         raise ValueError(f"doTs must be L scalar levels or an (L, n) array of intervention vectors with n = {n}, "
@@ -551,14 +588,18 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
         zz = _f(z)
         if zz.shape != (n, spp, S, L):
             raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
-    if slope:
+    if outcome and vec:
+        st = ctx.lib.gpslc_predict_outcome_vec(ctx.h, S, *g._params(), L, _p(doTs), float(g.hyperparams.predictionCovarianceNoise),
+                                               int(spp), int(seed), _p(zz), _p(ms), _p(vs), _p(mi), _p(dr))
+    elif slope or outcome:
         G = 0 if Wm is None else Wm.shape[0]
         if Wm is not None:
             ms = np.empty((S, L, G), order="F")
             vs = np.empty((S, L, G), order="F")
-        st = ctx.lib.gpslc_predict_slope(ctx.h, S, *g._params(), L, _p(doTs), G, _p(Wm),
-                                         float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
-                                         _p(ms), _p(vs), None, _p(mi), _p(dr))
+        fn = ctx.lib.gpslc_predict_outcome if outcome else ctx.lib.gpslc_predict_slope
+        st = fn(ctx.h, S, *g._params(), L, _p(doTs), G, _p(Wm),
+                float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
+                _p(ms), _p(vs), None, _p(mi), _p(dr))
         if wvec:
             ms, vs = ms[:, :, 0], vs[:, :, 0]
     elif Wm is not None:
@@ -591,12 +632,13 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
 
 
 def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_ite=False, spp=0, z=None, seed=0,
-                   want_draws=False, want_cov=True, devices=None, slope=False):
+                   want_draws=False, want_cov=True, devices=None, slope=False, outcome=False):
     """gpslc_predict_curve: (meanW (S, L, G), varW (S, L, G), covW (S, L, L, G) or None, MeanITE or None, draws or None) and
     whether ``weights`` was a single vector.  ``weights=None`` is 1/n for everybody.  ``slope=True``: gpslc_predict_slope's
-    weighted form."""
+    weighted form; ``outcome=True``: gpslc_predict_outcome's."""
     n, S = g.getN(), g.getNumPosteriorSamples()
     doTs = np.asarray(doTs, dtype=np.float64)
+    _outcome_refusals(outcome, baseline, slope, False, None, devices)
     _slope_refusals(slope, baseline, doTs.ndim > 1, devices)
     if doTs.ndim > 1:
         raise ValueError("an effect curve needs scalar levels: per-individual intervention vectors are not supported")
@@ -617,10 +659,11 @@ def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_
         zz = _f(z)
         if zz.shape != (n, spp, S, L):
             raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
-    if slope:
-        st = ctx.lib.gpslc_predict_slope(ctx.h, S, *g._params(), L, _p(doTs), G, _p(Wm),
-                                         float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
-                                         _p(mw), _p(vw), _p(cw), _p(mi), _p(dr))
+    if slope or outcome:
+        fn = ctx.lib.gpslc_predict_outcome if outcome else ctx.lib.gpslc_predict_slope
+        st = fn(ctx.h, S, *g._params(), L, _p(doTs), G, _p(Wm),
+                float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
+                _p(mw), _p(vw), _p(cw), _p(mi), _p(dr))
     else:
         st = ctx.lib.gpslc_predict_curve(ctx.h, S, *g._params(), L, _p(doTs), _p(base), G, _p(Wm),
                                          float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
@@ -629,15 +672,18 @@ def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_
     return (mw, vw, cw, mi, dr), wvec
 
 
-def effectCurve(g: GPSLCObject, doTs, baseline=None, weights=None, devices=None, slope=False):
+def effectCurve(g: GPSLCObject, doTs, baseline=None, weights=None, devices=None, slope=False, outcome=False):
     """The weighted effect over a sweep of L scalar levels as ONE Gaussian: mean (S, L[, G]) and the joint covariance
     cov (S, L, L[, G]) of tau_l = w' ITE_l across the levels, per posterior sample (gpslc_predict_curve).  The diagonal of
     ``cov`` is the ``var`` of ``predict`` to the bits; the off-diagonal blocks are what simultaneous bands, comparisons of
     two levels and functionals of the curve (slope, maximum, area) need.  ``weights=None`` means 1/n, the SATE curve; a
     length-n vector or a (G, n) array as in ``predict`` (a (G, n) array adds the trailing group axis); ``baseline`` as in
     ``predict``.  ``slope=True``: the curve of average marginal effects, tau_l = w' (d f / dt at doTs[l]) — the derivative of the
-    dose-response curve with its joint covariance (``weights=None`` is 1/n here too).  Scalar levels and one GPU only."""
-    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices, slope=slope)
+    dose-response curve with its joint covariance (``weights=None`` is 1/n here too).  ``outcome=True``: the average dose-response curve itself,
+    tau_l = w' f(doTs[l]), with its joint covariance across the levels — the curve of levels, where the default is the curve of
+    effects.  Scalar levels and one GPU only."""
+    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices, slope=slope,
+                                             outcome=outcome)
     if wvec:
         return mw[:, :, 0], cw[:, :, :, 0]
     return mw, cw
@@ -666,12 +712,14 @@ def curveSamples(mean, cov, samplesPerPosterior, z=None, seed=0):
 
 
 def sampleEffectCurve(g: GPSLCObject, doTs, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None, devices=None,
-                      slope=False):
+                      slope=False, outcome=False):
     """Joint draws of the effect curve over the L levels: (L, S*spp), column order sample-outer / draw-inner as sampleSATE, or
     (G, L, S*spp) for a (G, n) weight array.  Unlike sampleSATE per level, the L values of a column are ONE draw of the curve
     (they share the Gaussian process).  ``z``: (L, spp, S[, G]) standard normals, else the Philox stream ``seed``.
-    ``slope=True``: draws of the curve of average marginal effects (see effectCurve)."""
-    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices, slope=slope)
+    ``slope=True``: draws of the curve of average marginal effects; ``outcome=True``: draws of the dose-response curve (see
+    effectCurve)."""
+    (mw, _, cw, _, _), wvec = _predict_curve(g, doTs, baseline=baseline, weights=weights, devices=devices, slope=slope,
+                                             outcome=outcome)
     S, L, G = mw.shape
     spp = int(samplesPerPosterior)
     if z is not None:
@@ -683,11 +731,12 @@ def sampleEffectCurve(g: GPSLCObject, doTs, samplesPerPosterior=10, z=None, seed
     return np.ascontiguousarray(out[0]) if wvec else np.ascontiguousarray(out)
 
 
-def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, baseline=None, slope=False):
+def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, baseline=None, slope=False, outcome=False):
     """ITEsamples: n x (S*spp) draws, column order sample-outer / draw-inner (src/estimation.jl:95-109).
     Called as ITEsamples(g, doT, spp): the factor of CovITE + jitter is computed once per sample on the GPU.
     ``baseline`` = a scalar b: draws of the contrast doT against b (see predict).  ``slope=True``: draws of the per-individual
-    marginal effect at the scalar doT (see predict)."""
+    marginal effect at the scalar doT (see predict).  ``outcome=True``: draws of the per-individual potential outcome at the
+    scalar or per-individual doT (see predict)."""
     g, doT = g_or_means, doT_or_covs
     zz = None
     if z is not None:   # z given in the reference's (n, S*spp) column order
@@ -695,7 +744,7 @@ def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, base
         # column j*spp + d  ->  [i, d, j] under a column-major reshape
         zz = np.asarray(z, dtype=np.float64).reshape(n, nSamplesPerMixture, S, order="F")[:, :, :, None]
     _, _, _, dr = predict(g, _levels(g, doT), spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True, baseline=baseline,
-                          slope=slope)
+                          slope=slope, outcome=outcome)
     return np.asfortranarray(dr[0])
 
 
@@ -703,18 +752,21 @@ def ITEsamples(g_or_means, doT_or_covs, nSamplesPerMixture, z=None, seed=0, base
 # src/driver.jl, src/prediction.jl
 # ------------------------------------------------------------------------------------------
 
-def sampleITE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None, slope=False):
+def sampleITE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None, slope=False, outcome=False):
     """sampleITE(g, doT; samplesPerPosterior=10) -> n x (S*spp) (src/driver.jl:86-89); ``baseline``: the contrast doT
-    against that scalar level; ``slope=True``: the marginal effect at the scalar doT."""
-    return ITEsamples(g, doT, samplesPerPosterior, z=z, seed=seed, baseline=baseline, slope=slope)
+    against that scalar level; ``slope=True``: the marginal effect at the scalar doT; ``outcome=True``: the potential outcome
+    at doT itself."""
+    return ITEsamples(g, doT, samplesPerPosterior, z=z, seed=seed, baseline=baseline, slope=slope, outcome=outcome)
 
 
-def sampleSATE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None, slope=False):
+def sampleSATE(g: GPSLCObject, doT, samplesPerPosterior=10, z=None, seed=0, baseline=None, weights=None, slope=False,
+               outcome=False):
     """sampleSATE(g, doT; samplesPerPosterior=10) -> (S*spp,) (src/driver.jl:108-111); ``baseline``: the contrast doT
     against that scalar level.  ``weights`` = a length-n vector: samples of the weighted effect, (S*spp,); a (G, n) array:
     (G, S*spp), row g from SATEsamples of group g's means and variances with ``z[g]`` (``z``: (G, S*spp), or (S*spp,) shared
-    by every group) or the Philox seed ``seed + g``.  ``slope=True``: samples of the average marginal effect at the scalar doT."""
-    m, v = SATEDistributions(g, doT, baseline=baseline, weights=weights, slope=slope)
+    by every group) or the Philox seed ``seed + g``.  ``slope=True``: samples of the average marginal effect at the scalar doT.
+    ``outcome=True``: samples of the average potential outcome (the policy value for a per-individual doT)."""
+    m, v = SATEDistributions(g, doT, baseline=baseline, weights=weights, slope=slope, outcome=outcome)
     if m.ndim == 1:
         return SATEsamples(m, v, samplesPerPosterior, z=z, seed=seed)
     zz = None if z is None else np.broadcast_to(np.asarray(z, dtype=np.float64), (m.shape[1], m.shape[0] * samplesPerPosterior))
@@ -735,10 +787,12 @@ def doTRange(minDoT, maxDoT, fidelity):
 
 
 def predictCounterfactualEffects(g: GPSLCObject, nSamplesPerMixture, fidelity=100, minDoT=None, maxDoT=None,
-                                 z=None, seed=0, devices: Optional[Sequence[int]] = None):
+                                 z=None, seed=0, devices: Optional[Sequence[int]] = None, outcome=False):
     """predictCounterfactualEffects(g, spp; fidelity, minDoT, maxDoT) -> (ite [L, n, S*spp], doTrange)
     (src/prediction.jl:23-36).  All levels share one factorisation of A per posterior sample; ``devices`` shards the
-    posterior samples over several GPUs (``gpslc_predict_multi``)."""
+    posterior samples over several GPUs (``gpslc_predict_multi``).  ``outcome=True``: draws of every individual's outcome
+    surface f_i(a) over the sweep instead of the effects f_i(a) - f_i(T_i) (one GPU only)."""
+    _outcome_refusals(outcome, None, False, False, None, devices)
     lo = float(np.min(g.T)) if minDoT is None else float(minDoT)
     hi = float(np.max(g.T)) if maxDoT is None else float(maxDoT)
     rng = doTRange(lo, hi, fidelity)
@@ -748,7 +802,7 @@ def predictCounterfactualEffects(g: GPSLCObject, nSamplesPerMixture, fidelity=10
         L = rng.shape[0]
         zz = np.asarray(z, dtype=np.float64).reshape(L, n, nSamplesPerMixture, S, order="F")
         zz = np.transpose(zz, (1, 2, 3, 0))
-    _, _, _, dr = predict(g, rng, spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True, devices=devices)
+    _, _, _, dr = predict(g, rng, spp=nSamplesPerMixture, z=zz, seed=seed, want_draws=True, devices=devices, outcome=outcome)
     return dr, rng
 
 

@@ -626,8 +626,9 @@ struct Levels {
     const double* base = nullptr;    // contrasts (L): level l is doT[l] against base[l] (scalar levels only)
     bool slope = false;              // marginal effects: level l is d f_i(t) / dt at t = doT[l] (scalar levels only)
     // the level form the kernels take (FORM_*): what multiplies B_ij outside the pair loops
-    int form() const { return slope ? FORM_SLOPE : base ? FORM_CONTRAST : FORM_ORDINARY; }
-    bool needs_kw() const { return form() == FORM_ORDINARY; }     // contrasts and slopes have no K W term
+    bool outcome = false;            // potential outcomes: level l is f_i(doT[l]) itself (scalar or vector levels)
+    int form() const { return outcome ? FORM_OUTCOME : slope ? FORM_SLOPE : base ? FORM_CONTRAST : FORM_ORDINARY; }
+    bool needs_kw() const { return form() == FORM_ORDINARY; }     // contrasts, slopes and outcomes have no K W term
     // weighted effects: G weight columns — the caller's W[i + n*g] on the host, column fastest (W[g + G*j]) on the
     // device; meanSATE / varSATE are then S x L x G — element (s, l, g) at s + S*(l + L*g) — of tau_w = w_g' ITE_l, the weights
     // used as given (scalar levels only)
@@ -745,7 +746,7 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     if (sh.with_sums && !io.lv.W) b.part = take(2 * nt * sh.Np);
     b.bsum = take(sh.Np); b.ksum = take(sh.Np);
     b.sumdelta = take(std::max(sh.R, 1));
-    if (io.lv.W) {      // the contrast and slope forms need no K W
+    if (io.lv.W) {      // the contrast, slope and outcome forms need no K W
         b.bw = take((size_t)io.lv.G * sh.Np);
         b.kw = io.lv.needs_kw() ? take((size_t)io.lv.G * sh.Np) : b.bw;
         b.wnorm2 = take(io.lv.G);
@@ -782,6 +783,7 @@ VecArgs vec_args(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     va.L = sh.L; va.doT = io.lv.doT;
     va.M = ch.M; va.part = ch.vpart; va.sumdelta = ch.sumdelta;
     va.Y = io.Y; va.y_sstride = io.y_sstride;
+    va.form = io.lv.form();
     return va;
 }
 
@@ -1005,6 +1007,9 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     if (io.lv.slope && io.lv.vec) throw std::runtime_error("slopes cannot be combined with vector levels");
     if (io.lv.slope && io.lv.base) throw std::runtime_error("slopes cannot be combined with a contrast baseline");
     if (io.lv.slope && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("slopes need an fp64 context");
+    if (io.lv.outcome && io.lv.base) throw std::runtime_error("outcomes cannot be combined with a contrast baseline");
+    if (io.lv.outcome && io.lv.slope) throw std::runtime_error("outcomes cannot be combined with slopes");
+    if (io.lv.outcome && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("outcomes need an fp64 context");
     if (io.lv.W && io.lv.vec) throw std::runtime_error("weights cannot be combined with vector levels");
     if (io.lv.W && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("weighted effects need an fp64 context");
     if (io.lv.W && io.lv.G < 1) throw std::runtime_error("weights without a weight column");
@@ -1568,6 +1573,8 @@ static const ArgPos kPredictArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, false}, kPredic
     kIteVecArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true}, kIteContrastArgs{2, 3, 5, 6, 0, 9, 10, 0, 0, 0, true},
     kLikelihoodVecArgs{2, 3, 5, 6, 0, 8, 0, 0, 0, 0, false},
     kPredictSlopeArgs{2, 3, 5, 6, 9, 10, 0, 11, 12, 14, true, 19}, kIteSlopeArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true};
+// the outcome entry points share their twins' positions: gpslc_predict_outcome kPredictSlopeArgs, gpslc_predict_outcome_vec
+// kPredictVecArgs, gpslc_ite_distributions_outcome kIteSlopeArgs, gpslc_ite_distributions_outcome_vec kIteVecArgs
 
 // `count` host values: all there and all finite
 static int finite_check(gpslc_ctx* c, const double* v, int64_t count, int argk, const char* name) {
@@ -1579,8 +1586,8 @@ static int finite_check(gpslc_ctx* c, const double* v, int64_t count, int argk, 
 }
 
 // The argument checks of every prediction and ITE-distribution entry point, in the order of the arguments.  Levels given as
-// host values beyond the plain L scalars (vector levels: n x L; pairs with a baseline; slopes; weight columns: n x G) must be
-// finite.  The slope entry takes its weights or none (G == 0 and NULL: the plain 1/n average).
+// host values beyond the plain L scalars (vector levels: n x L; pairs with a baseline; slopes; outcomes; weight columns: n x G) must
+// be finite.  The slope and outcome entries take their weights or none (G == 0 and NULL: the plain 1/n average).
 static int validate(gpslc_ctx* c, const PredictRequest& rq, const ArgPos& k) {
     const Posterior& po = rq.post;
     const Levels& lv = rq.lv;
@@ -1601,7 +1608,7 @@ static int validate(gpslc_ctx* c, const PredictRequest& rq, const ArgPos& k) {
         if (c->ens_S > 0 && c->ens_off + po.S > c->ens_S)
             return bad_arg(c, k.S, "S exceeds the room gpslc_set_ensemble left: sample_offset + S > S_total");
     }
-    if (lv.vec || k.base || lv.slope) {
+    if (lv.vec || k.base || lv.slope || lv.outcome) {
         if ((rc = finite_check(c, lv.doT, lv.vec ? c->n * (int64_t)lv.L : lv.L, k.doT, "doT"))) return rc;
         // the baselines are optional beside weights
         if (k.base && (lv.base || !k.W) && (rc = finite_check(c, lv.base, lv.L, k.base, "doT_base"))) return rc;
@@ -1617,7 +1624,7 @@ static int validate(gpslc_ctx* c, const PredictRequest& rq, const ArgPos& k) {
     if (no_spp && (k.base || k.W)) return bad_arg(c, k.spp, "spp < 1 with ite_draws requested");
     if (k.covW && rq.out.covW && !lv.W) return bad_arg(c, k.covW, "covW needs weights");
     if (k.fp64_only && (c->flags & GPSLC_FLAG_FP32_KERNEL)) {
-        set_err(c, "vector levels, contrasts, slopes and weighted effects are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
+        set_err(c, "vector levels, contrasts, slopes, outcomes and weighted effects are not supported on a GPSLC_FLAG_FP32_KERNEL context (fp64 only)");
         return GPSLC_ERR_UNSUPPORTED;
     }
     return 0;
@@ -1784,6 +1791,31 @@ int gpslc_predict_slope(gpslc_ctx* c, int64_t S, const double* U, const double* 
     return rc ? rc : predict_host(c, rq);
 }
 
+// potential outcomes: level l is f_i(doT[l]) itself, everybody set to the finite scalar doT[l].  Arguments, weights
+// (or none) and checks are gpslc_predict_slope's
+int gpslc_predict_outcome(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                          const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
+                          int32_t G, const double* weights, double pred_noise, int32_t spp, uint64_t seed, const double* z,
+                          double* meanW, double* varW, double* covW, double* meanITE, double* ite_draws) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.lv.outcome = true; rq.lv.G = G; rq.lv.W = weights;
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws, covW};
+    int rc = validate(c, rq, kPredictSlopeArgs);
+    return rc ? rc : predict_host(c, rq);
+}
+
+// the outcome at vector levels: individual i set to doT[i + n*l]; arguments and checks are gpslc_predict_vec's
+int gpslc_predict_outcome_vec(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                              const double* tyLS, const double* yScale, const double* yNoise, int32_t L, const double* doT,
+                              double pred_noise, int32_t spp, uint64_t seed, const double* z, double* meanSATE,
+                              double* varSATE, double* meanITE, double* ite_draws) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    rq.lv.vec = true; rq.lv.outcome = true;
+    rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanSATE, varSATE, meanITE, ite_draws};
+    int rc = validate(c, rq, kPredictVecArgs);
+    return rc ? rc : predict_host(c, rq);
+}
+
 int gpslc_shard_range(int64_t S, int32_t nblocks, int32_t k, int64_t* s0, int64_t* s1) {
     if (S < 0) return -1;
     if (nblocks < 1) return -2;
@@ -1877,7 +1909,8 @@ int gpslc_predict_multi(int32_t nctx, gpslc_ctx* const* ctxs, int64_t S, const d
     }
 }
 
-// gpslc_ite_distributions*'s body: one level (host) — a scalar, n values (vec), the contrast of two scalars (base) or a slope
+// gpslc_ite_distributions*'s body: one level (host) — a scalar, n values (vec), the contrast of two scalars (base), a slope or
+// an outcome (scalar or vec)
 static int ite_distributions_host(gpslc_ctx* c, const PredictRequest& rq) {
     const int64_t S = rq.post.S;
     if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
@@ -1933,6 +1966,26 @@ int gpslc_ite_distributions_slope(gpslc_ctx* c, int64_t S, const double* U, cons
     rq.lv.slope = true;
     rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
     int rc = validate(c, rq, kIteSlopeArgs);
+    return rc ? rc : ite_distributions_host(c, rq);
+}
+
+int gpslc_ite_distributions_outcome(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                                    const double* tyLS, const double* yScale, const double* yNoise, double doT,
+                                    double pred_noise, double* MeanITEs, double* CovITEs) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, &doT);
+    rq.lv.outcome = true;
+    rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
+    int rc = validate(c, rq, kIteSlopeArgs);
+    return rc ? rc : ite_distributions_host(c, rq);
+}
+
+int gpslc_ite_distributions_outcome_vec(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                                        const double* tyLS, const double* yScale, const double* yNoise, const double* doT,
+                                        double pred_noise, double* MeanITEs, double* CovITEs) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, doT);
+    rq.lv.vec = true; rq.lv.outcome = true;
+    rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
+    int rc = validate(c, rq, kIteVecArgs);
     return rc ? rc : ite_distributions_host(c, rq);
 }
 

@@ -219,11 +219,13 @@ void launch_trsm_robust(const TRef& X, const TRef& L, int k, int i0, int count, 
 // info[g] (if still 0) <- the first nonzero of pair_info[g*lc .. g*lc + lc - 1], g < gs (k_robust.hip)
 void launch_fold_pair_info(const int* pair_info, int* info, int gs, int lc, hipStream_t st);
 
-// The level form of a prediction call (DESIGN.md §12, §15): what multiplies B_ij outside the pair loops.
+// The level form of a prediction call (DESIGN.md §12, §15, §16): what multiplies B_ij outside the pair loops.
 //   FORM_ORDINARY  f_i(doT_l) - f_i(T_i)
 //   FORM_CONTRAST  f_i(a_l) - f_i(b_l) for the pair (a, b) = (doT[l], doT_base[l])
 //   FORM_SLOPE     d f_i(t) / dt at t = doT[l]: cross term q^a_j = 2 (T_j - a) r^a_j / tyLS^2, prior term 2 / tyLS^2
-enum { FORM_ORDINARY = 0, FORM_CONTRAST = 1, FORM_SLOPE = 2 };
+//   FORM_OUTCOME   f_i(doT_l), the potential outcome itself: the ordinary level without its factual term — cross term r^a_j,
+//                  prior term 1 (vector levels d: cross term g_ji = rho(T_j, d_i), prior term h_ij = rho(d_i, d_j))
+enum { FORM_ORDINARY = 0, FORM_CONTRAST = 1, FORM_SLOPE = 2, FORM_OUTCOME = 3 };
 
 // q^a_j of the slope form, wt = 1 / tyLS^2: the difference T_j - a is formed in fp64 by the caller's arguments
 __host__ __device__ inline double gp_slope_q(double dt, double r, double wt) { return (2.0 * dt) * wt * r; }
@@ -245,6 +247,7 @@ struct RhsArgs {
     const double* W; int G;   // device, column g fastest: W[g + G*j]
     const double* bw; const double* kw; double* wnorm2;
     int form;   // FORM_*.  Slope: c_l = q^a .* bw_g and sum(Delta_l) = (2 / tyLS^2) sum B (weighted: (2 / tyLS^2) w . bw), no kw
+                // Outcome: c_l = r^a .* bw_g and sum(Delta_l) = sum B (weighted: w . bw), no kw
 };
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
 
@@ -252,7 +255,7 @@ void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
 struct WsumArgs : SampleGrid {
     int G;
     const double* W;       // device, column g fastest: W[g + G*j]
-    double* bw; double* kw;   // [b][G][Np]; kw is not written when with_k == 0 (contrasts and slopes need BW only)
+    double* bw; double* kw;   // [b][G][Np]; kw is not written when with_k == 0 (contrasts, slopes and outcomes need BW only)
     int with_k;
     int binary_t;          // as GramArgs::binary_t: the e_ij of the K that is factorised
 };
@@ -277,11 +280,12 @@ struct CurveArgs {
     const double* T; const double* tyLS; const double* doT;
     const double* doT_base;   // form == FORM_CONTRAST (level l is the pair (doT[l], doT_base[l]))
     const double* W;          // device, column g fastest: W[g + G*j]
-    const double* bw; const double* kw;   // [b][G][Np] (launch_wsum); kw is not read for contrasts and slopes
+    const double* bw; const double* kw;   // [b][G][Np] (launch_wsum); kw is not read for contrasts, slopes and outcomes
     double* prior;            // [b][G][L + 2]: beta = w . bw, kappa = w . kw, gamma_l = sum_j w_j r^l_j bw_j
     const double* varW;       // S x L x G, as the epilogue stored it: the diagonal
     double* covW;             // S x L x L x G: element (s, l, l', g) at s + S*(l + L*(l' + L*g))
     int form;                 // FORM_*.  Slope: P_ll' = (2 wt - 4 (a_l - a_l')^2 wt^2) rho(a_l, a_l') beta, wt = 1 / tyLS^2; no kw
+                              // Outcome: P_ll' = rho(a_l, a_l') beta; no kw
 };
 void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st);
 
@@ -304,6 +308,7 @@ struct IteMeanArgs : SampleGrid {
     const double* doT_base;   // form == FORM_CONTRAST (fp64 only): MeanITE_i(l) = sum_j B_ij (r^a_j - r^b_j) alpha_j for the pair
                               // (a, b) = (doT[l], doT_base[l])
     int form;                 // FORM_*.  Slope (fp64 only): MeanITE_i(l) = sum_j B_ij q^a_j alpha_j
+                              // Outcome (fp64 only): MeanITE_i(l) = sum_j B_ij r^a_j alpha_j, no K alpha term
 };
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st);
 
@@ -316,6 +321,8 @@ struct VecArgs : SampleGrid {
     // launch_vec_mean: alpha [b][Np] solves (K + yNoise I) alpha = Y; element (i, s, l) at meanITE[i*si + s*ss + l*sl]
     const double* alpha; const double* Y; long long y_sstride;
     double* meanITE; long long si, ss, sl;
+    int form;              // FORM_ORDINARY or FORM_OUTCOME: c_j = sum_i B_ij g_ji, 1' Delta 1 = sum_ij B_ij h_ij and
+                           // MeanITE_i = sum_j B_ij g_ji alpha_j, no e_ij, no K alpha term, no exact-zero rule
 };
 void launch_vec_sums(const VecArgs& a, int nbatch, hipStream_t st);
 void launch_vec_mean(const VecArgs& a, int nbatch, hipStream_t st);
@@ -336,6 +343,7 @@ struct DtArgs : SampleGrid {
     const double* doT_base;   // form == FORM_CONTRAST (scalar levels only): D_ij = B_ij (r^a_j - r^b_j) and
                               // Delta_ij = B_ij ((1 - rho) + (1 - rho)) for the pair (doT[l], doT_base[l])
     int form;                 // FORM_*.  Slope (scalar levels only): D_ij = B_ij q^a_j and Delta_ij = B_ij 2 / tyLS^2
+                              // Outcome: D_ij = B_ij r^a_j and Delta_ij = B_ij; with vec D_ij = B_ij g_ji and Delta_ij = B_ij h_ij
 };
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st);
 

@@ -9,6 +9,7 @@
 //     ordinary, f(d_l) - f(T):    P_ll' = rho(d_l, d_l') beta - gamma_l - gamma_l' + kappa
 //     contrast, f(a_l) - f(b_l):  P_ll' = [(rho(a_l, a_l') - rho(a_l, b_l')) - (rho(b_l, a_l') - rho(b_l, b_l'))] beta
 //     slope, f'(a_l) (§15):       P_ll' = (2 wt - 4 (a_l - a_l')^2 wt^2) rho(a_l, a_l') beta,  wt = 1 / tyLS^2
+//     outcome, f(a_l) (§16):      P_ll' = rho(a_l, a_l') beta
 //
 //   curve_prior_kernel   beta, kappa, gamma_l per (sample, weight column): fixed trees over the threads' strided j
 //   curve_gram_kernel    one workgroup per (16 x 16 block of right-hand-side pairs, sample): v_q . v_q' with
@@ -18,7 +19,7 @@
 #include "gp_math.h"
 
 // grid (G, batch).  prior[b][g][0] = beta, [1] = kappa, [2 + l] = gamma_l; the contrast form needs beta alone (kw is not
-// computed for it and is not read), and so does the slope form: CON is "contrast or slope" in this kernel
+// computed for it and is not read), and so do the slope and outcome forms: CON is "not the ordinary form" in this kernel
 template <bool CON>
 __global__ __launch_bounds__(256) void curve_prior_kernel(CurveArgs a) {
     __shared__ double red[4];
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256) void curve_prior_kernel(CurveArgs a) {
 // Accumulator v of a lane is the pair (qa = 16 A + (lane >> 4) + 4 v, qb = 16 Bk + (lane & 15)) (diag_block.h: mma).
 template <int FORM>
 __global__ __launch_bounds__(256) void curve_gram_kernel(CurveArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
     __shared__ double part[4][4][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y;
@@ -117,6 +118,8 @@ __global__ __launch_bounds__(256) void curve_gram_kernel(CurveArgs a) {
     } else if (SLP) {
         const double d = a.doT[l] - a.doT[lp];
         P = ((2.0 * wt - 4.0 * (d * d) * (wt * wt)) * gp_rho(a.doT[l], a.doT[lp], wt)) * pr[0];
+    } else if (OUT) {
+        P = gp_rho(a.doT[l], a.doT[lp], wt) * pr[0];
     } else {
         P = ((gp_rho(a.doT[l], a.doT[lp], wt) * pr[0] - pr[2 + l]) - pr[2 + lp]) + pr[1];
     }
@@ -132,7 +135,8 @@ static void launch_curve_t(const CurveArgs& a, int nbatch, hipStream_t st) {
     hipLaunchKernelGGL(curve_gram_kernel<FORM>, dim3(nblk * (nblk + 1) / 2, nbatch), dim3(256), 0, st, a);
 }
 void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st) {
-    if (a.form == FORM_SLOPE) launch_curve_t<FORM_SLOPE>(a, nbatch, st);
+    if (a.form == FORM_OUTCOME) launch_curve_t<FORM_OUTCOME>(a, nbatch, st);
+    else if (a.form == FORM_SLOPE) launch_curve_t<FORM_SLOPE>(a, nbatch, st);
     else if (a.form == FORM_CONTRAST) launch_curve_t<FORM_CONTRAST>(a, nbatch, st);
     else launch_curve_t<FORM_ORDINARY>(a, nbatch, st);
 }

@@ -5,8 +5,8 @@
 //                      fused with the per-tile partial column sums of B = yScale*exp(Lu+Lx) and
 //                      K = B.*E that the SATE path needs.
 //   rhs_prepare/tiles  column sums -> augmented right-hand sides [Y, c(1..L)] and sum(Delta).  CON: the contrast form of
-//                      both (level l = the pair (doT[l], doT_base[l])).  SLP: the slope form (§15).
-//                      FORM is RhsArgs::form; CON / SLP name its two special values inside the kernels.
+//                      both (level l = the pair (doT[l], doT_base[l])).  SLP: the slope form (§15).  OUT: the outcome form (§16).
+//                      FORM is RhsArgs::form; CON / SLP / OUT name its special values inside the kernels.
 //   rhs_w_prepare      the level sums of weighted effects: G weight columns x L levels from bw = B w, kw = K w (k_wsum.hip,
 //                      DESIGN.md §13); rhs_tiles writes their rows.
 //   epilogue           Schur complement of the augmented block -> MeanSATE, VarSATE (plain or weighted), logdet, quad.
@@ -242,10 +242,11 @@ void launch_gram(const GramArgs& g, int nbatch, hipStream_t st) {
 // B ((1 - rho) + (1 - rho)) with rho = exp(-(a - b)^2 / tyLS^2), so sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B: no sum
 // over the columns, and exactly 0.0 when a == b.
 // SLP (slope at a = doT[l]): the prior block is B 2 / tyLS^2 for every level, so sum(Delta_l) = (2 / tyLS^2) sum B.
+// OUT (outcome at a = doT[l]): the prior block is B itself, so sum(Delta_l) = sum B.
 // ---------------------------------------------------------------------------------------
 template <int FORM>
 __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -280,6 +281,10 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
         for (int l = tid; l < a.L; l += 256) a.sumdelta[(long long)b * a.L + l] = (2.0 * wt) * btot;
         return;
     }
+    if (OUT) {
+        for (int l = tid; l < a.L; l += 256) a.sumdelta[(long long)b * a.L + l] = btot;
+        return;
+    }
     for (int l = 0; l < a.L; ++l) {
         const double dot = a.doT[l];
         double acc = 0.0;
@@ -297,11 +302,13 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
 // (q = 0: Y, q = 1 + l + L*g: c_l = r_l .* bw_g - kw_g of column g), zero elsewhere; zero the aug x aug tiles.
 // CON: c_l = (r^a - r^b) .* bw_g for the pair (a, b) = (doT[l], doT_base[l]) — the e_ij of the ordinary level cancels, and
 // a == b gives r^a == r^b bit for bit: an exact zero row.  SLP: c_l = q^a .* bw_g, q^a_j = 2 (T_j - a) r^a_j / tyLS^2, no e_ij either.
+// OUT: c_l = r^a .* bw_g, the ordinary row without its - kw_g.
 // grid (nt + naug, naug, batch): tile (nt + a, j) with j = blockIdx.x, a = blockIdx.y (j <= nt + a).
 template <int FORM>
 __device__ __forceinline__ double rhs_level_value(const RhsArgs& a, int l, int gj, double wt, const double* bs, const double* ks) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
     const double r = gp_rho(a.T[gj], a.doT[l], wt);
+    if (OUT) return r * bs[gj];
     if (SLP) return gp_slope_q(a.T[gj] - a.doT[l], r, wt) * bs[gj];
     if (CON) return (r - gp_rho(a.T[gj], a.doT_base[l], wt)) * bs[gj];
     return r * bs[gj] - ks[gj];
@@ -352,13 +359,14 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
 //   c = D' w,  c_j = r_j bw_j - kw_j            w' Delta w = sum_j w_j ((kw_j - 2 r_j bw_j) + bw_j)
 //   CON: c_j = (r^a_j - r^b_j) bw_j             w' Delta w = ((1 - rho) + (1 - rho)) sum_j w_j bw_j
 //   SLP: c_j = q^a_j bw_j                       w' Delta w = (2 / tyLS^2) sum_j w_j bw_j
+//   OUT: c_j = r^a_j bw_j                       w' Delta w = sum_j w_j bw_j  (= beta of k_curve.hip)
 // rhs_w_prepare: one workgroup per (right-hand side, sample): sumdelta[b][l + L*g], and (l == 0) wnorm2[b][g] = w_g . w_g;
 // the sums run over the threads' strided j in a fixed tree.  r == 1 (every T equal to doT) and kw == bw give an exact 0.0
 // term by term; a == b gives rho == 1 and 0.0 * sum.
 // ---------------------------------------------------------------------------------------
 template <int FORM>
 __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int qq = blockIdx.x, b = blockIdx.y;
@@ -374,7 +382,7 @@ __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
     for (int j = tid; j < a.n; j += 256) {
         const double w = a.W[(long long)j * a.G + g];
         ww = fma(w, w, ww);
-        if (CON || SLP) {
+        if (CON || SLP || OUT) {
             acc += w * bs[j];
         } else {
             const double r = gp_rho(a.T[j], dot, wt);
@@ -405,7 +413,8 @@ static void launch_rhs_t(const RhsArgs& r, int nbatch, hipStream_t st) {
     hipLaunchKernelGGL(rhs_tiles_kernel<FORM>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
 }
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.form == FORM_SLOPE) launch_rhs_t<FORM_SLOPE>(r, nbatch, st);
+    if (r.form == FORM_OUTCOME) launch_rhs_t<FORM_OUTCOME>(r, nbatch, st);
+    else if (r.form == FORM_SLOPE) launch_rhs_t<FORM_SLOPE>(r, nbatch, st);
     else if (r.form == FORM_CONTRAST) launch_rhs_t<FORM_CONTRAST>(r, nbatch, st);
     else launch_rhs_t<FORM_ORDINARY>(r, nbatch, st);
 }

@@ -79,11 +79,13 @@ void launch_backsolve(const BackArgs& a, int nbatch, hipStream_t st) {
 // the same code.
 // SLP (slope at a = doT[l]): D_ij = B_ij q^a_j with q^a_j = 2 (T_j - a) r^a_j / tyLS^2, so
 // MeanITE_i(l) = sum_j B_ij (q^a_j alpha_j): no K alpha term as for CON, and no level gives an exact-zero row.
-// FORM is IteMeanArgs::form; CON / SLP name its two special values inside the kernels.
+// OUT (outcome at a = doT[l]): D_ij = B_ij r^a_j, so MeanITE_i(l) = sum_j B_ij (r^a_j alpha_j): what the ordinary
+// form stages, stored without the K alpha term and without the exact-zero rule.
+// FORM is IteMeanArgs::form; CON / SLP / OUT name its special values inside the kernels.
 // ---------------------------------------------------------------------------------------
 template <int FREG, int LCT, typename RT, int RB, int FORM = FORM_ORDINARY>
 __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
     double* etab = sm;                     // [32] 2^(j/32): table-driven exp (gp_math.h)
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 #pragma unroll
             for (int q = 0; q < RB; ++q) {
                 if (gi[q] >= n) continue;
-                if (CON || SLP) {
+                if (CON || SLP || OUT) {
 #pragma unroll
                     for (int ll = 0; ll < LCT; ++ll)
                         if (ll < nl) {
@@ -213,14 +215,15 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 //   - what is staged: R[j, l] = r_j(l) alpha_j; CON (contrasts as in ite_mean_kernel): (r^a_j - r^b_j) alpha_j;
 //   - the store, per 16-row sub-tile: rows i < n only, (K alpha)_i and T_i loaded once; instances with T_i == doT_l get the
 //     reference's exact 0.0 (row i of Ks' - K is identically zero there).  CON: no K alpha term, 0.0 for a level with a == b.
-//     SLP: q^a_j alpha_j is staged, no K alpha term and no exact-zero case.
+//     SLP: q^a_j alpha_j is staged, no K alpha term and no exact-zero case.  OUT: the ordinary staging, no K alpha term and
+//     no exact-zero case.
 // ---------------------------------------------------------------------------------------
 template <int FREG, int FORM = FORM_ORDINARY>   // FREG > 0: this lane's two rows' features live in registers (F <= FREG); 0: read from LDS
 __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const long long b = blockIdx.y, s = a.s0 + b;
     const double* alpha = a.alpha + b * (a.nt * GP_TS);
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
     pair_mfma_body<FREG, false, 0>(
         a, s, a.L, sm,
         [&](int j, int l, double wt, const double* etab) {
@@ -235,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
         [&](int gi, int l0, int nl, const d4* acc, const d4*) {
             if (gi >= a.n) return;
             double* out = a.meanITE + (long long)gi * a.si + s * a.ss;
-            if (CON || SLP) {
+            if (CON || SLP || OUT) {
                 pair_mfma_each_column(nl, [&](int q, int v, int ll) {
                     out[(long long)(l0 + ll) * a.sl] = (CON && a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : acc[q][v];
                 });
@@ -269,7 +272,7 @@ template <int FREG, typename RT, int FORM>
 static void launch_ite_mean_f(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     if (a.L <= 1) launch_ite_mean_t<FREG, 1, RT, FORM>(a, nbatch, st);
     else if (a.L <= 4) launch_ite_mean_t<FREG, 4, RT, FORM>(a, nbatch, st);
-    else if (FORM == FORM_ORDINARY) launch_ite_mean_t<FREG, 16, RT, FORM_ORDINARY>(a, nbatch, st);     // contrasts, slopes (fp64): L > 4 is the MFMA kernel's
+    else if (FORM == FORM_ORDINARY) launch_ite_mean_t<FREG, 16, RT, FORM_ORDINARY>(a, nbatch, st);     // contrasts, slopes, outcomes (fp64): L > 4 is the MFMA kernel's
 }
 template <typename RT, int FORM = FORM_ORDINARY>
 static void launch_ite_mean_r(const IteMeanArgs& a, int nbatch, hipStream_t st) {
@@ -286,7 +289,7 @@ static void launch_ite_mean_r(const IteMeanArgs& a, int nbatch, hipStream_t st) 
     else if (F <= 20) launch_ite_mean_f<20, RT, FORM>(a, nbatch, st);
     else launch_ite_mean_f<32, RT, FORM>(a, nbatch, st);
 }
-// contrasts and slopes: fp64 contexts only (the entry points refuse the fp32 kernel mode)
+// contrasts, slopes and outcomes: fp64 contexts only (the entry points refuse the fp32 kernel mode)
 template <int FORM>
 static void launch_ite_mean_f64(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     if (a.L > 4) launch_ite_mean_mfma<FORM>(a, nbatch, st);
@@ -295,6 +298,7 @@ static void launch_ite_mean_f64(const IteMeanArgs& a, int nbatch, hipStream_t st
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     if (a.form == FORM_CONTRAST) { launch_ite_mean_f64<FORM_CONTRAST>(a, nbatch, st); return; }
     if (a.form == FORM_SLOPE) { launch_ite_mean_f64<FORM_SLOPE>(a, nbatch, st); return; }
+    if (a.form == FORM_OUTCOME) { launch_ite_mean_f64<FORM_OUTCOME>(a, nbatch, st); return; }
     // many levels: the (B R) product belongs on the matrix cores (fp64 path; the fp32 mode keeps the VALU kernel)
     if (!a.f32 && a.L > 4) { launch_ite_mean_mfma<FORM_ORDINARY>(a, nbatch, st); return; }
     if (a.f32) launch_ite_mean_r<float>(a, nbatch, st);
@@ -310,20 +314,24 @@ void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
 //     e = rho(T_i, T_j)      g_ij = rho(T_i, d_j)      g_ji = rho(T_j, d_i)      h = rho(d_i, d_j)
 // for a per-individual intervention d (LEVEL_VECTOR; rr_ / rc_ hold d of the row / column block), and a scalar level doT is the
 // case g_ij = r_i, g_ji = r_j, h = 1 with r_i = rho(T_i, doT) staged in rr_ / rc_ (LEVEL_SCALAR).  LEVEL_NONE (contrasts) stages
-// the column block's values only, hands them over as g_ji and evaluates neither e nor the other terms.  A kernel supplies
+// the column block's values only, hands them over as g_ji and evaluates neither e nor the other terms.  LEVEL_VECTOR_OUTCOME
+// (the outcome at a vector level) stages d as LEVEL_VECTOR does and evaluates g_ji and h only.  A kernel supplies
 //   stage_level(g, t, wt)   what rr_ / rc_ hold for individual g (any g: the kernel decides what the padding gets) with
 //                           T_g = t (0.0 on the padding), wt = 1 / tyLS^2
 //   emit(rp, cq, inside, diag, Bv, terms)   element (row rp, column cq) of the tile: inside = both individuals < n, diag = on the
 //                           matrix diagonal, padding included; with level terms, Bv and the terms of an element outside
 //                           arrive as 0.0 (g_ji as staged).  Every element depends on its own row and column only.
 // ---------------------------------------------------------------------------------------
-enum { LEVEL_NONE, LEVEL_SCALAR, LEVEL_VECTOR };
+enum { LEVEL_NONE, LEVEL_SCALAR, LEVEL_VECTOR, LEVEL_VECTOR_OUTCOME };
 struct LevelTerms { double e, gij, gji, h; };
 template <bool VEC>
 __device__ __forceinline__ LevelTerms level_terms(double ti, double tj, double xi, double xj, double wt) {
     const double e = gp_rho(ti, tj, wt);
     if (VEC) return {e, gp_rho(ti, xj, wt), gp_rho(tj, xi, wt), gp_rho(xi, xj, wt)};
     return {e, xi, xj, 1.0};
+}
+__device__ __forceinline__ LevelTerms level_terms_outcome(double tj, double xi, double xj, double wt) {
+    return {0.0, 0.0, gp_rho(tj, xi, wt), gp_rho(xi, xj, wt)};
 }
 // LDS (doubles): fr [F][128] | fc [F][128] row / column features / LS | tr [128] | tc [128] T | rr_ [128] | rc_ [128]
 constexpr int tile_build_lds_bytes(int F) { return (2 * F * GP_TS + 4 * GP_TS) * 8; }
@@ -382,7 +390,8 @@ __device__ __forceinline__ void tile_build_body(const SampleGrid& a, long long s
             // interleave and the kernel no longer fits 8 waves per SIMD.  Contrasts (one exp per element) fit without it.
             if (LEVEL == LEVEL_NONE || inside) {
                 Bv = ys * gp_exp_neg(-lux[p]);
-                if constexpr (LEVEL != LEVEL_NONE) t = level_terms<LEVEL == LEVEL_VECTOR>(tr[rp], tcq, rr_[rp], xj, wt);
+                if constexpr (LEVEL == LEVEL_VECTOR_OUTCOME) t = level_terms_outcome(tcq, rr_[rp], xj, wt);
+                else if constexpr (LEVEL != LEVEL_NONE) t = level_terms<LEVEL == LEVEL_VECTOR>(tr[rp], tcq, rr_[rp], xj, wt);
             }
             emit(rp, cq, inside, gi == gj, Bv, t);
         }
@@ -397,18 +406,21 @@ __device__ __forceinline__ void tile_build_body(const SampleGrid& a, long long s
 // CON (contrast of the scalar levels a = doT[l], b = doT_base[l]): D_ij = B_ij (r^a_j - r^b_j) (rc_ holds the
 // difference) and Delta_ij = B_ij ((1 - rho) + (1 - rho)), rho = exp(-(a - b)^2 / tyLS^2) — exactly 0 when a == b.
 // SLP (slope at the scalar level a = doT[l]): D_ij = B_ij q^a_j (rc_ holds q^a) and Delta_ij = B_ij 2 / tyLS^2.
-// FORM is DtArgs::form (FORM_ORDINARY with VEC).
+// OUT (outcome): at the scalar level a = doT[l], D_ij = B_ij r^a_j (rc_ holds r^a) and Delta_ij = B_ij; with VEC
+// D_ij = B_ij g_ji and Delta_ij = B_ij h_ij.
+// FORM is DtArgs::form (FORM_ORDINARY or FORM_OUTCOME with VEC).
 // ---------------------------------------------------------------------------------------
 template <bool VEC, int FORM = FORM_ORDINARY>
 __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE;
+    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
+    constexpr bool NOLV = CON || SLP || (OUT && !VEC);      // the column block's staged values are all an element needs
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int ti = blockIdx.x / a.nt, tj = blockIdx.x % a.nt;
     const long long b = blockIdx.y, s = a.s0 + b / a.lc;       // batch element = (sample, level) pair
     const int l = a.l0 + (int)(b % a.lc), n = a.n;
     const double doT = VEC ? 0.0 : a.doT[l], doTb = CON ? a.doT_base[l] : 0.0;
     const double* dv = VEC ? a.doT + (long long)n * l : nullptr;
-    double kss = 0.0;       // CON: (1 - rho) + (1 - rho); SLP: 2 / tyLS^2
+    double kss = 0.0;       // CON: (1 - rho) + (1 - rho); SLP: 2 / tyLS^2 (OUT: 1, not multiplied)
     if (CON) {
         const double tl = a.p.tyLS[s];
         const double rho = gp_rho(doT, doTb, 1.0 / (tl * tl));
@@ -420,7 +432,7 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
     }
     double* wt_tile = tref_tile(a.W, b, ti, tj);
     double* c_tile = (ti >= tj) ? tref_tile(a.Cm, b, ti, tj) : nullptr;
-    tile_build_body<(CON || SLP) ? LEVEL_NONE : VEC ? LEVEL_VECTOR : LEVEL_SCALAR>(
+    tile_build_body<NOLV ? LEVEL_NONE : (VEC && OUT) ? LEVEL_VECTOR_OUTCOME : VEC ? LEVEL_VECTOR : LEVEL_SCALAR>(
         a, s, ti, tj, sm,
         [&](int g, double t, double wt) {
             if constexpr (VEC) return g < n ? dv[g] : 0.0;
@@ -430,7 +442,10 @@ __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
         },
         [&](int rp, int cq, bool inside, bool diag, double Bv, const LevelTerms& t) {
             double Dv, Cv;
-            if (CON || SLP) {
+            if (OUT) {
+                Dv = Bv * t.gji;
+                Cv = VEC ? Bv * t.h : Bv;
+            } else if (CON || SLP) {
                 Dv = Bv * t.gji;
                 Cv = Bv * kss;
             } else {
@@ -451,7 +466,11 @@ static void launch_dt_build_t(const DtArgs& a, int nbatch, hipStream_t st) {
     hipLaunchKernelGGL((dt_build_kernel<VEC, FORM>), dim3(a.nt * a.nt, nbatch), dim3(256), tile_build_lds_bytes(a.nU + a.nX), st, a);
 }
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st) {
-    if (a.form == FORM_SLOPE) launch_dt_build_t<false, FORM_SLOPE>(a, nbatch, st);
+    if (a.form == FORM_OUTCOME) {
+        if (a.vec) launch_dt_build_t<true, FORM_OUTCOME>(a, nbatch, st);
+        else launch_dt_build_t<false, FORM_OUTCOME>(a, nbatch, st);
+    }
+    else if (a.form == FORM_SLOPE) launch_dt_build_t<false, FORM_SLOPE>(a, nbatch, st);
     else if (a.form == FORM_CONTRAST) launch_dt_build_t<false, FORM_CONTRAST>(a, nbatch, st);
     else if (a.vec) launch_dt_build_t<true>(a, nbatch, st);
     else launch_dt_build_t<false>(a, nbatch, st);

@@ -22,11 +22,20 @@
 // so results are bit-reproducible and do not depend on how the samples are chunked.  fp64 throughout.
 // If d == T everywhere, g == e and h == e bit for bit (the same squares into the same exp), so c, Delta and MeanITE are
 // exact zeros.
+//
+// FORM (VecArgs::form) is FORM_ORDINARY, all of the above, or FORM_OUTCOME (OUT inside the kernel): the potential
+// outcome f_i(d_i) itself, the ordinary form with its factual terms dropped —
+//     D_ij = B_ij g_ji,    Delta_ij = B_ij h_ij
+//   sums   c_j = sum_i B_ij g_ji, and per tile of columns sum_j sum_i B_ij h_ij alone; no e is evaluated (two exps per pair
+//          and level, as before)
+//   mean   MeanITE_i = sum_j B_ij g_ji alpha_j: no K alpha term and no d_i == T_i rule
+// in the same reduction orders.
 #include "gpslc_internal.h"
 #include "gp_math.h"
 
-template <int LB, bool SUMS>
+template <int LB, bool SUMS, int FORM>
 __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
+    constexpr bool OUT = FORM == FORM_OUTCOME;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
     double* etab = sm;                          // [32] 2^(j/32): table-driven exp (gp_math.h)
@@ -83,7 +92,15 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
             }
             const double Bv = ys * gp_exp_neg_tab(-lux, etab);
             const double tr = tk[r];
-            if (SUMS) {
+            if (SUMS && OUT) {
+#pragma unroll
+                for (int ll = 0; ll < LB; ++ll) {
+                    const double dk = xk[ll * GP_TS + r];
+                    const double dg = to - dk, dh = dlo[ll] - dk;
+                    acc[ll] = fma(Bv, gp_exp_neg_tab(-((dg * dg) * wt), etab), acc[ll]);      // g_{own,other}: T_own - d_other
+                    acc2[ll] = fma(Bv, gp_exp_neg_tab(-((dh * dh) * wt), etab), acc2[ll]);
+                }
+            } else if (SUMS) {
                 const double de = to - tr;
                 const double Ev = gp_exp_neg_tab(-((de * de) * wt), etab);
 #pragma unroll
@@ -117,6 +134,13 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
     const int nl = min(LB, a.L - l0);
     if (!SUMS) {
         if (half == 1 || !own_in) return;
+        if (OUT) {
+#pragma unroll
+            for (int ll = 0; ll < LB; ++ll)
+                if (ll < nl)
+                    a.meanITE[(long long)go * a.si + s * a.ss + (long long)(l0 + ll) * a.sl] = acc[ll] + red[ll * GP_TS + o];
+            return;
+        }
         const double ka = a.Y[s * a.y_sstride + go] - a.p.yNoise[s] * alpha[go];      // (K alpha)_o: alpha solves (K + yNoise I) alpha = Y
 #pragma unroll
         for (int ll = 0; ll < LB; ++ll)
@@ -138,7 +162,7 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
             const double hs = acc2[ll] + red[(LB + ll) * GP_TS + o];
             const int q = 1 + l0 + ll;
             if (own_in && ll < nl) tref_tile(a.M, b, a.nt + (q >> 7), ot)[o * GP_TS + (q & 127)] = c;
-            if (own_in) v = hs - 2.0 * c;
+            if (own_in) v = OUT ? hs : hs - 2.0 * c;
         }
 #pragma unroll
         for (int w = 32; w >= 1; w >>= 1) v += __shfl_xor(v, w, 64);
@@ -159,20 +183,25 @@ __global__ __launch_bounds__(256) void vec_sumdelta_kernel(VecArgs a) {
     }
 }
 
-template <int LB, bool SUMS>
+template <int LB, bool SUMS, int FORM>
 static void launch_vec_t(const VecArgs& a, int nbatch, hipStream_t st) {
     const int F = a.nU + a.nX;
     const int bytes = (GP_EXP_TAB_DOUBLES + 2 * F * GP_TS + GP_TS + LB * GP_TS + 2 * LB * GP_TS) * 8;
     static DeviceOnce attr_set;
-    lds_opt_in(attr_set, (const void*)vec_pair_kernel<LB, SUMS>,
+    lds_opt_in(attr_set, (const void*)vec_pair_kernel<LB, SUMS, FORM>,
                (GP_EXP_TAB_DOUBLES + 2 * MAXF * GP_TS + GP_TS + 3 * LB * GP_TS) * 8);
-    hipLaunchKernelGGL((vec_pair_kernel<LB, SUMS>), dim3(a.nt, (a.L + LB - 1) / LB, nbatch), dim3(256), bytes, st, a);
+    hipLaunchKernelGGL((vec_pair_kernel<LB, SUMS, FORM>), dim3(a.nt, (a.L + LB - 1) / LB, nbatch), dim3(256), bytes, st, a);
+}
+template <bool SUMS, int FORM>
+static void launch_vec_f(const VecArgs& a, int nbatch, hipStream_t st) {
+    if (a.L <= 1) launch_vec_t<1, SUMS, FORM>(a, nbatch, st);
+    else if (a.L <= 4) launch_vec_t<4, SUMS, FORM>(a, nbatch, st);
+    else launch_vec_t<8, SUMS, FORM>(a, nbatch, st);
 }
 template <bool SUMS>
 static void launch_vec(const VecArgs& a, int nbatch, hipStream_t st) {
-    if (a.L <= 1) launch_vec_t<1, SUMS>(a, nbatch, st);
-    else if (a.L <= 4) launch_vec_t<4, SUMS>(a, nbatch, st);
-    else launch_vec_t<8, SUMS>(a, nbatch, st);
+    if (a.form == FORM_OUTCOME) launch_vec_f<SUMS, FORM_OUTCOME>(a, nbatch, st);
+    else launch_vec_f<SUMS, FORM_ORDINARY>(a, nbatch, st);
 }
 
 void launch_vec_sums(const VecArgs& a, int nbatch, hipStream_t st) {

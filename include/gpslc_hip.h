@@ -357,6 +357,54 @@ int gpslc_predict_slope(gpslc_ctx* ctx, int64_t S, const double* U, const double
                         const double* z_or_null, double* meanW, double* varW, double* covW, double* meanITE,
                         double* ite_draws);
 
+/* Potential outcomes: level l is individual i's expected outcome at dose a = doT[l], everybody set to that dose,
+ *     mu_i(a) = f_i(a),
+ * the response surface itself and not a difference of it.  Its average over the population is the average dose-response
+ * function mu(a) — E[Y(1)] and E[Y(0)] for a binary treatment.  It is the reference's own counterfactual block
+ * (src/likelihood.jl:27-49: CovWWs, CovWsWs, CovC22), which conditionalITE only uses inside a difference.  With
+ * B = yScale exp(Lu + Lx), wt = 1 / tyLS^2, r^a_j = exp(-(T_j - a)^2 wt), rho(x, y) = exp(-(x - y)^2 wt), alpha = (K + yNoise I)^-1 Y:
+ *     D_ij = Cov(f_i(a), Y_j) = B_ij r^a_j;    MeanITE = D alpha   (gpslc_predict's MeanITE without its - (Y_i - yNoise alpha_i),
+ *                                                                  and without its exact 0.0 where T_i == a);
+ *     CovITE = B - D (K + yNoise I)^-1 D' (= CovC22),  + pred_noise*I after symmetrisation (src/estimation.jl:82).
+ * The prior mean is zero as in the reference's model (MvNormal(0, cov)): far from the data mu_i(a) returns to 0, not to the sample
+ * mean of Y.  This is the latent surface: the predictive distribution of a new observation adds yNoise_s to the diagonal, which
+ * is left to the caller.  An outcome level costs what a scalar level costs: only what multiplies B_ij outside the pair loops
+ * differs.  doT: L finite host scalars (else -10).
+ *   weights_or_null == NULL and G == 0 (the plain form): meanW, varW are S x L with gpslc_predict's meanSATE / varSATE semantics,
+ *       the 1/n average: mean = w . z / n, var = (sum(B) - w . w + n pred_noise) / n^2 with w = L^-1 (r^a .* bsum); covW must be NULL
+ *       (else -19)
+ *   weights n x G, G >= 1 (the weighted form): meanW, varW S x L x G and covW S x L x L x G (or NULL) with the layouts and
+ *       guarantees of gpslc_predict_weighted / gpslc_predict_curve — c_j = r^a_j bw_j, w' Delta w = beta = w . bw (no kw), and across
+ *       the levels P_ll' = rho(a_l, a_l') beta; the block is exactly symmetric, its diagonal bit-identical to varW, a zero weight
+ *       column gives an all-0.0 block
+ *   meanITE n x S x L, ite_draws L x n x (S*spp): the per-individual outcome; normals, Philox streams, gpslc_set_ensemble
+ *       placement, chunking and gpslc_last_info are gpslc_predict's
+ * Errors: G < 0, or G == 0 with weights given: -11; G > 0 with NULL weights, or a non-finite weight: -12; ite_draws with spp < 1:
+ * -14; covW without weights: -19.  fp64 only: a ctx created with GPSLC_FLAG_FP32_KERNEL returns GPSLC_ERR_UNSUPPORTED.  No _dev
+ * variant; not sharded (gpslc_predict_multi is unchanged).  Where B is constant (no U and X effect) CovITE is semi-definite to
+ * rounding; the draws factorise it robustly, as every CovITE.   */
+int gpslc_predict_outcome(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                          const double* xyLS, const double* tyLS, const double* yScale,
+                          const double* yNoise, int32_t L, const double* doT, int32_t G,
+                          const double* weights_or_null, double pred_noise, int32_t spp, uint64_t seed,
+                          const double* z_or_null, double* meanW, double* varW, double* covW, double* meanITE,
+                          double* ite_draws);
+
+/* Potential outcomes at per-individual levels: level l sets individual i to d_l[i] = doT[i + n*l] (an n x L host array, every
+ * entry finite, else -10), mu_i(d_l[i]) = f_i(d_l[i]).  meanSATE / varSATE are the VALUE OF THE TREATMENT POLICY d_l,
+ * V(d_l) = (1/n) sum_i f_i(d_l[i]), and its variance.  With g_ji = rho(T_j, d_i) and h_ij = rho(d_i, d_j):
+ *     D_ij = B_ij g_ji,   Delta_ij = B_ij h_ij,   MeanITE_i = sum_j B_ij g_ji alpha_j,   CovITE = Delta - D (K + yNoise I)^-1 D'
+ * — gpslc_predict_vec's passes with the factual terms dropped: no K alpha term and no exact 0.0 where d_l[i] == T_i.  d_l == T
+ * is the fitted surface: mean K alpha = Y - yNoise alpha and covariance the reference's CovC11; fill(a, n) is the scalar level
+ * a of gpslc_predict_outcome.  Signature, layouts, normals, chunking (results are bit-reproducible and independent of it),
+ * gpslc_last_info and error codes are gpslc_predict_vec's.  No weights with vector levels.  fp64 only
+ * (GPSLC_ERR_UNSUPPORTED on a GPSLC_FLAG_FP32_KERNEL ctx); no _dev variant; not sharded.   */
+int gpslc_predict_outcome_vec(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                              const double* xyLS, const double* tyLS, const double* yScale,
+                              const double* yNoise, int32_t L, const double* doT, double pred_noise,
+                              int32_t spp, uint64_t seed, const double* z_or_null,
+                              double* meanSATE, double* varSATE, double* meanITE, double* ite_draws);
+
 /* The same call sharded over several GPUs of one node: what the loop of predictCounterfactualEffects (src/prediction.jl:30-33)
  * over the posterior samples (src/estimation.jl:78-84) becomes when the ensemble is partitioned.  ctxs[0..nctx) are
  * DISTINCT contexts created with the same (n, nX, nU), one per device (gpslc_create(&ctx_k, device_k, ...)), each holding the data
@@ -411,6 +459,21 @@ int gpslc_ite_distributions_slope(gpslc_ctx* ctx, int64_t S, const double* U, co
                                   const double* xyLS, const double* tyLS, const double* yScale,
                                   const double* yNoise, double doT, double pred_noise,
                                   double* MeanITEs, double* CovITEs);
+
+/* ITEDistributions for the potential outcome f_i(doT) at the scalar level doT (see gpslc_predict_outcome): same outputs and
+ * layouts as gpslc_ite_distributions — MeanITEs the outcome means, CovITEs = CovC22 with its + pred_noise*I.  A non-finite doT
+ * returns -9.  GPSLC_FLAG_FP32_KERNEL: GPSLC_ERR_UNSUPPORTED. */
+int gpslc_ite_distributions_outcome(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                                    const double* xyLS, const double* tyLS, const double* yScale,
+                                    const double* yNoise, double doT, double pred_noise,
+                                    double* MeanITEs, double* CovITEs);
+
+/* The same for a per-individual level doT (n values, host; see gpslc_predict_outcome_vec): outputs, layouts and error codes are
+ * gpslc_ite_distributions_vec's (a non-finite entry returns -9; GPSLC_FLAG_FP32_KERNEL: GPSLC_ERR_UNSUPPORTED). */
+int gpslc_ite_distributions_outcome_vec(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS,
+                                        const double* xyLS, const double* tyLS, const double* yScale,
+                                        const double* yNoise, const double* doT, double pred_noise,
+                                        double* MeanITEs, double* CovITEs);
 
 /* likelihoodDistribution(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT) (src/likelihood.jl:8-52 and
  * its three reduced methods :55-94, :97-136, :139-174) for ONE parameter set, as the reference exports it:

@@ -370,6 +370,53 @@ function predict_slope(c::Ctx, p::Pack, doT::Vector{Float64}, weights::Union{Not
     mW, vW, cW, mI, dr
 end
 
+"""Potential outcomes (gpslc_predict_outcome): level l is the expected outcome f_i(`doT[l]`) itself, everybody set to that dose
+— its average over the population is the average dose-response function (E[Y(1)], E[Y(0)] for a binary treatment).  The prior
+mean is zero as in the reference's model, and this is the latent surface (no yNoise on the diagonal).  Arguments, keywords and the
+returned tuple (mW, vW, covW | nothing, meanITE | nothing, ite | nothing) are `predict_slope`'s."""
+function predict_outcome(c::Ctx, p::Pack, doT::Vector{Float64}, weights::Union{Nothing,Matrix{Float64}}, pred_noise::Float64;
+                         spp::Integer=0, seed::Integer=0, z=nothing, want_mean_ite::Bool=false, want_draws::Bool=false,
+                         want_cov::Bool=true)
+    S, L, n = length(p.tyLS), length(doT), c.n
+    G = weights === nothing ? 0 : size(weights, 2)
+    weights === nothing || size(weights, 1) == n || throw(DimensionMismatch("weights has $(size(weights, 1)) rows, n = $n"))
+    mW = weights === nothing ? Array{Float64}(undef, S, L) : Array{Float64}(undef, S, L, G)
+    vW = similar(mW)
+    cW = (weights !== nothing && want_cov) ? Array{Float64}(undef, S, L, L, G) : nothing
+    mI = want_mean_ite ? Array{Float64}(undef, n, S, L) : nothing
+    dr = want_draws ? Array{Float64}(undef, L, n, S * spp) : nothing
+    zf = f64(z)
+    GC.@preserve p doT weights zf mW vW cW mI dr check(c, ccall((:gpslc_predict_outcome, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Int32, UInt64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        L, pointer(doT), G, ptr(weights), pred_noise, spp, seed, ptr(zf),
+        pointer(mW), pointer(vW), ptr(cW), ptr(mI), ptr(dr)))
+    mW, vW, cW, mI, dr
+end
+
+"""Potential outcomes at per-individual levels (gpslc_predict_outcome_vec): column l of the n x L matrix `doT` sets individual i
+to `doT[i, l]`; mS / vS are the value of that treatment policy, (1/n) sum_i f_i(doT[i, l]), and its variance.  `doT[:, l] == T`
+is the fitted surface.  Same keywords and return value as `predict_vec`."""
+function predict_outcome_vec(c::Ctx, p::Pack, doT::Matrix{Float64}, pred_noise::Float64; spp::Integer=0, seed::Integer=0,
+                             z=nothing, want_mean_ite::Bool=false, want_draws::Bool=false)
+    S, L, n = length(p.tyLS), size(doT, 2), c.n
+    size(doT, 1) == n || throw(DimensionMismatch("doT has $(size(doT, 1)) rows, n = $n"))
+    mS, vS = Matrix{Float64}(undef, S, L), Matrix{Float64}(undef, S, L)
+    mI = want_mean_ite ? Array{Float64}(undef, n, S, L) : nothing
+    dr = want_draws ? Array{Float64}(undef, L, n, S * spp) : nothing
+    zf = f64(z)
+    GC.@preserve p doT zf mS vS mI dr check(c, ccall((:gpslc_predict_outcome_vec, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Ptr{Float64}, Float64, Int32, UInt64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        L, pointer(doT), pred_noise, spp, seed, ptr(zf),
+        pointer(mS), pointer(vS), ptr(mI), ptr(dr)))
+    mS, vS, mI, dr
+end
+
 """`predict` sharded over several GPUs of one node — `cs` = one context per device (`Ctx(n, nX, nU; device=k)`, each with
 the data: `set_data!` on every one), the posterior samples split into contiguous blocks, one host thread per context inside the
 library, every device copying its block of the results into these host arrays.  Same results as `predict(cs[1], …)` over all S
@@ -463,6 +510,33 @@ function ite_distributions_slope(c::Ctx, p::Pack, doT::Float64, pred_noise::Floa
          Float64, Float64, Ptr{Float64}, Ptr{Float64}),
         c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
         doT, pred_noise, pointer(M), ptr(Cv)))
+    M, Cv
+end
+
+"""`ite_distributions` for the potential outcome f_i(`doT`) at the scalar level `doT`: gpslc_ite_distributions_outcome."""
+function ite_distributions_outcome(c::Ctx, p::Pack, doT::Float64, pred_noise::Float64; want_cov::Bool=true)
+    S, n = length(p.tyLS), c.n
+    M = Matrix{Float64}(undef, S, n)
+    Cv = want_cov ? Array{Float64}(undef, S, n, n) : nothing
+    GC.@preserve p M Cv check(c, ccall((:gpslc_ite_distributions_outcome, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Float64, Float64, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        doT, pred_noise, pointer(M), ptr(Cv)))
+    M, Cv
+end
+
+"""`ite_distributions_outcome` for a per-individual level `doT` (n values): gpslc_ite_distributions_outcome_vec."""
+function ite_distributions_outcome_vec(c::Ctx, p::Pack, doT::Vector{Float64}, pred_noise::Float64; want_cov::Bool=true)
+    S, n = length(p.tyLS), c.n
+    length(doT) == n || throw(DimensionMismatch("doT has length $(length(doT)), n = $n"))
+    M = Matrix{Float64}(undef, S, n)
+    Cv = want_cov ? Array{Float64}(undef, S, n, n) : nothing
+    GC.@preserve p doT M Cv check(c, ccall((:gpslc_ite_distributions_outcome_vec, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(p.U), ptr(p.uyLS), ptr(p.xyLS), pointer(p.tyLS), pointer(p.yScale), pointer(p.yNoise),
+        pointer(doT), pred_noise, pointer(M), ptr(Cv)))
     M, Cv
 end
 
@@ -848,6 +922,29 @@ function _slope_predict(g::GPSLCObject, devices, lv, baseline, weights; kw...)
     GPSLCHip.predict_slope(ctx(g), posterior_pack(g), lv, Wm, g.hyperparams.predictionCovarianceNoise; kw...)
 end
 
+# `outcome=true` of the estimation methods below: the potential outcome f_i(doT) itself instead of a difference of two settings
+# (gpslc_predict_outcome[_vec] / gpslc_ite_distributions_outcome[_vec]).  A scalar doT combines with `weights=`; a per-individual
+# doT (the value of a treatment policy) does not.  Not with `baseline=` (the contrast IS the difference of two outcomes),
+# `slope=true` or `devices=`.  Returns predict_outcome's 5-tuple (covW = nothing for per-individual levels).
+function _outcome_refusals(devices, lv, baseline, slope, weights)
+    baseline === nothing || throw(ArgumentError("outcome=true cannot be combined with baseline=: the contrast is the difference of two outcomes, f(a) - f(b)"))
+    slope && throw(ArgumentError("outcome=true cannot be combined with slope=true: the outcome is a level of the surface, the slope its derivative"))
+    devices === nothing || throw(ArgumentError("outcome=true is not sharded over devices: pass devices=nothing"))
+    (weights === nothing || lv isa Vector{Float64} || lv isa Float64) ||
+        throw(ArgumentError("outcome=true with weights= needs a scalar doT: weighted outcomes at per-individual intervention vectors are not supported"))
+    nothing
+end
+function _outcome_predict(g::GPSLCObject, devices, lv, baseline, slope, weights; want_cov::Bool=true, kw...)
+    _outcome_refusals(devices, lv, baseline, slope, weights)
+    pn = g.hyperparams.predictionCovarianceNoise
+    if lv isa Matrix{Float64}
+        mS, vS, mI, dr = GPSLCHip.predict_outcome_vec(ctx(g), posterior_pack(g), lv, pn; kw...)
+        return mS, vS, nothing, mI, dr
+    end
+    Wm = weights === nothing ? nothing : _weights(weights, getN(g))
+    GPSLCHip.predict_outcome(ctx(g), posterior_pack(g), lv, Wm, pn; want_cov=want_cov, kw...)
+end
+
 # `weights=` of SATEDistributions / sampleSATE: nothing = the average over everybody; a length-n vector or an n x G matrix of
 # weights used as given (a Bool vector / matrix is a mask: that group's average), gpslc_predict_weighted — scalar doT, one GPU only
 _weight_column(w::AbstractVector{Bool}) = (any(w) || throw(ArgumentError("weights= has an empty group mask")); Float64.(w) ./ count(w))
@@ -981,8 +1078,14 @@ function conditionalITE(g::GPSLCObject, psindex::Int64, doT::Intervention)      
     conditionalITE(uyLS, xyLS, tyLS, yNoise, yScale, U, g.X, g.T, g.Y, doT)
 end
 
-function ITEDistributions(g::GPSLCObject, doT::Intervention; baseline=nothing, slope::Bool=false)                  # :66-86
+function ITEDistributions(g::GPSLCObject, doT::Intervention; baseline=nothing, slope::Bool=false,
+                          outcome::Bool=false)                                                                     # :66-86
     d, pn = _dot(doT, getN(g)), g.hyperparams.predictionCovarianceNoise
+    if outcome                   # the potential outcome f_i(doT): mean D alpha, covariance CovC22 (+ jitter)
+        _outcome_refusals(nothing, d, baseline, slope, nothing)
+        d isa Float64 && return GPSLCHip.ite_distributions_outcome(ctx(g), posterior_pack(g), d, pn)
+        return GPSLCHip.ite_distributions_outcome_vec(ctx(g), posterior_pack(g), d, pn)
+    end
     if slope
         baseline === nothing || throw(ArgumentError("slope=true cannot be combined with baseline=: the slope is a derivative at one level, not a contrast"))
         d isa Float64 || throw(ArgumentError("slope=true needs a scalar doT: slopes at per-individual intervention vectors are not supported"))
@@ -994,7 +1097,12 @@ function ITEDistributions(g::GPSLCObject, doT::Intervention; baseline=nothing, s
 end
 
 function SATEDistributions(g::GPSLCObject, doT::Intervention; devices=nothing, baseline=nothing, weights=nothing,
-                           slope::Bool=false)                                                                      # :127-140
+                           slope::Bool=false, outcome::Bool=false)                                                 # :127-140
+    if outcome                   # the average potential outcome (dose-response function / policy value); shapes as below
+        mW, vW, _, _, _ = _outcome_predict(g, devices, _levels(_dot(doT, getN(g))), baseline, slope, weights; want_cov=false)
+        weights === nothing && return mW[:, 1], vW[:, 1]
+        return weights isa AbstractVector ? (mW[:, 1, 1], vW[:, 1, 1]) : (mW[:, 1, :], vW[:, 1, :])
+    end
     if slope                     # the average marginal effect at doT; shapes as below
         mW, vW, _, _, _ = _slope_predict(g, devices, _levels(_dot(doT, getN(g))), baseline, weights; want_cov=false)
         weights === nothing && return mW[:, 1], vW[:, 1]
@@ -1022,9 +1130,15 @@ function _normals(n, spp, S, L, seed)
 end
 
 function sampleITE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64=10,
-                   seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing, slope::Bool=false)     # :86-89
+                   seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing, slope::Bool=false,
+                   outcome::Bool=false)                                                                            # :86-89
     n, S = getN(g), getNumPosteriorSamples(g)
     sd, z = _normals(n, samplesPerPosterior, S, 1, seed)
+    if outcome
+        _, _, _, _, ite = _outcome_predict(g, devices, _levels(_dot(doT, n)), baseline, slope, nothing; spp=samplesPerPosterior,
+                                           seed=sd, z=z, want_draws=true)
+        return ite[1, :, :]
+    end
     if slope
         _, _, _, _, ite = _slope_predict(g, devices, _levels(_dot(doT, n)), baseline, nothing; spp=samplesPerPosterior, seed=sd, z=z,
                                          want_draws=true)
@@ -1036,8 +1150,9 @@ end
 
 function sampleSATE(g::GPSLCObject, doT::Intervention; samplesPerPosterior::Int64=10,
                     seed::Union{Nothing,Integer}=nothing, devices=nothing, baseline=nothing, weights=nothing,
-                    slope::Bool=false)                                                                             # :108-111
-    MeanSATEs, VarSATEs = SATEDistributions(g, doT; devices=devices, baseline=baseline, weights=weights, slope=slope)
+                    slope::Bool=false, outcome::Bool=false)                                                        # :108-111
+    MeanSATEs, VarSATEs = SATEDistributions(g, doT; devices=devices, baseline=baseline, weights=weights, slope=slope,
+                                            outcome=outcome)
     if MeanSATEs isa AbstractMatrix      # an n x G weight matrix: G x (S * spp), group g on the Philox seed `seed + g - 1`
         G = size(MeanSATEs, 2)
         rows = [seed === nothing ?
@@ -1057,9 +1172,14 @@ _curve_baseline(b::Nothing, L) = nothing
 _curve_baseline(b::Real, L) = fill(Float64(b), L)
 _curve_baseline(b::AbstractVector{<:Real}, L) =
     (length(b) == L || throw(ArgumentError("baseline= needs one value per level: $(length(b)) values, L = $L")); Vector{Float64}(b))
-function _curve(g::GPSLCObject, doTs::AbstractVector{<:Real}, baseline, weights, devices, slope::Bool=false)
+function _curve(g::GPSLCObject, doTs::AbstractVector{<:Real}, baseline, weights, devices, slope::Bool=false,
+                outcome::Bool=false)
     n = getN(g)
     lv = Vector{Float64}(doTs)
+    if outcome                   # the dose-response curve itself: gpslc_predict_outcome's weighted form, 1/n included
+        mW, _, cW, _, _ = _outcome_predict(g, devices, lv, baseline, slope, weights === nothing ? fill(1.0 / n, n) : weights)
+        return mW, cW, !(weights isa AbstractMatrix)
+    end
     if slope                     # the curve of average marginal effects: gpslc_predict_slope's weighted form, 1/n included
         mW, _, cW, _, _ = _slope_predict(g, devices, lv, baseline, weights === nothing ? fill(1.0 / n, n) : weights)
         return mW, cW, !(weights isa AbstractMatrix)
@@ -1073,10 +1193,11 @@ end
 
 """effectCurve(g, doTs; baseline, weights, slope) -> (mean S x L [x G], cov S x L x L [x G]): the weighted effect over the L scalar
 levels `doTs` and its joint covariance across the levels, per posterior sample.  `slope=true`: the weighted marginal effects
-d f / dt at the levels — the derivative of the dose-response curve — instead."""
+d f / dt at the levels — the derivative of the dose-response curve — instead.  `outcome=true`: the weighted outcomes f(doTs[l]),
+the dose-response curve itself (the curve of levels, not of effects)."""
 function effectCurve(g::GPSLCObject, doTs::AbstractVector{<:Real}; baseline=nothing, weights=nothing, devices=nothing,
-                     slope::Bool=false)
-    mW, cW, vec = _curve(g, doTs, baseline, weights, devices, slope)
+                     slope::Bool=false, outcome::Bool=false)
+    mW, cW, vec = _curve(g, doTs, baseline, weights, devices, slope, outcome)
     vec ? (mW[:, :, 1], cW[:, :, :, 1]) : (mW, cW)
 end
 
@@ -1084,8 +1205,8 @@ end
 the curve, column order sample-outer / draw-inner: every column is ONE curve over the L levels."""
 function sampleEffectCurve(g::GPSLCObject, doTs::AbstractVector{<:Real}; samplesPerPosterior::Int64=10,
                            seed::Union{Nothing,Integer}=nothing, baseline=nothing, weights=nothing, devices=nothing,
-                           slope::Bool=false)
-    mW, cW, vec = _curve(g, doTs, baseline, weights, devices, slope)
+                           slope::Bool=false, outcome::Bool=false)
+    mW, cW, vec = _curve(g, doTs, baseline, weights, devices, slope, outcome)
     S, L, G = size(mW)
     dr = seed === nothing ? GPSLCHip.curve_samples(mW, cW, samplesPerPosterior; z=randn(L, samplesPerPosterior, S, G)) :
                             GPSLCHip.curve_samples(mW, cW, samplesPerPosterior; seed=UInt64(seed))
@@ -1106,7 +1227,8 @@ end
 # ---- src/prediction.jl --------------------------------------------------------------------------------------------
 function predictCounterfactualEffects(g::GPSLCObject, nSamplesPerMixture::Int64; fidelity::Int64=100,
                                       minDoT=min(g.T...), maxDoT=max(g.T...),
-                                      seed::Union{Nothing,Integer}=nothing, devices=nothing)                       # :23-36
+                                      seed::Union{Nothing,Integer}=nothing, devices=nothing,
+                                      outcome::Bool=false)                                                         # :23-36
     delta = abs(maxDoT - minDoT)
     step = delta / fidelity
     doTrange = minDoT:step:maxDoT                                          # :24-28
@@ -1115,6 +1237,11 @@ function predictCounterfactualEffects(g::GPSLCObject, nSamplesPerMixture::Int64;
     # one factorisation of A per posterior sample, shared by its L levels; `ite` comes back in the reference's
     # layout (L x n x S*spp, level index fastest).  devices = 0:7 shards the posterior samples — the loop of :30-33 — over the
     # eight GPUs of a node: ONE ccall (gpslc_predict_multi), same tensor bit for bit
+    if outcome                   # draws of every individual's outcome surface f_i(a) over the sweep, not of the effects
+        _, _, _, _, ite = _outcome_predict(g, devices, Float64.(collect(doTrange)), nothing, false, nothing; spp=nSamplesPerMixture,
+                                           seed=sd, z=z, want_draws=true)
+        return ite, doTrange
+    end
     _, _, _, ite = _predict(g, devices, Float64.(collect(doTrange)); spp=nSamplesPerMixture, seed=sd, z=z, want_draws=true)
     return ite, doTrange
 end
