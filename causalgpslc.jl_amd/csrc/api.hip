@@ -619,16 +619,28 @@ struct Posterior {                   // the S posterior samples of the call
     int64_t S = 0;
     SampleParams p{};                // the six per-sample arrays
 };
+// What each level form (level_form.h) can be combined with: run_predict's backstop behind the entry points' validate.  A baseline
+// is required by the paired form and refused by the others.  Every form takes weights: their rules stay in run_predict.
+struct FormRules { int form; const char* name; bool factual, baseline, vec, fp32; };
+template <int FORM, typename LF = LevelForm<FORM>>
+constexpr FormRules form_row(const char* name) { return {FORM, name, LF::factual, LF::paired, LF::vector_levels, LF::fp32_kernels}; }
+constexpr FormRules kFormRules[] = {form_row<FORM_ORDINARY>("ordinary levels"), form_row<FORM_CONTRAST>("contrasts"),
+                                    form_row<FORM_SLOPE>("slopes"), form_row<FORM_OUTCOME>("outcomes")};
+static const FormRules& form_rules(int form) {
+    for (const FormRules& r : kFormRules)
+        if (r.form == form) return r;
+    throw std::runtime_error("unknown level form");
+}
+
 struct Levels {
     int L = 0;
     const double* doT = nullptr;
     bool vec = false;                // vector levels: doT is n x L (level l at doT + n*l), not L scalars
-    const double* base = nullptr;    // contrasts (L): level l is doT[l] against base[l] (scalar levels only)
-    bool slope = false;              // marginal effects: level l is d f_i(t) / dt at t = doT[l] (scalar levels only)
-    // the level form the kernels take (FORM_*): what multiplies B_ij outside the pair loops
-    bool outcome = false;            // potential outcomes: level l is f_i(doT[l]) itself (scalar or vector levels)
-    int form() const { return outcome ? FORM_OUTCOME : slope ? FORM_SLOPE : base ? FORM_CONTRAST : FORM_ORDINARY; }
-    bool needs_kw() const { return form() == FORM_ORDINARY; }     // contrasts, slopes and outcomes have no K W term
+    int form = FORM_ORDINARY;        // FORM_* (level_form.h), set by the entry points
+    const double* base = nullptr;    // FORM_CONTRAST (L): level l is doT[l] against base[l]
+    void against(const double* b) { base = b; form = b ? FORM_CONTRAST : FORM_ORDINARY; }   // a contrast exactly when a baseline is given
+    bool needs_kw() const { return form_rules(form).factual; }     // only the factual term brings K W in
+    LevelSet set(int nlevels) const { return LevelSet{doT, base, nlevels, form, vec ? 1 : 0}; }      // what the kernels take
     // weighted effects: G weight columns — the caller's W[i + n*g] on the host, column fastest (W[g + G*j]) on the
     // device; meanSATE / varSATE are then S x L x G — element (s, l, g) at s + S*(l + L*g) — of tau_w = w_g' ITE_l, the weights
     // used as given (scalar levels only)
@@ -746,7 +758,7 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     if (sh.with_sums && !io.lv.W) b.part = take(2 * nt * sh.Np);
     b.bsum = take(sh.Np); b.ksum = take(sh.Np);
     b.sumdelta = take(std::max(sh.R, 1));
-    if (io.lv.W) {      // the contrast, slope and outcome forms need no K W
+    if (io.lv.W) {      // only the factual form needs K W
         b.bw = take((size_t)io.lv.G * sh.Np);
         b.kw = io.lv.needs_kw() ? take((size_t)io.lv.G * sh.Np) : b.bw;
         b.wnorm2 = take(io.lv.G);
@@ -780,10 +792,9 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
 // the vector-level kernels' arguments of a chunk (doT is n x L: level l at doT + n*l)
 VecArgs vec_args(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     VecArgs va{ch.grid};
-    va.L = sh.L; va.doT = io.lv.doT;
+    va.lv = io.lv.set(sh.L);
     va.M = ch.M; va.part = ch.vpart; va.sumdelta = ch.sumdelta;
     va.Y = io.Y; va.y_sstride = io.y_sstride;
-    va.form = io.lv.form();
     return va;
 }
 
@@ -840,12 +851,12 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     }
 #endif
     RhsArgs ra{};
-    ra.T = c->dT; ra.Y = io.Y; ra.y_sstride = io.y_sstride; ra.tyLS = io.post.p.tyLS; ra.doT = io.lv.doT; ra.s0 = s0;
-    // vector levels: rhs_tiles writes zeros into the level rows and rhs_prepare no level sums (L = 0 here); launch_vec_sums
+    ra.T = c->dT; ra.Y = io.Y; ra.y_sstride = io.y_sstride; ra.tyLS = io.post.p.tyLS; ra.s0 = s0;
+    // vector levels: rhs_tiles writes zeros into the level rows and rhs_prepare no level sums (no levels here); launch_vec_sums
     // fills both below
-    ra.n = n; ra.nt = nt; ra.naug = sh.naug; ra.L = (sh.with_sums && !io.lv.vec) ? sh.L : 0; ra.with_sums = sh.with_sums ? 1 : 0;
+    ra.lv = io.lv.set((sh.with_sums && !io.lv.vec) ? sh.L : 0);
+    ra.n = n; ra.nt = nt; ra.naug = sh.naug; ra.with_sums = sh.with_sums ? 1 : 0;
     ra.part = ch.part; ra.bsum = ch.bsum; ra.ksum = ch.ksum; ra.sumdelta = ch.sumdelta; ra.M = ch.M;
-    ra.doT_base = io.lv.base; ra.form = io.lv.form();
     const bool epi_rows = (sh.naug == 1);                    // single augmented tile row: the epilogue sums from the rows of R
     const int live = (sh.with_sums ? sh.R : 0) + 1;          // right-hand sides: Y and one c_l per level (and weight column)
     ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
@@ -876,8 +887,8 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     launch_epilogue(ea, nb, st);
     if (io.out.covW) {      // the levels' joint covariance per weight column: Gram matrix of the rows the factorisation carried
         CurveArgs ca{};
-        ca.M = ch.M; ca.n = n; ca.nt = nt; ca.L = sh.L; ca.G = io.lv.G; ca.s0 = s0; ca.S = io.post.S;
-        ca.T = c->dT; ca.tyLS = io.post.p.tyLS; ca.doT = io.lv.doT; ca.doT_base = io.lv.base; ca.form = io.lv.form();
+        ca.M = ch.M; ca.n = n; ca.nt = nt; ca.lv = io.lv.set(sh.L); ca.G = io.lv.G; ca.s0 = s0; ca.S = io.post.S;
+        ca.T = c->dT; ca.tyLS = io.post.p.tyLS;
         ca.W = io.lv.W; ca.bw = ch.bw; ca.kw = ch.kw; ca.prior = ch.cprior;
         ca.varW = io.out.varSATE; ca.covW = io.out.covW;
         launch_curve(ca, nb, st);
@@ -910,10 +921,9 @@ void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
         return;
     }
     IteMeanArgs ia{ch.grid};
-    ia.S = S; ia.L = sh.L; ia.doT = io.lv.doT; ia.alpha = alpha;
+    ia.S = S; ia.lv = io.lv.set(sh.L); ia.alpha = alpha;
     ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.post.p.yNoise;
     ia.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
-    ia.doT_base = io.lv.base; ia.form = io.lv.form();
     for (const auto& o : outs)
         if (o.out) { ia.meanITE = o.out; ia.si = o.si; ia.ss = o.ss; ia.sl = o.sl; launch_ite_mean(ia, nb, st); }
 }
@@ -950,9 +960,7 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
             Ls.bdiv = lc;
             DtArgs da{ch.grid};
             da.s0 = s0 + g0;
-            da.doT = io.lv.doT; da.l0 = l0; da.lc = lc;
-            da.vec = io.lv.vec ? 1 : 0;
-            da.doT_base = io.lv.base; da.form = io.lv.form();
+            da.lv = io.lv.set(L); da.l0 = l0; da.lc = lc;
             da.pred_noise = io.out.pred_noise; da.W = W; da.Cm = Cm;
             launch_dt_build(da, ub, st);
             TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
@@ -1002,14 +1010,13 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
 // the chunked ensemble driver (device pointers everywhere)
 void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     PredictIO io = io_in;
-    if (io.lv.base && io.lv.vec) throw std::runtime_error("a contrast baseline cannot be combined with vector levels");
-    if (io.lv.base && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("contrasts need an fp64 context");
-    if (io.lv.slope && io.lv.vec) throw std::runtime_error("slopes cannot be combined with vector levels");
-    if (io.lv.slope && io.lv.base) throw std::runtime_error("slopes cannot be combined with a contrast baseline");
-    if (io.lv.slope && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("slopes need an fp64 context");
-    if (io.lv.outcome && io.lv.base) throw std::runtime_error("outcomes cannot be combined with a contrast baseline");
-    if (io.lv.outcome && io.lv.slope) throw std::runtime_error("outcomes cannot be combined with slopes");
-    if (io.lv.outcome && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("outcomes need an fp64 context");
+    const FormRules& fr = form_rules(io.lv.form);
+    const struct { bool refused; const char* why; } refusals[] = {
+        {io.lv.vec && !fr.vec, " cannot be combined with vector levels"},
+        {(c->flags & GPSLC_FLAG_FP32_KERNEL) && !fr.fp32, " need an fp64 context"},
+        {(io.lv.base != nullptr) != fr.baseline, fr.baseline ? " need a baseline" : " cannot be combined with a contrast baseline"}};
+    for (const auto& r : refusals)
+        if (r.refused) throw std::runtime_error(std::string(fr.name) + r.why);
     if (io.lv.W && io.lv.vec) throw std::runtime_error("weights cannot be combined with vector levels");
     if (io.lv.W && (c->flags & GPSLC_FLAG_FP32_KERNEL)) throw std::runtime_error("weighted effects need an fp64 context");
     if (io.lv.W && io.lv.G < 1) throw std::runtime_error("weights without a weight column");
@@ -1608,7 +1615,7 @@ static int validate(gpslc_ctx* c, const PredictRequest& rq, const ArgPos& k) {
         if (c->ens_S > 0 && c->ens_off + po.S > c->ens_S)
             return bad_arg(c, k.S, "S exceeds the room gpslc_set_ensemble left: sample_offset + S > S_total");
     }
-    if (lv.vec || k.base || lv.slope || lv.outcome) {
+    if (lv.vec || k.base || lv.form == FORM_SLOPE || lv.form == FORM_OUTCOME) {
         if ((rc = finite_check(c, lv.doT, lv.vec ? c->n * (int64_t)lv.L : lv.L, k.doT, "doT"))) return rc;
         // the baselines are optional beside weights
         if (k.base && (lv.base || !k.W) && (rc = finite_check(c, lv.base, lv.L, k.base, "doT_base"))) return rc;
@@ -1747,7 +1754,7 @@ int gpslc_predict_contrast(gpslc_ctx* c, int64_t S, const double* U, const doubl
                            const double* doT_base, double pred_noise, int32_t spp, uint64_t seed, const double* z,
                            double* meanSATE, double* varSATE, double* meanITE, double* ite_draws) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
-    rq.lv.base = doT_base;
+    rq.lv.against(doT_base);
     rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanSATE, varSATE, meanITE, ite_draws};
     int rc = validate(c, rq, kPredictContrastArgs);
     return rc ? rc : predict_host(c, rq);
@@ -1759,7 +1766,7 @@ int gpslc_predict_weighted(gpslc_ctx* c, int64_t S, const double* U, const doubl
                            const double* doT_base, int32_t G, const double* weights, double pred_noise, int32_t spp,
                            uint64_t seed, const double* z, double* meanW, double* varW, double* meanITE, double* ite_draws) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
-    rq.lv.base = doT_base; rq.lv.G = G; rq.lv.W = weights;
+    rq.lv.against(doT_base); rq.lv.G = G; rq.lv.W = weights;
     rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws};
     int rc = validate(c, rq, kPredictWeightedArgs);
     return rc ? rc : predict_host(c, rq);
@@ -1772,7 +1779,7 @@ int gpslc_predict_curve(gpslc_ctx* c, int64_t S, const double* U, const double* 
                         uint64_t seed, const double* z, double* meanW, double* varW, double* covW, double* meanITE,
                         double* ite_draws) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
-    rq.lv.base = doT_base; rq.lv.G = G; rq.lv.W = weights;
+    rq.lv.against(doT_base); rq.lv.G = G; rq.lv.W = weights;
     rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws, covW};
     int rc = validate(c, rq, kPredictWeightedArgs);
     return rc ? rc : predict_host(c, rq);
@@ -1785,7 +1792,7 @@ int gpslc_predict_slope(gpslc_ctx* c, int64_t S, const double* U, const double* 
                         int32_t G, const double* weights, double pred_noise, int32_t spp, uint64_t seed, const double* z,
                         double* meanW, double* varW, double* covW, double* meanITE, double* ite_draws) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
-    rq.lv.slope = true; rq.lv.G = G; rq.lv.W = weights;
+    rq.lv.form = FORM_SLOPE; rq.lv.G = G; rq.lv.W = weights;
     rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws, covW};
     int rc = validate(c, rq, kPredictSlopeArgs);
     return rc ? rc : predict_host(c, rq);
@@ -1798,7 +1805,7 @@ int gpslc_predict_outcome(gpslc_ctx* c, int64_t S, const double* U, const double
                           int32_t G, const double* weights, double pred_noise, int32_t spp, uint64_t seed, const double* z,
                           double* meanW, double* varW, double* covW, double* meanITE, double* ite_draws) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
-    rq.lv.outcome = true; rq.lv.G = G; rq.lv.W = weights;
+    rq.lv.form = FORM_OUTCOME; rq.lv.G = G; rq.lv.W = weights;
     rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanW, varW, meanITE, ite_draws, covW};
     int rc = validate(c, rq, kPredictSlopeArgs);
     return rc ? rc : predict_host(c, rq);
@@ -1810,7 +1817,7 @@ int gpslc_predict_outcome_vec(gpslc_ctx* c, int64_t S, const double* U, const do
                               double pred_noise, int32_t spp, uint64_t seed, const double* z, double* meanSATE,
                               double* varSATE, double* meanITE, double* ite_draws) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
-    rq.lv.vec = true; rq.lv.outcome = true;
+    rq.lv.vec = true; rq.lv.form = FORM_OUTCOME;
     rq.out = DrawsAndOutputs{pred_noise, spp, seed, z, meanSATE, varSATE, meanITE, ite_draws};
     int rc = validate(c, rq, kPredictVecArgs);
     return rc ? rc : predict_host(c, rq);
@@ -1953,7 +1960,7 @@ int gpslc_ite_distributions_contrast(gpslc_ctx* c, int64_t S, const double* U, c
                                      const double* tyLS, const double* yScale, const double* yNoise, double doT,
                                      double doT_base, double pred_noise, double* MeanITEs, double* CovITEs) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, &doT);
-    rq.lv.base = &doT_base;
+    rq.lv.against(&doT_base);
     rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
     int rc = validate(c, rq, kIteContrastArgs);
     return rc ? rc : ite_distributions_host(c, rq);
@@ -1963,7 +1970,7 @@ int gpslc_ite_distributions_slope(gpslc_ctx* c, int64_t S, const double* U, cons
                                   const double* tyLS, const double* yScale, const double* yNoise, double doT,
                                   double pred_noise, double* MeanITEs, double* CovITEs) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, &doT);
-    rq.lv.slope = true;
+    rq.lv.form = FORM_SLOPE;
     rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
     int rc = validate(c, rq, kIteSlopeArgs);
     return rc ? rc : ite_distributions_host(c, rq);
@@ -1973,7 +1980,7 @@ int gpslc_ite_distributions_outcome(gpslc_ctx* c, int64_t S, const double* U, co
                                     const double* tyLS, const double* yScale, const double* yNoise, double doT,
                                     double pred_noise, double* MeanITEs, double* CovITEs) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, &doT);
-    rq.lv.outcome = true;
+    rq.lv.form = FORM_OUTCOME;
     rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
     int rc = validate(c, rq, kIteSlopeArgs);
     return rc ? rc : ite_distributions_host(c, rq);
@@ -1983,7 +1990,7 @@ int gpslc_ite_distributions_outcome_vec(gpslc_ctx* c, int64_t S, const double* U
                                         const double* tyLS, const double* yScale, const double* yNoise, const double* doT,
                                         double pred_noise, double* MeanITEs, double* CovITEs) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, doT);
-    rq.lv.vec = true; rq.lv.outcome = true;
+    rq.lv.vec = true; rq.lv.form = FORM_OUTCOME;
     rq.out.pred_noise = pred_noise; rq.MeanITEs = MeanITEs; rq.CovITEs = CovITEs;
     int rc = validate(c, rq, kIteVecArgs);
     return rc ? rc : ite_distributions_host(c, rq);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "level_form.h"
 
 // ---------------------------------------------------------------------------------------
 // Tiled storage.  Every dense matrix the factorisation touches lives in HBM as 128 x 128
@@ -219,35 +220,31 @@ void launch_trsm_robust(const TRef& X, const TRef& L, int k, int i0, int count, 
 // info[g] (if still 0) <- the first nonzero of pair_info[g*lc .. g*lc + lc - 1], g < gs (k_robust.hip)
 void launch_fold_pair_info(const int* pair_info, int* info, int gs, int lc, hipStream_t st);
 
-// The level form of a prediction call: what multiplies B_ij outside the pair loops.
-//   FORM_ORDINARY  f_i(doT_l) - f_i(T_i)
-//   FORM_CONTRAST  f_i(a_l) - f_i(b_l) for the pair (a, b) = (doT[l], doT_base[l])
-//   FORM_SLOPE     d f_i(t) / dt at t = doT[l]: cross term q^a_j = 2 (T_j - a) r^a_j / tyLS^2, prior term 2 / tyLS^2
-//   FORM_OUTCOME   f_i(doT_l), the potential outcome itself: the ordinary level without its factual term — cross term r^a_j,
-//                  prior term 1 (vector levels d: cross term g_ji = rho(T_j, d_i), prior term h_ij = rho(d_i, d_j))
-enum { FORM_ORDINARY = 0, FORM_CONTRAST = 1, FORM_SLOPE = 2, FORM_OUTCOME = 3 };
-
-// q^a_j of the slope form, wt = 1 / tyLS^2: the difference T_j - a is formed in fp64 by the caller's arguments
-__host__ __device__ inline double gp_slope_q(double dt, double r, double wt) { return (2.0 * dt) * wt * r; }
+// The levels of a prediction call as every kernel that knows about levels receives them; what each form computes from them is
+// level_form.h's table.
+struct LevelSet {
+    const double* doT;    // device: L scalars, or with vec n x L (level l of individual i at doT[i + n*l])
+    const double* base;   // LevelForm<form>::paired: level l is the pair (doT[l], base[l]); else null
+    int L;
+    int form;             // FORM_*
+    int vec;              // vector levels (LevelForm<form>::vector_levels)
+};
 
 struct RhsArgs {
-    const double* T; const double* Y; const double* tyLS; const double* doT;
+    const double* T; const double* Y; const double* tyLS;
     long long y_sstride;   // right-hand side 0 of sample s is Y + s*y_sstride (0 = shared)
-    long long s0; int n, nt, naug, L; int with_sums;
+    long long s0; int n, nt, naug; int with_sums;
+    LevelSet lv;           // lv.L: the levels whose sums and rows this launch forms — 0 for vector levels (launch_vec_sums' work)
     const double* part; double* bsum; double* ksum; double* sumdelta;  // bsum/ksum [b][Np], sumdelta [b][L]
     TRef M;
     int live_rows;   // > 0 (single augmented tile row of <= 32 right-hand sides, epilogue sums from the rows of R): only the
                      // first 32 rows of the augmented tiles are written (right-hand sides, then zeros) and the augmented
                      // diagonal tile not at all — every reader of those tiles touches the live 16- / 32-row blocks only
-    const double* doT_base;   // form == FORM_CONTRAST: level l is the pair (doT[l], doT_base[l]), c_l = (r^a - r^b) .* bsum and
-                              // sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B
     // G columns of level sums, right-hand side 1 + l + L*g is level l of column g, rows from bw / kw [b][G][Np].  The plain call
     // is G = 1 with bw = bsum, kw = ksum and W null; weighted effects (W non-null) have G weight columns, bw / kw
     // from launch_wsum, sumdelta [b][L*G] and wnorm2 [b][G] = w_g . w_g
     const double* W; int G;   // device, column g fastest: W[g + G*j]
-    const double* bw; const double* kw; double* wnorm2;
-    int form;   // FORM_*.  Slope: c_l = q^a .* bw_g and sum(Delta_l) = (2 / tyLS^2) sum B (weighted: (2 / tyLS^2) w . bw), no kw
-                // Outcome: c_l = r^a .* bw_g and sum(Delta_l) = sum B (weighted: w . bw), no kw
+    const double* bw; const double* kw; double* wnorm2;      // kw is read by the factual form only
 };
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
 
@@ -255,7 +252,7 @@ void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
 struct WsumArgs : SampleGrid {
     int G;
     const double* W;       // device, column g fastest: W[g + G*j]
-    double* bw; double* kw;   // [b][G][Np]; kw is not written when with_k == 0 (contrasts, slopes and outcomes need BW only)
+    double* bw; double* kw;   // [b][G][Np]; kw is not written when with_k == 0 (only the factual form needs K W)
     int with_k;
     int binary_t;          // as GramArgs::binary_t: the e_ij of the K that is factorised
 };
@@ -276,16 +273,14 @@ void launch_epilogue(const EpiArgs& e, int nbatch, hipStream_t st);
 
 // joint covariance of the weighted effects across the levels of a call (k_curve.hip); runs after the epilogue
 struct CurveArgs {
-    TRef M; int n, nt, L, G; long long s0; long long S;
-    const double* T; const double* tyLS; const double* doT;
-    const double* doT_base;   // form == FORM_CONTRAST (level l is the pair (doT[l], doT_base[l]))
+    TRef M; int n, nt, G; long long s0; long long S;
+    const double* T; const double* tyLS;
+    LevelSet lv;              // scalar levels
     const double* W;          // device, column g fastest: W[g + G*j]
-    const double* bw; const double* kw;   // [b][G][Np] (launch_wsum); kw is not read for contrasts, slopes and outcomes
+    const double* bw; const double* kw;   // [b][G][Np] (launch_wsum); kw is read by the factual form only
     double* prior;            // [b][G][L + 2]: beta = w . bw, kappa = w . kw, gamma_l = sum_j w_j r^l_j bw_j
     const double* varW;       // S x L x G, as the epilogue stored it: the diagonal
     double* covW;             // S x L x L x G: element (s, l, l', g) at s + S*(l + L*(l' + L*g))
-    int form;                 // FORM_*.  Slope: P_ll' = (2 wt - 4 (a_l - a_l')^2 wt^2) rho(a_l, a_l') beta, wt = 1 / tyLS^2; no kw
-                              // Outcome: P_ll' = rho(a_l, a_l') beta; no kw
 };
 void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st);
 
@@ -297,7 +292,7 @@ void launch_backsolve(const BackArgs& a, int nbatch, hipStream_t st);
 
 struct IteMeanArgs : SampleGrid {
     long long S;
-    int L; const double* doT;
+    LevelSet lv;           // scalar levels; the forms without fp32 kernels run in fp64 whatever f32 says
     const double* alpha;   // [b][Np]
     const double* Y;       // right-hand side alpha solves for: A alpha = Y (sample s at Y + s*y_sstride)
     long long y_sstride;
@@ -305,24 +300,18 @@ struct IteMeanArgs : SampleGrid {
     double* meanITE;       // element (i, s, l) at i*si + s*ss + l*sl
     long long si, ss, sl;
     int f32;
-    const double* doT_base;   // form == FORM_CONTRAST (fp64 only): MeanITE_i(l) = sum_j B_ij (r^a_j - r^b_j) alpha_j for the pair
-                              // (a, b) = (doT[l], doT_base[l])
-    int form;                 // FORM_*.  Slope (fp64 only): MeanITE_i(l) = sum_j B_ij q^a_j alpha_j
-                              // Outcome (fp64 only): MeanITE_i(l) = sum_j B_ij r^a_j alpha_j, no K alpha term
 };
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st);
 
 // vector levels (per-individual interventions, k_vec.hip): the level sums and MeanITE as passes over the pairs
 struct VecArgs : SampleGrid {
-    int L;
-    const double* doT;     // n x L: d_l[i] at doT[i + n*l]
     // launch_vec_sums: c_l into row 1 + l of the augmented tiles of M, 1' Delta_l 1 into sumdelta [b][L] (part: [b][L][nt])
     TRef M; double* part; double* sumdelta;
+    LevelSet lv;           // d_l[i] at lv.doT[i + n*l].  KEEP IT HERE: first or last in the struct the ordinary mean kernels (LB = 4 | 8) take
+                           // 70 | 88 VGPRs, not 56 | 72, and lose one | two waves per SIMD: their argument loads regroup (profiles/level_form.md)
     // launch_vec_mean: alpha [b][Np] solves (K + yNoise I) alpha = Y; element (i, s, l) at meanITE[i*si + s*ss + l*sl]
     const double* alpha; const double* Y; long long y_sstride;
     double* meanITE; long long si, ss, sl;
-    int form;              // FORM_ORDINARY or FORM_OUTCOME: c_j = sum_i B_ij g_ji, 1' Delta 1 = sum_ij B_ij h_ij and
-                           // MeanITE_i = sum_j B_ij g_ji alpha_j, no e_ij, no K alpha term, no exact-zero rule
 };
 void launch_vec_sums(const VecArgs& a, int nbatch, hipStream_t st);
 void launch_vec_mean(const VecArgs& a, int nbatch, hipStream_t st);
@@ -334,16 +323,11 @@ void launch_process_cov(const double* in, long long n, double scale, double nois
 
 // unit B (full ITE covariance) helpers
 struct DtArgs : SampleGrid {
-    const double* doT;     // device: intervention levels; batch element b = (sample s0 + b / lc, level l0 + b % lc)
+    LevelSet lv;           // batch element b = (sample s0 + b / lc, level l0 + b % lc); with lv.vec g_ij / g_ji / h_ij per pair
     int l0, lc;
-    int vec;               // vector levels: doT is n x L (level l at doT + n*l), g_ij / g_ji / h_ij per pair
     double pred_noise;
     TRef W;    // nt x nt rectangular: receives D (rows = i, cols = j), D_ij = B_ij (r_j - e_ij)
     TRef Cm;   // lower packed nt: receives Delta + pred_noise*I (identity on the padding)
-    const double* doT_base;   // form == FORM_CONTRAST (scalar levels only): D_ij = B_ij (r^a_j - r^b_j) and
-                              // Delta_ij = B_ij ((1 - rho) + (1 - rho)) for the pair (doT[l], doT_base[l])
-    int form;                 // FORM_*.  Slope (scalar levels only): D_ij = B_ij q^a_j and Delta_ij = B_ij 2 / tyLS^2
-                              // Outcome: D_ij = B_ij r^a_j and Delta_ij = B_ij; with vec D_ij = B_ij g_ji and Delta_ij = B_ij h_ij
 };
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st);
 

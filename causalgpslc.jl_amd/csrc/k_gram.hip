@@ -4,9 +4,8 @@
 //                      src/likelihood.jl:24-32; src/model_likelihood.jl:83-120), lower tiles only,
 //                      fused with the per-tile partial column sums of B = yScale*exp(Lu+Lx) and
 //                      K = B.*E that the SATE path needs.
-//   rhs_prepare/tiles  column sums -> augmented right-hand sides [Y, c(1..L)] and sum(Delta).  CON: the contrast form of
-//                      both (level l = the pair (doT[l], doT_base[l])).  SLP: the slope form (§15).  OUT: the outcome form (§16).
-//                      FORM is RhsArgs::form; CON / SLP / OUT name its special values inside the kernels.
+//   rhs_prepare/tiles  column sums -> augmented right-hand sides [Y, c(1..L)] and sum(Delta), per level form (FORM is
+//                      RhsArgs::lv.form; level_form.h holds what each form multiplies in).
 //   rhs_w_prepare      the level sums of weighted effects: G weight columns x L levels from bw = B w, kw = K w (k_wsum.hip,
 //                      DESIGN.md §13); rhs_tiles writes their rows.
 //   epilogue           Schur complement of the augmented block -> MeanSATE, VarSATE (plain or weighted), logdet, quad.
@@ -238,15 +237,12 @@ void launch_gram(const GramArgs& g, int nbatch, hipStream_t st) {
 // ---------------------------------------------------------------------------------------
 // rhs_prepare: per sample, reduce the per-tile partial sums in a fixed order, form the totals and
 // sum(Delta_l) = sum K - 2 r.bsum + sum B for every level.  One workgroup per sample.
-// CON (contrast of the levels a = doT[l] and b = doT_base[l]): the prior block Kss_aa - Kss_ab - Kss_ba + Kss_bb is
-// B ((1 - rho) + (1 - rho)) with rho = exp(-(a - b)^2 / tyLS^2), so sum(Delta_l) = ((1 - rho) + (1 - rho)) sum B: no sum
-// over the columns, and exactly 0.0 when a == b.
-// SLP (slope at a = doT[l]): the prior block is B 2 / tyLS^2 for every level, so sum(Delta_l) = (2 / tyLS^2) sum B.
-// OUT (outcome at a = doT[l]): the prior block is B itself, so sum(Delta_l) = sum B.
+// The forms without a factual term (level_form.h): Delta_l = prior B, so sum(Delta_l) = prior sum B — no sum over the columns,
+// one level per thread.
 // ---------------------------------------------------------------------------------------
 template <int FORM>
 __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
+    using LF = LevelForm<FORM>;
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -270,23 +266,16 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
     const double ktot = block_sum_256(tk, red);
     const double tl = a.tyLS[s];
     const double wt = 1.0 / (tl * tl);
-    if (CON) {
-        for (int l = tid; l < a.L; l += 256) {
-            const double rho = gp_rho(a.doT[l], a.doT_base[l], wt);
-            a.sumdelta[(long long)b * a.L + l] = ((1.0 - rho) + (1.0 - rho)) * btot;
+    const int L = a.lv.L;
+    if constexpr (!LF::factual) {
+        for (int l = tid; l < L; l += 256) {
+            const double rho = LF::paired ? gp_rho(a.lv.doT[l], a.lv.base[l], wt) : 0.0;
+            a.sumdelta[(long long)b * L + l] = LF::prior(rho, wt) * btot;
         }
         return;
     }
-    if (SLP) {
-        for (int l = tid; l < a.L; l += 256) a.sumdelta[(long long)b * a.L + l] = (2.0 * wt) * btot;
-        return;
-    }
-    if (OUT) {
-        for (int l = tid; l < a.L; l += 256) a.sumdelta[(long long)b * a.L + l] = btot;
-        return;
-    }
-    for (int l = 0; l < a.L; ++l) {
-        const double dot = a.doT[l];
+    for (int l = 0; l < L; ++l) {
+        const double dot = a.lv.doT[l];
         double acc = 0.0;
         for (int j = tid; j < Np; j += 256) {
             // same thread -> j assignment and the same tree as btot, so r == 1 reproduces btot bit for bit
@@ -294,24 +283,22 @@ __global__ __launch_bounds__(256) void rhs_prepare_kernel(RhsArgs a) {
             acc += r * bs[j];
         }
         const double rb = block_sum_256(acc, red);
-        if (tid == 0) a.sumdelta[(long long)b * a.L + l] = (ktot - 2.0 * rb) + btot;
+        if (tid == 0) a.sumdelta[(long long)b * L + l] = (ktot - 2.0 * rb) + btot;
     }
 }
 
 // rhs_tiles: write the augmented row tiles: row q of the augmented block is right-hand side q
-// (q = 0: Y, q = 1 + l + L*g: c_l = r_l .* bw_g - kw_g of column g), zero elsewhere; zero the aug x aug tiles.
-// CON: c_l = (r^a - r^b) .* bw_g for the pair (a, b) = (doT[l], doT_base[l]) — the e_ij of the ordinary level cancels, and
-// a == b gives r^a == r^b bit for bit: an exact zero row.  SLP: c_l = q^a .* bw_g, q^a_j = 2 (T_j - a) r^a_j / tyLS^2, no e_ij either.
-// OUT: c_l = r^a .* bw_g, the ordinary row without its - kw_g.
+// (q = 0: Y, q = 1 + l + L*g: c_l = cross_l .* bw_g of column g, - kw_g for the factual form), zero elsewhere; zero the
+// aug x aug tiles.  A contrast with a == b gives r^a == r^b bit for bit: an exact zero row.
 // grid (nt + naug, naug, batch): tile (nt + a, j) with j = blockIdx.x, a = blockIdx.y (j <= nt + a).
 template <int FORM>
 __device__ __forceinline__ double rhs_level_value(const RhsArgs& a, int l, int gj, double wt, const double* bs, const double* ks) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
-    const double r = gp_rho(a.T[gj], a.doT[l], wt);
-    if (OUT) return r * bs[gj];
-    if (SLP) return gp_slope_q(a.T[gj] - a.doT[l], r, wt) * bs[gj];
-    if (CON) return (r - gp_rho(a.T[gj], a.doT_base[l], wt)) * bs[gj];
-    return r * bs[gj] - ks[gj];
+    using LF = LevelForm<FORM>;
+    const double r = gp_rho(a.T[gj], a.lv.doT[l], wt);
+    const double rb = LF::paired ? gp_rho(a.T[gj], a.lv.base[l], wt) : 0.0;
+    const double x = LF::cross(a.T[gj] - a.lv.doT[l], r, rb, wt);
+    if constexpr (LF::factual) return x * bs[gj] - ks[gj];
+    else return x * bs[gj];
 }
 template <int FORM>
 __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
@@ -326,7 +313,7 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
         return;
     }
     const int Np = a.nt * GP_TS;
-    const int R = a.L * a.G;
+    const int L = a.lv.L, R = L * a.G;
     const double tl = a.tyLS[s];
     const double wt = 1.0 / (tl * tl);
     // element (row q, col c) at c*128 + q; thread -> consecutive q for coalescing.
@@ -344,7 +331,7 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
         if (gj < a.n) {
             if (gq == 0) v = a.Y[s * a.y_sstride + gj];
             else if (gq <= R) {
-                const int g = a.G > 1 ? (gq - 1) / a.L : 0, l = gq - 1 - a.L * g;
+                const int g = a.G > 1 ? (gq - 1) / L : 0, l = gq - 1 - L * g;
                 const long long o = ((long long)b * a.G + g) * Np;
                 v = rhs_level_value<FORM>(a, l, gj, wt, a.bw + o, a.kw + o);
             }
@@ -356,33 +343,31 @@ __global__ __launch_bounds__(256) void rhs_tiles_kernel(RhsArgs a) {
 // ---------------------------------------------------------------------------------------
 // Weighted effects tau_w = w' ITE: G weight columns, right-hand side q = 1 + l + L*g is level l of column g.
 // With bw = B w, kw = K w from launch_wsum (B, K symmetric):
-//   c = D' w,  c_j = r_j bw_j - kw_j            w' Delta w = sum_j w_j ((kw_j - 2 r_j bw_j) + bw_j)
-//   CON: c_j = (r^a_j - r^b_j) bw_j             w' Delta w = ((1 - rho) + (1 - rho)) sum_j w_j bw_j
-//   SLP: c_j = q^a_j bw_j                       w' Delta w = (2 / tyLS^2) sum_j w_j bw_j
-//   OUT: c_j = r^a_j bw_j                       w' Delta w = sum_j w_j bw_j  (= beta of k_curve.hip)
+//   factual:      c = D' w,  c_j = r_j bw_j - kw_j    w' Delta w = sum_j w_j ((kw_j - 2 r_j bw_j) + bw_j)
+//   the others:   c_j = cross_j bw_j                  w' Delta w = prior sum_j w_j bw_j  (the sum is beta of k_curve.hip)
 // rhs_w_prepare: one workgroup per (right-hand side, sample): sumdelta[b][l + L*g], and (l == 0) wnorm2[b][g] = w_g . w_g;
 // the sums run over the threads' strided j in a fixed tree.  r == 1 (every T equal to doT) and kw == bw give an exact 0.0
 // term by term; a == b gives rho == 1 and 0.0 * sum.
 // ---------------------------------------------------------------------------------------
 template <int FORM>
 __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
+    using LF = LevelForm<FORM>;
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int qq = blockIdx.x, b = blockIdx.y;
-    const int l = qq % a.L, g = qq / a.L;
+    const int L = a.lv.L, l = qq % L, g = qq / L;
     const long long s = a.s0 + b;
     const int Np = a.nt * GP_TS;
     const double* bs = a.bw + ((long long)b * a.G + g) * Np;
     const double* ks = a.kw + ((long long)b * a.G + g) * Np;
     const double tl = a.tyLS[s];
     const double wt = 1.0 / (tl * tl);
-    const double dot = a.doT[l];
+    const double dot = a.lv.doT[l];
     double acc = 0.0, ww = 0.0;
     for (int j = tid; j < a.n; j += 256) {
         const double w = a.W[(long long)j * a.G + g];
         ww = fma(w, w, ww);
-        if (CON || SLP || OUT) {
+        if constexpr (!LF::factual) {
             acc += w * bs[j];
         } else {
             const double r = gp_rho(a.T[j], dot, wt);
@@ -395,28 +380,20 @@ __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
         if (tid == 0) a.wnorm2[(long long)b * a.G + g] = w2;
     }
     if (tid != 0) return;
-    if (CON) {
-        const double rho = gp_rho(dot, a.doT_base[l], wt);
-        a.sumdelta[(long long)b * a.L * a.G + qq] = ((1.0 - rho) + (1.0 - rho)) * tot;
-    } else if (SLP) {
-        a.sumdelta[(long long)b * a.L * a.G + qq] = (2.0 * wt) * tot;
-    } else {
-        a.sumdelta[(long long)b * a.L * a.G + qq] = tot;
-    }
+    const double rho = LF::paired ? gp_rho(dot, a.lv.base[l], wt) : 0.0;
+    if constexpr (LF::factual) a.sumdelta[(long long)b * L * a.G + qq] = tot;
+    else a.sumdelta[(long long)b * L * a.G + qq] = LF::prior(rho, wt) * tot;
 }
 
 // the plain and the weighted prepare kernels reduce in different orders (both are part of the results); the tiles are one kernel
 template <int FORM>
 static void launch_rhs_t(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.W) hipLaunchKernelGGL(rhs_w_prepare_kernel<FORM>, dim3(r.L * r.G, nbatch), dim3(256), 0, st, r);
+    if (r.W) hipLaunchKernelGGL(rhs_w_prepare_kernel<FORM>, dim3(r.lv.L * r.G, nbatch), dim3(256), 0, st, r);
     else if (r.with_sums) hipLaunchKernelGGL(rhs_prepare_kernel<FORM>, dim3(nbatch), dim3(256), 0, st, r);
     hipLaunchKernelGGL(rhs_tiles_kernel<FORM>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
 }
 void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.form == FORM_OUTCOME) launch_rhs_t<FORM_OUTCOME>(r, nbatch, st);
-    else if (r.form == FORM_SLOPE) launch_rhs_t<FORM_SLOPE>(r, nbatch, st);
-    else if (r.form == FORM_CONTRAST) launch_rhs_t<FORM_CONTRAST>(r, nbatch, st);
-    else launch_rhs_t<FORM_ORDINARY>(r, nbatch, st);
+    dispatch_form(r.lv.form, [&](auto form) { launch_rhs_t<decltype(form)::value>(r, nbatch, st); });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@
 #include "gp_math.h"
 #include "back_block.h"
 #include "pair_mfma.h"
+#include <stdexcept>
 
 // ---------------------------------------------------------------------------------------
 // Back-substitution L^T alpha = z, right-looking over tile rows i = nt-1 .. 0, two launches per row:
@@ -73,19 +74,13 @@ void launch_backsolve(const BackArgs& a, int nbatch, hipStream_t st) {
 // (T_i - T_j)^2 are then the same square, so Ks'_ij == K_ij bit for bit): the reference returns an exact 0.0 for such an
 // instance (test/estimation.jl:6-66 is the n = 1 case) and so does this kernel.
 // One workgroup per (row block, sample); levels are processed LCT at a time.
-// CON (contrast of the levels a = doT[l] and b = doT_base[l]): D = Ks_a' - Ks_b', the K of the ordinary level
-// cancels, so  MeanITE_i(l) = sum_j B_ij ((r^a_j - r^b_j) alpha_j)  with no K alpha term; a == b stages exact zeros (r^a == r^b
-// bit for bit) and every row returns 0.0.  Only what is staged per column block and the epilogue differ: the pair loop is
-// the same code.
-// SLP (slope at a = doT[l]): D_ij = B_ij q^a_j with q^a_j = 2 (T_j - a) r^a_j / tyLS^2, so
-// MeanITE_i(l) = sum_j B_ij (q^a_j alpha_j): no K alpha term as for CON, and no level gives an exact-zero row.
-// OUT (outcome at a = doT[l]): D_ij = B_ij r^a_j, so MeanITE_i(l) = sum_j B_ij (r^a_j alpha_j): what the ordinary
-// form stages, stored without the K alpha term and without the exact-zero rule.
-// FORM is IteMeanArgs::form; CON / SLP / OUT name its special values inside the kernels.
+// The level forms (FORM is IteMeanArgs::lv.form, level_form.h) differ in what is staged per column block, cross_j(l) alpha_j, and
+// in the store: only the factual form has the K alpha term and the T_i == doT rule; a level that is zero by its form (a contrast
+// with a == b stages exact zeros: r^a == r^b bit for bit) is stored as 0.0.  The pair loop is the same code.
 // ---------------------------------------------------------------------------------------
 template <int FREG, int LCT, typename RT, int RB, int FORM = FORM_ORDINARY>
 __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
+    using LF = LevelForm<FORM>;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
     double* etab = sm;                     // [32] 2^(j/32): table-driven exp (gp_math.h)
@@ -114,8 +109,10 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
     gp_exp_tab_stage(etab, tid);
     const double* alpha = a.alpha + b * Np;
 
-    for (int l0 = 0; l0 < a.L; l0 += LCT) {
-        const int nl = min(LCT, a.L - l0);
+    const int L = a.lv.L;
+    const double* doT = a.lv.doT;
+    for (int l0 = 0; l0 < L; l0 += LCT) {
+        const int nl = min(LCT, L - l0);
         double acc[RB][LCT];
 #pragma unroll
         for (int q = 0; q < RB; ++q)
@@ -130,16 +127,10 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
                 double v = 0.0;
                 if (ll < nl && g < n) {
                     // the difference in fp64, then ONE rounding (fp32 mode): its error does not grow with |T|
-                    const RT dt = (RT)(a.T[g] - a.doT[l0 + ll]);
-                    if (CON) {
-                        const RT db = (RT)(a.T[g] - a.doT_base[l0 + ll]);
-                        v = ((double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab) -
-                             (double)RbfMath<RT>::exp_neg_t(-((db * db) * wtq), etab)) * alpha[g];
-                    } else if (SLP) {
-                        v = gp_slope_q(a.T[g] - a.doT[l0 + ll], (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab), wt) * alpha[g];
-                    } else {
-                        v = (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab) * alpha[g];
-                    }
+                    const double dt64 = a.T[g] - doT[l0 + ll];
+                    const RT dt = (RT)dt64, db = LF::paired ? (RT)(a.T[g] - a.lv.base[l0 + ll]) : (RT)0;
+                    const double rb = LF::paired ? (double)RbfMath<RT>::exp_neg_t(-((db * db) * wtq), etab) : 0.0;
+                    v = LF::cross(dt64, (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab), rb, wt) * alpha[g];
                 }
                 rl[idx] = v;
             }
@@ -179,13 +170,13 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 #pragma unroll
             for (int q = 0; q < RB; ++q) {
                 if (gi[q] >= n) continue;
-                if (CON || SLP || OUT) {
+                if constexpr (!LF::factual) {
 #pragma unroll
                     for (int ll = 0; ll < LCT; ++ll)
                         if (ll < nl) {
                             const double v = acc[q][ll] + red[(q * GP_TS + r) * LCT + ll];
                             a.meanITE[(long long)gi[q] * a.si + s * a.ss + (long long)(l0 + ll) * a.sl] =
-                                (CON && a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : v;
+                                (LF::paired && LF::zero_level(doT[l0 + ll], a.lv.base[l0 + ll])) ? 0.0 : v;
                         }
                     continue;
                 }
@@ -197,7 +188,7 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
                     if (ll < nl) {
                         const double v = (acc[q][ll] + red[(q * GP_TS + r) * LCT + ll]) - ka;
                         a.meanITE[(long long)gi[q] * a.si + s * a.ss + (long long)(l0 + ll) * a.sl] =
-                            (ti == a.doT[l0 + ll]) ? 0.0 : v;
+                            (ti == doT[l0 + ll]) ? 0.0 : v;
                     }
             }
         }
@@ -212,42 +203,38 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 // The product is the pair-product body this kernel shares with wsum_mfma_kernel (pair_mfma.h: no operand tile of B goes
 // through LDS, each lane computes its own B_rc, R is staged per 64-column chunk, fixed summation order, and why the FREG
 // rung that serves an F cannot change a bit).  This kernel supplies the two things the body asks of a caller:
-//   - what is staged: R[j, l] = r_j(l) alpha_j; CON (contrasts as in ite_mean_kernel): (r^a_j - r^b_j) alpha_j;
+//   - what is staged: R[j, l] = cross_j(l) alpha_j of the level form (level_form.h), r_j(l) alpha_j for the ordinary one;
 //   - the store, per 16-row sub-tile: rows i < n only, (K alpha)_i and T_i loaded once; instances with T_i == doT_l get the
-//     reference's exact 0.0 (row i of Ks' - K is identically zero there).  CON: no K alpha term, 0.0 for a level with a == b.
-//     SLP: q^a_j alpha_j is staged, no K alpha term and no exact-zero case.  OUT: the ordinary staging, no K alpha term and
-//     no exact-zero case.
+//     reference's exact 0.0 (row i of Ks' - K is identically zero there).  Without a factual term: no K alpha term, and 0.0
+//     only for a level that is zero by its form, as in ite_mean_kernel.
 // ---------------------------------------------------------------------------------------
 template <int FREG, int FORM = FORM_ORDINARY>   // FREG > 0: this lane's two rows' features live in registers (F <= FREG); 0: read from LDS
 __global__ __launch_bounds__(256, 2) void ite_mean_mfma_kernel(IteMeanArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const long long b = blockIdx.y, s = a.s0 + b;
     const double* alpha = a.alpha + b * (a.nt * GP_TS);
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
+    using LF = LevelForm<FORM>;
+    const double* doT = a.lv.doT;
     pair_mfma_body<FREG, false, 0>(
-        a, s, a.L, sm,
+        a, s, a.lv.L, sm,
         [&](int j, int l, double wt, const double* etab) {
-            const double dt = a.T[j] - a.doT[l];
-            if (CON) {
-                const double db = a.T[j] - a.doT_base[l];
-                return (gp_exp_neg_tab(-((dt * dt) * wt), etab) - gp_exp_neg_tab(-((db * db) * wt), etab)) * alpha[j];
-            }
-            if (SLP) return gp_slope_q(dt, gp_exp_neg_tab(-((dt * dt) * wt), etab), wt) * alpha[j];
-            return gp_exp_neg_tab(-((dt * dt) * wt), etab) * alpha[j];
+            const double dt = a.T[j] - doT[l], db = LF::paired ? a.T[j] - a.lv.base[l] : 0.0;
+            const double rb = LF::paired ? gp_exp_neg_tab(-((db * db) * wt), etab) : 0.0;
+            return LF::cross(dt, gp_exp_neg_tab(-((dt * dt) * wt), etab), rb, wt) * alpha[j];
         },
         [&](int gi, int l0, int nl, const d4* acc, const d4*) {
             if (gi >= a.n) return;
             double* out = a.meanITE + (long long)gi * a.si + s * a.ss;
-            if (CON || SLP || OUT) {
+            if constexpr (!LF::factual) {
                 pair_mfma_each_column(nl, [&](int q, int v, int ll) {
-                    out[(long long)(l0 + ll) * a.sl] = (CON && a.doT[l0 + ll] == a.doT_base[l0 + ll]) ? 0.0 : acc[q][v];
+                    out[(long long)(l0 + ll) * a.sl] = (LF::paired && LF::zero_level(doT[l0 + ll], a.lv.base[l0 + ll])) ? 0.0 : acc[q][v];
                 });
                 return;
             }
             const double ka = a.Y[s * a.y_sstride + gi] - a.yNoise[s] * alpha[gi];     // (K alpha)_i from A alpha = Y
             const double ti = a.T[gi];
             pair_mfma_each_column(nl, [&](int q, int v, int ll) {
-                out[(long long)(l0 + ll) * a.sl] = (ti == a.doT[l0 + ll]) ? 0.0 : acc[q][v] - ka;
+                out[(long long)(l0 + ll) * a.sl] = (ti == doT[l0 + ll]) ? 0.0 : acc[q][v] - ka;
             });
         });
 }
@@ -270,11 +257,12 @@ static void launch_ite_mean_t(const IteMeanArgs& a, int nbatch, hipStream_t st) 
 }
 template <int FREG, typename RT, int FORM>
 static void launch_ite_mean_f(const IteMeanArgs& a, int nbatch, hipStream_t st) {
-    if (a.L <= 1) launch_ite_mean_t<FREG, 1, RT, FORM>(a, nbatch, st);
-    else if (a.L <= 4) launch_ite_mean_t<FREG, 4, RT, FORM>(a, nbatch, st);
-    else if (FORM == FORM_ORDINARY) launch_ite_mean_t<FREG, 16, RT, FORM_ORDINARY>(a, nbatch, st);     // contrasts, slopes, outcomes (fp64): L > 4 is the MFMA kernel's
+    if (a.lv.L <= 1) launch_ite_mean_t<FREG, 1, RT, FORM>(a, nbatch, st);
+    else if (a.lv.L <= 4) launch_ite_mean_t<FREG, 4, RT, FORM>(a, nbatch, st);
+    // L > 4 reaches this VALU ladder in the fp32 mode only (fp64: the MFMA kernel, launch_ite_mean), so only the forms with it get the rung
+    else if constexpr (LevelForm<FORM>::fp32_kernels) launch_ite_mean_t<FREG, 16, RT, FORM>(a, nbatch, st);
 }
-template <typename RT, int FORM = FORM_ORDINARY>
+template <typename RT, int FORM>
 static void launch_ite_mean_r(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     const int F = a.nU + a.nX;
     // exact register counts for the common feature widths: the pass is fp64-VALU bound (2 instructions per
@@ -289,20 +277,17 @@ static void launch_ite_mean_r(const IteMeanArgs& a, int nbatch, hipStream_t st) 
     else if (F <= 20) launch_ite_mean_f<20, RT, FORM>(a, nbatch, st);
     else launch_ite_mean_f<32, RT, FORM>(a, nbatch, st);
 }
-// contrasts, slopes and outcomes: fp64 contexts only (the entry points refuse the fp32 kernel mode)
-template <int FORM>
-static void launch_ite_mean_f64(const IteMeanArgs& a, int nbatch, hipStream_t st) {
-    if (a.L > 4) launch_ite_mean_mfma<FORM>(a, nbatch, st);
-    else launch_ite_mean_r<double, FORM>(a, nbatch, st);
-}
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
-    if (a.form == FORM_CONTRAST) { launch_ite_mean_f64<FORM_CONTRAST>(a, nbatch, st); return; }
-    if (a.form == FORM_SLOPE) { launch_ite_mean_f64<FORM_SLOPE>(a, nbatch, st); return; }
-    if (a.form == FORM_OUTCOME) { launch_ite_mean_f64<FORM_OUTCOME>(a, nbatch, st); return; }
-    // many levels: the (B R) product belongs on the matrix cores (fp64 path; the fp32 mode keeps the VALU kernel)
-    if (!a.f32 && a.L > 4) { launch_ite_mean_mfma<FORM_ORDINARY>(a, nbatch, st); return; }
-    if (a.f32) launch_ite_mean_r<float>(a, nbatch, st);
-    else launch_ite_mean_r<double>(a, nbatch, st);
+    dispatch_form(a.lv.form, [&](auto form) {
+        constexpr int FORM = decltype(form)::value;
+        // the fp32 mode keeps the VALU kernel for every L; the forms without it (the entry points refuse the mode) run in fp64
+        if constexpr (LevelForm<FORM>::fp32_kernels) {
+            if (a.f32) { launch_ite_mean_r<float, FORM>(a, nbatch, st); return; }
+        }
+        // many levels: the (B R) product belongs on the matrix cores
+        if (a.lv.L > 4) launch_ite_mean_mfma<FORM>(a, nbatch, st);
+        else launch_ite_mean_r<double, FORM>(a, nbatch, st);
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -403,51 +388,38 @@ __device__ __forceinline__ void tile_build_body(const SampleGrid& a, long long s
 // rectangular matrix W and Delta + pred_noise*I (Delta_ij = B_ij (e_ij - r_i - r_j + 1) =
 // CovWW - CovWWs - CovWWs' + CovWsWs, src/likelihood.jl:46-49 / estimation.jl:47, :82) into Cm, with the identity on the padding.
 // VEC (per-individual intervention d, k_vec.hip): D_ij = B_ij (g_ji - e_ij), Delta_ij = B_ij (e_ij - g_ij - g_ji + h_ij).
-// CON (contrast of the scalar levels a = doT[l], b = doT_base[l]): D_ij = B_ij (r^a_j - r^b_j) (rc_ holds the
-// difference) and Delta_ij = B_ij ((1 - rho) + (1 - rho)), rho = exp(-(a - b)^2 / tyLS^2) — exactly 0 when a == b.
-// SLP (slope at the scalar level a = doT[l]): D_ij = B_ij q^a_j (rc_ holds q^a) and Delta_ij = B_ij 2 / tyLS^2.
-// OUT (outcome): at the scalar level a = doT[l], D_ij = B_ij r^a_j (rc_ holds r^a) and Delta_ij = B_ij; with VEC
-// D_ij = B_ij g_ji and Delta_ij = B_ij h_ij.
-// FORM is DtArgs::form (FORM_ORDINARY or FORM_OUTCOME with VEC).
+// Without a factual term (FORM is DtArgs::lv.form, level_form.h): at a scalar level D_ij = B_ij cross_j (rc_ holds cross) and
+// Delta_ij = B_ij prior — exactly 0 for a contrast with a == b; with VEC D_ij = B_ij g_ji and Delta_ij = B_ij h_ij.
 // ---------------------------------------------------------------------------------------
 template <bool VEC, int FORM = FORM_ORDINARY>
 __global__ __launch_bounds__(256) void dt_build_kernel(DtArgs a) {
-    constexpr bool CON = FORM == FORM_CONTRAST, SLP = FORM == FORM_SLOPE, OUT = FORM == FORM_OUTCOME;
-    constexpr bool NOLV = CON || SLP || (OUT && !VEC);      // the column block's staged values are all an element needs
+    using LF = LevelForm<FORM>;
+    constexpr bool NOLV = !LF::factual && !VEC;      // the column block's staged values are all an element needs
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int ti = blockIdx.x / a.nt, tj = blockIdx.x % a.nt;
     const long long b = blockIdx.y, s = a.s0 + b / a.lc;       // batch element = (sample, level) pair
     const int l = a.l0 + (int)(b % a.lc), n = a.n;
-    const double doT = VEC ? 0.0 : a.doT[l], doTb = CON ? a.doT_base[l] : 0.0;
-    const double* dv = VEC ? a.doT + (long long)n * l : nullptr;
-    double kss = 0.0;       // CON: (1 - rho) + (1 - rho); SLP: 2 / tyLS^2 (OUT: 1, not multiplied)
-    if (CON) {
+    const double doT = VEC ? 0.0 : a.lv.doT[l], doTb = LF::paired ? a.lv.base[l] : 0.0;
+    const double* dv = VEC ? a.lv.doT + (long long)n * l : nullptr;
+    double kss = 0.0;       // Delta_ij = B_ij kss
+    if constexpr (NOLV) {
         const double tl = a.p.tyLS[s];
-        const double rho = gp_rho(doT, doTb, 1.0 / (tl * tl));
-        kss = (1.0 - rho) + (1.0 - rho);
-    }
-    if (SLP) {
-        const double tl = a.p.tyLS[s];
-        kss = 2.0 * (1.0 / (tl * tl));
+        const double wt = 1.0 / (tl * tl);
+        kss = LF::prior(LF::paired ? gp_rho(doT, doTb, wt) : 0.0, wt);
     }
     double* wt_tile = tref_tile(a.W, b, ti, tj);
     double* c_tile = (ti >= tj) ? tref_tile(a.Cm, b, ti, tj) : nullptr;
-    tile_build_body<NOLV ? LEVEL_NONE : (VEC && OUT) ? LEVEL_VECTOR_OUTCOME : VEC ? LEVEL_VECTOR : LEVEL_SCALAR>(
+    tile_build_body<NOLV ? LEVEL_NONE : !VEC ? LEVEL_SCALAR : LF::factual ? LEVEL_VECTOR : LEVEL_VECTOR_OUTCOME>(
         a, s, ti, tj, sm,
         [&](int g, double t, double wt) {
             if constexpr (VEC) return g < n ? dv[g] : 0.0;
-            else if constexpr (CON) return gp_rho(t, doT, wt) - gp_rho(t, doTb, wt);
-            else if constexpr (SLP) return gp_slope_q(t - doT, gp_rho(t, doT, wt), wt);
-            else return gp_rho(t, doT, wt);
+            else return LF::cross(t - doT, gp_rho(t, doT, wt), LF::paired ? gp_rho(t, doTb, wt) : 0.0, wt);
         },
         [&](int rp, int cq, bool inside, bool diag, double Bv, const LevelTerms& t) {
             double Dv, Cv;
-            if (OUT) {
+            if constexpr (!LF::factual) {
                 Dv = Bv * t.gji;
-                Cv = VEC ? Bv * t.h : Bv;
-            } else if (CON || SLP) {
-                Dv = Bv * t.gji;
-                Cv = Bv * kss;
+                Cv = VEC ? Bv * t.h : Bv * kss;
             } else {
                 Dv = Bv * (t.gji - t.e);
                 Cv = Bv * (((t.e - t.gij) - t.gji) + t.h);
@@ -466,14 +438,12 @@ static void launch_dt_build_t(const DtArgs& a, int nbatch, hipStream_t st) {
     hipLaunchKernelGGL((dt_build_kernel<VEC, FORM>), dim3(a.nt * a.nt, nbatch), dim3(256), tile_build_lds_bytes(a.nU + a.nX), st, a);
 }
 void launch_dt_build(const DtArgs& a, int nbatch, hipStream_t st) {
-    if (a.form == FORM_OUTCOME) {
-        if (a.vec) launch_dt_build_t<true, FORM_OUTCOME>(a, nbatch, st);
-        else launch_dt_build_t<false, FORM_OUTCOME>(a, nbatch, st);
-    }
-    else if (a.form == FORM_SLOPE) launch_dt_build_t<false, FORM_SLOPE>(a, nbatch, st);
-    else if (a.form == FORM_CONTRAST) launch_dt_build_t<false, FORM_CONTRAST>(a, nbatch, st);
-    else if (a.vec) launch_dt_build_t<true>(a, nbatch, st);
-    else launch_dt_build_t<false>(a, nbatch, st);
+    dispatch_form(a.lv.form, [&](auto form) {
+        constexpr int FORM = decltype(form)::value;
+        if (!a.lv.vec) launch_dt_build_t<false, FORM>(a, nbatch, st);
+        else if constexpr (LevelForm<FORM>::vector_levels) launch_dt_build_t<true, FORM>(a, nbatch, st);
+        else throw std::logic_error("this level form has no vector-level kernels");     // run_predict refuses the call
+    });
 }
 
 // CovITEs[s + S*(i + n*j)] (src/estimation.jl:75, :82 layout: sample index fastest), both triangles

@@ -23,8 +23,8 @@
 // If d == T everywhere, g == e and h == e bit for bit (the same squares into the same exp), so c, Delta and MeanITE are
 // exact zeros.
 //
-// FORM (VecArgs::form) is FORM_ORDINARY, all of the above, or FORM_OUTCOME (OUT inside the kernel): the potential
-// outcome f_i(d_i) itself, the ordinary form with its factual terms dropped —
+// FORM (VecArgs::lv.form) is one of the forms with vector levels (level_form.h): the ordinary form, all of the above, or one
+// without a factual term — the potential outcome f_i(d_i) itself, the ordinary form with its factual terms dropped —
 //     D_ij = B_ij g_ji,    Delta_ij = B_ij h_ij
 //   sums   c_j = sum_i B_ij g_ji, and per tile of columns sum_j sum_i B_ij h_ij alone; no e is evaluated (two exps per pair
 //          and level, as before)
@@ -32,10 +32,11 @@
 // in the same reduction orders.
 #include "gpslc_internal.h"
 #include "gp_math.h"
+#include <stdexcept>
 
 template <int LB, bool SUMS, int FORM>
 __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
-    constexpr bool OUT = FORM == FORM_OUTCOME;
+    constexpr bool FACTUAL = LevelForm<FORM>::factual;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int F = a.nU + a.nX;
     double* etab = sm;                          // [32] 2^(j/32): table-driven exp (gp_math.h)
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
     const double to = own_in ? a.T[go] : 0.0;
     double dlo[LB];     // own d per level (levels beyond L repeat the last one; their results are not written)
 #pragma unroll
-    for (int ll = 0; ll < LB; ++ll) dlo[ll] = own_in ? a.doT[go + (long long)n * min(l0 + ll, a.L - 1)] : 0.0;
+    for (int ll = 0; ll < LB; ++ll) dlo[ll] = own_in ? a.lv.doT[go + (long long)n * min(l0 + ll, a.lv.L - 1)] : 0.0;
     double acc[LB], acc2[LB];
 #pragma unroll
     for (int ll = 0; ll < LB; ++ll) { acc[ll] = 0.0; acc2[ll] = 0.0; }
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
         if (SUMS) {
             for (int idx = tid; idx < LB * GP_TS; idx += 256) {
                 const int ll = idx >> 7, r = idx & 127;
-                xk[idx] = k0 + r < n ? a.doT[k0 + r + (long long)n * min(l0 + ll, a.L - 1)] : 0.0;
+                xk[idx] = k0 + r < n ? a.lv.doT[k0 + r + (long long)n * min(l0 + ll, a.lv.L - 1)] : 0.0;
             }
         } else if (tid < GP_TS) {
             xk[tid] = k0 + tid < n ? alpha[k0 + tid] : 0.0;
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
             }
             const double Bv = ys * gp_exp_neg_tab(-lux, etab);
             const double tr = tk[r];
-            if (SUMS && OUT) {
+            if (SUMS && !FACTUAL) {
 #pragma unroll
                 for (int ll = 0; ll < LB; ++ll) {
                     const double dk = xk[ll * GP_TS + r];
@@ -131,10 +132,10 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
         }
     }
     __syncthreads();
-    const int nl = min(LB, a.L - l0);
+    const int nl = min(LB, a.lv.L - l0);
     if (!SUMS) {
         if (half == 1 || !own_in) return;
-        if (OUT) {
+        if (!FACTUAL) {
 #pragma unroll
             for (int ll = 0; ll < LB; ++ll)
                 if (ll < nl)
@@ -162,24 +163,24 @@ __global__ __launch_bounds__(256) void vec_pair_kernel(VecArgs a) {
             const double hs = acc2[ll] + red[(LB + ll) * GP_TS + o];
             const int q = 1 + l0 + ll;
             if (own_in && ll < nl) tref_tile(a.M, b, a.nt + (q >> 7), ot)[o * GP_TS + (q & 127)] = c;
-            if (own_in) v = OUT ? hs : hs - 2.0 * c;
+            if (own_in) v = FACTUAL ? hs - 2.0 * c : hs;
         }
 #pragma unroll
         for (int w = 32; w >= 1; w >>= 1) v += __shfl_xor(v, w, 64);
         if (lane == 0 && wave < 2) wsum[wave][ll] = v;
     }
     __syncthreads();
-    if (tid < nl) a.part[((long long)b * a.L + l0 + tid) * a.nt + ot] = wsum[0][tid] + wsum[1][tid];
+    if (tid < nl) a.part[((long long)b * a.lv.L + l0 + tid) * a.nt + ot] = wsum[0][tid] + wsum[1][tid];
 }
 
 // 1' Delta 1 of every (sample, level): the per-tile shares in tile order.  One workgroup per sample.
 __global__ __launch_bounds__(256) void vec_sumdelta_kernel(VecArgs a) {
     const long long b = blockIdx.x;
-    for (int l = threadIdx.x; l < a.L; l += 256) {
-        const double* p = a.part + ((long long)b * a.L + l) * a.nt;
+    for (int l = threadIdx.x; l < a.lv.L; l += 256) {
+        const double* p = a.part + ((long long)b * a.lv.L + l) * a.nt;
         double v = 0.0;
         for (int t = 0; t < a.nt; ++t) v += p[t];
-        a.sumdelta[b * a.L + l] = v;
+        a.sumdelta[b * a.lv.L + l] = v;
     }
 }
 
@@ -190,18 +191,21 @@ static void launch_vec_t(const VecArgs& a, int nbatch, hipStream_t st) {
     static DeviceOnce attr_set;
     lds_opt_in(attr_set, (const void*)vec_pair_kernel<LB, SUMS, FORM>,
                (GP_EXP_TAB_DOUBLES + 2 * MAXF * GP_TS + GP_TS + 3 * LB * GP_TS) * 8);
-    hipLaunchKernelGGL((vec_pair_kernel<LB, SUMS, FORM>), dim3(a.nt, (a.L + LB - 1) / LB, nbatch), dim3(256), bytes, st, a);
+    hipLaunchKernelGGL((vec_pair_kernel<LB, SUMS, FORM>), dim3(a.nt, (a.lv.L + LB - 1) / LB, nbatch), dim3(256), bytes, st, a);
 }
 template <bool SUMS, int FORM>
 static void launch_vec_f(const VecArgs& a, int nbatch, hipStream_t st) {
-    if (a.L <= 1) launch_vec_t<1, SUMS, FORM>(a, nbatch, st);
-    else if (a.L <= 4) launch_vec_t<4, SUMS, FORM>(a, nbatch, st);
+    if (a.lv.L <= 1) launch_vec_t<1, SUMS, FORM>(a, nbatch, st);
+    else if (a.lv.L <= 4) launch_vec_t<4, SUMS, FORM>(a, nbatch, st);
     else launch_vec_t<8, SUMS, FORM>(a, nbatch, st);
 }
 template <bool SUMS>
 static void launch_vec(const VecArgs& a, int nbatch, hipStream_t st) {
-    if (a.form == FORM_OUTCOME) launch_vec_f<SUMS, FORM_OUTCOME>(a, nbatch, st);
-    else launch_vec_f<SUMS, FORM_ORDINARY>(a, nbatch, st);
+    dispatch_form(a.lv.form, [&](auto form) {
+        constexpr int FORM = decltype(form)::value;
+        if constexpr (LevelForm<FORM>::vector_levels) launch_vec_f<SUMS, FORM>(a, nbatch, st);
+        else throw std::logic_error("this level form has no vector-level kernels");     // run_predict refuses the call
+    });
 }
 
 void launch_vec_sums(const VecArgs& a, int nbatch, hipStream_t st) {
