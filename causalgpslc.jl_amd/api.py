@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Optional, Sequence
 
 import numpy as np
@@ -68,35 +69,6 @@ def _baseline(baseline, L):
     raise ValueError(f"baseline must be a scalar or one value per level (L = {L}), got an array of shape {b.shape}")
 
 
-def _slope_refusals(slope, baseline, vec, devices):
-    """What ``slope=True`` (gpslc_predict_slope) cannot be combined with, refused before any device work."""
-    if not slope:
-        return
-    if baseline is not None:
-        raise ValueError("slope=True cannot be combined with baseline=: the slope is a derivative at one level, not a contrast")
-    if vec:
-        raise ValueError("slope=True needs scalar levels: slopes at per-individual intervention vectors are not supported")
-    if devices is not None:
-        raise ValueError("slope=True is not sharded over devices: call without devices=")
-
-
-def _outcome_refusals(outcome, baseline, slope, vec, weights, devices):
-    """What ``outcome=True`` (gpslc_predict_outcome / gpslc_predict_outcome_vec) cannot be combined with, refused before any
-    device work.  Vector levels are allowed; weights with them are not."""
-    if not outcome:
-        return
-    if baseline is not None:
-        raise ValueError("outcome=True cannot be combined with baseline=: the contrast is the difference of two outcomes, "
-                         "f(a) - f(b); ask for the contrast, or for the outcomes at a and at b")
-    if slope:
-        raise ValueError("outcome=True cannot be combined with slope=True: the outcome is a level of the surface, the slope its derivative")
-    if devices is not None:
-        raise ValueError("outcome=True is not sharded over devices: call without devices=")
-    if weights is not None and vec:
-        raise ValueError("outcome=True with weights= needs scalar levels: weighted outcomes at per-individual intervention "
-                         "vectors are not supported")
-
-
 def _weight_row(w, n):
     """One weight vector for n individuals -> (n,) float64.  Float (or integer) values are used as given; a Bool vector is a
     group mask and becomes that group's average, ``mask / mask.sum()`` (an empty mask raises ValueError)."""
@@ -141,6 +113,112 @@ def groupWeights(labels):
     W[inv, np.arange(lab.shape[0])] = 1.0
     W /= W.sum(axis=1, keepdims=True)
     return keys, W
+
+
+# What a level call cannot ask for, refused before any device work: (condition on the request, exception, message).  The first
+# row that fires is the call's complaint.  ``q.caller`` is "predict", "curve" (_predict_curve) or "distributions"
+# (_ite_distributions); ``q.vec``: per-individual levels; ``q.base`` / ``q.w`` / ``q.dev``: baseline= / weights= / devices= given.
+_REFUSALS = (
+    (lambda q: q.outcome and q.base, ValueError,
+     "outcome=True cannot be combined with baseline=: the contrast is the difference of two outcomes, "
+     "f(a) - f(b); ask for the contrast, or for the outcomes at a and at b"),
+    (lambda q: q.outcome and q.slope, ValueError,
+     "outcome=True cannot be combined with slope=True: the outcome is a level of the surface, the slope its derivative"),
+    (lambda q: q.outcome and q.dev, ValueError, "outcome=True is not sharded over devices: call without devices="),
+    (lambda q: q.outcome and q.w and q.vec and q.caller == "predict", ValueError,
+     "outcome=True with weights= needs scalar levels: weighted outcomes at per-individual intervention "
+     "vectors are not supported"),
+    (lambda q: q.slope and q.base, ValueError,
+     "slope=True cannot be combined with baseline=: the slope is a derivative at one level, not a contrast"),
+    (lambda q: q.slope and q.vec, ValueError,
+     "slope=True needs scalar levels: slopes at per-individual intervention vectors are not supported"),
+    (lambda q: q.slope and q.dev, ValueError, "slope=True is not sharded over devices: call without devices="),
+    (lambda q: q.caller == "curve" and q.vec, ValueError,
+     "an effect curve needs scalar levels: per-individual intervention vectors are not supported"),
+    (lambda q: q.caller == "curve" and q.dev, NotImplementedError,
+     "effect curves are not sharded over devices: call without devices="),
+    (lambda q: len(q.shape) > 2 or (q.vec and q.shape[1] != q.n), ValueError,
+     "doTs must be L scalar levels or an (L, n) array of intervention vectors with n = {n}, got an array of shape {shape}"),
+    (lambda q: q.vec and q.dev, NotImplementedError,
+     "vector interventions are not sharded over devices: call predict without devices="),
+    (lambda q: q.base and q.vec and q.caller == "predict", ValueError,
+     "baseline= needs scalar levels: contrasts of per-individual intervention vectors are not supported"),
+    (lambda q: q.base and q.vec and q.caller == "distributions", ValueError,
+     "baseline= needs a scalar doT: contrasts of per-individual intervention vectors are not supported"),
+    (lambda q: q.base and q.dev, NotImplementedError, "contrasts are not sharded over devices: call predict without devices="),
+    (lambda q: q.w and q.vec, ValueError,
+     "weights= needs scalar levels: weighted effects of per-individual intervention vectors are not supported"),
+    (lambda q: q.w and q.dev, NotImplementedError, "weighted effects are not sharded over devices: call predict without devices="),
+)
+
+
+def _refuse(caller, shape=(0,), n=0, baseline=None, weights=None, slope=False, outcome=False, devices=None):
+    """Raise the first row of ``_REFUSALS`` that the request (levels of this shape for n individuals, these keywords) meets.
+    Vector levels are a 2-D array; a curve takes every array beyond 1-D for them, where predict complains of its shape."""
+    q = SimpleNamespace(caller=caller, shape=shape, n=n, vec=len(shape) == 2 or (caller == "curve" and len(shape) > 2),
+                        base=baseline is not None, w=weights is not None, slope=slope, outcome=outcome, dev=devices is not None)
+    for cond, exc, msg in _REFUSALS:
+        if cond(q):
+            raise exc(msg.format(n=n, shape=shape))
+
+
+@dataclass(frozen=True)
+class _Plan:
+    """One level call, normalised: what ``predict``, ``_predict_curve`` and ``_ite_distributions`` hand to ``_SYMBOLS``."""
+    caller: str                    # "predict", "curve" or "distributions"
+    form: str                      # as csrc/level_form.h names it: "ordinary", "contrast", "slope" or "outcome"
+    vec: bool                      # per-individual levels
+    levels: np.ndarray             # (L,), or (n, L) column-major for vector levels: doT[i + n*l]
+    base: Optional[np.ndarray]     # (L,) for a contrast
+    W: Optional[np.ndarray]        # (G, n) C order = weights[i + n*g]
+    wvec: bool                     # ``weights`` was one vector: the caller drops the group axis
+    devices: Optional[Sequence[int]]
+
+    L = property(lambda self: self.levels.shape[-1])
+    weighted = property(lambda self: self.W is not None)
+    sharded = property(lambda self: self.devices is not None)
+
+
+def _plan(g, doTs, caller, baseline=None, weights=None, slope=False, outcome=False, devices=None) -> _Plan:
+    """Refuse (``_REFUSALS``, then the parse errors of ``_weights`` and ``_baseline``) or describe the call.  Nothing here
+    touches a device.  A curve's ``weights=None`` is 1/n for everybody."""
+    n = g.getN()
+    a = np.asarray(doTs, dtype=np.float64)
+    _refuse(caller, a.shape, n, baseline, weights, slope, outcome, devices)
+    W, wvec = (None, False) if weights is None else _weights(weights, n)
+    if W is None and caller == "curve":
+        W, wvec = np.full((1, n), 1.0 / n), True
+    vec = a.ndim == 2
+    levels = np.asfortranarray(a.T) if vec else np.ascontiguousarray(np.atleast_1d(a))
+    base = None if baseline is None else _baseline(baseline, levels.shape[-1])
+    form = "outcome" if outcome else "slope" if slope else "ordinary" if base is None else "contrast"
+    return _Plan(caller, form, vec, levels, base, W, wvec, devices)
+
+
+# The entry points of the C boundary that take levels: (symbol, the plan fields that select it, the optional arguments it has
+# besides the common ones).  The first row whose every field equals the plan's is the call's.  "base": doT_base (NULL for no
+# contrast); "weights": G, weights (0, NULL for none); "cov": covW; "multi": nctx, ctxs in place of ctx and a trailing info.
+_SYMBOLS = (
+    ("gpslc_ite_distributions_outcome_vec", dict(caller="distributions", form="outcome", vec=True), ()),
+    ("gpslc_ite_distributions_outcome", dict(caller="distributions", form="outcome"), ()),
+    ("gpslc_ite_distributions_slope", dict(caller="distributions", form="slope"), ()),
+    ("gpslc_ite_distributions_contrast", dict(caller="distributions", form="contrast"), ("base",)),
+    ("gpslc_ite_distributions_vec", dict(caller="distributions", vec=True), ()),
+    ("gpslc_ite_distributions", dict(caller="distributions"), ()),
+    ("gpslc_predict_outcome_vec", dict(form="outcome", vec=True), ()),
+    ("gpslc_predict_outcome", dict(form="outcome"), ("weights", "cov")),
+    ("gpslc_predict_slope", dict(form="slope"), ("weights", "cov")),
+    ("gpslc_predict_curve", dict(caller="curve"), ("base", "weights", "cov")),
+    ("gpslc_predict_weighted", dict(weighted=True), ("base", "weights")),
+    ("gpslc_predict_contrast", dict(form="contrast"), ("base",)),
+    ("gpslc_predict_vec", dict(vec=True), ()),
+    ("gpslc_predict_multi", dict(sharded=True), ("multi",)),
+    ("gpslc_predict", dict(), ()),
+)
+
+
+def _symbol(p: _Plan):
+    return next((sym, opt) for sym, sel, opt in _SYMBOLS if all(getattr(p, k) == v for k, v in sel.items()))
 
 
 class Context:
@@ -450,30 +528,15 @@ def conditionalITE(uyLS, xyLS, tyLS, yNoise, yScale, U, X, T, Y, doT):
 
 
 def _ite_distributions(g: GPSLCObject, doT, pred_noise, want_cov=True, baseline=None, slope=False, outcome=False):
+    p = _plan(g, _levels(g, doT), "distributions", baseline=baseline, slope=slope, outcome=outcome)
     n, S = g.getN(), g.getNumPosteriorSamples()
-    x, d = _intervention(doT, n)
-    _outcome_refusals(outcome, baseline, slope, d is not None, None, None)
-    _slope_refusals(slope, baseline, d is not None, None)
-    if baseline is not None:
-        if d is not None:
-            raise ValueError("baseline= needs a scalar doT: contrasts of per-individual intervention vectors are not supported")
-        base = float(_baseline(baseline, 1)[0])
+    sym, opt = _symbol(p)
     ctx = g.ctx()
     M = np.empty((S, n), order="F")
     Cv = np.empty((S, n, n), order="F") if want_cov else None
-    if outcome and d is None:
-        st = ctx.lib.gpslc_ite_distributions_outcome(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
-    elif outcome:
-        st = ctx.lib.gpslc_ite_distributions_outcome_vec(ctx.h, S, *g._params(), _p(d), float(pred_noise), _p(M), _p(Cv))
-    elif slope:
-        st = ctx.lib.gpslc_ite_distributions_slope(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
-    elif baseline is not None:
-        st = ctx.lib.gpslc_ite_distributions_contrast(ctx.h, S, *g._params(), x, base, float(pred_noise), _p(M), _p(Cv))
-    elif d is None:
-        st = ctx.lib.gpslc_ite_distributions(ctx.h, S, *g._params(), x, float(pred_noise), _p(M), _p(Cv))
-    else:
-        st = ctx.lib.gpslc_ite_distributions_vec(ctx.h, S, *g._params(), _p(d), float(pred_noise), _p(M), _p(Cv))
-    ctx.check(st)
+    level = _p(p.levels[:, 0]) if p.vec else float(p.levels[0])           # one level: the n values, or the scalar by value
+    base = (float(p.base[0]),) if "base" in opt else ()
+    ctx.check(getattr(ctx.lib, sym)(ctx.h, S, *g._params(), level, *base, float(pred_noise), _p(M), _p(Cv)))
     return M, Cv
 
 
@@ -553,104 +616,24 @@ def predict(g: GPSLCObject, doTs, want_mean_ite=False, spp=0, z=None, seed=0,
     observation adds yNoise to the diagonal, which is left to the caller.  Combines with ``weights`` for scalar levels;
     ``baseline`` (the contrast IS the difference of two outcomes), ``slope``, ``devices`` and ``weights`` with vector levels
     raise ValueError."""
-    n, S = g.getN(), g.getNumPosteriorSamples()
-    doTs = np.asarray(doTs, dtype=np.float64)
-    vec = doTs.ndim == 2
-    _outcome_refusals(outcome, baseline, slope, vec, weights, devices)
-    _slope_refusals(slope, baseline, vec, devices)
-    if doTs.ndim > 2 or (vec and doTs.shape[1] != n):
-        raise ValueError(f"doTs must be L scalar levels or an (L, n) array of intervention vectors with n = {n}, "
-                         f"got an array of shape {doTs.shape}")
-    if vec and devices is not None:
-        raise NotImplementedError("vector interventions are not sharded over devices: call predict without devices=")
-    if baseline is not None and vec:
-        raise ValueError("baseline= needs scalar levels: contrasts of per-individual intervention vectors are not supported")
-    if baseline is not None and devices is not None:
-        raise NotImplementedError("contrasts are not sharded over devices: call predict without devices=")
-    Wm = wvec = None
-    if weights is not None:
-        if vec:
-            raise ValueError("weights= needs scalar levels: weighted effects of per-individual intervention vectors are not supported")
-        if devices is not None:
-            raise NotImplementedError("weighted effects are not sharded over devices: call predict without devices=")
-        Wm, wvec = _weights(weights, n)
-    # vector levels: n x L column-major, doT[i + n*l]
-    doTs = np.asfortranarray(doTs.T) if vec else np.ascontiguousarray(np.atleast_1d(doTs))
-    L = doTs.shape[1] if vec else doTs.shape[0]
-    base = None if baseline is None else _baseline(baseline, L)
-    ctx = g.ctx() if devices is None else g.ctxs(devices)[0]
-    ms = np.empty((S, L), order="F")
-    vs = np.empty((S, L), order="F")
-    mi = np.empty((n, S, L), order="F") if want_mean_ite else None
-    dr = np.empty((L, n, S * spp), order="F") if want_draws else None
-    zz = None
-    if z is not None:
-        zz = _f(z)
-        if zz.shape != (n, spp, S, L):
-            raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
-    if outcome and vec:
-        st = ctx.lib.gpslc_predict_outcome_vec(ctx.h, S, *g._params(), L, _p(doTs), float(g.hyperparams.predictionCovarianceNoise),
-                                               int(spp), int(seed), _p(zz), _p(ms), _p(vs), _p(mi), _p(dr))
-    elif slope or outcome:
-        G = 0 if Wm is None else Wm.shape[0]
-        if Wm is not None:
-            ms = np.empty((S, L, G), order="F")
-            vs = np.empty((S, L, G), order="F")
-        fn = ctx.lib.gpslc_predict_outcome if outcome else ctx.lib.gpslc_predict_slope
-        st = fn(ctx.h, S, *g._params(), L, _p(doTs), G, _p(Wm),
-                float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
-                _p(ms), _p(vs), None, _p(mi), _p(dr))
-        if wvec:
-            ms, vs = ms[:, :, 0], vs[:, :, 0]
-    elif Wm is not None:
-        G = Wm.shape[0]
-        ms = np.empty((S, L, G), order="F")
-        vs = np.empty((S, L, G), order="F")
-        st = ctx.lib.gpslc_predict_weighted(ctx.h, S, *g._params(), L, _p(doTs), _p(base), G, _p(Wm),     # (G, n) C order =
-                                            float(g.hyperparams.predictionCovarianceNoise), int(spp),     # weights[i + n*g]
-                                            int(seed), _p(zz), _p(ms), _p(vs), _p(mi), _p(dr))
-        if wvec:
-            ms, vs = ms[:, :, 0], vs[:, :, 0]
-    elif base is not None:
-        st = ctx.lib.gpslc_predict_contrast(ctx.h, S, *g._params(), L, _p(doTs), _p(base),
-                                            float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
-                                            _p(ms), _p(vs), _p(mi), _p(dr))
-    elif devices is None:
-        fn = ctx.lib.gpslc_predict_vec if vec else ctx.lib.gpslc_predict
-        st = fn(ctx.h, S, *g._params(), L, _p(doTs), float(g.hyperparams.predictionCovarianceNoise),
-                int(spp), int(seed), _p(zz), _p(ms), _p(vs), _p(mi), _p(dr))
-    else:
-        cs = g.ctxs(devices)
-        hs = (C.c_void_p * len(cs))(*[c.h for c in cs])
-        st = ctx.lib.gpslc_predict_multi(len(cs), hs, S, *g._params(), L, _p(doTs),
-                                         float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
-                                         _p(ms), _p(vs), _p(mi), _p(dr), None)
-    ctx.check(st)
+    p = _plan(g, doTs, "predict", baseline=baseline, weights=weights, slope=slope, outcome=outcome, devices=devices)
+    ms, vs, _, mi, dr = _run(g, p, want_mean_ite, spp, z, seed, want_draws, False)
+    if p.wvec:
+        ms, vs = ms[:, :, 0], vs[:, :, 0]
     if want_draws:
         return ms, vs, mi, dr
     return ms, vs, mi
 
 
-def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_ite=False, spp=0, z=None, seed=0,
-                   want_draws=False, want_cov=True, devices=None, slope=False, outcome=False):
-    """gpslc_predict_curve: (meanW (S, L, G), varW (S, L, G), covW (S, L, L, G) or None, MeanITE or None, draws or None) and
-    whether ``weights`` was a single vector.  ``weights=None`` is 1/n for everybody.  ``slope=True``: gpslc_predict_slope's
-    weighted form; ``outcome=True``: gpslc_predict_outcome's."""
-    n, S = g.getN(), g.getNumPosteriorSamples()
-    doTs = np.asarray(doTs, dtype=np.float64)
-    _outcome_refusals(outcome, baseline, slope, False, None, devices)
-    _slope_refusals(slope, baseline, doTs.ndim > 1, devices)
-    if doTs.ndim > 1:
-        raise ValueError("an effect curve needs scalar levels: per-individual intervention vectors are not supported")
-    if devices is not None:
-        raise NotImplementedError("effect curves are not sharded over devices: call without devices=")
-    Wm, wvec = (np.full((1, n), 1.0 / n), True) if weights is None else _weights(weights, n)
-    doTs = np.ascontiguousarray(np.atleast_1d(doTs))
-    L, G = doTs.shape[0], Wm.shape[0]
-    base = None if baseline is None else _baseline(baseline, L)
-    ctx = g.ctx()
-    mw = np.empty((S, L, G), order="F")
-    vw = np.empty((S, L, G), order="F")
+def _run(g: GPSLCObject, p: _Plan, want_mean_ite, spp, z, seed, want_draws, want_cov):
+    """Allocate the outputs of a ``predict`` / ``curve`` plan, check ``z``, call the plan's symbol: (mean, var, covW or None,
+    MeanITE or None, draws or None), the first two (S, L) without weights and (S, L, G) with."""
+    n, S, L = g.getN(), g.getNumPosteriorSamples(), p.L
+    sym, opt = _symbol(p)
+    cs = [g.ctx()] if p.devices is None else g.ctxs(p.devices)
+    ctx = cs[0]
+    G = p.W.shape[0] if p.weighted else 0
+    ms, vs = (np.empty((S, L, G) if p.weighted else (S, L), order="F") for _ in range(2))
     cw = np.empty((S, L, L, G), order="F") if want_cov else None
     mi = np.empty((n, S, L), order="F") if want_mean_ite else None
     dr = np.empty((L, n, S * spp), order="F") if want_draws else None
@@ -659,17 +642,26 @@ def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_
         zz = _f(z)
         if zz.shape != (n, spp, S, L):
             raise AssertionError(f"z must be (n, spp, S, L) = {(n, spp, S, L)}, got {zz.shape}")
-    if slope or outcome:
-        fn = ctx.lib.gpslc_predict_outcome if outcome else ctx.lib.gpslc_predict_slope
-        st = fn(ctx.h, S, *g._params(), L, _p(doTs), G, _p(Wm),
-                float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
-                _p(mw), _p(vw), _p(cw), _p(mi), _p(dr))
-    else:
-        st = ctx.lib.gpslc_predict_curve(ctx.h, S, *g._params(), L, _p(doTs), _p(base), G, _p(Wm),
-                                         float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz),
-                                         _p(mw), _p(vw), _p(cw), _p(mi), _p(dr))
+    st = getattr(ctx.lib, sym)(
+        *((len(cs), (C.c_void_p * len(cs))(*[c.h for c in cs])) if "multi" in opt else (ctx.h,)),
+        S, *g._params(), L, _p(p.levels),
+        *((_p(p.base),) if "base" in opt else ()),
+        *((G, _p(p.W)) if "weights" in opt else ()),
+        float(g.hyperparams.predictionCovarianceNoise), int(spp), int(seed), _p(zz), _p(ms), _p(vs),
+        *((_p(cw),) if "cov" in opt else ()),
+        _p(mi), _p(dr),
+        *((None,) if "multi" in opt else ()))
     ctx.check(st)
-    return (mw, vw, cw, mi, dr), wvec
+    return ms, vs, cw, mi, dr
+
+
+def _predict_curve(g: GPSLCObject, doTs, baseline=None, weights=None, want_mean_ite=False, spp=0, z=None, seed=0,
+                   want_draws=False, want_cov=True, devices=None, slope=False, outcome=False):
+    """gpslc_predict_curve: (meanW (S, L, G), varW (S, L, G), covW (S, L, L, G) or None, MeanITE or None, draws or None) and
+    whether ``weights`` was a single vector.  ``weights=None`` is 1/n for everybody.  ``slope=True``: gpslc_predict_slope's
+    weighted form; ``outcome=True``: gpslc_predict_outcome's."""
+    p = _plan(g, doTs, "curve", baseline=baseline, weights=weights, slope=slope, outcome=outcome, devices=devices)
+    return _run(g, p, want_mean_ite, spp, z, seed, want_draws, want_cov), p.wvec
 
 
 def effectCurve(g: GPSLCObject, doTs, baseline=None, weights=None, devices=None, slope=False, outcome=False):
@@ -792,7 +784,7 @@ def predictCounterfactualEffects(g: GPSLCObject, nSamplesPerMixture, fidelity=10
     (src/prediction.jl:23-36).  All levels share one factorisation of A per posterior sample; ``devices`` shards the
     posterior samples over several GPUs (``gpslc_predict_multi``).  ``outcome=True``: draws of every individual's outcome
     surface f_i(a) over the sweep instead of the effects f_i(a) - f_i(T_i) (one GPU only)."""
-    _outcome_refusals(outcome, None, False, False, None, devices)
+    _refuse("predict", outcome=outcome, devices=devices)
     lo = float(np.min(g.T)) if minDoT is None else float(minDoT)
     hi = float(np.max(g.T)) if maxDoT is None else float(maxDoT)
     rng = doTRange(lo, hi, fidelity)
