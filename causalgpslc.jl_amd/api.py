@@ -10,6 +10,7 @@ like the reference's own tests:
     sampleITE, sampleSATE, summarizeEstimates     src/driver.jl:86-89, 108-111, 129-149
     predictCounterfactualEffects                  src/prediction.jl:23-36
     yLogpdf                                       src/model_likelihood.jl:83-120 (:Y node score)
+    looPredictive, looSummary                     leave-one-out checks of that node's outcome model (no reference counterpart)
 
 Everything numeric is done by libgpslc_hip.so through the C ABI (``_lib``); this module only
 marshals arrays (NumPy, column-major) and reproduces the reference's output layouts.
@@ -274,6 +275,18 @@ class Context:
         out = np.zeros(S, dtype=np.int32)
         self.check(self.lib.gpslc_last_info(self.h, out.ctypes.data_as(_lib.c_int32_p), S))
         return out
+
+    def y_loo(self, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, want=("mean", "var", "lpd", "logpdf")):
+        """gpslc_y_loo with host arrays as given (None = NULL): ``(status, looMean, looVar, looLpd, logpdf)`` — the outputs
+        named in ``want`` as (n, S) / (S,) arrays, the others None (NULL to the library).  The status is returned, not raised:
+        a positive one (a parameter set's factorisation broke down) still leaves the other sets' values."""
+        S = int(S)
+        shape = (self.n, max(S, 0))
+        out = {k: np.full(shape if k != "logpdf" else (shape[1],), np.nan, order="F") if k in want else None
+               for k in ("mean", "var", "lpd", "logpdf")}
+        st = self.lib.gpslc_y_loo(self.h, S, _p(U), _p(X_or_none), _p(Y_or_none), _p(uyLS), _p(xyLS), _p(tyLS), _p(yScale),
+                                  _p(yNoise), _p(out["mean"]), _p(out["var"]), _p(out["lpd"]), _p(out["logpdf"]))
+        return st, out["mean"], out["var"], out["lpd"], out["logpdf"]
 
     def profile_reset(self):
         self.lib.gpslc_profile_reset(self.h)
@@ -847,6 +860,42 @@ def yLogpdf(g: GPSLCObject, X_override=None, Y_override=None):
     st = ctx.lib.gpslc_y_logpdf(ctx.h, S, U, _p(Xo), _p(Yo), uy, xy, ty, ys, yn, _p(out))
     ctx.check(st)
     return out
+
+
+def _loo_call(g: GPSLCObject, X_override, Y_override, want):
+    n = g.getN()
+    Xo = None if X_override is None else _f(X_override).reshape(n, g.getNX(), order="F")
+    Yo = None if Y_override is None else _f(Y_override, (n,))
+    ctx = g.ctx()
+    st, *out = ctx.y_loo(g.getNumPosteriorSamples(), g.U, Xo, Yo, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise, want=want)
+    ctx.check(st)
+    return out
+
+
+def looPredictive(g: GPSLCObject, X_override=None, Y_override=None):
+    """Leave-one-out predictive distribution of every observation under the outcome model of every posterior sample
+    (gpslc_y_loo; Rasmussen & Williams §5.4.2) -> ``(mean, var, lpd)``, each (n, S): mean and variance of Y_i given all the
+    other observations (``var`` is for the observation: it includes yNoise) and the log density of Y_i under that predictive.
+    Each sample conditions on its own hyper-parameters and U, which were inferred with Y_i present.  Overrides and errors as
+    ``yLogpdf``: ``Y_override`` is the outcome vector being checked, a failed factorisation raises ``PosDefException``."""
+    mean, var, lpd, _ = _loo_call(g, X_override, Y_override, ("mean", "var", "lpd"))
+    return mean, var, lpd
+
+
+def looSummary(g: GPSLCObject, X_override=None, Y_override=None, loo=None):
+    """Summaries of ``looPredictive`` (host arithmetic only; ``loo`` = its result, to summarise one already computed):
+
+    ``elpd`` (S,): sum_i lpd[i, s], the LOO log predictive density of every posterior sample — compare models (nU = 0 / 1 / 2,
+    with / without X) on it; ``pointwise`` (n,): log mean_s exp(lpd[i, s]), the individuals the surface misses;
+    ``zscore`` (n, S): (Y - mean) / sqrt(var); ``pit`` (n,): mean_s Phi(zscore), uniform on (0, 1) for a calibrated model."""
+    from math import erf
+    mean, var, lpd = looPredictive(g, X_override, Y_override) if loo is None else loo
+    Y = g.Y if Y_override is None else _f(Y_override, (g.getN(),))
+    z = (Y[:, None] - mean) / np.sqrt(var)
+    top = np.max(lpd, axis=1)
+    pointwise = top + np.log(np.mean(np.exp(lpd - top[:, None]), axis=1))
+    pit = np.mean(0.5 * (1.0 + np.vectorize(erf)(z / np.sqrt(2.0))), axis=1)
+    return {"elpd": np.sum(lpd, axis=0), "pointwise": pointwise, "zscore": z, "pit": pit}
 
 
 def gpLogpdf(F, LS, scale, noise, target, ctx: Optional[Context] = None):

@@ -677,6 +677,8 @@ struct PredictIO {
     const double* nz = nullptr;
     const double* nzero = nullptr;
     double* ndraw = nullptr;
+    // leave-one-out predictive checks of the outcome model (gpslc_y_loo): n x S each, device, or null
+    double *looMean = nullptr, *looVar = nullptr, *looLpd = nullptr;
 };
 
 // chunk and unit-B sub-batch sizes of a call (batch_plan.h holds the arithmetic; here: what the schedule would like and what
@@ -712,11 +714,13 @@ struct PredictShape {
     int n, nt, L, R, naug, ntot;      // R: right-hand sides beside Y — one per level, or L*G with weight columns
     long long Np, tiles_per, nlow;   // padded N, tiles of A with its augmented rows, tiles of an nt x nt triangle
     bool with_sums, want_cov, want_draws, want_mean, unitB;     // unitB: full ITE covariance (CovITE, draws)
+    bool want_loo, want_alpha;        // leave-one-out outputs; alpha = A^-1 Y is wanted (by the MeanITE pass or by them)
     PredictShape(const gpslc_ctx* c, const PredictIO& io)
         : n((int)c->n), nt(c->nt), L(io.lv.L), R(io.lv.W ? io.lv.L * io.lv.G : io.lv.L), naug((R + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug),
           Np((long long)nt * GP_TS), tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2),
           with_sums(io.out.meanSATE || io.out.varSATE || io.out.covW), want_cov(io.CovITEs != nullptr), want_draws(io.out.ite_draws != nullptr),
-          want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws) {}
+          want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws),
+          want_loo(io.looMean || io.looVar || io.looLpd), want_alpha(want_mean || want_loo) {}
 };
 
 // one chunk of a call: samples s0 .. s0 + nb - 1 on one stream slot, and the buffers carve_chunk takes for it from the slot's arena
@@ -729,6 +733,7 @@ struct Chunk {
     double *vpart = nullptr, *zwork = nullptr, *znode = nullptr;
     double *bw = nullptr, *kw = nullptr, *wnorm2 = nullptr;      // weighted effects: B W, K W [nb][G][Np], w_g . w_g [nb][G]
     double* cprior = nullptr;        // joint covariance across the levels: beta, kappa, gamma_l [nb][G][L + 2]
+    double *loo_w = nullptr, *loo_c = nullptr;      // leave-one-out: W = L^-T as a packed triangle of tiles [nb][nlow], diag(A^-1) [nb][Np]
     // unit B: a sub-batch of gs_max samples x lc_max levels; W, CovITE, the draws' normals, level-sweep staging, failure codes
     int lc_max = 0, gs_max = 0;
     double *Wt = nullptr, *Ct = nullptr, *zt = nullptr, *dtmp = nullptr;
@@ -767,6 +772,7 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     if (io.lv.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
     if (io.ndraw) b.znode = take(draws_image_doubles(1, sh.Np));        // operand image of the node draw's normals
+    if (sh.want_loo) { b.loo_w = take((size_t)sh.nlow * GP_TSQ); b.loo_c = take(sh.Np); }
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
     if (!sh.unitB) return by;
     by.per_pair = (size_t)((long long)nt * nt + sh.nlow) * GP_TSQ * 8;
@@ -873,8 +879,8 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     if (potrf_tasks_ok(c, nt, sh.ntot, short_rows, epi_rows, nb, ch.inv)) {
         // small tile counts: the whole factorisation (and the back-substitution) as ONE persistent launch of tile tasks
         potrf_tasks(c, *ch.s, ch.M, nt, ch.inv, inv_bs, io.info + s0, 0, nb, short_rows,
-                    sh.want_mean ? ch.zwork + (long long)nb * sh.Np : nullptr);
-        back_done = sh.want_mean;
+                    sh.want_alpha ? ch.zwork + (long long)nb * sh.Np : nullptr);
+        back_done = sh.want_alpha;
     } else {
         factor_panels(c, *ch.s, ch.M, nt, sh.ntot, ch.inv, inv_bs, io.info + s0, 0, nb, live, epi_rows, 0);
     }
@@ -902,14 +908,18 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     return back_done;
 }
 
-// MeanITE of a chunk: the back-substitution (unless the factorisation delivered alpha) and the ITE-mean kernels, once per output
-// layout asked for: meanITE n x S x L, MeanITEs S x n (the reference layout, single level)
-void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch, bool back_done) {
-    hipStream_t st = ch.s->st;
-    const int n = sh.n, nb = ch.nb;
+// alpha = A^-1 Y of a chunk where the factorisation did not deliver it: the back-substitution
+void back_substitute(const PredictShape& sh, const Chunk& ch) {
     BackArgs ba{};
     ba.M = ch.M; ba.inv = ch.inv; ba.inv_bstride = (long long)sh.nt * GP_TSQ; ba.nt = sh.nt; ba.naug = sh.naug; ba.zwork = ch.zwork;
-    if (!back_done) launch_backsolve(ba, nb, st);
+    launch_backsolve(ba, ch.nb, ch.s->st);
+}
+
+// MeanITE of a chunk from alpha: the ITE-mean kernels, once per output layout asked for: meanITE n x S x L, MeanITEs S x n (the
+// reference layout, single level)
+void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    hipStream_t st = ch.s->st;
+    const int n = sh.n, nb = ch.nb;
     const double* alpha = ch.zwork + (long long)nb * sh.Np;
     const long long S = io.post.S;
     const struct { double* out; long long si, ss, sl; } outs[2] = {{io.out.meanITE, 1, n, (long long)n * S}, {io.MeanITEs, S, 1, 0}};
@@ -939,6 +949,38 @@ void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const T
         g.k0 = 0; g.k1 = k; g.fuse = 1;
         gemm(c, g, s, 3);
     }
+}
+
+// Leave-one-out predictive checks of a chunk: c = diag(A^-1) as the squared row norms of W = L^-T, then the
+// outputs from alpha, c and Y.  W is built block diagonal by block diagonal, one launch each: diagonal d holds the tiles
+// (i, i + d) of all tile rows and matrices, each a chain of d tile products from kk = i on (nt^3/6 products in all, the
+// factorisation's count); the tile rows of a matrix are independent chains, so nt x nb of them are in flight.
+void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    hipStream_t st = ch.s->st;
+    const int nt = sh.nt, nb = ch.nb;
+    LooArgs la{};
+    la.inv = ch.inv; la.inv_bstride = (long long)nt * GP_TSQ;
+    la.W = ch.loo_w; la.w_bstride = sh.nlow * GP_TSQ;
+    la.n = sh.n; la.nt = nt; la.s0 = ch.s0; la.S = io.post.S;
+    la.c = ch.loo_c; la.alpha = ch.zwork + (long long)nb * sh.Np;
+    la.Y = io.Y; la.y_sstride = io.y_sstride; la.info = io.info;
+    la.looMean = io.looMean; la.looVar = io.looVar; la.looLpd = io.looLpd;
+    HC(hipMemsetAsync(ch.loo_w, 0, sizeof(double) * (size_t)nb * sh.nlow * GP_TSQ, st));     // every chain starts from a zero tile
+    launch_loo_init(la, nb, st);
+    rearm_queue(*ch.s);
+    for (int d = 1; d < nt; ++d) {
+        GemmArgs g{};
+        g.A = g.C = lower_ref(ch.loo_w, la.w_bstride);
+        g.B = ch.M;
+        g.F = TRef{ch.inv, la.inv_bstride, 1, 0, 0, 0};
+        g.shape = 1; g.mj = 1; g.fuse = 1; g.nbatch = nb; g.ntiles = nt - d;
+        g.queue = ch.s->queue;
+        launch_loo_diagonal(g, nt, d, st);
+    }
+    launch_loo_rownorm(la, nb, st);
+    launch_loo_finish(la, nb, st);
+    HC(hipGetLastError());
+    (void)c;
 }
 
 // Unit B of a chunk batches over (posterior sample, level) PAIRS: a sub-batch is gs samples x lc levels (gs * lc <= Bb), batch
@@ -1051,7 +1093,9 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         carve_chunk(sh, io, Bb, &ch);
         ch.grid = SampleGrid{io.X, c->dT, io.post.p, s0, sh.n, io.nX, io.nU, sh.nt};
         const bool back_done = unit_a(c, io, sh, ch);
-        if (sh.want_mean) mean_ite(c, io, sh, ch, back_done);
+        if (sh.want_alpha && !back_done) back_substitute(sh, ch);
+        if (sh.want_mean) mean_ite(c, io, sh, ch);
+        if (sh.want_loo) loo(c, io, sh, ch);
         if (sh.unitB) unit_b(c, io, sh, ch);
     }
     for (auto& s : c->slots) HC(hipStreamSynchronize(s.st));
@@ -1576,7 +1620,7 @@ struct ArgPos { int S, U, xyLS, tyLS, L, doT, base, G, W, spp; bool fp64_only; i
 static const ArgPos kPredictArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, false}, kPredictVecArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, true},
     kPredictContrastArgs{2, 3, 5, 6, 9, 10, 11, 0, 0, 13, true}, kPredictWeightedArgs{2, 3, 5, 6, 9, 10, 11, 12, 13, 15, true},
     kPredictMultiArgs{3, 4, 6, 7, 10, 11, 0, 0, 0, 13, false},      // two more leading arguments: nctx, ctxs
-    kSamplesArgs{2, 3, 5, 6, 0, 0, 0, 0, 0, 0, false},      // gpslc_ite_distributions, gpslc_y_logpdf, gpslc_likelihood_distribution
+    kSamplesArgs{2, 3, 5, 6, 0, 0, 0, 0, 0, 0, false},      // gpslc_ite_distributions, gpslc_y_logpdf, gpslc_y_loo, gpslc_likelihood_distribution
     kIteVecArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true}, kIteContrastArgs{2, 3, 5, 6, 0, 9, 10, 0, 0, 0, true},
     kLikelihoodVecArgs{2, 3, 5, 6, 0, 8, 0, 0, 0, 0, false},
     kPredictSlopeArgs{2, 3, 5, 6, 9, 10, 0, 11, 12, 14, true, 19}, kIteSlopeArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true};
@@ -2244,6 +2288,35 @@ int gpslc_y_logpdf(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_
         io.X = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
         if (Y_or_null) { io.Y = up(c, Y_or_null, n); io.y_sstride = 0; }    // the value being scored (Gen passes it to logpdf), else the ctx's Y
         return tiled_score(c, io, logpdf);
+    });
+}
+
+int gpslc_y_loo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                double* looMean, double* looVar, double* looLpd, double* logpdf_or_null) {
+    const PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 0, nullptr);
+    int rc = validate(c, rq, kSamplesArgs);
+    if (rc) return rc;
+    if (!looMean && !looVar && !looLpd && !logpdf_or_null) return bad_arg(c, 11, "looMean, looVar, looLpd and logpdf are all NULL");
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        // the tiled path at every n: the outputs come from the tile factor gpslc_y_logpdf's general path computes
+        const size_t n = (size_t)c->n, nS = n * (size_t)S;
+        c->io.reset();
+        PredictIO io;
+        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
+        io.X = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
+        if (Y_or_null) { io.Y = up(c, Y_or_null, n); io.y_sstride = 0; }
+        io.looMean = looMean ? c->io.take<double>(nS) : nullptr;
+        io.looVar = looVar ? c->io.take<double>(nS) : nullptr;
+        io.looLpd = looLpd ? c->io.take<double>(nS) : nullptr;
+        std::vector<double> lp(logpdf_or_null ? 0 : (size_t)S);
+        const int st = tiled_score(c, io, logpdf_or_null ? logpdf_or_null : lp.data());
+        if (st < 0) return st;
+        if (looMean) copy_out_large(c, looMean, io.looMean, nS * sizeof(double));
+        if (looVar) copy_out_large(c, looVar, io.looVar, nS * sizeof(double));
+        if (looLpd) copy_out_large(c, looLpd, io.looLpd, nS * sizeof(double));
+        return st;
     });
 }
 

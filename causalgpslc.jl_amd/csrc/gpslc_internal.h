@@ -316,6 +316,34 @@ struct VecArgs : SampleGrid {
 void launch_vec_sums(const VecArgs& a, int nbatch, hipStream_t st);
 void launch_vec_mean(const VecArgs& a, int nbatch, hipStream_t st);
 
+// ---------------------------------------------------------------------------------------
+// Leave-one-out predictive checks of the outcome model (k_loo.hip): c = diag(A^-1) = the squared row norms of
+// W = L^-T from the chunk's tiled factor.  W is upper block-triangular and lives as a PACKED triangle: tile row i keeps its
+// nt - i tiles (i, i) .. (i, nt - 1) as one contiguous run in ascending k — the A operand strip_item streams — at the place a
+// lower-packed matrix keeps its row nt - 1 - i: tile (i, k) is tile (nt - 1 - i, k - i) of a lower-packed TRef.
+// ---------------------------------------------------------------------------------------
+__host__ __device__ inline long long loo_w_index(int nt, int i, int k) {
+    const long long r = nt - 1 - i;
+    return r * (r + 1) / 2 + (k - i);
+}
+struct LooArgs {
+    const double* inv; long long inv_bstride;   // the inverted diagonal tiles of the factor (Chunk::inv)
+    double* W; long long w_bstride;             // [b][nt (nt + 1) / 2 tiles], loo_w_index
+    int n, nt; long long s0, S;
+    double* c;                                  // [b][Np]: diag(A^-1)
+    const double* alpha;                        // [b][Np]: A alpha = Y (the vector ite_mean_kernel reads)
+    const double* Y; long long y_sstride;       // sample s at Y + s*y_sstride
+    const int* info;                            // S: a sample whose factorisation broke down gets NaN
+    double* looMean; double* looVar; double* looLpd;   // n x S each (element (i, s) at i + n*s) or null
+};
+void launch_loo_init(const LooArgs& a, int nbatch, hipStream_t st);       // W(i, i) = inv(L_ii)^T (the other tiles: zeroed by the caller)
+// block diagonal d >= 1 of W (k_tilegemm.hip, strip_item): the items (b, i, i + d), i < nt - d = g.ntiles, of
+// W(i, k) = -(sum_{kk = i}^{k - 1} W(i, kk) L(k, kk)^T) inv(L_kk)^T.  g: A = C = W as a lower-packed TRef (ro / co are set per
+// item), B = the factor, F = the inverted diagonal tiles, nbatch, ntiles, queue
+void launch_loo_diagonal(const GemmArgs& g, int nt, int d, hipStream_t st);
+void launch_loo_rownorm(const LooArgs& a, int nbatch, hipStream_t st);    // c_r = sum_{k >= i} sum_col W(i, k)[r, col]^2
+void launch_loo_finish(const LooArgs& a, int nbatch, hipStream_t st);     // alpha, c, Y -> looMean, looVar, looLpd for the rows < n
+
 void launch_rbf_log(const double* X1, const double* X2, long long n, int d, const double* ls,
                     int ls_len, double* out, hipStream_t st);
 void launch_process_cov(const double* in, long long n, double scale, double noise, double* out,

@@ -6,6 +6,7 @@
 //   tile_fused_strip_kernel   one tile column: the left-looking column update and, in the same work item, the panel product
 //                             with the inverted diagonal block (strip_item) — the panels of the factorisation and the
 //                             "D L^-T" solves (w_solve, api.hip);
+//   loo_diagonal_kernel       one block diagonal of L^-T for the leave-one-out checks: strip_item with a K range per item;
 //   tile_syrk_diag_kernel,    the diagonal tiles of a symmetric update (lower triangle only), alone or followed by the
 //   diag_update_potrf_kernel  tile's Cholesky and inverse;
 //   potrf_tasks_kernel        a whole factorisation as tile tasks of one persistent launch (strip_item and the diagonal-tile
@@ -632,6 +633,38 @@ __global__ __launch_bounds__(256, 2) void tile_fused_strip_kernel(GemmArgs g) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Leave-one-out checks: block diagonal d of W = L^-T, tile (i, i + d) for every tile row i < nt - d = g.ntiles
+// of every matrix — strip_item with an item's own K range [i, i + d) (the triangular structure: tile row i starts at kk = i),
+// its own inverted diagonal tile (fk = i + d) and its own row of the packed triangle (gpslc_internal.h, loo_w_index: tile
+// (i, k) of W is tile (nt - 1 - i, k - i) of the lower-packed TRef, hence ro / co).  The C tile comes in zeroed, so the K loop
+// leaves X = -sum_kk W(i, kk) L(k, kk)^T and the second phase W(i, k) = X inv(L_kk)^T.  All items of a launch run d tile
+// products: the K length is uniform, the chains of different tile rows are independent.
+// ---------------------------------------------------------------------------------------
+template <int WD>
+__global__ __launch_bounds__(256, 2) void loo_diagonal_kernel(GemmArgs g, int nt, int d) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lg = lane >> 4;
+    double* lB = smem;
+    const int frow_b = lg * LROW + li;
+    int loff[4];
+    stage_offsets(tid, loff);
+    const int nslab = d * (GP_TS / KS);
+
+    ticket_loop(g, (long long)g.ntiles * g.nbatch, tid, [&](const long long item) {
+        const int b = (int)(item / g.ntiles);
+        const int i = (int)(item - (long long)b * g.ntiles);
+        GemmArgs gl = g;
+        gl.k0 = i; gl.k1 = i + d; gl.fk = i + d;
+        gl.A.ro = gl.C.ro = nt - 1 - 2 * i;
+        gl.A.co = gl.C.co = -i;
+        strip_item<WD>(gl, b, i, i + d, false, nslab, lB, tid, lane, wave, li, lg, frow_b, loff, item);
+    });
+}
+
+// ---------------------------------------------------------------------------------------
 // Update of ONE diagonal tile, one wave's share:  C(t, t) -= sum_kk A(t, kk) A(t, kk)^T over the nslab slabs (nslab / 8 tile
 // columns) from tile column g.k0, lower triangle only.  Wave W owns sub-tile rows W and 7 - W of the 8 x 8 grid of 16 x 16
 // sub-tiles: (W, 0..W) and (7 - W, 0..7 - W), 9 sub-tiles, 9 accumulators — 36 of the 64 sub-tile products of a full tile.  Both
@@ -1131,6 +1164,14 @@ void launch_syrk_diag(const GemmArgs& g, int carry_aug, hipStream_t st) {
     const unsigned grid = persistent_grid((long long)g.mi * g.nbatch);
     dispatch_mt(carry_aug ? (g.short_rows + 15) / 16 : 0,      // callers pass carry_aug only for up to 32 live rows
                 [&](auto mt) { launch_syrk_diag_t<decltype(mt)::value>(g, grid, st); });
+}
+
+void launch_loo_diagonal(const GemmArgs& g, int nt, int d, hipStream_t st) {
+    if (g.ntiles <= 0 || g.nbatch <= 0 || d < 1 || g.ntiles != nt - d) return;
+    static DeviceOnce once;
+    lds_opt_in(once, (const void*)loo_diagonal_kernel<FUSE_WD>, STRIP_LDS_BYTES);
+    hipLaunchKernelGGL((loo_diagonal_kernel<FUSE_WD>), dim3(persistent_grid((long long)g.ntiles * g.nbatch)), dim3(256),
+                       STRIP_LDS_BYTES, st, g, nt, d);
 }
 
 template <int DIAG>

@@ -131,6 +131,27 @@ int gpslc_y_logpdf(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_o
                    const double* Y_or_null, const double* uyLS, const double* xyLS, const double* tyLS,
                    const double* yScale, const double* yNoise, double* logpdf /* S */);
 
+/* Leave-one-out (LOO) predictive checks of the outcome model Y ~ N(0, A), A = Ycov as above = L L^T (Rasmussen &
+ * Williams, Gaussian Processes for Machine Learning, §5.4.2).  With alpha = A^-1 Y and c_i = [A^-1]_ii, for every individual
+ * i and parameter set s (element (i, s) of an n x S array at i + n*s):
+ *   looMean = Y_i - alpha_i / c_i                                   mean of Y_i given all the other observations
+ *   looVar  = 1 / c_i                                               its variance: predictive for the OBSERVATION, yNoise included
+ *   looLpd  = -log(2 pi)/2 + log(c_i)/2 - alpha_i^2 / (2 c_i)       log density of Y_i under that predictive
+ * c is computed as the squared row norms of L^-T from the tiled factor (a sum of squares: no cancellation), on the GPU.
+ * Each parameter set's LOO conditions on THAT set's hyper-parameters and U, which were themselves inferred with Y_i present:
+ * it checks the outcome surface given the posterior sample, not the whole inference (no importance-weighting correction).
+ * Arguments as gpslc_y_logpdf (host pointers; X_or_null / Y_or_null override the ctx's X / Y for this call).  Any of the four
+ * outputs may be NULL; all four NULL is the argument error of looMean (-11).  logpdf_or_null receives gpslc_y_logpdf's value
+ * from the same factorisation: bit-identical to that call wherever it takes the batched tiled path (n > 640, more
+ * parameter sets than the single-launch kernels take, or a GPSLC_FLAG_FP32_KERNEL context) — this call takes the tiled path
+ * at every n.  Works on any context (nothing here evaluates the RBF kernel beyond the shared Gram build).
+ * A parameter set whose factorisation breaks down gets NaN in all its LOO outputs; return value (first failing pivot) and
+ * gpslc_last_info as for gpslc_y_logpdf.  There is no _dev variant and no sharding over several contexts. */
+int gpslc_y_loo(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                double* looMean /* n x S */, double* looVar /* n x S */, double* looLpd /* n x S */,
+                double* logpdf_or_null /* S */);
+
 /* ---- the other Gaussian-process nodes of the Gen models -------------- */
 
 /* log N(target; 0, scale * exp.(rbfKernelLog(F, F, ls)) + noise * I) for S parameter sets: the score of

@@ -164,6 +164,22 @@ function y_logpdf(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS,
     out
 end
 
+"""Leave-one-out predictive checks of the :Y node's outcome model for S parameter sets (gpslc_y_loo): `(looMean, looVar,
+looLpd, logpdf)`, the first three n x S — mean and variance (yNoise included) of every Y_i given all the others, and its log
+density under that predictive — the last the node's score from the same factorisation."""
+function y_loo(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS, tyLS::Vector{Float64},
+               yScale::Vector{Float64}, yNoise::Vector{Float64})
+    looMean, looVar, looLpd = (Matrix{Float64}(undef, c.n, S) for _ in 1:3)
+    lp = Vector{Float64}(undef, S)
+    Uf, Xf, Yf, uy, xy = f64(U), f64(X_or_nothing), f64(Y_or_nothing), f64(uyLS), f64(xyLS)
+    GC.@preserve Uf Xf Yf uy xy tyLS yScale yNoise looMean looVar looLpd lp check(c, ccall((:gpslc_y_loo, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(Uf), ptr(Xf), ptr(Yf), ptr(uy), ptr(xy), pointer(tyLS), pointer(yScale), pointer(yNoise),
+        pointer(looMean), pointer(looVar), pointer(looLpd), pointer(lp)))
+    looMean, looVar, looLpd, lp
+end
+
 """log N(target; 0, scale exp.(rbfKernelLog(F, F, ls)) + noise I) for S parameter sets: :X => k => :X, :T / :logitT."""
 function gp_logpdf(c::Ctx, S::Integer, nF::Integer, F::Array{Float64}, f_shared::Bool, ls::Array{Float64},
                    scale::Vector{Float64}, noise::Vector{Float64}, target::Array{Float64}, t_shared::Bool)
