@@ -679,6 +679,11 @@ struct PredictIO {
     double* ndraw = nullptr;
     // leave-one-out predictive checks of the outcome model (gpslc_y_loo): n x S each, device, or null
     double *looMean = nullptr, *looVar = nullptr, *looLpd = nullptr;
+    // predictions for m new individuals (gpslc_predict_new): their features (device; Xnew m x nX, Unew m x nU x S)
+    // and the outputs, m x S x L each and m x m x S x L (device, or null).  newCov needs newVar: its diagonal
+    const double *Xnew = nullptr, *Unew = nullptr;
+    int m = 0;
+    double *newMean = nullptr, *newVar = nullptr, *newCov = nullptr;
 };
 
 // chunk and unit-B sub-batch sizes of a call (batch_plan.h holds the arithmetic; here: what the schedule would like and what
@@ -715,12 +720,20 @@ struct PredictShape {
     long long Np, tiles_per, nlow;   // padded N, tiles of A with its augmented rows, tiles of an nt x nt triangle
     bool with_sums, want_cov, want_draws, want_mean, unitB;     // unitB: full ITE covariance (CovITE, draws)
     bool want_loo, want_alpha;        // leave-one-out outputs; alpha = A^-1 Y is wanted (by the MeanITE pass or by them)
+    int mt = 0;                       // new individuals: their row tiles, the tiles of an mt x mt triangle, and whether the
+    long long mlow = 0;               // (sample, level) pairs need tile workspace (variance, covariance)
+    bool want_new = false, new_pairs = false;
     PredictShape(const gpslc_ctx* c, const PredictIO& io)
         : n((int)c->n), nt(c->nt), L(io.lv.L), R(io.lv.W ? io.lv.L * io.lv.G : io.lv.L), naug((R + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug),
           Np((long long)nt * GP_TS), tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2),
           with_sums(io.out.meanSATE || io.out.varSATE || io.out.covW), want_cov(io.CovITEs != nullptr), want_draws(io.out.ite_draws != nullptr),
           want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws),
-          want_loo(io.looMean || io.looVar || io.looLpd), want_alpha(want_mean || want_loo) {}
+          want_loo(io.looMean || io.looVar || io.looLpd), want_alpha(want_mean || want_loo || io.newMean) {
+        want_new = io.newMean || io.newVar || io.newCov;
+        new_pairs = io.newVar || io.newCov;
+        mt = (io.m + GP_TS - 1) / GP_TS;
+        mlow = (long long)mt * (mt + 1) / 2;
+    }
 };
 
 // one chunk of a call: samples s0 .. s0 + nb - 1 on one stream slot, and the buffers carve_chunk takes for it from the slot's arena
@@ -774,6 +787,16 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     if (io.ndraw) b.znode = take(draws_image_doubles(1, sh.Np));        // operand image of the node draw's normals
     if (sh.want_loo) { b.loo_w = take((size_t)sh.nlow * GP_TSQ); b.loo_c = take(sh.Np); }
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
+    if (sh.new_pairs) {       // new individuals: W* (mt x nt) and, with the covariance, an mt triangle per (sample, level) pair
+        const size_t w_tiles = (size_t)sh.mt * nt, c_tiles = io.newCov ? (size_t)sh.mlow : 0;
+        by.per_pair = (w_tiles + c_tiles) * GP_TSQ * 8 + 512;
+        if (!ar) return by;
+        b.lc_max = std::min(L, Bb);
+        b.gs_max = std::max(1, Bb / b.lc_max);
+        b.Wt = ar->take<double>((size_t)Bb * w_tiles * GP_TSQ);
+        if (c_tiles) b.Ct = ar->take<double>((size_t)Bb * c_tiles * GP_TSQ);
+        return by;
+    }
     if (!sh.unitB) return by;
     by.per_pair = (size_t)((long long)nt * nt + sh.nlow) * GP_TSQ * 8;
     if (sh.want_draws) {
@@ -940,12 +963,13 @@ void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
 
 // unit B's W <- D L^-T for ub (sample, level) pairs, left-looking over the whole width: one strip launch per tile column (column
 // update + panel product with inv(L_kk)^T in the same work item; column 0 takes the panel product alone), which measured level
-// with blocking it like the factorisation (profiles/r04_ab_experiments.md §7).
-void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const TRef& invref, int nt, int ub) {
+// with blocking it like the factorisation (profiles/r04_ab_experiments.md §7).  W has `rows` tile rows: nt for unit B's D, the
+// row tiles of the new individuals for D* (unit_new).
+void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const TRef& invref, int nt, int ub, int rows) {
     for (int k = 0; k < nt; ++k) {
         GemmArgs g{};
         g.A = W; g.B = Ls; g.C = W; g.F = invref; g.fk = k;
-        g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = nt; g.mj = 1; g.nbatch = ub; g.ntiles = nt;
+        g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = rows; g.mj = 1; g.nbatch = ub; g.ntiles = rows;
         g.k0 = 0; g.k1 = k; g.fuse = 1;
         gemm(c, g, s, 3);
     }
@@ -1007,7 +1031,7 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
             launch_dt_build(da, ub, st);
             TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
             invref.bdiv = lc;
-            w_solve(c, *ch.s, W, Ls, invref, nt, ub);
+            w_solve(c, *ch.s, W, Ls, invref, nt, ub, nt);
             GemmArgs g{};            // CovITE (+ jitter) = Delta - W W^T, lower tiles
             g.A = W; g.B = W; g.C = Cm;
             g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt; g.sym = 2;
@@ -1049,6 +1073,51 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     }
 }
 
+// Predictions for new individuals of a chunk.  The mean is one pass over the m x n pairs per sample for all
+// levels and needs no workspace; variance and covariance batch over (sample, level) pairs like unit B: D*(l) (and prior_l B**)
+// into the pair's tiles, W* = D* L^-T against the sample's factor (TRef::bdiv = lc), var from the squared row norms of W*, cov
+// from the lower tiles of prior_l B** + pred_noise I - W* W*^T.
+void unit_new(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    hipStream_t st = ch.s->st;
+    const int nt = sh.nt, mt = sh.mt, L = sh.L, nb = ch.nb;
+    const long long bstride = sh.tiles_per * GP_TSQ, inv_bs = (long long)nt * GP_TSQ;
+    NewArgs na{};
+    static_cast<SampleGrid&>(na) = ch.grid;
+    na.Xnew = io.Xnew; na.Unew = io.Unew; na.un_sstride = (long long)io.m * io.nU; na.m = io.m; na.mt = mt;
+    na.S = io.post.S; na.lv = io.lv.set(L); na.l0 = 0; na.lc = 1; na.pred_noise = io.out.pred_noise;
+    na.alpha = ch.zwork + (long long)nb * sh.Np;
+    na.mean = io.newMean; na.var = io.newVar; na.cov = io.newCov;
+    if (io.newMean) launch_new_mean(na, nb, st);
+    if (sh.new_pairs) {
+        na.W = rect_ref(ch.Wt, (long long)mt * nt * GP_TSQ, nt);
+        na.Cm = io.newCov ? lower_ref(ch.Ct, sh.mlow * GP_TSQ) : TRef{};
+        for (int g0 = 0; g0 < nb; g0 += ch.gs_max) {
+            const int gs = std::min(ch.gs_max, nb - g0);
+            for (int l0 = 0; l0 < L; l0 += ch.lc_max) {
+                const int lc = std::min(ch.lc_max, L - l0);
+                const int ub = gs * lc;                           // (sample, level) pairs of this sub-batch
+                na.s0 = ch.s0 + g0; na.l0 = l0; na.lc = lc;
+                launch_new_build(na, ub, st);
+                TRef Ls = lower_ref(ch.tiles + (long long)g0 * bstride, bstride);
+                Ls.bdiv = lc;
+                TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
+                invref.bdiv = lc;
+                w_solve(c, *ch.s, na.W, Ls, invref, nt, ub, mt);
+                launch_new_var(na, ub, st);
+                if (!io.newCov) continue;
+                GemmArgs g{};            // prior B** + pred_noise I - W* W*^T, lower tiles
+                g.A = na.W; g.B = na.W; g.C = na.Cm;
+                g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = mt; g.mj = mt; g.sym = 2;
+                g.k0 = 0; g.k1 = nt; g.nbatch = ub; g.ntiles = (int)sh.mlow;
+                g.order = tri_order(c, mt);
+                gemm(c, g, *ch.s, 3);
+                launch_new_gather(na, ub, st);
+            }
+        }
+    }
+    HC(hipGetLastError());
+}
+
 // the chunked ensemble driver (device pointers everywhere)
 void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     PredictIO io = io_in;
@@ -1064,6 +1133,12 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     if (io.lv.W && io.lv.G < 1) throw std::runtime_error("weights without a weight column");
     if (io.out.covW && (!io.lv.W || !io.out.varSATE)) throw std::runtime_error("the joint covariance needs weights and varW");
     if (io.lv.W && !io.out.meanSATE && !io.out.varSATE) { io.lv.W = nullptr; io.lv.G = 0; }      // nothing weighted is asked for
+    if (io.newMean || io.newVar || io.newCov) {
+        if (fr.factual) throw std::runtime_error("new individuals have no factual treatment: ordinary levels cannot be predicted for them");
+        if (io.lv.vec || io.m < 1) throw std::runtime_error("new individuals need scalar levels and m >= 1");
+        if (io.newCov && !io.newVar) throw std::runtime_error("the covariance of new individuals needs their variance: its diagonal");
+        if (io.CovITEs || io.out.ite_draws) throw std::runtime_error("new individuals cannot be combined with CovITE or draws: one pair workspace");
+    }
     if (io.nU < 0) io.nU = c->nU;
     if (io.nX < 0) io.nX = c->nX;
     if (!io.Y) { io.Y = c->dY; io.y_sstride = 0; }
@@ -1097,6 +1172,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         if (sh.want_mean) mean_ite(c, io, sh, ch);
         if (sh.want_loo) loo(c, io, sh, ch);
         if (sh.unitB) unit_b(c, io, sh, ch);
+        if (sh.want_new) unit_new(c, io, sh, ch);
     }
     for (auto& s : c->slots) HC(hipStreamSynchronize(s.st));
     HC(hipGetLastError());
@@ -2320,6 +2396,68 @@ int gpslc_y_loo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
     });
 }
 
+// predictions for m new individuals: host pointers; every check before any device work
+int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
+                      const double* yScale, const double* yNoise, int64_t m, const double* Xnew, const double* Unew,
+                      int32_t form, int32_t L, const double* doT, const double* doT_base, double pred_noise, double* mean,
+                      double* var, double* cov) {
+    static const ArgPos kNewArgs{2, 3, 5, 6, 13, 14, 0, 0, 0, 0, true};
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    int rc = validate(c, rq, kNewArgs);
+    if (rc) return rc;
+    if (m < 1 || m > (int64_t)GP_TS * 32767) return bad_arg(c, 9, "m < 1 (or beyond 32767 row tiles)");
+    if ((c->nX > 0) != (Xnew != nullptr)) return bad_arg(c, 10, c->nX > 0 ? "Xnew is NULL but nX > 0" : "Xnew given but nX == 0");
+    if (Xnew && (rc = finite_check(c, Xnew, m * c->nX, 10, "Xnew"))) return rc;
+    if ((c->nU > 0) != (Unew != nullptr)) return bad_arg(c, 11, c->nU > 0 ? "Unew is NULL but nU > 0" : "Unew given but nU == 0");
+    if (Unew && (rc = finite_check(c, Unew, m * c->nU * S, 11, "Unew"))) return rc;
+    if (form != GPSLC_NEW_OUTCOME && form != GPSLC_NEW_CONTRAST && form != GPSLC_NEW_SLOPE)
+        return bad_arg(c, 12, "unknown form (GPSLC_NEW_OUTCOME, GPSLC_NEW_CONTRAST or GPSLC_NEW_SLOPE: the ordinary effect f(a) - f(T) "
+                              "needs a factual treatment, which a new individual does not have)");
+    if ((rc = finite_check(c, doT, L, 14, "doT"))) return rc;
+    if (form == GPSLC_NEW_CONTRAST) {
+        if ((rc = finite_check(c, doT_base, L, 15, "doT_base"))) return rc;
+    } else if (doT_base) {
+        return bad_arg(c, 15, "doT_base given for a form that is no contrast");
+    }
+    if (!std::isfinite(pred_noise)) return bad_arg(c, 16, "pred_noise is not finite");
+    if (!mean && !var && !cov) return bad_arg(c, 17, "mean, var and cov are all NULL");
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        const size_t mm = (size_t)m, SL = (size_t)S * L;
+        c->io.reset();
+        PredictIO io;
+        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
+        io.X = c->dX;
+        io.lv.L = L; io.lv.doT = up(c, doT, (size_t)L);
+        io.lv.form = form == GPSLC_NEW_OUTCOME ? FORM_OUTCOME : form == GPSLC_NEW_SLOPE ? FORM_SLOPE : FORM_CONTRAST;
+        io.lv.base = doT_base ? up(c, doT_base, (size_t)L) : nullptr;
+        io.out.pred_noise = pred_noise;
+        io.m = (int)m;
+        io.Xnew = Xnew ? up(c, Xnew, mm * c->nX) : nullptr;
+        io.Unew = Unew ? up(c, Unew, mm * c->nU * (size_t)S) : nullptr;
+        io.newMean = mean ? c->io.take<double>(mm * SL) : nullptr;
+        io.newVar = (var || cov) ? c->io.take<double>(mm * SL) : nullptr;      // the covariance takes its diagonal from it
+        io.newCov = cov ? c->io.take<double>(mm * mm * SL) : nullptr;
+        io.info = c->io.take<int>((size_t)S);
+        run_predict(c, io);
+        const int st = first_info(c);
+        if (mean) copy_out_large(c, mean, io.newMean, mm * SL * sizeof(double));
+        if (var) copy_out_large(c, var, io.newVar, mm * SL * sizeof(double));
+        if (cov) copy_out_large(c, cov, io.newCov, mm * mm * SL * sizeof(double));
+        if (st > 0)      // a sample whose factorisation broke down: NaN in everything of it
+            for (int64_t s = 0; s < S; ++s) {
+                if (c->last_info[(size_t)s] == 0) continue;
+                for (int64_t l = 0; l < L; ++l) {
+                    const size_t o = mm * (size_t)(s + S * l);
+                    if (mean) std::fill(mean + o, mean + o + mm, NAN);
+                    if (var) std::fill(var + o, var + o + mm, NAN);
+                    if (cov) std::fill(cov + mm * o, cov + mm * (o + mm), NAN);
+                }
+            }
+        return st;
+    });
+}
+
 int gpslc_gp_logpdf(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_t f_shared, const double* ls,
                     const double* scale, const double* noise, const double* target, int32_t t_shared,
                     double* logpdf) {
@@ -2499,8 +2637,8 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
             HC(hipMemcpyAsync(W1.base, Kt.base, (size_t)rs * 8, hipMemcpyDeviceToDevice, st));
             HC(hipMemcpyAsync(W2.base, KsTt.base, (size_t)rs * 8, hipMemcpyDeviceToDevice, st));
             TRef invref = TRef{inv.as<double>(), (long long)nt * GP_TSQ, 1, 0, 0, 0};
-            w_solve(c, slot, W1, M, invref, nt, 1);
-            w_solve(c, slot, W2, M, invref, nt, 1);
+            w_solve(c, slot, W1, M, invref, nt, 1, nt);
+            w_solve(c, slot, W2, M, invref, nt, 1, nt);
             // C11 = K - W1 W1', C12 = Ks - W1 W2', C21 = Ks' - W2 W1', C22 = Kss - W2 W2'   (src/likelihood.jl:46-49)
             auto block = [&](const TRef& Cm, const TRef& Wa, const TRef& Wb, double* host) {
                 if (!host) return;

@@ -344,6 +344,44 @@ void launch_loo_diagonal(const GemmArgs& g, int nt, int d, hipStream_t st);
 void launch_loo_rownorm(const LooArgs& a, int nbatch, hipStream_t st);    // c_r = sum_{k >= i} sum_col W(i, k)[r, col]^2
 void launch_loo_finish(const LooArgs& a, int nbatch, hipStream_t st);     // alpha, c, Y -> looMean, looVar, looLpd for the rows < n
 
+// ---------------------------------------------------------------------------------------
+// Predictions for new individuals (k_new.hip): the rows of B* (m x n) and B** (m x m) come from the caller's
+// features [Unew_s | Xnew], the columns of B* from the training grid.  NewGrid is a SampleGrid with that second row source;
+// stage_scaled_new_features forms x * (1.0 / ls) as stage_scaled_features does, so a new individual that copies a training
+// individual gets that individual's row of B bit for bit.  fp64 only.
+// ---------------------------------------------------------------------------------------
+struct NewGrid : SampleGrid {
+    const double* Xnew;     // m x nX, column-major
+    const double* Unew;     // m x nU x S, offset to sample 0 of the call like SampleParams::U
+    long long un_sstride;   // doubles between the Unew blocks of consecutive samples (m*nU)
+    int m, mt;              // new individuals and their row tiles, mt = ceil(m / 128)
+    __host__ __device__ const double* new_column(long long s, int f) const {      // feature f of sample s: m values
+        return f < nU ? Unew + s * un_sstride + (long long)f * m : Xnew + (long long)(f - nU) * m;
+    }
+};
+template <int COUNT>
+__device__ __forceinline__ void stage_scaled_new_features(const NewGrid& a, long long s, int F, int FS, int g0, double* dst) {
+    for (int idx = threadIdx.x; idx < FS * COUNT; idx += 256) {
+        const int f = idx / COUNT, r = idx % COUNT;
+        dst[idx] = (f < F && g0 + r < a.m) ? a.new_column(s, f)[g0 + r] * (1.0 / a.lengthscale(s, f)) : 0.0;
+    }
+}
+struct NewArgs : NewGrid {
+    long long S;
+    LevelSet lv;            // scalar levels of a non-factual form
+    int l0, lc;             // the tile kernels' batch element b = (sample s0 + b / lc, level l0 + b % lc); the mean kernel's b = sample s0 + b
+    double pred_noise;
+    const double* alpha;    // [sample of the chunk][Np]: A alpha = Y
+    TRef W;                 // mt x nt rectangular: D*(l), then W*(l) = D*(l) L^-T
+    TRef Cm;                // lower packed mt: prior_l B** + pred_noise I, then the covariance (base null: not asked for)
+    double* mean; double* var;   // m x S x L: element (i, s, l) at i + m*(s + S*l)
+    double* cov;            // m x m x S x L: element (i, i', s, l) at i + m*(i' + m*(s + S*l))
+};
+void launch_new_mean(const NewArgs& a, int nbatch, hipStream_t st);      // mean = (B* R)[i, l], R[j, l] = cross_j(l) alpha_j, all L levels
+void launch_new_build(const NewArgs& a, int nbatch, hipStream_t st);     // W <- D*(l) (zero padding), Cm <- prior_l B** + pred_noise I
+void launch_new_var(const NewArgs& a, int nbatch, hipStream_t st);       // var = (prior_l yScale - ||row of W||^2) + pred_noise
+void launch_new_gather(const NewArgs& a, int nbatch, hipStream_t st);    // Cm -> cov, both triangles; the diagonal is var
+
 void launch_rbf_log(const double* X1, const double* X2, long long n, int d, const double* ls,
                     int ls_len, double* out, hipStream_t st);
 void launch_process_cov(const double* in, long long n, double scale, double noise, double* out,

@@ -69,9 +69,12 @@ template <typename Fn> __device__ __forceinline__ void pair_mfma_each_column(int
         }
 }
 
-template <int FREG, bool WK, int BIN, typename StageX, typename Store>
-__device__ __forceinline__ void pair_mfma_body(const SampleGrid& a, long long s, int ncols, double* sm, StageX&& stage_x,
-                                               Store&& store) {
+// stage_rows(F, g0, fr): the features / LS of the 128 rows from g0 into fr [F][128], zeros beyond the row source's end.  The rows
+// may come from another set of individuals than the columns (k_new.hip: new individuals against the training grid) — then
+// WK must be false: e_rc needs the rows' T.  Row block = blockIdx.x.
+template <int FREG, bool WK, int BIN, typename StageRows, typename StageX, typename Store>
+__device__ __forceinline__ void pair_mfma_body_rows(const SampleGrid& a, long long s, int ncols, double* sm, StageRows&& stage_rows,
+                                                    StageX&& stage_x, Store&& store) {
     const int F = a.nU + a.nX;
     double* etab = sm;                       // [32] 2^(j/32): table-driven exp (gp_math.h)
     double* fr = etab + GP_EXP_TAB_DOUBLES;
@@ -84,7 +87,7 @@ __device__ __forceinline__ void pair_mfma_body(const SampleGrid& a, long long s,
     const int ib = blockIdx.x;
     const int n = a.n, Np = a.nt * GP_TS;
 
-    stage_scaled_features<GP_TS>(a, s, F, F, ib * GP_TS, fr);
+    stage_rows(F, ib * GP_TS, fr);
     const double ys = a.p.yScale[s];
     const double tl = a.p.tyLS[s];
     const double wt = 1.0 / (tl * tl);
@@ -173,4 +176,12 @@ __device__ __forceinline__ void pair_mfma_body(const SampleGrid& a, long long s,
 #pragma unroll
         for (int m = 0; m < 2; ++m) store(ib * GP_TS + 32 * wave + 16 * m + li, l0, nl, accB[m], accK[WK ? m : 0]);
     }
+}
+
+// rows and columns from the same grid: the body of ite_mean_mfma_kernel and wsum_mfma_kernel
+template <int FREG, bool WK, int BIN, typename StageX, typename Store>
+__device__ __forceinline__ void pair_mfma_body(const SampleGrid& a, long long s, int ncols, double* sm, StageX&& stage_x,
+                                               Store&& store) {
+    pair_mfma_body_rows<FREG, WK, BIN>(
+        a, s, ncols, sm, [&](int F, int g0, double* fr) { stage_scaled_features<GP_TS>(a, s, F, F, g0, fr); }, stage_x, store);
 }

@@ -426,6 +426,38 @@ int gpslc_predict_outcome_vec(gpslc_ctx* ctx, int64_t S, const double* U, const 
                               int32_t spp, uint64_t seed, const double* z_or_null,
                               double* meanSATE, double* varSATE, double* meanITE, double* ite_draws);
 
+/* Predictions for NEW individuals: m individuals that are not in the data, with covariates x*_i (Xnew, m x nX column-major; NULL
+ * iff nX == 0) and, per posterior sample, latent confounders u*_i(s) (Unew, m x nU x S; NULL iff nU == 0) — the caller's to
+ * supply: a new member of a known object copies a member's U[:, :, s]; an unseen object would need an integral over its U, which
+ * is not closed form and not offered.  No reference counterpart: the textbook GP prediction at new inputs from the factorisation
+ * of gpslc_predict.  Per sample, with w*_i = [u*_i(s) | x*_i], B*_ij = yScale exp(-sum_f ((w*_if - w_jf) / l_f)^2) (m x n), B** the
+ * same between two new individuals, A = K + yNoise I = L L', alpha = A^-1 Y, and for level l of one of the three forms
+ *     GPSLC_NEW_OUTCOME   f*(a), a = doT[l]                          cross_j = r^a_j                  prior = 1
+ *     GPSLC_NEW_CONTRAST  f*(a) - f*(b), b = doT_base[l] (the CATE)  cross_j = r^a_j - r^b_j          prior = 2 (1 - rho(a, b))
+ *     GPSLC_NEW_SLOPE     d f*(t) / dt at t = a                      cross_j = 2 (T_j - a) r^a_j / tyLS^2   prior = 2 / tyLS^2
+ * (r^x_j = rho(T_j, x), rho(x, y) = exp(-(x - y)^2 / tyLS^2); the latent surface, no yNoise):
+ *     D*_ij = B*_ij cross_j      mean_i = sum_j D*_ij alpha_j      W* = D* L^-T
+ *     var_i = (prior yScale - ||row i of W*||^2) + pred_noise      cov_ii' = prior B**_ii' - (W* W*')_ii' + pred_noise [i == i']
+ * The ordinary effect f(a) - f(T_i) needs a factual treatment of the new individual: it is the contrast with b = T*, and no form
+ * of this call.  doT (L) and doT_base (L; contrast only, else NULL) are finite scalars.
+ * Outputs (host; each may be NULL, not all three): mean, var m x S x L — element (i, s, l) at i + m*(s + S*l); cov m x m x S x L —
+ * element (i, i', s, l) at i + m*(i' + m*(s + S*l)), exactly symmetric, its diagonal bit-identical to var.  mean and var of a new
+ * individual do not depend on which others share the call; every output is bit-reproducible and independent of chunking, streams
+ * and the factorisation schedule.  A new individual that copies a training individual (same x, same u(s)) reproduces that
+ * individual's row of gpslc_ite_distributions_outcome / _contrast / _slope.  A contrast with a == b gives mean 0.0, var pred_noise
+ * and off-diagonal cov 0.0 exactly.  A sample whose factorisation breaks down gets NaN in all its outputs; the call returns the
+ * first failing pivot and gpslc_last_info every sample's, as gpslc_y_loo.
+ * Errors: m < 1: -9; Xnew / Unew NULL-ness against nX / nU, or a non-finite entry: -10 / -11; unknown form: -12; L < 1: -13; doT
+ * NULL or non-finite: -14; doT_base missing for a contrast, given for another form, or non-finite: -15; all outputs NULL: -17.
+ * fp64 only (GPSLC_ERR_UNSUPPORTED on a GPSLC_FLAG_FP32_KERNEL ctx); no _dev variant; not sharded; no draws.   */
+#define GPSLC_NEW_OUTCOME 0
+#define GPSLC_NEW_CONTRAST 1
+#define GPSLC_NEW_SLOPE 2
+int gpslc_predict_new(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                      const double* tyLS, const double* yScale, const double* yNoise, int64_t m,
+                      const double* Xnew, const double* Unew, int32_t form, int32_t L, const double* doT,
+                      const double* doT_base, double pred_noise, double* mean, double* var, double* cov);
+
 /* The same call sharded over several GPUs of one node: what the loop of predictCounterfactualEffects (src/prediction.jl:30-33)
  * over the posterior samples (src/estimation.jl:78-84) becomes when the ensemble is partitioned.  ctxs[0..nctx) are
  * DISTINCT contexts created with the same (n, nX, nU), one per device (gpslc_create(&ctx_k, device_k, ...)), each holding the data

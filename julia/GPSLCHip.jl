@@ -180,6 +180,31 @@ function y_loo(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS, ty
     looMean, looVar, looLpd, lp
 end
 
+const NEW_OUTCOME, NEW_CONTRAST, NEW_SLOPE = Int32(0), Int32(1), Int32(2)     # GPSLC_NEW_*: the `form` of predict_new
+
+"""Predictions for m individuals who are not in the data (gpslc_predict_new): `(mean, var, cov)` — mean and var m x S x L, cov
+m x m x S x L (`nothing` unless asked for) — of the latent outcome f*(doT[l]) (NEW_OUTCOME), the contrast f*(doT[l]) -
+f*(doT_base[l]) (NEW_CONTRAST) or the slope at doT[l] (NEW_SLOPE) at the new covariates `Xnew` (m x nX, `nothing` iff nX == 0)
+and the caller's latent confounders `Unew` (m x nU x S, `nothing` iff nU == 0: a new member of a known object copies a member's
+U[:, :, s]).  `m` has to be given only for a model with neither.  A failed factorisation throws PosDefException."""
+function predict_new(c::Ctx, S::Integer, U, uyLS, xyLS, tyLS::Vector{Float64}, yScale::Vector{Float64},
+                     yNoise::Vector{Float64}, Xnew, Unew, form::Integer, doT::Vector{Float64}, doT_base,
+                     pred_noise::Float64; m::Integer=(Xnew !== nothing ? size(Xnew, 1) : Unew !== nothing ? size(Unew, 1) : 1),
+                     want_var::Bool=true, want_cov::Bool=false)
+    L = length(doT)
+    Uf, uy, xy, Xn, Un, base = f64(U), f64(uyLS), f64(xyLS), f64(Xnew), f64(Unew), f64(doT_base)
+    mean = Array{Float64}(undef, m, S, L)
+    var = (want_var || want_cov) ? Array{Float64}(undef, m, S, L) : nothing
+    cov = want_cov ? Array{Float64}(undef, m, m, S, L) : nothing
+    GC.@preserve Uf uy xy tyLS yScale yNoise Xn Un doT base mean var cov check(c, ccall((:gpslc_predict_new, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}),
+        c.h, S, ptr(Uf), ptr(uy), ptr(xy), pointer(tyLS), pointer(yScale), pointer(yNoise), m, ptr(Xn), ptr(Un), form, L,
+        pointer(doT), ptr(base), pred_noise, ptr(mean), ptr(var), ptr(cov)))
+    mean, var, cov
+end
+
 """log N(target; 0, scale exp.(rbfKernelLog(F, F, ls)) + noise I) for S parameter sets: :X => k => :X, :T / :logitT."""
 function gp_logpdf(c::Ctx, S::Integer, nF::Integer, F::Array{Float64}, f_shared::Bool, ls::Array{Float64},
                    scale::Vector{Float64}, noise::Vector{Float64}, target::Array{Float64}, t_shared::Bool)
