@@ -11,6 +11,7 @@ like the reference's own tests:
     predictCounterfactualEffects                  src/prediction.jl:23-36
     yLogpdf                                       src/model_likelihood.jl:83-120 (:Y node score)
     looPredictive, looSummary                     leave-one-out checks of that node's outcome model (no reference counterpart)
+    lgoPredictive, lgoSummary, foldLabels         leave-group-out checks and K-fold cross-validation of it (no reference counterpart)
     predictNew                                    outcome, contrast or slope at individuals who are not in the data (no reference counterpart)
 
 Everything numeric is done by libgpslc_hip.so through the C ABI (``_lib``); this module only
@@ -290,6 +291,22 @@ class Context:
                for k in ("mean", "var", "lpd", "logpdf")}
         st = self.lib.gpslc_y_loo(self.h, S, _p(U), _p(X_or_none), _p(Y_or_none), _p(uyLS), _p(xyLS), _p(tyLS), _p(yScale),
                                   _p(yNoise), _p(out["mean"]), _p(out["var"]), _p(out["lpd"]), _p(out["logpdf"]))
+        return st, out["mean"], out["var"], out["lpd"], out["logpdf"]
+
+    def y_lgo(self, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, G, labels, want=("mean", "var", "lpd", "logpdf")):
+        """gpslc_y_lgo with host arrays as given (None = NULL; ``labels``: n integers in [0, G)): ``(status, lgoMean, lgoVar,
+        lgoLpd, logpdf)`` — the outputs named in ``want`` as (n, S) / (n, S) / (G, S) / (S,) arrays, the others None (NULL to
+        the library).  The status is returned, not raised, as for ``y_loo``."""
+        S, G = int(S), int(G)
+        Sn, Gn = max(S, 0), max(G, 0)
+        shapes = {"mean": (self.n, Sn), "var": (self.n, Sn), "lpd": (Gn, Sn), "logpdf": (Sn,)}
+        out = {k: np.full(shapes[k], np.nan, order="F") if k in want else None for k in shapes}
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32)
+        if lab is not None and lab.shape != (self.n,):
+            raise ValueError(f"labels must have shape ({self.n},), got {lab.shape}")
+        st = self.lib.gpslc_y_lgo(self.h, S, _p(U), _p(X_or_none), _p(Y_or_none), _p(uyLS), _p(xyLS), _p(tyLS), _p(yScale),
+                                  _p(yNoise), G, None if lab is None else lab.ctypes.data_as(_lib.c_int32_p),
+                                  _p(out["mean"]), _p(out["var"]), _p(out["lpd"]), _p(out["logpdf"]))
         return st, out["mean"], out["var"], out["lpd"], out["logpdf"]
 
     def predict_new(self, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, doT, doT_base, pred_noise,
@@ -918,6 +935,68 @@ def looSummary(g: GPSLCObject, X_override=None, Y_override=None, loo=None):
     pointwise = top + np.log(np.mean(np.exp(lpd - top[:, None]), axis=1))
     pit = np.mean(0.5 * (1.0 + np.vectorize(erf)(z / np.sqrt(2.0))), axis=1)
     return {"elpd": np.sum(lpd, axis=0), "pointwise": pointwise, "zscore": z, "pit": pit}
+
+
+def _group_labels(g: GPSLCObject, groups):
+    """``groups`` (None: the object's ``obj`` column) -> (keys, labels): the distinct group keys in ``np.unique``'s order and
+    the int32 label in [0, len(keys)) of every individual"""
+    n = g.getN()
+    if groups is None:
+        groups = getattr(g, "obj", None)
+        if groups is None:
+            raise ValueError("lgoPredictive: this object has no `obj` column to take the groups from; pass groups= (one label per "
+                             "individual, e.g. foldLabels(n, K, seed) for K-fold cross-validation)")
+    groups = np.asarray(groups)
+    if groups.shape != (n,):
+        raise ValueError(f"groups must have one label per individual: shape ({n},), got {groups.shape}")
+    keys, labels = np.unique(groups, return_inverse=True)
+    return keys, np.ascontiguousarray(labels.reshape(n), dtype=np.int32)
+
+
+def lgoPredictive(g: GPSLCObject, groups=None, X_override=None, Y_override=None):
+    """Leave-group-out predictive distribution under the outcome model of every posterior sample (gpslc_y_lgo; Rasmussen &
+    Williams §5.4.2 in block form) -> ``(mean, var, lpd, keys)``: a whole group — by default an object of the hierarchical
+    data (``g.obj``), with ``groups=foldLabels(n, K, seed)`` a cross-validation fold, or any length-n labelling (ints, strings)
+    — is removed and its members predicted jointly from everybody else.  ``mean``, ``var`` (n, S): mean and marginal variance
+    (for the observation: yNoise included) of Y_i given all individuals outside i's group; ``lpd`` (G, S): the joint log
+    density of each group's outcomes under that predictive, row j belonging to group ``keys[j]`` (the distinct labels,
+    sorted).  A group has at most 128 members.  Overrides and errors as ``looPredictive``."""
+    n = g.getN()
+    keys, labels = _group_labels(g, groups)
+    Xo = None if X_override is None else _f(X_override).reshape(n, g.getNX(), order="F")
+    Yo = None if Y_override is None else _f(Y_override, (n,))
+    ctx = g.ctx()
+    st, mean, var, lpd, _ = ctx.y_lgo(g.getNumPosteriorSamples(), g.U, Xo, Yo, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise,
+                                      len(keys), labels, want=("mean", "var", "lpd"))
+    ctx.check(st)
+    return mean, var, lpd, keys
+
+
+def foldLabels(n, K, seed=0):
+    """Labels of K random cross-validation folds of near-equal size (sizes differ by at most one) for n individuals -> (n,)
+    int32 in [0, K): a random permutation dealt round-robin.  Pass as ``lgoPredictive(g, groups=...)``."""
+    n, K = int(n), int(K)
+    if not 1 <= K <= n:
+        raise ValueError(f"foldLabels needs 1 <= K <= n, got K = {K}, n = {n}")
+    labels = np.empty(n, dtype=np.int32)
+    labels[np.random.default_rng(seed).permutation(n)] = np.arange(n, dtype=np.int32) % K
+    return labels
+
+
+def lgoSummary(g: GPSLCObject, groups=None, X_override=None, Y_override=None, lgo=None):
+    """Summaries of ``lgoPredictive`` (host arithmetic only; ``lgo`` = its result, to summarise one already computed):
+
+    ``elpd`` (S,): sum_g lpd[g, s], the leave-group-out log predictive density of every posterior sample — the score to compare
+    models (nU = 0 / 1 / 2) on for hierarchical data; ``groupwise`` (G,): log mean_s exp(lpd[g, s]), the groups the surface
+    misses; ``zscore`` (n, S): the marginal (Y - mean) / sqrt(var); ``pit`` (n,): mean_s Phi(zscore); ``keys`` (G,)."""
+    from math import erf
+    mean, var, lpd, keys = lgoPredictive(g, groups, X_override, Y_override) if lgo is None else lgo
+    Y = g.Y if Y_override is None else _f(Y_override, (g.getN(),))
+    z = (Y[:, None] - mean) / np.sqrt(var)
+    top = np.max(lpd, axis=1)
+    groupwise = top + np.log(np.mean(np.exp(lpd - top[:, None]), axis=1))
+    pit = np.mean(0.5 * (1.0 + np.vectorize(erf)(z / np.sqrt(2.0))), axis=1)
+    return {"elpd": np.sum(lpd, axis=0), "groupwise": groupwise, "zscore": z, "pit": pit, "keys": keys}
 
 
 # ------------------------------------------------------------------------------------------

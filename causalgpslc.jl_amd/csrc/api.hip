@@ -679,6 +679,11 @@ struct PredictIO {
     double* ndraw = nullptr;
     // leave-one-out predictive checks of the outcome model (gpslc_y_loo): n x S each, device, or null
     double *looMean = nullptr, *looVar = nullptr, *looLpd = nullptr;
+    // leave-group-out predictive checks (gpslc_y_lgo): the members sorted by (group, row) with the G + 1 offsets
+    // into them (device), and the outputs: n x S, n x S, G x S (device, or null)
+    int lgoG = 0, lgoMmax = 0;       // groups; members of the largest
+    const int *lgoMembers = nullptr, *lgoOffsets = nullptr;
+    double *lgoMean = nullptr, *lgoVar = nullptr, *lgoLpd = nullptr;
     // predictions for m new individuals (gpslc_predict_new): their features (device; Xnew m x nX, Unew m x nU x S)
     // and the outputs, m x S x L each and m x m x S x L (device, or null).  newCov needs newVar: its diagonal
     const double *Xnew = nullptr, *Unew = nullptr;
@@ -719,7 +724,8 @@ struct PredictShape {
     int n, nt, L, R, naug, ntot;      // R: right-hand sides beside Y — one per level, or L*G with weight columns
     long long Np, tiles_per, nlow;   // padded N, tiles of A with its augmented rows, tiles of an nt x nt triangle
     bool with_sums, want_cov, want_draws, want_mean, unitB;     // unitB: full ITE covariance (CovITE, draws)
-    bool want_loo, want_alpha;        // leave-one-out outputs; alpha = A^-1 Y is wanted (by the MeanITE pass or by them)
+    bool want_loo, want_lgo, want_w;  // leave-one-out outputs, leave-group-out outputs; W = L^-T is wanted (by either)
+    bool want_alpha;                  // alpha = A^-1 Y is wanted (by the MeanITE pass or by them)
     int mt = 0;                       // new individuals: their row tiles, the tiles of an mt x mt triangle, and whether the
     long long mlow = 0;               // (sample, level) pairs need tile workspace (variance, covariance)
     bool want_new = false, new_pairs = false;
@@ -728,7 +734,8 @@ struct PredictShape {
           Np((long long)nt * GP_TS), tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2),
           with_sums(io.out.meanSATE || io.out.varSATE || io.out.covW), want_cov(io.CovITEs != nullptr), want_draws(io.out.ite_draws != nullptr),
           want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws),
-          want_loo(io.looMean || io.looVar || io.looLpd), want_alpha(want_mean || want_loo || io.newMean) {
+          want_loo(io.looMean || io.looVar || io.looLpd), want_lgo(io.lgoMean || io.lgoVar || io.lgoLpd), want_w(want_loo || want_lgo),
+          want_alpha(want_mean || want_w || io.newMean) {
         want_new = io.newMean || io.newVar || io.newCov;
         new_pairs = io.newVar || io.newCov;
         mt = (io.m + GP_TS - 1) / GP_TS;
@@ -785,7 +792,8 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     if (io.lv.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
     if (io.ndraw) b.znode = take(draws_image_doubles(1, sh.Np));        // operand image of the node draw's normals
-    if (sh.want_loo) { b.loo_w = take((size_t)sh.nlow * GP_TSQ); b.loo_c = take(sh.Np); }
+    if (sh.want_w) b.loo_w = take((size_t)sh.nlow * GP_TSQ);
+    if (sh.want_loo) b.loo_c = take(sh.Np);
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
     if (sh.new_pairs) {       // new individuals: W* (mt x nt) and, with the covariance, an mt triangle per (sample, level) pair
         const size_t w_tiles = (size_t)sh.mt * nt, c_tiles = io.newCov ? (size_t)sh.mlow : 0;
@@ -976,7 +984,7 @@ void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const T
 }
 
 // Leave-one-out predictive checks of a chunk: c = diag(A^-1) as the squared row norms of W = L^-T, then the
-// outputs from alpha, c and Y.  W is built block diagonal by block diagonal, one launch each: diagonal d holds the tiles
+// outputs from alpha, c and Y; and / or its leave-group-out checks (§20) from the same W and alpha.  W is built block diagonal by block diagonal, one launch each: diagonal d holds the tiles
 // (i, i + d) of all tile rows and matrices, each a chain of d tile products from kk = i on (nt^3/6 products in all, the
 // factorisation's count); the tile rows of a matrix are independent chains, so nt x nb of them are in flight.
 void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
@@ -1001,8 +1009,18 @@ void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk&
         g.queue = ch.s->queue;
         launch_loo_diagonal(g, nt, d, st);
     }
-    launch_loo_rownorm(la, nb, st);
-    launch_loo_finish(la, nb, st);
+    if (sh.want_loo) {
+        launch_loo_rownorm(la, nb, st);
+        launch_loo_finish(la, nb, st);
+    }
+    if (sh.want_lgo) {      // leave-group-out: one workgroup per (group, sample) on the same W and alpha
+        LgoArgs ga{};
+        ga.W = la.W; ga.w_bstride = la.w_bstride; ga.n = la.n; ga.nt = nt; ga.s0 = la.s0; ga.G = io.lgoG; ga.mmax = io.lgoMmax;
+        ga.members = io.lgoMembers; ga.offsets = io.lgoOffsets;
+        ga.alpha = la.alpha; ga.Y = la.Y; ga.y_sstride = la.y_sstride; ga.info = la.info;
+        ga.lgoMean = io.lgoMean; ga.lgoVar = io.lgoVar; ga.lgoLpd = io.lgoLpd;
+        launch_lgo_groups(ga, nb, st);
+    }
     HC(hipGetLastError());
     (void)c;
 }
@@ -1170,7 +1188,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         const bool back_done = unit_a(c, io, sh, ch);
         if (sh.want_alpha && !back_done) back_substitute(sh, ch);
         if (sh.want_mean) mean_ite(c, io, sh, ch);
-        if (sh.want_loo) loo(c, io, sh, ch);
+        if (sh.want_w) loo(c, io, sh, ch);
         if (sh.unitB) unit_b(c, io, sh, ch);
         if (sh.want_new) unit_new(c, io, sh, ch);
     }
@@ -1696,7 +1714,7 @@ struct ArgPos { int S, U, xyLS, tyLS, L, doT, base, G, W, spp; bool fp64_only; i
 static const ArgPos kPredictArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, false}, kPredictVecArgs{2, 3, 5, 6, 9, 10, 0, 0, 0, 12, true},
     kPredictContrastArgs{2, 3, 5, 6, 9, 10, 11, 0, 0, 13, true}, kPredictWeightedArgs{2, 3, 5, 6, 9, 10, 11, 12, 13, 15, true},
     kPredictMultiArgs{3, 4, 6, 7, 10, 11, 0, 0, 0, 13, false},      // two more leading arguments: nctx, ctxs
-    kSamplesArgs{2, 3, 5, 6, 0, 0, 0, 0, 0, 0, false},      // gpslc_ite_distributions, gpslc_y_logpdf, gpslc_y_loo, gpslc_likelihood_distribution
+    kSamplesArgs{2, 3, 5, 6, 0, 0, 0, 0, 0, 0, false},      // gpslc_ite_distributions, gpslc_y_logpdf, gpslc_y_loo, gpslc_y_lgo, gpslc_likelihood_distribution
     kIteVecArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true}, kIteContrastArgs{2, 3, 5, 6, 0, 9, 10, 0, 0, 0, true},
     kLikelihoodVecArgs{2, 3, 5, 6, 0, 8, 0, 0, 0, 0, false},
     kPredictSlopeArgs{2, 3, 5, 6, 9, 10, 0, 11, 12, 14, true, 19}, kIteSlopeArgs{2, 3, 5, 6, 0, 9, 0, 0, 0, 0, true};
@@ -2392,6 +2410,68 @@ int gpslc_y_loo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
         if (looMean) copy_out_large(c, looMean, io.looMean, nS * sizeof(double));
         if (looVar) copy_out_large(c, looVar, io.looVar, nS * sizeof(double));
         if (looLpd) copy_out_large(c, looLpd, io.looLpd, nS * sizeof(double));
+        return st;
+    });
+}
+
+// leave-group-out checks: gpslc_y_loo's call with a labelling; every check before any device work
+int gpslc_y_lgo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                int32_t G, const int32_t* labels, double* lgoMean, double* lgoVar, double* lgoLpd, double* logpdf_or_null) {
+    const PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 0, nullptr);
+    int rc = validate(c, rq, kSamplesArgs);
+    if (rc) return rc;
+    const int64_t n = c->n;
+    if (G < 1 || G > n) return bad_arg(c, 11, "G < 1 or G > n");
+    if (!labels) return bad_arg(c, 12, "labels is NULL");
+    // the member list sorted by (group, row): a counting sort, rows ascending inside every group
+    std::vector<int> offsets((size_t)G + 1, 0), members((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (labels[i] < 0 || labels[i] >= G) return bad_arg(c, 12, "a label is outside [0, G)");
+        ++offsets[(size_t)labels[i] + 1];
+    }
+    for (int32_t g = 0; g < G; ++g) {
+        if (offsets[(size_t)g + 1] == 0) return bad_arg(c, 12, "a group has no member");
+        offsets[(size_t)g + 1] += offsets[g];
+    }
+    if (!lgoMean && !lgoVar && !lgoLpd) return bad_arg(c, 13, "lgoMean, lgoVar and lgoLpd are all NULL");
+    int mmax = 0;
+    for (int32_t g = 0; g < G; ++g) {
+        const int m = offsets[(size_t)g + 1] - offsets[g];
+        mmax = std::max(mmax, m);
+        if (m > LGO_MAX_GROUP) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "group %d has %d members: gpslc_y_lgo takes groups of at most %d", (int)g, m, LGO_MAX_GROUP);
+            set_err(c, buf);
+            return GPSLC_ERR_UNSUPPORTED;
+        }
+    }
+    {
+        std::vector<int> fill(offsets.begin(), offsets.end() - 1);
+        for (int64_t i = 0; i < n; ++i) members[(size_t)fill[labels[i]]++] = (int)i;
+    }
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        const size_t nn = (size_t)n, nS = nn * (size_t)S, GS = (size_t)G * (size_t)S;
+        c->io.reset();
+        PredictIO io;
+        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
+        io.X = (X_or_null && c->nX) ? up(c, X_or_null, nn * c->nX) : c->dX;
+        if (Y_or_null) { io.Y = up(c, Y_or_null, nn); io.y_sstride = 0; }
+        int* dmem = c->io.take<int>(nn);
+        int* doff = c->io.take<int>((size_t)G + 1);
+        HC(hipMemcpy(dmem, members.data(), nn * sizeof(int), hipMemcpyHostToDevice));
+        HC(hipMemcpy(doff, offsets.data(), ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice));
+        io.lgoG = G; io.lgoMmax = mmax; io.lgoMembers = dmem; io.lgoOffsets = doff;
+        io.lgoMean = lgoMean ? c->io.take<double>(nS) : nullptr;
+        io.lgoVar = lgoVar ? c->io.take<double>(nS) : nullptr;
+        io.lgoLpd = lgoLpd ? c->io.take<double>(GS) : nullptr;
+        std::vector<double> lp(logpdf_or_null ? 0 : (size_t)S);
+        const int st = tiled_score(c, io, logpdf_or_null ? logpdf_or_null : lp.data());
+        if (st < 0) return st;
+        if (lgoMean) copy_out_large(c, lgoMean, io.lgoMean, nS * sizeof(double));
+        if (lgoVar) copy_out_large(c, lgoVar, io.lgoVar, nS * sizeof(double));
+        if (lgoLpd) copy_out_large(c, lgoLpd, io.lgoLpd, GS * sizeof(double));
         return st;
     });
 }

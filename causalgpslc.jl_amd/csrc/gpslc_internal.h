@@ -345,6 +345,24 @@ void launch_loo_rownorm(const LooArgs& a, int nbatch, hipStream_t st);    // c_r
 void launch_loo_finish(const LooArgs& a, int nbatch, hipStream_t st);     // alpha, c, Y -> looMean, looVar, looLpd for the rows < n
 
 // ---------------------------------------------------------------------------------------
+// Leave-group-out predictive checks (k_lgo.hip): for a group I of m <= LGO_MAX_GROUP individuals,
+// C = [A^-1]_II = W[I, :] W[I, :]^T from the same packed W, then its m x m Cholesky factor in LDS.  One workgroup per
+// (group, sample).  Larger groups would need a tiled factorisation of C: refused at the C boundary.
+// ---------------------------------------------------------------------------------------
+#define LGO_MAX_GROUP GP_TS
+struct LgoArgs {
+    const double* W; long long w_bstride;       // [b][nt (nt + 1) / 2 tiles], loo_w_index
+    int n, nt; long long s0;
+    int G, mmax;                                // groups; members of the largest (sizes the launch's LDS)
+    const int* members; const int* offsets;     // rows sorted by (group, row); G + 1 offsets into them
+    const double* alpha;                        // [b][Np]
+    const double* Y; long long y_sstride;
+    const int* info;                            // S: a sample whose factorisation broke down gets NaN
+    double* lgoMean; double* lgoVar; double* lgoLpd;   // n x S, n x S, G x S (element (g, s) at g + G*s) or null
+};
+void launch_lgo_groups(const LgoArgs& a, int nbatch, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // Predictions for new individuals (k_new.hip): the rows of B* (m x n) and B** (m x m) come from the caller's
 // features [Unew_s | Xnew], the columns of B* from the training grid.  NewGrid is a SampleGrid with that second row source;
 // stage_scaled_new_features forms x * (1.0 / ls) as stage_scaled_features does, so a new individual that copies a training

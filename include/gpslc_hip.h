@@ -152,6 +152,34 @@ int gpslc_y_loo(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_or_n
                 double* looMean /* n x S */, double* looVar /* n x S */, double* looLpd /* n x S */,
                 double* logpdf_or_null /* S */);
 
+/* Leave-group-out (LGO) predictive checks of the same outcome model: a whole group of individuals (the members of an object;
+ * a cross-validation fold) is removed and predicted jointly from everybody else.  labels[i] in [0, G) is the group of
+ * individual i; every group has at least one member and at most 128.  For a group I of m members, alpha = A^-1 Y and
+ * C = [A^-1]_II (Rasmussen & Williams §5.4.2 in block form), for every parameter set s:
+ *   lgoMean[i + n*s] = [Y_I - C^-1 alpha_I]_i         mean of Y_i given every individual outside i's group
+ *   lgoVar[i + n*s]  = [C^-1]_ii                      its marginal variance: for the OBSERVATION, yNoise included
+ *   lgoLpd[g + G*s]  = -(m/2) log(2 pi) + log det(C)/2 - alpha_I^T C^-1 alpha_I / 2      joint log density of the whole group
+ * C is a Gram matrix of rows of L^-T from the tiled factor (a sum of products, no subtraction from a prior term), factorised
+ * C = R R^T in the workgroup's local memory; lgoVar is the squared norm of a column of R^-1, a sum of squares.
+ * Arguments 1-10, validation, overrides and logpdf_or_null are gpslc_y_loo's (logpdf_or_null is bit-identical to that call's);
+ * works on a GPSLC_FLAG_FP32_KERNEL context.  Any output may be NULL.  Errors: G < 1 or G > n: -11; labels NULL, a label
+ * outside [0, G) or a group without a member: -12; lgoMean, lgoVar and lgoLpd all NULL: -13; a group of more than 128 members:
+ * GPSLC_ERR_UNSUPPORTED, gpslc_last_error names the group and its size (larger groups would need a tiled factorisation of C:
+ * out of scope).  S = 0 is an empty call.
+ * A parameter set whose factorisation of A breaks down gets NaN in all its outputs; return value (first failing pivot) and
+ * gpslc_last_info as for gpslc_y_loo.  A group whose C loses positive definiteness in the small factorisation gets NaN in its
+ * outputs for that parameter set; the return value and gpslc_last_info do not change.
+ * Guarantees: the outputs are bit-reproducible and independent of chunking, stream count and factorisation schedule.  A
+ * group's outputs depend only on its member set, the members taken in ascending row order: not on its label number, not on
+ * how the other individuals are grouped.  Groups of one member give gpslc_y_loo's values to rounding (the summation order
+ * differs); one group of everybody (n <= 128) gives lgoLpd = logpdf, lgoMean = 0 (the prior mean) and lgoVar = diag(A), to
+ * rounding.  There is no _dev variant, no sharding over several contexts and no joint covariance output. */
+int gpslc_y_lgo(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                int32_t G, const int32_t* labels /* n, values in [0, G) */,
+                double* lgoMean /* n x S */, double* lgoVar /* n x S */, double* lgoLpd /* G x S */,
+                double* logpdf_or_null /* S */);
+
 /* ---- the other Gaussian-process nodes of the Gen models -------------- */
 
 /* log N(target; 0, scale * exp.(rbfKernelLog(F, F, ls)) + noise * I) for S parameter sets: the score of

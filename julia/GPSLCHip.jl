@@ -180,6 +180,26 @@ function y_loo(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS, ty
     looMean, looVar, looLpd, lp
 end
 
+"""Leave-group-out predictive checks of the :Y node's outcome model for S parameter sets (gpslc_y_lgo): `labels[i]` in
+`0:G-1` is the group of individual i (every group has 1 to 128 members).  Returns `(lgoMean, lgoVar, lgoLpd, logpdf)`: the
+first two n x S — mean and marginal variance (yNoise included) of every Y_i given everybody outside i's group —, lgoLpd
+G x S — the joint log density of each whole group under that predictive —, the last the node's score."""
+function y_lgo(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS, tyLS::Vector{Float64},
+               yScale::Vector{Float64}, yNoise::Vector{Float64}, G::Integer, labels::AbstractVector{<:Integer})
+    length(labels) == c.n || throw(ArgumentError("labels must have one entry per individual"))
+    lab = Vector{Int32}(labels)
+    lgoMean, lgoVar = (Matrix{Float64}(undef, c.n, S) for _ in 1:2)
+    lgoLpd = Matrix{Float64}(undef, G, S)
+    lp = Vector{Float64}(undef, S)
+    Uf, Xf, Yf, uy, xy = f64(U), f64(X_or_nothing), f64(Y_or_nothing), f64(uyLS), f64(xyLS)
+    GC.@preserve Uf Xf Yf uy xy tyLS yScale yNoise lab lgoMean lgoVar lgoLpd lp check(c, ccall((:gpslc_y_lgo, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(Uf), ptr(Xf), ptr(Yf), ptr(uy), ptr(xy), pointer(tyLS), pointer(yScale), pointer(yNoise),
+        G, pointer(lab), pointer(lgoMean), pointer(lgoVar), pointer(lgoLpd), pointer(lp)))
+    lgoMean, lgoVar, lgoLpd, lp
+end
+
 const NEW_OUTCOME, NEW_CONTRAST, NEW_SLOPE = Int32(0), Int32(1), Int32(2)     # GPSLC_NEW_*: the `form` of predict_new
 
 """Predictions for m individuals who are not in the data (gpslc_predict_new): `(mean, var, cov)` — mean and var m x S x L, cov
