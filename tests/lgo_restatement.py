@@ -126,3 +126,69 @@ def with_block(n, lo, hi, rest=17):
     lab[others] = np.arange(len(others)) // rest
     lab[lo:hi] = (lab[others].max() + 1) if len(others) else 0
     return lab.astype(np.int32)
+
+
+# ---- group sizes and placements (tests/test_lgo_sizes.py, tests/test_gpu_lgo_sizes.py) ---------------------------------------
+# lgo_group_kernel picks its layout from the padded size mp = 16 ceil(m / 16): slab width 128, 64, 32, 32, 16, 16, 16, 16 and
+# 1, 3, 6, 10, 15, 21, 28, 36 lower blocks of C over four waves for mp = 16 .. 128; its gather starts at the tile row k0 of the
+# group's first member and a member contributes zeros before its own tile row.
+SIZES_N = 640                                               # five tiles
+SIZES = (33, 48, 49, 80, 81, 96, 97, 112, 44)               # mp = 48, 48, 64, 80, 96, 96, 112, 112, 48; sums to 640
+LATE_SIZES = (33, 48, 80, 96, 112, 15)                      # rows 256..639: mp = 48, 48, 80, 96, 112, 16
+LATER_SIZES = (128, 113, 64, 50, 32, 31, 17, 16, 61)        # rows 128..639: mp = 128, 128, 64, 64, 32, 32, 32, 16, 64
+EDGE_N = 300                                                # three tiles
+EDGE_SIZES = (15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 79, 80, 81, 95, 96, 97, 111, 112, 113, 127, 128)
+
+
+def padded(m):
+    return 16 * ((m + 15) // 16)
+
+
+def _dealt(rows, sizes, first_label):
+    """labels for `rows` (already in the order they are dealt): the first sizes[0] get first_label, the next sizes[1] the next"""
+    assert sum(sizes) == len(rows)
+    return np.repeat(first_label + np.arange(len(sizes)), sizes)
+
+
+def size_labellings():
+    """name -> labels (SIZES_N,), every label in use.
+    contiguous: one group of each of SIZES in row order (first members in tile rows 0, 0, 0, 1, 1, 2, 3, 3, 4; several
+                straddle a tile boundary);
+    scattered:  the same sizes dealt through a fixed permutation of the rows (every group has members in all five tile rows);
+    late:       rows 0..255 in blocks of 17, rows 256..639 permuted into groups of LATE_SIZES (first member in tile row 2,
+                members scattered over tile rows 2..4);
+    later:      rows 0..127 in blocks of 17, rows 128..639 permuted into groups of LATER_SIZES (first member in tile row 1,
+                members in tile rows 1..4): with `late`, every mp from 16 to 128 with k0 > 0 and three tile rows or more."""
+    n = SIZES_N
+    out = {"contiguous": _dealt(np.arange(n), SIZES, 0)}
+    lab = np.empty(n, dtype=np.int64)
+    lab[np.random.default_rng(640).permutation(n)] = out["contiguous"]
+    out["scattered"] = lab
+    for name, lo, sizes, seed in (("late", 256, LATE_SIZES, 641), ("later", 128, LATER_SIZES, 642)):
+        lab = np.empty(n, dtype=np.int64)
+        lab[:lo] = np.arange(lo) // 17
+        lab[lo + np.random.default_rng(seed).permutation(n - lo)] = _dealt(np.arange(n - lo), sizes, lab[lo - 1] + 1)
+        out[name] = lab
+    return {k: v.astype(np.int32) for k, v in out.items()}
+
+
+def edge_group(m, n=EDGE_N):
+    """rows of the one group of m members of the size-edge cases: a fixed permutation of the rows that begins with one row of
+    every tile row, so m >= 3 members are scattered over all of them; ascending"""
+    perm = np.random.default_rng(300).permutation(n)
+    firsts = [int(perm[np.argmax(perm // 128 == t)]) for t in range((n + 127) // 128)]
+    order = firsts + [int(p) for p in perm if p not in firsts]
+    return np.sort(np.array(order[:m]))
+
+
+def beside(n, rows, rest):
+    """`rows` as group 0, everybody else in row order in blocks of `rest` (1: singletons) with the labels 1, 2, ..."""
+    lab = np.zeros(n, dtype=np.int64)
+    others = np.setdiff1d(np.arange(n), rows)
+    lab[others] = 1 + np.arange(len(others)) // rest
+    return lab.astype(np.int32)
+
+
+def tile_rows(labels):
+    """per group: the sorted tile rows its members fall in (the first one is the kernel's k0)"""
+    return [sorted(set((I // 128).tolist())) for I in members_of(labels)]
