@@ -11,6 +11,7 @@ like the reference's own tests:
     predictCounterfactualEffects                  src/prediction.jl:23-36
     yLogpdf                                       src/model_likelihood.jl:83-120 (:Y node score)
     looPredictive, looSummary                     leave-one-out checks of that node's outcome model (no reference counterpart)
+    yLogpdfGrad                                   gradient of that node's score in U, the hyper-parameters and Y (no reference counterpart)
     lgoPredictive, lgoSummary, foldLabels         leave-group-out checks and K-fold cross-validation of it (no reference counterpart)
     predictNew                                    outcome, contrast or slope at individuals who are not in the data (no reference counterpart)
 
@@ -308,6 +309,24 @@ class Context:
                                   _p(yNoise), G, None if lab is None else lab.ctypes.data_as(_lib.c_int32_p),
                                   _p(out["mean"]), _p(out["var"]), _p(out["lpd"]), _p(out["logpdf"]))
         return st, out["mean"], out["var"], out["lpd"], out["logpdf"]
+
+    GRAD_OUTPUTS = ("dU", "duyLS", "dxyLS", "dtyLS", "dyScale", "dyNoise", "dY", "logpdf")
+
+    def y_logpdf_grad(self, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, want=GRAD_OUTPUTS):
+        """gpslc_y_logpdf_grad with host arrays as given (None = NULL): ``(status, out)`` with ``out`` a dict of the outputs named
+        in ``want`` — ``dU`` (n, nU, S), ``duyLS`` (nU, S), ``dxyLS`` (nX, S), ``dtyLS``, ``dyScale``, ``dyNoise``, ``logpdf`` (S,),
+        ``dY`` (n, S) — the others None (NULL to the library).  The status is returned, not raised, as for ``y_loo``."""
+        S = int(S)
+        Sn = max(S, 0)
+        shapes = {"dU": (self.n, self.nU, Sn), "duyLS": (self.nU, Sn), "dxyLS": (self.nX, Sn), "dtyLS": (Sn,), "dyScale": (Sn,),
+                  "dyNoise": (Sn,), "dY": (self.n, Sn), "logpdf": (Sn,)}
+        unknown = set(want) - set(shapes)
+        if unknown:
+            raise ValueError(f"unknown gradient outputs {sorted(unknown)}: choose from {self.GRAD_OUTPUTS}")
+        out = {k: np.full(shapes[k], np.nan, order="F") if k in want else None for k in shapes}
+        st = self.lib.gpslc_y_logpdf_grad(self.h, S, _p(U), _p(X_or_none), _p(Y_or_none), _p(uyLS), _p(xyLS), _p(tyLS), _p(yScale),
+                                          _p(yNoise), *[_p(out[k]) for k in self.GRAD_OUTPUTS])
+        return st, out
 
     def predict_new(self, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, doT, doT_base, pred_noise,
                     want=("mean", "var")):
@@ -919,6 +938,27 @@ def looPredictive(g: GPSLCObject, X_override=None, Y_override=None):
     ``yLogpdf``: ``Y_override`` is the outcome vector being checked, a failed factorisation raises ``PosDefException``."""
     mean, var, lpd, _ = _loo_call(g, X_override, Y_override, ("mean", "var", "lpd"))
     return mean, var, lpd
+
+
+def yLogpdfGrad(g: GPSLCObject, X_override=None, Y_override=None, log_params=False):
+    """Gradient of ``yLogpdf`` for every posterior sample (gpslc_y_logpdf_grad; Rasmussen & Williams §5.4.1) -> a dict: ``dU``
+    (n, nU, S), ``duyLS`` (nU, S), ``dxyLS`` (nX, S), ``dtyLS``, ``dyScale``, ``dyNoise`` (S,), ``dY`` (n, S) — each in the layout
+    of what it differentiates — and ``logpdf`` (S,), the score from the same factorisation.  What a gradient-based move on U and
+    the hyper-parameters (HMC, MALA, MAP), a type-II maximum-likelihood start or a sensitivity check of a posterior sample
+    needs.  ``log_params=True``: the five positive parameters' gradients are with respect to their logarithms (multiplied by
+    the parameter, on the host); ``dU`` and ``dY`` are unchanged.  Overrides and errors as ``yLogpdf``; an fp32 context is
+    refused."""
+    n = g.getN()
+    Xo = None if X_override is None else _f(X_override).reshape(n, g.getNX(), order="F")
+    Yo = None if Y_override is None else _f(Y_override, (n,))
+    ctx = g.ctx()
+    st, out = ctx.y_logpdf_grad(g.getNumPosteriorSamples(), g.U, Xo, Yo, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise)
+    ctx.check(st)
+    if log_params:
+        for k, par in (("duyLS", g.uyLS), ("dxyLS", g.xyLS), ("dtyLS", g.tyLS), ("dyScale", g.yScale), ("dyNoise", g.yNoise)):
+            if par is not None and out[k].size:       # a model without U (without X) has no uyLS (xyLS): its block stays empty
+                out[k] = out[k] * _f(par).reshape(out[k].shape, order="F")
+    return out
 
 
 def looSummary(g: GPSLCObject, X_override=None, Y_override=None, loo=None):

@@ -684,6 +684,9 @@ struct PredictIO {
     int lgoG = 0, lgoMmax = 0;       // groups; members of the largest
     const int *lgoMembers = nullptr, *lgoOffsets = nullptr;
     double *lgoMean = nullptr, *lgoVar = nullptr, *lgoLpd = nullptr;
+    // gradient of the outcome log-likelihood (gpslc_y_logpdf_grad): device, in the layouts of the arguments they
+    // differentiate (gU n x nU x S, guyLS nU x S, gxyLS nX x S, the others S; gY n x S), or null
+    double *gU = nullptr, *guyLS = nullptr, *gxyLS = nullptr, *gtyLS = nullptr, *gyScale = nullptr, *gyNoise = nullptr, *gY = nullptr;
     // predictions for m new individuals (gpslc_predict_new): their features (device; Xnew m x nX, Unew m x nU x S)
     // and the outputs, m x S x L each and m x m x S x L (device, or null).  newCov needs newVar: its diagonal
     const double *Xnew = nullptr, *Unew = nullptr;
@@ -724,7 +727,10 @@ struct PredictShape {
     int n, nt, L, R, naug, ntot;      // R: right-hand sides beside Y — one per level, or L*G with weight columns
     long long Np, tiles_per, nlow;   // padded N, tiles of A with its augmented rows, tiles of an nt x nt triangle
     bool with_sums, want_cov, want_draws, want_mean, unitB;     // unitB: full ITE covariance (CovITE, draws)
-    bool want_loo, want_lgo, want_w;  // leave-one-out outputs, leave-group-out outputs; W = L^-T is wanted (by either)
+    bool want_loo, want_lgo;          // leave-one-out outputs, leave-group-out outputs
+    bool want_grad, grad_pairs, grad_c;   // gradient outputs; those that need the pass over the pairs (gU and the lengthscales'); those
+                                      // that need c = diag(A^-1) (gyScale, gyNoise)
+    bool want_w;                      // W = L^-T is wanted (by any of them)
     bool want_alpha;                  // alpha = A^-1 Y is wanted (by the MeanITE pass or by them)
     int mt = 0;                       // new individuals: their row tiles, the tiles of an mt x mt triangle, and whether the
     long long mlow = 0;               // (sample, level) pairs need tile workspace (variance, covariance)
@@ -734,7 +740,9 @@ struct PredictShape {
           Np((long long)nt * GP_TS), tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2),
           with_sums(io.out.meanSATE || io.out.varSATE || io.out.covW), want_cov(io.CovITEs != nullptr), want_draws(io.out.ite_draws != nullptr),
           want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws),
-          want_loo(io.looMean || io.looVar || io.looLpd), want_lgo(io.lgoMean || io.lgoVar || io.lgoLpd), want_w(want_loo || want_lgo),
+          want_loo(io.looMean || io.looVar || io.looLpd), want_lgo(io.lgoMean || io.lgoVar || io.lgoLpd),
+          want_grad(io.gU || io.guyLS || io.gxyLS || io.gtyLS || io.gyScale || io.gyNoise || io.gY),
+          grad_pairs(io.gU || io.guyLS || io.gxyLS || io.gtyLS), grad_c(io.gyScale || io.gyNoise), want_w(want_loo || want_lgo || want_grad),
           want_alpha(want_mean || want_w || io.newMean) {
         want_new = io.newMean || io.newVar || io.newCov;
         new_pairs = io.newVar || io.newCov;
@@ -754,6 +762,7 @@ struct Chunk {
     double *bw = nullptr, *kw = nullptr, *wnorm2 = nullptr;      // weighted effects: B W, K W [nb][G][Np], w_g . w_g [nb][G]
     double* cprior = nullptr;        // joint covariance across the levels: beta, kappa, gamma_l [nb][G][L + 2]
     double *loo_w = nullptr, *loo_c = nullptr;      // leave-one-out: W = L^-T as a packed triangle of tiles [nb][nlow], diag(A^-1) [nb][Np]
+    double *grad_ls = nullptr, *grad_u = nullptr;   // gradient: the pair pass's partial sums per tile (GradArgs::part_ls, part_u)
     // unit B: a sub-batch of gs_max samples x lc_max levels; W, CovITE, the draws' normals, level-sweep staging, failure codes
     int lc_max = 0, gs_max = 0;
     double *Wt = nullptr, *Ct = nullptr, *zt = nullptr, *dtmp = nullptr;
@@ -793,7 +802,11 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
     if (io.ndraw) b.znode = take(draws_image_doubles(1, sh.Np));        // operand image of the node draw's normals
     if (sh.want_w) b.loo_w = take((size_t)sh.nlow * GP_TSQ);
-    if (sh.want_loo) b.loo_c = take(sh.Np);
+    if (sh.want_loo || sh.grad_c) b.loo_c = take(sh.Np);
+    if (sh.grad_pairs) {      // F numbers per lower tile; 128 nU per (tile row, tile column)
+        b.grad_ls = take((size_t)sh.nlow * (io.nU + io.nX + 1));
+        if (io.nU > 0) b.grad_u = take((size_t)nt * nt * io.nU * GP_TS);
+    }
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
     if (sh.new_pairs) {       // new individuals: W* (mt x nt) and, with the covariance, an mt triangle per (sample, level) pair
         const size_t w_tiles = (size_t)sh.mt * nt, c_tiles = io.newCov ? (size_t)sh.mlow : 0;
@@ -984,7 +997,8 @@ void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const T
 }
 
 // Leave-one-out predictive checks of a chunk: c = diag(A^-1) as the squared row norms of W = L^-T, then the
-// outputs from alpha, c and Y; and / or its leave-group-out checks (§20) from the same W and alpha.  W is built block diagonal by block diagonal, one launch each: diagonal d holds the tiles
+// outputs from alpha, c and Y; and / or its leave-group-out checks (§20) from the same W and alpha.  The gradient (§21, grad() below) reads W,
+// alpha and c as this function leaves them.  W is built block diagonal by block diagonal, one launch each: diagonal d holds the tiles
 // (i, i + d) of all tile rows and matrices, each a chain of d tile products from kk = i on (nt^3/6 products in all, the
 // factorisation's count); the tile rows of a matrix are independent chains, so nt x nb of them are in flight.
 void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
@@ -1009,10 +1023,8 @@ void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk&
         g.queue = ch.s->queue;
         launch_loo_diagonal(g, nt, d, st);
     }
-    if (sh.want_loo) {
-        launch_loo_rownorm(la, nb, st);
-        launch_loo_finish(la, nb, st);
-    }
+    if (sh.want_loo || sh.grad_c) launch_loo_rownorm(la, nb, st);
+    if (sh.want_loo) launch_loo_finish(la, nb, st);
     if (sh.want_lgo) {      // leave-group-out: one workgroup per (group, sample) on the same W and alpha
         LgoArgs ga{};
         ga.W = la.W; ga.w_bstride = la.w_bstride; ga.n = la.n; ga.nt = nt; ga.s0 = la.s0; ga.G = io.lgoG; ga.mmax = io.lgoMmax;
@@ -1023,6 +1035,26 @@ void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk&
     }
     HC(hipGetLastError());
     (void)c;
+}
+
+// Gradient of the outcome log-likelihood of a chunk, after loo() has left W, alpha and, where asked, c: the pass
+// over the lower tiles of A^-1 = W W^T (nt^3/6 tile products, the factorisation's count) when U's or a lengthscale's gradient is
+// asked, then the kernel that adds the tiles' partial sums and writes every output.  gyScale, gyNoise and gY alone need no pair pass.
+void grad(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    hipStream_t st = ch.s->st;
+    GradArgs ga{ch.grid};
+    ga.W = ch.loo_w; ga.w_bstride = sh.nlow * GP_TSQ; ga.S = io.post.S;
+    ga.alpha = ch.zwork + (long long)ch.nb * sh.Np; ga.c = ch.loo_c;
+    ga.Y = io.Y; ga.y_sstride = io.y_sstride; ga.info = io.info;
+    ga.part_ls = ch.grad_ls; ga.part_u = ch.grad_u; ga.queue = ch.s->queue;
+    ga.dU = io.gU; ga.duyLS = io.guyLS; ga.dxyLS = io.gxyLS; ga.dtyLS = io.gtyLS;
+    ga.dyScale = io.gyScale; ga.dyNoise = io.gyNoise; ga.dY = io.gY;
+    if (sh.grad_pairs) {
+        rearm_queue(*ch.s);
+        launch_grad_pairs(ga, ch.nb, st);
+    }
+    launch_grad_finish(ga, ch.nb, st);
+    HC(hipGetLastError());
 }
 
 // Unit B of a chunk batches over (posterior sample, level) PAIRS: a sub-batch is gs samples x lc levels (gs * lc <= Bb), batch
@@ -1189,6 +1221,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         if (sh.want_alpha && !back_done) back_substitute(sh, ch);
         if (sh.want_mean) mean_ite(c, io, sh, ch);
         if (sh.want_w) loo(c, io, sh, ch);
+        if (sh.want_grad) grad(io, sh, ch);
         if (sh.unitB) unit_b(c, io, sh, ch);
         if (sh.want_new) unit_new(c, io, sh, ch);
     }
@@ -2410,6 +2443,45 @@ int gpslc_y_loo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
         if (looMean) copy_out_large(c, looMean, io.looMean, nS * sizeof(double));
         if (looVar) copy_out_large(c, looVar, io.looVar, nS * sizeof(double));
         if (looLpd) copy_out_large(c, looLpd, io.looLpd, nS * sizeof(double));
+        return st;
+    });
+}
+
+// gradient of the outcome log-likelihood: gpslc_y_loo's call with other outputs
+int gpslc_y_logpdf_grad(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                        const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                        double* dU, double* duyLS, double* dxyLS, double* dtyLS, double* dyScale, double* dyNoise, double* dY,
+                        double* logpdf_or_null) {
+    const PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 0, nullptr);
+    int rc = validate(c, rq, kSamplesArgs);
+    if (rc) return rc;
+    if (!dU && !duyLS && !dxyLS && !dtyLS && !dyScale && !dyNoise && !dY)
+        return bad_arg(c, 11, "dU, duyLS, dxyLS, dtyLS, dyScale, dyNoise and dY are all NULL");
+    if (c->flags & GPSLC_FLAG_FP32_KERNEL) {
+        set_err(c, "gpslc_y_logpdf_grad needs an fp64 context: the pair pass evaluates K in fp64, not the matrix an fp32 context factorises");
+        return GPSLC_ERR_UNSUPPORTED;
+    }
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    if (c->nU == 0) dU = duyLS = nullptr;       // the outputs of an empty block are ignored
+    if (c->nX == 0) dxyLS = nullptr;
+    return guarded(c, [&]() {
+        // the tiled path at every n, as gpslc_y_loo
+        const size_t n = (size_t)c->n, nS = n * (size_t)S, uS = (size_t)c->nU * (size_t)S, xS = (size_t)c->nX * (size_t)S;
+        c->io.reset();
+        PredictIO io;
+        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
+        io.X = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
+        if (Y_or_null) { io.Y = up(c, Y_or_null, n); io.y_sstride = 0; }
+        const struct { double* host; double** dev; size_t count; } outs[] = {
+            {dU, &io.gU, nS * (size_t)c->nU}, {duyLS, &io.guyLS, uS}, {dxyLS, &io.gxyLS, xS}, {dtyLS, &io.gtyLS, (size_t)S},
+            {dyScale, &io.gyScale, (size_t)S}, {dyNoise, &io.gyNoise, (size_t)S}, {dY, &io.gY, nS}};
+        for (const auto& o : outs)
+            if (o.host) *o.dev = c->io.take<double>(o.count);
+        std::vector<double> lp(logpdf_or_null ? 0 : (size_t)S);
+        const int st = tiled_score(c, io, logpdf_or_null ? logpdf_or_null : lp.data());
+        if (st < 0) return st;
+        for (const auto& o : outs)
+            if (o.host) copy_out_large(c, o.host, *o.dev, o.count * sizeof(double));
         return st;
     });
 }

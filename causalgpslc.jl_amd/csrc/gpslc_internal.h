@@ -363,6 +363,32 @@ struct LgoArgs {
 void launch_lgo_groups(const LgoArgs& a, int nbatch, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// Gradient of the outcome log-likelihood (k_grad.hip): with Q = alpha alpha^T - A^-1, K = A - yNoise I and
+// P = Q o K, the lengthscale gradients are sums of P_ij D_ijf^2 and the gradient of U_if a row sum of P_ij D_ijf, D_ijf =
+// w_if - w_jf over the raw features w = [U | X | T].  A^-1 = W W^T comes tile by tile from the packed W of the leave-one-out
+// checks (loo_w_index) and never reaches memory: the pair kernel forms P on the MFMA accumulators and leaves partial sums,
+// every work item in its own slot; the finish kernel adds them in ascending tile order.
+// ---------------------------------------------------------------------------------------
+struct GradArgs : SampleGrid {
+    const double* W; long long w_bstride;       // [b][nt (nt + 1) / 2 tiles], loo_w_index
+    long long S;
+    const double* alpha;                        // [b][Np]: A alpha = Y
+    const double* c;                            // [b][Np]: diag(A^-1), or null (neither dyScale nor dyNoise is asked)
+    const double* Y; long long y_sstride;       // sample s at Y + s*y_sstride
+    const int* info;                            // S: a sample whose factorisation broke down gets NaN
+    double* part_ls;                            // [b][nlow][F]: sum of P D_f^2 of lower tile t (off-diagonal tiles doubled); null: no pair pass
+    double* part_u;                             // [b][nt][nt][nU][128]: sum over the columns of tile column tj of P D_f, rows of tile row ti
+    int* queue;                                 // the stream's ticket counters (GemmArgs::queue)
+    // outputs (device, in the layouts of the arguments they differentiate) or null
+    double *dU, *duyLS, *dxyLS, *dtyLS, *dyScale, *dyNoise, *dY;
+    __host__ __device__ int F() const { return nU + nX + 1; }
+    __host__ __device__ const double* raw_column(long long s, int f) const { return f < nU + nX ? column(s, f) : T; }
+    __host__ __device__ double ls(long long s, int f) const { return f < nU + nX ? lengthscale(s, f) : p.tyLS[s]; }
+};
+void launch_grad_pairs(const GradArgs& a, int nbatch, hipStream_t st);    // needs part_ls (and part_u when nU > 0)
+void launch_grad_finish(const GradArgs& a, int nbatch, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // Predictions for new individuals (k_new.hip): the rows of B* (m x n) and B** (m x m) come from the caller's
 // features [Unew_s | Xnew], the columns of B* from the training grid.  NewGrid is a SampleGrid with that second row source;
 // stage_scaled_new_features forms x * (1.0 / ls) as stage_scaled_features does, so a new individual that copies a training

@@ -180,6 +180,35 @@ int gpslc_y_lgo(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_or_n
                 double* lgoMean /* n x S */, double* lgoVar /* n x S */, double* lgoLpd /* G x S */,
                 double* logpdf_or_null /* S */);
 
+/* Gradient of the :Y node's score log N(Y; 0, A), A = K + yNoise I, K_ij = yScale exp(-sum_f ((w_if - w_jf) / ls_f)^2) over
+ * the features w = [U | X | T] with ls = [uyLS; xyLS; tyLS], for S parameter sets: what a gradient-based move on U and the
+ * hyper-parameters (HMC, MALA, MAP), a type-II maximum-likelihood start or a sensitivity check needs (Rasmussen & Williams
+ * §5.4.1).  With alpha = A^-1 Y, Q = alpha alpha^T - A^-1, P = Q o K (element-wise), c = diag(A^-1) and D_ijf = w_if - w_jf:
+ *   dLS_f    =  (1 / ls_f^3) sum_ij P_ij D_ijf^2                    every feature: duyLS (nU x S), dxyLS (nX x S), dtyLS (S)
+ *   dU_if    = -(2 / ls_f^2) sum_j P_ij D_ijf                       f < nU: dU (n x nU x S)
+ *   dyNoise  =  (alpha . alpha - sum_i c_i) / 2                     (S)
+ *   dyScale  =  (alpha . Y - n - yNoise (alpha . alpha - sum_i c_i)) / (2 yScale)        (S)
+ *   dY       = -alpha                                               (n x S)
+ * Every output has the layout of the argument it differentiates (dU: element (i, f, s) at i + n*(f + nU*s)).  A^-1 is formed
+ * tile by tile from the L^-T of gpslc_y_loo on the f64 matrix cores and never stored; K is evaluated again in fp64 and D from
+ * the raw features; c is a sum of squares.  Derivatives are with respect to the parameters themselves, not their logarithms.
+ * Arguments 1-10, validation, overrides and logpdf_or_null are gpslc_y_loo's (logpdf_or_null is bit-identical to that call's);
+ * this call takes the tiled path at every n.  Any output may be NULL; dU .. dY all NULL is the argument error of dU (-11).
+ * With nU == 0 (nX == 0) the outputs of that block are ignored.  When only dyScale, dyNoise and dY are asked for, no pass over
+ * the pairs runs and the call costs what gpslc_y_loo costs.  A GPSLC_FLAG_FP32_KERNEL context: GPSLC_ERR_UNSUPPORTED (the
+ * fp64 K of the pair pass is not the matrix such a context factorises).  S = 0 is an empty call.
+ * A parameter set whose factorisation breaks down gets NaN in all its outputs; return value (first failing pivot) and
+ * gpslc_last_info as for gpslc_y_loo.
+ * Guarantees: the outputs are bit-reproducible and independent of chunking, stream count and factorisation schedule (no
+ * floating-point atomics: fixed summation orders); asking for a subset of the outputs gives the same bits for that subset;
+ * sum_i dU[i, f, s] vanishes to rounding (the score does not change when a column of U is shifted).
+ * There is no _dev variant and no sharding over several contexts; no gradient with respect to X or T. */
+int gpslc_y_logpdf_grad(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                        const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                        double* dU /* n x nU x S */, double* duyLS /* nU x S */, double* dxyLS /* nX x S */,
+                        double* dtyLS /* S */, double* dyScale /* S */, double* dyNoise /* S */, double* dY /* n x S */,
+                        double* logpdf_or_null /* S */);
+
 /* ---- the other Gaussian-process nodes of the Gen models -------------- */
 
 /* log N(target; 0, scale * exp.(rbfKernelLog(F, F, ls)) + noise * I) for S parameter sets: the score of

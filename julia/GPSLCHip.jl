@@ -200,6 +200,25 @@ function y_lgo(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS, ty
     lgoMean, lgoVar, lgoLpd, lp
 end
 
+"""Gradient of the :Y node's score for S parameter sets (gpslc_y_logpdf_grad): `(dU, duyLS, dxyLS, dtyLS, dyScale, dyNoise, dY,
+logpdf)` in the layouts of the arguments they differentiate — dU n x nU x S, duyLS nU x S, dxyLS nX x S, dY n x S, the others
+length S — with respect to the parameters themselves (multiply by the parameter for a gradient in its logarithm)."""
+function y_logpdf_grad(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS, tyLS::Vector{Float64},
+                       yScale::Vector{Float64}, yNoise::Vector{Float64})
+    dU = Array{Float64}(undef, c.n, c.nU, S)
+    duyLS, dxyLS = Matrix{Float64}(undef, c.nU, S), Matrix{Float64}(undef, c.nX, S)
+    dtyLS, dyScale, dyNoise, lp = (Vector{Float64}(undef, S) for _ in 1:4)
+    dY = Matrix{Float64}(undef, c.n, S)
+    Uf, Xf, Yf, uy, xy = f64(U), f64(X_or_nothing), f64(Y_or_nothing), f64(uyLS), f64(xyLS)
+    GC.@preserve Uf Xf Yf uy xy tyLS yScale yNoise dU duyLS dxyLS dtyLS dyScale dyNoise dY lp check(c, ccall((:gpslc_y_logpdf_grad, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(Uf), ptr(Xf), ptr(Yf), ptr(uy), ptr(xy), pointer(tyLS), pointer(yScale), pointer(yNoise),
+        pointer(dU), pointer(duyLS), pointer(dxyLS), pointer(dtyLS), pointer(dyScale), pointer(dyNoise), pointer(dY), pointer(lp)))
+    dU, duyLS, dxyLS, dtyLS, dyScale, dyNoise, dY, lp
+end
+
 const NEW_OUTCOME, NEW_CONTRAST, NEW_SLOPE = Int32(0), Int32(1), Int32(2)     # GPSLC_NEW_*: the `form` of predict_new
 
 """Predictions for m individuals who are not in the data (gpslc_predict_new): `(mean, var, cov)` — mean and var m x S x L, cov
