@@ -282,17 +282,24 @@ class Context:
         self.check(self.lib.gpslc_last_info(self.h, out.ctypes.data_as(_lib.c_int32_p), S))
         return out
 
+    def _call_for(self, fn, shapes, want, *args, fill=np.nan):
+        """What y_loo, y_lgo, y_logpdf_grad and predict_new share: one column-major array per output named in ``want`` (``shapes``:
+        every output's shape, in the order of ``fn``'s trailing pointer arguments) full of ``fill`` (None: as allocated), None
+        (NULL to the library) for the others -> ``(status, outputs)``.  ``args`` go before them: host arrays as given (None =
+        NULL), numbers and ctypes pointers as they are."""
+        out = {k: (np.empty(s, order="F") if fill is None else np.full(s, fill, order="F")) if k in want else None
+               for k, s in shapes.items()}
+        return fn(self.h, *[_p(a) if isinstance(a, np.ndarray) else a for a in args], *map(_p, out.values())), out
+
     def y_loo(self, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, want=("mean", "var", "lpd", "logpdf")):
         """gpslc_y_loo with host arrays as given (None = NULL): ``(status, looMean, looVar, looLpd, logpdf)`` — the outputs
         named in ``want`` as (n, S) / (S,) arrays, the others None (NULL to the library).  The status is returned, not raised:
         a positive one (a parameter set's factorisation broke down) still leaves the other sets' values."""
         S = int(S)
-        shape = (self.n, max(S, 0))
-        out = {k: np.full(shape if k != "logpdf" else (shape[1],), np.nan, order="F") if k in want else None
-               for k in ("mean", "var", "lpd", "logpdf")}
-        st = self.lib.gpslc_y_loo(self.h, S, _p(U), _p(X_or_none), _p(Y_or_none), _p(uyLS), _p(xyLS), _p(tyLS), _p(yScale),
-                                  _p(yNoise), _p(out["mean"]), _p(out["var"]), _p(out["lpd"]), _p(out["logpdf"]))
-        return st, out["mean"], out["var"], out["lpd"], out["logpdf"]
+        nS = (self.n, max(S, 0))
+        st, out = self._call_for(self.lib.gpslc_y_loo, {"mean": nS, "var": nS, "lpd": nS, "logpdf": nS[1:]}, want,
+                                 S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise)
+        return (st, *out.values())
 
     def y_lgo(self, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, G, labels, want=("mean", "var", "lpd", "logpdf")):
         """gpslc_y_lgo with host arrays as given (None = NULL; ``labels``: n integers in [0, G)): ``(status, lgoMean, lgoVar,
@@ -300,15 +307,13 @@ class Context:
         the library).  The status is returned, not raised, as for ``y_loo``."""
         S, G = int(S), int(G)
         Sn, Gn = max(S, 0), max(G, 0)
-        shapes = {"mean": (self.n, Sn), "var": (self.n, Sn), "lpd": (Gn, Sn), "logpdf": (Sn,)}
-        out = {k: np.full(shapes[k], np.nan, order="F") if k in want else None for k in shapes}
         lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32)
         if lab is not None and lab.shape != (self.n,):
             raise ValueError(f"labels must have shape ({self.n},), got {lab.shape}")
-        st = self.lib.gpslc_y_lgo(self.h, S, _p(U), _p(X_or_none), _p(Y_or_none), _p(uyLS), _p(xyLS), _p(tyLS), _p(yScale),
-                                  _p(yNoise), G, None if lab is None else lab.ctypes.data_as(_lib.c_int32_p),
-                                  _p(out["mean"]), _p(out["var"]), _p(out["lpd"]), _p(out["logpdf"]))
-        return st, out["mean"], out["var"], out["lpd"], out["logpdf"]
+        st, out = self._call_for(self.lib.gpslc_y_lgo, {"mean": (self.n, Sn), "var": (self.n, Sn), "lpd": (Gn, Sn), "logpdf": (Sn,)},
+                                 want, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, G,
+                                 None if lab is None else lab.ctypes.data_as(_lib.c_int32_p))
+        return (st, *out.values())
 
     GRAD_OUTPUTS = ("dU", "duyLS", "dxyLS", "dtyLS", "dyScale", "dyNoise", "dY", "logpdf")
 
@@ -319,14 +324,11 @@ class Context:
         S = int(S)
         Sn = max(S, 0)
         shapes = {"dU": (self.n, self.nU, Sn), "duyLS": (self.nU, Sn), "dxyLS": (self.nX, Sn), "dtyLS": (Sn,), "dyScale": (Sn,),
-                  "dyNoise": (Sn,), "dY": (self.n, Sn), "logpdf": (Sn,)}
+                  "dyNoise": (Sn,), "dY": (self.n, Sn), "logpdf": (Sn,)}          # in GRAD_OUTPUTS' order
         unknown = set(want) - set(shapes)
         if unknown:
             raise ValueError(f"unknown gradient outputs {sorted(unknown)}: choose from {self.GRAD_OUTPUTS}")
-        out = {k: np.full(shapes[k], np.nan, order="F") if k in want else None for k in shapes}
-        st = self.lib.gpslc_y_logpdf_grad(self.h, S, _p(U), _p(X_or_none), _p(Y_or_none), _p(uyLS), _p(xyLS), _p(tyLS), _p(yScale),
-                                          _p(yNoise), *[_p(out[k]) for k in self.GRAD_OUTPUTS])
-        return st, out
+        return self._call_for(self.lib.gpslc_y_logpdf_grad, shapes, want, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise)
 
     def predict_new(self, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, doT, doT_base, pred_noise,
                     want=("mean", "var")):
@@ -338,13 +340,10 @@ class Context:
         S, m = int(S), int(m)
         L = 0 if doT is None else int(np.size(doT))
         dims = (max(m, 0), max(S, 0), L)
-        out = {k: np.empty(dims if k != "cov" else (dims[0],) + dims, order="F") if k in want else None
-               for k in ("mean", "var", "cov")}          # written in full by every call that returns a status >= 0
-        code = NEW_FORMS.get(form, form)
-        st = self.lib.gpslc_predict_new(self.h, S, _p(U), _p(uyLS), _p(xyLS), _p(tyLS), _p(yScale), _p(yNoise), m, _p(Xnew),
-                                        _p(Unew), int(code), L, _p(doT), _p(doT_base), float(pred_noise), _p(out["mean"]),
-                                        _p(out["var"]), _p(out["cov"]))
-        return st, out["mean"], out["var"], out["cov"]
+        st, out = self._call_for(self.lib.gpslc_predict_new, {"mean": dims, "var": dims, "cov": (dims[0],) + dims}, want,
+                                 S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, int(NEW_FORMS.get(form, form)), L, doT,
+                                 doT_base, float(pred_noise), fill=None)      # written in full by every call that returns a status >= 0
+        return (st, *out.values())
 
     def profile_reset(self):
         self.lib.gpslc_profile_reset(self.h)
@@ -905,6 +904,12 @@ def summarizeEstimates(samples, credible_interval=0.90):
 # src/model_likelihood.jl :Y node
 # ------------------------------------------------------------------------------------------
 
+def _overrides(g: GPSLCObject, X_override, Y_override):
+    """the overrides of the outcome-model calls as the library takes them (None: the context's data)"""
+    return (None if X_override is None else _f(X_override).reshape(g.getN(), g.getNX(), order="F"),
+            None if Y_override is None else _f(Y_override, (g.getN(),)))
+
+
 def yLogpdf(g: GPSLCObject, X_override=None, Y_override=None):
     """log N(y; 0, Ycov) for every parameter set of ``g`` (the score the :Y address contributes to a
     Gen trace; src/model_likelihood.jl:83-120).  ``y`` is ``Y_override`` when given (the value Gen hands to a
@@ -912,20 +917,9 @@ def yLogpdf(g: GPSLCObject, X_override=None, Y_override=None):
     S = g.getNumPosteriorSamples()
     ctx = g.ctx()
     out = np.empty(S)
-    Xo = None if X_override is None else _f(X_override).reshape(g.getN(), g.getNX(), order="F")
-    Yo = None if Y_override is None else _f(Y_override, (g.getN(),))
+    Xo, Yo = _overrides(g, X_override, Y_override)
     U, uy, xy, ty, ys, yn = g._params()
     st = ctx.lib.gpslc_y_logpdf(ctx.h, S, U, _p(Xo), _p(Yo), uy, xy, ty, ys, yn, _p(out))
-    ctx.check(st)
-    return out
-
-
-def _loo_call(g: GPSLCObject, X_override, Y_override, want):
-    n = g.getN()
-    Xo = None if X_override is None else _f(X_override).reshape(n, g.getNX(), order="F")
-    Yo = None if Y_override is None else _f(Y_override, (n,))
-    ctx = g.ctx()
-    st, *out = ctx.y_loo(g.getNumPosteriorSamples(), g.U, Xo, Yo, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise, want=want)
     ctx.check(st)
     return out
 
@@ -936,7 +930,10 @@ def looPredictive(g: GPSLCObject, X_override=None, Y_override=None):
     other observations (``var`` is for the observation: it includes yNoise) and the log density of Y_i under that predictive.
     Each sample conditions on its own hyper-parameters and U, which were inferred with Y_i present.  Overrides and errors as
     ``yLogpdf``: ``Y_override`` is the outcome vector being checked, a failed factorisation raises ``PosDefException``."""
-    mean, var, lpd, _ = _loo_call(g, X_override, Y_override, ("mean", "var", "lpd"))
+    ctx = g.ctx()
+    st, mean, var, lpd, _ = ctx.y_loo(g.getNumPosteriorSamples(), g.U, *_overrides(g, X_override, Y_override), g.uyLS, g.xyLS,
+                                      g.tyLS, g.yScale, g.yNoise, want=("mean", "var", "lpd"))
+    ctx.check(st)
     return mean, var, lpd
 
 
@@ -948,11 +945,9 @@ def yLogpdfGrad(g: GPSLCObject, X_override=None, Y_override=None, log_params=Fal
     needs.  ``log_params=True``: the five positive parameters' gradients are with respect to their logarithms (multiplied by
     the parameter, on the host); ``dU`` and ``dY`` are unchanged.  Overrides and errors as ``yLogpdf``; an fp32 context is
     refused."""
-    n = g.getN()
-    Xo = None if X_override is None else _f(X_override).reshape(n, g.getNX(), order="F")
-    Yo = None if Y_override is None else _f(Y_override, (n,))
     ctx = g.ctx()
-    st, out = ctx.y_logpdf_grad(g.getNumPosteriorSamples(), g.U, Xo, Yo, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise)
+    st, out = ctx.y_logpdf_grad(g.getNumPosteriorSamples(), g.U, *_overrides(g, X_override, Y_override), g.uyLS, g.xyLS, g.tyLS,
+                                g.yScale, g.yNoise)
     ctx.check(st)
     if log_params:
         for k, par in (("duyLS", g.uyLS), ("dxyLS", g.xyLS), ("dtyLS", g.tyLS), ("dyScale", g.yScale), ("dyNoise", g.yNoise)):
@@ -961,20 +956,25 @@ def yLogpdfGrad(g: GPSLCObject, X_override=None, Y_override=None, log_params=Fal
     return out
 
 
+def _predictive_summary(g: GPSLCObject, Y_override, mean, var, lpd):
+    """what looSummary and lgoSummary share -> (elpd (S,), log mean_s exp(lpd) per row of lpd, zscore (n, S), pit (n,))"""
+    from math import erf
+    Y = g.Y if Y_override is None else _f(Y_override, (g.getN(),))
+    z = (Y[:, None] - mean) / np.sqrt(var)
+    top = np.max(lpd, axis=1)
+    rowwise = top + np.log(np.mean(np.exp(lpd - top[:, None]), axis=1))
+    pit = np.mean(0.5 * (1.0 + np.vectorize(erf)(z / np.sqrt(2.0))), axis=1)
+    return np.sum(lpd, axis=0), rowwise, z, pit
+
+
 def looSummary(g: GPSLCObject, X_override=None, Y_override=None, loo=None):
     """Summaries of ``looPredictive`` (host arithmetic only; ``loo`` = its result, to summarise one already computed):
 
     ``elpd`` (S,): sum_i lpd[i, s], the LOO log predictive density of every posterior sample — compare models (nU = 0 / 1 / 2,
     with / without X) on it; ``pointwise`` (n,): log mean_s exp(lpd[i, s]), the individuals the surface misses;
     ``zscore`` (n, S): (Y - mean) / sqrt(var); ``pit`` (n,): mean_s Phi(zscore), uniform on (0, 1) for a calibrated model."""
-    from math import erf
-    mean, var, lpd = looPredictive(g, X_override, Y_override) if loo is None else loo
-    Y = g.Y if Y_override is None else _f(Y_override, (g.getN(),))
-    z = (Y[:, None] - mean) / np.sqrt(var)
-    top = np.max(lpd, axis=1)
-    pointwise = top + np.log(np.mean(np.exp(lpd - top[:, None]), axis=1))
-    pit = np.mean(0.5 * (1.0 + np.vectorize(erf)(z / np.sqrt(2.0))), axis=1)
-    return {"elpd": np.sum(lpd, axis=0), "pointwise": pointwise, "zscore": z, "pit": pit}
+    elpd, pointwise, z, pit = _predictive_summary(g, Y_override, *(looPredictive(g, X_override, Y_override) if loo is None else loo))
+    return {"elpd": elpd, "pointwise": pointwise, "zscore": z, "pit": pit}
 
 
 def _group_labels(g: GPSLCObject, groups):
@@ -1001,13 +1001,10 @@ def lgoPredictive(g: GPSLCObject, groups=None, X_override=None, Y_override=None)
     (for the observation: yNoise included) of Y_i given all individuals outside i's group; ``lpd`` (G, S): the joint log
     density of each group's outcomes under that predictive, row j belonging to group ``keys[j]`` (the distinct labels,
     sorted).  A group has at most 128 members.  Overrides and errors as ``looPredictive``."""
-    n = g.getN()
     keys, labels = _group_labels(g, groups)
-    Xo = None if X_override is None else _f(X_override).reshape(n, g.getNX(), order="F")
-    Yo = None if Y_override is None else _f(Y_override, (n,))
     ctx = g.ctx()
-    st, mean, var, lpd, _ = ctx.y_lgo(g.getNumPosteriorSamples(), g.U, Xo, Yo, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise,
-                                      len(keys), labels, want=("mean", "var", "lpd"))
+    st, mean, var, lpd, _ = ctx.y_lgo(g.getNumPosteriorSamples(), g.U, *_overrides(g, X_override, Y_override), g.uyLS, g.xyLS,
+                                      g.tyLS, g.yScale, g.yNoise, len(keys), labels, want=("mean", "var", "lpd"))
     ctx.check(st)
     return mean, var, lpd, keys
 
@@ -1029,14 +1026,9 @@ def lgoSummary(g: GPSLCObject, groups=None, X_override=None, Y_override=None, lg
     ``elpd`` (S,): sum_g lpd[g, s], the leave-group-out log predictive density of every posterior sample — the score to compare
     models (nU = 0 / 1 / 2) on for hierarchical data; ``groupwise`` (G,): log mean_s exp(lpd[g, s]), the groups the surface
     misses; ``zscore`` (n, S): the marginal (Y - mean) / sqrt(var); ``pit`` (n,): mean_s Phi(zscore); ``keys`` (G,)."""
-    from math import erf
-    mean, var, lpd, keys = lgoPredictive(g, groups, X_override, Y_override) if lgo is None else lgo
-    Y = g.Y if Y_override is None else _f(Y_override, (g.getN(),))
-    z = (Y[:, None] - mean) / np.sqrt(var)
-    top = np.max(lpd, axis=1)
-    groupwise = top + np.log(np.mean(np.exp(lpd - top[:, None]), axis=1))
-    pit = np.mean(0.5 * (1.0 + np.vectorize(erf)(z / np.sqrt(2.0))), axis=1)
-    return {"elpd": np.sum(lpd, axis=0), "groupwise": groupwise, "zscore": z, "pit": pit, "keys": keys}
+    *lgo, keys = lgoPredictive(g, groups, X_override, Y_override) if lgo is None else lgo
+    elpd, groupwise, z, pit = _predictive_summary(g, Y_override, *lgo)
+    return {"elpd": elpd, "groupwise": groupwise, "zscore": z, "pit": pit, "keys": keys}
 
 
 # ------------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <initializer_list>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -658,6 +660,32 @@ struct DrawsAndOutputs {
     double* covW = nullptr;
 };
 
+// What the outcome-model calls add to a prediction call: device pointers, null where the output is not asked
+struct Loo {                         // leave-one-out predictive checks (gpslc_y_loo): n x S each
+    double *mean = nullptr, *var = nullptr, *lpd = nullptr;
+    bool any() const { return mean || var || lpd; }
+};
+struct Lgo {                         // leave-group-out predictive checks (gpslc_y_lgo): n x S, n x S, G x S
+    int G = 0, mmax = 0;             // groups; members of the largest
+    const int *members = nullptr, *offsets = nullptr;      // the members sorted by (group, row), the G + 1 offsets into them
+    double *mean = nullptr, *var = nullptr, *lpd = nullptr;
+    bool any() const { return mean || var || lpd; }
+};
+struct Grad {                        // gradient of the outcome log-likelihood (gpslc_y_logpdf_grad), in the layouts of
+    // the arguments they differentiate: U n x nU x S, uyLS nU x S, xyLS nX x S, the others S; Y n x S
+    double *U = nullptr, *uyLS = nullptr, *xyLS = nullptr, *tyLS = nullptr, *yScale = nullptr, *yNoise = nullptr, *Y = nullptr;
+    bool pairs() const { return U || uyLS || xyLS || tyLS; }     // those that need the pass over the pairs
+    bool needs_c() const { return yScale || yNoise; }            // those that need c = diag(A^-1)
+    bool any() const { return pairs() || needs_c() || Y; }
+};
+struct NewIndividuals {              // predictions for m new individuals (gpslc_predict_new)
+    const double *Xnew = nullptr, *Unew = nullptr;      // their features: m x nX, m x nU x S
+    int m = 0;
+    double *mean = nullptr, *var = nullptr, *cov = nullptr;     // m x S x L each and m x m x S x L; cov needs var: its diagonal
+    bool pairs() const { return var || cov; }            // the (sample, level) pairs need tile workspace
+    bool any() const { return mean || pairs(); }
+};
+
 struct PredictIO {
     Posterior post;
     Levels lv;
@@ -677,21 +705,10 @@ struct PredictIO {
     const double* nz = nullptr;
     const double* nzero = nullptr;
     double* ndraw = nullptr;
-    // leave-one-out predictive checks of the outcome model (gpslc_y_loo): n x S each, device, or null
-    double *looMean = nullptr, *looVar = nullptr, *looLpd = nullptr;
-    // leave-group-out predictive checks (gpslc_y_lgo): the members sorted by (group, row) with the G + 1 offsets
-    // into them (device), and the outputs: n x S, n x S, G x S (device, or null)
-    int lgoG = 0, lgoMmax = 0;       // groups; members of the largest
-    const int *lgoMembers = nullptr, *lgoOffsets = nullptr;
-    double *lgoMean = nullptr, *lgoVar = nullptr, *lgoLpd = nullptr;
-    // gradient of the outcome log-likelihood (gpslc_y_logpdf_grad): device, in the layouts of the arguments they
-    // differentiate (gU n x nU x S, guyLS nU x S, gxyLS nX x S, the others S; gY n x S), or null
-    double *gU = nullptr, *guyLS = nullptr, *gxyLS = nullptr, *gtyLS = nullptr, *gyScale = nullptr, *gyNoise = nullptr, *gY = nullptr;
-    // predictions for m new individuals (gpslc_predict_new): their features (device; Xnew m x nX, Unew m x nU x S)
-    // and the outputs, m x S x L each and m x m x S x L (device, or null).  newCov needs newVar: its diagonal
-    const double *Xnew = nullptr, *Unew = nullptr;
-    int m = 0;
-    double *newMean = nullptr, *newVar = nullptr, *newCov = nullptr;
+    Loo loo;
+    Lgo lgo;
+    Grad grad;
+    NewIndividuals fresh;
 };
 
 // chunk and unit-B sub-batch sizes of a call (batch_plan.h holds the arithmetic; here: what the schedule would like and what
@@ -728,27 +745,22 @@ struct PredictShape {
     long long Np, tiles_per, nlow;   // padded N, tiles of A with its augmented rows, tiles of an nt x nt triangle
     bool with_sums, want_cov, want_draws, want_mean, unitB;     // unitB: full ITE covariance (CovITE, draws)
     bool want_loo, want_lgo;          // leave-one-out outputs, leave-group-out outputs
-    bool want_grad, grad_pairs, grad_c;   // gradient outputs; those that need the pass over the pairs (gU and the lengthscales'); those
-                                      // that need c = diag(A^-1) (gyScale, gyNoise)
+    bool want_grad, grad_pairs, grad_c;   // gradient outputs; those that need the pass over the pairs (U and the lengthscales'); those
+                                      // that need c = diag(A^-1) (yScale, yNoise)
     bool want_w;                      // W = L^-T is wanted (by any of them)
     bool want_alpha;                  // alpha = A^-1 Y is wanted (by the MeanITE pass or by them)
-    int mt = 0;                       // new individuals: their row tiles, the tiles of an mt x mt triangle, and whether the
-    long long mlow = 0;               // (sample, level) pairs need tile workspace (variance, covariance)
-    bool want_new = false, new_pairs = false;
+    int mt;                           // new individuals: their row tiles, the tiles of an mt x mt triangle, and whether the
+    long long mlow;                   // (sample, level) pairs need tile workspace (variance, covariance)
+    bool want_new, new_pairs;
     PredictShape(const gpslc_ctx* c, const PredictIO& io)
         : n((int)c->n), nt(c->nt), L(io.lv.L), R(io.lv.W ? io.lv.L * io.lv.G : io.lv.L), naug((R + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug),
           Np((long long)nt * GP_TS), tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2),
           with_sums(io.out.meanSATE || io.out.varSATE || io.out.covW), want_cov(io.CovITEs != nullptr), want_draws(io.out.ite_draws != nullptr),
           want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws),
-          want_loo(io.looMean || io.looVar || io.looLpd), want_lgo(io.lgoMean || io.lgoVar || io.lgoLpd),
-          want_grad(io.gU || io.guyLS || io.gxyLS || io.gtyLS || io.gyScale || io.gyNoise || io.gY),
-          grad_pairs(io.gU || io.guyLS || io.gxyLS || io.gtyLS), grad_c(io.gyScale || io.gyNoise), want_w(want_loo || want_lgo || want_grad),
-          want_alpha(want_mean || want_w || io.newMean) {
-        want_new = io.newMean || io.newVar || io.newCov;
-        new_pairs = io.newVar || io.newCov;
-        mt = (io.m + GP_TS - 1) / GP_TS;
-        mlow = (long long)mt * (mt + 1) / 2;
-    }
+          want_loo(io.loo.any()), want_lgo(io.lgo.any()), want_grad(io.grad.any()), grad_pairs(io.grad.pairs()),
+          grad_c(io.grad.needs_c()), want_w(want_loo || want_lgo || want_grad), want_alpha(want_mean || want_w || io.fresh.mean),
+          mt((io.fresh.m + GP_TS - 1) / GP_TS), mlow((long long)mt * (mt + 1) / 2), want_new(io.fresh.any()),
+          new_pairs(io.fresh.pairs()) {}
 };
 
 // one chunk of a call: samples s0 .. s0 + nb - 1 on one stream slot, and the buffers carve_chunk takes for it from the slot's arena
@@ -809,7 +821,7 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     }
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
     if (sh.new_pairs) {       // new individuals: W* (mt x nt) and, with the covariance, an mt triangle per (sample, level) pair
-        const size_t w_tiles = (size_t)sh.mt * nt, c_tiles = io.newCov ? (size_t)sh.mlow : 0;
+        const size_t w_tiles = (size_t)sh.mt * nt, c_tiles = io.fresh.cov ? (size_t)sh.mlow : 0;
         by.per_pair = (w_tiles + c_tiles) * GP_TSQ * 8 + 512;
         if (!ar) return by;
         b.lc_max = std::min(L, Bb);
@@ -996,21 +1008,26 @@ void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const T
     }
 }
 
+// what LooArgs, LgoArgs and GradArgs share: the chunk's W = L^-T, alpha = A^-1 Y, the scored Y and the samples' failure codes
+template <class Args>
+Args on_w(const PredictIO& io, const PredictShape& sh, const Chunk& ch, Args a = Args{}) {
+    a.W = ch.loo_w; a.w_bstride = sh.nlow * GP_TSQ; a.n = sh.n; a.nt = sh.nt; a.s0 = ch.s0;
+    a.alpha = ch.zwork + (long long)ch.nb * sh.Np; a.Y = io.Y; a.y_sstride = io.y_sstride; a.info = io.info;
+    return a;
+}
+
 // Leave-one-out predictive checks of a chunk: c = diag(A^-1) as the squared row norms of W = L^-T, then the
 // outputs from alpha, c and Y; and / or its leave-group-out checks (§20) from the same W and alpha.  The gradient (§21, grad() below) reads W,
 // alpha and c as this function leaves them.  W is built block diagonal by block diagonal, one launch each: diagonal d holds the tiles
 // (i, i + d) of all tile rows and matrices, each a chain of d tile products from kk = i on (nt^3/6 products in all, the
 // factorisation's count); the tile rows of a matrix are independent chains, so nt x nb of them are in flight.
-void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+void loo(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     hipStream_t st = ch.s->st;
     const int nt = sh.nt, nb = ch.nb;
-    LooArgs la{};
+    LooArgs la = on_w<LooArgs>(io, sh, ch);
     la.inv = ch.inv; la.inv_bstride = (long long)nt * GP_TSQ;
-    la.W = ch.loo_w; la.w_bstride = sh.nlow * GP_TSQ;
-    la.n = sh.n; la.nt = nt; la.s0 = ch.s0; la.S = io.post.S;
-    la.c = ch.loo_c; la.alpha = ch.zwork + (long long)nb * sh.Np;
-    la.Y = io.Y; la.y_sstride = io.y_sstride; la.info = io.info;
-    la.looMean = io.looMean; la.looVar = io.looVar; la.looLpd = io.looLpd;
+    la.S = io.post.S; la.c = ch.loo_c;
+    la.looMean = io.loo.mean; la.looVar = io.loo.var; la.looLpd = io.loo.lpd;
     HC(hipMemsetAsync(ch.loo_w, 0, sizeof(double) * (size_t)nb * sh.nlow * GP_TSQ, st));     // every chain starts from a zero tile
     launch_loo_init(la, nb, st);
     rearm_queue(*ch.s);
@@ -1026,15 +1043,12 @@ void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk&
     if (sh.want_loo || sh.grad_c) launch_loo_rownorm(la, nb, st);
     if (sh.want_loo) launch_loo_finish(la, nb, st);
     if (sh.want_lgo) {      // leave-group-out: one workgroup per (group, sample) on the same W and alpha
-        LgoArgs ga{};
-        ga.W = la.W; ga.w_bstride = la.w_bstride; ga.n = la.n; ga.nt = nt; ga.s0 = la.s0; ga.G = io.lgoG; ga.mmax = io.lgoMmax;
-        ga.members = io.lgoMembers; ga.offsets = io.lgoOffsets;
-        ga.alpha = la.alpha; ga.Y = la.Y; ga.y_sstride = la.y_sstride; ga.info = la.info;
-        ga.lgoMean = io.lgoMean; ga.lgoVar = io.lgoVar; ga.lgoLpd = io.lgoLpd;
+        LgoArgs ga = on_w<LgoArgs>(io, sh, ch);
+        ga.G = io.lgo.G; ga.mmax = io.lgo.mmax; ga.members = io.lgo.members; ga.offsets = io.lgo.offsets;
+        ga.lgoMean = io.lgo.mean; ga.lgoVar = io.lgo.var; ga.lgoLpd = io.lgo.lpd;
         launch_lgo_groups(ga, nb, st);
     }
     HC(hipGetLastError());
-    (void)c;
 }
 
 // Gradient of the outcome log-likelihood of a chunk, after loo() has left W, alpha and, where asked, c: the pass
@@ -1042,13 +1056,11 @@ void loo(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk&
 // asked, then the kernel that adds the tiles' partial sums and writes every output.  gyScale, gyNoise and gY alone need no pair pass.
 void grad(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     hipStream_t st = ch.s->st;
-    GradArgs ga{ch.grid};
-    ga.W = ch.loo_w; ga.w_bstride = sh.nlow * GP_TSQ; ga.S = io.post.S;
-    ga.alpha = ch.zwork + (long long)ch.nb * sh.Np; ga.c = ch.loo_c;
-    ga.Y = io.Y; ga.y_sstride = io.y_sstride; ga.info = io.info;
+    GradArgs ga = on_w(io, sh, ch, GradArgs{ch.grid});
+    ga.S = io.post.S; ga.c = ch.loo_c;
     ga.part_ls = ch.grad_ls; ga.part_u = ch.grad_u; ga.queue = ch.s->queue;
-    ga.dU = io.gU; ga.duyLS = io.guyLS; ga.dxyLS = io.gxyLS; ga.dtyLS = io.gtyLS;
-    ga.dyScale = io.gyScale; ga.dyNoise = io.gyNoise; ga.dY = io.gY;
+    ga.dU = io.grad.U; ga.duyLS = io.grad.uyLS; ga.dxyLS = io.grad.xyLS; ga.dtyLS = io.grad.tyLS;
+    ga.dyScale = io.grad.yScale; ga.dyNoise = io.grad.yNoise; ga.dY = io.grad.Y;
     if (sh.grad_pairs) {
         rearm_queue(*ch.s);
         launch_grad_pairs(ga, ch.nb, st);
@@ -1057,113 +1069,112 @@ void grad(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     HC(hipGetLastError());
 }
 
-// Unit B of a chunk batches over (posterior sample, level) PAIRS: a sub-batch is gs samples x lc levels (gs * lc <= Bb), batch
-// element b = (sample b / lc, level l0 + b % lc).  Every pair has its own W / CovITE workspace; the factor of A and its inverted
-// diagonal blocks are shared by a sample's levels (TRef::bdiv = lc) — the shape of predictCounterfactualEffects
-// (src/prediction.jl:30-33): few samples, ~100 levels.
+// The pair workspaces of a chunk (unit B's CovITE, the new individuals' variance and covariance) batch over (posterior sample,
+// level) PAIRS: a sub-batch is gs samples x lc levels (gs * lc = ub <= Bb), batch element b = (sample g0 + b / lc, level l0 +
+// b % lc).  Every pair has its own tiles; the factor of A (Ls) and its inverted diagonal blocks (invref) are shared by a
+// sample's levels (TRef::bdiv = lc) — the shape of predictCounterfactualEffects (src/prediction.jl:30-33): few samples, ~100 levels.
+template <class Body>
+void for_pair_batches(const PredictShape& sh, const Chunk& ch, Body&& body) {
+    const long long bstride = sh.tiles_per * GP_TSQ, inv_bs = (long long)sh.nt * GP_TSQ;
+    for (int g0 = 0; g0 < ch.nb; g0 += ch.gs_max) {
+        const int gs = std::min(ch.gs_max, ch.nb - g0);
+        for (int l0 = 0; l0 < sh.L; l0 += ch.lc_max) {
+            const int lc = std::min(ch.lc_max, sh.L - l0);
+            TRef Ls = lower_ref(ch.tiles + (long long)g0 * bstride, bstride);
+            TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
+            Ls.bdiv = invref.bdiv = lc;
+            body(g0, gs, l0, lc, gs * lc, Ls, invref);
+        }
+    }
+}
+
+// C <- C - W W^T on the lower tiles of C's `rows` tile rows, for ub pairs (W: rows x nt tiles)
+void minus_w_wt(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& C, int nt, int ub, int rows) {
+    GemmArgs g{};
+    g.A = W; g.B = W; g.C = C;
+    g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = rows; g.mj = rows; g.sym = 2;
+    g.k0 = 0; g.k1 = nt; g.nbatch = ub; g.ntiles = (int)((long long)rows * (rows + 1) / 2);
+    g.order = tri_order(c, rows);
+    gemm(c, g, s, 3);
+}
+
+// Unit B of a chunk: the full ITE covariance of every pair, W <- D L^-T, CovITE (+ jitter) = Delta - W W^T, and what is asked of
+// it: the covariance itself, or draws from it
 void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     hipStream_t st = ch.s->st;
-    const int n = sh.n, nt = sh.nt, L = sh.L, nb = ch.nb;
+    const int n = sh.n, nt = sh.nt, L = sh.L;
     const int64_t s0 = ch.s0;
-    const long long bstride = sh.tiles_per * GP_TSQ, inv_bs = (long long)nt * GP_TSQ;
     const TRef W = rect_ref(ch.Wt, (long long)nt * nt * GP_TSQ, nt), Cm = lower_ref(ch.Ct, sh.nlow * GP_TSQ);
-    for (int g0 = 0; g0 < nb; g0 += ch.gs_max) {
-        const int gs = std::min(ch.gs_max, nb - g0);
-        for (int l0 = 0; l0 < L; l0 += ch.lc_max) {
-            const int lc = std::min(ch.lc_max, L - l0);
-            const int ub = gs * lc;                           // (sample, level) pairs of this sub-batch
-            TRef Ls = lower_ref(ch.tiles + (long long)g0 * bstride, bstride);
-            Ls.bdiv = lc;
-            DtArgs da{ch.grid};
-            da.s0 = s0 + g0;
-            da.lv = io.lv.set(L); da.l0 = l0; da.lc = lc;
-            da.pred_noise = io.out.pred_noise; da.W = W; da.Cm = Cm;
-            launch_dt_build(da, ub, st);
-            TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
-            invref.bdiv = lc;
-            w_solve(c, *ch.s, W, Ls, invref, nt, ub, nt);
-            GemmArgs g{};            // CovITE (+ jitter) = Delta - W W^T, lower tiles
-            g.A = W; g.B = W; g.C = Cm;
-            g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt; g.sym = 2;
-            g.k0 = 0; g.k1 = nt; g.nbatch = ub; g.ntiles = (int)sh.nlow;
-            g.order = tri_order(c, nt);
-            gemm(c, g, *ch.s, 3);
-            if (sh.want_cov) {       // ITEDistributions: single level (lc == 1)
-                GatherCovArgs gc{};
-                gc.Cm = Cm; gc.n = n; gc.nt = nt; gc.s0 = s0 + g0; gc.S = io.post.S; gc.out = io.CovITEs;
-                launch_gather_cov(gc, ub, st);
-            }
-            if (sh.want_draws) {
-                // one failure code per pair, then per sample the code of its lowest-index failing level (the reference's loop
-                // order, src/prediction.jl:30-33): a shared word per sample would let the lc levels of a diagonal launch race,
-                // and the lowest failing tile column win across launches
-                HC(hipMemsetAsync(ch.pinfo, 0, sizeof(int) * ub, st));
-                factor_robust(c, *ch.s, Cm, nt, ch.pinfo, n, ub, 3);
-                launch_fold_pair_info(ch.pinfo, io.info + s0 + g0, gs, lc, st);
-                DrawArgs dr{};
-                dr.Lc = Cm; dr.n = n; dr.nt = nt; dr.s0 = s0 + g0; dr.S = io.post.S; dr.l = l0; dr.lc = lc; dr.L = L;
-                dr.spp = io.out.spp; dr.mean = io.out.meanITE; dr.z = io.out.z; dr.zt = ch.zt; dr.seed = io.out.seed;
-                const int64_t eS = io.ens_S > 0 ? io.ens_S : c->ens_S, eo = io.ens_S > 0 ? io.ens_off : c->ens_off;
-                dr.rs0 = dr.s0 + (eS > 0 ? eo : 0); dr.rS = eS > 0 ? eS : io.post.S;
-                if (L == 1) {     // the reference tensor directly: n x (S*spp), instance fastest
-                    dr.out = io.out.ite_draws;
-                    dr.obase = (long long)n * io.out.spp * (s0 + g0); dr.osb = (long long)n * io.out.spp; dr.osl = 0;
-                    dr.osi = 1; dr.osd = n;
-                } else {          // staging [sample][level][d][i]
-                    dr.out = ch.dtmp;
-                    dr.obase = (long long)l0 * io.out.spp * n; dr.osb = (long long)L * io.out.spp * n;
-                    dr.osl = (long long)io.out.spp * n; dr.osi = 1; dr.osd = n;
-                }
-                ProfScope ps(c, 2, (double)ub * io.out.spp, st);     // unit C: work = draws
-                launch_draws(dr, ub, st);
-            }
+    for_pair_batches(sh, ch, [&](int g0, int gs, int l0, int lc, int ub, const TRef& Ls, const TRef& invref) {
+        DtArgs da{ch.grid};
+        da.s0 = s0 + g0;
+        da.lv = io.lv.set(L); da.l0 = l0; da.lc = lc;
+        da.pred_noise = io.out.pred_noise; da.W = W; da.Cm = Cm;
+        launch_dt_build(da, ub, st);
+        w_solve(c, *ch.s, W, Ls, invref, nt, ub, nt);
+        minus_w_wt(c, *ch.s, W, Cm, nt, ub, nt);
+        if (sh.want_cov) {       // ITEDistributions: single level (lc == 1)
+            GatherCovArgs gc{};
+            gc.Cm = Cm; gc.n = n; gc.nt = nt; gc.s0 = s0 + g0; gc.S = io.post.S; gc.out = io.CovITEs;
+            launch_gather_cov(gc, ub, st);
         }
-        if (sh.want_draws && L > 1)
+        if (!sh.want_draws) return;
+        // one failure code per pair, then per sample the code of its lowest-index failing level (the reference's loop
+        // order, src/prediction.jl:30-33): a shared word per sample would let the lc levels of a diagonal launch race,
+        // and the lowest failing tile column win across launches
+        HC(hipMemsetAsync(ch.pinfo, 0, sizeof(int) * ub, st));
+        factor_robust(c, *ch.s, Cm, nt, ch.pinfo, n, ub, 3);
+        launch_fold_pair_info(ch.pinfo, io.info + s0 + g0, gs, lc, st);
+        DrawArgs dr{};
+        dr.Lc = Cm; dr.n = n; dr.nt = nt; dr.s0 = s0 + g0; dr.S = io.post.S; dr.l = l0; dr.lc = lc; dr.L = L;
+        dr.spp = io.out.spp; dr.mean = io.out.meanITE; dr.z = io.out.z; dr.zt = ch.zt; dr.seed = io.out.seed;
+        const int64_t eS = io.ens_S > 0 ? io.ens_S : c->ens_S, eo = io.ens_S > 0 ? io.ens_off : c->ens_off;
+        dr.rs0 = dr.s0 + (eS > 0 ? eo : 0); dr.rS = eS > 0 ? eS : io.post.S;
+        if (L == 1) {     // the reference tensor directly: n x (S*spp), instance fastest
+            dr.out = io.out.ite_draws;
+            dr.obase = (long long)n * io.out.spp * (s0 + g0); dr.osb = (long long)n * io.out.spp; dr.osl = 0;
+            dr.osi = 1; dr.osd = n;
+        } else {          // staging [sample][level][d][i]
+            dr.out = ch.dtmp;
+            dr.obase = (long long)l0 * io.out.spp * n; dr.osb = (long long)L * io.out.spp * n;
+            dr.osl = (long long)io.out.spp * n; dr.osi = 1; dr.osd = n;
+        }
+        {
+            ProfScope ps(c, 2, (double)ub * io.out.spp, st);     // unit C: work = draws
+            launch_draws(dr, ub, st);
+        }
+        if (L > 1 && l0 + lc == L)      // the sample group's last levels: its staged draws into the level-fastest tensor
             launch_draws_scatter(ch.dtmp, io.out.ite_draws, n, L, io.out.spp, s0 + g0, gs, st);
-    }
+    });
 }
 
 // Predictions for new individuals of a chunk.  The mean is one pass over the m x n pairs per sample for all
 // levels and needs no workspace; variance and covariance batch over (sample, level) pairs like unit B: D*(l) (and prior_l B**)
-// into the pair's tiles, W* = D* L^-T against the sample's factor (TRef::bdiv = lc), var from the squared row norms of W*, cov
-// from the lower tiles of prior_l B** + pred_noise I - W* W*^T.
+// into the pair's tiles, W* = D* L^-T against the sample's factor, var from the squared row norms of W*, cov from the lower
+// tiles of prior_l B** + pred_noise I - W* W*^T.
 void unit_new(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     hipStream_t st = ch.s->st;
-    const int nt = sh.nt, mt = sh.mt, L = sh.L, nb = ch.nb;
-    const long long bstride = sh.tiles_per * GP_TSQ, inv_bs = (long long)nt * GP_TSQ;
+    const int nt = sh.nt, mt = sh.mt, nb = ch.nb;
+    const NewIndividuals& f = io.fresh;
     NewArgs na{};
     static_cast<SampleGrid&>(na) = ch.grid;
-    na.Xnew = io.Xnew; na.Unew = io.Unew; na.un_sstride = (long long)io.m * io.nU; na.m = io.m; na.mt = mt;
-    na.S = io.post.S; na.lv = io.lv.set(L); na.l0 = 0; na.lc = 1; na.pred_noise = io.out.pred_noise;
+    na.Xnew = f.Xnew; na.Unew = f.Unew; na.un_sstride = (long long)f.m * io.nU; na.m = f.m; na.mt = mt;
+    na.S = io.post.S; na.lv = io.lv.set(sh.L); na.l0 = 0; na.lc = 1; na.pred_noise = io.out.pred_noise;
     na.alpha = ch.zwork + (long long)nb * sh.Np;
-    na.mean = io.newMean; na.var = io.newVar; na.cov = io.newCov;
-    if (io.newMean) launch_new_mean(na, nb, st);
+    na.mean = f.mean; na.var = f.var; na.cov = f.cov;
+    if (f.mean) launch_new_mean(na, nb, st);
     if (sh.new_pairs) {
         na.W = rect_ref(ch.Wt, (long long)mt * nt * GP_TSQ, nt);
-        na.Cm = io.newCov ? lower_ref(ch.Ct, sh.mlow * GP_TSQ) : TRef{};
-        for (int g0 = 0; g0 < nb; g0 += ch.gs_max) {
-            const int gs = std::min(ch.gs_max, nb - g0);
-            for (int l0 = 0; l0 < L; l0 += ch.lc_max) {
-                const int lc = std::min(ch.lc_max, L - l0);
-                const int ub = gs * lc;                           // (sample, level) pairs of this sub-batch
-                na.s0 = ch.s0 + g0; na.l0 = l0; na.lc = lc;
-                launch_new_build(na, ub, st);
-                TRef Ls = lower_ref(ch.tiles + (long long)g0 * bstride, bstride);
-                Ls.bdiv = lc;
-                TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
-                invref.bdiv = lc;
-                w_solve(c, *ch.s, na.W, Ls, invref, nt, ub, mt);
-                launch_new_var(na, ub, st);
-                if (!io.newCov) continue;
-                GemmArgs g{};            // prior B** + pred_noise I - W* W*^T, lower tiles
-                g.A = na.W; g.B = na.W; g.C = na.Cm;
-                g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = mt; g.mj = mt; g.sym = 2;
-                g.k0 = 0; g.k1 = nt; g.nbatch = ub; g.ntiles = (int)sh.mlow;
-                g.order = tri_order(c, mt);
-                gemm(c, g, *ch.s, 3);
-                launch_new_gather(na, ub, st);
-            }
-        }
+        na.Cm = f.cov ? lower_ref(ch.Ct, sh.mlow * GP_TSQ) : TRef{};
+        for_pair_batches(sh, ch, [&](int g0, int, int l0, int lc, int ub, const TRef& Ls, const TRef& invref) {
+            na.s0 = ch.s0 + g0; na.l0 = l0; na.lc = lc;
+            launch_new_build(na, ub, st);
+            w_solve(c, *ch.s, na.W, Ls, invref, nt, ub, mt);
+            launch_new_var(na, ub, st);
+            if (!f.cov) return;
+            minus_w_wt(c, *ch.s, na.W, na.Cm, nt, ub, mt);
+            launch_new_gather(na, ub, st);
+        });
     }
     HC(hipGetLastError());
 }
@@ -1183,10 +1194,10 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     if (io.lv.W && io.lv.G < 1) throw std::runtime_error("weights without a weight column");
     if (io.out.covW && (!io.lv.W || !io.out.varSATE)) throw std::runtime_error("the joint covariance needs weights and varW");
     if (io.lv.W && !io.out.meanSATE && !io.out.varSATE) { io.lv.W = nullptr; io.lv.G = 0; }      // nothing weighted is asked for
-    if (io.newMean || io.newVar || io.newCov) {
+    if (io.fresh.any()) {
         if (fr.factual) throw std::runtime_error("new individuals have no factual treatment: ordinary levels cannot be predicted for them");
-        if (io.lv.vec || io.m < 1) throw std::runtime_error("new individuals need scalar levels and m >= 1");
-        if (io.newCov && !io.newVar) throw std::runtime_error("the covariance of new individuals needs their variance: its diagonal");
+        if (io.lv.vec || io.fresh.m < 1) throw std::runtime_error("new individuals need scalar levels and m >= 1");
+        if (io.fresh.cov && !io.fresh.var) throw std::runtime_error("the covariance of new individuals needs their variance: its diagonal");
         if (io.CovITEs || io.out.ite_draws) throw std::runtime_error("new individuals cannot be combined with CovITE or draws: one pair workspace");
     }
     if (io.nU < 0) io.nU = c->nU;
@@ -1220,7 +1231,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         const bool back_done = unit_a(c, io, sh, ch);
         if (sh.want_alpha && !back_done) back_substitute(sh, ch);
         if (sh.want_mean) mean_ite(c, io, sh, ch);
-        if (sh.want_w) loo(c, io, sh, ch);
+        if (sh.want_w) loo(io, sh, ch);
         if (sh.want_grad) grad(io, sh, ch);
         if (sh.unitB) unit_b(c, io, sh, ch);
         if (sh.want_new) unit_new(c, io, sh, ch);
@@ -2188,6 +2199,40 @@ int tiled_score(gpslc_ctx* c, PredictIO& io, double* logpdf) {
     return first_info(c);
 }
 
+// One output of an outcome-model call: the caller's array (null: not asked), the io's device pointer that stands for it, doubles
+struct Output { double* host; double** dev; size_t count; };
+using Outputs = std::initializer_list<Output>;
+void take_outputs(gpslc_ctx* c, Outputs outs) {            // staging memory for the asked outputs
+    for (const Output& o : outs)
+        if (o.host) *o.dev = c->io.take<double>(o.count);
+}
+void deliver_outputs(gpslc_ctx* c, Outputs outs) {
+    for (const Output& o : outs)
+        if (o.host) copy_out_large(c, o.host, *o.dev, o.count * sizeof(double));
+}
+
+// The body of the outcome-model entry points that score on the tiled factor (gpslc_y_logpdf beyond the single-workgroup kernels,
+// gpslc_y_loo, gpslc_y_lgo, gpslc_y_logpdf_grad), after their checks: uploads the request's samples and the
+// overrides (Y_or_null: the value being scored — Gen passes it to logpdf — else the ctx's Y), lets `special` add what only this
+// call has, takes device memory for the asked outputs (`outs` points into io) and scores.  Nothing is copied out after a negative status.
+int outcome_call(gpslc_ctx* c, const PredictRequest& rq, const double* X_or_null, const double* Y_or_null, double* logpdf_or_null,
+                 PredictIO& io, Outputs outs, const std::function<void()>& special = nullptr) {
+    const size_t n = (size_t)c->n, S = (size_t)rq.post.S;
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        c->io.reset();
+        io.post.S = rq.post.S; io.post.p = upload_samples(c, rq.post.p, 0, S);
+        io.X = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
+        if (Y_or_null) { io.Y = up(c, Y_or_null, n); io.y_sstride = 0; }
+        if (special) special();
+        take_outputs(c, outs);
+        std::vector<double> lp(logpdf_or_null ? 0 : S);       // the scores are computed either way: kept only when the caller asks
+        const int st = tiled_score(c, io, logpdf_or_null ? logpdf_or_null : lp.data());
+        if (st >= 0) deliver_outputs(c, outs);
+        return st;
+    });
+}
+
 // general (tiled, multi-launch) path of gpslc_gp_logpdf; arguments already validated
 // draws_or_null (host, n x S; needs t_shared == 0): also chol(K_s) target_s — the targets are then standard normals
 int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_t f_shared, const double* ls,
@@ -2397,27 +2442,24 @@ int gpslc_y_logpdf(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_
     if (rc) return rc;
     if (!logpdf) return bad_arg(c, 11, "logpdf is NULL");
     if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return guarded(c, [&]() {
-        const size_t n = (size_t)c->n;
-        if (fast_path_ok(c, c->nU + c->nX + 1, S)) {
-            // small n: every parameter set is one workgroup of ONE launch (k_small.hip); T enters as a feature column
-            std::vector<HostNode> hn;
-            hn.reserve((size_t)S);
-            for (int64_t s = 0; s < S; ++s)
-                hn.push_back(y_node(c->nU, U + s * n * c->nU, uyLS + s * c->nU, c->nX, X_or_null ? X_or_null : c->hX.data(),
-                                    xyLS + s * c->nX, c->hT.data(), tyLS[s], yScale[s], yNoise[s],
-                                    Y_or_null ? Y_or_null : c->hY.data()));
-            return small_nodes_logpdf(c, (int)S, hn.data(), logpdf);
-        }
-        c->io.reset();
+    if (!fast_path_ok(c, c->nU + c->nX + 1, S)) {
         PredictIO io;
-        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
-        io.X = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
-        if (Y_or_null) { io.Y = up(c, Y_or_null, n); io.y_sstride = 0; }    // the value being scored (Gen passes it to logpdf), else the ctx's Y
-        return tiled_score(c, io, logpdf);
+        return outcome_call(c, rq, X_or_null, Y_or_null, logpdf, io, {});
+    }
+    return guarded(c, [&]() {
+        // small n: every parameter set is one workgroup of ONE launch (k_small.hip); T enters as a feature column
+        const size_t n = (size_t)c->n;
+        std::vector<HostNode> hn;
+        hn.reserve((size_t)S);
+        for (int64_t s = 0; s < S; ++s)
+            hn.push_back(y_node(c->nU, U + s * n * c->nU, uyLS + s * c->nU, c->nX, X_or_null ? X_or_null : c->hX.data(),
+                                xyLS + s * c->nX, c->hT.data(), tyLS[s], yScale[s], yNoise[s],
+                                Y_or_null ? Y_or_null : c->hY.data()));
+        return small_nodes_logpdf(c, (int)S, hn.data(), logpdf);
     });
 }
 
+// leave-one-out checks from the tile factor gpslc_y_logpdf's general path computes: the tiled path at every n
 int gpslc_y_loo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
                 const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
                 double* looMean, double* looVar, double* looLpd, double* logpdf_or_null) {
@@ -2425,26 +2467,10 @@ int gpslc_y_loo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
     int rc = validate(c, rq, kSamplesArgs);
     if (rc) return rc;
     if (!looMean && !looVar && !looLpd && !logpdf_or_null) return bad_arg(c, 11, "looMean, looVar, looLpd and logpdf are all NULL");
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return guarded(c, [&]() {
-        // the tiled path at every n: the outputs come from the tile factor gpslc_y_logpdf's general path computes
-        const size_t n = (size_t)c->n, nS = n * (size_t)S;
-        c->io.reset();
-        PredictIO io;
-        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
-        io.X = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
-        if (Y_or_null) { io.Y = up(c, Y_or_null, n); io.y_sstride = 0; }
-        io.looMean = looMean ? c->io.take<double>(nS) : nullptr;
-        io.looVar = looVar ? c->io.take<double>(nS) : nullptr;
-        io.looLpd = looLpd ? c->io.take<double>(nS) : nullptr;
-        std::vector<double> lp(logpdf_or_null ? 0 : (size_t)S);
-        const int st = tiled_score(c, io, logpdf_or_null ? logpdf_or_null : lp.data());
-        if (st < 0) return st;
-        if (looMean) copy_out_large(c, looMean, io.looMean, nS * sizeof(double));
-        if (looVar) copy_out_large(c, looVar, io.looVar, nS * sizeof(double));
-        if (looLpd) copy_out_large(c, looLpd, io.looLpd, nS * sizeof(double));
-        return st;
-    });
+    const size_t nS = (size_t)c->n * (size_t)S;
+    PredictIO io;
+    return outcome_call(c, rq, X_or_null, Y_or_null, logpdf_or_null, io,
+                        {{looMean, &io.loo.mean, nS}, {looVar, &io.loo.var, nS}, {looLpd, &io.loo.lpd, nS}});
 }
 
 // gradient of the outcome log-likelihood: gpslc_y_loo's call with other outputs
@@ -2461,29 +2487,14 @@ int gpslc_y_logpdf_grad(gpslc_ctx* c, int64_t S, const double* U, const double* 
         set_err(c, "gpslc_y_logpdf_grad needs an fp64 context: the pair pass evaluates K in fp64, not the matrix an fp32 context factorises");
         return GPSLC_ERR_UNSUPPORTED;
     }
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
     if (c->nU == 0) dU = duyLS = nullptr;       // the outputs of an empty block are ignored
     if (c->nX == 0) dxyLS = nullptr;
-    return guarded(c, [&]() {
-        // the tiled path at every n, as gpslc_y_loo
-        const size_t n = (size_t)c->n, nS = n * (size_t)S, uS = (size_t)c->nU * (size_t)S, xS = (size_t)c->nX * (size_t)S;
-        c->io.reset();
-        PredictIO io;
-        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
-        io.X = (X_or_null && c->nX) ? up(c, X_or_null, n * c->nX) : c->dX;
-        if (Y_or_null) { io.Y = up(c, Y_or_null, n); io.y_sstride = 0; }
-        const struct { double* host; double** dev; size_t count; } outs[] = {
-            {dU, &io.gU, nS * (size_t)c->nU}, {duyLS, &io.guyLS, uS}, {dxyLS, &io.gxyLS, xS}, {dtyLS, &io.gtyLS, (size_t)S},
-            {dyScale, &io.gyScale, (size_t)S}, {dyNoise, &io.gyNoise, (size_t)S}, {dY, &io.gY, nS}};
-        for (const auto& o : outs)
-            if (o.host) *o.dev = c->io.take<double>(o.count);
-        std::vector<double> lp(logpdf_or_null ? 0 : (size_t)S);
-        const int st = tiled_score(c, io, logpdf_or_null ? logpdf_or_null : lp.data());
-        if (st < 0) return st;
-        for (const auto& o : outs)
-            if (o.host) copy_out_large(c, o.host, *o.dev, o.count * sizeof(double));
-        return st;
-    });
+    const size_t sS = (size_t)S, nS = (size_t)c->n * sS;
+    PredictIO io;
+    return outcome_call(c, rq, X_or_null, Y_or_null, logpdf_or_null, io,
+                        {{dU, &io.grad.U, nS * (size_t)c->nU}, {duyLS, &io.grad.uyLS, (size_t)c->nU * sS},
+                         {dxyLS, &io.grad.xyLS, (size_t)c->nX * sS}, {dtyLS, &io.grad.tyLS, sS}, {dyScale, &io.grad.yScale, sS},
+                         {dyNoise, &io.grad.yNoise, sS}, {dY, &io.grad.Y, nS}});
 }
 
 // leave-group-out checks: gpslc_y_loo's call with a labelling; every check before any device work
@@ -2507,10 +2518,11 @@ int gpslc_y_lgo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
         offsets[(size_t)g + 1] += offsets[g];
     }
     if (!lgoMean && !lgoVar && !lgoLpd) return bad_arg(c, 13, "lgoMean, lgoVar and lgoLpd are all NULL");
-    int mmax = 0;
+    PredictIO io;
+    io.lgo.G = G;
     for (int32_t g = 0; g < G; ++g) {
         const int m = offsets[(size_t)g + 1] - offsets[g];
-        mmax = std::max(mmax, m);
+        io.lgo.mmax = std::max(io.lgo.mmax, m);
         if (m > LGO_MAX_GROUP) {
             char buf[160];
             snprintf(buf, sizeof buf, "group %d has %d members: gpslc_y_lgo takes groups of at most %d", (int)g, m, LGO_MAX_GROUP);
@@ -2522,30 +2534,16 @@ int gpslc_y_lgo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
         std::vector<int> fill(offsets.begin(), offsets.end() - 1);
         for (int64_t i = 0; i < n; ++i) members[(size_t)fill[labels[i]]++] = (int)i;
     }
-    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
-    return guarded(c, [&]() {
-        const size_t nn = (size_t)n, nS = nn * (size_t)S, GS = (size_t)G * (size_t)S;
-        c->io.reset();
-        PredictIO io;
-        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
-        io.X = (X_or_null && c->nX) ? up(c, X_or_null, nn * c->nX) : c->dX;
-        if (Y_or_null) { io.Y = up(c, Y_or_null, nn); io.y_sstride = 0; }
-        int* dmem = c->io.take<int>(nn);
-        int* doff = c->io.take<int>((size_t)G + 1);
-        HC(hipMemcpy(dmem, members.data(), nn * sizeof(int), hipMemcpyHostToDevice));
-        HC(hipMemcpy(doff, offsets.data(), ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice));
-        io.lgoG = G; io.lgoMmax = mmax; io.lgoMembers = dmem; io.lgoOffsets = doff;
-        io.lgoMean = lgoMean ? c->io.take<double>(nS) : nullptr;
-        io.lgoVar = lgoVar ? c->io.take<double>(nS) : nullptr;
-        io.lgoLpd = lgoLpd ? c->io.take<double>(GS) : nullptr;
-        std::vector<double> lp(logpdf_or_null ? 0 : (size_t)S);
-        const int st = tiled_score(c, io, logpdf_or_null ? logpdf_or_null : lp.data());
-        if (st < 0) return st;
-        if (lgoMean) copy_out_large(c, lgoMean, io.lgoMean, nS * sizeof(double));
-        if (lgoVar) copy_out_large(c, lgoVar, io.lgoVar, nS * sizeof(double));
-        if (lgoLpd) copy_out_large(c, lgoLpd, io.lgoLpd, GS * sizeof(double));
-        return st;
-    });
+    const size_t nS = (size_t)n * (size_t)S, GS = (size_t)G * (size_t)S;
+    return outcome_call(c, rq, X_or_null, Y_or_null, logpdf_or_null, io,
+                        {{lgoMean, &io.lgo.mean, nS}, {lgoVar, &io.lgo.var, nS}, {lgoLpd, &io.lgo.lpd, GS}}, [&]() {
+                            auto upload = [&](const std::vector<int>& v) {      // the member list and its offsets
+                                int* d = c->io.take<int>(v.size());
+                                HC(hipMemcpy(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+                                return d;
+                            };
+                            io.lgo.members = upload(members); io.lgo.offsets = upload(offsets);
+                        });
 }
 
 // predictions for m new individuals: host pointers; every check before any device work
@@ -2584,18 +2582,16 @@ int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uy
         io.lv.form = form == GPSLC_NEW_OUTCOME ? FORM_OUTCOME : form == GPSLC_NEW_SLOPE ? FORM_SLOPE : FORM_CONTRAST;
         io.lv.base = doT_base ? up(c, doT_base, (size_t)L) : nullptr;
         io.out.pred_noise = pred_noise;
-        io.m = (int)m;
-        io.Xnew = Xnew ? up(c, Xnew, mm * c->nX) : nullptr;
-        io.Unew = Unew ? up(c, Unew, mm * c->nU * (size_t)S) : nullptr;
-        io.newMean = mean ? c->io.take<double>(mm * SL) : nullptr;
-        io.newVar = (var || cov) ? c->io.take<double>(mm * SL) : nullptr;      // the covariance takes its diagonal from it
-        io.newCov = cov ? c->io.take<double>(mm * mm * SL) : nullptr;
+        io.fresh.m = (int)m;
+        io.fresh.Xnew = Xnew ? up(c, Xnew, mm * c->nX) : nullptr;
+        io.fresh.Unew = Unew ? up(c, Unew, mm * c->nU * (size_t)S) : nullptr;
+        const Outputs outs = {{mean, &io.fresh.mean, mm * SL}, {var, &io.fresh.var, mm * SL}, {cov, &io.fresh.cov, mm * mm * SL}};
+        take_outputs(c, outs);
+        if (cov && !var) io.fresh.var = c->io.take<double>(mm * SL);      // the covariance takes its diagonal from it
         io.info = c->io.take<int>((size_t)S);
         run_predict(c, io);
         const int st = first_info(c);
-        if (mean) copy_out_large(c, mean, io.newMean, mm * SL * sizeof(double));
-        if (var) copy_out_large(c, var, io.newVar, mm * SL * sizeof(double));
-        if (cov) copy_out_large(c, cov, io.newCov, mm * mm * SL * sizeof(double));
+        deliver_outputs(c, outs);
         if (st > 0)      // a sample whose factorisation broke down: NaN in everything of it
             for (int64_t s = 0; s < S; ++s) {
                 if (c->last_info[(size_t)s] == 0) continue;
