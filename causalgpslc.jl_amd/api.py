@@ -330,6 +330,23 @@ class Context:
             raise ValueError(f"unknown gradient outputs {sorted(unknown)}: choose from {self.GRAD_OUTPUTS}")
         return self._call_for(self.lib.gpslc_y_logpdf_grad, shapes, want, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise)
 
+    NODE_GRAD_OUTPUTS = ("dF", "dls", "dscale", "dnoise", "dtarget", "logpdf")
+
+    def nodes_logpdf_grad(self, nodes, want=NODE_GRAD_OUTPUTS):
+        """gpslc_nodes_logpdf_grad for a sequence of (F, LS, scale, noise, target) as ``nodesLogpdf`` takes them: ``(status, out)``
+        with ``out`` a dict of the outputs named in ``want`` in the library's flat layouts — ``dF`` (n * sum nF,): the nodes'
+        (n, nF) column-major blocks one after the other; ``dls`` (sum nF,); ``dscale``, ``dnoise``, ``logpdf`` (count,);
+        ``dtarget`` (n, count) — the others None (NULL to the library).  The status is returned, not raised, as for ``y_loo``."""
+        unknown = set(want) - set(self.NODE_GRAD_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown gradient outputs {sorted(unknown)}: choose from {self.NODE_GRAD_OUTPUTS}")
+        cnt = len(nodes)
+        arr, _keep = _marshal_nodes(nodes, self)
+        total = sum(int(arr[i].nF) for i in range(cnt))
+        shapes = {"dF": (self.n * total,), "dls": (total,), "dscale": (cnt,), "dnoise": (cnt,), "dtarget": (self.n, cnt),
+                  "logpdf": (cnt,)}          # in NODE_GRAD_OUTPUTS' order
+        return self._call_for(self.lib.gpslc_nodes_logpdf_grad, shapes, want, cnt, C.cast(arr, C.c_void_p))
+
     def predict_new(self, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, doT, doT_base, pred_noise,
                     want=("mean", "var")):
         """gpslc_predict_new with host arrays as given (None = NULL): ``(status, mean, var, cov)`` — the outputs named in
@@ -1197,6 +1214,29 @@ def nodesLogpdf(nodes, ctx: Context, fail_value=None):
         return out
     ctx.check(st)
     return out
+
+
+def nodesLogpdfGrad(nodes, ctx: Context, want=Context.NODE_GRAD_OUTPUTS):
+    """The fused whole-model gradient (gpslc_nodes_logpdf_grad): ``nodes`` as for nodesLogpdf; one dict per
+    node with ``dF`` (n, nF), ``dls`` (nF,), ``dscale``, ``dnoise``, ``dtarget`` (n,) and ``logpdf`` — the derivatives of the
+    node's score with respect to its feature block, lengthscales, scale, noise and target (the parameters themselves, not
+    their logarithms); outputs not named in ``want`` are None.  One call and, at the sizes the chains run at, one launch.
+    A covariance that is not positive definite raises PosDefException."""
+    st, out = ctx.nodes_logpdf_grad(nodes, want)
+    ctx.check(st)
+    res, fo, lo = [], 0, 0
+    for i, nd in enumerate(nodes):
+        F = nd[0]
+        nF = 0 if F is None or np.size(F) == 0 else (1 if np.ndim(F) == 1 else np.shape(F)[1])
+        res.append({"dF": None if out["dF"] is None else out["dF"][ctx.n * fo:ctx.n * (fo + nF)].reshape((ctx.n, nF), order="F"),
+                    "dls": None if out["dls"] is None else out["dls"][lo:lo + nF],
+                    "dscale": None if out["dscale"] is None else float(out["dscale"][i]),
+                    "dnoise": None if out["dnoise"] is None else float(out["dnoise"][i]),
+                    "dtarget": None if out["dtarget"] is None else out["dtarget"][:, i],
+                    "logpdf": None if out["logpdf"] is None else float(out["logpdf"][i])})
+        fo += nF
+        lo += nF
+    return res
 
 
 def nodesDraw(nodes, ctx: Context):

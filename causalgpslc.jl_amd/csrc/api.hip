@@ -708,6 +708,7 @@ struct PredictIO {
     Loo loo;
     Lgo lgo;
     Grad grad;
+    bool grad_no_t = false;          // node mode of the gradient (GradArgs::no_t): no treatment column
     NewIndividuals fresh;
 };
 
@@ -816,7 +817,7 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     if (sh.want_w) b.loo_w = take((size_t)sh.nlow * GP_TSQ);
     if (sh.want_loo || sh.grad_c) b.loo_c = take(sh.Np);
     if (sh.grad_pairs) {      // F numbers per lower tile; 128 nU per (tile row, tile column)
-        b.grad_ls = take((size_t)sh.nlow * (io.nU + io.nX + 1));
+        b.grad_ls = take((size_t)sh.nlow * (io.nU + io.nX + (io.grad_no_t ? 0 : 1)));
         if (io.nU > 0) b.grad_u = take((size_t)nt * nt * io.nU * GP_TS);
     }
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
@@ -1061,6 +1062,7 @@ void grad(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     ga.part_ls = ch.grad_ls; ga.part_u = ch.grad_u; ga.queue = ch.s->queue;
     ga.dU = io.grad.U; ga.duyLS = io.grad.uyLS; ga.dxyLS = io.grad.xyLS; ga.dtyLS = io.grad.tyLS;
     ga.dyScale = io.grad.yScale; ga.dyNoise = io.grad.yNoise; ga.dY = io.grad.Y;
+    ga.no_t = io.grad_no_t ? 1 : 0;
     if (sh.grad_pairs) {
         rearm_queue(*ch.s);
         launch_grad_pairs(ga, ch.nb, st);
@@ -1424,23 +1426,38 @@ void copy_out_rows(gpslc_ctx* c, void* dst, size_t dpitch, const void* src_dev, 
 }
 void copy_out_large(gpslc_ctx* c, void* dst, const void* src_dev, size_t bytes) { copy_out_rows(c, dst, bytes, src_dev, bytes, 1); }
 
+// The gradient outputs of gpslc_nodes_logpdf_grad (host, any may be null): dF and dls are the nodes' n x nF_i blocks and nF_i
+// values concatenated in node order, dscale and dnoise hold `count` values, dtarget is n x count
+struct NodeGradOut {
+    double *dF, *dls, *dscale, *dnoise, *dtarget;
+    bool any() const { return dF || dls || dscale || dnoise || dtarget; }
+};
+
 // scores `count` nodes in ONE launch; logdet/quad/info per node come back through the pinned buffer.
 // Returns the first failing pivot (0 = all fine); logpdf[i] = gauss_logpdf(n, logdet_i, quad_i).
 // draw_out (optional, host, n x count): node i also returns chol(K_i) * target_i.
-int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* logpdf, double* draw_out = nullptr) {
+// grad (optional; RBF nodes that fit small_grad_lds_bytes): the same launch also differentiates every score (k_small.hip); a
+// node whose factorisation broke down gets NaN.
+int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* logpdf, double* draw_out = nullptr,
+                       const NodeGradOut* grad = nullptr) {
     ensure_streams(c);
     const size_t n = (size_t)c->n;
-    size_t doubles = 0;
+    size_t doubles = 0, gdoubles = 0;
     int nF_max = 0;
     for (int i = 0; i < count; ++i) {
         doubles += n * nodes[i].nF + n;
+        if (grad) {      // raw features and lengthscales in, [dF | dls | dscale dnoise | dtarget] out
+            doubles += n * nodes[i].nF + nodes[i].nF;
+            gdoubles += n * nodes[i].nF + nodes[i].nF + 2 + n;
+        }
         nF_max = std::max(nF_max, nodes[i].nF);
     }
     const size_t off_out = ((size_t)count * sizeof(SmallNode) + 63) & ~size_t(63);
     // 4 results + 8 stamp words per node (+ 8 x 8 per-wave words of node 0 for the mid-size kernel: measurement build)
     const size_t off_data = off_out + ((size_t)count * 12 + 64) * sizeof(double);
     const size_t off_draw = off_data + doubles * sizeof(double);          // [count][n] draws (pinned, written by the kernel)
-    pin_reserve(c, off_draw + (draw_out ? (size_t)count * n * sizeof(double) : 0));
+    const size_t off_grad = off_draw + (draw_out ? (size_t)count * n * sizeof(double) : 0);     // the gradient launch's result block
+    pin_reserve(c, off_grad + gdoubles * sizeof(double));
     void* dbase = nullptr;
     HC(hipHostGetDevicePointer(&dbase, c->pin, 0));
     char* dev = static_cast<char*>(dbase);
@@ -1455,10 +1472,11 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
         for (size_t r = 0; r < n; ++r) hd[o + r] = col[r] * il;
         o += n;
     };
+    size_t go = 0;
     for (int i = 0; i < count; ++i) {
         const HostNode& h = nodes[i];
         SmallNode& sn = hn[i];
-        sn.nF = h.nF; sn.pad_ = 0; sn.scale = h.scale; sn.noise = h.noise;
+        sn.nF = h.nF; sn.gofs = (int)go; sn.scale = h.scale; sn.noise = h.noise;
         sn.cov = h.dev_cov; sn.covscale = h.covscale;
         sn.Fs = dd + o;
         for (int g = 0; g < 2; ++g)
@@ -1467,6 +1485,17 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
         sn.target = dd + o;
         memcpy(hd + o, h.target, n * sizeof(double));
         o += n;
+        if (grad) {      // D comes from the raw features: they and the lengthscales follow the target
+            for (int g = 0; g < 2; ++g) {
+                if (h.nFpart[g]) memcpy(hd + o, h.F[g], n * (size_t)h.nFpart[g] * sizeof(double));
+                o += n * (size_t)h.nFpart[g];
+            }
+            if (h.col) { memcpy(hd + o, h.col, n * sizeof(double)); o += n; }
+            for (int g = 0; g < 2; ++g)
+                for (int f = 0; f < h.nFpart[g]; ++f) hd[o++] = h.ls[g][f];
+            if (h.col) hd[o++] = h.ls_col;
+            go += n * (size_t)h.nF + h.nF + 2 + n;
+        }
     }
     SmallArgs a{};
     a.nodes = reinterpret_cast<const SmallNode*>(dev);
@@ -1475,7 +1504,8 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
     a.out = reinterpret_cast<double*>(dev + off_out);
     a.stamps = nullptr;
     a.draw = draw_out ? reinterpret_cast<double*>(dev + off_draw) : nullptr;
-    const bool in_lds = small_gp_lds_bytes((int)n, nF_max) <= kLdsBytes;
+    const bool in_lds = grad || small_gp_lds_bytes((int)n, nF_max) <= kLdsBytes;
+    if (grad && small_grad_lds_bytes((int)n, nF_max) > kLdsBytes) throw std::runtime_error("gradient launch beyond its LDS image");
     if (!in_lds) {       // mid-size kernel: per-node scratch for the finished block columns and the scaled features
         const size_t per = (mid_gp_scratch_doubles((int)n, nF_max) + 31) & ~size_t(31);
         arena_reserve(c, c->scratch, per * (size_t)count * sizeof(double) + 256);
@@ -1488,7 +1518,8 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
     if (want_stamps) a.stamps = a.out + 4 * (size_t)count;
 #endif
     hipStream_t st = c->slots[0].st;
-    if (in_lds) launch_small_gp(a, count, nF_max, st);
+    if (grad) launch_small_grad(a, reinterpret_cast<double*>(dev + off_grad), count, nF_max, st);
+    else if (in_lds) launch_small_gp(a, count, nF_max, st);
     else launch_mid_gp(a, count, nF_max, st);
     HC(hipGetLastError());
     HC(hipStreamSynchronize(st));
@@ -1517,6 +1548,25 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
         c->last_info[i] = info;
         if (info != 0 && first == 0) first = info;
         logpdf[i] = gauss_logpdf(n, hout[4 * i], hout[4 * i + 1]);
+    }
+    if (grad) {
+        const double* r = reinterpret_cast<const double*>(c->pin + off_grad);
+        size_t fo = 0, lo = 0;        // node i's slots of dF and dls
+        auto deliver = [](double* dst, const double* src, size_t cnt, bool bad) {
+            if (!dst) return;
+            if (bad) std::fill(dst, dst + cnt, (double)NAN);
+            else memcpy(dst, src, cnt * sizeof(double));
+        };
+        for (int i = 0; i < count; ++i) {
+            const size_t nF = (size_t)nodes[i].nF;
+            const bool bad = c->last_info[i] != 0;
+            deliver(grad->dF ? grad->dF + fo : nullptr, r, n * nF, bad);
+            deliver(grad->dls ? grad->dls + lo : nullptr, r + n * nF, nF, bad);
+            deliver(grad->dscale ? grad->dscale + i : nullptr, r + n * nF + nF, 1, bad);
+            deliver(grad->dnoise ? grad->dnoise + i : nullptr, r + n * nF + nF + 1, 1, bad);
+            deliver(grad->dtarget ? grad->dtarget + (size_t)i * n : nullptr, r + n * nF + nF + 2, n, bad);
+            fo += n * nF; lo += nF; r += n * nF + nF + 2 + n;
+        }
     }
     return first;
 }
@@ -2235,9 +2285,11 @@ int outcome_call(gpslc_ctx* c, const PredictRequest& rq, const double* X_or_null
 
 // general (tiled, multi-launch) path of gpslc_gp_logpdf; arguments already validated
 // draws_or_null (host, n x S; needs t_shared == 0): also chol(K_s) target_s — the targets are then standard normals
+// grad_or_null (host, the layouts of S sets of nF columns: dF n x nF x S, dls nF x S, dtarget n x S): also the gradient of every
+// score, §21's pair pass and finish kernel in node mode (GradArgs::no_t)
 int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_t f_shared, const double* ls,
                       const double* scale, const double* noise, const double* target, int32_t t_shared, double* logpdf,
-                      double* draws_or_null = nullptr) {
+                      double* draws_or_null = nullptr, const NodeGradOut* grad_or_null = nullptr) {
     const size_t n = (size_t)c->n;
     c->io.reset();
     const double* dF = nF ? up(c, F, n * nF * (f_shared ? 1 : S)) : nullptr;
@@ -2262,14 +2314,22 @@ int gp_logpdf_general(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int3
         HC(hipStreamSynchronize(c->slots[0].st));
         io.nz = dtg; io.nzero = zero_mean; io.ndraw = ddraw;
     }
+    NodeGradOut g = grad_or_null ? *grad_or_null : NodeGradOut{};
+    if (nF == 0) g.dF = g.dls = nullptr;
+    const Outputs outs = {{g.dF, &io.grad.U, n * (size_t)nF * S}, {g.dls, &io.grad.uyLS, (size_t)nF * S}, {g.dscale, &io.grad.yScale, (size_t)S},
+                          {g.dnoise, &io.grad.yNoise, (size_t)S}, {g.dtarget, &io.grad.Y, n * (size_t)S}};
+    io.grad_no_t = true;
+    take_outputs(c, outs);
     const int st = tiled_score(c, io, logpdf);
     if (draws_or_null) HC(hipMemcpy(draws_or_null, ddraw, n * (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    deliver_outputs(c, outs);
     return st;
 }
 
 // ONE batched pass of the general tiled path over all nodes of a call (S = count parameter sets with per-set feature blocks
 // and per-set targets); draws_or_null: also chol(K_i) target_i per node (gpslc_nodes_draw)
-int nodes_general(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, int nF_max, double* logpdf, double* draws_or_null) {
+int nodes_general(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, int nF_max, double* logpdf, double* draws_or_null,
+                  const NodeGradOut* grad_or_null = nullptr) {
     // Nodes with fewer than nF_max feature columns are padded with zero
     // columns of lengthscale 1: a padding column adds (0 * 1 - 0 * 1)^2 = +0.0 to every squared distance, so a
     // node's Gram matrix — and its score — is bit-identical to the one its own feature count would give.
@@ -2302,7 +2362,23 @@ int nodes_general(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, int nF_m
         memcpy(tg + (size_t)i * n, q.target, n * sizeof(double));
     }
     const double* Fsrc = nF_max == 0 ? nullptr : (same_f ? nodes[0].F : Fp.data());
-    return gp_logpdf_general(c, count, nF_max, Fsrc, same_f ? 1 : 0, nF_max ? lsp : nullptr, sc, no, tg, 0, logpdf, draws_or_null);
+    if (!grad_or_null)
+        return gp_logpdf_general(c, count, nF_max, Fsrc, same_f ? 1 : 0, nF_max ? lsp : nullptr, sc, no, tg, 0, logpdf, draws_or_null);
+    // The gradient comes back in the padded layout (count sets of nF_max columns, one block per node even where the nodes share
+    // their features); the padding columns' gradients are dropped here.  A real column's sums do not see the padding: K adds
+    // +0.0 per padding column and every feature is summed on its own, so a node's bits do not depend on the widest node.
+    const NodeGradOut& g = *grad_or_null;
+    std::vector<double> pF(g.dF ? n * (size_t)nF_max * count : 0), pls(g.dls ? (size_t)nF_max * count : 0);
+    const NodeGradOut padded{g.dF ? pF.data() : nullptr, g.dls ? pls.data() : nullptr, g.dscale, g.dnoise, g.dtarget};
+    const int st = gp_logpdf_general(c, count, nF_max, Fsrc, same_f ? 1 : 0, nF_max ? lsp : nullptr, sc, no, tg, 0, logpdf, nullptr, &padded);
+    size_t fo = 0, lo = 0;
+    for (int i = 0; i < count && st >= 0; ++i) {
+        const size_t nF = (size_t)nodes[i].nF;
+        if (g.dF && nF) memcpy(g.dF + fo, pF.data() + (size_t)i * n * nF_max, n * nF * sizeof(double));
+        if (g.dls && nF) memcpy(g.dls + lo, pls.data() + (size_t)i * nF_max, nF * sizeof(double));
+        fo += n * nF; lo += nF;
+    }
+    return st;
 }
 
 // The argument checks of the fused node calls (`out`: the output the call must deliver, argument 4 of both signatures):
@@ -2631,6 +2707,35 @@ int gpslc_gp_logpdf(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_
 int gpslc_nodes_logpdf(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, double* logpdf) {
     const int nF_max = nodes_check(c, count, nodes, logpdf, "logpdf is NULL");
     return nF_max < 0 ? nF_max : nodes_score(c, count, nodes, nF_max, logpdf, nullptr);
+}
+
+// The fused whole-model gradient: the score's single launch with the gradient phases behind it while every node
+// fits small_grad_lds_bytes, else — one node that does not fit, more than 4096 nodes — the tiled path for the whole call
+int gpslc_nodes_logpdf_grad(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, double* dF, double* dls, double* dscale,
+                            double* dnoise, double* dtarget, double* logpdf_or_null) {
+    const NodeGradOut g{dF, dls, dscale, dnoise, dtarget};
+    const double* some = g.any() ? (dF ? dF : dls ? dls : dscale ? dscale : dnoise ? dnoise : dtarget) : nullptr;
+    const int nF_max = nodes_check(c, count, nodes, some, "dF, dls, dscale, dnoise and dtarget are all NULL");
+    if (nF_max < 0) return nF_max;
+    if (c->flags & GPSLC_FLAG_FP32_KERNEL) {
+        set_err(c, "gpslc_nodes_logpdf_grad needs an fp64 context: the gradient evaluates K in fp64, not the matrix an fp32 context factorises");
+        return GPSLC_ERR_UNSUPPORTED;
+    }
+    if (count == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        std::vector<double> lp;
+        double* logpdf = logpdf_or_null;
+        if (!logpdf) { lp.resize((size_t)count); logpdf = lp.data(); }
+        if (small_grad_lds_bytes((int)c->n, nF_max) > kLdsBytes || count > 4096)
+            return nodes_general(c, count, nodes, nF_max, logpdf, nullptr, &g);
+        std::vector<HostNode> hn;
+        hn.reserve((size_t)count);
+        for (int i = 0; i < count; ++i) {
+            const gpslc_node& q = nodes[i];
+            hn.push_back(rbf_node(q.nF, q.F, q.ls, q.scale, q.noise, q.target));
+        }
+        return small_nodes_logpdf(c, count, hn.data(), logpdf, nullptr, &g);
+    });
 }
 
 int gpslc_nodes_draw(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, double* draws, double* logpdf_or_null) {

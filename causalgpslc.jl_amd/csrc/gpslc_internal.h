@@ -381,7 +381,9 @@ struct GradArgs : SampleGrid {
     int* queue;                                 // the stream's ticket counters (GemmArgs::queue)
     // outputs (device, in the layouts of the arguments they differentiate) or null
     double *dU, *duyLS, *dxyLS, *dtyLS, *dyScale, *dyNoise, *dY;
-    __host__ __device__ int F() const { return nU + nX + 1; }
+    int no_t;                                   // node mode (gpslc_nodes_logpdf_grad): the features are [U | X] alone,
+                                                // T (null on a context without data) and tyLS are never read
+    __host__ __device__ int F() const { return nU + nX + (no_t ? 0 : 1); }
     __host__ __device__ const double* raw_column(long long s, int f) const { return f < nU + nX ? column(s, f) : T; }
     __host__ __device__ double ls(long long s, int f) const { return f < nU + nX ? lengthscale(s, f) : p.tyLS[s]; }
 };
@@ -498,8 +500,8 @@ struct SmallNode {
     const double* target;   // n
     double scale, noise;
     int nF;
-    int pad_;
-    const double* cov;      // non-null: dense n x n covariance in DEVICE memory (lower triangle read); the matrix is
+    int gofs;               // gradient launch: where this node's results start in the launch's result block (doubles); else 0
+    const double* cov;     // non-null: dense n x n covariance in DEVICE memory (lower triangle read); the matrix is
     double covscale;        //   covscale * cov instead of the RBF Gram matrix (the :U => u => :U prior nodes)
 };
 #define SMALL_INLINE_NODES 4
@@ -516,6 +518,10 @@ struct SmallArgs {
 };
 size_t small_gp_lds_bytes(int n, int nF);
 void launch_small_gp(const SmallArgs& a, int count, int nF_max, hipStream_t st);
+// the score and its gradient in the same launch (k_small.hip); the nodes' staging carries the raw features and
+// lengthscales behind the target, node i's results land at gout + nodes[i].gofs
+size_t small_grad_lds_bytes(int n, int nF);
+void launch_small_grad(const SmallArgs& a, double* gout, int count, int nF_max, hipStream_t st);
 // left-looking variant for 176 < n <= 640: only the current block column in LDS, finished columns in an L2-resident scratch
 size_t mid_gp_scratch_doubles(int n, int nF);
 size_t mid_gp_lds_bytes(int n, int nF);

@@ -31,10 +31,11 @@
 
 #include "sm_blocks.h"
 
-__global__ __launch_bounds__(SM_THREADS) void small_gp_logpdf_kernel(SmallArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double P[];
+// The whole score of one node on the LDS image P.  GRAD: the gradient kernel's instantiation — the same operations in the same
+// order, and the factor's diagonal blocks are kept as draw mode keeps them.
+template <bool GRAD>
+__device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNode& nd, double* P) {
     const unsigned long long tstart = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
-    const SmallNode nd = blockIdx.x < SMALL_INLINE_NODES ? a.inl[blockIdx.x] : a.nodes[blockIdx.x];
     const int n = a.n, NB = a.NB, NP = NB * SB;
     const int NBLK = NB * (NB + 1) / 2;
     double* yv = P + NBLK * 256;      // right-hand side, updated in place block by block
@@ -139,8 +140,8 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_logpdf_kernel(SmallArgs a
             if (is_diag) {
                 if (wave == 0) {
                     ldv[SB * p + li] = lcc;              // the score never reads the factor's diagonal block again
-                    if (a.draw) {
-                        // a draw does.  The other carrying waves may still be loading their copy of the block's rows, of
+                    if (GRAD || a.draw) {
+                        // a draw does, and so does the gradient.  The other carrying waves may still be loading their copy of the block's rows, of
                         // which only the lower triangle matters: L_pp goes, transposed, into the strictly UPPER triangle
                         // (element (c, li) <- L[li][c], c < li); its diagonal is ldv.
                         double* up = SBLK(p, p) + li * SB;
@@ -263,6 +264,307 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_logpdf_kernel(SmallArgs a
                 sp[4] = (double)t_chain; sp[5] = (double)(__builtin_amdgcn_s_memtime() - tstart);
             }
         }
+    }
+}
+
+__global__ __launch_bounds__(SM_THREADS) void small_gp_logpdf_kernel(SmallArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double P[];
+    const SmallNode nd = blockIdx.x < SMALL_INLINE_NODES ? a.inl[blockIdx.x] : a.nodes[blockIdx.x];
+    small_gp_score<false>(a, nd, P);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The gradient of the same score in the same launch: with alpha = A^-1 target, Q = alpha alpha^T - A^-1,
+// P = Q o K, c = diag(A^-1) and D_rcf = F_rf - F_cf from the RAW features
+//     dF_rf = -(2 / ls_f^2) sum_c P_rc D_rcf      dls_f = (1 / ls_f^3) sum_rc P_rc D_rcf^2      dtarget = -alpha
+//     dnoise = (alpha . alpha - sum c) / 2        dscale = (alpha . target - n - noise (alpha . alpha - sum c)) / (2 scale)
+// After the score (factor L in the packed blocks, z = L^-1 target) everything stays on the LDS image:
+//   W = L^-1   in place.  The diagonal blocks by substitution (one wave per block, a column per lane), then block columns from
+//              right to left: Z_k = L_kj W_jj for the blocks below the diagonal (left transposed), X_i = -sum_{j < k <= i}
+//              W_ik Z_k, the 16 x 16 products on v_mfma_f64_16x16x4_f64; a block column's results wait in accumulators for the
+//              barrier after which they replace their operands.  Then every block is transposed in place, once: what follows
+//              reads W by columns, and a column of a packed block is one LDS bank pair.
+//   alpha = W^T z, one row per thread, ascending k.
+//   A^-1 = W^T W over the lower blocks, block rows ascending: row i reads the rows >= i only, so it overwrites its operands.
+//   P      replaces A^-1 block by block, K_rc evaluated again from the scaled features by the Gram build's arithmetic; rows and
+//          columns >= n are exact zeros.
+//   sums   a wave owns block rows; for a row it walks every block column of the symmetric P (block (j, i) read transposed for
+//          j > i) with D from the raw features, which sit in LDS beside the scaled ones.  dF is a row sum inside the wave
+//          (four lane groups, xor 16 then 32); a lengthscale sum goes through one partial per block row, added in ascending
+//          block-row order.  No atomics; nothing depends on the other nodes of the launch.
+// Staging of a node (pinned): [scaled features n x nF][target n][raw features n x nF][ls nF]; results at gout + nd.gofs:
+// [dF n x nF][dls nF][dscale][dnoise][dtarget n].  A failed factorisation leaves garbage here: the host answers NaN from info.
+// ---------------------------------------------------------------------------------------------------------------------
+// fragment of the TRANSPOSE of a packed block: element (k = 4kk + lane>>4, col = lane&15) of blk, i.e. row lane&15 of blk^T
+__device__ __forceinline__ double sm_frag_t(const double* blk, int kk, int lane) {
+    return blk[(lane & 15) * SB + 4 * kk + (lane >> 4)];
+}
+// acc(r, c) += sum_m fb(r, m) fa(c, m): r = lane & 15, c = (lane >> 4) + 4 v, the operands as (row = lane & 15, m = 4 kk + lane >> 4)
+#define SM_MFMA_ADD(fa, fb, acc) __builtin_amdgcn_mfma_f64_16x16x4f64(fa, fb, acc, 0, 0, 0)
+
+__global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, double* gout) {
+    extern __shared__ __attribute__((aligned(16))) double P[];
+    const SmallNode nd = blockIdx.x < SMALL_INLINE_NODES ? a.inl[blockIdx.x] : a.nodes[blockIdx.x];
+    small_gp_score<true>(a, nd, P);
+
+    const int n = a.n, NB = a.NB, NP = NB * SB, nF = nd.nF;
+    const int NBLK = NB * (NB + 1) / 2;
+    double* yv = P + NBLK * 256;      // the score's layout
+    double* zv = yv + NP;
+    double* ldv = zv + NP;
+    double* fs = ldv + NP + SM_WAVES * SB;
+    double* al = fs + nF * NP;        // alpha
+    double* rw = al + NP;             // raw features [f][NP]
+    double* lsp = rw + nF * NP;       // [f][NB]: a block row's share of sum P D_f^2
+    double* lsl = lsp + nF * NB;      // the lengthscales: the staging buffer is host memory, a round trip per read
+    const double* raw = nd.target + n;
+    const double* lsv = raw + (long long)nF * n;
+    double* g_dF = gout + nd.gofs;
+    double* g_dls = g_dF + (long long)nF * n;
+    double* g_sn = g_dls + nF;        // dscale, dnoise
+    double* g_dt = g_sn + 2;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lg = lane >> 4;
+
+    // the forward solve consumed yv: the target again, the raw features and the lengthscales.  The staging buffer is host memory
+    // and a round trip to it costs microseconds: a thread's loads (target, lengthscale, four raw values per batch) are all issued
+    // before the first of them is stored
+    {
+        const double tg = tid < n ? nd.target[tid] : 0.0;            // NP <= 176 and nF <= 32: one value per thread
+        const double lf = tid < nF ? lsv[tid] : 0.0;
+        const int total = nF * NP;
+        for (int base = 0; base < total; base += 4 * SM_THREADS) {
+            double v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int idx = base + tid + SM_THREADS * u;
+                const int f = idx / NP, i = idx - f * NP;
+                v[u] = (idx < total && i < n) ? raw[(long long)f * n + i] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int idx = base + tid + SM_THREADS * u;
+                if (idx < total) rw[idx] = v[u];
+            }
+        }
+        if (tid < NP) yv[tid] = tg;
+        if (tid < nF) lsl[tid] = lf;
+    }
+
+    // ---- W_pp = L_pp^-1: L_pp sits transposed above the diagonal (L[r][m] at element (m, r)), its diagonal in ldv.  Lane c
+    // solves L w = e_c (w[m] = 0 falls out for m < c) and writes column c, zeros above the diagonal
+    for (int p = wave; p < NB; p += SM_WAVES) {
+        if (lane < SB) {
+            double* B = SBLK(p, p);
+            double w[SB];
+#pragma unroll
+            for (int r = 0; r < SB; ++r) {
+                double s = (r == lane) ? 1.0 : 0.0;
+#pragma unroll
+                for (int m = 0; m < r; ++m) s = fma(-B[r * SB + m], w[m], s);
+                w[r] = s / ldv[SB * p + r];
+            }
+#pragma unroll
+            for (int r = 0; r < SB; ++r) B[lane * SB + r] = (r >= lane) ? w[r] : 0.0;
+        }
+    }
+    __syncthreads();
+
+    auto store_block = [&](double* B, const d4& x, double sign) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) B[(lg + 4 * v) * SB + li] = sign * x[v];
+    };
+    const d4 zero4 = {0.0, 0.0, 0.0, 0.0};
+
+    // ---- block columns of W from right to left
+    for (int j = NB - 2; j >= 0; --j) {
+        const double* Wjj = SBLK(j, j);
+        for (int k = j + 1 + wave; k < NB; k += SM_WAVES) {         // Z_k = L_kj W_jj, left TRANSPOSED in L_kj's place (the loads
+            double* Lkj = SBLK(k, j);                                // feed the stores' values): the products below then read
+            d4 acc = zero4;                                          // both operands along the banks
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) acc = SM_MFMA_ADD(sm_frag(Lkj, kk, lane), sm_frag_t(Wjj, kk, lane), acc);
+            store_block(Lkj, acc, 1.0);
+        }
+        __syncthreads();
+        d4 x[2] = {zero4, zero4};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                                // at most 10 blocks below the diagonal: two per wave
+            const int i = j + 1 + wave + SM_WAVES * u;
+            if (i < NB)
+                for (int k = j + 1; k <= i; ++k) {
+                    const double* Wik = SBLK(i, k);
+                    const double* Zk = SBLK(k, j);
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) x[u] = SM_MFMA_ADD(sm_frag(Zk, kk, lane), sm_frag(Wik, kk, lane), x[u]);
+                }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = j + 1 + wave + SM_WAVES * u;
+            if (i < NB) store_block(SBLK(i, j), x[u], -1.0);
+        }
+    }
+    __syncthreads();
+
+    // ---- every block transposed in place (a wave's four loads execute before its four stores): alpha and W^T W read W by
+    // columns, which in the packed layout is a 16-way bank conflict per read
+    for (int blk = wave; blk < NBLK; blk += SM_WAVES) {
+        double* B = P + (blk << 8);
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = B[lane + 64 * u];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) B[li * SB + lg + 4 * u] = v[u];
+    }
+    __syncthreads();
+
+    // ---- alpha_r = sum_{k >= r} W[k][r] z_k
+    for (int r = tid; r < NP; r += SM_THREADS) {
+        const int br = r >> 4, rl = r & 15;
+        double acc = 0.0;
+        for (int bk = br; bk < NB; ++bk) {
+            const double* B = SBLK(bk, br) + rl;
+#pragma unroll
+            for (int kl = 0; kl < SB; ++kl) acc = fma(B[kl * SB], zv[SB * bk + kl], acc);
+        }
+        al[r] = acc;
+        if (r < n) g_dt[r] = -acc;
+    }
+    __syncthreads();
+
+    // ---- A^-1 = W^T W: block (i, j) = sum_{k >= i} W_ki^T W_kj, rows ascending (the blocks hold W_ki^T now)
+    for (int i = 0; i < NB; ++i) {
+        d4 x[2] = {zero4, zero4};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int j = wave + SM_WAVES * u;
+            if (j <= i)
+                for (int k = i; k < NB; ++k) {
+                    const double* Wki = SBLK(k, i);
+                    const double* Wkj = SBLK(k, j);
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) x[u] = SM_MFMA_ADD(sm_frag(Wkj, kk, lane), sm_frag(Wki, kk, lane), x[u]);
+                }
+        }
+        __syncthreads();                 // everybody has read row i
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int j = wave + SM_WAVES * u;
+            if (j <= i) store_block(SBLK(i, j), x[u], 1.0);
+        }
+    }
+    __syncthreads();
+
+    // ---- the closed forms: alpha . alpha, sum c, alpha . target
+    if (wave == 0) {
+        double aa = 0.0, sc = 0.0, ay = 0.0;
+        for (int i = lane; i < n; i += 64) {
+            const double ai = al[i];
+            aa = fma(ai, ai, aa);
+            sc += SBLK(i >> 4, i >> 4)[(i & 15) * (SB + 1)];
+            ay = fma(ai, yv[i], ay);
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            aa += __shfl_xor(aa, o, 64);
+            sc += __shfl_xor(sc, o, 64);
+            ay += __shfl_xor(ay, o, 64);
+        }
+        if (lane == 0) {
+            const double tr = aa - sc;
+            g_sn[0] = (ay - (double)n - nd.noise * tr) / (2.0 * nd.scale);
+            g_sn[1] = 0.5 * tr;
+        }
+    }
+    __syncthreads();
+
+    // ---- P = (alpha alpha^T - A^-1) o K replaces A^-1
+    {
+        int bi = 0, bj = 0;
+        for (int t = 0; t < wave; ++t) { if (++bj > bi) { ++bi; bj = 0; } }
+        for (int blk = wave; blk < NBLK; blk += SM_WAVES) {
+            double* B = P + (blk << 8);
+            int gi[4], gj[4];
+            double lux[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int w = lane + 64 * u;
+                gi[u] = SB * bi + (w & 15);
+                gj[u] = SB * bj + (w >> 4);
+            }
+            for (int f = 0; f < nF; ++f) {
+                const double* ff = fs + f * NP;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const double d = ff[gi[u]] - ff[gj[u]];
+                    lux[u] = fma(d, d, lux[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const double e = nd.scale * gp_exp_neg(-lux[u]);
+                const double q = al[gi[u]] * al[gj[u]] - B[lane + 64 * u];
+                B[lane + 64 * u] = (gi[u] < n && gj[u] < n) ? q * e : 0.0;
+            }
+            for (int t = 0; t < SM_WAVES; ++t) { if (++bj > bi) { ++bi; bj = 0; } }
+        }
+    }
+    __syncthreads();
+
+    // ---- the sums over the pairs: row r = 16 bi + li, columns 16 bj + lg + 4 v; four features per pass over P (a feature beyond
+    // the last repeats the last one and is not stored), every feature's sums in the order (bj, v)
+    for (int bi = wave; bi < NB; bi += SM_WAVES) {
+        const int r = SB * bi + li;
+        for (int f0 = 0; f0 < nF; f0 += 4) {
+            const double* xf[4];
+            double xr[4], rs[4], sq[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                xf[u] = rw + min(f0 + u, nF - 1) * NP;
+                xr[u] = xf[u][r];
+                rs[u] = sq[u] = 0.0;
+            }
+            for (int bj = 0; bj < NB; ++bj) {
+                const double* B = bj <= bi ? SBLK(bi, bj) + li : SBLK(bj, bi) + li * SB;
+                const int step = bj <= bi ? SB : 1;
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int cl = lg + 4 * v;
+                    const double p = B[cl * step];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const double d = xr[u] - xf[u][SB * bj + cl];
+                        const double pd = p * d;
+                        rs[u] += pd;
+                        sq[u] = fma(pd, d, sq[u]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int f = f0 + u;
+                if (f < nF) {                    // scalar
+                    double rsum = rs[u], ssum = sq[u];
+                    rsum += __shfl_xor(rsum, 16, 64);
+                    rsum += __shfl_xor(rsum, 32, 64);
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) ssum += __shfl_xor(ssum, o, 64);
+                    const double l = lsl[f];
+                    if (lg == 0 && r < n) g_dF[(long long)f * n + r] = -2.0 * rsum / (l * l);
+                    if (lane == 0) lsp[f * NB + bi] = ssum;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int f = tid; f < nF; f += SM_THREADS) {
+        double sum = 0.0;
+        for (int bi = 0; bi < NB; ++bi) sum += lsp[f * NB + bi];
+        const double l = lsl[f];
+        g_dls[f] = sum / (l * l * l);
     }
 }
 
@@ -669,6 +971,19 @@ void launch_mid_gp(const SmallArgs& a, int count, int nF_max, hipStream_t st) {
 size_t small_gp_lds_bytes(int n, int nF) {
     const int NB = (n + SB - 1) / SB, NP = NB * SB;
     return ((size_t)(NB * (NB + 1) / 2) * 256 + 3 * (size_t)NP + SM_WAVES * SB + (size_t)nF * NP) * 8;
+}
+
+// the gradient kernel's image: the score's, then alpha, the raw features, a lengthscale partial per block row, the lengthscales
+size_t small_grad_lds_bytes(int n, int nF) {
+    const int NB = (n + SB - 1) / SB, NP = NB * SB;
+    return small_gp_lds_bytes(n, nF) + ((size_t)NP + (size_t)nF * NP + (size_t)nF * NB + (size_t)nF) * 8;
+}
+
+void launch_small_grad(const SmallArgs& a, double* gout, int count, int nF_max, hipStream_t st) {
+    const size_t bytes = small_grad_lds_bytes(a.n, nF_max);
+    static DeviceOnce once;
+    lds_opt_in(once, (const void*)small_gp_grad_kernel, 160 * 1024);
+    hipLaunchKernelGGL(small_gp_grad_kernel, dim3(count), dim3(SM_THREADS), bytes, st, a, gout);
 }
 
 void launch_small_gp(const SmallArgs& a, int count, int nF_max, hipStream_t st) {

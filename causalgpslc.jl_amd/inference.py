@@ -371,6 +371,54 @@ class _RealTChain:
         out = api.nodesLogpdf(allnodes, self.ctx, fail_value=-math.inf)
         return [self._xty_split(out[i * per:(i + 1) * per], nx, has_t) for i in range(len(Us))]
 
+    def grad_xty(self, v=None, U=None):
+        """The gradient of `score_xty`'s sum s_x.sum() + s_t + s_y in ONE fused call (gpslc_nodes_logpdf_grad): what a
+        gradient-based move on U or on the hyper-parameters of these nodes needs.  Returns a dict:
+          ``dUm`` (n, nU)  with respect to the model-side matrix `_umodel(U)`: the X nodes (all their columns), the T node and
+                           the Y node (their first nU columns) added up;
+          ``dU``           the same carried back through `toMatrixModel`'s permutation: one (n,) vector per traced vector;
+          the hyper-parameters under the chain's own names and shapes — ``uxLS`` (nU, nX) as `v["uxLS"][u][k]`, ``xScale``,
+          ``xNoise`` (nX,), ``utLS``, ``xtLS``, ``tScale``, ``tNoise``, ``uyLS``, ``xyLS``, ``tyLS``, ``yScale``, ``yNoise`` —
+          with respect to the parameters themselves; ``dlogitT`` (n,) on a binary chain.
+        A node that is absent (no T node when nothing feeds it, no X nodes without U or covariates) contributes no entry.
+        No move uses it yet."""
+        v = v or self.v
+        nodes, nx, has_t = self._xty_nodes(v, U)
+        g = api.nodesLogpdfGrad(nodes, self.ctx, want=("dF", "dls", "dscale", "dnoise", "dtarget"))
+        n, nU, nX = self.n, self.nU, self.nX
+        out = {}
+        dUm = np.zeros((n, nU), order="F")
+        if nx:
+            for k in range(nx):
+                dUm += g[k]["dF"]
+            # row k of `_uxls_model` feeds X node k; element (k, c) of that (nX, nU) matrix is uxLS[u][i] with u + nU i = k + nX c
+            dls_model = np.vstack([g[k]["dls"] for k in range(nx)])
+            out["uxLS"] = dls_model.reshape(-1, order="F").reshape(nU, nX, order="F")
+            out["xScale"] = np.array([g[k]["dscale"] for k in range(nx)])
+            out["xNoise"] = np.array([g[k]["dnoise"] for k in range(nx)])
+        if has_t:
+            gt = g[nx]
+            if nU:
+                dUm += gt["dF"][:, :nU]
+                out["utLS"] = np.array(gt["dls"][:nU])
+            if nX:
+                out["xtLS"] = np.array(gt["dls"][nU:nU + nX])
+            out["tScale"], out["tNoise"] = gt["dscale"], gt["dnoise"]
+            if self.binary:
+                out["dlogitT"] = np.array(gt["dtarget"])
+        gy = g[-1]
+        if nU:
+            dUm += gy["dF"][:, :nU]
+            out["uyLS"] = np.array(gy["dls"][:nU])
+            out["dUm"] = dUm
+            # toMatrixModel: element p = u + nU i of the flattened model matrix is traced vector u, individual i
+            back = dUm.reshape(-1, order="F").reshape(nU, n, order="F")
+            out["dU"] = [np.array(back[u]) for u in range(nU)]
+        if nX:
+            out["xyLS"] = np.array(gy["dls"][nU:nU + nX])
+        out["tyLS"], out["yScale"], out["yNoise"] = float(gy["dls"][-1]), gy["dscale"], gy["dnoise"]
+        return out
+
     # which node an address touches
     TOUCH = {"uNoise": "u", "tNoise": "t", "yNoise": "y", "tyLS": "y", "tScale": "t", "yScale": "y",
              "utLS": "t", "uyLS": "y", "uxLS": "x", "xNoise": "x", "xScale": "x", "xtLS": "t", "xyLS": "y"}

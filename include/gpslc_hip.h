@@ -242,6 +242,39 @@ typedef struct gpslc_node {
 } gpslc_node;
 int gpslc_nodes_logpdf(gpslc_ctx* ctx, int32_t count, const gpslc_node* nodes, double* logpdf /* count */);
 
+/* The fused whole-model gradient: the gradient of every score of gpslc_nodes_logpdf in one call — what a gradient-based move on
+ * a latent confounder (HMC, MALA, MAP) needs, since U feeds every `:X => k => :X` node, `:T` / `:logitT` and `:Y`.  Node i is
+ * that of gpslc_nodes_logpdf: its score is log N(target_i; 0, A_i), A_i = K_i + noise_i I, K_i = scale_i exp(-sum_f ((F_rf -
+ * F_cf) / ls_f)^2).  With alpha = A^-1 target, Q = alpha alpha^T - A^-1, P = Q o K, c = diag(A^-1), D_rcf = F_rf - F_cf:
+ *   dF_rf    = -(2 / ls_f^2) sum_c P_rc D_rcf                 EVERY feature column of the node
+ *   dls_f    =  (1 / ls_f^3) sum_rc P_rc D_rcf^2
+ *   dnoise   =  (alpha . alpha - sum_r c_r) / 2
+ *   dscale   =  (alpha . target - n - noise (alpha . alpha - sum_r c_r)) / (2 scale)
+ *   dtarget  = -alpha
+ * with respect to the parameters themselves, not their logarithms.  Layouts (host; flat, no struct): dF is the nodes' n x nF_i
+ * column-major blocks concatenated in node order (node i starts at n sum_{k<i} nF_k), dls the same with nF_i values per node;
+ * dscale, dnoise and logpdf_or_null hold `count` values; dtarget is n x count.  A node with nF = 0 owns no slot of dF / dls.
+ * Any of arguments 4-9 may be NULL; 4-8 all NULL returns -4; count < 0: -2; nodes NULL or a malformed node: -3; count = 0 is
+ * an empty call.  A GPSLC_FLAG_FP32_KERNEL context: GPSLC_ERR_UNSUPPORTED.  Needs no gpslc_set_data.  A node whose factorisation
+ * breaks down gets NaN in all its gradient outputs; the call returns the first failing pivot, gpslc_last_info has count entries.
+ * Paths: while every node fits one CU's LDS with the gradient's extra image (the score's packed blocks, the scaled AND the raw
+ * features, alpha) and count <= 4096, ONE launch, one workgroup per node: the score kernel's own Gram build and Cholesky, then
+ * L^-1, A^-1 = L^-T L^-1 and P in place in LDS on the f64 matrix cores and the sums over the pairs, D from the raw features.
+ * Largest n of that path per widest node of the call:
+ *     nF <= 7: 176      nF <= 17: 160      nF <= 27: 144      nF <= 32: 128
+ * Otherwise the whole call takes the batched tiled path: gpslc_y_logpdf_grad's pair pass without a treatment column over the
+ * nodes padded to the widest one; the padding columns' gradients are dropped.  (The left-looking kernel that scores
+ * 176 < n <= 640 has no gradient mode.)
+ * Guarantees: the outputs are bit-reproducible from run to run (no floating-point atomics, fixed summation orders); on a given
+ * path a node's outputs do not depend on which other nodes share the call, on the widest of them, or on the node's position;
+ * asking for a subset of the outputs gives the same bits for that subset; sum_r dF[r, f] vanishes to rounding; logpdf_or_null is
+ * bit-identical to gpslc_nodes_logpdf for the same nodes whenever both calls take the same path (they differ where the score
+ * fits its single launch and the gradient's larger image does not).  No _dev variant; dense-covariance (`:U` prior) nodes have
+ * no node kind here: their gradient -Sigma^-1 x / covscale is one solve with gpslc_mvn_logpdf's cached factor.   */
+int gpslc_nodes_logpdf_grad(gpslc_ctx* ctx, int32_t count, const gpslc_node* nodes, double* dF /* n x sum nF */,
+                            double* dls /* sum nF */, double* dscale /* count */, double* dnoise /* count */,
+                            double* dtarget /* n x count */, double* logpdf_or_null /* count */);
+
 /* Draws from the nodes' priors: draws[:, i] = chol(K_i) * target_i with K_i the node's covariance as above and
  * target_i a vector of standard normals supplied by the caller (the host keeps its random-number stream) — what Gen's
  * `mvnormal(zeros(n), cov)` does inside `elliptical_slice(trace, addr, mu, cov)` (src/inference.jl:48-54, 92-98, 232,

@@ -265,6 +265,25 @@ function nodes_logpdf(c::Ctx, nodes::Vector{GPSLCNode})
     out
 end
 
+"""The fused whole-model gradient (gpslc_nodes_logpdf_grad): `(dF, dls, dscale, dnoise, dtarget, logpdf)` for the nodes of
+`nodes_logpdf` — dF a vector of n x nF_i matrices and dls a vector of nF_i-vectors, one per node (views into the library's flat
+blocks), dscale, dnoise and logpdf of length(nodes), dtarget n x length(nodes) — with respect to the parameters themselves.  The
+arrays the nodes point into must be kept alive by the caller, as for `nodes_logpdf`.  A failed factorisation throws PosDefException."""
+function nodes_logpdf_grad(c::Ctx, nodes::Vector{GPSLCNode})
+    cnt = length(nodes)
+    nFs = Int[nd.nF for nd in nodes]
+    dF = Vector{Float64}(undef, c.n * sum(nFs; init=0))
+    dls = Vector{Float64}(undef, sum(nFs; init=0))
+    dscale, dnoise, lp = (Vector{Float64}(undef, cnt) for _ in 1:3)
+    dtarget = Matrix{Float64}(undef, c.n, cnt)
+    GC.@preserve nodes dF dls dscale dnoise dtarget lp check(c, ccall((:gpslc_nodes_logpdf_grad, lib), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{GPSLCNode}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, cnt, pointer(nodes), pointer(dF), pointer(dls), pointer(dscale), pointer(dnoise), pointer(dtarget), pointer(lp)))
+    offs = cumsum([0; nFs])
+    dFs = [reshape(view(dF, c.n * offs[i] + 1:c.n * offs[i + 1]), c.n, nFs[i]) for i in 1:cnt]
+    dFs, [view(dls, offs[i] + 1:offs[i + 1]) for i in 1:cnt], dscale, dnoise, dtarget, lp
+end
+
 """draws[:, i] = chol(K_i) * target_i (target = the caller's standard normals): Gen's mvnormal(zeros(n), cov) inside
 elliptical_slice(trace, :logitT, zeros(n), logitTCov) (src/inference.jl:225-232, 286-289, 343-348)."""
 function nodes_draw(c::Ctx, nodes::Vector{GPSLCNode}; want_logpdf::Bool=false)
