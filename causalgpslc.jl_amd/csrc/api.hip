@@ -4,6 +4,7 @@
 #include "../../include/gpslc_hip.h"
 #include "gpslc_internal.h"
 #include "batch_plan.h"
+#include "sm_layout.h"
 #include "philox.h"
 
 #include <algorithm>
@@ -1291,8 +1292,6 @@ double* up(gpslc_ctx* c, const double* host, size_t count) {
 }
 
 // ---- single-launch small-n node scores ----------------------------------------------------------------------------
-constexpr size_t kLdsBytes = 160 * 1024;
-
 struct HostNode {            // host view of one node (gpslc_node with plain pointers)
     int nF;
     const double* F[2];      // up to two column groups + one extra column are concatenated into the feature block:
@@ -1348,8 +1347,8 @@ void pin_reserve(gpslc_ctx* c, size_t bytes) {
 // for 100+ us: worth it up to a few hundred nodes per call, beyond that the batched tiled path wins.
 bool fast_path_ok(const gpslc_ctx* c, int nF_max, int64_t count) {
     if (c->flags & GPSLC_FLAG_FP32_KERNEL) return false;
-    if (small_gp_lds_bytes((int)c->n, nF_max) <= kLdsBytes) return count <= 4096;
-    return mid_gp_fits((int)c->n) && count <= 512;
+    if (small_gp_lds_bytes((int)c->n, nF_max) <= kLdsCapBytes) return count <= 4096;
+    return MidLayout::fits((int)c->n) && count <= 512;
 }
 
 // Device -> host hand-over of a LARGE result (draw tensors, MeanITE of a level sweep: GB).  A plain hipMemcpy into pageable
@@ -1442,19 +1441,15 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
                        const NodeGradOut* grad = nullptr) {
     ensure_streams(c);
     const size_t n = (size_t)c->n;
+    auto stage = [&](int i) { return NodeStage(n, (size_t)nodes[i].nF, grad != nullptr); };     // sm_layout.h
     size_t doubles = 0, gdoubles = 0;
     int nF_max = 0;
     for (int i = 0; i < count; ++i) {
-        doubles += n * nodes[i].nF + n;
-        if (grad) {      // raw features and lengthscales in, [dF | dls | dscale dnoise | dtarget] out
-            doubles += n * nodes[i].nF + nodes[i].nF;
-            gdoubles += n * nodes[i].nF + nodes[i].nF + 2 + n;
-        }
+        doubles += stage(i).in_total; gdoubles += stage(i).out_total;
         nF_max = std::max(nF_max, nodes[i].nF);
     }
     const size_t off_out = ((size_t)count * sizeof(SmallNode) + 63) & ~size_t(63);
-    // 4 results + 8 stamp words per node (+ 8 x 8 per-wave words of node 0 for the mid-size kernel: measurement build)
-    const size_t off_data = off_out + ((size_t)count * 12 + 64) * sizeof(double);
+    const size_t off_data = off_out + NodeStage::header((size_t)count) * sizeof(double);
     const size_t off_draw = off_data + doubles * sizeof(double);          // [count][n] draws (pinned, written by the kernel)
     const size_t off_grad = off_draw + (draw_out ? (size_t)count * n * sizeof(double) : 0);     // the gradient launch's result block
     pin_reserve(c, off_grad + gdoubles * sizeof(double));
@@ -1465,47 +1460,38 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
     double* hout = reinterpret_cast<double*>(c->pin + off_out);
     double* hd = reinterpret_cast<double*>(c->pin + off_data);
     double* dd = reinterpret_cast<double*>(dev + off_data);
-    size_t o = 0;
-    // features are staged already divided by their lengthscale: x * (1 / l), the arithmetic of the general path
-    auto put_scaled = [&](const double* col, double l) {
-        const double il = 1.0 / l;
-        for (size_t r = 0; r < n; ++r) hd[o + r] = col[r] * il;
-        o += n;
-    };
-    size_t go = 0;
+    size_t o = 0, go = 0;        // where node i's input and results start
     for (int i = 0; i < count; ++i) {
         const HostNode& h = nodes[i];
+        const NodeStage S = stage(i);
         SmallNode& sn = hn[i];
         sn.nF = h.nF; sn.gofs = (int)go; sn.scale = h.scale; sn.noise = h.noise;
         sn.cov = h.dev_cov; sn.covscale = h.covscale;
         sn.Fs = dd + o;
+        sn.target = dd + o + S.target;
+        // a feature column goes in twice: divided by its lengthscale, x * (1 / l), the arithmetic of the general path, and
+        // (gradient) as it is with the lengthscale, because D comes from the raw features
+        size_t f = 0;
+        auto put = [&](const double* col, double l) {
+            const double il = 1.0 / l;
+            for (size_t r = 0; r < n; ++r) hd[o + f * n + r] = col[r] * il;
+            if (grad) { memcpy(hd + o + S.raw + f * n, col, n * sizeof(double)); hd[o + S.ls + f] = l; }
+            ++f;
+        };
         for (int g = 0; g < 2; ++g)
-            for (int f = 0; f < h.nFpart[g]; ++f) put_scaled(h.F[g] + (size_t)f * n, h.ls[g][f]);
-        if (h.col) put_scaled(h.col, h.ls_col);
-        sn.target = dd + o;
-        memcpy(hd + o, h.target, n * sizeof(double));
-        o += n;
-        if (grad) {      // D comes from the raw features: they and the lengthscales follow the target
-            for (int g = 0; g < 2; ++g) {
-                if (h.nFpart[g]) memcpy(hd + o, h.F[g], n * (size_t)h.nFpart[g] * sizeof(double));
-                o += n * (size_t)h.nFpart[g];
-            }
-            if (h.col) { memcpy(hd + o, h.col, n * sizeof(double)); o += n; }
-            for (int g = 0; g < 2; ++g)
-                for (int f = 0; f < h.nFpart[g]; ++f) hd[o++] = h.ls[g][f];
-            if (h.col) hd[o++] = h.ls_col;
-            go += n * (size_t)h.nF + h.nF + 2 + n;
-        }
+            for (int k = 0; k < h.nFpart[g]; ++k) put(h.F[g] + (size_t)k * n, h.ls[g][k]);
+        if (h.col) put(h.col, h.ls_col);
+        memcpy(hd + o + S.target, h.target, n * sizeof(double));
+        o += S.in_total; go += S.out_total;
     }
     SmallArgs a{};
     a.nodes = reinterpret_cast<const SmallNode*>(dev);
     for (int i = 0; i < std::min(count, SMALL_INLINE_NODES); ++i) a.inl[i] = hn[i];
     a.n = (int)n; a.NB = (int)((n + 15) / 16);
     a.out = reinterpret_cast<double*>(dev + off_out);
-    a.stamps = nullptr;
     a.draw = draw_out ? reinterpret_cast<double*>(dev + off_draw) : nullptr;
-    const bool in_lds = grad || small_gp_lds_bytes((int)n, nF_max) <= kLdsBytes;
-    if (grad && small_grad_lds_bytes((int)n, nF_max) > kLdsBytes) throw std::runtime_error("gradient launch beyond its LDS image");
+    const bool in_lds = grad || small_gp_lds_bytes((int)n, nF_max) <= kLdsCapBytes;
+    if (grad && small_grad_lds_bytes((int)n, nF_max) > kLdsCapBytes) throw std::runtime_error("gradient launch beyond its LDS image");
     if (!in_lds) {       // mid-size kernel: per-node scratch for the finished block columns and the scaled features
         const size_t per = (mid_gp_scratch_doubles((int)n, nF_max) + 31) & ~size_t(31);
         arena_reserve(c, c->scratch, per * (size_t)count * sizeof(double) + 256);
@@ -1515,7 +1501,7 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
     }
 #ifdef GPSLC_DIAG
     static const int want_stamps = diag_env("GPSLC_SMALL_STAMPS", 0);
-    if (want_stamps) a.stamps = a.out + 4 * (size_t)count;
+    if (want_stamps) a.stamps = a.out + NodeStage::kResult * (size_t)count;
 #endif
     hipStream_t st = c->slots[0].st;
     if (grad) launch_small_grad(a, reinterpret_cast<double*>(dev + off_grad), count, nF_max, st);
@@ -1526,28 +1512,29 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
 #ifdef GPSLC_DIAG
     if (want_stamps && in_lds) {
         static int printed = 0;
-        const double* sp = hout + 4 * (size_t)count;
+        const double* sp = hout + NodeStage::kResult * (size_t)count;
         if (printed++ < want_stamps)
             fprintf(stderr, "small_gp stamps (shader clocks): inputs %.0f gram %.0f factor+panel %.0f (wave 0 inside the pivot chains: %.0f) update %.0f total %.0f\n",
                     sp[0], sp[1], sp[2], sp[4], sp[3], sp[5]);
     }
     if (want_stamps && !in_lds) {      // node 0, per wave: cumulative shader clocks of the phases over all block columns
         static int printed = 0;
-        const double* sp = hout + 12 * (size_t)count;
+        const double* sp = hout + (NodeStage::kResult + NodeStage::kStamps) * (size_t)count;
         if (printed++ < want_stamps)
-            for (int w = 0; w < 8; ++w)
+            for (int w = 0; w < kSmWaves; ++w, sp += NodeStage::kWaveStamps / kSmWaves)
                 fprintf(stderr, "mid_gp wave %d: gram %.0f k-loop %.0f to-LDS %.0f wait %.0f factor+store %.0f wait %.0f\n", w,
-                        sp[8 * w], sp[8 * w + 1], sp[8 * w + 2], sp[8 * w + 3], sp[8 * w + 4], sp[8 * w + 5]);
+                        sp[0], sp[1], sp[2], sp[3], sp[4], sp[5]);
     }
 #endif
     if (draw_out) memcpy(draw_out, c->pin + off_draw, (size_t)count * n * sizeof(double));
     int first = 0;
     c->last_info.resize((size_t)count);
     for (int i = 0; i < count; ++i) {
-        const int info = (int)hout[4 * i + 2];
+        const double* res = hout + NodeStage::kResult * (size_t)i;        // logdet, quad, info
+        const int info = (int)res[2];
         c->last_info[i] = info;
         if (info != 0 && first == 0) first = info;
-        logpdf[i] = gauss_logpdf(n, hout[4 * i], hout[4 * i + 1]);
+        logpdf[i] = gauss_logpdf(n, res[0], res[1]);
     }
     if (grad) {
         const double* r = reinterpret_cast<const double*>(c->pin + off_grad);
@@ -1558,14 +1545,15 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
             else memcpy(dst, src, cnt * sizeof(double));
         };
         for (int i = 0; i < count; ++i) {
+            const NodeStage S = stage(i);
             const size_t nF = (size_t)nodes[i].nF;
             const bool bad = c->last_info[i] != 0;
             deliver(grad->dF ? grad->dF + fo : nullptr, r, n * nF, bad);
-            deliver(grad->dls ? grad->dls + lo : nullptr, r + n * nF, nF, bad);
-            deliver(grad->dscale ? grad->dscale + i : nullptr, r + n * nF + nF, 1, bad);
-            deliver(grad->dnoise ? grad->dnoise + i : nullptr, r + n * nF + nF + 1, 1, bad);
-            deliver(grad->dtarget ? grad->dtarget + (size_t)i * n : nullptr, r + n * nF + nF + 2, n, bad);
-            fo += n * nF; lo += nF; r += n * nF + nF + 2 + n;
+            deliver(grad->dls ? grad->dls + lo : nullptr, r + S.dls, nF, bad);
+            deliver(grad->dscale ? grad->dscale + i : nullptr, r + S.dscale, 1, bad);
+            deliver(grad->dnoise ? grad->dnoise + i : nullptr, r + S.dnoise, 1, bad);
+            deliver(grad->dtarget ? grad->dtarget + (size_t)i * n : nullptr, r + S.dtarget, n, bad);
+            fo += n * nF; lo += nF; r += S.out_total;
         }
     }
     return first;
@@ -2726,7 +2714,7 @@ int gpslc_nodes_logpdf_grad(gpslc_ctx* c, int32_t count, const gpslc_node* nodes
         std::vector<double> lp;
         double* logpdf = logpdf_or_null;
         if (!logpdf) { lp.resize((size_t)count); logpdf = lp.data(); }
-        if (small_grad_lds_bytes((int)c->n, nF_max) > kLdsBytes || count > 4096)
+        if (small_grad_lds_bytes((int)c->n, nF_max) > kLdsCapBytes || count > 4096)
             return nodes_general(c, count, nodes, nF_max, logpdf, nullptr, &g);
         std::vector<HostNode> hn;
         hn.reserve((size_t)count);

@@ -524,8 +524,6 @@ size_t small_grad_lds_bytes(int n, int nF);
 void launch_small_grad(const SmallArgs& a, double* gout, int count, int nF_max, hipStream_t st);
 // left-looking variant for 176 < n <= 640: only the current block column in LDS, finished columns in an L2-resident scratch
 size_t mid_gp_scratch_doubles(int n, int nF);
-size_t mid_gp_lds_bytes(int n, int nF);
-bool mid_gp_fits(int n);
 void launch_mid_gp(const SmallArgs& a, int count, int nF_max, hipStream_t st);
 
 // summarizeEstimates (src/driver.jl:129-149): per-row mean and two type-7 quantiles of an n x m sample matrix

@@ -13,6 +13,7 @@
 // its own tile row.  The factorisation, V, z and the outputs are plain loops in ascending index.  Nothing depends on the label
 // number, on the other groups, on the chunk, the stream or the schedule that produced the factor.
 #include "gpslc_internal.h"
+#include "sm_blocks.h"           // sm_tri_block
 
 #define LGO_THREADS 256
 #define LGO_NE 8        // slab elements per thread at most: KC * mp <= 256 * LGO_NE
@@ -97,8 +98,8 @@ __global__ __launch_bounds__(LGO_THREADS) void lgo_group_kernel(LgoArgs a) {
         d4 acc[LGO_NQ];
 #pragma unroll
         for (int q = 0; q < LGO_NQ; ++q) {
-            int p = wave + 4 * q, bi = 0;
-            while (p > bi) { p -= bi + 1; ++bi; }       // block (bi, bj = p)
+            int bi, p;
+            sm_tri_block(wave + 4 * q, bi, p);          // block (bi, bj = p)
             aoff[q] = lg * LDM + 16 * bi + li;
             boff[q] = lg * LDM + 16 * p + li;
             acc[q] = (d4){0.0, 0.0, 0.0, 0.0};
@@ -122,8 +123,8 @@ __global__ __launch_bounds__(LGO_THREADS) void lgo_group_kernel(LgoArgs a) {
 #pragma unroll
         for (int q = 0; q < LGO_NQ; ++q) {
             if (q < nq) {
-                int p = wave + 4 * q, bi = 0;
-                while (p > bi) { p -= bi + 1; ++bi; }
+                int bi, p;
+                sm_tri_block(wave + 4 * q, bi, p);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) Cm[16 * bi + lg + 4 * u + (16 * p + li) * LD] = acc[q][u];
             }

@@ -26,32 +26,24 @@
 //     itself is only needed for the diagonal entry and is finished off the chain);
 //   * inputs are read straight from the pinned host staging buffer (a few KB, coalesced, once) and the three result
 //     words are written back to it: a score costs one kernel launch and one stream synchronisation.
-#include "gpslc_internal.h"
-#include "gp_math.h"
-
 #include "sm_blocks.h"
 
-// The whole score of one node on the LDS image P.  GRAD: the gradient kernel's instantiation — the same operations in the same
-// order, and the factor's diagonal blocks are kept as draw mode keeps them.
+// The whole score of one node on the LDS image P, laid out by L (sm_layout.h).  GRAD: the gradient kernel's instantiation — the
+// same operations in the same order, and the factor's diagonal blocks are kept as draw mode keeps them.
 template <bool GRAD>
-__device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNode& nd, double* P) {
+__device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNode& nd, double* P, const SmallLayout& L) {
     const unsigned long long tstart = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
-    const int n = a.n, NB = a.NB, NP = NB * SB;
-    const int NBLK = NB * (NB + 1) / 2;
-    double* yv = P + NBLK * 256;      // right-hand side, updated in place block by block
-    double* zv = yv + NP;             // z = L^-1 target
-    double* ldv = zv + NP;            // diag(L), for the log-determinant
-    double* bcl = ldv + NP;           // [8 waves][16]: multiplier broadcast lines of the pivot chains (sm_factor_rows_lds)
-    double* fs = bcl + SM_WAVES * SB; // scaled features, fs[f*NP + i] = F[i, f] * (1 / ls[f]) (scaled by the host)
+    const int n = a.n, NB = L.NB, NP = L.NP, NBLK = NB * (NB + 1) / 2;
+    double* yv = P + L.yv;            // right-hand side, updated in place block by block
+    double* zv = P + L.zv;            // z = L^-1 target
+    double* ldv = P + L.ldv;          // diag(L), for the log-determinant
+    double* bcl = P + L.bcl;          // [8 waves][16]: multiplier broadcast lines of the pivot chains (sm_factor_rows_lds)
+    double* fs = P + L.fs;            // scaled features, fs[f*NP + i] = F[i, f] * (1 / ls[f]) (scaled by the host)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // scalar: branches on it are scalar branches
     const int li = lane & 15;
 
-    for (int idx = tid; idx < nd.nF * NP; idx += SM_THREADS) {
-        const int f = idx / NP, i = idx - f * NP;
-        fs[idx] = (i < n) ? nd.Fs[(long long)f * n + i] : 0.0;
-    }
-    for (int i = tid; i < NP; i += SM_THREADS) yv[i] = (i < n) ? nd.target[i] : 0.0;
+    sm_stage_node(nd, n, NP, tid, fs, yv);
     __syncthreads();
     const unsigned long long t0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
 
@@ -59,11 +51,11 @@ __device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNo
     // independent entries per lane, the feature loop outermost, so that eight distance accumulations and then eight exp
     // chains interleave (a wave's dependent chains would otherwise run back to back: one or two waves per SIMD here)
     {
-        int bi = 0, bj = 0;                              // block `wave` of the row-major lower-triangle enumeration
-        for (int t = 0; t < wave; ++t) { if (++bj > bi) { ++bi; bj = 0; } }
+        int bi, bj;                                      // block `wave` of the row-major lower-triangle enumeration
+        sm_tri_block(wave, bi, bj);
         for (int blk = wave; blk < NBLK; blk += 2 * SM_WAVES) {
             int bi2 = bi, bj2 = bj;                      // the second block of this iteration: blk + SM_WAVES
-            for (int t = 0; t < SM_WAVES; ++t) { if (++bj2 > bi2) { ++bi2; bj2 = 0; } }
+            sm_tri_next(bi2, bj2, SM_WAVES);
             const bool two = blk + SM_WAVES < NBLK;
             int gi[8], gj[8];
 #pragma unroll
@@ -73,28 +65,14 @@ __device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNo
                 gj[u] = SB * (u < 4 ? bj : bj2) + (w >> 4);
             }
             double v[8];
-            if (nd.cov) {          // dense covariance node (uCov = SigmaU * uNoise, src/model_likelihood.jl:4-10)
+            if (nd.cov) {          // dense covariance node
 #pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    v[u] = (gi[u] < n && gj[u] < n && (u < 4 || two)) ? nd.covscale * nd.cov[(long long)gj[u] * n + gi[u]]
-                                                                       : (gi[u] == gj[u] ? 1.0 : 0.0);
+                for (int u = 0; u < 8; ++u) v[u] = sm_dense_entry(nd, gi[u], gj[u], n, u < 4 || two);
             } else {
                 double lux[8];
+                sm_dist2<8>(fs, NP, nd.nF, gi, gj, lux);
 #pragma unroll
-                for (int u = 0; u < 8; ++u) lux[u] = 0.0;
-                for (int f = 0; f < nd.nF; ++f) {
-                    const double* ff = fs + f * NP;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const double d = ff[gi[u]] - ff[gj[u]];      // padded instances carry zeros: harmless, masked below
-                        lux[u] = fma(d, d, lux[u]);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const double e = nd.scale * gp_exp_neg(-lux[u]);
-                    v[u] = (gi[u] < n && gj[u] < n) ? (gi[u] == gj[u] ? e + nd.noise : e) : (gi[u] == gj[u] ? 1.0 : 0.0);
-                }
+                for (int u = 0; u < 8; ++u) v[u] = sm_cov_entry(nd, lux[u], gi[u], gj[u], n);
             }
             double* B = P + (blk << 8);
 #pragma unroll
@@ -104,7 +82,7 @@ __device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNo
 #pragma unroll
                 for (int u = 0; u < 4; ++u) B2[lane + 64 * u] = v[4 + u];
             }
-            for (int t = 0; t < 2 * SM_WAVES; ++t) { if (++bj > bi) { ++bi; bj = 0; } }
+            sm_tri_next(bi, bj, 2 * SM_WAVES);
         }
     }
     int bad = 0;
@@ -120,20 +98,16 @@ __device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNo
         if (wave * 48 <= rows) {                         // scalar: this wave has rows to carry
             const bool is_diag = lane < SB;
             const int q = wave * 48 + (lane - SB);       // this lane's row below the block (lanes >= 16)
-            double r[SB];
+            double r[SB] = {};
             double* dst = nullptr;                       // where this lane's row lives (null: nothing to carry)
             if (is_diag) dst = SBLK(p, p) + li;
             else if (q < rows) { const int gr = SB * (p + 1) + q; dst = SBLK(gr >> 4, p) + (gr & 15); }
             const bool is_y = !is_diag && q == rows;
             if (dst) {
-#pragma unroll
-                for (int c = 0; c < SB; ++c) r[c] = dst[c * SB];
+                sm_row_load(r, dst);
             } else if (is_y) {
 #pragma unroll
                 for (int c = 0; c < SB; ++c) r[c] = yv[SB * p + c];
-            } else {
-#pragma unroll
-                for (int c = 0; c < SB; ++c) r[c] = 0.0;
             }
             double lcc;
             sm_factor_rows_lds(r, li, lane, SB * p, bad, lcc, bcl + wave * SB);
@@ -151,8 +125,7 @@ __device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNo
                     }
                 }
             } else if (dst) {
-#pragma unroll
-                for (int c = 0; c < SB; ++c) dst[c * SB] = r[c];
+                sm_row_store(dst, r);
             } else if (is_y) {
 #pragma unroll
                 for (int c = 0; c < SB; ++c) zv[SB * p + c] = r[c];
@@ -205,13 +178,13 @@ __device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNo
                 const int w = wave - u0, nw = SM_WAVES - u0;
                 const int m1 = m - 1, cnt = m1 * (m1 + 1) / 2;          // triangle over (ii, rem), 1 <= rem <= ii <= m - 1
                 for (int t = w; t < cnt; t += 2 * nw) {
-                    int ii = 0, rem = t;
-                    while (rem > ii) { rem -= ii + 1; ++ii; }
+                    int ii, rem;
+                    sm_tri_block(t, ii, rem);
                     const int bi = p + 2 + ii, bj = p + 2 + rem;
                     const int t2 = t + nw;
                     if (t2 < cnt) {
-                        int i2 = 0, rem2 = t2;
-                        while (rem2 > i2) { rem2 -= i2 + 1; ++i2; }
+                        int i2, rem2;
+                        sm_tri_block(t2, i2, rem2);
                         sm_update2(SBLK(bi, bj), SBLK(bi, p), SBLK(bj, p),
                                    SBLK(p + 2 + i2, p + 2 + rem2), SBLK(p + 2 + i2, p), SBLK(p + 2 + rem2, p), lane);
                     } else {
@@ -242,27 +215,11 @@ __device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNo
         }
     }
     if (wave == 0) {
-        double q = 0.0, ld = 0.0;
-        for (int i = lane; i < n; i += 64) {
-            q = fma(zv[i], zv[i], q);
-            ld += log(ldv[i]);
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            q += __shfl_xor(q, o, 64);
-            ld += __shfl_xor(ld, o, 64);
-        }
-        if (lane == 0) {
-            double* o = a.out + 4 * (long long)blockIdx.x;
-            o[0] = 2.0 * ld;
-            o[1] = q;
-            o[2] = (double)bad;
-            o[3] = 0.0;
-            if (a.stamps) {    // shader-clock ticks: inputs, Gram, factor+panel phases, update phases, -, total
-                double* sp = a.stamps + 8 * (long long)blockIdx.x;
-                sp[0] = (double)(t0 - tstart); sp[1] = (double)(t1 - t0); sp[2] = (double)t_fac; sp[3] = (double)t_upd;
-                sp[4] = (double)t_chain; sp[5] = (double)(__builtin_amdgcn_s_memtime() - tstart);
-            }
+        sm_write_score(a, lane, bad, ldv, [&](int i) { return zv[i]; });
+        if (lane == 0 && a.stamps) {    // shader-clock ticks: inputs, Gram, factor+panel phases, update phases, -, total
+            double* sp = a.stamps + NodeStage::kStamps * (long long)blockIdx.x;
+            sp[0] = (double)(t0 - tstart); sp[1] = (double)(t1 - t0); sp[2] = (double)t_fac; sp[3] = (double)t_upd;
+            sp[4] = (double)t_chain; sp[5] = (double)(__builtin_amdgcn_s_memtime() - tstart);
         }
     }
 }
@@ -270,7 +227,7 @@ __device__ __forceinline__ void small_gp_score(const SmallArgs& a, const SmallNo
 __global__ __launch_bounds__(SM_THREADS) void small_gp_logpdf_kernel(SmallArgs a) {
     extern __shared__ __attribute__((aligned(16))) double P[];
     const SmallNode nd = blockIdx.x < SMALL_INLINE_NODES ? a.inl[blockIdx.x] : a.nodes[blockIdx.x];
-    small_gp_score<false>(a, nd, P);
+    small_gp_score<false>(a, nd, P, SmallLayout(a.n, nd.nF, false));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -292,8 +249,8 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_logpdf_kernel(SmallArgs a
 //          j > i) with D from the raw features, which sit in LDS beside the scaled ones.  dF is a row sum inside the wave
 //          (four lane groups, xor 16 then 32); a lengthscale sum goes through one partial per block row, added in ascending
 //          block-row order.  No atomics; nothing depends on the other nodes of the launch.
-// Staging of a node (pinned): [scaled features n x nF][target n][raw features n x nF][ls nF]; results at gout + nd.gofs:
-// [dF n x nF][dls nF][dscale][dnoise][dtarget n].  A failed factorisation leaves garbage here: the host answers NaN from info.
+// A node's staging and its results at gout + nd.gofs are laid out by NodeStage (sm_layout.h).  A failed factorisation leaves
+// garbage there: the host answers NaN from info.
 // ---------------------------------------------------------------------------------------------------------------------
 // fragment of the TRANSPOSE of a packed block: element (k = 4kk + lane>>4, col = lane&15) of blk, i.e. row lane&15 of blk^T
 __device__ __forceinline__ double sm_frag_t(const double* blk, int kk, int lane) {
@@ -305,24 +262,22 @@ __device__ __forceinline__ double sm_frag_t(const double* blk, int kk, int lane)
 __global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, double* gout) {
     extern __shared__ __attribute__((aligned(16))) double P[];
     const SmallNode nd = blockIdx.x < SMALL_INLINE_NODES ? a.inl[blockIdx.x] : a.nodes[blockIdx.x];
-    small_gp_score<true>(a, nd, P);
+    small_gp_score<true>(a, nd, P, SmallLayout(a.n, nd.nF, true));
 
-    const int n = a.n, NB = a.NB, NP = NB * SB, nF = nd.nF;
-    const int NBLK = NB * (NB + 1) / 2;
-    double* yv = P + NBLK * 256;      // the score's layout
-    double* zv = yv + NP;
-    double* ldv = zv + NP;
-    double* fs = ldv + NP + SM_WAVES * SB;
-    double* al = fs + nF * NP;        // alpha
-    double* rw = al + NP;             // raw features [f][NP]
-    double* lsp = rw + nF * NP;       // [f][NB]: a block row's share of sum P D_f^2
-    double* lsl = lsp + nF * NB;      // the lengthscales: the staging buffer is host memory, a round trip per read
-    const double* raw = nd.target + n;
-    const double* lsv = raw + (long long)nF * n;
+    // the layouts again, not kept across the score: held in SGPRs over its body they cost SGPR spills into VGPRs (no scratch)
+    const int n = a.n, nF = nd.nF;
+    const SmallLayout L(n, nF, true);
+    const NodeStage S(n, nF, true);
+    const int NB = L.NB, NP = L.NP, NBLK = NB * (NB + 1) / 2;
+    double *yv = P + L.yv, *zv = P + L.zv, *ldv = P + L.ldv, *fs = P + L.fs;
+    double* al = P + L.al;            // alpha
+    double* rw = P + L.rw;            // raw features [f][NP]
+    double* lsp = P + L.lsp;          // [f][NB]: a block row's share of sum P D_f^2
+    double* lsl = P + L.lsl;          // the lengthscales: the staging buffer is host memory, a round trip per read
+    const double *raw = nd.Fs + S.raw, *lsv = nd.Fs + S.ls;
     double* g_dF = gout + nd.gofs;
-    double* g_dls = g_dF + (long long)nF * n;
-    double* g_sn = g_dls + nF;        // dscale, dnoise
-    double* g_dt = g_sn + 2;
+    double* g_dls = g_dF + S.dls;
+    double *g_sn = g_dF + S.dscale, *g_dt = g_dF + S.dtarget;      // g_sn: dscale, then dnoise
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
@@ -371,10 +326,6 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, 
     }
     __syncthreads();
 
-    auto store_block = [&](double* B, const d4& x, double sign) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) B[(lg + 4 * v) * SB + li] = sign * x[v];
-    };
     const d4 zero4 = {0.0, 0.0, 0.0, 0.0};
 
     // ---- block columns of W from right to left
@@ -385,7 +336,7 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, 
             d4 acc = zero4;                                          // both operands along the banks
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) acc = SM_MFMA_ADD(sm_frag(Lkj, kk, lane), sm_frag_t(Wjj, kk, lane), acc);
-            store_block(Lkj, acc, 1.0);
+            sm_acc_store(Lkj, acc, lane);
         }
         __syncthreads();
         d4 x[2] = {zero4, zero4};
@@ -404,7 +355,7 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, 
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int i = j + 1 + wave + SM_WAVES * u;
-            if (i < NB) store_block(SBLK(i, j), x[u], -1.0);
+            if (i < NB) sm_acc_store(SBLK(i, j), -x[u], lane);
         }
     }
     __syncthreads();
@@ -453,7 +404,7 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, 
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int j = wave + SM_WAVES * u;
-            if (j <= i) store_block(SBLK(i, j), x[u], 1.0);
+            if (j <= i) sm_acc_store(SBLK(i, j), x[u], lane);
         }
     }
     __syncthreads();
@@ -483,33 +434,25 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, 
 
     // ---- P = (alpha alpha^T - A^-1) o K replaces A^-1
     {
-        int bi = 0, bj = 0;
-        for (int t = 0; t < wave; ++t) { if (++bj > bi) { ++bi; bj = 0; } }
+        int bi, bj;
+        sm_tri_block(wave, bi, bj);
         for (int blk = wave; blk < NBLK; blk += SM_WAVES) {
             double* B = P + (blk << 8);
             int gi[4], gj[4];
-            double lux[4] = {0.0, 0.0, 0.0, 0.0};
+            double lux[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int w = lane + 64 * u;
                 gi[u] = SB * bi + (w & 15);
                 gj[u] = SB * bj + (w >> 4);
             }
-            for (int f = 0; f < nF; ++f) {
-                const double* ff = fs + f * NP;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double d = ff[gi[u]] - ff[gj[u]];
-                    lux[u] = fma(d, d, lux[u]);
-                }
-            }
+            sm_dist2<4>(fs, NP, nF, gi, gj, lux);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const double e = nd.scale * gp_exp_neg(-lux[u]);
                 const double q = al[gi[u]] * al[gj[u]] - B[lane + 64 * u];
-                B[lane + 64 * u] = (gi[u] < n && gj[u] < n) ? q * e : 0.0;
+                B[lane + 64 * u] = (gi[u] < n && gj[u] < n) ? q * sm_rbf(nd, lux[u]) : 0.0;
             }
-            for (int t = 0; t < SM_WAVES; ++t) { if (++bj > bi) { ++bi; bj = 0; } }
+            sm_tri_next(bi, bj, SM_WAVES);
         }
     }
     __syncthreads();
@@ -572,7 +515,7 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, 
 // The same score for the sizes between the LDS-resident kernel and the batched tiled path (176 < n <= 640: IHDP
 // n = 272): one workgroup per node, LEFT-looking over block columns.  Only the current block column lives in LDS; the
 // finished columns X(i, k) = L blocks sit in a per-node global scratch that stays in L2 (n = 272: 306 KiB).
-// Every wave owns up to MID_MAXI block rows of a column and keeps their 16 x 16 blocks in MFMA accumulators from the
+// Every wave owns up to kMidMaxRows block rows of a column and keeps their 16 x 16 blocks in MFMA accumulators from the
 // Gram evaluation to the hand-over to the factorisation.  Step p of the main loop, two barriers:
 //   phase B   waves that carry rows: factor + panel of column p — exactly the register-resident column operations of the
 //             small kernel (sm_factor_rows_lds) on the LDS image of the column, 48 rows per wave; the finished rows go
@@ -586,7 +529,6 @@ __global__ __launch_bounds__(SM_THREADS) void small_gp_grad_kernel(SmallArgs a, 
 // The right-hand side rides along as block row NB (its row 0 = target, the other 15 rows zero): z = L^-1 target
 // falls out of the same block operations, no special case.
 // ---------------------------------------------------------------------------------------------------------------------
-#define MID_MAXI 6         // block rows per wave at most: (NB + 1) <= 8 * MID_MAXI  ->  NB <= 47, limited to n <= 640 by the host
 #define MBLK(i, j) (X + ((((long long)(i) * ((i) + 1)) / 2 + (j)) << 8))     // scratch: packed lower blocks, rows 0..NB
 
 // operand-fragment register sets of the k loop for a wave that owns R block rows: the fragments of steps
@@ -654,9 +596,7 @@ __device__ __forceinline__ void mid_gram(const SmallNode& nd, const MidCtx& c, i
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 const int gj = SB * q + lg + 4 * v;
-                const bool in = gi < n && gj < n;
-                const double cv = nd.cov[in ? (long long)gj * n + gi : 0];
-                acc[u][v] = in ? nd.covscale * cv : (gi == gj ? 1.0 : 0.0);
+                acc[u][v] = sm_dense_entry(nd, gi, gj, n);
             }
         }
     } else {             // branch-free: the exp chains of all 4 R entries interleave
@@ -666,8 +606,7 @@ __device__ __forceinline__ void mid_gram(const SmallNode& nd, const MidCtx& c, i
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 const int gj = SB * q + lg + 4 * v;
-                const double e = nd.scale * gp_exp_neg(-lux[u][v]) + (gi == gj ? nd.noise : 0.0);
-                acc[u][v] = (gi < n && gj < n) ? e : (gi == gj ? 1.0 : 0.0);
+                acc[u][v] = sm_cov_entry(nd, lux[u][v], gi, gj, n);
             }
         }
     }
@@ -731,17 +670,11 @@ __device__ __forceinline__ void mid_factor(const MidCtx& c, int p, int& bad) {
         if (q0 + wave * 48 < rows) {                                 // scalar: this wave carries rows
             const bool is_diag = lane < SB;
             const int q = q0 + wave * 48 + (lane - SB);
-            double r[SB];
+            double r[SB] = {};
             double* src = nullptr;
             if (is_diag) src = c.Cp + li;
             else if (q < rows) src = c.Cp + (((q >> 4) + 1) << 8) + (q & 15);
-            if (src) {
-#pragma unroll
-                for (int cc = 0; cc < SB; ++cc) r[cc] = src[cc * SB];
-            } else {
-#pragma unroll
-                for (int cc = 0; cc < SB; ++cc) r[cc] = 0.0;
-            }
+            if (src) sm_row_load(r, src);
             double lcc;
             sm_factor_rows_lds(r, li, lane, SB * p, bad, lcc, c.bc);
             if (is_diag) {
@@ -754,13 +687,8 @@ __device__ __forceinline__ void mid_factor(const MidCtx& c, int p, int& bad) {
                     }
                 }
             } else if (src) {
-                double* dst = MBLK(p + 1 + (q >> 4), p) + (q & 15);
-#pragma unroll
-                for (int cc = 0; cc < SB; ++cc) dst[cc * SB] = r[cc];
-                if (DB) {
-#pragma unroll
-                    for (int cc = 0; cc < SB; ++cc) src[cc * SB] = r[cc];
-                }
+                sm_row_store(MBLK(p + 1 + (q >> 4), p) + (q & 15), r);
+                if (DB) sm_row_store(src, r);
             }
         }
     }
@@ -810,13 +738,8 @@ __device__ __forceinline__ void mid_step(const SmallNode& nd, const MidCtx& c, i
             if (DB) mid_kstep_lds<RA>(c, acc);
             else mid_kloop<RA, false>(c, q, p, p + 1, acc);
         }
-        const int li = c.lane & 15, lg = c.lane >> 4;
 #pragma unroll
-        for (int u = 0; u < RA; ++u) {
-            double* B = c.Cn + ((c.own + SM_WAVES * u) << 8);
-#pragma unroll
-            for (int v = 0; v < 4; ++v) B[(lg + 4 * v) * SB + li] = acc[u][v];
-        }
+        for (int u = 0; u < RA; ++u) sm_acc_store(c.Cn + ((c.own + SM_WAVES * u) << 8), acc[u], c.lane);
     }
     MID_STAMP(c.tt, 2);
     __syncthreads();                 // the LDS image of column q is complete
@@ -832,29 +755,21 @@ template <bool FL, bool DB, bool XR>
 __global__ __launch_bounds__(SM_THREADS) void mid_gp_logpdf_kernel(SmallArgs a) {
     extern __shared__ __attribute__((aligned(16))) double P[];
     const SmallNode nd = blockIdx.x < SMALL_INLINE_NODES ? a.inl[blockIdx.x] : a.nodes[blockIdx.x];
-    const int n = a.n, NB = a.NB, NP = NB * SB, NBa = NB + 1;
+    const MidLayout L(a.n, nd.nF, FL, DB, XR);
+    const int n = a.n, NB = L.NB, NP = L.NP;
     double* __restrict__ X = a.scratch + (long long)blockIdx.x * a.scratch_stride;     // finished columns
     double* C0 = P;                       // block column image(s): slot (i - p) = block (i, p), i = p..NB
-    double* ldv = C0 + (DB ? 2 : 1) * NBa * 256;   // diag(L)
-    double* bcl = ldv + NP;               // [8 waves][16] multiplier broadcast lines
-    double* xrow = bcl + SM_WAVES * SB;   // XR: [NB][256]
-    double* fl = xrow + (XR ? NB * 256 : 0);                // FL: features [f][NP] then target [NP];  else: the block column's features [f][16]
-    double* featg = X + ((long long)NBa * (NBa + 1) / 2) * 256;                        // !FL: features [f][NP], target [NP]
+    double* ldv = P + L.ldv;              // diag(L)
+    double* fl = P + L.feat;              // FL: features [f][NP] then target [NP];  else: the block column's features [f][16]
+    double* featg = X + L.s_feat;         // !FL: features [f][NP], target [NP]
+    double* tgt = FL ? P + L.tgt : X + L.s_tgt;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // scalar: every branch on it is a scalar branch
 
-    {
-        double* dstf = FL ? fl : featg;
-        for (int idx = tid; idx < nd.nF * NP; idx += SM_THREADS) {
-            const int f = idx / NP, i = idx - f * NP;
-            dstf[idx] = (i < n) ? nd.Fs[(long long)f * n + i] : 0.0;
-        }
-        // the right-hand side too: it is read once per block column, and nd.target lives in pinned HOST memory
-        double* dstt = dstf + (long long)nd.nF * NP;
-        for (int i = tid; i < NP; i += SM_THREADS) dstt[i] = (i < n) ? nd.target[i] : 0.0;
-    }
+    // the right-hand side is staged too: it is read once per block column, and nd.target lives in pinned HOST memory
+    sm_stage_node(nd, n, NP, tid, FL ? fl : featg, tgt);
     MidCtx mc;
-    mc.X = X; mc.Cp = C0; mc.Cn = C0; mc.ldv = ldv; mc.Xrow = xrow; mc.tid = tid; mc.bc = bcl + wave * SB; mc.draw = a.draw != nullptr; mc.fl = fl; mc.featg = featg; mc.tgt = (FL ? fl : featg) + (long long)nd.nF * NP;
+    mc.X = X; mc.Cp = C0; mc.Cn = C0; mc.ldv = ldv; mc.Xrow = P + L.orow; mc.tid = tid; mc.bc = P + L.bcl + wave * SB; mc.draw = a.draw != nullptr; mc.fl = fl; mc.featg = featg; mc.tgt = tgt;
     mc.n = n; mc.NB = NB; mc.NP = NP; mc.wave = wave; mc.lane = lane; mc.own = SM_WAVES - 1 - wave;
 #ifdef GPSLC_DIAG
     long long tt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -870,8 +785,8 @@ __global__ __launch_bounds__(SM_THREADS) void mid_gp_logpdf_kernel(SmallArgs a) 
     for (int p = -1; p < NB; ++p) {
         const int q = p + 1;
         // image of column p (factored in this step) / of column q (built in this step)
-        mc.Cp = C0 + ((DB && (p & 1)) ? NBa * 256 : 0);
-        mc.Cn = C0 + ((DB && (q & 1)) ? NBa * 256 : 0);
+        mc.Cp = C0 + ((DB && (p & 1)) ? L.image : 0);
+        mc.Cn = C0 + ((DB && (q & 1)) ? L.image : 0);
         if (!FL && q < NB) {       // stage the features of block column q (read by mid_gram only, which nobody runs right now)
             for (int idx = tid; idx < nd.nF * SB; idx += SM_THREADS) fl[idx] = featg[(idx >> 4) * NP + SB * q + (idx & 15)];
             __syncthreads();
@@ -891,7 +806,7 @@ __global__ __launch_bounds__(SM_THREADS) void mid_gp_logpdf_kernel(SmallArgs a) 
     }
 #ifdef GPSLC_DIAG
     if (a.stamps && blockIdx.x == 0 && lane == 0)
-        for (int j = 0; j < 6; ++j) a.stamps[8 * (long long)gridDim.x + 8 * wave + j] = (double)tt[j];
+        for (int j = 0; j < 6; ++j) a.stamps[NodeStage::kStamps * (long long)gridDim.x + NodeStage::kWaveStamps / SM_WAVES * wave + j] = (double)tt[j];
 #endif
 
     if (a.draw) {          // draw = L * target: row i of the factor from the scratch (L2), target from its staged copy
@@ -906,89 +821,34 @@ __global__ __launch_bounds__(SM_THREADS) void mid_gp_logpdf_kernel(SmallArgs a) 
             a.draw[(long long)blockIdx.x * n + i] = acc;
         }
     }
-    if (wave == 0) {      // z = row 0 of the right-hand side blocks (NB, k): z[16k + c] = X(NB, k)[c*16 + 0]
-        double q = 0.0, ld = 0.0;
-        for (int i = lane; i < n; i += 64) {
-            const double z = MBLK(NB, i >> 4)[(i & 15) * SB];
-            q = fma(z, z, q);
-            ld += log(ldv[i]);
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            q += __shfl_xor(q, o, 64);
-            ld += __shfl_xor(ld, o, 64);
-        }
-        if (lane == 0) {
-            double* o = a.out + 4 * (long long)blockIdx.x;
-            o[0] = 2.0 * ld;
-            o[1] = q;
-            o[2] = (double)bad;
-            o[3] = 0.0;
-        }
-    }
+    // z = row 0 of the right-hand side blocks (NB, k): z[16k + c] = X(NB, k)[c*16 + 0]
+    if (wave == 0) sm_write_score(a, lane, bad, ldv, [&](int i) { return MBLK(NB, i >> 4)[(i & 15) * SB]; });
 }
 
-size_t mid_gp_scratch_doubles(int n, int nF) {
-    const long long NB = (n + SB - 1) / SB, NBa = NB + 1;
-    return (size_t)(NBa * (NBa + 1) / 2 * 256 + (long long)(nF + 1) * NB * SB);
-}
-// LDS: column image(s) + diag(L) [+ shared operand row] + the features resident (preferred) or staged per block column
-static size_t mid_lds(int n, int nF, bool resident, bool two_images, bool xrow) {
-    const size_t NB = (n + SB - 1) / SB;
-    return ((two_images ? 2 : 1) * (NB + 1) * 256 + NB * SB + SM_WAVES * SB + (xrow ? NB * 256 : 0) +
-            (resident ? (size_t)(nF + 1) * NB * SB : (size_t)nF * SB)) * 8;
-}
-static void mid_choose(int n, int nF, bool& resident, bool& two_images, bool& xrow) {
-    const size_t cap = 160 * 1024;
-    xrow = mid_lds(n, nF, true, true, true) <= cap;
-    two_images = xrow || mid_lds(n, nF, true, true, false) <= cap;
-    resident = two_images || mid_lds(n, nF, true, false, false) <= cap;
-}
-size_t mid_gp_lds_bytes(int n, int nF) {
-    bool r, d, x;
-    mid_choose(n, nF, r, d, x);
-    return mid_lds(n, nF, r, d, x);
-}
-bool mid_gp_fits(int n) { return (n + SB - 1) / SB + 1 <= SM_WAVES * MID_MAXI && n <= 640; }
+size_t mid_gp_scratch_doubles(int n, int nF) { return (size_t)MidLayout::choose(n, nF).s_total; }
 
-template <bool FL, bool DB, bool XR>
-static void launch_mid_inst(const SmallArgs& a, int count, size_t bytes, hipStream_t st) {
+// one workgroup per node, the whole LDS of a CU opted in to once per kernel and device
+template <auto Kernel, class... Args>
+static void sm_launch(int count, size_t bytes, hipStream_t st, const Args&... args) {
     static DeviceOnce once;
-    lds_opt_in(once, (const void*)mid_gp_logpdf_kernel<FL, DB, XR>, 160 * 1024);
-    hipLaunchKernelGGL((mid_gp_logpdf_kernel<FL, DB, XR>), dim3(count), dim3(SM_THREADS), bytes, st, a);
+    lds_opt_in(once, (const void*)Kernel, (int)kLdsCapBytes);
+    hipLaunchKernelGGL(Kernel, dim3(count), dim3(SM_THREADS), bytes, st, args...);
 }
 
 void launch_mid_gp(const SmallArgs& a, int count, int nF_max, hipStream_t st) {
-    bool resident, two, xrow;
-    mid_choose(a.n, nF_max, resident, two, xrow);
-    const size_t bytes = mid_lds(a.n, nF_max, resident, two, xrow);
-    if (xrow) launch_mid_inst<true, true, true>(a, count, bytes, st);
-    else if (two) launch_mid_inst<true, true, false>(a, count, bytes, st);
-    else if (resident) launch_mid_inst<true, false, false>(a, count, bytes, st);
-    else launch_mid_inst<false, false, false>(a, count, bytes, st);
+    const MidLayout L = MidLayout::choose(a.n, nF_max);
+    if (L.xrow) sm_launch<mid_gp_logpdf_kernel<true, true, true>>(count, L.lds_bytes(), st, a);
+    else if (L.two) sm_launch<mid_gp_logpdf_kernel<true, true, false>>(count, L.lds_bytes(), st, a);
+    else if (L.resident) sm_launch<mid_gp_logpdf_kernel<true, false, false>>(count, L.lds_bytes(), st, a);
+    else sm_launch<mid_gp_logpdf_kernel<false, false, false>>(count, L.lds_bytes(), st, a);
 }
 
-size_t small_gp_lds_bytes(int n, int nF) {
-    const int NB = (n + SB - 1) / SB, NP = NB * SB;
-    return ((size_t)(NB * (NB + 1) / 2) * 256 + 3 * (size_t)NP + SM_WAVES * SB + (size_t)nF * NP) * 8;
-}
-
-// the gradient kernel's image: the score's, then alpha, the raw features, a lengthscale partial per block row, the lengthscales
-size_t small_grad_lds_bytes(int n, int nF) {
-    const int NB = (n + SB - 1) / SB, NP = NB * SB;
-    return small_gp_lds_bytes(n, nF) + ((size_t)NP + (size_t)nF * NP + (size_t)nF * NB + (size_t)nF) * 8;
-}
+size_t small_gp_lds_bytes(int n, int nF) { return SmallLayout(n, nF, false).bytes(); }
+size_t small_grad_lds_bytes(int n, int nF) { return SmallLayout(n, nF, true).bytes(); }
 
 void launch_small_grad(const SmallArgs& a, double* gout, int count, int nF_max, hipStream_t st) {
-    const size_t bytes = small_grad_lds_bytes(a.n, nF_max);
-    static DeviceOnce once;
-    lds_opt_in(once, (const void*)small_gp_grad_kernel, 160 * 1024);
-    hipLaunchKernelGGL(small_gp_grad_kernel, dim3(count), dim3(SM_THREADS), bytes, st, a, gout);
+    sm_launch<small_gp_grad_kernel>(count, small_grad_lds_bytes(a.n, nF_max), st, a, gout);
 }
-
 void launch_small_gp(const SmallArgs& a, int count, int nF_max, hipStream_t st) {
-    const size_t bytes = small_gp_lds_bytes(a.n, nF_max);
-    static DeviceOnce once;
-    lds_opt_in(once, (const void*)small_gp_logpdf_kernel, 160 * 1024);
-    hipLaunchKernelGGL(small_gp_logpdf_kernel, dim3(count), dim3(SM_THREADS), bytes, st, a);
+    sm_launch<small_gp_logpdf_kernel>(count, small_gp_lds_bytes(a.n, nF_max), st, a);
 }

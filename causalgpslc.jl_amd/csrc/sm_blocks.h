@@ -4,11 +4,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gpslc_internal.h"     // d4, d2
+#include "gpslc_internal.h"     // d4, d2, SmallNode, SmallArgs
+#include "gp_math.h"
+#include "sm_layout.h"
 
-#define SB 16
-#define SM_THREADS 512
-#define SM_WAVES (SM_THREADS / 64)
+#define SB kSmB
+#define SM_WAVES kSmWaves
+#define SM_THREADS (64 * SM_WAVES)
 #define SBLK(i, j) (P + ((((i) * ((i) + 1)) / 2 + (j)) << 8))
 
 __device__ __forceinline__ double sm_readlane(double x, int lane) {
@@ -19,6 +21,87 @@ __device__ __forceinline__ double sm_readlane(double x, int lane) {
 // fragment of a packed 16 x 16 block (column-major, ld 16): element (row = lane&15, k = 4kk + lane>>4)
 __device__ __forceinline__ double sm_frag(const double* blk, int kk, int lane) {
     return blk[(4 * kk + (lane >> 4)) * SB + (lane & 15)];
+}
+// a lane's row of a packed block column: 16 entries at stride 16
+__device__ __forceinline__ void sm_row_load(double (&r)[SB], const double* src) {
+#pragma unroll
+    for (int c = 0; c < SB; ++c) r[c] = src[c * SB];
+}
+__device__ __forceinline__ void sm_row_store(double* dst, const double (&r)[SB]) {
+#pragma unroll
+    for (int c = 0; c < SB; ++c) dst[c * SB] = r[c];
+}
+// MFMA accumulator -> packed block: element (row = lane&15, col = lane>>4 + 4v)
+__device__ __forceinline__ void sm_acc_store(double* B, const d4& acc, int lane) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) B[((lane >> 4) + 4 * v) * SB + (lane & 15)] = acc[v];
+}
+
+// block t of the row-major enumeration of the lower triangle, t = bi (bi + 1) / 2 + bj with bj <= bi, and the step to block t + 1
+__device__ __forceinline__ void sm_tri_block(int t, int& bi, int& bj) {
+    bi = 0; bj = t;
+    while (bj > bi) { bj -= bi + 1; ++bi; }
+}
+__device__ __forceinline__ void sm_tri_next(int& bi, int& bj, int steps = 1) {
+    for (int t = 0; t < steps; ++t) { if (++bj > bi) { ++bi; bj = 0; } }
+}
+
+// a node's scaled features [f][NP] and target [NP] out of the pinned staging, zeros for the padded instances
+__device__ __forceinline__ void sm_stage_node(const SmallNode& nd, int n, int NP, int tid, double* feat, double* tgt) {
+    for (int idx = tid; idx < nd.nF * NP; idx += SM_THREADS) {
+        const int f = idx / NP, i = idx - f * NP;
+        feat[idx] = (i < n) ? nd.Fs[(long long)f * n + i] : 0.0;
+    }
+    for (int i = tid; i < NP; i += SM_THREADS) tgt[i] = (i < n) ? nd.target[i] : 0.0;
+}
+// squared scaled distances of U index pairs from the LDS features fs[f * NP + i], the feature loop outermost: U independent
+// accumulations interleave.  Padded instances carry zeros: harmless, sm_cov_entry masks them
+template <int U>
+__device__ __forceinline__ void sm_dist2(const double* fs, int NP, int nF, const int (&gi)[U], const int (&gj)[U], double (&d2)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) d2[u] = 0.0;
+    for (int f = 0; f < nF; ++f) {
+        const double* ff = fs + f * NP;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double d = ff[gi[u]] - ff[gj[u]];
+            d2[u] = fma(d, d, d2[u]);
+        }
+    }
+}
+// entry (gi, gj) of scale * exp(-d2) + noise * I (src/kernel.jl:13-32, 53-59), the identity on the padding beyond n
+__device__ __forceinline__ double sm_rbf(const SmallNode& nd, double d2) { return nd.scale * gp_exp_neg(-d2); }
+__device__ __forceinline__ double sm_cov_entry(const SmallNode& nd, double d2, int gi, int gj, int n) {
+    const double e = sm_rbf(nd, d2) + (gi == gj ? nd.noise : 0.0);       // e + 0 = e exactly
+    return (gi < n && gj < n) ? e : (gi == gj ? 1.0 : 0.0);
+}
+// the same entry of a dense-covariance node, covscale * cov (uCov = SigmaU * uNoise, src/model_likelihood.jl:4-10)
+__device__ __forceinline__ double sm_dense_entry(const SmallNode& nd, int gi, int gj, int n, bool live = true) {
+    const bool in = live && gi < n && gj < n;
+    const double cv = nd.cov[in ? (long long)gj * n + gi : 0];
+    return in ? nd.covscale * cv : (gi == gj ? 1.0 : 0.0);
+}
+// wave 0: logdet, quad and info of node blockIdx.x from diag(L) and z = L^-1 target (z(i): where the kernel keeps z_i)
+template <class Z>
+__device__ __forceinline__ void sm_write_score(const SmallArgs& a, int lane, int bad, const double* ldv, Z z) {
+    double q = 0.0, ld = 0.0;
+    for (int i = lane; i < a.n; i += 64) {
+        const double zi = z(i);
+        q = fma(zi, zi, q);
+        ld += log(ldv[i]);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        q += __shfl_xor(q, o, 64);
+        ld += __shfl_xor(ld, o, 64);
+    }
+    if (lane == 0) {
+        double* o = a.out + NodeStage::kResult * (long long)blockIdx.x;
+        o[0] = 2.0 * ld;
+        o[1] = q;
+        o[2] = (double)bad;
+        o[3] = 0.0;
+    }
 }
 
 // y = d^-1/2: hardware estimate (~2^-23) + one third-order step (error^3 ~ 2^-69)
@@ -128,4 +211,3 @@ __device__ __forceinline__ void sm_update2(double* A0, const double* Xi0, const 
 #pragma unroll
     for (int v = 0; v < 4; ++v) { A0[(lg + 4 * v) * SB + li] = acc0[v]; A1[(lg + 4 * v) * SB + li] = acc1[v]; }
 }
-
