@@ -4,6 +4,7 @@
 #include "../../include/gpslc_hip.h"
 #include "gpslc_internal.h"
 #include "batch_plan.h"
+#include "tile_launch.h"
 #include "sm_layout.h"
 #include "philox.h"
 
@@ -14,6 +15,7 @@
 #include <cstring>
 #include <functional>
 #include <initializer_list>
+#include <memory>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -105,7 +107,6 @@ struct ProfRec {
     int cls;     // kernel class, see gpslc_profile_get_class (include/gpslc_hip.h)
 };
 constexpr int kProfClasses = 5;
-constexpr int kOrderBlock = 8;     // super-block edge (tiles) of the L2-blocked visiting order of a trailing update (tri_order)
 
 // device-resident task list of one (tile count, augmented row, batch size, group size) shape of the persistent
 // factorisation launch (potrf_tasks_kernel); built once per shape and kept (see task_list_for)
@@ -262,18 +263,35 @@ void ensure_streams(gpslc_ctx* c) {
 void rearm_queue(StreamSlot& s) { HC(hipMemsetAsync(s.queue, 0, 16 * sizeof(int), s.st)); }
 
 // ---- profiled launch of the tile kernels ------------------------------------------------
-// GemmArgs::sym of a symmetric launch of the factorisation of A: with a single short augmented tile row, its off-diagonal tiles
-// ride with the diagonal items (3).  Up to 32 live rows (31 levels): beyond that the diagonal kernel runs out of registers and
-// the augmented tiles carry enough real work to stay ordinary items
-static int aug_sym(int short_rows) { return (short_rows > 0 && short_rows <= 32) ? 3 : 2; }
+#ifdef GPSLC_DIAG
+// measurement build only: the in-kernel stamps of one launch.  arm() hands the kernel a zeroed buffer of 8-byte words; after the
+// launch, where armed (words != 0), dump() waits for it and writes the words to the file its caller opened (null: nothing is
+// written); the buffer goes with the capture
+struct StampCapture {
+    DevBuf buf;
+    size_t words = 0;
+    unsigned long long* arm(size_t n) {
+        buf.alloc((words = n) * 8);
+        HC(hipMemset(buf.p, 0, n * 8));
+        return buf.as<unsigned long long>();
+    }
+    void dump(hipStream_t st, FILE* file) {
+        std::unique_ptr<FILE, int (*)(FILE*)> f(file, fclose);      // closed on every way out
+        HC(hipStreamSynchronize(st));
+        std::vector<unsigned long long> h(words);
+        HC(hipMemcpy(h.data(), buf.p, words * 8, hipMemcpyDeviceToHost));
+        if (f) fwrite(h.data(), 8, words, f.get());
+    }
+};
+#endif
+
+// a launch description (tile_launch.h) on its stream slot: the slot's ticket counters, no measurement variant
+GemmArgs on_slot(GemmArgs g, const StreamSlot& s) { g.diag_skip = 0; g.dbg = nullptr; g.queue = s.queue; return g; }
 
 // prof_base: the kernel class of the profiled launches (0 = class 0 or 1 by the launch's shape)
 void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
     hipStream_t st = s.st;
-    GemmArgs g = g0;
-    g.diag_skip = 0;
-    g.dbg = nullptr;
-    g.queue = s.queue;
+    GemmArgs g = on_slot(g0, s);
     if (g.ntiles <= 0 || g.nbatch <= 0 || (g.k1 <= g.k0 && !g.fuse)) return;     // fuse with an empty K range: panel product only
 #ifdef GPSLC_DIAG
     // measurement build only: timing-only kernel variants (results are garbage by construction) and in-kernel
@@ -282,75 +300,33 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
     g.diag_skip = diag_skip;
     static const int dbg_m = diag_env("GPSLC_GEMM_DBG", 0);
     static bool dbg_done = false;
-    DevBuf dbg_buf;
-    size_t dbg_words = 0;
+    StampCapture stamps;
     // GPSLC_GEMM_DBG_FUSEK=<K>: the first FUSED in-panel launch whose K loop is K tiles deep instead
     static const int dbg_fk = diag_env("GPSLC_GEMM_DBG_FUSEK", -1);
     const bool dbg_fused = dbg_fk >= 0 && g.fuse && (g.k1 - g.k0) == dbg_fk;
     if (!dbg_done && ((dbg_fk < 0 && dbg_m > 0 && g.shape == 0 && g.mi == dbg_m) || dbg_fused)) {
-        dbg_words = (size_t)g.ntiles * g.nbatch * 8;
-        dbg_buf.alloc(dbg_words * 8);
-        HC(hipMemset(dbg_buf.p, 0, dbg_words * 8));
-        g.dbg = dbg_buf.as<unsigned long long>();
+        g.dbg = stamps.arm((size_t)g.ntiles * g.nbatch * 8);
         dbg_done = true;
     }
 #endif
-    // symmetric launches: the full-size diagonal tiles (those above the augmented rows) go to the lower-triangle kernel
-    auto launch_diag_tiles = [&]() {
-        if (g.fuse) return;     // factor_panels updated the diagonal tile before this launch (launch_diag_update_potrf)
-        if (g.sym && g.i0 == g.j0 && (g.diag_skip == 0 || g.diag_skip == 3)) {
-            GemmArgs d = g;
-            const int cand = g.shape == 0 ? g.mi : 1;      // a column update holds one diagonal tile
-            d.mi = g.short_rows > 0 ? std::max(0, std::min(cand, g.short_row0 - g.i0)) : cand;
-            launch_syrk_diag(d, g.sym == 3 && g.short_rows > 0 && g.diag_skip == 0, st);
-        }
-    };
-    const bool prof = (c->flags & GPSLC_FLAG_PROFILE) != 0;
-    if (prof) {
-        // algorithmic flop: full tiles count 2*128^3 per K tile, items in the (single) augmented row only
-        // their live right-hand-side rows
-        double short_items = 0;
-        if (g.short_rows > 0) {
-            const int last = g.i0 + g.mi - 1;                       // last output tile row of the launch
-            if (last >= g.short_row0) short_items = (g.shape == 0) ? (double)g.mi : (double)g.mj;
-        }
-        // diagonal tiles of a symmetric launch need only their lower triangle: half a tile product, as in the
-        // textbook N^3/3 count (the kernel runs 36 of the 64 sub-tile products, GemmArgs::sym); the short
-        // augmented diagonal tile is already counted by its live rows
-        double diag_items = 0.0;
-        if (g.sym && g.i0 == g.j0) diag_items = (g.shape == 0) ? (double)g.mi : 1.0;
-        if (short_items > 0 && g.shape == 0) diag_items -= 1.0;
-        // this kernel does not run the full-size diagonal tiles at all (launch_syrk_diag does, outside the timed bracket, so
-        // that the HIP-event average equals rocprofv3's average for the dominant kernel); the timing-only variants
-        // (GPSLC_GEMM_DIAG = 1 / 2) keep them as half a tile product each
-        const double diag_out = (g.diag_skip == 0 || g.diag_skip == 3) ? 1.0 : 0.5;
-        // sym == 3: the off-diagonal augmented-row tiles are not this kernel's either (they ride with the diagonal items)
-        double short_exec = short_items;
-        if (g.sym == 3 && short_items > 0) short_exec = (g.shape == 0) ? 1.0 : 0.0;
-        if (g.skip_gdiag && g.shape == 0 && short_exec >= 1.0) short_exec -= 1.0;     // the augmented diagonal tile is not run
-        const double rows = GP_TS * ((double)g.ntiles - short_items - diag_out * diag_items)
-                          + (double)g.short_rows * short_exec;
-        double flop = 2.0 * GP_TS * GP_TS * rows * (double)(g.k1 - g.k0) * (double)g.nbatch;
-        // fused panel product: one triangular solve per tile row = 128^2 * 128 multiply-adds... counted as the
-        // textbook n^2 b flop of a TRSM (the kernel runs 56 % of the dense 2*128^3 product)
-        if (g.fuse) flop += (double)GP_TS * GP_TS * rows * (double)g.nbatch;
-        {
-            ProfScope ps(c, prof_base ? prof_base : (g.fuse ? 1 : 0), flop, st);
-            launch_tile_gemm(g, st);
-        }
-        launch_diag_tiles();
-    } else {
+    {
+        const bool prof = (c->flags & GPSLC_FLAG_PROFILE) != 0;       // ProfScope does nothing without it
+        ProfScope ps(c, prof_base ? prof_base : (g.fuse ? 1 : 0), prof ? tile_launch_flop(g, g.diag_skip) : 0.0, st);
         launch_tile_gemm(g, st);
-        launch_diag_tiles();
+    }
+    // symmetric launches: the full-size diagonal tiles (those above the augmented rows) go to the lower-triangle kernel; those of
+    // a fused launch factor_panels updated before it (launch_diag_update_potrf)
+    if (!g.fuse && g.sym && g.i0 == g.j0 && (g.diag_skip == 0 || g.diag_skip == 3)) {
+        GemmArgs d = g;
+        const int cand = g.shape == 0 ? g.mi : 1;      // a column update holds one diagonal tile
+        d.mi = g.short_rows > 0 ? std::max(0, std::min(cand, g.short_row0 - g.i0)) : cand;
+        launch_syrk_diag(d, g.sym == 3 && g.short_rows > 0 && g.diag_skip == 0, st);
     }
     HC(hipGetLastError());   // launch-configuration errors (LDS opt-in, grid) surface here, not at the end of the call
 #ifdef GPSLC_DIAG
-    if (dbg_buf.p) {
-        HC(hipStreamSynchronize(st));
-        std::vector<unsigned long long> h(dbg_words);
-        HC(hipMemcpy(h.data(), dbg_buf.p, dbg_words * 8, hipMemcpyDeviceToHost));
+    if (stamps.words) {
         FILE* f = fopen("gpurun_out/gemm_dbg.bin", "wb");
-        if (f) { fwrite(h.data(), 8, dbg_words, f); fclose(f); }
+        stamps.dump(st, f);
     }
 #endif
 }
@@ -368,34 +344,18 @@ void prof_collect(gpslc_ctx* c) {
     c->prof_used = 0;
 }
 
-// Visiting order of the m(m+1)/2 lower-triangular output tiles: G x G super-blocks in row-major order,
-// row-major inside.  The kernel hands XCD x the x-th contiguous run of work items, so the ~64
-// workgroups an XCD runs concurrently cover about one super-block: they walk the K slabs of the same
-// G + G operand tile rows together and share them in that XCD's L2 instead of each streaming its own
-// copy from HBM (operand traffic / ~G).
+// the device copy of tri_order_pairs(m) (tile_launch.h), made once per ctx and m; null for m <= 2 (tri_decode's order serves)
 const unsigned short* tri_order(gpslc_ctx* c, int m) {
-    constexpr int G = kOrderBlock;
     if (m <= 2) return nullptr;
     if ((int)c->tri_order.size() <= m) c->tri_order.resize(m + 1, nullptr);
     if (c->tri_order[m]) return c->tri_order[m];
-    std::vector<unsigned short> h;
-    h.reserve((size_t)m * (m + 1));
-    for (int I = 0; I < m; I += G)
-        for (int J = 0; J <= I; J += G)
-            for (int i = I; i < std::min(I + G, m); ++i)
-                for (int j = J; j < std::min(J + G, m) && j <= i; ++j) {
-                    h.push_back((unsigned short)i);
-                    h.push_back((unsigned short)j);
-                }
+    const std::vector<unsigned short> h = tri_order_pairs(m);
     unsigned short* d = nullptr;
     HC(hipMalloc((void**)&d, h.size() * sizeof(unsigned short)));
     HC(hipMemcpy(d, h.data(), h.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
     c->tri_order[m] = d;
     return d;
 }
-
-TRef lower_ref(double* base, long long bstride) { return TRef{base, bstride, 0, 0, 0, 0}; }
-TRef rect_ref(double* base, long long bstride, int ld) { return TRef{base, bstride, 1, 0, 0, ld}; }
 
 // ---- the persistent factorisation launch (potrf_tasks_kernel, k_tilegemm.hip): task order = build_task_list, task_list.h ----
 const TaskList& task_list_for(gpslc_ctx* c, int nt, int back, int nb, int G, int rows, bool aug_full) {
@@ -435,8 +395,8 @@ bool potrf_tasks_ok(const gpslc_ctx* c, int nt, int ntot, int short_rows, bool s
 // back_alpha (optional, [nb][nt 128]): every matrix's task chain ends with its back-substitution alpha = L^-T z (z = right-hand
 // side 0 after the forward solve the factorisation carries): launch_backsolve's result, bit for bit.  The caller checks the
 // time-out word when its streams have drained (check_task_timeout).
-void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv, long long inv_bstride, int* info, int info_base,
-                 int nb, int short_rows, double* back_alpha) {
+void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv, int* info, int info_base, int nb, int short_rows,
+                 double* back_alpha) {
     hipStream_t st = s.st;
     rearm_queue(s);
     const size_t ints = TASK_SYNC_HDR + (size_t)TASK_SYNC_STRIDE * nb;
@@ -453,11 +413,7 @@ void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv
                                        std::max(1, std::min(4, nt > 8 ? 1 : c->task_rows)), short_rows > 32);
     HC(hipMemsetAsync(s.sync, 0, ints * sizeof(int), st));
     PotrfTaskArgs a{};
-    a.g.A = M; a.g.B = M; a.g.C = M;
-    a.g.F = TRef{inv, inv_bstride, 1, 0, 0, 0};
-    a.g.shape = 1; a.g.k0 = 0; a.g.fuse = 1; a.g.nbatch = nb;
-    a.g.short_row0 = nt; a.g.short_rows = short_rows; a.g.sym = 3;
-    a.g.info = info; a.g.info_base = info_base;
+    a.g = task_matrix(M, inv_ref(inv, nt), nt, short_rows, nb, info, info_base);
     a.list = tl.dev; a.sync = s.sync; a.timeout = c->task_timeout; a.nt = nt; a.alpha = back_alpha;
     a.fence_mode = diag_env("GPSLC_TASK_FENCE", 0x30);      // measurement build: bit 0 = no release fence (WRONG results: the
                                                             // price of the fence), bits 4..5 = priority of the diagonal tasks
@@ -474,12 +430,8 @@ void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv
     // measurement build, GPSLC_TASK_DBG=<n>: per-task stamps of the n-th launch -> gpurun_out/task_dbg.bin (tools/task_stamps.py)
     static const int dbg_at = diag_env("GPSLC_TASK_DBG", 0);
     static int dbg_seen = 0;
-    DevBuf dbg_buf;
-    if (dbg_at > 0 && ++dbg_seen == dbg_at) {
-        dbg_buf.alloc((size_t)tl.ntasks * 64);
-        HC(hipMemset(dbg_buf.p, 0, (size_t)tl.ntasks * 64));
-        a.dbg = dbg_buf.as<unsigned long long>();
-    }
+    StampCapture stamps;
+    if (dbg_at > 0 && ++dbg_seen == dbg_at) a.dbg = stamps.arm((size_t)tl.ntasks * 8);
 #endif
     {
         ProfScope ps(c, 4, (Np * Np * Np / 3.0 + (double)a.g.short_rows * Np * Np) * (double)nb, st);
@@ -487,12 +439,9 @@ void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv
     }
     HC(hipGetLastError());
 #ifdef GPSLC_DIAG
-    if (dbg_buf.p) {
-        HC(hipStreamSynchronize(st));
-        std::vector<unsigned long long> h((size_t)tl.ntasks * 8);
-        HC(hipMemcpy(h.data(), dbg_buf.p, h.size() * 8, hipMemcpyDeviceToHost));
+    if (stamps.words) {
         FILE* f = fopen("gpurun_out/task_dbg.bin", "wb");
-        if (f) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+        stamps.dump(st, f);
     }
 #endif
 }
@@ -529,24 +478,11 @@ void factor_robust(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int* info
     for (int k = 0; k < nt; ++k) {
         const int ka = (k / pw) * pw;
         const int kend = std::min(ka + pw, nt);
-        if (k > ka) {
-            GemmArgs g{};
-            g.A = M; g.B = M; g.C = M;
-            g.shape = 1; g.i0 = k; g.j0 = k; g.mi = nt - k; g.mj = 1; g.sym = 2;
-            g.k0 = ka; g.k1 = k; g.nbatch = nb; g.ntiles = g.mi;
-            gemm(c, g, s, prof_base);
-        }
+        if (k > ka) gemm(c, tile_column(M, M, M, k, k, nt - k, ka, k, nb, true), s, prof_base);
         launch_diag_robust(M, k, info, info_base, nb, s.st);
         launch_trsm_robust(M, M, k, k + 1, nt - k - 1, nb, s.st);
-        if (k == kend - 1 && nt - kend > 0) {
-            GemmArgs g{};
-            g.A = M; g.B = M; g.C = M;
-            const int m = nt - kend;
-            g.shape = 0; g.i0 = kend; g.j0 = kend; g.mi = m; g.mj = m; g.sym = 2;
-            g.k0 = ka; g.k1 = kend; g.nbatch = nb; g.ntiles = m * (m + 1) / 2;
-            g.order = tri_order(c, m);
-            gemm(c, g, s, prof_base);
-        }
+        if (k == kend - 1 && nt - kend > 0)
+            gemm(c, tile_triangle(M, M, M, kend, nt - kend, ka, kend, nb, tri_order(c, nt - kend)), s, prof_base);
     }
     HC(hipGetLastError());
 }
@@ -555,64 +491,48 @@ void factor_robust(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int* info
 // the rows nt..ntot-1 are carried along (augmented rows): after the call they hold R = rows * L^-T and the trailing (ntot-nt)^2
 // block its Schur complement.  Panels of `pw` tile columns: left-looking inside a panel, one right-looking trailing update
 // (K = pw*128) per panel.  prof_base: see gemm.
-void factor_panels(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int ntot, double* inv, long long inv_bstride,
-                   int* info, int info_base, int nb, int aug_rows, bool skip_aug_diag, int prof_base) {
+void factor_panels(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, int ntot, double* inv, int* info, int info_base, int nb,
+                   int aug_rows, bool skip_aug_diag, int prof_base) {
     hipStream_t st = s.st;
     // aug_rows > 0: the tile rows nt.. hold only that many live rows in total (right-hand sides);
     // a single augmented tile row is the common case and the only one the kernel shortens
     const int short_rows = (aug_rows > 0 && ntot == nt + 1) ? aug_rows : 0;
     const int pw = std::max(1, c->panel);
     rearm_queue(s);
-    TRef invref = TRef{inv, inv_bstride, 1, 0, 0, 0};   // tile (j, kk) -> inv[kk]
+    const TRef invref = inv_ref(inv, nt);
     for (int k = 0; k < nt; ++k) {
         const int ka = (k / pw) * pw;
         const int kend = std::min(ka + pw, nt);
         const int below = ntot - k - 1;      // tiles of column k below the diagonal
-        GemmArgs g{};                        // the column's strip launch: update over the panel columns [ka, k) + panel product
-                                             // (F / fk are read by the fused launches only: strip_item's panel product)
-        g.A = M; g.B = M; g.C = M; g.F = invref; g.fk = k;
-        g.shape = 1; g.j0 = k; g.mj = 1; g.k1 = k; g.nbatch = nb;
-        g.short_row0 = nt; g.short_rows = short_rows;
+        // the column's strip launch, rows [i0, ntot): update over the panel columns [ka, k), fused with the panel product or not
+        auto column = [&](int i0, int k0, bool sym) {
+            return short_aug_row(tile_column(M, M, M, i0, k, ntot - i0, k0, k, nb, sym), nt, short_rows);
+        };
         if (k > ka && below > 0) {
             // in-panel update: the diagonal tile first — update, factor and inverse in ONE launch — then ONE pass over the column:
             // tile(i,k) -= sum_{kk in [ka,k)} tile(i,kk) tile(k,kk)^T and tile(i,k) *= inv(L_kk)^T for every tile below the
             // diagonal (the column makes one HBM round trip instead of two)
-            g.i0 = k; g.mi = ntot - k; g.ntiles = g.mi; g.k0 = ka; g.sym = aug_sym(short_rows);
-            GemmArgs d = g;
+            const GemmArgs g = fused(column(k, ka, true), invref, k);
+            GemmArgs d = g;       // the diagonal-tile launch reads the strip's column, K range, F and augmented row (not its fuse)
             d.info = info; d.info_base = info_base;
             launch_diag_update_potrf(d, g.sym == 3, st);
-            g.fuse = 1;
             gemm(c, g, s, prof_base);
         } else {
-            if (k > ka) {
-                // the last column of a matrix without augmented rows (ntot == nt: likelihood_distribution_impl) inside a panel:
-                // nothing lies below the diagonal, the column update holds the diagonal tile alone
-                g.i0 = k; g.mi = 1; g.ntiles = 1; g.k0 = ka; g.sym = 2;
-                gemm(c, g, s, prof_base);
-            }
-            launch_diag(M, k, inv, inv_bstride, info, info_base, nb, st);
-            if (below > 0) {
-                // the first column of a panel has no column update: its panel product tile(i,k) *= inv(L_kk)^T runs as the strip
-                // kernel's second phase alone (empty K range: the tile goes from HBM into the accumulators, the fragments of
-                // inv(L_kk) from L2 into registers, no LDS staging)
-                g.i0 = k + 1; g.mi = below; g.ntiles = below; g.k0 = k; g.sym = 0; g.fuse = 1;
-                gemm(c, g, s, prof_base);
-            }
+            // the last column of a matrix without augmented rows (ntot == nt: likelihood_distribution_impl) inside a panel:
+            // nothing lies below the diagonal, the column update holds the diagonal tile alone
+            if (k > ka) gemm(c, column(k, ka, true), s, prof_base);
+            launch_diag(M, k, inv, invref.bstride, info, info_base, nb, st);
+            // the first column of a panel has no column update: its panel product tile(i,k) *= inv(L_kk)^T runs as the strip
+            // kernel's second phase alone (empty K range: the tile goes from HBM into the accumulators, the fragments of
+            // inv(L_kk) from L2 into registers, no LDS staging)
+            if (below > 0) gemm(c, fused(column(k + 1, k, false), invref, k), s, prof_base);
         }
         // skip_aug_diag (single short augmented row, epilogue sums from the rows of R): the augmented diagonal tile is
         // never updated — after the last panel it would be the launch's only item
         const bool skip_gd = skip_aug_diag && short_rows > 0;
-        if (k == kend - 1 && ntot - kend > (skip_gd ? 1 : 0)) {   // trailing update with the whole panel
-            GemmArgs t{};
-            t.A = M; t.B = M; t.C = M;
-            const int m = ntot - kend;
-            t.skip_gdiag = skip_gd ? 1 : 0;
-            t.shape = 0; t.i0 = kend; t.j0 = kend; t.mi = m; t.mj = m; t.sym = aug_sym(short_rows);
-            t.k0 = ka; t.k1 = kend; t.nbatch = nb; t.ntiles = m * (m + 1) / 2;
-            t.order = tri_order(c, m);
-            t.short_row0 = nt; t.short_rows = short_rows;
-            gemm(c, t, s, prof_base);
-        }
+        if (k == kend - 1 && ntot - kend > (skip_gd ? 1 : 0))     // trailing update with the whole panel
+            gemm(c, short_aug_row(tile_triangle(M, M, M, kend, ntot - kend, ka, kend, nb, tri_order(c, ntot - kend)), nt, short_rows,
+                                  skip_gd), s, prof_base);
     }
 }
 
@@ -886,13 +806,8 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
 #ifdef GPSLC_DIAG
     static const int gram_dbg = diag_env("GPSLC_GRAM_DBG", 0);
     static bool gram_dbg_done = false;
-    DevBuf gdbg;
-    if (gram_dbg && !gram_dbg_done) {
-        const size_t words = (size_t)8 * nb * (nt * (nt + 1) / 2);
-        gdbg.alloc(words * 8);
-        HC(hipMemset(gdbg.p, 0, words * 8));
-        ga.dbg = gdbg.as<unsigned long long>();
-    }
+    StampCapture stamps;
+    if (gram_dbg && !gram_dbg_done) ga.dbg = stamps.arm((size_t)8 * nb * (nt * (nt + 1) / 2));
 #endif
     ga.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
     ga.binary_t = (c->binary_t && io.nU == c->nU && io.nX == c->nX && io.Y == c->dY) ? 1 : 0;   // ctx data only
@@ -905,12 +820,8 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     launch_gram(ga, nb, st);
 #ifdef GPSLC_DIAG
     if (ga.dbg) {      // GPSLC_GRAM_DBG: dump the first launch's per-workgroup stamps
-        HC(hipStreamSynchronize(st));
-        const size_t words = (size_t)8 * nb * (nt * (nt + 1) / 2);
-        std::vector<unsigned long long> h(words);
-        HC(hipMemcpy(h.data(), ga.dbg, words * 8, hipMemcpyDeviceToHost));
         FILE* f = fopen("gpurun_out/gram_dbg.bin", "wb");
-        if (f) { fwrite(h.data(), 8, words, f); fclose(f); }
+        stamps.dump(st, f);
         gram_dbg_done = true;
     }
 #endif
@@ -931,16 +842,15 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     // NB: the MeanITE pass takes K alpha as Y - yNoise alpha (k_solve.hip, ite_mean_kernel): it relies on alpha solving EXACTLY
     // (K_gram + yNoise I) alpha = Y.  Any future jitter, robust fallback or different right-hand side in this factorisation must
     // be reflected there (tests: test_mean_ite_tiny_noise_and_near_coincident_levels).
-    const long long inv_bs = (long long)nt * GP_TSQ;
     const int short_rows = sh.naug == 1 ? live : 0;
     bool back_done = false;
     if (potrf_tasks_ok(c, nt, sh.ntot, short_rows, epi_rows, nb, ch.inv)) {
         // small tile counts: the whole factorisation (and the back-substitution) as ONE persistent launch of tile tasks
-        potrf_tasks(c, *ch.s, ch.M, nt, ch.inv, inv_bs, io.info + s0, 0, nb, short_rows,
+        potrf_tasks(c, *ch.s, ch.M, nt, ch.inv, io.info + s0, 0, nb, short_rows,
                     sh.want_alpha ? ch.zwork + (long long)nb * sh.Np : nullptr);
         back_done = sh.want_alpha;
     } else {
-        factor_panels(c, *ch.s, ch.M, nt, sh.ntot, ch.inv, inv_bs, io.info + s0, 0, nb, live, epi_rows, 0);
+        factor_panels(c, *ch.s, ch.M, nt, sh.ntot, ch.inv, io.info + s0, 0, nb, live, epi_rows, 0);
     }
     EpiArgs ea{};
     ea.M = ch.M; ea.n = n; ea.nt = nt; ea.naug = sh.naug; ea.L = sh.with_sums ? sh.R : 0; ea.s0 = s0; ea.S = io.post.S;
@@ -1001,13 +911,7 @@ void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
 // with blocking it like the factorisation (profiles/r04_ab_experiments.md §7).  W has `rows` tile rows: nt for unit B's D, the
 // row tiles of the new individuals for D* (unit_new).
 void w_solve(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& Ls, const TRef& invref, int nt, int ub, int rows) {
-    for (int k = 0; k < nt; ++k) {
-        GemmArgs g{};
-        g.A = W; g.B = Ls; g.C = W; g.F = invref; g.fk = k;
-        g.shape = 1; g.i0 = 0; g.j0 = k; g.mi = rows; g.mj = 1; g.nbatch = ub; g.ntiles = rows;
-        g.k0 = 0; g.k1 = k; g.fuse = 1;
-        gemm(c, g, s, 3);
-    }
+    for (int k = 0; k < nt; ++k) gemm(c, fused(tile_column(W, Ls, W, 0, k, rows, 0, k, ub, false), invref, k), s, 3);
 }
 
 // what LooArgs, LgoArgs and GradArgs share: the chunk's W = L^-T, alpha = A^-1 Y, the scored Y and the samples' failure codes
@@ -1033,15 +937,10 @@ void loo(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     HC(hipMemsetAsync(ch.loo_w, 0, sizeof(double) * (size_t)nb * sh.nlow * GP_TSQ, st));     // every chain starts from a zero tile
     launch_loo_init(la, nb, st);
     rearm_queue(*ch.s);
-    for (int d = 1; d < nt; ++d) {
-        GemmArgs g{};
-        g.A = g.C = lower_ref(ch.loo_w, la.w_bstride);
-        g.B = ch.M;
-        g.F = TRef{ch.inv, la.inv_bstride, 1, 0, 0, 0};
-        g.shape = 1; g.mj = 1; g.fuse = 1; g.nbatch = nb; g.ntiles = nt - d;
-        g.queue = ch.s->queue;
-        launch_loo_diagonal(g, nt, d, st);
-    }
+    const TRef W = lower_ref(ch.loo_w, la.w_bstride), invref = inv_ref(ch.inv, nt);
+    // a fused column of nt - d items; the kernel gives item i its own tile (i, i + d), K range and inverted block
+    for (int d = 1; d < nt; ++d)
+        launch_loo_diagonal(on_slot(fused(tile_column(W, ch.M, W, 0, 0, nt - d, 0, 0, nb, false), invref, 0), *ch.s), nt, d, st);
     if (sh.want_loo || sh.grad_c) launch_loo_rownorm(la, nb, st);
     if (sh.want_loo) launch_loo_finish(la, nb, st);
     if (sh.want_lgo) {      // leave-group-out: one workgroup per (group, sample) on the same W and alpha
@@ -1084,7 +983,7 @@ void for_pair_batches(const PredictShape& sh, const Chunk& ch, Body&& body) {
         for (int l0 = 0; l0 < sh.L; l0 += ch.lc_max) {
             const int lc = std::min(ch.lc_max, sh.L - l0);
             TRef Ls = lower_ref(ch.tiles + (long long)g0 * bstride, bstride);
-            TRef invref = TRef{ch.inv + (long long)g0 * inv_bs, inv_bs, 1, 0, 0, 0};
+            TRef invref = inv_ref(ch.inv + (long long)g0 * inv_bs, sh.nt);
             Ls.bdiv = invref.bdiv = lc;
             body(g0, gs, l0, lc, gs * lc, Ls, invref);
         }
@@ -1093,12 +992,7 @@ void for_pair_batches(const PredictShape& sh, const Chunk& ch, Body&& body) {
 
 // C <- C - W W^T on the lower tiles of C's `rows` tile rows, for ub pairs (W: rows x nt tiles)
 void minus_w_wt(gpslc_ctx* c, StreamSlot& s, const TRef& W, const TRef& C, int nt, int ub, int rows) {
-    GemmArgs g{};
-    g.A = W; g.B = W; g.C = C;
-    g.shape = 0; g.i0 = 0; g.j0 = 0; g.mi = rows; g.mj = rows; g.sym = 2;
-    g.k0 = 0; g.k1 = nt; g.nbatch = ub; g.ntiles = (int)((long long)rows * (rows + 1) / 2);
-    g.order = tri_order(c, rows);
-    gemm(c, g, s, 3);
+    gemm(c, tile_triangle(W, W, C, 0, rows, 0, nt, ub, tri_order(c, rows)), s, 3);
 }
 
 // Unit B of a chunk: the full ITE covariance of every pair, W <- D L^-T, CovITE (+ jitter) = Delta - W W^T, and what is asked of
@@ -2765,14 +2659,8 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
         // remaining column block in parallel on the MFMA tile kernel
         for (int k = 0; k < nt; ++k) {
             launch_trsm_robust(W, Ls, k, 0, naug, 1, st);
-            if (k + 1 < nt) {   // W(:, j) -= W(:, k) L(j, k)^T for j > k
-                GemmArgs u{};
-                u.A = W; u.B = Ls; u.C = W;
-                u.shape = 1; u.i0 = 0; u.j0 = k + 1; u.mi = naug; u.mj = nt - k - 1;
-                u.k0 = k; u.k1 = k + 1; u.nbatch = 1; u.ntiles = naug * (nt - k - 1);
-                u.short_row0 = 0; u.short_rows = short_rows;
-                gemm(c, u, slot, 0);
-            }
+            if (k + 1 < nt)     // W(:, j) -= W(:, k) L(j, k)^T for j > k
+                gemm(c, short_aug_row(tile_rect(W, Ls, W, 0, k + 1, naug, nt - k - 1, k, k + 1, 1), 0, short_rows), slot, 0);
         }
         launch_row_norms(RowNormArgs{W, nt, naug, S, oq}, st);
         HC(hipStreamSynchronize(st));
@@ -2860,7 +2748,7 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
         GramArgs ga{grid};
         ga.M = M; ga.part = nullptr; ga.with_sums = 0; ga.f32 = 0;
         launch_gram(ga, 1, st);
-        factor_panels(c, slot, M, nt, nt, inv.as<double>(), (long long)nt * GP_TSQ, info.as<int>(), 0, 1, 0, false, 0);
+        factor_panels(c, slot, M, nt, nt, inv.as<double>(), info.as<int>(), 0, 1, 0, false, 0);
         LdBuildArgs la{grid, doT, Kt, Kst, KsTt, Ksst};
         if (doTv) la.doTv = up(bdo, doTv, (size_t)n);
         launch_ld_build(la, st);
@@ -2877,17 +2765,13 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
             // W1 = K L^-T, W2 = Ks' L^-T  (copies, then unit B's tile-level left-looking solve)
             HC(hipMemcpyAsync(W1.base, Kt.base, (size_t)rs * 8, hipMemcpyDeviceToDevice, st));
             HC(hipMemcpyAsync(W2.base, KsTt.base, (size_t)rs * 8, hipMemcpyDeviceToDevice, st));
-            TRef invref = TRef{inv.as<double>(), (long long)nt * GP_TSQ, 1, 0, 0, 0};
+            TRef invref = inv_ref(inv.as<double>(), nt);
             w_solve(c, slot, W1, M, invref, nt, 1, nt);
             w_solve(c, slot, W2, M, invref, nt, 1, nt);
             // C11 = K - W1 W1', C12 = Ks - W1 W2', C21 = Ks' - W2 W1', C22 = Kss - W2 W2'   (src/likelihood.jl:46-49)
             auto block = [&](const TRef& Cm, const TRef& Wa, const TRef& Wb, double* host) {
                 if (!host) return;
-                GemmArgs g{};
-                g.A = Wa; g.B = Wb; g.C = Cm;
-                g.shape = 1; g.i0 = 0; g.j0 = 0; g.mi = nt; g.mj = nt;
-                g.k0 = 0; g.k1 = nt; g.nbatch = 1; g.ntiles = nt * nt;
-                gemm(c, g, slot, 0);
+                gemm(c, tile_rect(Wa, Wb, Cm, 0, 0, nt, nt, 0, nt, 1), slot, 0);
                 emit(Cm, host, 0.0);
             };
             block(Kt, W1, W1, CovC11);      // K, Ks, Ks', Kss are consumed in place: emitted above already

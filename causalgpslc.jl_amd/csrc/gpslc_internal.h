@@ -87,7 +87,9 @@ __host__ __device__ inline double* tref_tile(const TRef& t, long long b, int i, 
     return t.base + b * t.bstride + tref_index(t, i, j) * (long long)GP_TSQ;
 }
 
-// C(i, j) -= sum_{kk in [k0, k1)} A(i, kk) * B(j, kk)^T over a set of output tiles.
+// C(i, j) -= sum_{kk in [k0, k1)} A(i, kk) * B(j, kk)^T over a set of output tiles.  The host fills one in through the builders
+// of tile_launch.h only (one per kind of launch: rectangle, tile column, lower triangle, task matrix), which own the invariants
+// between the fields: ntiles against shape / mi / mj / order, short_row0 with short_rows, F / fk with fuse, sym == 3, skip_gdiag.
 struct GemmArgs {
     TRef A, B, C;
     int shape;        // 0: lower triangle (incl. diagonal) of an mi x mi tile square, 1: mi x mj rectangle
@@ -193,8 +195,8 @@ struct GramArgs : SampleGrid {
 // ---------------------------------------------------------------------------------------
 #include "task_list.h"     // descriptor layout + the host-built task order (plain C++: tests/c/task_list_test.cpp exercises it on the CPU)
 struct PotrfTaskArgs {
-    GemmArgs g;             // A = B = C = the tile matrix, F = the inverted diagonal blocks, k0 = 0, short_row0 = nt, short_rows,
-                            // sym = 3 with an augmented row riding along, info / info_base, nbatch
+    GemmArgs g;             // task_matrix (tile_launch.h): A = B = C = the tile matrix, F = the inverted diagonal blocks, k0 = 0,
+                            // short_row0 = nt, short_rows, sym = 3 with an augmented row riding along, info / info_base, nbatch
     const unsigned* list;   // TASK_LIST_HDR header words, then the descriptors of the eight queues
     int* sync;              // TASK_SYNC_HDR + TASK_SYNC_STRIDE * nbatch ints (ticket heads, progress words), all zeroed before every
                             // launch by the launcher's caller
