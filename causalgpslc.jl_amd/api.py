@@ -14,6 +14,7 @@ like the reference's own tests:
     yLogpdfGrad                                   gradient of that node's score in U, the hyper-parameters and Y (no reference counterpart)
     lgoPredictive, lgoSummary, foldLabels         leave-group-out checks and K-fold cross-validation of it (no reference counterpart)
     predictNew                                    outcome, contrast or slope at individuals who are not in the data (no reference counterpart)
+    averageNew                                    their weighted averages over a target population, with variance and joint covariance (no reference counterpart)
 
 Everything numeric is done by libgpslc_hip.so through the C ABI (``_lib``); this module only
 marshals arrays (NumPy, column-major) and reproduces the reference's output layouts.
@@ -360,6 +361,22 @@ class Context:
         st, out = self._call_for(self.lib.gpslc_predict_new, {"mean": dims, "var": dims, "cov": (dims[0],) + dims}, want,
                                  S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, int(NEW_FORMS.get(form, form)), L, doT,
                                  doT_base, float(pred_noise), fill=None)      # written in full by every call that returns a status >= 0
+        return (st, *out.values())
+
+    def predict_new_weighted(self, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, doT, doT_base, weights, pred_noise,
+                             want=("mean", "var"), G=None):
+        """gpslc_predict_new_weighted with host arrays as given (None = NULL): ``(status, meanW, varW, covW)`` — the outputs named
+        in ``want`` as (S, L, G) / (S, L, L, G) column-major arrays, the others None (NULL to the library).  ``weights`` is (G, m)
+        (row g = weight column g; a vector: G = 1), ``G`` overrides the count that is passed.  ``form`` and the status are
+        ``predict_new``'s: a positive one leaves NaN in that sample's outputs and the other samples' values."""
+        S, m = int(S), int(m)
+        L = 0 if doT is None else int(np.size(doT))
+        W = None if weights is None else np.ascontiguousarray(np.atleast_2d(np.asarray(weights, dtype=np.float64)))   # weights[i + m*g]
+        G = int(G) if G is not None else 0 if W is None else W.shape[0]
+        dims = (max(S, 0), L, max(G, 0))
+        st, out = self._call_for(self.lib.gpslc_predict_new_weighted, {"mean": dims, "var": dims, "cov": dims[:2] + dims[1:]}, want,
+                                 S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, int(NEW_FORMS.get(form, form)), L, doT,
+                                 doT_base, G, W, float(pred_noise), fill=None)      # written in full by every call that returns a status >= 0
         return (st, *out.values())
 
     def profile_reset(self):
@@ -1083,10 +1100,26 @@ def predictNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, baseline=N
     A model with neither has one kind of new individual: m = 1.  The ordinary effect f(a) - f(T) needs the new individual's own
     treatment: ask for the contrast with ``baseline=`` that treatment.  Refusals are raised before any library call; a failed
     factorisation raises ``PosDefException``."""
+    levels, base, X, U, m, form = _new_request(g, doTs, Xnew, like, Unew, baseline, slope)
+    want = ("mean",) + (("var",) if want_var or want_cov else ()) + (("cov",) if want_cov else ())
+    ctx = g.ctx()
+    st, mean, var, cov = ctx.predict_new(g.getNumPosteriorSamples(), g.U, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise, m, X, U, form,
+                                         levels, base, g.hyperparams.predictionCovarianceNoise, want=want)
+    ctx.check(st)
+    var = var if want_var else None
+    # (S, L, m, m) as a view of the library's m x m x S x L: every block is exactly symmetric, so no copy is needed to index it
+    # [s, l, i, i']
+    return (mean, var, np.transpose(cov, (2, 3, 0, 1))) if want_cov else (mean, var)
+
+
+def _new_request(g, doTs, Xnew, like, Unew, baseline, slope):
+    """What predictNew and averageNew share: the refusals of ``_NEW_REFUSALS`` and the parsing of the levels and of the new
+    individuals' features -> (levels (L,), base (L,) or None, Xnew (m, nX) or None, Unew (m, nU, S) or None, m, form), the arrays
+    column-major as the library takes them.  Raises before any library call."""
     nX, nU, n, S = g.getNX(), g.getNU(), g.getN(), g.getNumPosteriorSamples()
     a = np.asarray(doTs, dtype=np.float64)
     q = SimpleNamespace(fp32=g.fp32_kernel, slope=bool(slope), base=baseline is not None, ndim=a.ndim, nX=nX, nU=nU,
-                        X=Xnew is not None, like=like is not None, U=Unew is not None, want_var=want_var, want_cov=want_cov)
+                        X=Xnew is not None, like=like is not None, U=Unew is not None)
     for cond, exc, msg in _NEW_REFUSALS:
         if cond(q):
             raise exc(msg.format(nX=nX, nU=nU))
@@ -1115,16 +1148,31 @@ def predictNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, baseline=N
     for name, v in (("doTs", levels), ("Xnew", X), ("Unew", U)):
         if v is not None and not np.all(np.isfinite(v)):
             raise ValueError(f"{name} has a non-finite entry")
-    form = "slope" if slope else "outcome" if base is None else "contrast"
-    want = ("mean",) + (("var",) if want_var or want_cov else ()) + (("cov",) if want_cov else ())
+    return levels, base, X, U, m, "slope" if slope else "outcome" if base is None else "contrast"
+
+
+def averageNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, weights=None, baseline=None, slope=False, want_cov=False):
+    """Weighted averages over m individuals who are not in the data (gpslc_predict_new_weighted) -> ``mean`` (S, L[, G]), ``var``
+    (S, L[, G]) [, ``cov`` (S, L, L[, G]) with ``want_cov=True``]: per posterior sample, level and weight column, the average
+    tau_g = w_g' f* of what ``predictNew`` gives per individual — the outcome, the contrast with ``baseline=`` or the slope —
+    over a target population that is not the sample, with the variance ``predictNew``'s ``var`` cannot give (the new individuals
+    share one Gaussian process) and the joint covariance of the levels; no (m, m) array exists anywhere.
+
+    ``weights=None`` is 1/m for everybody: the population average.  A length-m vector is one weight column (no group axis), an
+    (G, m) array or a sequence of rows keeps it; Bool rows are group masks (the group's average), Float rows are used as given:
+    a difference of two group rows is the difference of the groups with its correct variance; ``groupWeights(labels)`` builds
+    the rows of a labelling of the new individuals.  ``Xnew`` / ``like`` / ``Unew`` / ``baseline`` / ``slope`` are
+    ``predictNew``'s, parsed and refused as there.  The outputs have ``effectCurve``'s shapes: ``curveSamples(mean, cov, spp)``
+    draws whole curves of the target population.  A failed factorisation raises ``PosDefException``."""
+    levels, base, X, U, m, form = _new_request(g, doTs, Xnew, like, Unew, baseline, slope)
+    W, is_vec = (np.full((1, m), 1.0 / m), True) if weights is None else _weights(weights, m)
+    want = ("mean", "var") + (("cov",) if want_cov else ())
     ctx = g.ctx()
-    st, mean, var, cov = ctx.predict_new(S, g.U, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise, m, X, U, form, levels, base,
-                                         g.hyperparams.predictionCovarianceNoise, want=want)
+    st, mean, var, cov = ctx.predict_new_weighted(g.getNumPosteriorSamples(), g.U, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise, m, X,
+                                                  U, form, levels, base, W, g.hyperparams.predictionCovarianceNoise, want=want)
     ctx.check(st)
-    var = var if want_var else None
-    # (S, L, m, m) as a view of the library's m x m x S x L: every block is exactly symmetric, so no copy is needed to index it
-    # [s, l, i, i']
-    return (mean, var, np.transpose(cov, (2, 3, 0, 1))) if want_cov else (mean, var)
+    out = (mean, var) + ((cov,) if want_cov else ())
+    return tuple(o[..., 0] for o in out) if is_vec else out
 
 
 def gpLogpdf(F, LS, scale, noise, target, ctx: Optional[Context] = None):

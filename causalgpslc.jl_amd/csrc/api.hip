@@ -605,6 +605,9 @@ struct NewIndividuals {              // predictions for m new individuals (gpslc
     double *mean = nullptr, *var = nullptr, *cov = nullptr;     // m x S x L each and m x m x S x L; cov needs var: its diagonal
     bool pairs() const { return var || cov; }            // the (sample, level) pairs need tile workspace
     bool any() const { return mean || pairs(); }
+    // weighted averages over them (gpslc_predict_new_weighted), a call of its own: Levels::W / G are then G weight
+    // columns over the m NEW individuals (device: W[g + G*i]) and DrawsAndOutputs::meanSATE / varSATE / covW receive meanW, varW, covW
+    bool weighted = false;
 };
 
 struct PredictIO {
@@ -695,6 +698,7 @@ struct Chunk {
     double *vpart = nullptr, *zwork = nullptr, *znode = nullptr;
     double *bw = nullptr, *kw = nullptr, *wnorm2 = nullptr;      // weighted effects: B W, K W [nb][G][Np], w_g . w_g [nb][G]
     double* cprior = nullptr;        // joint covariance across the levels: beta, kappa, gamma_l [nb][G][L + 2]
+    double* wpart = nullptr;         // weighted averages over new individuals: the row blocks' shares of w' B** w [nb][mt][G]
     double *loo_w = nullptr, *loo_c = nullptr;      // leave-one-out: W = L^-T as a packed triangle of tiles [nb][nlow], diag(A^-1) [nb][Np]
     double *grad_ls = nullptr, *grad_u = nullptr;   // gradient: the pair pass's partial sums per tile (GradArgs::part_ls, part_u)
     // unit B: a sub-batch of gs_max samples x lc_max levels; W, CovITE, the draws' normals, level-sweep staging, failure codes
@@ -731,6 +735,7 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
         b.kw = io.lv.needs_kw() ? take((size_t)io.lv.G * sh.Np) : b.bw;
         b.wnorm2 = take(io.lv.G);
         if (io.out.covW) b.cprior = take((size_t)io.lv.G * (L + 2));
+        if (io.fresh.weighted) b.wpart = take((size_t)sh.mt * io.lv.G);
     }
     if (io.lv.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
@@ -811,7 +816,15 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
 #endif
     ga.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
     ga.binary_t = (c->binary_t && io.nU == c->nU && io.nX == c->nX && io.Y == c->dY) ? 1 : 0;   // ctx data only
-    if (io.lv.W) {      // weighted effects: B W and K W, one pass over the pairs for all columns and levels (independent of the tiles)
+    const bool over_new = io.fresh.weighted;      // the weight columns run over the new individuals
+    if (over_new) {     // B*' W over the m x n pairs, w' B** w over the m x m pairs, and the sums the prepare kernels would form
+        NewWsumArgs wa{};
+        static_cast<SampleGrid&>(wa) = ch.grid;
+        wa.Xnew = io.fresh.Xnew; wa.Unew = io.fresh.Unew; wa.un_sstride = (long long)io.fresh.m * io.nU; wa.m = io.fresh.m; wa.mt = sh.mt;
+        wa.lv = io.lv.set(sh.L); wa.G = io.lv.G; wa.W = io.lv.W;
+        wa.bw = ch.bw; wa.part = ch.wpart; wa.sumdelta = ch.sumdelta; wa.wnorm2 = ch.wnorm2; wa.prior = ch.cprior;
+        launch_new_wsum(wa, nb, st);
+    } else if (io.lv.W) {      // weighted effects: B W and K W, one pass over the pairs for all columns and levels (independent of the tiles)
         WsumArgs wa{ch.grid};
         wa.G = io.lv.G; wa.W = io.lv.W;
         wa.bw = ch.bw; wa.kw = ch.kw; wa.with_k = io.lv.needs_kw() ? 1 : 0; wa.binary_t = ga.binary_t;
@@ -836,8 +849,8 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
     const int live = (sh.with_sums ? sh.R : 0) + 1;          // right-hand sides: Y and one c_l per level (and weight column)
     ra.live_rows = (epi_rows && live <= 32) ? 16 * ((live + 15) / 16) : 0;
     ra.G = 1; ra.bw = ch.bsum; ra.kw = ch.ksum;       // the plain call: one column of level sums, the Gram build's
-    if (io.lv.W) { ra.W = io.lv.W; ra.G = io.lv.G; ra.bw = ch.bw; ra.kw = ch.kw; ra.wnorm2 = ch.wnorm2; }
-    launch_rhs(ra, nb, st);
+    if (io.lv.W) { ra.W = over_new ? nullptr : io.lv.W; ra.G = io.lv.G; ra.bw = ch.bw; ra.kw = ch.kw; ra.wnorm2 = ch.wnorm2; }
+    launch_rhs(ra, nb, st, over_new);
     if (io.lv.vec && sh.with_sums) launch_vec_sums(vec_args(io, sh, ch), nb, st);
     // NB: the MeanITE pass takes K alpha as Y - yNoise alpha (k_solve.hip, ite_mean_kernel): it relies on alpha solving EXACTLY
     // (K_gram + yNoise I) alpha = Y.  Any future jitter, robust fallback or different right-hand side in this factorisation must
@@ -865,7 +878,7 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
         ca.T = c->dT; ca.tyLS = io.post.p.tyLS;
         ca.W = io.lv.W; ca.bw = ch.bw; ca.kw = ch.kw; ca.prior = ch.cprior;
         ca.varW = io.out.varSATE; ca.covW = io.out.covW;
-        launch_curve(ca, nb, st);
+        launch_curve(ca, nb, st, over_new);
     }
     if (io.ndraw) {
         // one draw from N(0, A_s) per parameter set with the caller's normals: L_s z_s on the factor just computed — Gen's
@@ -1096,6 +1109,12 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         if (io.lv.vec || io.fresh.m < 1) throw std::runtime_error("new individuals need scalar levels and m >= 1");
         if (io.fresh.cov && !io.fresh.var) throw std::runtime_error("the covariance of new individuals needs their variance: its diagonal");
         if (io.CovITEs || io.out.ite_draws) throw std::runtime_error("new individuals cannot be combined with CovITE or draws: one pair workspace");
+    }
+    if (io.fresh.weighted) {
+        if (fr.factual) throw std::runtime_error("new individuals have no factual treatment: ordinary levels cannot be predicted for them");
+        if (!io.lv.W || io.fresh.m < 1) throw std::runtime_error("weighted averages over new individuals need weights and m >= 1");
+        if (io.fresh.any() || io.CovITEs || io.out.ite_draws || io.out.meanITE || io.MeanITEs)
+            throw std::runtime_error("weighted averages over new individuals are a call of their own: no per-individual outputs, CovITE or draws");
     }
     if (io.nU < 0) io.nU = c->nU;
     if (io.nX < 0) io.nX = c->nX;
@@ -2504,13 +2523,14 @@ int gpslc_y_lgo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
                         });
 }
 
-// predictions for m new individuals (DESIGN.md §19): host pointers; every check before any device work
-int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
-                      const double* yScale, const double* yNoise, int64_t m, const double* Xnew, const double* Unew,
-                      int32_t form, int32_t L, const double* doT, const double* doT_base, double pred_noise, double* mean,
-                      double* var, double* cov) {
+// The checks gpslc_predict_new and gpslc_predict_new_weighted share: the samples, then arguments 9 - 15 (m, Xnew, Unew, form, L,
+// doT, doT_base), which sit at the same positions in both
+static int validate_new(gpslc_ctx* c, const PredictRequest& rq, int64_t m, const double* Xnew, const double* Unew, int32_t form,
+                        const double* doT_base) {
     static const ArgPos kNewArgs{2, 3, 5, 6, 13, 14, 0, 0, 0, 0, true};
-    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    const int64_t S = rq.post.S;
+    const int32_t L = rq.lv.L;
+    const double* doT = rq.lv.doT;
     int rc = validate(c, rq, kNewArgs);
     if (rc) return rc;
     if (m < 1 || m > (int64_t)GP_TS * 32767) return bad_arg(c, 9, "m < 1 (or beyond 32767 row tiles)");
@@ -2527,22 +2547,40 @@ int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uy
     } else if (doT_base) {
         return bad_arg(c, 15, "doT_base given for a form that is no contrast");
     }
+    return 0;
+}
+// ... and their uploads: the samples, the levels of the form and the new individuals' features
+static PredictIO new_io(gpslc_ctx* c, const PredictRequest& rq, int64_t m, const double* Xnew, const double* Unew, int32_t form,
+                        const double* doT_base, double pred_noise) {
+    const size_t mm = (size_t)m, S = (size_t)rq.post.S, L = (size_t)rq.lv.L;
+    PredictIO io;
+    io.post.S = rq.post.S; io.post.p = upload_samples(c, rq.post.p, 0, S);
+    io.X = c->dX;
+    io.lv.L = rq.lv.L; io.lv.doT = up(c, rq.lv.doT, L);
+    io.lv.form = form == GPSLC_NEW_OUTCOME ? FORM_OUTCOME : form == GPSLC_NEW_SLOPE ? FORM_SLOPE : FORM_CONTRAST;
+    io.lv.base = doT_base ? up(c, doT_base, L) : nullptr;
+    io.out.pred_noise = pred_noise;
+    io.fresh.m = (int)m;
+    io.fresh.Xnew = Xnew ? up(c, Xnew, mm * c->nX) : nullptr;
+    io.fresh.Unew = Unew ? up(c, Unew, mm * c->nU * S) : nullptr;
+    return io;
+}
+
+// predictions for m new individuals (DESIGN.md §19): host pointers; every check before any device work
+int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
+                      const double* yScale, const double* yNoise, int64_t m, const double* Xnew, const double* Unew,
+                      int32_t form, int32_t L, const double* doT, const double* doT_base, double pred_noise, double* mean,
+                      double* var, double* cov) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    int rc = validate_new(c, rq, m, Xnew, Unew, form, doT_base);
+    if (rc) return rc;
     if (!std::isfinite(pred_noise)) return bad_arg(c, 16, "pred_noise is not finite");
     if (!mean && !var && !cov) return bad_arg(c, 17, "mean, var and cov are all NULL");
     if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
     return guarded(c, [&]() {
         const size_t mm = (size_t)m, SL = (size_t)S * L;
         c->io.reset();
-        PredictIO io;
-        io.post.S = S; io.post.p = upload_samples(c, rq.post.p, 0, (size_t)S);
-        io.X = c->dX;
-        io.lv.L = L; io.lv.doT = up(c, doT, (size_t)L);
-        io.lv.form = form == GPSLC_NEW_OUTCOME ? FORM_OUTCOME : form == GPSLC_NEW_SLOPE ? FORM_SLOPE : FORM_CONTRAST;
-        io.lv.base = doT_base ? up(c, doT_base, (size_t)L) : nullptr;
-        io.out.pred_noise = pred_noise;
-        io.fresh.m = (int)m;
-        io.fresh.Xnew = Xnew ? up(c, Xnew, mm * c->nX) : nullptr;
-        io.fresh.Unew = Unew ? up(c, Unew, mm * c->nU * (size_t)S) : nullptr;
+        PredictIO io = new_io(c, rq, m, Xnew, Unew, form, doT_base, pred_noise);
         const Outputs outs = {{mean, &io.fresh.mean, mm * SL}, {var, &io.fresh.var, mm * SL}, {cov, &io.fresh.cov, mm * mm * SL}};
         take_outputs(c, outs);
         if (cov && !var) io.fresh.var = c->io.take<double>(mm * SL);      // the covariance takes its diagonal from it
@@ -2560,6 +2598,47 @@ int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uy
                     if (cov) std::fill(cov + mm * o, cov + mm * (o + mm), NAN);
                 }
             }
+        return st;
+    });
+}
+
+// weighted averages over m new individuals: gpslc_predict_new's checks, then G >= 1 columns of m finite weights
+int gpslc_predict_new_weighted(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
+                               const double* yScale, const double* yNoise, int64_t m, const double* Xnew, const double* Unew,
+                               int32_t form, int32_t L, const double* doT, const double* doT_base, int32_t G, const double* weights,
+                               double pred_noise, double* meanW, double* varW, double* covW) {
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
+    int rc = validate_new(c, rq, m, Xnew, Unew, form, doT_base);
+    if (rc) return rc;
+    if (G < 1) return bad_arg(c, 16, "G < 1");
+    if ((rc = finite_check(c, weights, m * (int64_t)G, 17, "weights"))) return rc;
+    if (!std::isfinite(pred_noise)) return bad_arg(c, 18, "pred_noise is not finite");
+    if (!meanW && !varW && !covW) return bad_arg(c, 19, "meanW, varW and covW are all NULL");
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        const size_t mm = (size_t)m, Gs = (size_t)G, SR = (size_t)S * L * Gs;
+        c->io.reset();
+        PredictIO io = new_io(c, rq, m, Xnew, Unew, form, doT_base, pred_noise);
+        io.fresh.weighted = true;
+        {       // m x G host (weights[i + m*g]) -> column fastest on the device (W[g + G*i]), as predict_host does
+            std::vector<double> wt(mm * Gs);
+            for (size_t i = 0; i < mm; ++i)
+                for (size_t g = 0; g < Gs; ++g) wt[g + Gs * i] = weights[i + mm * g];
+            io.lv.W = up(c, wt.data(), wt.size());
+            io.lv.G = G;
+        }
+        const Outputs outs = {{meanW, &io.out.meanSATE, SR}, {varW, &io.out.varSATE, SR}, {covW, &io.out.covW, SR * L}};
+        take_outputs(c, outs);
+        if (covW && !varW) io.out.varSATE = c->io.take<double>(SR);      // the joint covariance takes its diagonal from it
+        io.info = c->io.take<int>((size_t)S);
+        run_predict(c, io);
+        const int st = first_info(c);
+        deliver_outputs(c, outs);
+        if (st > 0)      // a sample whose factorisation broke down: NaN in everything of it (sample fastest in every output)
+            for (const Output& o : outs)
+                for (size_t s = 0; o.host && s < (size_t)S; ++s)
+                    if (c->last_info[s] != 0)
+                        for (size_t k = s; k < o.count; k += (size_t)S) o.host[k] = NAN;
         return st;
     });
 }

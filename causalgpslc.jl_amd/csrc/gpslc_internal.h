@@ -248,7 +248,9 @@ struct RhsArgs {
     const double* W; int G;   // device, column g fastest: W[g + G*j]
     const double* bw; const double* kw; double* wnorm2;      // kw is read by the factual form only
 };
-void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st);
+// sums_given: sumdelta (and wnorm2) are already there and neither prepare kernel runs — the weight columns run over other
+// individuals than the n of this grid (launch_new_wsum); W stays null, G and bw are a weighted call's
+void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st, bool sums_given = false);
 
 // weighted column sums BW = B W, KW = K W of a chunk (k_wsum.hip): one pass over the pairs per sample for all G columns
 struct WsumArgs : SampleGrid {
@@ -284,7 +286,9 @@ struct CurveArgs {
     const double* varW;       // S x L x G, as the epilogue stored it: the diagonal
     double* covW;             // S x L x L x G: element (s, l, l', g) at s + S*(l + L*(l' + L*g))
 };
-void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st);
+// prior_given: prior[b][g][0] = beta is already there (launch_new_wsum; non-factual forms): curve_prior_kernel does not run, and W,
+// bw, kw are not read
+void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st, bool prior_given = false);
 
 struct BackArgs {
     TRef M; const double* inv; long long inv_bstride; int nt; int naug;
@@ -429,6 +433,21 @@ void launch_new_mean(const NewArgs& a, int nbatch, hipStream_t st);      // mean
 void launch_new_build(const NewArgs& a, int nbatch, hipStream_t st);     // W <- D*(l) (zero padding), Cm <- prior_l B** + pred_noise I
 void launch_new_var(const NewArgs& a, int nbatch, hipStream_t st);       // var = (prior_l yScale - ||row of W||^2) + pred_noise
 void launch_new_gather(const NewArgs& a, int nbatch, hipStream_t st);    // Cm -> cov, both triangles; the diagonal is var
+
+// Weighted averages over the new individuals: what launch_rhs, launch_epilogue and launch_curve read of a weighted
+// call — bw, sumdelta, wnorm2 and beta — for G weight columns over the m new individuals, from one pass over the m x n pairs and one
+// over the m x m pairs.  Everything downstream is the weighted call's (§13, §14) with RhsArgs::sums_given / CurveArgs::prior_given.
+struct NewWsumArgs : NewGrid {
+    LevelSet lv;            // scalar levels of a non-factual form: prior_l of sumdelta
+    int G;
+    const double* W;        // device, column g fastest over the new individuals: W[g + G*i]
+    double* bw;             // [b][G][Np]: bw*_g = B*^T w_g (rows j >= n: 0.0)
+    double* part;           // [b][mt][G]: row block ti's share of beta_g = w_g' B** w_g
+    double* sumdelta;       // [b][L*G]: prior_l beta_g at l + L*g
+    double* wnorm2;         // [b][G]: w_g . w_g
+    double* prior;          // [b][G][L + 2] (CurveArgs::prior): beta_g into slot 0, 0.0 into slot 1; or null
+};
+void launch_new_wsum(const NewWsumArgs& a, int nbatch, hipStream_t st);
 
 void launch_rbf_log(const double* X1, const double* X2, long long n, int d, const double* ls,
                     int ls_len, double* out, hipStream_t st);

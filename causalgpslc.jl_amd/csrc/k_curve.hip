@@ -123,11 +123,11 @@ __global__ __launch_bounds__(256) void curve_gram_kernel(CurveArgs a) {
 }
 
 template <int FORM>
-static void launch_curve_t(const CurveArgs& a, int nbatch, hipStream_t st) {
+static void launch_curve_t(const CurveArgs& a, int nbatch, hipStream_t st, bool prior_given) {
     const int nblk = (a.lv.L * a.G + 1 + 15) / 16;
-    hipLaunchKernelGGL(curve_prior_kernel<LevelForm<FORM>::factual>, dim3(a.G, nbatch), dim3(256), 0, st, a);
+    if (!prior_given) hipLaunchKernelGGL(curve_prior_kernel<LevelForm<FORM>::factual>, dim3(a.G, nbatch), dim3(256), 0, st, a);
     hipLaunchKernelGGL(curve_gram_kernel<FORM>, dim3(nblk * (nblk + 1) / 2, nbatch), dim3(256), 0, st, a);
 }
-void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st) {
-    dispatch_form(a.lv.form, [&](auto form) { launch_curve_t<decltype(form)::value>(a, nbatch, st); });
+void launch_curve(const CurveArgs& a, int nbatch, hipStream_t st, bool prior_given) {
+    dispatch_form(a.lv.form, [&](auto form) { launch_curve_t<decltype(form)::value>(a, nbatch, st, prior_given); });
 }

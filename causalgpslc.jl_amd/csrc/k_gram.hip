@@ -387,13 +387,14 @@ __global__ __launch_bounds__(256) void rhs_w_prepare_kernel(RhsArgs a) {
 
 // the plain and the weighted prepare kernels reduce in different orders (both are part of the results); the tiles are one kernel
 template <int FORM>
-static void launch_rhs_t(const RhsArgs& r, int nbatch, hipStream_t st) {
-    if (r.W) hipLaunchKernelGGL(rhs_w_prepare_kernel<FORM>, dim3(r.lv.L * r.G, nbatch), dim3(256), 0, st, r);
-    else if (r.with_sums) hipLaunchKernelGGL(rhs_prepare_kernel<FORM>, dim3(nbatch), dim3(256), 0, st, r);
+static void launch_rhs_t(const RhsArgs& r, int nbatch, hipStream_t st, bool sums_given) {
+    // both prepare kernels sum over the n individuals of this grid: sums_given, the caller's sums run over others
+    if (r.W && !sums_given) hipLaunchKernelGGL(rhs_w_prepare_kernel<FORM>, dim3(r.lv.L * r.G, nbatch), dim3(256), 0, st, r);
+    else if (r.with_sums && !sums_given) hipLaunchKernelGGL(rhs_prepare_kernel<FORM>, dim3(nbatch), dim3(256), 0, st, r);
     hipLaunchKernelGGL(rhs_tiles_kernel<FORM>, dim3(r.nt + r.naug, r.naug, nbatch), dim3(256), 0, st, r);
 }
-void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st) {
-    dispatch_form(r.lv.form, [&](auto form) { launch_rhs_t<decltype(form)::value>(r, nbatch, st); });
+void launch_rhs(const RhsArgs& r, int nbatch, hipStream_t st, bool sums_given) {
+    dispatch_form(r.lv.form, [&](auto form) { launch_rhs_t<decltype(form)::value>(r, nbatch, st, sums_given); });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -9,14 +9,15 @@
 // product W* W*^T are the tile kernels' (api.hip: w_solve, gemm).
 // Every output element depends on its own new individual(s), the training data and the sample only, in a fixed summation order:
 // results do not depend on which other new individuals share the call, nor on the chunk, the stream or the schedule.
+// Further down: weighted averages over the new individuals, which need none of these tiles.
 #include "pair_mfma.h"
 #include <stdexcept>
 
 namespace {
 
 // prior_l of batch element (s, l): Delta*_ii' = prior_l B**_ii'
-template <int FORM>
-__device__ __forceinline__ double new_prior(const NewArgs& a, long long s, int l) {
+template <int FORM, class Args>
+__device__ __forceinline__ double new_prior(const Args& a, long long s, int l) {
     using LF = LevelForm<FORM>;
     const double tl = a.p.tyLS[s];
     const double wt = 1.0 / (tl * tl);
@@ -198,6 +199,108 @@ __global__ __launch_bounds__(256) void new_gather_kernel(NewArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Weighted averages over the new individuals: tau_g(l) = w_g' f*(l) for G weight columns over the m new
+// individuals.  c_g(l) = D*(l)' w_g = cross(l) .* bw*_g with bw*_g = B*' w_g, and w_g' Delta*(l, l') w_g = joint_ll' beta_g with
+// beta_g = w_g' B** w_g: with bw*, sumdelta = prior_l beta_g, wnorm2 = w_g . w_g and beta the weighted call's kernels (rhs_tiles,
+// the factorisation, the epilogue, curve_gram: §13, §14) do the rest, and neither an mt x nt tile workspace nor anything m x m
+// exists.  Both passes are wsum_mfma_kernel's product (k_wsum.hip: X[i, g] = W[i, g], passes of 64 weight columns) with another
+// choice of the two sides.
+// ---------------------------------------------------------------------------------------
+// bw*[j, g] = sum_i B*_ij W[i, g] for one row block of 128 training individuals of one sample: the new individuals are the column
+// side.  The store is wsum_mfma_kernel's: new individuals that copy the training individuals give that kernel's bw bit for bit.
+template <int FREG>
+__global__ __launch_bounds__(256, 2) void new_wsum_cross_kernel(NewWsumArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const long long b = blockIdx.y, s = a.s0 + b;
+    const int Np = a.nt * GP_TS, G = a.G;
+    pair_mfma_body_sides<FREG, false, 0>(
+        a, s, G, sm, a.m, a.mt * GP_TS, [&](int F, int g0, double* fr) { stage_scaled_features<GP_TS>(a, s, F, F, g0, fr); },
+        [&](int F, int FS, int c0, double* fc) { stage_scaled_new_features<PM_CC>(a, s, F, FS, c0, fc); },
+        [&](int i, int g, double, const double*) { return a.W[(long long)i * G + g]; },
+        [&](int gj, int g0, int ng, const d4* acc, const d4*) {
+            const bool in = gj < a.n;
+            pair_mfma_each_column(ng, [&](int q, int v, int ll) { a.bw[(b * G + (g0 + ll)) * Np + gj] = in ? acc[q][v] : 0.0; });
+        });
+}
+
+// part[ti, g] = sum_{i in row block ti} W[i, g] (B** W)[i, g]: new individuals on both sides, and the product is reduced against
+// W before it leaves the workgroup — no m x G buffer.  Order of a column's sum, fixed: per wave and 16-row sub-tile the xor tree
+// over the 16 rows (1, 2, 4, 8), sub-tile 0 + sub-tile 1, then the waves as (w0 + w1) + (w2 + w3).  Rows i >= m contribute 0.0.
+// LDS: the body's layout, then red [4 waves][PM_NL].
+constexpr int new_wsum_self_lds_bytes(int F, int FS) { return pair_mfma_lds_bytes(F, FS, false) + 4 * PM_NL * 8; }
+
+template <int FREG>
+__global__ __launch_bounds__(256, 2) void new_wsum_self_kernel(NewWsumArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const long long b = blockIdx.y, s = a.s0 + b;
+    const int G = a.G, F = a.nU + a.nX;
+    double* red = sm + pair_mfma_lds_bytes(F, FREG > F ? FREG : F, false) / 8;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double p[4][4];
+    pair_mfma_body_sides<FREG, false, 0>(
+        a, s, G, sm, a.m, a.mt * GP_TS, [&](int F_, int g0, double* fr) { stage_scaled_new_features<GP_TS>(a, s, F_, F_, g0, fr); },
+        [&](int F_, int FS, int c0, double* fc) { stage_scaled_new_features<PM_CC>(a, s, F_, FS, c0, fc); },
+        [&](int i, int g, double, const double*) { return a.W[(long long)i * G + g]; },
+        [&](int gi, int g0, int ng, const d4* acc, const d4*) {
+            const bool second = (gi >> 4) & 1;      // the body's sub-tile index (row = 128 ib + 32 wave + 16 sub + li): workgroup-uniform
+            const double* wrow = a.W + (long long)gi * G + g0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int ll = 16 * q + (lane >> 4) + 4 * v;
+                    const double t = (gi < a.m && ll < ng) ? wrow[ll] * acc[q][v] : 0.0;
+                    p[q][v] = second ? p[q][v] + t : t;
+                }
+            if (!second) return;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    double x = p[q][v];
+#pragma unroll
+                    for (int o = 1; o <= 8; o <<= 1) x += __shfl_xor(x, o, 64);
+                    if ((lane & 15) == 0) red[wave * PM_NL + 16 * q + (lane >> 4) + 4 * v] = x;
+                }
+            __syncthreads();
+            // red is next written after the barriers of the next pass's chunk loop
+            if (tid < ng)
+                a.part[(b * a.mt + blockIdx.x) * G + g0 + tid] =
+                    (red[tid] + red[PM_NL + tid]) + (red[2 * PM_NL + tid] + red[3 * PM_NL + tid]);
+        });
+}
+
+// per (weight column, sample): beta_g = the row blocks' shares in ascending order, wnorm2_g = w_g . w_g (rhs_w_prepare_kernel's
+// strided sum and tree), sumdelta[l + L g] = prior_l beta_g, and beta into slot 0 of the curve's prior (kappa, slot 1: 0.0)
+template <int FORM>
+__global__ __launch_bounds__(256) void new_wsum_finish_kernel(NewWsumArgs a) {
+    __shared__ double red[4];
+    __shared__ double s_beta;
+    const int tid = threadIdx.x, g = blockIdx.x;
+    const long long b = blockIdx.y, s = a.s0 + b;
+    const int G = a.G, L = a.lv.L;
+    double ww = 0.0;
+    for (int i = tid; i < a.m; i += 256) {
+        const double w = a.W[(long long)i * G + g];
+        ww = fma(w, w, ww);
+    }
+    const double w2 = block_sum_256(ww, red);
+    if (tid == 0) {
+        double beta = 0.0;
+        for (int ti = 0; ti < a.mt; ++ti) beta += a.part[(b * a.mt + ti) * G + g];
+        s_beta = beta;
+        a.wnorm2[b * G + g] = w2;
+        if (a.prior) {
+            double* pr = a.prior + (b * G + g) * (L + 2);
+            pr[0] = beta; pr[1] = 0.0;
+        }
+    }
+    __syncthreads();
+    const double beta = s_beta;
+    for (int l = tid; l < L; l += 256) a.sumdelta[b * L * G + l + (long long)L * g] = new_prior<FORM>(a, s, l) * beta;
+}
+
 // the level forms new individuals can be asked for: the non-factual ones of level_form.h (run_predict refuses the others)
 template <typename F>
 void dispatch_new_form(int form, F&& f) {
@@ -208,6 +311,22 @@ void dispatch_new_form(int form, F&& f) {
 }
 
 }  // namespace
+
+void launch_new_wsum(const NewWsumArgs& a, int nbatch, hipStream_t st) {
+    if (nbatch <= 0) return;
+    const int F = a.nU + a.nX;
+    pair_mfma_freg_ladder(F, [&](auto freg) {
+        constexpr int FREG = decltype(freg)::value;
+        pair_mfma_launch<new_wsum_cross_kernel<FREG>, FREG, false>(a, nbatch, st);
+        static DeviceOnce attr_set;
+        lds_opt_in(attr_set, (const void*)new_wsum_self_kernel<FREG>, new_wsum_self_lds_bytes(MAXF, MAXF));
+        hipLaunchKernelGGL((new_wsum_self_kernel<FREG>), dim3(a.mt, nbatch), dim3(256),
+                           new_wsum_self_lds_bytes(F, FREG > F ? FREG : F), st, a);
+    });
+    dispatch_new_form(a.lv.form, [&](auto form) {
+        hipLaunchKernelGGL((new_wsum_finish_kernel<decltype(form)::value>), dim3(a.G, nbatch), dim3(256), 0, st, a);
+    });
+}
 
 void launch_new_mean(const NewArgs& a, int nbatch, hipStream_t st) {
     if (nbatch <= 0) return;

@@ -1,7 +1,7 @@
 // The pair product on the MFMA: (B X)[i, col] = sum_j B_ij X[j, col] (and (K X) with K = B .* e) for one row block of 128
 // individuals of one posterior sample, B = yScale exp(Lu + Lx), e_ij = exp(-(T_i - T_j)^2 / tyLS^2).  The one body of
 // ite_mean_mfma_kernel (k_solve.hip: X[j, l] = r_j(l) alpha_j) and wsum_mfma_kernel (k_wsum.hip: X[j, g] = W[j, g]); DESIGN.md,
-// "MeanITE on the MFMA" and §13.
+// "MeanITE on the MFMA" and §13.  k_new.hip runs it with the new individuals on one side or on both (§19, §25).
 //
 // No operand tile of B goes through LDS: the f64 16x16x4 MFMA wants one element per lane, and each lane computes exactly its
 // own B_rc (row = 16m + lane&15, column = 4kk + lane>>4) from the staged features; the N x ncols right operand is staged per
@@ -69,12 +69,14 @@ template <typename Fn> __device__ __forceinline__ void pair_mfma_each_column(int
         }
 }
 
-// stage_rows(F, g0, fr): the features / LS of the 128 rows from g0 into fr [F][128], zeros beyond the row source's end.  The rows
-// may come from another set of individuals than the columns (k_new.hip: new individuals against the training grid) — then
-// WK must be false: e_rc needs the rows' T.  Row block = blockIdx.x.
-template <int FREG, bool WK, int BIN, typename StageRows, typename StageX, typename Store>
-__device__ __forceinline__ void pair_mfma_body_rows(const SampleGrid& a, long long s, int ncols, double* sm, StageRows&& stage_rows,
-                                                    StageX&& stage_x, Store&& store) {
+// stage_rows(F, g0, fr): the features / LS of the 128 rows from g0 into fr [F][128], zeros beyond the row source's end.
+// stage_cols(F, FS, c0, fc): those of the PM_CC individuals from c0 on the column side into fc [FS][PM_CC], zeros beyond that
+// side's end and in the rows F .. FS - 1; the column side has n individuals, padded to Np (a multiple of PM_CC).  Rows and columns
+// may come from different sets of individuals (k_new.hip: the new individuals and the training grid, either way round, or the
+// new individuals on both sides) — then WK must be false: e_rc needs both sides' T from `a`.  Row block = blockIdx.x.
+template <int FREG, bool WK, int BIN, typename StageRows, typename StageCols, typename StageX, typename Store>
+__device__ __forceinline__ void pair_mfma_body_sides(const SampleGrid& a, long long s, int ncols, double* sm, int n, int Np,
+                                                     StageRows&& stage_rows, StageCols&& stage_cols, StageX&& stage_x, Store&& store) {
     const int F = a.nU + a.nX;
     double* etab = sm;                       // [32] 2^(j/32): table-driven exp (gp_math.h)
     double* fr = etab + GP_EXP_TAB_DOUBLES;
@@ -85,7 +87,6 @@ __device__ __forceinline__ void pair_mfma_body_rows(const SampleGrid& a, long lo
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lq = lane >> 4;
     const int ib = blockIdx.x;
-    const int n = a.n, Np = a.nt * GP_TS;
 
     stage_rows(F, ib * GP_TS, fr);
     const double ys = a.p.yScale[s];
@@ -119,7 +120,7 @@ __device__ __forceinline__ void pair_mfma_body_rows(const SampleGrid& a, long lo
             }
         for (int c0 = 0; c0 < Np; c0 += PM_CC) {
             __syncthreads();
-            stage_scaled_features<PM_CC>(a, s, F, FS, c0, fc);
+            stage_cols(F, FS, c0, fc);
             if (WK && tid < PM_CC) tc[tid] = (c0 + tid < n) ? a.T[c0 + tid] : 0.0;
             for (int idx = tid; idx < PM_CC * PM_NL; idx += 256) {
                 const int cc = idx >> 6, ll = idx & 63;      // consecutive threads -> consecutive right-operand columns
@@ -176,6 +177,15 @@ __device__ __forceinline__ void pair_mfma_body_rows(const SampleGrid& a, long lo
 #pragma unroll
         for (int m = 0; m < 2; ++m) store(ib * GP_TS + 32 * wave + 16 * m + li, l0, nl, accB[m], accK[WK ? m : 0]);
     }
+}
+
+// the columns from the training grid, the rows from stage_rows (new_mean_mfma_kernel: the new individuals)
+template <int FREG, bool WK, int BIN, typename StageRows, typename StageX, typename Store>
+__device__ __forceinline__ void pair_mfma_body_rows(const SampleGrid& a, long long s, int ncols, double* sm, StageRows&& stage_rows,
+                                                    StageX&& stage_x, Store&& store) {
+    pair_mfma_body_sides<FREG, WK, BIN>(
+        a, s, ncols, sm, a.n, a.nt * GP_TS, stage_rows,
+        [&](int F, int FS, int c0, double* fc) { stage_scaled_features<PM_CC>(a, s, F, FS, c0, fc); }, stage_x, store);
 }
 
 // rows and columns from the same grid: the body of ite_mean_mfma_kernel and wsum_mfma_kernel

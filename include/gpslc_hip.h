@@ -548,6 +548,38 @@ int gpslc_predict_new(gpslc_ctx* ctx, int64_t S, const double* U, const double* 
                       const double* Xnew, const double* Unew, int32_t form, int32_t L, const double* doT,
                       const double* doT_base, double pred_noise, double* mean, double* var, double* cov);
 
+/* Weighted averages over NEW individuals: tau_g(l) = w_g' f*(l) for G weight columns over the m new individuals of
+ * gpslc_predict_new — the average effect in a target population that is not the sample (next year's cohort, another hospital, a
+ * re-weighted grid of profiles, a held-out fold), its subgroups and their differences — with the variance that var of
+ * gpslc_predict_new cannot give (the new individuals share one Gaussian process), and the joint covariance of the L levels.
+ * Arguments 2 - 15 are gpslc_predict_new's.  weights: m x G host, weights[i + m*g], every entry finite, used AS GIVEN (1/m: the
+ * population average; 1_A / |A|: a subgroup; a difference of two such columns: the difference of two groups with its correct
+ * variance; e_i: individual i).  Per sample, in the notation above and with joint_ll' of gpslc_predict_curve's forms:
+ *     bw*_g = B*' w_g (n)      beta_g = w_g' B** w_g      c_g(l) = cross(l) .* bw*_g      v_g(l) = L^-1 c_g(l)      z = L^-1 Y
+ *     meanW = v_g(l) . z      varW = (prior_l beta_g - v_g(l) . v_g(l)) + pred_noise (w_g . w_g)
+ *     covW(l, l') = joint_ll' beta_g - v_g(l) . v_g(l')   (l != l'; the diagonal is varW, copied)
+ * — w_g' mean and w_g' cov w_g of gpslc_predict_new, without its m x n tile workspace and without anything m x m: one pass over the
+ * m n pairs, one over the m^2 pairs and L G more right-hand sides of the factorisation that runs anyway.
+ * Outputs (host; each may be NULL, not all three): meanW, varW S x L x G — element (s, l, g) at s + S*(l + L*g); covW S x L x L x G —
+ * element (s, l, l', g) at s + S*(l + L*(l' + L*g)): the layouts of gpslc_predict_weighted / gpslc_predict_curve, so
+ * gpslc_curve_samples draws whole curves of the target population.  covW without varW: the device computes varW all the same.
+ * Exact identities: a zero column gives meanW == 0.0, varW == 0.0 and an all-0.0 covW block; a contrast with a == b gives meanW
+ * == 0.0, varW = pred_noise (w . w) and row and column l of covW 0.0 off the diagonal; every covW block is exactly symmetric and its
+ * diagonal bit-identical to varW.  A column's results do not depend on the other columns of the call — to the bits among calls
+ * of at most 127 right-hand sides (L G <= 127, one augmented tile row); a larger call takes z . v and v . v from the Schur tiles
+ * like every weighted call, and agrees with a smaller one in all but the last bits.  Every output is bit-reproducible and
+ * independent of chunking, streams and the factorisation schedule.  A sample whose factorisation breaks down
+ * gets NaN in all its outputs; the call returns the first failing pivot and gpslc_last_info every sample's.
+ * Errors: -9 ... -15 as gpslc_predict_new; G < 1: -16; weights NULL or non-finite: -17; pred_noise non-finite: -18; all outputs
+ * NULL: -19.  fp64 only (GPSLC_ERR_UNSUPPORTED on a GPSLC_FLAG_FP32_KERNEL ctx).  Not offered: a _dev variant, sharding, draws per
+ * individual, cross-covariances between weight columns (a difference of groups is a weight column), individuals of unseen
+ * objects.   */
+int gpslc_predict_new_weighted(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                               const double* tyLS, const double* yScale, const double* yNoise, int64_t m,
+                               const double* Xnew, const double* Unew, int32_t form, int32_t L, const double* doT,
+                               const double* doT_base, int32_t G, const double* weights, double pred_noise,
+                               double* meanW, double* varW, double* covW);
+
 /* The same call sharded over several GPUs of one node: what the loop of predictCounterfactualEffects (src/prediction.jl:30-33)
  * over the posterior samples (src/estimation.jl:78-84) becomes when the ensemble is partitioned.  ctxs[0..nctx) are
  * DISTINCT contexts created with the same (n, nX, nU), one per device (gpslc_create(&ctx_k, device_k, ...)), each holding the data

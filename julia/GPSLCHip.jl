@@ -244,6 +244,29 @@ function predict_new(c::Ctx, S::Integer, U, uyLS, xyLS, tyLS::Vector{Float64}, y
     mean, var, cov
 end
 
+"""Weighted averages over m individuals who are not in the data (gpslc_predict_new_weighted): `(meanW, varW, covW)` — meanW and
+varW S x L x G, covW S x L x L x G (`nothing` unless asked for) — of w_g' f* for the G columns of `weights` (m x G, used as
+given: 1/m is the average over the target population, a difference of two group columns the difference of the groups with its
+correct variance), with `predict_new`'s forms, `Xnew` and `Unew`.  No m x m array exists anywhere; the layouts are
+`predict_curve`'s, so `curve_samples(meanW, covW, spp)` draws whole curves.  A failed factorisation throws PosDefException."""
+function predict_new_weighted(c::Ctx, S::Integer, U, uyLS, xyLS, tyLS::Vector{Float64}, yScale::Vector{Float64},
+                              yNoise::Vector{Float64}, Xnew, Unew, form::Integer, doT::Vector{Float64}, doT_base,
+                              weights::Matrix{Float64}, pred_noise::Float64; want_cov::Bool=false)
+    L, m, G = length(doT), size(weights, 1), size(weights, 2)
+    Xnew === nothing || size(Xnew, 1) == m || throw(DimensionMismatch("weights has $m rows, Xnew $(size(Xnew, 1))"))
+    Unew === nothing || size(Unew, 1) == m || throw(DimensionMismatch("weights has $m rows, Unew $(size(Unew, 1))"))
+    Uf, uy, xy, Xn, Un, base = f64(U), f64(uyLS), f64(xyLS), f64(Xnew), f64(Unew), f64(doT_base)
+    mW, vW = Array{Float64}(undef, S, L, G), Array{Float64}(undef, S, L, G)
+    cW = want_cov ? Array{Float64}(undef, S, L, L, G) : nothing
+    GC.@preserve Uf uy xy tyLS yScale yNoise Xn Un doT base weights mW vW cW check(c, ccall((:gpslc_predict_new_weighted, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(Uf), ptr(uy), ptr(xy), pointer(tyLS), pointer(yScale), pointer(yNoise), m, ptr(Xn), ptr(Un), form, L,
+        pointer(doT), ptr(base), G, pointer(weights), pred_noise, pointer(mW), pointer(vW), ptr(cW)))
+    mW, vW, cW
+end
+
 """log N(target; 0, scale exp.(rbfKernelLog(F, F, ls)) + noise I) for S parameter sets: :X => k => :X, :T / :logitT."""
 function gp_logpdf(c::Ctx, S::Integer, nF::Integer, F::Array{Float64}, f_shared::Bool, ls::Array{Float64},
                    scale::Vector{Float64}, noise::Vector{Float64}, target::Array{Float64}, t_shared::Bool)
@@ -1311,6 +1334,28 @@ function sampleEffectCurve(g::GPSLCObject, doTs::AbstractVector{<:Real}; samples
                             GPSLCHip.curve_samples(mW, cW, samplesPerPosterior; seed=UInt64(seed))
     out = permutedims(reshape(dr, L, samplesPerPosterior * S, G), (3, 1, 2))
     vec ? out[1, :, :] : out
+end
+
+# ---- averages over a target population that is not the sample (gpslc_predict_new_weighted; not in the reference) --------------
+"""averageNew(g, doTs, Xnew, Unew; weights, baseline, slope, want_cov) -> (mean S x L [x G], var S x L [x G][, cov S x L x L [x G]]):
+the weighted average over m new individuals (`Xnew` m x nX or `nothing`, `Unew` m x nU x S or `nothing`) of the outcome f*(doTs[l]),
+the contrast with `baseline=` or the slope, with its variance and the joint covariance of the levels.  `weights = nothing`: 1/m; a
+length-m vector or an m x G matrix as in SATEDistributions (Bool: group masks)."""
+function averageNew(g::GPSLCObject, doTs::AbstractVector{<:Real}, Xnew, Unew; weights=nothing, baseline=nothing,
+                    slope::Bool=false, want_cov::Bool=false)
+    (slope && baseline !== nothing) &&
+        throw(ArgumentError("slope=true cannot be combined with baseline=: the slope is a derivative at one level, not a contrast"))
+    lv = Vector{Float64}(doTs)
+    m = Xnew !== nothing ? size(Xnew, 1) : Unew !== nothing ? size(Unew, 1) : 1
+    Wm = weights === nothing ? fill(1.0 / m, m, 1) : _weights(weights, m)
+    p = posterior_pack(g)
+    form = slope ? GPSLCHip.NEW_SLOPE : baseline === nothing ? GPSLCHip.NEW_OUTCOME : GPSLCHip.NEW_CONTRAST
+    mW, vW, cW = GPSLCHip.predict_new_weighted(ctx(g), length(p.tyLS), p.U, p.uyLS, p.xyLS, p.tyLS, p.yScale, p.yNoise, Xnew, Unew,
+                                               form, lv, _curve_baseline(baseline, length(lv)), Wm,
+                                               g.hyperparams.predictionCovarianceNoise; want_cov=want_cov)
+    vec = !(weights isa AbstractMatrix)
+    out = vec ? (mW[:, :, 1], vW[:, :, 1]) : (mW, vW)
+    want_cov ? (out..., vec ? cW[:, :, :, 1] : cW) : out
 end
 
 function summarizeEstimates(samples; savetofile::String="", credible_interval::Float64=0.90)                        # :129-149
