@@ -5,6 +5,7 @@
 #include "gpslc_internal.h"
 #include "batch_plan.h"
 #include "tile_launch.h"
+#include "dev_mem.h"
 #include "sm_layout.h"
 #include "philox.h"
 
@@ -35,74 +36,53 @@ struct HipFail {
         if (_e != hipSuccess) throw HipFail{_e, #x, __LINE__};        \
     } while (0)
 
-struct Arena {
-    char* base = nullptr;
-    size_t bytes = 0;
-    size_t off = 0;
-    void reset() { off = 0; }
-    template <class T>
-    T* take(size_t count) {
-        size_t a = (off + 255) & ~size_t(255);
-        size_t need = count * sizeof(T);
-        if (a + need > bytes) throw std::bad_alloc();
-        off = a + need;
-        return reinterpret_cast<T*>(base + a);
-    }
-};
-
-// Growable device staging pool of a ctx (host-pointer entry points: uploads, outputs, info words).  take() never
-// moves earlier allocations: when the current block is full a new one is chained; the next reset() merges the
-// chain into one block of the total size, so a steady-state call sequence allocates nothing.
-struct PoolArena {
-    struct Block { char* base; size_t bytes; };
-    std::vector<Block> blocks;
-    size_t off = 0;
-    void release() {
-        for (auto& b : blocks) (void)hipFree(b.base);
-        blocks.clear();
-        off = 0;
-    }
-    void reset() {
-        if (blocks.size() > 1) {
-            size_t total = 0;
-            for (auto& b : blocks) total += b.bytes;
-            (void)hipDeviceSynchronize();
-            release();
-            add_block(total);
-        }
-        off = 0;
-    }
-    void add_block(size_t bytes) {
+// The two memory policies of dev_mem.h.  A failed allocation also clears the runtime's sticky error.
+struct DeviceMem {
+    static void* alloc(size_t bytes) {
         void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); throw std::bad_alloc(); }
-        blocks.push_back(Block{static_cast<char*>(p), bytes});
-        off = 0;
+        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        return p;
     }
-    template <class T>
-    T* take(size_t count) {
-        const size_t need = std::max<size_t>(count * sizeof(T), 8);
-        size_t a = (off + 255) & ~size_t(255);
-        if (blocks.empty() || a + need > blocks.back().bytes) {
-            add_block(std::max<size_t>((need + 255) & ~size_t(255), size_t(1) << 20));
-            a = 0;
-        }
-        off = a + need;
-        return reinterpret_cast<T*>(blocks.back().base + a);
+    static void release(void* p) { (void)hipFree(p); }
+    static void quiesce() { HC(hipDeviceSynchronize()); }
+};
+struct PinnedMem {      // pinned, device-visible host memory
+    static void* alloc(size_t bytes) {
+        void* p = nullptr;
+        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        return p;
     }
+    static void release(void* p) { (void)hipHostFree(p); }
+    static void quiesce() { HC(hipDeviceSynchronize()); }
+};
+template <class T = char> using DevBuffer = Buffer<DeviceMem, T>;
+using PinnedBuffer = Buffer<PinnedMem>;
+
+// a HIP stream, owned: stands where its hipStream_t stood
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(std::exchange(o.s, nullptr)) {}
+    Stream& operator=(Stream&& o) noexcept { std::swap(s, o.s); return *this; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
 };
 
-struct DevBuf {   // RAII device allocation for the host-pointer entry points
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    void alloc(size_t bytes) {
-        if (bytes == 0) bytes = 8;
-        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; throw std::bad_alloc(); }
+// the two HIP events around one profiled launch region, owned
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() = default;
+    EventPair(EventPair&& o) noexcept : a(std::exchange(o.a, nullptr)), b(std::exchange(o.b, nullptr)) {}
+    EventPair& operator=(EventPair&& o) noexcept { std::swap(a, o.a); std::swap(b, o.b); return *this; }
+    ~EventPair() {
+        for (hipEvent_t e : {a, b})
+            if (e) (void)hipEventDestroy(e);
     }
-    template <class T> T* as() { return static_cast<T*>(p); }
+    bool create() { return hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess; }
 };
 
 struct ProfRec {
-    hipEvent_t a, b;
+    EventPair ev;
     double flop;
     int cls;     // kernel class, see gpslc_profile_get_class (include/gpslc_hip.h)
 };
@@ -113,18 +93,30 @@ constexpr int kProfClasses = 5;
 struct TaskList {
     int nt = 0, back = 0, nb = 0, G = 0, rows = 0;
     bool aug_full = false;
-    unsigned* dev = nullptr;
+    DevBuffer<unsigned> dev;
     long long ntasks = 0;
     unsigned long long used = 0;
 };
 
 // one HIP stream of a ctx and what its launches use: the chunks of a call alternate over the slots
 struct StreamSlot {
-    hipStream_t st = nullptr;
-    Arena arena;
-    int* queue = nullptr;          // ticket-counter block (16 ints), see GemmArgs::queue
-    int* sync = nullptr;           // progress words of the persistent factorisation launch (PotrfTaskArgs::sync)
-    size_t sync_ints = 0;
+    Stream st;
+    Arena<DeviceMem> arena;
+    DevBuffer<int> queue;          // ticket-counter block (16 ints), see GemmArgs::queue
+    DevBuffer<int> sync;           // progress words of the persistent factorisation launch (PotrfTaskArgs::sync), grown on demand
+};
+
+// The last dense covariance handed to gpslc_mvn_logpdf / gpslc_mvn_draw (SigmaU is constant per data set).  n <= 640 (both
+// paths can run): the matrix itself, always, whichever path the hand-over took; the tiled factor is built from it when a
+// call on the tiled path finds it missing or older (tiles_gen != gen).  n > 640: only the tiled factor.
+struct MvnCache {
+    DevBuffer<double> tiles;     // tiled factor (substitution-based: no inverted diagonal blocks are kept)
+    DevBuffer<double> dense;     // n <= 640: the dense covariance itself (the single-workgroup path refactorises it in LDS)
+    uint64_t gen = 0;            // hand-overs so far
+    uint64_t tiles_gen = 0;      // the hand-over `tiles` was factorised from (0 = none)
+    double logdet = 0.0;         // of `tiles`
+    int info = 0;                // LAPACK-style info of the latest covariance
+    bool valid = false;
 };
 
 }  // namespace
@@ -135,7 +127,7 @@ struct gpslc_ctx {
     int nX = 0, nU = 0;
     uint32_t flags = 0;
     int nt = 0;
-    double *dX = nullptr, *dT = nullptr, *dY = nullptr;
+    DevBuffer<double> dX, dT, dY;
     bool has_data = false;
     bool binary_t = false;   // every treatment is exactly 0 or 1 (detected in gpslc_set_data)
     int max_batch = 0;   // 0 = auto
@@ -148,7 +140,7 @@ struct gpslc_ctx {
     // when a poll exceeds its bound, and whether a call has used it (the word is then checked when the call's streams have drained)
     std::vector<TaskList> task_lists;
     unsigned long long task_clock = 0;
-    int* task_timeout = nullptr;
+    DevBuffer<int> task_timeout;
     bool task_used = false;        // a persistent launch ran since the time-out word was last read (check_task_timeout)
     int task_min_nt = 2, task_max_nt = TASK_MAX_NT;   // tile counts in this range take the persistent launch (128 < N <= 4096: with
                                             // groups of 32 it wins at every tile count the descriptor can hold — N = 256 +1..3 %, 384 +6 %, 512 +10 %,
@@ -161,30 +153,20 @@ struct gpslc_ctx {
     int task_rows = 2;             // consecutive tile rows of a column per strip task up to 8 tiles per side (beyond: one — long K
                                    // loops amortise the task's fetch / acquire / publish by themselves, and finer tasks balance
                                    // better: N = 1536 .. 4096 +0.6 .. 1.2 %, profiles/r06_ab_experiments.md §1d)
-    Arena scratch;                 // call-level buffers (internal MeanITE of a draws-only call, ...)
-    PoolArena io;                  // staging of the host-pointer entry points and per-call info words
+    Arena<DeviceMem> scratch;      // call-level buffers (internal MeanITE of a draws-only call, ...)
+    PoolArena<DeviceMem> io;       // staging of the host-pointer entry points and per-call info words
     // single-launch small-n node scores (k_small.hip): pinned, device-visible host staging (descriptors, inputs,
     // results) and host copies of the ctx's data for assembling the :Y node's feature block
-    char* pin = nullptr;
-    size_t pin_bytes = 0;
+    PinnedBuffer pin;
     // two pinned bounce chunks for large device -> pageable-host hand-overs (copy_out_large), allocated on first use
-    char* bounce[2] = {nullptr, nullptr};
+    PinnedBuffer bounce[2];
     std::vector<double> hX, hT, hY;
     std::vector<double> stage_f, stage_rest;   // host staging of gpslc_nodes_logpdf's batched pass (grown, never shrunk)
     std::string err;
     std::vector<int32_t> last_info;
-    // the last dense covariance handed to gpslc_mvn_logpdf / gpslc_mvn_draw (SigmaU is constant per data set).  n <= 640 (both
-    // paths can run): the matrix itself, always, whichever path the hand-over took; the tiled factor is built from it when a
-    // call on the tiled path finds it missing or older (mvn_tiles_gen != mvn_gen).  n > 640: only the tiled factor.
-    double* mvn_tiles = nullptr;     // tiled factor (substitution-based: no inverted diagonal blocks are kept)
-    double* mvn_dense = nullptr;     // n <= 640: the dense covariance itself (the single-workgroup path refactorises it in LDS)
-    uint64_t mvn_gen = 0;            // hand-overs so far
-    uint64_t mvn_tiles_gen = 0;      // the hand-over mvn_tiles was factorised from (0 = none)
-    double mvn_logdet = 0.0;         // of mvn_tiles
-    int mvn_info = 0;                // LAPACK-style info of the latest covariance
-    bool mvn_valid = false;
+    MvnCache mvn;
     // L2-blocked visiting orders of the lower-triangular tile sets, keyed by the triangle size m
-    std::vector<unsigned short*> tri_order;
+    std::vector<DevBuffer<unsigned short>> tri_order;
     // profiling of the dominant kernel
     std::vector<ProfRec> prof;
     size_t prof_used = 0;
@@ -207,15 +189,15 @@ struct ProfScope {
         if (!(c->flags & GPSLC_FLAG_PROFILE)) return;
         if (c->prof_used == c->prof.size()) {
             ProfRec n{};
-            if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) return;
-            c->prof.push_back(n);
+            if (!n.ev.create()) return;
+            c->prof.push_back(std::move(n));
         }
         r = &c->prof[c->prof_used++];
         r->flop = work;
         r->cls = cls;
-        (void)hipEventRecord(r->a, st);
+        (void)hipEventRecord(r->ev.a, st);
     }
-    ~ProfScope() { if (r) (void)hipEventRecord(r->b, st); }
+    ~ProfScope() { if (r) (void)hipEventRecord(r->ev.b, st); }
 };
 
 int fail_hip(gpslc_ctx* c, const HipFail& f) {
@@ -226,35 +208,19 @@ int fail_hip(gpslc_ctx* c, const HipFail& f) {
     return GPSLC_ERR_HIP;
 }
 
-void arena_reserve(gpslc_ctx* c, Arena& a, size_t bytes) {
-    if (a.bytes >= bytes) return;
-    if (a.base) {
-        HC(hipDeviceSynchronize());
-        HC(hipFree(a.base));
-        a.base = nullptr;
-        a.bytes = 0;
-    }
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        throw std::bad_alloc();
-    }
-    a.base = static_cast<char*>(p);
-    a.bytes = bytes;
-    (void)c;
-}
-
 void ensure_streams(gpslc_ctx* c) {
     if (!c->task_timeout) {
-        HC(hipMalloc((void**)&c->task_timeout, sizeof(int)));
-        HC(hipMemset(c->task_timeout, 0, sizeof(int)));
+        DevBuffer<int> w;
+        w.reserve(sizeof(int));
+        HC(hipMemset(w, 0, sizeof(int)));
+        c->task_timeout = std::move(w);
     }
     while ((int)c->slots.size() < c->nstreams) {
-        StreamSlot& s = c->slots.emplace_back();
-        HC(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-        HC(hipMalloc((void**)&s.queue, 16 * sizeof(int)));
+        StreamSlot s;       // joins the ctx complete or not at all
+        HC(hipStreamCreateWithFlags(&s.st.s, hipStreamNonBlocking));
+        s.queue.reserve(16 * sizeof(int));
         HC(hipMemset(s.queue, 0, 16 * sizeof(int)));
+        c->slots.push_back(std::move(s));
     }
 }
 
@@ -268,18 +234,18 @@ void rearm_queue(StreamSlot& s) { HC(hipMemsetAsync(s.queue, 0, 16 * sizeof(int)
 // launch, where armed (words != 0), dump() waits for it and writes the words to the file its caller opened (null: nothing is
 // written); the buffer goes with the capture
 struct StampCapture {
-    DevBuf buf;
+    DevBuffer<unsigned long long> buf;
     size_t words = 0;
     unsigned long long* arm(size_t n) {
-        buf.alloc((words = n) * 8);
-        HC(hipMemset(buf.p, 0, n * 8));
-        return buf.as<unsigned long long>();
+        buf.reserve(std::max<size_t>((words = n) * 8, 8));
+        HC(hipMemset(buf, 0, n * 8));
+        return buf;
     }
     void dump(hipStream_t st, FILE* file) {
         std::unique_ptr<FILE, int (*)(FILE*)> f(file, fclose);      // closed on every way out
         HC(hipStreamSynchronize(st));
         std::vector<unsigned long long> h(words);
-        HC(hipMemcpy(h.data(), buf.p, words * 8, hipMemcpyDeviceToHost));
+        HC(hipMemcpy(h.data(), buf, words * 8, hipMemcpyDeviceToHost));
         if (f) fwrite(h.data(), 8, words, f.get());
     }
 };
@@ -334,7 +300,7 @@ void gemm(gpslc_ctx* c, const GemmArgs& g0, StreamSlot& s, int prof_base) {
 void prof_collect(gpslc_ctx* c) {
     for (size_t i = 0; i < c->prof_used; ++i) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->prof[i].a, c->prof[i].b) == hipSuccess) {
+        if (hipEventElapsedTime(&ms, c->prof[i].ev.a, c->prof[i].ev.b) == hipSuccess) {
             const int k = c->prof[i].cls;
             c->prof_ms[k] += ms;
             c->prof_flop[k] += c->prof[i].flop;
@@ -347,14 +313,13 @@ void prof_collect(gpslc_ctx* c) {
 // the device copy of tri_order_pairs(m) (tile_launch.h), made once per ctx and m; null for m <= 2 (tri_decode's order serves)
 const unsigned short* tri_order(gpslc_ctx* c, int m) {
     if (m <= 2) return nullptr;
-    if ((int)c->tri_order.size() <= m) c->tri_order.resize(m + 1, nullptr);
+    if ((int)c->tri_order.size() <= m) c->tri_order.resize(m + 1);
     if (c->tri_order[m]) return c->tri_order[m];
     const std::vector<unsigned short> h = tri_order_pairs(m);
-    unsigned short* d = nullptr;
-    HC(hipMalloc((void**)&d, h.size() * sizeof(unsigned short)));
+    DevBuffer<unsigned short> d;        // kept only once the upload has succeeded
+    d.reserve(h.size() * sizeof(unsigned short));
     HC(hipMemcpy(d, h.data(), h.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    c->tri_order[m] = d;
-    return d;
+    return c->tri_order[m] = std::move(d);
 }
 
 // ---- the persistent factorisation launch (potrf_tasks_kernel, k_tilegemm.hip): task order = build_task_list, task_list.h ----
@@ -365,17 +330,16 @@ const TaskList& task_list_for(gpslc_ctx* c, int nt, int back, int nb, int G, int
         size_t v = 0;
         for (size_t i = 1; i < c->task_lists.size(); ++i)
             if (c->task_lists[i].used < c->task_lists[v].used) v = i;
-        HC(hipDeviceSynchronize());
-        HC(hipFree(c->task_lists[v].dev));
+        DeviceMem::quiesce();
         c->task_lists.erase(c->task_lists.begin() + (long)v);
     }
     TaskList t;
     t.nt = nt; t.back = back; t.nb = nb; t.G = G; t.rows = rows; t.aug_full = aug_full;
     std::vector<unsigned> h = build_task_list(nt, back, nb, G, rows, aug_full, &t.ntasks, /*merge_diag=*/1);
-    HC(hipMalloc((void**)&t.dev, h.size() * sizeof(unsigned)));
+    t.dev.reserve(h.size() * sizeof(unsigned));
     HC(hipMemcpy(t.dev, h.data(), h.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     t.used = ++c->task_clock;
-    c->task_lists.push_back(t);
+    c->task_lists.push_back(std::move(t));
     return c->task_lists.back();
 }
 
@@ -400,15 +364,7 @@ void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv
     hipStream_t st = s.st;
     rearm_queue(s);
     const size_t ints = TASK_SYNC_HDR + (size_t)TASK_SYNC_STRIDE * nb;
-    if (s.sync_ints < ints) {
-        if (s.sync) {
-            HC(hipDeviceSynchronize());
-            HC(hipFree(s.sync));
-            s.sync = nullptr;
-        }
-        HC(hipMalloc((void**)&s.sync, ints * sizeof(int)));
-        s.sync_ints = ints;
-    }
+    s.sync.reserve(ints * sizeof(int));
     const TaskList& tl = task_list_for(c, nt, back_alpha ? 1 : 0, nb, c->task_group,
                                        std::max(1, std::min(4, nt > 8 ? 1 : c->task_rows)), short_rows > 32);
     HC(hipMemsetAsync(s.sync, 0, ints * sizeof(int), st));
@@ -654,7 +610,7 @@ BatchPlan auto_batch(gpslc_ctx* c, int64_t S, int L, size_t per_sample_bytes, si
     size_t free_b = 0, tot_b = 0;
     HC(hipMemGetInfo(&free_b, &tot_b));
     size_t have = 0;
-    for (auto& sl : c->slots) have += sl.arena.bytes;
+    for (auto& sl : c->slots) have += sl.arena.bytes();
     // the AUTOMATIC chunk also stays under 30 % of the device's memory (arenas never shrink, and the host process usually
     // shares the device: torch's caching allocator under sharded.py / bench.py, other contexts of gpslc_predict_multi on one
     // GPU); 1,024 matrices at N = 4096 are 28 %.  gpslc_set_tuning(max_batch) may ask for more: then only what is free counts.
@@ -717,7 +673,7 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     ChunkBytes by;
     Chunk none;
     Chunk& b = ch ? *ch : none;
-    Arena* ar = ch ? &ch->s->arena : nullptr;
+    Arena<DeviceMem>* ar = ch ? &ch->s->arena : nullptr;
     auto take = [&](size_t per_sample) -> double* {
         by.per_sample += per_sample * 8;
         return ar ? ar->take<double>((size_t)b.nb * per_sample) : nullptr;
@@ -1129,10 +1085,10 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     const BatchPlan plan = auto_batch(c, io.post.S, sh.L, by.per_sample, by.per_pair, by.per_level);
     const int Bt = (int)plan.Bt, Bb = (int)plan.Bb;      // Bb: (sample, level) pairs per unit-B sub-batch, no more than the call has
     const size_t need = (size_t)Bt * by.per_sample + plan.fixed;
-    for (int i = 0; i < c->nstreams; ++i) arena_reserve(c, c->slots[i].arena, need);
+    for (int i = 0; i < c->nstreams; ++i) c->slots[i].arena.reserve(need);
     // internal MeanITE buffer when the caller did not ask for it but the draws need it
     if (sh.want_draws && !io.out.meanITE) {
-        arena_reserve(c, c->scratch, std::max(c->scratch.bytes, (size_t)sh.n * io.post.S * sh.L * 8 + (1 << 16)));
+        c->scratch.reserve((size_t)sh.n * io.post.S * sh.L * 8 + (1 << 16));
         c->scratch.reset();
         io.out.meanITE = c->scratch.take<double>((size_t)sh.n * io.post.S * sh.L);
     }
@@ -1192,10 +1148,10 @@ int bad_arg(gpslc_ctx* c, int k, const char* what) {
     return -k;
 }
 
-double* up(DevBuf& b, const double* host, size_t count) {
-    b.alloc(count * sizeof(double));
-    if (count) HC(hipMemcpy(b.p, host, count * sizeof(double), hipMemcpyHostToDevice));
-    return b.as<double>();
+double* up(DevBuffer<double>& b, const double* host, size_t count) {
+    b.reserve(std::max<size_t>(count * sizeof(double), 8));
+    if (count) HC(hipMemcpy(b, host, count * sizeof(double), hipMemcpyHostToDevice));
+    return b;
 }
 // upload into the ctx's staging pool (no allocation in steady state)
 double* up(gpslc_ctx* c, const double* host, size_t count) {
@@ -1245,16 +1201,6 @@ HostNode dense_node(const double* dev_cov, double covscale, const double* target
 constexpr double kLog2Pi = 1.8378770664093454835606594728112;
 inline double gauss_logpdf(size_t n, double logdet, double quad) { return -0.5 * ((double)n * kLog2Pi + logdet + quad); }
 
-void pin_reserve(gpslc_ctx* c, size_t bytes) {
-    if (c->pin_bytes >= bytes) return;
-    if (c->pin) { HC(hipDeviceSynchronize()); HC(hipHostFree(c->pin)); c->pin = nullptr; c->pin_bytes = 0; }
-    void* p = nullptr;
-    bytes = (bytes + 4095) & ~size_t(4095);
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); throw std::bad_alloc(); }
-    c->pin = static_cast<char*>(p);
-    c->pin_bytes = bytes;
-}
-
 // A node score can run as ONE workgroup of one launch: matrix resident in LDS (n <= 160..176), or the left-looking
 // kernel with the finished block columns in an L2-resident scratch (n <= 640).  The latter keeps one CU busy per node
 // for 100+ us: worth it up to a few hundred nodes per call, beyond that the batched tiled path wins.
@@ -1292,16 +1238,12 @@ void copy_out_rows(gpslc_ctx* c, void* dst, size_t dpitch, const void* src_dev, 
     }
     if (plain) { direct(); return; }
     ensure_streams(c);
-    for (int i = 0; i < 2; ++i)
-        if (!c->bounce[i]) {
-            void* p = nullptr;
-            if (hipHostMalloc(&p, kBounceBytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                direct();                             // no pinned memory to be had: the plain way
-                return;
-            }
-            c->bounce[i] = static_cast<char*>(p);
-        }
+    try {
+        for (PinnedBuffer& b : c->bounce) b.reserve(kBounceBytes);
+    } catch (const std::bad_alloc&) {
+        direct();                                     // no pinned memory to be had: the plain way
+        return;
+    }
     hipStream_t st = c->slots[0].st;
     const size_t nchunk = (bytes + kBounceBytes - 1) / kBounceBytes;
     const unsigned nthr = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
@@ -1365,11 +1307,11 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
     const size_t off_data = off_out + NodeStage::header((size_t)count) * sizeof(double);
     const size_t off_draw = off_data + doubles * sizeof(double);          // [count][n] draws (pinned, written by the kernel)
     const size_t off_grad = off_draw + (draw_out ? (size_t)count * n * sizeof(double) : 0);     // the gradient launch's result block
-    pin_reserve(c, off_grad + gdoubles * sizeof(double));
+    c->pin.reserve((off_grad + gdoubles * sizeof(double) + 4095) & ~size_t(4095));
     void* dbase = nullptr;
     HC(hipHostGetDevicePointer(&dbase, c->pin, 0));
     char* dev = static_cast<char*>(dbase);
-    SmallNode* hn = reinterpret_cast<SmallNode*>(c->pin);
+    SmallNode* hn = c->pin.as<SmallNode>();
     double* hout = reinterpret_cast<double*>(c->pin + off_out);
     double* hd = reinterpret_cast<double*>(c->pin + off_data);
     double* dd = reinterpret_cast<double*>(dev + off_data);
@@ -1407,7 +1349,7 @@ int small_nodes_logpdf(gpslc_ctx* c, int count, const HostNode* nodes, double* l
     if (grad && small_grad_lds_bytes((int)n, nF_max) > kLdsCapBytes) throw std::runtime_error("gradient launch beyond its LDS image");
     if (!in_lds) {       // mid-size kernel: per-node scratch for the finished block columns and the scaled features
         const size_t per = (mid_gp_scratch_doubles((int)n, nF_max) + 31) & ~size_t(31);
-        arena_reserve(c, c->scratch, per * (size_t)count * sizeof(double) + 256);
+        c->scratch.reserve(per * (size_t)count * sizeof(double) + 256);
         c->scratch.reset();
         a.scratch = c->scratch.take<double>(per * (size_t)count);
         a.scratch_stride = (long long)per;
@@ -1499,9 +1441,9 @@ int gpslc_create(gpslc_ctx** out, int device, int64_t n, int32_t nX, int32_t nU,
             set_err(c, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
             return GPSLC_ERR_NODEVICE;
         }
-        HC(hipMalloc((void**)&c->dX, sizeof(double) * std::max<int64_t>(1, n * nX)));
-        HC(hipMalloc((void**)&c->dT, sizeof(double) * n));
-        HC(hipMalloc((void**)&c->dY, sizeof(double) * n));
+        c->dX.reserve(sizeof(double) * std::max<int64_t>(1, n * nX));
+        c->dT.reserve(sizeof(double) * n);
+        c->dY.reserve(sizeof(double) * n);
         // defined contents before gpslc_set_data: the node-score entry points that bring their own features and
         // target (gpslc_gp_logpdf, gpslc_mvn_logpdf) work on a ctx without data
         HC(hipMemset(c->dX, 0, sizeof(double) * std::max<int64_t>(1, n * nX)));
@@ -1519,23 +1461,6 @@ int gpslc_destroy(gpslc_ctx* c) {
     if (!c) return GPSLC_OK;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (auto& s : c->slots) {
-        if (s.st) (void)hipStreamDestroy(s.st);
-        (void)hipFree(s.arena.base); (void)hipFree(s.queue); (void)hipFree(s.sync);     // hipFree(nullptr) is a no-op
-    }
-    if (c->task_timeout) (void)hipFree(c->task_timeout);
-    for (auto& t : c->task_lists) if (t.dev) (void)hipFree(t.dev);
-    if (c->scratch.base) (void)hipFree(c->scratch.base);
-    c->io.release();
-    if (c->pin) (void)hipHostFree(c->pin);
-    for (char* b : c->bounce) if (b) (void)hipHostFree(b);
-    for (auto& r : c->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    for (auto p : c->tri_order) if (p) (void)hipFree(p);
-    if (c->mvn_tiles) (void)hipFree(c->mvn_tiles);
-    if (c->mvn_dense) (void)hipFree(c->mvn_dense);
-    if (c->dX) (void)hipFree(c->dX);
-    if (c->dT) (void)hipFree(c->dT);
-    if (c->dY) (void)hipFree(c->dY);
     delete c;
     return GPSLC_OK;
 }
@@ -2322,79 +2247,110 @@ int nodes_score(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, int nF_max
 bool mvn_dual(const gpslc_ctx* c) { return fast_path_ok(c, 0, 1); }
 
 // the tiled factor of the device covariance dcov (substitution-based: SigmaU * uNoise is near-singular by construction, 1e-13
-// jitter, src/utils.jl:17-33); mvn_logdet / mvn_info from it, and it now stands for hand-over mvn_gen
+// jitter, src/utils.jl:17-33); mvn.logdet / mvn.info from it, and it now stands for hand-over mvn.gen
 void mvn_factor_tiles(gpslc_ctx* c, const double* dcov) {
     ensure_streams(c);
     const int nt = c->nt;
     const long long nlow = (long long)nt * (nt + 1) / 2;
     StreamSlot& slot = c->slots[0];
     hipStream_t st = slot.st;
-    c->mvn_tiles_gen = 0;
-    if (!c->mvn_tiles) HC(hipMalloc((void**)&c->mvn_tiles, (size_t)nlow * GP_TSQ * 8));
-    DevBuf old, oq, info;
-    old.alloc(8); oq.alloc(8); info.alloc(sizeof(int));
-    HC(hipMemsetAsync(info.p, 0, sizeof(int), st));
-    TRef M = lower_ref(c->mvn_tiles, nlow * GP_TSQ);
+    c->mvn.tiles_gen = 0;
+    c->mvn.tiles.reserve((size_t)nlow * GP_TSQ * 8);
+    DevBuffer<double> old, oq;
+    DevBuffer<int> info;
+    old.reserve(8); oq.reserve(8); info.reserve(sizeof(int));
+    HC(hipMemsetAsync(info, 0, sizeof(int), st));
+    TRef M = lower_ref(c->mvn.tiles, nlow * GP_TSQ);
     launch_dense_load(DenseLoadArgs{dcov, (int)c->n, nt, M}, st);
-    factor_robust(c, slot, M, nt, info.as<int>(), 0, 1, 0);
-    launch_quad_rows(QuadRowsArgs{M, (int)c->n, nt, 0, 0, old.as<double>(), oq.as<double>()}, st);
+    factor_robust(c, slot, M, nt, info, 0, 1, 0);
+    launch_quad_rows(QuadRowsArgs{M, (int)c->n, nt, 0, 0, old, oq}, st);
     HC(hipStreamSynchronize(st));
     HC(hipGetLastError());
-    HC(hipMemcpy(&c->mvn_logdet, old.p, 8, hipMemcpyDeviceToHost));
-    HC(hipMemcpy(&c->mvn_info, info.p, sizeof(int), hipMemcpyDeviceToHost));
-    c->mvn_tiles_gen = c->mvn_gen;
+    HC(hipMemcpy(&c->mvn.logdet, old, 8, hipMemcpyDeviceToHost));
+    HC(hipMemcpy(&c->mvn.info, info, sizeof(int), hipMemcpyDeviceToHost));
+    c->mvn.tiles_gen = c->mvn.gen;
+}
+
+// the tiled solve of gpslc_mvn_logpdf against the cached factor: z_s = L^-1 x_s for all S vectors (host, n x S) as the rows of
+// W = X^T L^-T, a tile-level solve; returns |z_s|^2 (device, S values in the ctx's staging pool), the stream drained
+const double* mvn_solve_tiles(gpslc_ctx* c, int64_t S, const double* x) {
+    ensure_streams(c);
+    const int n = (int)c->n, nt = c->nt;
+    const long long nlow = (long long)nt * (nt + 1) / 2;
+    StreamSlot& slot = c->slots[0];
+    hipStream_t st = slot.st;
+    const int naug = (int)((S + GP_TS - 1) / GP_TS);
+    c->io.reset();
+    const double* dx = up(c, x, (size_t)n * S);
+    double* wt = c->io.take<double>((size_t)naug * nt * GP_TSQ);
+    double* oq = c->io.take<double>((size_t)S);
+    TRef W = rect_ref(wt, (long long)naug * nt * GP_TSQ, nt);
+    TRef Ls = lower_ref(c->mvn.tiles, nlow * GP_TSQ);
+    launch_rows_rhs(RowsRhsArgs{dx, S, n, nt, naug, W, 0, 1}, st);
+    const int short_rows = naug == 1 ? (int)S : 0;
+    // right-looking: z_k = w_k L_kk^-T by substitution (no inverted block: the factor is near-singular), then every
+    // remaining column block in parallel on the MFMA tile kernel
+    for (int k = 0; k < nt; ++k) {
+        launch_trsm_robust(W, Ls, k, 0, naug, 1, st);
+        if (k + 1 < nt)     // W(:, j) -= W(:, k) L(j, k)^T for j > k
+            gemm(c, short_aug_row(tile_rect(W, Ls, W, 0, k + 1, naug, nt - k - 1, k, k + 1, 1), 0, short_rows), slot, 0);
+    }
+    launch_row_norms(RowNormArgs{W, nt, naug, S, oq}, st);
+    HC(hipStreamSynchronize(st));
+    HC(hipGetLastError());
+    return oq;
 }
 
 // hands a covariance over: n <= 640 keeps the dense matrix (and validates it on the single-workgroup kernel when the call takes
-// that path), the tiled path factorises it; mvn_info = its LAPACK-style info
+// that path), the tiled path factorises it; mvn.info = its LAPACK-style info
 void mvn_cache(gpslc_ctx* c, const double* cov, bool small) {
     const size_t n = (size_t)c->n;
-    c->mvn_valid = false;
-    ++c->mvn_gen;
+    c->mvn.valid = false;
+    ++c->mvn.gen;
     if (!mvn_dual(c)) {      // n > 640 (or the fp32 kernel mode): the tiled path is the only one
-        DevBuf bcov;
+        DevBuffer<double> bcov;
         mvn_factor_tiles(c, up(bcov, cov, n * n));
-        c->mvn_valid = true;
+        c->mvn.valid = true;
         return;
     }
-    if (!c->mvn_dense) HC(hipMalloc((void**)&c->mvn_dense, n * n * sizeof(double)));
-    HC(hipMemcpy(c->mvn_dense, cov, n * n * sizeof(double), hipMemcpyHostToDevice));
+    c->mvn.dense.reserve(n * n * sizeof(double));
+    HC(hipMemcpy(c->mvn.dense, cov, n * n * sizeof(double), hipMemcpyHostToDevice));
     if (small) {
         // validate once (as the tiled path does when it factorises): info of cov itself
         std::vector<double> zeros(n, 0.0);
-        const HostNode probe = dense_node(c->mvn_dense, 1.0, zeros.data());
+        const HostNode probe = dense_node(c->mvn.dense, 1.0, zeros.data());
         double dummy = 0.0;
-        c->mvn_info = small_nodes_logpdf(c, 1, &probe, &dummy);
+        c->mvn.info = small_nodes_logpdf(c, 1, &probe, &dummy);
     } else {
-        mvn_factor_tiles(c, c->mvn_dense);
+        mvn_factor_tiles(c, c->mvn.dense);
     }
-    c->mvn_valid = true;
+    c->mvn.valid = true;
 }
 
 // before a cov = NULL call on the tiled path: the factor of the latest hand-over (rebuilt from the dense copy when an earlier
 // hand-over went to the single-workgroup path)
 void mvn_tiles_current(gpslc_ctx* c) {
-    if (c->mvn_tiles && c->mvn_tiles_gen == c->mvn_gen) return;
-    mvn_factor_tiles(c, c->mvn_dense);
+    if (c->mvn.tiles && c->mvn.tiles_gen == c->mvn.gen) return;
+    mvn_factor_tiles(c, c->mvn.dense);
 }
 
 // What gpslc_mvn_logpdf and gpslc_mvn_draw do before they differ (`in`: x / z, argument 5; `out`: the result, argument 6):
 // the pointer checks, then — small: the call runs on the single-workgroup kernels — the covariance is handed over, or the tiled
 // factor brought up to date when the call runs tiled and gave none, and every vector's info is that of the covariance.
-// `body(small)` goes on from there; mvn_info != 0 and S == 0 are its to answer (the two calls differ there).
+// `body(small)` goes on from there; mvn.info != 0 and S == 0 are its to answer (the two calls differ there).
 template <class Body>
 int mvn_call(gpslc_ctx* c, int64_t S, const double* cov, const double* in, const char* in_is_null, const double* out,
              const char* out_is_null, Body&& body) {
     if (!c) return -1;
     if (S < 0) return bad_arg(c, 2, "S < 0");
-    if (!cov && !c->mvn_valid) return bad_arg(c, 3, "cov is NULL and no factor is cached");
+    if (!cov && !c->mvn.valid) return bad_arg(c, 3, "cov is NULL and no factor is cached");
     if (S > 0 && !in) return bad_arg(c, 5, in_is_null);
     if (S > 0 && !out) return bad_arg(c, 6, out_is_null);
     const bool small = fast_path_ok(c, 0, std::max<int64_t>(S, 1));
     return guarded(c, [&]() {
         if (cov) mvn_cache(c, cov, small);   // factor once, keep it in the context
         else if (!small) mvn_tiles_current(c);
-        c->last_info.assign((size_t)S, c->mvn_info);
+        c->last_info.assign((size_t)S, c->mvn.info);
         return body(small);
     });
 }
@@ -2403,7 +2359,7 @@ int mvn_call(gpslc_ctx* c, int64_t S, const double* cov, const double* in, const
 std::vector<HostNode> mvn_nodes(const gpslc_ctx* c, int64_t S, const double* covscale, const double* target) {
     std::vector<HostNode> hn;
     hn.reserve((size_t)S);
-    for (int64_t s = 0; s < S; ++s) hn.push_back(dense_node(c->mvn_dense, covscale ? covscale[s] : 1.0, target + s * c->n));
+    for (int64_t s = 0; s < S; ++s) hn.push_back(dense_node(c->mvn.dense, covscale ? covscale[s] : 1.0, target + s * c->n));
     return hn;
 }
 
@@ -2707,9 +2663,9 @@ int gpslc_nodes_draw(gpslc_ctx* c, int32_t count, const gpslc_node* nodes, doubl
 int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* covscale, const double* x,
                      double* logpdf) {
     return mvn_call(c, S, cov, x, "x is NULL", logpdf, "logpdf is NULL", [&](bool small) {
-        if (S == 0 || c->mvn_info != 0) {
+        if (S == 0 || c->mvn.info != 0) {
             for (int64_t s = 0; s < S; ++s) logpdf[s] = NAN;
-            return c->mvn_info;
+            return c->mvn.info;
         }
         if (small) {
             // small n: the dense matrix stays on the device; every evaluation is one workgroup that scales, factorises
@@ -2719,37 +2675,14 @@ int gpslc_mvn_logpdf(gpslc_ctx* c, int64_t S, const double* cov, const double* c
             if (st > 0) for (int64_t s = 0; s < S; ++s) if (c->last_info[s] != 0) logpdf[s] = NAN;
             return st;
         }
-        ensure_streams(c);
-        const int n = (int)c->n, nt = c->nt;
-        const long long nlow = (long long)nt * (nt + 1) / 2;
-        StreamSlot& slot = c->slots[0];
-        hipStream_t st = slot.st;
-        // z_s = L^-1 x_s for all S vectors: rows of W = X^T L^-T, tile-level left-looking solve
-        const int naug = (int)((S + GP_TS - 1) / GP_TS);
-        c->io.reset();
-        const double* dx = up(c, x, (size_t)n * S);
-        double* wt = c->io.take<double>((size_t)naug * nt * GP_TSQ);
-        double* oq = c->io.take<double>((size_t)S);
-        TRef W = rect_ref(wt, (long long)naug * nt * GP_TSQ, nt);
-        TRef Ls = lower_ref(c->mvn_tiles, nlow * GP_TSQ);
-        launch_rows_rhs(RowsRhsArgs{dx, S, n, nt, naug, W, 0, 1}, st);
-        const int short_rows = naug == 1 ? (int)S : 0;
-        // right-looking: z_k = w_k L_kk^-T by substitution (no inverted block: the factor is near-singular), then every
-        // remaining column block in parallel on the MFMA tile kernel
-        for (int k = 0; k < nt; ++k) {
-            launch_trsm_robust(W, Ls, k, 0, naug, 1, st);
-            if (k + 1 < nt)     // W(:, j) -= W(:, k) L(j, k)^T for j > k
-                gemm(c, short_aug_row(tile_rect(W, Ls, W, 0, k + 1, naug, nt - k - 1, k, k + 1, 1), 0, short_rows), slot, 0);
-        }
-        launch_row_norms(RowNormArgs{W, nt, naug, S, oq}, st);
-        HC(hipStreamSynchronize(st));
-        HC(hipGetLastError());
+        const int n = (int)c->n;
+        const double* oq = mvn_solve_tiles(c, S, x);
         if (c->flags & GPSLC_FLAG_PROFILE) prof_collect(c);
         std::vector<double> q(S);
         HC(hipMemcpy(q.data(), oq, sizeof(double) * S, hipMemcpyDeviceToHost));
         for (int64_t s = 0; s < S; ++s) {
             const double sc = covscale ? covscale[s] : 1.0;
-            logpdf[s] = -0.5 * ((double)n * kLog2Pi + (double)n * std::log(sc) + c->mvn_logdet + q[s] / sc);
+            logpdf[s] = -0.5 * ((double)n * kLog2Pi + (double)n * std::log(sc) + c->mvn.logdet + q[s] / sc);
         }
         return GPSLC_OK;
     });
@@ -2762,9 +2695,9 @@ int gpslc_mvn_draw(gpslc_ctx* c, int64_t S, const double* cov, const double* cov
     return mvn_call(c, S, cov, z, "z is NULL", draws, "draws is NULL", [&](bool small) {
         const size_t n = (size_t)c->n;
         if (S == 0) return GPSLC_OK;        // a hand-over alone answers GPSLC_OK here; the covariance's info is in last_info
-        if (c->mvn_info != 0) {
+        if (c->mvn.info != 0) {
             for (size_t e = 0; e < n * (size_t)S; ++e) draws[e] = NAN;
-            return c->mvn_info;
+            return c->mvn.info;
         }
         if (small) {
             const std::vector<HostNode> hn = mvn_nodes(c, S, covscale, z);
@@ -2782,7 +2715,7 @@ int gpslc_mvn_draw(gpslc_ctx* c, int64_t S, const double* cov, const double* cov
         double* out = c->io.take<double>(n * (size_t)S);
         double* zt = c->io.take<double>((size_t)S * draws_image_doubles(1, Np));
         HC(hipMemsetAsync(zero_mean, 0, n * (size_t)S * sizeof(double), st));
-        launch_draws(zero_mean_draw(lower_ref(c->mvn_tiles, 0), (int)n, nt, 0, S, zero_mean, dz, zt, out), (int)S, st);
+        launch_draws(zero_mean_draw(lower_ref(c->mvn.tiles, 0), (int)n, nt, 0, S, zero_mean, dz, zt, out), (int)S, st);
         HC(hipStreamSynchronize(st));
         HC(hipGetLastError());
         HC(hipMemcpy(draws, out, n * (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
@@ -2807,35 +2740,36 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
         hipStream_t st = slot.st;
         const int n = (int)c->n, nt = c->nt;
         const long long nlow = (long long)nt * (nt + 1) / 2, nsq = (long long)nt * nt;
-        DevBuf bdo, info, tiles, inv, part, rect, outb;
+        DevBuffer<double> bdo, tiles, inv, rect, outb;
+        DevBuffer<int> info;
         c->io.reset();
         SampleParams sp = upload_samples(c, SampleParams{U, uyLS, xyLS, &ty, &ysc, &yno}, 0, 1);
         sp.u_sstride = (long long)n * c->nU;
-        info.alloc(sizeof(int));
-        HC(hipMemsetAsync(info.p, 0, sizeof(int), st));
-        tiles.alloc((size_t)nlow * GP_TSQ * 8);
-        inv.alloc((size_t)nt * GP_TSQ * 8);
-        rect.alloc((size_t)6 * nsq * GP_TSQ * 8);        // K, Ks, Ks', Kss, W1, W2
-        outb.alloc((size_t)n * n * 8);
-        double* rb = rect.as<double>();
+        info.reserve(sizeof(int));
+        HC(hipMemsetAsync(info, 0, sizeof(int), st));
+        tiles.reserve((size_t)nlow * GP_TSQ * 8);
+        inv.reserve((size_t)nt * GP_TSQ * 8);
+        rect.reserve((size_t)6 * nsq * GP_TSQ * 8);      // K, Ks, Ks', Kss, W1, W2
+        outb.reserve((size_t)n * n * 8);
+        double* rb = rect;
         const long long rs = nsq * GP_TSQ;
         TRef Kt = rect_ref(rb, rs, nt), Kst = rect_ref(rb + rs, rs, nt), KsTt = rect_ref(rb + 2 * rs, rs, nt),
              Ksst = rect_ref(rb + 3 * rs, rs, nt), W1 = rect_ref(rb + 4 * rs, rs, nt), W2 = rect_ref(rb + 5 * rs, rs, nt);
-        TRef M = lower_ref(tiles.as<double>(), nlow * GP_TSQ);
+        TRef M = lower_ref(tiles, nlow * GP_TSQ);
         // A = K + yNoise I (lower tiles) and its factor
         const SampleGrid grid{c->dX, c->dT, sp, 0, n, c->nX, c->nU, nt};
         GramArgs ga{grid};
         ga.M = M; ga.part = nullptr; ga.with_sums = 0; ga.f32 = 0;
         launch_gram(ga, 1, st);
-        factor_panels(c, slot, M, nt, nt, inv.as<double>(), info.as<int>(), 0, 1, 0, false, 0);
+        factor_panels(c, slot, M, nt, nt, inv, info, 0, 1, 0, false, 0);
         LdBuildArgs la{grid, doT, Kt, Kst, KsTt, Ksst};
         if (doTv) la.doTv = up(bdo, doTv, (size_t)n);
         launch_ld_build(la, st);
         auto emit = [&](const TRef& R, double* host, double diag_add) {
             if (!host) return;
-            launch_rect_gather(RectGatherArgs{R, n, nt, outb.as<double>(), diag_add}, st);
+            launch_rect_gather(RectGatherArgs{R, n, nt, outb, diag_add}, st);
             HC(hipStreamSynchronize(st));
-            copy_out_large(c, host, outb.p, (size_t)n * n * 8);
+            copy_out_large(c, host, outb, (size_t)n * n * 8);
         };
         emit(Kt, CovWW, 0.0);
         emit(Kst, CovWWs, 0.0);
@@ -2844,7 +2778,7 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
             // W1 = K L^-T, W2 = Ks' L^-T  (copies, then unit B's tile-level left-looking solve)
             HC(hipMemcpyAsync(W1.base, Kt.base, (size_t)rs * 8, hipMemcpyDeviceToDevice, st));
             HC(hipMemcpyAsync(W2.base, KsTt.base, (size_t)rs * 8, hipMemcpyDeviceToDevice, st));
-            TRef invref = inv_ref(inv.as<double>(), nt);
+            TRef invref = inv_ref(inv, nt);
             w_solve(c, slot, W1, M, invref, nt, 1, nt);
             w_solve(c, slot, W2, M, invref, nt, 1, nt);
             // C11 = K - W1 W1', C12 = Ks - W1 W2', C21 = Ks' - W2 W1', C22 = Kss - W2 W2'   (src/likelihood.jl:46-49)
@@ -2861,7 +2795,7 @@ static int likelihood_distribution_impl(gpslc_ctx* c, const double* U, const dou
         HC(hipStreamSynchronize(st));
         HC(hipGetLastError());
         int hinfo = 0;
-        HC(hipMemcpy(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost));
+        HC(hipMemcpy(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost));
         c->last_info.assign(1, hinfo);
         return hinfo;
     });
@@ -2925,10 +2859,10 @@ int gpslc_summarize(gpslc_ctx* c, const double* samples, int64_t n, int64_t m, d
     if (!(credible_interval > 0.0 && credible_interval < 1.0)) return bad_arg(c, 5, "credible_interval not in (0,1)");
     if (!mean || !lower || !upper) return bad_arg(c, 6, "output is NULL");
     return guarded(c, [&]() {
-        DevBuf bx, o;
+        DevBuffer<double> bx, o;
         const double* dx = up(bx, samples, (size_t)n * m);
-        o.alloc(sizeof(double) * 3 * n);
-        double* d = o.as<double>();
+        o.reserve(sizeof(double) * 3 * n);
+        double* d = o;
         summarize_impl(c, dx, n, m, 1, n, credible_interval, d, d + n, d + 2 * n);
         HC(hipMemcpy(mean, d, sizeof(double) * n, hipMemcpyDeviceToHost));
         HC(hipMemcpy(lower, d + n, sizeof(double) * n, hipMemcpyDeviceToHost));
