@@ -335,7 +335,7 @@ const TaskList& task_list_for(gpslc_ctx* c, int nt, int back, int nb, int G, int
     }
     TaskList t;
     t.nt = nt; t.back = back; t.nb = nb; t.G = G; t.rows = rows; t.aug_full = aug_full;
-    std::vector<unsigned> h = build_task_list(nt, back, nb, G, rows, aug_full, &t.ntasks, /*merge_diag=*/1);
+    std::vector<unsigned> h = build_task_list(nt, back, nb, G, rows, aug_full, &t.ntasks);
     t.dev.reserve(h.size() * sizeof(unsigned));
     HC(hipMemcpy(t.dev, h.data(), h.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     t.used = ++c->task_clock;
@@ -365,8 +365,9 @@ void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv
     rearm_queue(s);
     const size_t ints = TASK_SYNC_HDR + (size_t)TASK_SYNC_STRIDE * nb;
     s.sync.reserve(ints * sizeof(int));
+    const int mt = task_aug_blocks(short_rows);     // 0: the augmented row is a tile row of the list, not a rider of the diagonal tasks
     const TaskList& tl = task_list_for(c, nt, back_alpha ? 1 : 0, nb, c->task_group,
-                                       std::max(1, std::min(4, nt > 8 ? 1 : c->task_rows)), short_rows > 32);
+                                       std::max(1, std::min(4, nt > 8 ? 1 : c->task_rows)), /*aug_full=*/mt == 0);
     HC(hipMemsetAsync(s.sync, 0, ints * sizeof(int), st));
     PotrfTaskArgs a{};
     a.g = task_matrix(M, inv_ref(inv, nt), nt, short_rows, nb, info, info_base);
@@ -391,7 +392,7 @@ void potrf_tasks(gpslc_ctx* c, StreamSlot& s, const TRef& M, int nt, double* inv
 #endif
     {
         ProfScope ps(c, 4, (Np * Np * Np / 3.0 + (double)a.g.short_rows * Np * Np) * (double)nb, st);
-        launch_potrf_tasks(a, tl.ntasks, short_rows > 32 ? 0 : (short_rows + 15) / 16, st);
+        launch_potrf_tasks(a, tl.ntasks, mt, st);
     }
     HC(hipGetLastError());
 #ifdef GPSLC_DIAG

@@ -791,9 +791,10 @@ void launch_diag_update_potrf(const GemmArgs& g, int carry_aug, hipStream_t st) 
 // A workgroup draws a ticket from its XCD's queue (the queue is chosen by the hardware XCC_ID, not by blockIdx: the
 // strips of one matrix column then really share one L2; a workgroup whose queue has run dry goes on with the next
 // queue, so every task is executed whatever the placement), reads the task descriptor the host laid out
-// (PotrfTaskArgs::list), waits for the task's producers on the matrix's progress words, runs the body — exactly the
-// device functions of the per-column launches: strip_item, syrk_chain_wave + diag_potrf_inv_la_body, so every tile
-// receives the same MFMA chains in the same order and the factor is bit-identical — and publishes its own progress.
+// (PotrfTaskArgs::list), waits for the task's producers on the matrix's progress words (task_needs, task_list.h: the one
+// statement of which task waits for what), runs the body — exactly the device functions of the per-column launches:
+// strip_item, syrk_chain_wave + diag_potrf_inv_la_body, so every tile receives the same MFMA chains in the same order and
+// the factor is bit-identical — and publishes its own progress (task_products, task_list.h).
 // Hand-off between workgroups (MI355X_MICROARCH.md "inter-workgroup visibility", form R1): every tile another workgroup of the
 // launch will read is stored WRITE-THROUGH (agent-scope relaxed atomic stores = global_store ... sc1: out_store, diag_block.h),
 // every storing wave drains its stores (s_waitcnt vmcnt(0)), workgroup barrier, ONE lane stores the progress word (relaxed,
@@ -828,11 +829,11 @@ __device__ __forceinline__ void task_wait(const int* p, int need, int* tmo) {
 // lane 0 of a workgroup: the next descriptor of queue `q` (or of the queues after it once it has run dry: `visited` counts
 // the empty ones), TASK_NONE when all eight are exhausted
 __device__ __forceinline__ unsigned task_fetch(const PotrfTaskArgs& a, int& q, int& visited) {
-    while (visited < 8) {
-        const int len = (int)a.list[8 + q];
-        const int t = len > 0 ? atomicAdd(&a.sync[q], 1) : len;
-        if (t < len) return a.list[TASK_LIST_HDR + a.list[q] + t];
-        q = (q + 1) & 7;
+    while (visited < TASK_QUEUES) {
+        const int len = (int)a.list[TASK_LIST_LEN(q)];
+        const int t = len > 0 ? atomicAdd(&a.sync[TASK_SYNC_HEAD(q)], 1) : len;
+        if (t < len) return a.list[TASK_LIST_HDR + a.list[TASK_LIST_FIRST(q)] + t];
+        q = (q + 1) & (TASK_QUEUES - 1);
         ++visited;
     }
     return TASK_NONE;
@@ -862,24 +863,8 @@ __global__ __launch_bounds__(256, 2) void potrf_tasks_kernel(PotrfTaskArgs a) {
             int* const tmo = a.timeout;
             const unsigned d = s_next;
             if (d != TASK_NONE) {
-                const int nt = a.nt;
-                const int b = TASK_B(d), k = TASK_K(d), i = TASK_I(d), rows = TASK_ROWS(d);
-                const int* prog = a.sync + TASK_SYNC_HDR + (long long)b * TASK_SYNC_STRIDE;
-                if ((d >> 30) == 3) {               // back-substitution: the whole factor and the solved augmented row
-                    task_wait(prog, nt, tmo);
-                    task_wait(prog + 1 + nt, nt, tmo);
-                } else if ((d >> 30) & 1) {         // diag(k): tile row k (and the augmented row) final up to column k - 1
-                    if (k > 0) {
-                        task_wait(prog + 1 + k, k, tmo);
-                        if (MT > 0) task_wait(prog + 1 + nt, k, tmo);
-                        if (rows > 1) task_wait(prog + 2 + k, k, tmo);      // ... and tile row k + 1 for the strip it goes on with
-                    }
-                } else {                            // strip(i.., k): inv(L_kk) and tile row k (diag(k)), the tile rows up to column k - 1
-                    task_wait(prog, k + 1, tmo);
-                    // MT == 0: the augmented row (i == nt) is an ordinary tile row whose strips carry their own column update
-                    if ((i < nt || MT == 0) && k > 0)
-                        for (int r = 0; r < rows; ++r) task_wait(prog + 1 + i + r, k, tmo);
-                }
+                const int* prog = a.sync + TASK_SYNC_HDR + (long long)TASK_B(d) * TASK_SYNC_STRIDE;
+                task_needs(d, a.nt, MT > 0, [&](int word, int value) { task_wait(prog + word, value, tmo); });
                 if (GP_DBG_ON(a)) s_ready = __builtin_amdgcn_s_memtime();       // producers done (before the acquire)
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -890,17 +875,16 @@ __global__ __launch_bounds__(256, 2) void potrf_tasks_kernel(PotrfTaskArgs a) {
         const unsigned d = s_desc;
         if (d == TASK_NONE) break;
         const int b = TASK_B(d), k = TASK_K(d), i = TASK_I(d), rows = TASK_ROWS(d);
-        const bool is_back = (d >> 30) == 3;
-        const bool is_diag = (d >> 30) == 1;
-        const bool with_aug = (d >> 30) == 2;       // strip(k + 1, k) also carries the augmented tile (nt, k)
+        const bool is_back = TASK_KIND(d) == TASK_BACK;
+        const bool is_diag = TASK_KIND(d) == TASK_DIAG;
         unsigned long long st0 = 0, st1 = 0;
         if (GP_DBG_ON(a)) st0 = __builtin_amdgcn_s_memtime();
         // the ticket of the NEXT task is drawn now and read after the body: its round trip hides behind the tile
         int tnext = 0, qn = 0, lenn = 0;
         if (tid == 0) {
             qn = s_q;
-            lenn = s_visited < 8 ? (int)a.list[8 + qn] : 0;
-            tnext = lenn > 0 ? atomicAdd(&a.sync[qn], 1) : 0;
+            lenn = s_visited < TASK_QUEUES ? (int)a.list[TASK_LIST_LEN(qn)] : 0;
+            tnext = lenn > 0 ? atomicAdd(&a.sync[TASK_SYNC_HEAD(qn)], 1) : 0;
         }
         const int lane = tid & 63;
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -951,7 +935,7 @@ __global__ __launch_bounds__(256, 2) void potrf_tasks_kernel(PotrfTaskArgs a) {
             else
                 for (int r = 0; r < rows; ++r)
                     strip_item<FUSE_WD, (MT > 0), WT>(gl, b, i + r, k, /*no_update=*/MT > 0 && i >= a.nt, 8 * k, smem, tid, lane, wave, li, lg,
-                                                  lg * LROW + li, loff, 0, with_aug && r == 0);
+                                                  lg * LROW + li, loff, 0, /*with_aug=*/false);
         }
         // publish: every wave's stores have left the CU, then one lane releases and moves the matrix's progress word(s)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -961,31 +945,24 @@ __global__ __launch_bounds__(256, 2) void potrf_tasks_kernel(PotrfTaskArgs a) {
             // the next descriptor travels under the release fence
             unsigned dn = TASK_NONE;
             const bool hit = tnext < lenn;
-            if (hit) dn = a.list[TASK_LIST_HDR + a.list[qn] + tnext];
+            if (hit) dn = a.list[TASK_LIST_HDR + a.list[TASK_LIST_FIRST(qn)] + tnext];
             int* prog = a.sync + TASK_SYNC_HDR + (long long)b * TASK_SYNC_STRIDE;
             if (!is_back && !GP_TASK_WITHHOLD(a, b, is_diag, k)) {
                 if (GP_FENCE_MODE(a) == 0 && !WT) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (is_diag) {
-                    __hip_atomic_store(prog, k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (diag_then_strip) {
-                        __hip_atomic_store(prog + 2 + k, k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (MT > 0) __hip_atomic_store(prog + 1 + a.nt, k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                } else
-                    for (int r = 0; r < rows; ++r)
-                        __hip_atomic_store(prog + 1 + i + r, k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (with_aug) __hip_atomic_store(prog + 1 + a.nt, k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                task_products(d, a.nt, MT > 0, [&](int word, int value) {
+                    __hip_atomic_store(prog + word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                });
             }
             if (!hit) {                      // this queue has run dry (or had long before): go on with the others
                 int q = qn, visited = s_visited;
-                if (visited < 8) { q = (q + 1) & 7; ++visited; }
+                if (visited < TASK_QUEUES) { q = (q + 1) & (TASK_QUEUES - 1); ++visited; }
                 dn = task_fetch(a, q, visited);
                 s_q = q; s_visited = visited;
             }
             s_next = dn;
             if (GP_DBG_ON(a)) {     // measurement build: fetch start, body start, body end, published, descriptor, workgroup, ready
-                unsigned long long* dd = a.dbg + 8 * (size_t)atomicAdd(a.sync + 9, 1);
+                unsigned long long* dd = a.dbg + 8 * (size_t)atomicAdd(a.sync + TASK_SYNC_DONE, 1);
                 dd[0] = stf; dd[1] = st0; dd[2] = st1; dd[3] = __builtin_amdgcn_s_memtime(); dd[4] = d; dd[5] = blockIdx.x;
                 dd[6] = s_ready; dd[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
             }

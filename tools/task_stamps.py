@@ -9,12 +9,12 @@ import numpy as np
 d = np.fromfile(sys.argv[1], dtype=np.uint64).reshape(-1, 8)
 d = d[d[:, 3] > 0]
 desc = d[:, 4]
-kind4 = (desc >> np.uint64(30)).astype(int)          # 0 strip, 1 diag, 2 strip + augmented tile, 3 back-substitution
+kind4 = (desc >> np.uint64(30)).astype(int)          # 0 strip, 1 diag, 3 back-substitution (task_list.h; 2 is unused)
 kind = (kind4 == 1).astype(int)
 isback = kind4 == 3
 k = ((desc >> np.uint64(19)) & np.uint64(31)).astype(int)
 i = ((desc >> np.uint64(24)) & np.uint64(63)).astype(int)
-nt = int(i[(kind4 == 0) | (kind4 == 2)].max()) if ((kind4 == 0) | (kind4 == 2)).any() else 0
+nt = int(i[kind4 == 0].max()) if (kind4 == 0).any() else 0
 kind = np.where(isback, 7, kind)
 t = d[:, :4].astype(np.int64)
 ready = d[:, 6].astype(np.int64)
