@@ -1,4 +1,4 @@
-// Chunk sizing of the ensemble driver (run_predict, api.hip) as plain host arithmetic — no HIP in here, so that the CPU test
+// Chunk sizing of the ensemble driver (run_predict, predict.hip) as plain host arithmetic — no HIP in here, so that the CPU test
 // suite can compile and exercise it (tests/c/batch_plan_test.cpp).
 //   per        bytes of workspace per posterior sample of a chunk (tiles of A, inverted blocks, sums, ...)
 //   unit       bytes per (sample, level) unit of the full-ITE-covariance sub-batch (W, CovITE, draw workspaces); 0 = no unit B

@@ -1,9 +1,9 @@
-// Ownership of a ctx's memory (api.hip) as plain host C++ — no HIP in here, so that the CPU test (tests/test_dev_mem.py) compiles
+// Ownership of a ctx's memory (host_ctx.h) as plain host C++ — no HIP in here, so that the CPU test (tests/test_dev_mem.py) compiles
 // it with g++ against a counting fake.  A memory policy `Mem` says where the bytes come from:
 //     static void* alloc(size_t bytes);   // null on failure
 //     static void  release(void* p);
 //     static void  quiesce();             // before memory that launches may still use is freed
-// api.hip supplies the two real ones (device memory, pinned host memory).  Every block has exactly one owner, a Buffer; an Arena
+// host_ctx.h supplies the two real ones (device memory, pinned host memory).  Every block has exactly one owner, a Buffer; an Arena
 // and a PoolArena carve aligned pieces out of the Buffers they hold.
 #pragma once
 

@@ -6,7 +6,7 @@
 //     var_i(l) = (prior_l yScale - ||row i of W*(l)||^2) + pred_noise      cov(l) = prior_l B** + pred_noise I - W*(l) W*(l)^T
 // Here: the mean on the MFMA (the pair-product body of pair_mfma.h with the rows from the new grid), the builder of the D*(l) and
 // prior_l B** tiles, the row norms that give var, and the gather of cov into the caller's layout.  The solve W* = D* L^-T and the
-// product W* W*^T are the tile kernels' (api.hip: w_solve, gemm).
+// product W* W*^T are the tile kernels' (w_solve, predict.hip; gemm, factor.hip).
 // Every output element depends on its own new individual(s), the training data and the sample only, in a fixed summation order:
 // results do not depend on which other new individuals share the call, nor on the chunk, the stream or the schedule.
 // Further down: weighted averages over the new individuals, which need none of these tiles.

@@ -5,7 +5,7 @@
 //                             covariance, the conditional blocks of the likelihood distribution;
 //   tile_fused_strip_kernel   one tile column: the left-looking column update and, in the same work item, the panel product
 //                             with the inverted diagonal block (strip_item) — the panels of the factorisation and the
-//                             "D L^-T" solves (w_solve, api.hip; tile_column + fused, tile_launch.h);
+//                             "D L^-T" solves (w_solve, predict.hip; tile_column + fused, tile_launch.h);
 //   loo_diagonal_kernel       one block diagonal of L^-T for the leave-one-out checks: strip_item with a K range per item;
 //   tile_syrk_diag_kernel,    the diagonal tiles of a symmetric update (lower triangle only), alone or followed by the
 //   diag_update_potrf_kernel  tile's Cholesky and inverse;

@@ -3,7 +3,7 @@
 // b = doT_base[l], wt = 1 / tyLS^2, r^x_j = rho(T_j, x), rho(x, y) = exp(-(x - y)^2 wt): the callers evaluate the exponentials their
 // own way (gp_rho, the table-driven exp, fp32) and hand the values over, and the operation order of every expression here is part
 // of the results.  Needs <type_traits> and the includer's __host__ / __device__ only (tests/c/level_form_test.cpp: the CPU check).
-// A fifth form takes one LevelForm specialisation, one line in dispatch_form, one row in kFormRules (api.hip) and one entry point.
+// A fifth form takes one LevelForm specialisation, one line in dispatch_form, one row in kFormRules (predict.h) and one entry point.
 #pragma once
 #include <type_traits>
 

@@ -1,5 +1,5 @@
 // Where everything of the single-workgroup node kernels (k_small.hip) lives: the LDS images, the left-looking kernel's scratch
-// and a node's pinned staging.  Each is written down here once and read by the kernels, the host's size functions and api.hip
+// and a node's pinned staging.  Each is written down here once and read by the kernels, the host's size functions and api_score.hip
 // (DESIGN.md §24).  Plain C++17: tests/c/sm_layout_test.cpp compiles it with g++.  Offsets are in doubles unless named bytes.
 #pragma once
 #include <cstddef>

@@ -1,6 +1,6 @@
 // The launches of the tile-product kernels (k_tilegemm.hip), described in one place: the makers of the tile-matrix references, one
 // builder per kind of GemmArgs, and the profiler's flop count of a launch.  Plain host C++ (tests/c/tile_launch_test.cpp compiles
-// it with g++).  A builder returns a complete GemmArgs and owns the invariants between its fields; api.hip sets no field of the
+// it with g++).  A builder returns a complete GemmArgs and owns the invariants between its fields; no caller sets a field of the
 // launches it passes to gemm() itself ("Where a tile-product launch is described").
 #pragma once
 #include <algorithm>
@@ -81,7 +81,7 @@ inline GemmArgs task_matrix(const TRef& M, const TRef& F, int nt, int short_rows
     return g;
 }
 
-// The profiler's algorithmic flop count of launch_tile_gemm(g) (gemm(), api.hip); diag_skip: the measurement build's
+// The profiler's algorithmic flop count of launch_tile_gemm(g) (gemm(), factor.hip); diag_skip: the measurement build's
 // GPSLC_GEMM_DIAG variant, 0 otherwise
 inline double tile_launch_flop(const GemmArgs& g, int diag_skip) {
     // algorithmic flop: full tiles count 2*128^3 per K tile, items in the (single) augmented row only

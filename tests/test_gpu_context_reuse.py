@@ -1,4 +1,4 @@
-"""One context serving calls of changing size: every buffer a gpslc_ctx owns (csrc/dev_mem.h, csrc/api.hip) is made to grow and
+"""One context serving calls of changing size: every buffer a gpslc_ctx owns (csrc/dev_mem.h, csrc/host_ctx.h) is made to grow and
 is then used again at a smaller size, and the last call of each sequence is compared BIT FOR BIT with the same call on a fresh
 context.  Growth has no other observable effect: a buffer that lost its contents' owner, kept a stale size or pointer, or was
 freed under a launch shows as different bytes (or as a fault), never as a status.  Every status is GPSLC_OK: the front end raises

@@ -1,5 +1,5 @@
 """likelihoodDistribution's W1 = K L^-T and W2 = Ks' L^-T against the bits recorded BEFORE the solve went through w_solve
-(api.hip): one strip-kernel launch per tile column, column update and panel product in one work item, instead of a column
+(predict.hip): one strip-kernel launch per tile column, column update and panel product in one work item, instead of a column
 update by the trailing kernel followed by that kernel's stand-alone panel product.  Per output element both forms run the same
 MFMA chain — ascending k in the column update, ascending column of X in the product with inv(L_kk)^T (strip_item,
 k_tilegemm.hip) — so all seven blocks must be equal BIT FOR BIT; a tolerance has no place here.

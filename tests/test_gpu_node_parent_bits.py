@@ -1,6 +1,6 @@
 """The node-score entry points (gpslc_y_logpdf, gpslc_gp_logpdf, gpslc_nodes_logpdf, gpslc_nodes_draw, gpslc_mvn_logpdf,
 gpslc_mvn_draw) against results recorded BEFORE their host side was folded together: one constructor per kind of node view,
-one body for the fused node calls, one tiled score, one MVN prologue, one zero-mean node draw (api.hip).  None of that
+one body for the fused node calls, one tiled score, one MVN prologue, one zero-mean node draw (api_score.hip).  None of that
 touches a kernel or reorders a floating-point operation, so every output must be equal BIT FOR BIT; a tolerance has no place
 here.  tests/golden/node_parent_hashes.json holds the parent commit's hash and the SHA-256 of every output the parent returned
 on an MI355X for the seeded cases below, at the smallest sizes that reach each path: n = 150 (the LDS-resident kernel), 400

@@ -1,7 +1,7 @@
 """The outcome-model entry points that ride on the tiled factor (gpslc_y_loo, gpslc_y_lgo, gpslc_y_logpdf_grad, gpslc_predict_new)
 against results recorded BEFORE their host side was folded together: one body for the calls at the C boundary, the features'
 members of PredictIO grouped, one sub-batch loop for the pair workspaces of unit B and of the new individuals, one plan for the
-four Context methods (api.hip, api.py).  None of that touches a kernel or reorders a floating-point operation, so every output
+four Context methods (api_score.hip, predict.hip, api.py).  None of that touches a kernel or reorders a floating-point operation, so every output
 must be equal BIT FOR BIT; a tolerance has no place here.  tests/golden/outcome_parent_hashes.json holds the parent commit's hash
 and the SHA-256 of every output the parent returned on an MI355X for the seeded cases below, at the smallest sizes that reach
 each path: tiles are 128 wide, so n = 200 is two tiles and n = 300 three with a ragged last one.

@@ -1,5 +1,5 @@
 """Node and MVN scores on both sides of the switch between the single-workgroup kernels and the batched tiled path
-(fast_path_ok, csrc/api.hip): a call takes the single-workgroup kernels (k_small.hip) for n <= 640 and at most 4096 nodes
+(fast_path_ok, csrc/api_score.hip): a call takes the single-workgroup kernels (k_small.hip) for n <= 640 and at most 4096 nodes
 (the matrix fits LDS) or 512 (the left-looking kernel, n up to 640), the batched tiled factorisation otherwise — and that
 path runs the persistent task launch (potrf_tasks_kernel) for chunks of >= 256 matrices.  The MH chain crosses these
 counts (score_xty_many and the batched sweep of inference.py score len(Us) x (nX + 2) nodes per call), so every call here

@@ -1,5 +1,5 @@
 """Every prediction entry point against results recorded BEFORE the prediction path's plumbing was folded together: one
-request struct through the host front end (api.hip), one SampleGrid inside the launch-argument structs (gpslc_internal.h)
+request struct through the host front end (request.h), one SampleGrid inside the launch-argument structs (gpslc_internal.h)
 and the weighted right-hand sides / epilogue served by the general kernels (k_gram.hip).  None of that reorders a
 floating-point operation, so every output must be equal BIT FOR BIT; a tolerance has no place here.
 tests/golden/predict_parent_hashes.json holds the parent commit's hash and the SHA-256 of every output array the parent

@@ -16,7 +16,7 @@ runtime-F path) and 32 (MAXF, the LDS opt-in limit).
      F in {0, 32} (the entry point takes one parameter set: the case's second sample).
   3. Unit B through predict with draws: n = 129, L = 3, spp = 2, seeded, plain / vector / contrast (the b / lc, b % lc, l0
      indexing of dt_build_kernel).  No gpslc_set_tuning makes l0 > 0 at this size (a sub-batch holds min(128, Bt L) >= L
-     pairs, api.hip), so there is no split case.
+     pairs, predict.hip), so there is no split case.
   4. The VALU MeanITE ladder (predict(want_mean_ite=True), n = 200): fp64 at L = 1 and 2 with F in {3, 5, 6, 7, 9, 11, 14, 18,
      32} (rungs 4, 5, 6, 8, 10, 12, 16, 20, 32), a contrast at F = 5, L = 2, and fp32_kernel at F = 5 and 14 with L = 2 and
      L = 17 (the 16-level VALU path; F = 14 takes the float runtime-F Gram path).

@@ -1,5 +1,5 @@
 """The launch builders of the tile-product kernels (causalgpslc.jl_amd/csrc/tile_launch.h), compiled with g++ against the HIP stub
-and exercised by tests/c/tile_launch_test.cpp: at every launch site of api.hip, over tile counts 1..9, 17 and 34, panel widths
+and exercised by tests/c/tile_launch_test.cpp: at every launch site of the host files, over tile counts 1..9, 17 and 34, panel widths
 1, 4 and 8, up to two augmented tile rows, 0..128 live rows, with and without the skipped augmented diagonal tile, row counts
 other than the tile count for the pair workspaces and one or two tile rows of MVN vectors, the builder's GemmArgs equals field by
 field what api.hip assigned by hand before, ntiles is the number of tiles the kernel's decode visits and every one of them lies

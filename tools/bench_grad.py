@@ -29,7 +29,7 @@ SCALARS = ("dyScale", "dyNoise", "dY")
 
 def auto_chunk(n, nU, nX, S, total_bytes, grad):
     """samples per chunk of a gpslc_y_loo (grad=False) or full gpslc_y_logpdf_grad call, restated: the per-sample workspace of
-    carve_chunk (api.hip) under 30 % of the device, at most 1048576 / nt^2 (32 .. 16384)"""
+    carve_chunk (predict.hip) under 30 % of the device, at most 1048576 / nt^2 (32 .. 16384)"""
     nt = (n + 127) // 128
     Np, tile = nt * 128, 128 * 128
     nlow, tiles_per = nt * (nt + 1) // 2, (nt + 1) * (nt + 2) // 2

@@ -75,7 +75,7 @@ if os.path.isdir(c2dir):
     if tot > 0:
         consts["c2_hbm_bytes_per_sample"] = {
             "value": tot / samples, "samples_per_step": 8192,
-            "source_shas": shas("k_tilegemm.hip", "k_gram.hip", "k_solve.hip", "k_diag.hip", "diag_block.h", "api.hip"),
+            "source_shas": shas("k_tilegemm.hip", "k_gram.hip", "k_solve.hip", "k_diag.hip", "diag_block.h", "factor.hip", "api.hip"),
             "from": f"profiles/{rnd}_pmc_n1024_per_kernel.md",
             "per_kernel_bytes_per_sample": {k: v / samples for k, v in per.items()},
             "what": "HBM bytes per posterior sample at BASELINE config 2 (N=1024 D=4 nU=1, 8,192 samples per step): FETCH_SIZE x 2 "
