@@ -64,6 +64,7 @@ SIGNATURES = {
     "gpslc_y_logpdf": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
     "gpslc_y_loo": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
     "gpslc_y_lgo": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _D, C.c_int32, c_int32_p, _D, _D, _D, _D]),
+    "gpslc_y_kfold": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _D, C.c_int32, c_int32_p, _D, _D, _D, _D]),
     "gpslc_y_logpdf_grad": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
     "gpslc_gp_logpdf": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _D, C.c_int32, _D, _D, _D, _D, C.c_int32, _D]),
     "gpslc_nodes_logpdf": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, _D]),

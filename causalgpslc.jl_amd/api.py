@@ -12,7 +12,8 @@ like the reference's own tests:
     yLogpdf                                       src/model_likelihood.jl:83-120 (:Y node score)
     looPredictive, looSummary                     leave-one-out checks of that node's outcome model (no reference counterpart)
     yLogpdfGrad                                   gradient of that node's score in U, the hyper-parameters and Y (no reference counterpart)
-    lgoPredictive, lgoSummary, foldLabels         leave-group-out checks and K-fold cross-validation of it (no reference counterpart)
+    lgoPredictive, lgoSummary, foldLabels         leave-group-out checks of it, groups of at most 128 members (no reference counterpart)
+    kfoldPredictive, kfoldSummary                 K-fold cross-validation of it: groups of any size (no reference counterpart)
     predictNew                                    outcome, contrast or slope at individuals who are not in the data (no reference counterpart)
     averageNew                                    their weighted averages over a target population, with variance and joint covariance (no reference counterpart)
 
@@ -306,12 +307,21 @@ class Context:
         """gpslc_y_lgo with host arrays as given (None = NULL; ``labels``: n integers in [0, G)): ``(status, lgoMean, lgoVar,
         lgoLpd, logpdf)`` — the outputs named in ``want`` as (n, S) / (n, S) / (G, S) / (S,) arrays, the others None (NULL to
         the library).  The status is returned, not raised, as for ``y_loo``."""
+        return self._group_call(self.lib.gpslc_y_lgo, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, G, labels, want)
+
+    def y_kfold(self, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, G, labels, want=("mean", "var", "lpd", "logpdf")):
+        """gpslc_y_kfold — ``y_lgo`` for groups of any size: ``(status, cvMean, cvVar, cvLpd, logpdf)``, arguments and outputs as
+        there."""
+        return self._group_call(self.lib.gpslc_y_kfold, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, G, labels, want)
+
+    def _group_call(self, fn, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, G, labels, want):
+        """what y_lgo and y_kfold share: the same signature"""
         S, G = int(S), int(G)
         Sn, Gn = max(S, 0), max(G, 0)
         lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32)
         if lab is not None and lab.shape != (self.n,):
             raise ValueError(f"labels must have shape ({self.n},), got {lab.shape}")
-        st, out = self._call_for(self.lib.gpslc_y_lgo, {"mean": (self.n, Sn), "var": (self.n, Sn), "lpd": (Gn, Sn), "logpdf": (Sn,)},
+        st, out = self._call_for(fn, {"mean": (self.n, Sn), "var": (self.n, Sn), "lpd": (Gn, Sn), "logpdf": (Sn,)},
                                  want, S, U, X_or_none, Y_or_none, uyLS, xyLS, tyLS, yScale, yNoise, G,
                                  None if lab is None else lab.ctypes.data_as(_lib.c_int32_p))
         return (st, *out.values())
@@ -1011,14 +1021,14 @@ def looSummary(g: GPSLCObject, X_override=None, Y_override=None, loo=None):
     return {"elpd": elpd, "pointwise": pointwise, "zscore": z, "pit": pit}
 
 
-def _group_labels(g: GPSLCObject, groups):
+def _group_labels(g: GPSLCObject, groups, who="lgoPredictive"):
     """``groups`` (None: the object's ``obj`` column) -> (keys, labels): the distinct group keys in ``np.unique``'s order and
     the int32 label in [0, len(keys)) of every individual"""
     n = g.getN()
     if groups is None:
         groups = getattr(g, "obj", None)
         if groups is None:
-            raise ValueError("lgoPredictive: this object has no `obj` column to take the groups from; pass groups= (one label per "
+            raise ValueError(who + ": this object has no `obj` column to take the groups from; pass groups= (one label per "
                              "individual, e.g. foldLabels(n, K, seed) for K-fold cross-validation)")
     groups = np.asarray(groups)
     if groups.shape != (n,):
@@ -1034,7 +1044,8 @@ def lgoPredictive(g: GPSLCObject, groups=None, X_override=None, Y_override=None)
     — is removed and its members predicted jointly from everybody else.  ``mean``, ``var`` (n, S): mean and marginal variance
     (for the observation: yNoise included) of Y_i given all individuals outside i's group; ``lpd`` (G, S): the joint log
     density of each group's outcomes under that predictive, row j belonging to group ``keys[j]`` (the distinct labels,
-    sorted).  A group has at most 128 members.  Overrides and errors as ``looPredictive``."""
+    sorted).  A group has at most 128 members: ``kfoldPredictive`` takes groups of any size (5 or 10 folds at any n).  Overrides
+    and errors as ``looPredictive``."""
     keys, labels = _group_labels(g, groups)
     ctx = g.ctx()
     st, mean, var, lpd, _ = ctx.y_lgo(g.getNumPosteriorSamples(), g.U, *_overrides(g, X_override, Y_override), g.uyLS, g.xyLS,
@@ -1045,7 +1056,8 @@ def lgoPredictive(g: GPSLCObject, groups=None, X_override=None, Y_override=None)
 
 def foldLabels(n, K, seed=0):
     """Labels of K random cross-validation folds of near-equal size (sizes differ by at most one) for n individuals -> (n,)
-    int32 in [0, K): a random permutation dealt round-robin.  Pass as ``lgoPredictive(g, groups=...)``."""
+    int32 in [0, K): a random permutation dealt round-robin.  Pass as ``lgoPredictive(g, groups=...)`` (folds of at most 128
+    members) or take ``kfoldPredictive(g, K=K, seed=seed)``."""
     n, K = int(n), int(K)
     if not 1 <= K <= n:
         raise ValueError(f"foldLabels needs 1 <= K <= n, got K = {K}, n = {n}")
@@ -1062,6 +1074,30 @@ def lgoSummary(g: GPSLCObject, groups=None, X_override=None, Y_override=None, lg
     misses; ``zscore`` (n, S): the marginal (Y - mean) / sqrt(var); ``pit`` (n,): mean_s Phi(zscore); ``keys`` (G,)."""
     *lgo, keys = lgoPredictive(g, groups, X_override, Y_override) if lgo is None else lgo
     elpd, groupwise, z, pit = _predictive_summary(g, Y_override, *lgo)
+    return {"elpd": elpd, "groupwise": groupwise, "zscore": z, "pit": pit, "keys": keys}
+
+
+def kfoldPredictive(g: GPSLCObject, K=None, seed=0, groups=None, X_override=None, Y_override=None):
+    """K-fold cross-validation of the outcome model of every posterior sample (gpslc_y_kfold) -> ``(mean, var, lpd, keys)``, as
+    ``lgoPredictive`` gives them, for groups of ANY size.  ``K``: the folds ``foldLabels(n, K, seed)`` (``keys`` = 0 .. K - 1);
+    ``groups``: any length-n labelling (ints, strings); neither: the objects of the data (``g.obj``); both: ``ValueError``.  Groups of
+    at most 128 members are computed exactly as ``lgoPredictive`` computes them (the same bits); larger ones through a tiled
+    factorisation of their block of inv(A).  Overrides and errors as ``looPredictive``."""
+    if K is not None and groups is not None:
+        raise ValueError("kfoldPredictive takes K= (random folds) or groups= (a labelling), not both")
+    keys, labels = _group_labels(g, foldLabels(g.getN(), K, seed) if K is not None else groups, "kfoldPredictive")
+    ctx = g.ctx()
+    st, mean, var, lpd, _ = ctx.y_kfold(g.getNumPosteriorSamples(), g.U, *_overrides(g, X_override, Y_override), g.uyLS, g.xyLS,
+                                        g.tyLS, g.yScale, g.yNoise, len(keys), labels, want=("mean", "var", "lpd"))
+    ctx.check(st)
+    return mean, var, lpd, keys
+
+
+def kfoldSummary(g: GPSLCObject, K=None, seed=0, groups=None, X_override=None, Y_override=None, kfold=None):
+    """``lgoSummary``'s dictionary (``elpd``, ``groupwise``, ``zscore``, ``pit``, ``keys``) of ``kfoldPredictive`` (``kfold`` = its
+    result, to summarise one already computed)."""
+    *cv, keys = kfoldPredictive(g, K, seed, groups, X_override, Y_override) if kfold is None else kfold
+    elpd, groupwise, z, pit = _predictive_summary(g, Y_override, *cv)
     return {"elpd": elpd, "groupwise": groupwise, "zscore": z, "pit": pit, "keys": keys}
 
 

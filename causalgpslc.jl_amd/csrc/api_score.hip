@@ -1,4 +1,4 @@
-// Entry points of include/gpslc_hip.h that score: the outcome model (gpslc_y_logpdf, gpslc_y_loo, gpslc_y_lgo,
+// Entry points of include/gpslc_hip.h that score: the outcome model (gpslc_y_logpdf, gpslc_y_loo, gpslc_y_lgo, gpslc_y_kfold,
 // gpslc_y_logpdf_grad), the Gaussian-process nodes (gpslc_gp_logpdf, gpslc_nodes_*) and the dense-covariance nodes with their
 // cache (gpslc_mvn_*); the single-workgroup node path and the switch between it and the tiled score.
 #include "request.h"
@@ -555,10 +555,12 @@ int gpslc_y_logpdf_grad(gpslc_ctx* c, int64_t S, const double* U, const double* 
                          {dyNoise, &io.grad.yNoise, sS}, {dY, &io.grad.Y, nS}});
 }
 
-// leave-group-out checks: gpslc_y_loo's call with a labelling; every check before any device work
-int gpslc_y_lgo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
-                const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
-                int32_t G, const int32_t* labels, double* lgoMean, double* lgoVar, double* lgoLpd, double* logpdf_or_null) {
+// What gpslc_y_lgo and gpslc_y_kfold share: gpslc_y_loo's call with a labelling, every check before any device
+// work.  kfold: groups of any size — those beyond LGO_MAX_GROUP take the tiled path (predict.hip, kfold_large); else they are
+// refused.
+static int group_call(gpslc_ctx* c, bool kfold, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                      const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                      int32_t G, const int32_t* labels, double* gMean, double* gVar, double* gLpd, double* logpdf_or_null) {
     const PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 0, nullptr);
     int rc = validate(c, rq, kSamplesArgs);
     if (rc) return rc;
@@ -575,17 +577,36 @@ int gpslc_y_lgo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
         if (offsets[(size_t)g + 1] == 0) return bad_arg(c, 12, "a group has no member");
         offsets[(size_t)g + 1] += offsets[g];
     }
-    if (!lgoMean && !lgoVar && !lgoLpd) return bad_arg(c, 13, "lgoMean, lgoVar and lgoLpd are all NULL");
+    if (!gMean && !gVar && !gLpd)
+        return bad_arg(c, 13, kfold ? "cvMean, cvVar and cvLpd are all NULL" : "lgoMean, lgoVar and lgoLpd are all NULL");
     PredictIO io;
     io.lgo.G = G;
+    io.lgo.kfold = kfold;
+    std::vector<int> split;                     // gpslc_y_kfold: the small groups, then the large ones by ascending tile count
+    std::vector<std::pair<int, int>> large;     // (tile rows of C, group): sorted, a class is a run of equal tile counts
     for (int32_t g = 0; g < G; ++g) {
         const int m = offsets[(size_t)g + 1] - offsets[g];
-        io.lgo.mmax = std::max(io.lgo.mmax, m);
-        if (m > LGO_MAX_GROUP) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "group %d has %d members: gpslc_y_lgo takes groups of at most %d", (int)g, m, LGO_MAX_GROUP);
+        if (m > io.lgo.big_m) { io.lgo.big_m = m; io.lgo.big_group = g; }
+        if (m <= LGO_MAX_GROUP) {
+            io.lgo.mmax = std::max(io.lgo.mmax, m);
+            split.push_back(g);
+        } else if (kfold) {
+            large.emplace_back((m + GP_TS - 1) / GP_TS, g);
+        } else {
+            char buf[200];
+            snprintf(buf, sizeof buf, "group %d has %d members: gpslc_y_lgo takes groups of at most %d (use gpslc_y_kfold)", (int)g, m,
+                     LGO_MAX_GROUP);
             set_err(c, buf);
             return GPSLC_ERR_UNSUPPORTED;
+        }
+    }
+    if (kfold) {
+        io.lgo.nsmall = (int)split.size(); io.lgo.nlarge = (int)large.size();
+        std::sort(large.begin(), large.end());
+        for (const auto& lg : large) {
+            if (io.lgo.classes.empty() || io.lgo.classes.back().mt != lg.first) io.lgo.classes.push_back({lg.first, (int)split.size(), 0});
+            ++io.lgo.classes.back().count;
+            split.push_back(lg.second);
         }
     }
     {
@@ -594,14 +615,31 @@ int gpslc_y_lgo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_nul
     }
     const size_t nS = (size_t)n * (size_t)S, GS = (size_t)G * (size_t)S;
     return outcome_call(c, rq, X_or_null, Y_or_null, logpdf_or_null, io,
-                        {{lgoMean, &io.lgo.mean, nS}, {lgoVar, &io.lgo.var, nS}, {lgoLpd, &io.lgo.lpd, GS}}, [&]() {
+                        {{gMean, &io.lgo.mean, nS}, {gVar, &io.lgo.var, nS}, {gLpd, &io.lgo.lpd, GS}}, [&]() {
                             auto upload = [&](const std::vector<int>& v) {      // the member list and its offsets
                                 int* d = c->io.take<int>(v.size());
                                 HC(hipMemcpy(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
                                 return d;
                             };
                             io.lgo.members = upload(members); io.lgo.offsets = upload(offsets);
+                            if (kfold) io.lgo.split = upload(split);
                         });
+}
+
+// leave-group-out checks, groups of at most LGO_MAX_GROUP members
+int gpslc_y_lgo(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                int32_t G, const int32_t* labels, double* lgoMean, double* lgoVar, double* lgoLpd, double* logpdf_or_null) {
+    return group_call(c, false, S, U, X_or_null, Y_or_null, uyLS, xyLS, tyLS, yScale, yNoise, G, labels, lgoMean, lgoVar, lgoLpd,
+                      logpdf_or_null);
+}
+
+// K-fold cross-validation: gpslc_y_lgo for groups of any size
+int gpslc_y_kfold(gpslc_ctx* c, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                  const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                  int32_t G, const int32_t* labels, double* cvMean, double* cvVar, double* cvLpd, double* logpdf_or_null) {
+    return group_call(c, true, S, U, X_or_null, Y_or_null, uyLS, xyLS, tyLS, yScale, yNoise, G, labels, cvMean, cvVar, cvLpd,
+                      logpdf_or_null);
 }
 
 int gpslc_gp_logpdf(gpslc_ctx* c, int64_t S, int32_t nF, const double* F, int32_t f_shared, const double* ls,

@@ -353,7 +353,7 @@ void launch_loo_finish(const LooArgs& a, int nbatch, hipStream_t st);     // alp
 // ---------------------------------------------------------------------------------------
 // Leave-group-out predictive checks (k_lgo.hip): for a group I of m <= LGO_MAX_GROUP individuals,
 // C = [A^-1]_II = W[I, :] W[I, :]^T from the same packed W, then its m x m Cholesky factor in LDS.  One workgroup per
-// (group, sample).  Larger groups would need a tiled factorisation of C: refused at the C boundary.
+// (group, sample).  Larger groups need a tiled factorisation of C: refused at gpslc_y_lgo's boundary, taken by gpslc_y_kfold (below).
 // ---------------------------------------------------------------------------------------
 #define LGO_MAX_GROUP GP_TS
 struct LgoArgs {
@@ -365,8 +365,36 @@ struct LgoArgs {
     const double* Y; long long y_sstride;
     const int* info;                            // S: a sample whose factorisation broke down gets NaN
     double* lgoMean; double* lgoVar; double* lgoLpd;   // n x S, n x S, G x S (element (g, s) at g + G*s) or null
+    const int* gmap; int ngroups;               // null: workgroup x is group x, all G of them (gpslc_y_lgo); else the launch covers
+                                                // the ngroups groups gmap[x] (gpslc_y_kfold's groups of at most LGO_MAX_GROUP)
 };
 void launch_lgo_groups(const LgoArgs& a, int nbatch, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
+// K-fold cross-validation (k_kfold.hip): the groups of more than LGO_MAX_GROUP members.  C = W[I, :] W[I, :]^T is
+// built as an mt x mt triangle of tiles with alpha_I as its augmented row, factorised by factor_panels, and read by the
+// back-substitution, the epilogue and §18's launches.  The groups of a launch share mt = ceil(m / 128); batch element b is pair
+// p0 + b of the class: (sample (p0 + b) / ng of the chunk, group large[(p0 + b) % ng]).
+// ---------------------------------------------------------------------------------------
+struct KfoldArgs {
+    const double* W; long long w_bstride;       // of A: [sample of the chunk][nt (nt + 1) / 2 tiles], loo_w_index
+    int n, nt; long long s0;
+    int G;                                      // groups of the call (the stride of cvLpd)
+    const int* members; const int* offsets;     // as LgoArgs
+    const int* large; int ng; long long p0;     // the class's groups, their count, the launch's first pair
+    int mt;                                     // tile rows of C
+    const double* alpha;                        // [sample of the chunk][Np]
+    const double* Y; long long y_sstride;
+    const int* info;                            // S: a sample whose factorisation of A broke down gets NaN
+    TRef Cm;                                    // lower packed, mt + 1 tile rows: C, and alpha_I in row 0 of tile row mt
+    // kfold_finish_kernel: per pair of the launch, [b][mt 128] and [b]
+    const double* u; const double* cdiag;       // C^-1 alpha_I (launch_backsolve), diag(C^-1) (launch_loo_rownorm)
+    const double* logdet; const double* quad;   // log det C, alpha_I^T C^-1 alpha_I (launch_epilogue)
+    const int* pinfo;                           // nonzero: the factorisation of C broke down, the group gets NaN for this sample
+    double* cvMean; double* cvVar; double* cvLpd;      // n x S, n x S, G x S or null
+};
+void launch_kfold_gram(const KfoldArgs& a, int nbatch, hipStream_t st);       // Cm <- C (identity on the padding) and alpha_I
+void launch_kfold_finish(const KfoldArgs& a, int nbatch, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // Gradient of the outcome log-likelihood (k_grad.hip): with Q = alpha alpha^T - A^-1, K = A - yNoise I and

@@ -27,6 +27,13 @@ struct HipFail {
         if (_e != hipSuccess) throw HipFail{_e, #x, __FILE__, __LINE__}; \
     } while (0)
 
+// a call whose workspace cannot fit, with a message that says what was too large (guarded: GPSLC_ERR_NOMEM with this text)
+struct WorkspaceTooLarge : std::bad_alloc {
+    std::string msg;
+    explicit WorkspaceTooLarge(std::string m) : msg(std::move(m)) {}
+    const char* what() const noexcept override { return msg.c_str(); }
+};
+
 // The two memory policies of dev_mem.h.  A failed allocation also clears the runtime's sticky error.
 struct DeviceMem {
     static void* alloc(size_t bytes) {
@@ -189,6 +196,9 @@ int guarded(gpslc_ctx* c, F&& f) {
         return f();
     } catch (const HipFail& h) {
         return fail_hip(c, h);
+    } catch (const WorkspaceTooLarge& w) {
+        set_err(c, w.msg);
+        return GPSLC_ERR_NOMEM;
     } catch (const std::bad_alloc&) {
         set_err(c, "device workspace allocation failed");
         return GPSLC_ERR_NOMEM;

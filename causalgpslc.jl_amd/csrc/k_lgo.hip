@@ -36,7 +36,7 @@ static size_t lgo_lds_bytes(int mp) { return ((size_t)lgo_region(mp) + 4 * (size
 
 __global__ __launch_bounds__(LGO_THREADS) void lgo_group_kernel(LgoArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int g = a.gmap ? a.gmap[blockIdx.x] : (int)blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
@@ -219,11 +219,12 @@ __global__ __launch_bounds__(LGO_THREADS) void lgo_group_kernel(LgoArgs a) {
 }
 
 void launch_lgo_groups(const LgoArgs& a, int nbatch, hipStream_t st) {
-    if (nbatch <= 0 || a.G <= 0) return;
+    const int ng = a.gmap ? a.ngroups : a.G;        // a subset of the groups (gpslc_y_kfold's small ones), or all of them
+    if (nbatch <= 0 || ng <= 0) return;
     // one launch covers groups of every size up to mmax: the LDS of the largest layout among them
     size_t bytes = 0;
     for (int mp = 16; mp <= ((a.mmax + 15) & ~15); mp += 16) bytes = std::max(bytes, lgo_lds_bytes(mp));
     static DeviceOnce once;
     lds_opt_in(once, (const void*)lgo_group_kernel, (int)lgo_lds_bytes(LGO_MAX_GROUP));
-    hipLaunchKernelGGL(lgo_group_kernel, dim3(a.G, nbatch), dim3(LGO_THREADS), bytes, st, a);
+    hipLaunchKernelGGL(lgo_group_kernel, dim3(ng, nbatch), dim3(LGO_THREADS), bytes, st, a);
 }

@@ -61,6 +61,16 @@ struct Lgo {                         // leave-group-out predictive checks (gpslc
     const int *members = nullptr, *offsets = nullptr;      // the members sorted by (group, row), the G + 1 offsets into them
     double *mean = nullptr, *var = nullptr, *lpd = nullptr;
     bool any() const { return mean || var || lpd; }
+    // gpslc_y_kfold (kfold == false: every group goes through lgo_group_kernel, gpslc_y_lgo's launch).  The groups
+    // of at most LGO_MAX_GROUP members are the nsmall entries of `split` (mmax: the largest of THEM), the larger ones follow in
+    // classes of equal tile count mt = ceil(m / 128): the batch elements of the tiled path's launches share it
+    struct Class { int mt, first, count; };     // `count` groups from split[first] on
+    bool kfold = false;
+    const int* split = nullptr;                 // device: group numbers, the small ones first, then class by class
+    int nsmall = 0, nlarge = 0;
+    std::vector<Class> classes;
+    int big_group = 0, big_m = 0;               // the largest group and its size: named when its workspace does not fit
+    int mt_max() const { return classes.empty() ? 0 : classes.back().mt; }      // ascending mt
 };
 struct Grad {                        // gradient of the outcome log-likelihood (gpslc_y_logpdf_grad), in the layouts of
     // the arguments they differentiate: U n x nU x S, uyLS nU x S, xyLS nX x S, the others S; Y n x S

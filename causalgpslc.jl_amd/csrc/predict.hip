@@ -50,6 +50,8 @@ struct PredictShape {
     int mt;                           // new individuals: their row tiles, the tiles of an mt x mt triangle, and whether the
     long long mlow;                   // (sample, level) pairs need tile workspace (variance, covariance)
     bool want_new, new_pairs;
+    bool kfold_pairs;                 // gpslc_y_kfold with groups beyond LGO_MAX_GROUP: (group, sample) pairs with tile workspace
+    int kf_mt;                        // ... and the tile rows of the largest group's C
     PredictShape(const gpslc_ctx* c, const PredictIO& io)
         : n((int)c->n), nt(c->nt), L(io.lv.L), R(io.lv.W ? io.lv.L * io.lv.G : io.lv.L), naug((R + 1 + GP_TS - 1) / GP_TS), ntot(nt + naug),
           Np((long long)nt * GP_TS), tiles_per((long long)ntot * (ntot + 1) / 2), nlow((long long)nt * (nt + 1) / 2),
@@ -58,7 +60,7 @@ struct PredictShape {
           want_loo(io.loo.any()), want_lgo(io.lgo.any()), want_grad(io.grad.any()), grad_pairs(io.grad.pairs()),
           grad_c(io.grad.needs_c()), want_w(want_loo || want_lgo || want_grad), want_alpha(want_mean || want_w || io.fresh.mean),
           mt((io.fresh.m + GP_TS - 1) / GP_TS), mlow((long long)mt * (mt + 1) / 2), want_new(io.fresh.any()),
-          new_pairs(io.fresh.pairs()) {}
+          new_pairs(io.fresh.pairs()), kfold_pairs(io.lgo.any() && io.lgo.kfold && io.lgo.nlarge > 0), kf_mt(io.lgo.mt_max()) {}
 };
 
 // one chunk of a call: samples s0 .. s0 + nb - 1 on one stream slot, and the buffers carve_chunk takes for it from the slot's arena
@@ -78,6 +80,10 @@ struct Chunk {
     int lc_max = 0, gs_max = 0;
     double *Wt = nullptr, *Ct = nullptr, *zt = nullptr, *dtmp = nullptr;
     int* pinfo = nullptr;
+    // gpslc_y_kfold's large groups: a sub-batch of kf_max (group, sample) pairs; C with its augmented row, its inverted diagonal
+    // tiles, its L^-T, [z | C^-1 alpha_I] (launch_backsolve's layout), diag(C^-1), log det C and the quadratic form, failure codes
+    int kf_max = 0;
+    double *kf_c = nullptr, *kf_inv = nullptr, *kf_w = nullptr, *kf_zu = nullptr, *kf_diag = nullptr, *kf_ldq = nullptr;
     SampleGrid grid{};               // the chunk's samples and feature blocks, as every RBF-evaluating kernel takes them
 };
 
@@ -120,6 +126,20 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
         if (io.nU > 0) b.grad_u = take((size_t)nt * nt * io.nU * GP_TS);
     }
     b.M = lower_ref(b.tiles, sh.tiles_per * GP_TSQ);
+    if (sh.kfold_pairs) {     // sized for the largest group: a class of fewer tile rows uses the front of every buffer
+        const size_t mt = (size_t)sh.kf_mt, c_tiles = (mt + 1) * (mt + 2) / 2, w_tiles = mt * (mt + 1) / 2, Nc = mt * GP_TS;
+        by.per_pair = (c_tiles + mt + w_tiles) * GP_TSQ * 8 + (3 * Nc + 2) * 8 + sizeof(int);
+        if (!ar) return by;
+        b.kf_max = Bb;
+        b.kf_c = ar->take<double>((size_t)Bb * c_tiles * GP_TSQ);
+        b.kf_inv = ar->take<double>((size_t)Bb * mt * GP_TSQ);
+        b.kf_w = ar->take<double>((size_t)Bb * w_tiles * GP_TSQ);
+        b.kf_zu = ar->take<double>((size_t)Bb * 2 * Nc);
+        b.kf_diag = ar->take<double>((size_t)Bb * Nc);
+        b.kf_ldq = ar->take<double>((size_t)Bb * 2);
+        b.pinfo = ar->take<int>((size_t)Bb);
+        return by;
+    }
     if (sh.new_pairs) {       // new individuals: W* (mt x nt) and, with the covariance, an mt triangle per (sample, level) pair
         const size_t w_tiles = (size_t)sh.mt * nt, c_tiles = io.fresh.cov ? (size_t)sh.mlow : 0;
         by.per_pair = (w_tiles + c_tiles) * GP_TSQ * 8 + 512;
@@ -341,7 +361,54 @@ void loo(const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
         LgoArgs ga = on_w<LgoArgs>(io, sh, ch);
         ga.G = io.lgo.G; ga.mmax = io.lgo.mmax; ga.members = io.lgo.members; ga.offsets = io.lgo.offsets;
         ga.lgoMean = io.lgo.mean; ga.lgoVar = io.lgo.var; ga.lgoLpd = io.lgo.lpd;
+        if (io.lgo.kfold) { ga.gmap = io.lgo.split; ga.ngroups = io.lgo.nsmall; }      // the larger groups: kfold_large below
         launch_lgo_groups(ga, nb, st);
+    }
+    HC(hipGetLastError());
+}
+
+// gpslc_y_kfold's groups of more than LGO_MAX_GROUP members, after loo() has left W and alpha of the chunk.  Per
+// class of equal tile count mt, sub-batches of (group, sample) pairs: C = W[I, :] W[I, :]^T into the pair's tiles with alpha_I as
+// the augmented row (launch_kfold_gram); the panel schedule's factorisation of C with the forward solve it carries; log det C and
+// the quadratic form from the epilogue, C^-1 alpha_I from the back-substitution, diag(C^-1) as the squared row norms of C's own
+// L^-T (loo()'s launches on C's factor); kfold_finish_kernel writes the outputs.  Everything of a pair depends on its member set
+// and its sample alone: the sub-batch, the class and the chunk only decide which launch carries it.
+void kfold_large(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
+    hipStream_t st = ch.s->st;
+    KfoldArgs ka = on_w<KfoldArgs>(io, sh, ch);
+    ka.G = io.lgo.G; ka.members = io.lgo.members; ka.offsets = io.lgo.offsets;
+    ka.cvMean = io.lgo.mean; ka.cvVar = io.lgo.var; ka.cvLpd = io.lgo.lpd;
+    for (const Lgo::Class& cl : io.lgo.classes) {
+        const int mt = cl.mt;
+        const long long c_bs = (long long)(mt + 1) * (mt + 2) / 2 * GP_TSQ, w_bs = (long long)mt * (mt + 1) / 2 * GP_TSQ,
+                        inv_bs = (long long)mt * GP_TSQ, Nc = (long long)mt * GP_TS, pairs = (long long)cl.count * ch.nb;
+        ka.large = io.lgo.split + cl.first; ka.ng = cl.count; ka.mt = mt;
+        ka.Cm = lower_ref(ch.kf_c, c_bs);
+        for (long long p0 = 0; p0 < pairs; p0 += ch.kf_max) {
+            const int ub = (int)std::min<long long>(ch.kf_max, pairs - p0);
+            ka.p0 = p0;
+            launch_kfold_gram(ka, ub, st);
+            HC(hipMemsetAsync(ch.pinfo, 0, sizeof(int) * ub, st));
+            factor_panels(c, *ch.s, ka.Cm, mt, mt + 1, ch.kf_inv, ch.pinfo, 0, ub, 1, true, 3);
+            EpiArgs ea{};
+            ea.M = ka.Cm; ea.n = (int)Nc; ea.nt = mt; ea.naug = 1; ea.from_rows = 1;
+            ea.logdet = ch.kf_ldq; ea.quad = ch.kf_ldq + ub;       // sample index = batch element: s0 = 0
+            launch_epilogue(ea, ub, st);
+            BackArgs ba{};
+            ba.M = ka.Cm; ba.inv = ch.kf_inv; ba.inv_bstride = inv_bs; ba.nt = mt; ba.naug = 1; ba.zwork = ch.kf_zu;
+            launch_backsolve(ba, ub, st);
+            LooArgs la{};
+            la.inv = ch.kf_inv; la.inv_bstride = inv_bs; la.W = ch.kf_w; la.w_bstride = w_bs; la.nt = mt; la.c = ch.kf_diag;
+            HC(hipMemsetAsync(ch.kf_w, 0, sizeof(double) * (size_t)ub * w_bs, st));
+            launch_loo_init(la, ub, st);
+            rearm_queue(*ch.s);
+            const TRef W = lower_ref(ch.kf_w, w_bs), invref = inv_ref(ch.kf_inv, mt);
+            for (int d = 1; d < mt; ++d)
+                launch_loo_diagonal(on_slot(fused(tile_column(W, ka.Cm, W, 0, 0, mt - d, 0, 0, ub, false), invref, 0), *ch.s), mt, d, st);
+            launch_loo_rownorm(la, ub, st);
+            ka.u = ch.kf_zu + (long long)ub * Nc; ka.cdiag = ch.kf_diag; ka.logdet = ea.logdet; ka.quad = ea.quad; ka.pinfo = ch.pinfo;
+            launch_kfold_finish(ka, ub, st);
+        }
     }
     HC(hipGetLastError());
 }
@@ -509,7 +576,18 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
     // chunk size and sub-batch from what the device has (the sub-batch's workspace is sized from the pairs the call
     // really has, and the 30 % rule of the automatic chunk covers its per-sample part only)
     const ChunkBytes by = carve_chunk(sh, io, 0, nullptr);
-    const BatchPlan plan = auto_batch(c, io.post.S, sh.L, by.per_sample, by.per_pair, by.per_level);
+    // gpslc_y_kfold: the pairs of a sub-batch are (group, sample), a sample has as many as there are large groups
+    const int pairs_per_sample = sh.kfold_pairs ? io.lgo.nlarge : sh.L;
+    BatchPlan plan;
+    try {
+        plan = auto_batch(c, io.post.S, pairs_per_sample, by.per_sample, by.per_pair, by.per_level);
+    } catch (const std::bad_alloc&) {
+        if (!sh.kfold_pairs) throw;
+        char buf[200];
+        snprintf(buf, sizeof buf, "device workspace allocation failed: group %d has %d members, the workspace of one (group, sample) "
+                 "pair is %.1f MB", io.lgo.big_group, io.lgo.big_m, (double)by.per_pair / 1e6);
+        throw WorkspaceTooLarge(buf);
+    }
     const int Bt = (int)plan.Bt, Bb = (int)plan.Bb;      // Bb: (sample, level) pairs per unit-B sub-batch, no more than the call has
     const size_t need = (size_t)Bt * by.per_sample + plan.fixed;
     for (int i = 0; i < c->nstreams; ++i) c->slots[i].arena.reserve(need);
@@ -531,6 +609,7 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         if (sh.want_alpha && !back_done) back_substitute(sh, ch);
         if (sh.want_mean) mean_ite(c, io, sh, ch);
         if (sh.want_w) loo(io, sh, ch);
+        if (sh.kfold_pairs) kfold_large(c, io, sh, ch);
         if (sh.want_grad) grad(io, sh, ch);
         if (sh.unitB) unit_b(c, io, sh, ch);
         if (sh.want_new) unit_new(c, io, sh, ch);

@@ -164,8 +164,8 @@ int gpslc_y_loo(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_or_n
  * Arguments 1-10, validation, overrides and logpdf_or_null are gpslc_y_loo's (logpdf_or_null is bit-identical to that call's);
  * works on a GPSLC_FLAG_FP32_KERNEL context.  Any output may be NULL.  Errors: G < 1 or G > n: -11; labels NULL, a label
  * outside [0, G) or a group without a member: -12; lgoMean, lgoVar and lgoLpd all NULL: -13; a group of more than 128 members:
- * GPSLC_ERR_UNSUPPORTED, gpslc_last_error names the group and its size (larger groups would need a tiled factorisation of C:
- * out of scope).  S = 0 is an empty call.
+ * GPSLC_ERR_UNSUPPORTED, gpslc_last_error names the group and its size (larger groups need the tiled factorisation of C:
+ * gpslc_y_kfold below).  S = 0 is an empty call.
  * A parameter set whose factorisation of A breaks down gets NaN in all its outputs; return value (first failing pivot) and
  * gpslc_last_info as for gpslc_y_loo.  A group whose C loses positive definiteness in the small factorisation gets NaN in its
  * outputs for that parameter set; the return value and gpslc_last_info do not change.
@@ -179,6 +179,30 @@ int gpslc_y_lgo(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_or_n
                 int32_t G, const int32_t* labels /* n, values in [0, G) */,
                 double* lgoMean /* n x S */, double* lgoVar /* n x S */, double* lgoLpd /* G x S */,
                 double* logpdf_or_null /* S */);
+
+/* K-fold cross-validation of the same outcome model: gpslc_y_lgo for groups of ANY size, 1 .. n members — 5 or 10 folds at any
+ * n, a hospital of 129 patients.  Signature, argument numbering, validation order, overrides, logpdf_or_null, outputs, layouts
+ * and the errors -11 / -12 / -13 are gpslc_y_lgo's; works on a GPSLC_FLAG_FP32_KERNEL context.
+ * Groups of at most 128 members go through gpslc_y_lgo's kernel: a call whose groups are all that small returns that call's
+ * outputs bit for bit.  For a larger group, C = [A^-1]_II is built as 128 x 128 tiles in device memory (mt = ceil(m / 128) tile
+ * rows) with alpha_I beside it, and factorised, solved with and inverted on its diagonal by the kernels that do the same for A:
+ * cvMean = Y_I - C^-1 alpha_I, cvVar = diag(C^-1) as squared row norms of C's own L^-T, cvLpd from log det C and the quadratic
+ * form.  The (group, sample) pairs of the larger groups run in sub-batches whose workspace (about (mt^2 + 3 mt) x 128 KiB per pair)
+ * is sized from the free device memory; a call in which not even one pair fits returns GPSLC_ERR_NOMEM, before any launch, and
+ * gpslc_last_error names the largest group and its size.
+ * A parameter set whose factorisation of A breaks down gets NaN in all its outputs; return value and gpslc_last_info as for
+ * gpslc_y_lgo.  A group whose C loses positive definiteness gets NaN for that parameter set; the return value and
+ * gpslc_last_info do not change.
+ * Guarantees, for groups of every size: the outputs are bit-reproducible and independent of chunking, stream count, sub-batching
+ * of the pairs and factorisation schedule; a group's outputs depend only on its member set, the members taken in ascending row
+ * order: not on its label number, not on how the other individuals are grouped.  One group of everybody gives cvLpd = logpdf,
+ * cvMean = 0 and cvVar = diag(A), to rounding, at any n.  Nothing is continuous in the bits across m = 128 / 129: the two paths
+ * sum in different orders.  There is no _dev variant, no sharding over several contexts and no joint covariance output. */
+int gpslc_y_kfold(gpslc_ctx* ctx, int64_t S, const double* U, const double* X_or_null, const double* Y_or_null,
+                  const double* uyLS, const double* xyLS, const double* tyLS, const double* yScale, const double* yNoise,
+                  int32_t G, const int32_t* labels /* n, values in [0, G) */,
+                  double* cvMean /* n x S */, double* cvVar /* n x S */, double* cvLpd /* G x S */,
+                  double* logpdf_or_null /* S */);
 
 /* Gradient of the :Y node's score log N(Y; 0, A), A = K + yNoise I, K_ij = yScale exp(-sum_f ((w_if - w_jf) / ls_f)^2) over
  * the features w = [U | X | T] with ls = [uyLS; xyLS; tyLS], for S parameter sets: what a gradient-based move on U and the

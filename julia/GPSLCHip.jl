@@ -200,6 +200,25 @@ function y_lgo(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS, ty
     lgoMean, lgoVar, lgoLpd, lp
 end
 
+"""K-fold cross-validation of the :Y node's outcome model for S parameter sets (gpslc_y_kfold): `y_lgo` for groups of any size
+(1 to n members; groups of at most 128 members give `y_lgo`'s bits).  Returns `(cvMean, cvVar, cvLpd, logpdf)`, n x S, n x S,
+G x S and length S, as `y_lgo` returns them."""
+function y_kfold(c::Ctx, S::Integer, U, X_or_nothing, Y_or_nothing, uyLS, xyLS, tyLS::Vector{Float64},
+                 yScale::Vector{Float64}, yNoise::Vector{Float64}, G::Integer, labels::AbstractVector{<:Integer})
+    length(labels) == c.n || throw(ArgumentError("labels must have one entry per individual"))
+    lab = Vector{Int32}(labels)
+    cvMean, cvVar = (Matrix{Float64}(undef, c.n, S) for _ in 1:2)
+    cvLpd = Matrix{Float64}(undef, G, S)
+    lp = Vector{Float64}(undef, S)
+    Uf, Xf, Yf, uy, xy = f64(U), f64(X_or_nothing), f64(Y_or_nothing), f64(uyLS), f64(xyLS)
+    GC.@preserve Uf Xf Yf uy xy tyLS yScale yNoise lab cvMean cvVar cvLpd lp check(c, ccall((:gpslc_y_kfold, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(Uf), ptr(Xf), ptr(Yf), ptr(uy), ptr(xy), pointer(tyLS), pointer(yScale), pointer(yNoise),
+        G, pointer(lab), pointer(cvMean), pointer(cvVar), pointer(cvLpd), pointer(lp)))
+    cvMean, cvVar, cvLpd, lp
+end
+
 """Gradient of the :Y node's score for S parameter sets (gpslc_y_logpdf_grad): `(dU, duyLS, dxyLS, dtyLS, dyScale, dyNoise, dY,
 logpdf)` in the layouts of the arguments they differentiate — dU n x nU x S, duyLS nU x S, dxyLS nX x S, dY n x S, the others
 length S — with respect to the parameters themselves (multiply by the parameter for a gradient in its logarithm)."""
