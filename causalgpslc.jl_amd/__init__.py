@@ -10,7 +10,7 @@ from .api import (  # noqa: F401
     rbfKernelLog, rbfKernelLogScalar, logit, expit, processCov, likelihoodDistribution, extractParameters, conditionalITE, ITEDistributions, ITEsamples, conditionalSATE,
     SATEDistributions, SATEsamples, sampleITE, sampleSATE, predictCounterfactualEffects, groupWeights,
     effectCurve, sampleEffectCurve, curveSamples,
-    summarizeEstimates, yLogpdf, yLogpdfGrad, looPredictive, looSummary, lgoPredictive, lgoSummary, foldLabels, kfoldPredictive, kfoldSummary, predictNew, averageNew, gpLogpdf, nodesLogpdf, nodesLogpdfGrad, nodesDraw, mvnLogpdf, mvnDraw, predict, doTRange, getN, getNX, getNU, getNumPosteriorSamples,
+    summarizeEstimates, yLogpdf, yLogpdfGrad, looPredictive, looSummary, lgoPredictive, lgoSummary, foldLabels, kfoldPredictive, kfoldSummary, predictNew, averageNew, testPredictive, testSummary, gpLogpdf, nodesLogpdf, nodesLogpdfGrad, nodesDraw, mvnLogpdf, mvnDraw, predict, doTRange, getN, getNX, getNU, getNumPosteriorSamples,
 )
 from . import synth  # noqa: F401
 from .pack import saveGPSLCObject, loadGPSLCObject, readPackHeader  # noqa: F401

@@ -94,6 +94,9 @@ SIGNATURES = {
                                             C.c_int32, C.c_uint64, _D, _D, _D, _D, _D]),
     "gpslc_predict_new": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, C.c_int64, _D, _D, C.c_int32, C.c_int32,
                                     _D, _D, C.c_double, _D, _D, _D]),
+    "gpslc_predict_new_vec": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, C.c_int64, _D, _D, C.c_int32, C.c_int32,
+                                        _D, _D, C.c_double, _D, _D, _D]),
+    "gpslc_y_test": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, C.c_int64, _D, _D, _D, _D, _D, _D, _D, _D]),
     "gpslc_predict_new_weighted": (C.c_int, [C.c_void_p, C.c_int64, _D, _D, _D, _D, _D, _D, C.c_int64, _D, _D, C.c_int32,
                                              C.c_int32, _D, _D, C.c_int32, _D, C.c_double, _D, _D, _D]),
     "gpslc_shard_range": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, c_int64_p, c_int64_p]),

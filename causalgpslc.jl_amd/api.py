@@ -373,6 +373,28 @@ class Context:
                                  doT_base, float(pred_noise), fill=None)      # written in full by every call that returns a status >= 0
         return (st, *out.values())
 
+    def predict_new_vec(self, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, doT, doT_base, pred_noise,
+                        want=("mean", "var")):
+        """gpslc_predict_new_vec — ``predict_new`` at per-individual levels: ``doT`` (and ``doT_base``) are (m, L) column-major,
+        new individual i at level l is set to ``doT[i, l]``.  Forms "outcome" and "contrast"; outputs and status as there."""
+        S, m = int(S), int(m)
+        L = 0 if doT is None or np.ndim(doT) != 2 else int(np.shape(doT)[1])
+        dims = (max(m, 0), max(S, 0), L)
+        st, out = self._call_for(self.lib.gpslc_predict_new_vec, {"mean": dims, "var": dims, "cov": (dims[0],) + dims}, want,
+                                 S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, int(NEW_FORMS.get(form, form)), L, doT,
+                                 doT_base, float(pred_noise), fill=None)      # written in full by every call that returns a status >= 0
+        return (st, *out.values())
+
+    def y_test(self, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xtest, Utest, Ttest, Ytest, want=("mean", "var", "lpd", "joint")):
+        """gpslc_y_test with host arrays as given (None = NULL): ``(status, mean, var, lpd, lpd_joint)`` — the outputs named in
+        ``want`` as (m, S) / (S,) arrays, the others None (NULL to the library).  The status is returned, not raised, as for
+        ``predict_new``."""
+        S, m = int(S), int(m)
+        mS = (max(m, 0), max(S, 0))
+        st, out = self._call_for(self.lib.gpslc_y_test, {"mean": mS, "var": mS, "lpd": mS, "joint": mS[1:]}, want,
+                                 S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xtest, Utest, Ttest, Ytest, fill=None)
+        return (st, *out.values())
+
     def predict_new_weighted(self, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, doT, doT_base, weights, pred_noise,
                              want=("mean", "var"), G=None):
         """gpslc_predict_new_weighted with host arrays as given (None = NULL): ``(status, meanW, varW, covW)`` — the outputs named
@@ -1000,10 +1022,11 @@ def yLogpdfGrad(g: GPSLCObject, X_override=None, Y_override=None, log_params=Fal
     return out
 
 
-def _predictive_summary(g: GPSLCObject, Y_override, mean, var, lpd):
-    """what looSummary and lgoSummary share -> (elpd (S,), log mean_s exp(lpd) per row of lpd, zscore (n, S), pit (n,))"""
+def _predictive_summary(g: GPSLCObject, Y_override, mean, var, lpd, rows=None):
+    """what looSummary, lgoSummary and testSummary share -> (elpd (S,), log mean_s exp(lpd) per row of lpd, zscore (n, S), pit
+    (n,)); ``rows``: the outcomes are those of that many other individuals (a test set), not of the n in the data"""
     from math import erf
-    Y = g.Y if Y_override is None else _f(Y_override, (g.getN(),))
+    Y = g.Y if Y_override is None else _f(Y_override, (g.getN() if rows is None else rows,))
     z = (Y[:, None] - mean) / np.sqrt(var)
     top = np.max(lpd, axis=1)
     rowwise = top + np.log(np.mean(np.exp(lpd - top[:, None]), axis=1))
@@ -1111,8 +1134,14 @@ _NEW_REFUSALS = (
     (lambda q: q.fp32, ValueError, "predictNew needs an fp64 model: new individuals are not supported with fp32_kernel=True"),
     (lambda q: q.slope and q.base, ValueError,
      "slope=True cannot be combined with baseline=: the slope is a derivative at one level, not a contrast"),
-    (lambda q: q.ndim > 1, ValueError,
-     "predictNew needs scalar levels: a new individual has no factual treatment and no per-individual intervention vector; "
+    (lambda q: q.tnew and q.base, ValueError,
+     "Tnew= cannot be combined with baseline=: Tnew is the baseline, each new individual's own treatment"),
+    (lambda q: q.tnew and q.slope, ValueError,
+     "Tnew= cannot be combined with slope=True: the slope is a derivative at one level, not a contrast"),
+    (lambda q: q.slope and q.ndim == 2 and q.vec_ok, ValueError,
+     "slope=True needs scalar levels: slopes at per-individual levels are not supported"),
+    (lambda q: q.ndim > (2 if q.vec_ok else 1), ValueError,
+     "{who} needs scalar levels{or_vec}: a new individual has no factual treatment unless Tnew= gives it; "
      "the ordinary effect f(a) - f(T) is the contrast with baseline = its treatment"),
     (lambda q: q.nX > 0 and not q.X, ValueError, "Xnew= is required: the model has nX = {nX} covariates"),
     (lambda q: q.nX == 0 and q.X, ValueError, "Xnew= cannot be given: the model has no covariates"),
@@ -1123,7 +1152,8 @@ _NEW_REFUSALS = (
 )
 
 
-def predictNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, baseline=None, slope=False, want_var=True, want_cov=False):
+def predictNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, baseline=None, slope=False, want_var=True, want_cov=False,
+               Tnew=None):
     """Predictions for m individuals who are not in the data (gpslc_predict_new) -> ``mean`` (m, S, L), ``var`` (m, S, L)
     [, ``cov`` (S, L, m, m) with ``want_cov=True``]: per posterior sample and level, the latent surface's value at the new
     covariates — the potential outcome f*(doT) by default, the contrast f*(doT) - f*(baseline) (the CATE at x*) with
@@ -1133,14 +1163,20 @@ def predictNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, baseline=N
 
     ``Xnew`` (m, nX) is required iff the model has covariates.  With latent confounders exactly one of ``like`` (m training
     indices, 0-based: individual i takes U[like[i], :, s], a new member of a known object) and ``Unew`` (m, nU, S) is required.
-    A model with neither has one kind of new individual: m = 1.  The ordinary effect f(a) - f(T) needs the new individual's own
-    treatment: ask for the contrast with ``baseline=`` that treatment.  Refusals are raised before any library call; a failed
-    factorisation raises ``PosDefException``."""
-    levels, base, X, U, m, form = _new_request(g, doTs, Xnew, like, Unew, baseline, slope)
+    A model with neither has one kind of new individual: m = 1.
+
+    Per-individual levels (gpslc_predict_new_vec): ``doTs`` may be an (L, m) array, level l setting new individual i to
+    ``doTs[l, i]`` — a policy for a new population; ``baseline=`` may then be a scalar, (L,) or (L, m).  ``Tnew=`` (m,) gives
+    the new individuals' own factual treatments and turns the call into the ordinary effect f*(a) - f*(Tnew_i), for scalar or
+    per-individual ``doTs``; it excludes ``baseline=`` and ``slope=True``.  The value of a policy over the new population with
+    its variance is ``w @ mean`` and ``w @ cov @ w`` on the host (``averageNew`` takes scalar levels only).  Refusals are raised
+    before any library call; a failed factorisation raises ``PosDefException``."""
+    levels, base, X, U, m, form, vec = _new_request(g, doTs, Xnew, like, Unew, baseline, slope, Tnew, who="predictNew")
     want = ("mean",) + (("var",) if want_var or want_cov else ()) + (("cov",) if want_cov else ())
     ctx = g.ctx()
-    st, mean, var, cov = ctx.predict_new(g.getNumPosteriorSamples(), g.U, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise, m, X, U, form,
-                                         levels, base, g.hyperparams.predictionCovarianceNoise, want=want)
+    st, mean, var, cov = (ctx.predict_new_vec if vec else ctx.predict_new)(
+        g.getNumPosteriorSamples(), g.U, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise, m, X, U, form, levels, base,
+        g.hyperparams.predictionCovarianceNoise, want=want)
     ctx.check(st)
     var = var if want_var else None
     # (S, L, m, m) as a view of the library's m x m x S x L: every block is exactly symmetric, so no copy is needed to index it
@@ -1148,19 +1184,9 @@ def predictNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, baseline=N
     return (mean, var, np.transpose(cov, (2, 3, 0, 1))) if want_cov else (mean, var)
 
 
-def _new_request(g, doTs, Xnew, like, Unew, baseline, slope):
-    """What predictNew and averageNew share: the refusals of ``_NEW_REFUSALS`` and the parsing of the levels and of the new
-    individuals' features -> (levels (L,), base (L,) or None, Xnew (m, nX) or None, Unew (m, nU, S) or None, m, form), the arrays
-    column-major as the library takes them.  Raises before any library call."""
+def _new_features(g, Xnew, like, Unew):
+    """The new individuals' features as the library takes them -> (Xnew (m, nX) or None, Unew (m, nU, S) or None, m), column-major."""
     nX, nU, n, S = g.getNX(), g.getNU(), g.getN(), g.getNumPosteriorSamples()
-    a = np.asarray(doTs, dtype=np.float64)
-    q = SimpleNamespace(fp32=g.fp32_kernel, slope=bool(slope), base=baseline is not None, ndim=a.ndim, nX=nX, nU=nU,
-                        X=Xnew is not None, like=like is not None, U=Unew is not None)
-    for cond, exc, msg in _NEW_REFUSALS:
-        if cond(q):
-            raise exc(msg.format(nX=nX, nU=nU))
-    levels = np.ascontiguousarray(np.atleast_1d(a))
-    base = None if baseline is None else _baseline(baseline, levels.shape[0])
     X = None
     if nX > 0:
         X = np.asarray(Xnew, dtype=np.float64)
@@ -1181,10 +1207,95 @@ def _new_request(g, doTs, Xnew, like, Unew, baseline, slope):
     m = X.shape[0] if X is not None else U.shape[0] if U is not None else 1
     if X is not None and U is not None and U.shape[0] != m:
         raise ValueError(f"Xnew has {m} rows but like / Unew names {U.shape[0]} new individuals")
-    for name, v in (("doTs", levels), ("Xnew", X), ("Unew", U)):
+    return X, U, m
+
+
+def _new_request(g, doTs, Xnew, like, Unew, baseline, slope, Tnew=None, who=None):
+    """The one plan of a call about new individuals, shared by predictNew and averageNew: the refusals of ``_NEW_REFUSALS`` and the
+    parsing of the levels and of the new individuals' features -> (levels, base or None, Xnew (m, nX) or None, Unew (m, nU, S) or
+    None, m, form, vec), the arrays column-major as the library takes them.  ``vec`` (predictNew alone, ``who`` given: a 2-D
+    ``doTs`` or ``Tnew=``): levels and base are (m, L), per-individual; else (L,).  Raises before any library call."""
+    nX, nU = g.getNX(), g.getNU()
+    a = np.asarray(doTs, dtype=np.float64)
+    q = SimpleNamespace(fp32=g.fp32_kernel, slope=bool(slope), base=baseline is not None, ndim=a.ndim, nX=nX, nU=nU,
+                        X=Xnew is not None, like=like is not None, U=Unew is not None, tnew=Tnew is not None, vec_ok=who is not None)
+    for cond, exc, msg in _NEW_REFUSALS:
+        if cond(q):
+            raise exc(msg.format(nX=nX, nU=nU, who=who or "averageNew", or_vec=" or an (L, m) array of per-individual levels" if who else ""))
+    X, U, m = _new_features(g, Xnew, like, Unew)
+    vec = a.ndim == 2 or Tnew is not None
+    if a.ndim == 2 and a.shape[1] != m:
+        raise ValueError(f"{who} needs scalar levels or an (L, m) array of per-individual levels with m = {m}, got an array of shape {a.shape}")
+    if not vec:
+        levels = np.ascontiguousarray(np.atleast_1d(a))
+        base = None if baseline is None else _baseline(baseline, levels.shape[0])
+    else:
+        levels = np.asfortranarray(a.T if a.ndim == 2 else np.tile(np.atleast_1d(a)[None, :], (m, 1)))
+        L, base = levels.shape[1], None
+        if Tnew is not None:
+            t = np.asarray(Tnew, dtype=np.float64)
+            if t.shape != (m,):
+                raise ValueError(f"Tnew must be a vector of m = {m} factual treatments, got an array of shape {t.shape}")
+            base = np.asfortranarray(np.tile(t[:, None], (1, L)))
+        elif baseline is not None:
+            b = np.asarray(baseline, dtype=np.float64)
+            if b.shape == (L, m):
+                base = np.asfortranarray(b.T)
+            elif b.ndim <= 1:
+                base = np.asfortranarray(np.tile(_baseline(b, L)[None, :], (m, 1)))
+            else:
+                raise ValueError(f"baseline must be a scalar, one value per level (L = {L}) or an (L, m) array with m = {m}, "
+                                 f"got an array of shape {b.shape}")
+    for name, v in (("doTs", levels), ("Xnew", X), ("Unew", U), ("Tnew" if Tnew is not None else "baseline", base)):
         if v is not None and not np.all(np.isfinite(v)):
             raise ValueError(f"{name} has a non-finite entry")
-    return levels, base, X, U, m, "slope" if slope else "outcome" if base is None else "contrast"
+    return levels, base, X, U, m, "slope" if slope else "outcome" if base is None else "contrast", vec
+
+
+def testPredictive(g: GPSLCObject, Xtest=None, Ttest=None, Ytest=None, like=None, Utest=None):
+    """The predictive distribution of a held-out test set under the outcome model of every posterior sample (gpslc_y_test) ->
+    ``(mean, var, lpd, lpd_joint)``: ``mean``, ``var`` (m, S) of Ytest_i at the test individual's own treatment Ttest_i given
+    the n training individuals (``var`` is for the observation: it includes yNoise), ``lpd`` (m, S) the log density of Ytest_i
+    under it, ``lpd_joint`` (S,) the joint log density of the whole test set.  The chain has never seen the test set, so each
+    sample's U and hyper-parameters were inferred without these outcomes: the clean out-of-sample comparison of models
+    (nU = 0 / 1 / 2), which ``looPredictive`` / ``kfoldPredictive`` approximate on the training rows.  ``Xtest`` / ``like`` /
+    ``Utest`` are ``predictNew``'s Xnew / like / Unew.  A failed factorisation raises ``PosDefException``."""
+    if g.fp32_kernel:
+        raise ValueError("testPredictive needs an fp64 model: new individuals are not supported with fp32_kernel=True")
+    if Ttest is None or Ytest is None:
+        raise ValueError("testPredictive needs Ttest= and Ytest=: the test set's treatments and outcomes")
+    nX, nU = g.getNX(), g.getNU()
+    q = SimpleNamespace(fp32=False, slope=False, base=False, ndim=1, nX=nX, nU=nU, X=Xtest is not None, like=like is not None,
+                        U=Utest is not None, tnew=False, vec_ok=True)
+    for cond, exc, msg in _NEW_REFUSALS:
+        if cond(q):
+            raise exc(msg.format(nX=nX, nU=nU, who="testPredictive", or_vec="").replace("Xnew", "Xtest").replace("Unew", "Utest"))
+    X, U, m = _new_features(g, Xtest, like, Utest)
+    T, Y = np.asarray(Ttest, dtype=np.float64), np.asarray(Ytest, dtype=np.float64)
+    if m == 1 and X is None and U is None and T.ndim == 1:
+        m = T.shape[0]      # a model with neither X nor U: the test set is its treatments and outcomes
+    for name, v in (("Ttest", T), ("Ytest", Y)):
+        if v.shape != (m,):
+            raise ValueError(f"{name} must be a vector of m = {m} values, got an array of shape {v.shape}")
+    for name, v in (("Xtest", X), ("Utest", U), ("Ttest", T), ("Ytest", Y)):
+        if v is not None and not np.all(np.isfinite(v)):
+            raise ValueError(f"{name} has a non-finite entry")
+    ctx = g.ctx()
+    st, mean, var, lpd, joint = ctx.y_test(g.getNumPosteriorSamples(), g.U, g.uyLS, g.xyLS, g.tyLS, g.yScale, g.yNoise, m, X, U,
+                                           np.ascontiguousarray(T), np.ascontiguousarray(Y))
+    ctx.check(st)
+    return mean, var, lpd, joint
+
+
+def testSummary(g: GPSLCObject, Xtest=None, Ttest=None, Ytest=None, like=None, Utest=None, test=None):
+    """Summaries of ``testPredictive`` (host arithmetic only; ``test`` = its result, to summarise one already computed):
+    ``looSummary``'s ``elpd`` (S,), ``pointwise`` (m,), ``zscore`` (m, S) and ``pit`` (m,) of the test individuals, plus ``joint``
+    (S,): the joint log density of the test set, and ``rmse`` (S,): sqrt(mean_i (Ytest_i - mean[i, s])^2)."""
+    mean, var, lpd, joint = testPredictive(g, Xtest, Ttest, Ytest, like, Utest) if test is None else test
+    Y = np.asarray(Ytest, dtype=np.float64)
+    elpd, pointwise, z, pit = _predictive_summary(g, Y, mean, var, lpd, rows=Y.shape[0])
+    return {"elpd": elpd, "pointwise": pointwise, "zscore": z, "pit": pit, "joint": joint,
+            "rmse": np.sqrt(np.mean((Y[:, None] - mean) ** 2, axis=0))}
 
 
 def averageNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, weights=None, baseline=None, slope=False, want_cov=False):
@@ -1199,8 +1310,10 @@ def averageNew(g: GPSLCObject, doTs, Xnew=None, like=None, Unew=None, weights=No
     a difference of two group rows is the difference of the groups with its correct variance; ``groupWeights(labels)`` builds
     the rows of a labelling of the new individuals.  ``Xnew`` / ``like`` / ``Unew`` / ``baseline`` / ``slope`` are
     ``predictNew``'s, parsed and refused as there.  The outputs have ``effectCurve``'s shapes: ``curveSamples(mean, cov, spp)``
-    draws whole curves of the target population.  A failed factorisation raises ``PosDefException``."""
-    levels, base, X, U, m, form = _new_request(g, doTs, Xnew, like, Unew, baseline, slope)
+    draws whole curves of the target population.  Levels are scalar: the value of a policy with per-individual doses over a new
+    population, with its variance, is ``predictNew(..., want_cov=True)``'s ``cov`` contracted with the weights on the host
+    (``w @ mean``, ``w @ cov @ w``).  A failed factorisation raises ``PosDefException``."""
+    levels, base, X, U, m, form, _ = _new_request(g, doTs, Xnew, like, Unew, baseline, slope)
     W, is_vec = (np.full((1, m), 1.0 / m), True) if weights is None else _weights(weights, m)
     want = ("mean", "var") + (("cov",) if want_cov else ())
     ctx = g.ctx()

@@ -1,5 +1,5 @@
 // Entry points of include/gpslc_hip.h that describe a prediction call: gpslc_predict* and gpslc_predict_multi,
-// gpslc_ite_distributions*, gpslc_predict_new*, gpslc_likelihood_distribution*.
+// gpslc_ite_distributions*, gpslc_predict_new*, gpslc_y_test, gpslc_likelihood_distribution*.
 #include "request.h"
 
 #include <algorithm>
@@ -346,25 +346,35 @@ int gpslc_ite_distributions_outcome_vec(gpslc_ctx* c, int64_t S, const double* U
 
 // The checks gpslc_predict_new and gpslc_predict_new_weighted share: the samples, then arguments 9 - 15 (m, Xnew, Unew, form, L,
 // doT, doT_base), which sit at the same positions in both
-static int validate_new(gpslc_ctx* c, const PredictRequest& rq, int64_t m, const double* Xnew, const double* Unew, int32_t form,
-                        const double* doT_base) {
-    static const ArgPos kNewArgs{2, 3, 5, 6, 13, 14, 0, 0, 0, 0, true};
+// the samples and the new individuals themselves (arguments 2 - 11 of every call that takes new individuals)
+static int validate_new_rows(gpslc_ctx* c, const PredictRequest& rq, const ArgPos& k, int64_t m, const double* Xnew, const double* Unew) {
     const int64_t S = rq.post.S;
-    const int32_t L = rq.lv.L;
-    const double* doT = rq.lv.doT;
-    int rc = validate(c, rq, kNewArgs);
+    int rc = validate(c, rq, k);
     if (rc) return rc;
     if (m < 1 || m > (int64_t)GP_TS * 32767) return bad_arg(c, 9, "m < 1 (or beyond 32767 row tiles)");
     if ((c->nX > 0) != (Xnew != nullptr)) return bad_arg(c, 10, c->nX > 0 ? "Xnew is NULL but nX > 0" : "Xnew given but nX == 0");
     if (Xnew && (rc = finite_check(c, Xnew, m * c->nX, 10, "Xnew"))) return rc;
     if ((c->nU > 0) != (Unew != nullptr)) return bad_arg(c, 11, c->nU > 0 ? "Unew is NULL but nU > 0" : "Unew given but nU == 0");
     if (Unew && (rc = finite_check(c, Unew, m * c->nU * S, 11, "Unew"))) return rc;
+    return 0;
+}
+// vec (gpslc_predict_new_vec): doT and doT_base are m x L, and the slope is no form of the call
+static int validate_new(gpslc_ctx* c, const PredictRequest& rq, int64_t m, const double* Xnew, const double* Unew, int32_t form,
+                        const double* doT_base, bool vec = false) {
+    static const ArgPos kNewArgs{2, 3, 5, 6, 13, 14, 0, 0, 0, 0, true};
+    const int32_t L = rq.lv.L;
+    const double* doT = rq.lv.doT;
+    int rc = validate_new_rows(c, rq, kNewArgs, m, Xnew, Unew);
+    if (rc) return rc;
     if (form != GPSLC_NEW_OUTCOME && form != GPSLC_NEW_CONTRAST && form != GPSLC_NEW_SLOPE)
         return bad_arg(c, 12, "unknown form (GPSLC_NEW_OUTCOME, GPSLC_NEW_CONTRAST or GPSLC_NEW_SLOPE: the ordinary effect f(a) - f(T) "
                               "needs a factual treatment, which a new individual does not have)");
-    if ((rc = finite_check(c, doT, L, 14, "doT"))) return rc;
+    if (vec && form == GPSLC_NEW_SLOPE)
+        return bad_arg(c, 12, "unsupported form: the slope at per-individual levels is not offered (GPSLC_NEW_OUTCOME or GPSLC_NEW_CONTRAST)");
+    const int64_t nlev = vec ? m * L : L;
+    if ((rc = finite_check(c, doT, nlev, 14, "doT"))) return rc;
     if (form == GPSLC_NEW_CONTRAST) {
-        if ((rc = finite_check(c, doT_base, L, 15, "doT_base"))) return rc;
+        if ((rc = finite_check(c, doT_base, nlev, 15, "doT_base"))) return rc;
     } else if (doT_base) {
         return bad_arg(c, 15, "doT_base given for a form that is no contrast");
     }
@@ -372,8 +382,8 @@ static int validate_new(gpslc_ctx* c, const PredictRequest& rq, int64_t m, const
 }
 // ... and their uploads: the samples, the levels of the form and the new individuals' features
 static PredictIO new_io(gpslc_ctx* c, const PredictRequest& rq, int64_t m, const double* Xnew, const double* Unew, int32_t form,
-                        const double* doT_base, double pred_noise) {
-    const size_t mm = (size_t)m, S = (size_t)rq.post.S, L = (size_t)rq.lv.L;
+                        const double* doT_base, double pred_noise, bool vec = false) {
+    const size_t mm = (size_t)m, S = (size_t)rq.post.S, L = (size_t)rq.lv.L * (vec ? (size_t)m : 1);
     PredictIO io;
     io.post.S = rq.post.S; io.post.p = upload_samples(c, rq.post.p, 0, S);
     io.X = c->dX;
@@ -381,19 +391,20 @@ static PredictIO new_io(gpslc_ctx* c, const PredictRequest& rq, int64_t m, const
     io.lv.form = form == GPSLC_NEW_OUTCOME ? FORM_OUTCOME : form == GPSLC_NEW_SLOPE ? FORM_SLOPE : FORM_CONTRAST;
     io.lv.base = doT_base ? up(c, doT_base, L) : nullptr;
     io.out.pred_noise = pred_noise;
-    io.fresh.m = (int)m;
+    io.fresh.m = (int)m; io.fresh.vec = vec;
     io.fresh.Xnew = Xnew ? up(c, Xnew, mm * c->nX) : nullptr;
     io.fresh.Unew = Unew ? up(c, Unew, mm * c->nU * S) : nullptr;
     return io;
 }
 
-// predictions for m new individuals: host pointers; every check before any device work
-int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
-                      const double* yScale, const double* yNoise, int64_t m, const double* Xnew, const double* Unew,
-                      int32_t form, int32_t L, const double* doT, const double* doT_base, double pred_noise, double* mean,
-                      double* var, double* cov) {
+// predictions for m new individuals (vec: at per-individual levels, §29): host pointers; every check before any
+// device work
+static int predict_new_host(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
+                            const double* yScale, const double* yNoise, int64_t m, const double* Xnew, const double* Unew,
+                            int32_t form, int32_t L, const double* doT, const double* doT_base, double pred_noise, double* mean,
+                            double* var, double* cov, bool vec) {
     PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, L, doT);
-    int rc = validate_new(c, rq, m, Xnew, Unew, form, doT_base);
+    int rc = validate_new(c, rq, m, Xnew, Unew, form, doT_base, vec);
     if (rc) return rc;
     if (!std::isfinite(pred_noise)) return bad_arg(c, 16, "pred_noise is not finite");
     if (!mean && !var && !cov) return bad_arg(c, 17, "mean, var and cov are all NULL");
@@ -401,7 +412,7 @@ int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uy
     return guarded(c, [&]() {
         const size_t mm = (size_t)m, SL = (size_t)S * L;
         c->io.reset();
-        PredictIO io = new_io(c, rq, m, Xnew, Unew, form, doT_base, pred_noise);
+        PredictIO io = new_io(c, rq, m, Xnew, Unew, form, doT_base, pred_noise, vec);
         const Outputs outs = {{mean, &io.fresh.mean, mm * SL}, {var, &io.fresh.var, mm * SL}, {cov, &io.fresh.cov, mm * mm * SL}};
         take_outputs(c, outs);
         if (cov && !var) io.fresh.var = c->io.take<double>(mm * SL);      // the covariance takes its diagonal from it
@@ -418,6 +429,61 @@ int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uy
                     if (var) std::fill(var + o, var + o + mm, NAN);
                     if (cov) std::fill(cov + mm * o, cov + mm * (o + mm), NAN);
                 }
+            }
+        return st;
+    });
+}
+
+int gpslc_predict_new(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
+                      const double* yScale, const double* yNoise, int64_t m, const double* Xnew, const double* Unew,
+                      int32_t form, int32_t L, const double* doT, const double* doT_base, double pred_noise, double* mean,
+                      double* var, double* cov) {
+    return predict_new_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, L, doT, doT_base, pred_noise, mean, var,
+                            cov, false);
+}
+
+// ... at per-individual levels: doT and doT_base are m x L
+int gpslc_predict_new_vec(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
+                          const double* yScale, const double* yNoise, int64_t m, const double* Xnew, const double* Unew,
+                          int32_t form, int32_t L, const double* doT, const double* doT_base, double pred_noise, double* mean,
+                          double* var, double* cov) {
+    return predict_new_host(c, S, U, uyLS, xyLS, tyLS, yScale, yNoise, m, Xnew, Unew, form, L, doT, doT_base, pred_noise, mean, var,
+                            cov, true);
+}
+
+// The score of a held-out test set: the outcome form at the test set's own treatments with the observation's
+// noise, the pointwise log densities and the joint one.  Arguments 9 - 11 and their checks are gpslc_predict_new's.
+int gpslc_y_test(gpslc_ctx* c, int64_t S, const double* U, const double* uyLS, const double* xyLS, const double* tyLS,
+                 const double* yScale, const double* yNoise, int64_t m, const double* Xtest, const double* Utest,
+                 const double* Ttest, const double* Ytest, double* mean, double* var, double* lpd, double* lpd_joint) {
+    static const ArgPos kTestArgs{2, 3, 5, 6, 0, 0, 0, 0, 0, 0, true};
+    PredictRequest rq = make_request(S, {U, uyLS, xyLS, tyLS, yScale, yNoise}, 1, Ttest);
+    int rc = validate_new_rows(c, rq, kTestArgs, m, Xtest, Utest);
+    if (rc) return rc;
+    if ((rc = finite_check(c, Ttest, m, 12, "Ttest"))) return rc;
+    if ((rc = finite_check(c, Ytest, m, 13, "Ytest"))) return rc;
+    if (!mean && !var && !lpd && !lpd_joint) return bad_arg(c, 14, "mean, var, lpd and lpd_joint are all NULL");
+    if (S == 0) { c->last_info.clear(); return GPSLC_OK; }
+    return guarded(c, [&]() {
+        const size_t mm = (size_t)m, mS = mm * (size_t)S;
+        c->io.reset();
+        PredictIO io = new_io(c, rq, m, Xtest, Utest, GPSLC_NEW_OUTCOME, nullptr, 0.0, true);
+        io.fresh.Ytest = up(c, Ytest, mm);
+        const Outputs outs = {{mean, &io.fresh.mean, mS}, {var, &io.fresh.var, mS}, {lpd, &io.fresh.lpd, mS},
+                              {lpd_joint, &io.fresh.lpd_joint, (size_t)S}};
+        take_outputs(c, outs);
+        if (!mean) io.fresh.mean = c->io.take<double>(mS);      // the densities read both
+        if (!var) io.fresh.var = c->io.take<double>(mS);
+        io.info = c->io.take<int>((size_t)S);
+        run_predict(c, io);
+        const int st = first_info(c);
+        deliver_outputs(c, outs);
+        if (st > 0)      // a sample whose factorisation of A broke down: NaN in everything of it
+            for (int64_t s = 0; s < S; ++s) {
+                if (c->last_info[(size_t)s] == 0) continue;
+                for (double* o : {mean, var, lpd})
+                    if (o) std::fill(o + mm * (size_t)s, o + mm * (size_t)(s + 1), NAN);
+                if (lpd_joint) lpd_joint[s] = NAN;
             }
         return st;
     });

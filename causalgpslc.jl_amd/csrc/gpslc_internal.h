@@ -456,11 +456,24 @@ struct NewArgs : NewGrid {
     TRef Cm;                // lower packed mt: prior_l B** + pred_noise I, then the covariance (base null: not asked for)
     double* mean; double* var;   // m x S x L: element (i, s, l) at i + m*(s + S*l)
     double* cov;            // m x m x S x L: element (i, i', s, l) at i + m*(i' + m*(s + S*l))
+    // Per-individual levels (lv.vec): lv.doT and lv.base are m x L, new individual i at level l is set to
+    // doT[i + m*l] (against base[i + m*l]); outcome and contrast only.  The test-set score (gpslc_y_test) is the outcome form of
+    // such a call with L = 1, doT = the test set's own treatments and the observation's noise:
+    const double* noise_s;  // non-null: yNoise of the call's samples takes pred_noise's place (S, offset like SampleParams)
+    int score;              // Cm has mt + 1 tile rows, the identity on its padded diagonal and Ytest - mean as its augmented row
+    const double* Ytest;    // m
+    const int* pinfo;       // [b]: nonzero where the factorisation of the pair's C broke down
+    const double* ldq;      // [b] log det C, then [nbatch + b] the quadratic form (launch_epilogue)
+    double* lpd;            // m x S or null
+    double* lpd_joint;      // S or null
 };
 void launch_new_mean(const NewArgs& a, int nbatch, hipStream_t st);      // mean = (B* R)[i, l], R[j, l] = cross_j(l) alpha_j, all L levels
 void launch_new_build(const NewArgs& a, int nbatch, hipStream_t st);     // W <- D*(l) (zero padding), Cm <- prior_l B** + pred_noise I
 void launch_new_var(const NewArgs& a, int nbatch, hipStream_t st);       // var = (prior_l yScale - ||row of W||^2) + pred_noise
 void launch_new_gather(const NewArgs& a, int nbatch, hipStream_t st);    // Cm -> cov, both triangles; the diagonal is var
+void launch_new_mean_vec(const NewArgs& a, int nbatch, hipStream_t st);  // per-individual levels: the mean as a pass over the pairs
+void launch_new_score_rhs(const NewArgs& a, int nbatch, hipStream_t st);     // the augmented row of Cm <- Ytest - mean
+void launch_new_score_finish(const NewArgs& a, int nbatch, hipStream_t st);  // mean, var, log det C, the quadratic form -> lpd, lpd_joint
 
 // Weighted averages over the new individuals: what launch_rhs, launch_epilogue and launch_curve read of a weighted
 // call — bw, sumdelta, wnorm2 and beta — for G weight columns over the m new individuals, from one pass over the m x n pairs and one

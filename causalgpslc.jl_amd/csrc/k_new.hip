@@ -9,7 +9,9 @@
 // product W* W*^T are the tile kernels' (w_solve, predict.hip; gemm, factor.hip).
 // Every output element depends on its own new individual(s), the training data and the sample only, in a fixed summation order:
 // results do not depend on which other new individuals share the call, nor on the chunk, the stream or the schedule.
-// Further down: weighted averages over the new individuals, which need none of these tiles.
+// Further down: weighted averages over the new individuals, which need none of these tiles; and levels that depend
+// on the new individual with the score of a held-out test set on top of them: the mean as a pass over the pairs, the
+// VEC instantiations of the builder and of the row norms, the augmented row and the densities of the score.
 #include "pair_mfma.h"
 #include <stdexcept>
 
@@ -73,9 +75,13 @@ void launch_new_mean_t(const NewArgs& a, int nbatch, hipStream_t st) {
 // A contrast with a == b: cross_j = r^a_j - r^b_j = 0.0 for every j (the same square into the same exp) and prior = 0.0.
 // LDS (doubles): etab [32] | fr [F][128] | fc [F][128] | xc [128] cross_j of the column block
 // ---------------------------------------------------------------------------------------
-constexpr int new_build_lds_bytes(int F) { return (GP_EXP_TAB_DOUBLES + 2 * F * GP_TS + GP_TS) * 8; }
+// VEC (per-individual levels): xc gives way to ra | rb | ca | cb [128] each, the doses (and baselines) of the row
+// block and, for a Cm tile, of the column block; cross_ij and P_ii' are evaluated per element with the table-driven exp (one
+// exp per element for the outcome; two for a D* tile and four for a Cm tile of the contrast).  a.score: the padded diagonal of Cm
+// is the identity (the tile is factorised); a.noise_s: the sample's yNoise on the diagonal.
+constexpr int new_build_lds_bytes(int F, bool vec = false) { return (GP_EXP_TAB_DOUBLES + 2 * F * GP_TS + (vec ? 4 : 1) * GP_TS) * 8; }
 
-template <int FORM>
+template <int FORM, bool VEC>
 __global__ __launch_bounds__(256) void new_build_kernel(NewArgs a) {
     using LF = LevelForm<FORM>;
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -100,7 +106,13 @@ __global__ __launch_bounds__(256) void new_build_kernel(NewArgs a) {
     if (cross) stage_scaled_features<GP_TS>(a, s, F, F, gj0, fc);
     else stage_scaled_new_features<GP_TS>(a, s, F, F, gj0, fc);
     gp_exp_tab_stage(etab, tid);
-    if (cross && tid < GP_TS) {
+    if (VEC) {       // xc: ra | rb | ca | cb
+        for (int idx = tid; idx < 4 * GP_TS; idx += 256) {
+            const int k = idx >> 7, r = idx & 127, g = (k < 2 ? gi0 : gj0) + r;
+            const double* src = (k & 1) ? a.lv.base : a.lv.doT;
+            xc[idx] = (src && g < a.m && (k < 2 || !cross)) ? src[g + (long long)a.m * l] : 0.0;
+        }
+    } else if (cross && tid < GP_TS) {
         const int g = gj0 + tid;
         double v = 0.0;
         if (g < a.n) {
@@ -109,9 +121,12 @@ __global__ __launch_bounds__(256) void new_build_kernel(NewArgs a) {
         }
         xc[tid] = v;
     }
-    const double prior = cross ? 0.0 : new_prior<FORM>(a, s, l);
+    double prior = 0.0;
+    if constexpr (!VEC) prior = cross ? 0.0 : new_prior<FORM>(a, s, l);
     __syncthreads();
     const double ys = a.p.yScale[s];
+    const double noise = (VEC && a.noise_s) ? a.noise_s[s] : a.pred_noise;
+    auto rho = [&](double x, double y) { const double d = x - y; return gp_exp_neg_tab(-((d * d) * wt), etab); };
     double* tile = tref_tile(cross ? a.W : a.Cm, b, ti, tj);
     const int ty = tid & 15, tx = tid >> 4;
 #pragma unroll 1
@@ -129,15 +144,24 @@ __global__ __launch_bounds__(256) void new_build_kernel(NewArgs a) {
                 lux[p] = fma(d, d, lux[p]);
             }
         }
-        const double xj = cross ? xc[cq] : prior;
+        const double xj = VEC ? 0.0 : cross ? xc[cq] : prior;
+        const double tj = (VEC && cross && gj < a.n) ? a.T[gj] : 0.0;
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             const int rp = ty + 16 * p;
             const int gi = gi0 + rp;
             double v = 0.0;
             if (gi < a.m && gj < ncol) {
-                v = (ys * gp_exp_neg_tab(-lux[p], etab)) * xj;
-                if (!cross && gi == gj) v += a.pred_noise;
+                double x = xj;
+                if constexpr (VEC) {
+                    const double ai = xc[rp], bi = xc[GP_TS + rp];
+                    if (cross) x = LF::cross(tj - ai, rho(tj, ai), LF::paired ? rho(tj, bi) : 0.0, wt);
+                    else x = level_pair_prior<FORM>(ai, bi, xc[2 * GP_TS + cq], xc[3 * GP_TS + cq], wt, rho);
+                }
+                v = (ys * gp_exp_neg_tab(-lux[p], etab)) * x;
+                if (!cross && gi == gj) v += noise;
+            } else if (VEC && !cross && a.score && gi == gj) {
+                v = 1.0;
             }
             tile[cq * GP_TS + rp] = v;
         }
@@ -150,7 +174,8 @@ __global__ __launch_bounds__(256) void new_build_kernel(NewArgs a) {
 // parity h of the tiles (two halves of the workgroup) ascending k, inside a tile ascending column in four interleaved partial sums
 // ((p0 + p1) + (p2 + p3)); the norm = half 0 + half 1.
 // ---------------------------------------------------------------------------------------
-template <int FORM>
+// VEC: prior_l is the row's own P_ii = prior(rho(a_i, b_i)), and a.noise_s (the test-set score) takes pred_noise's place.
+template <int FORM, bool VEC>
 __global__ __launch_bounds__(256) void new_var_kernel(NewArgs a) {
     __shared__ double s_half[GP_TS];
     const int i = blockIdx.x;
@@ -174,8 +199,17 @@ __global__ __launch_bounds__(256) void new_var_kernel(NewArgs a) {
     if (h == 1) s_half[r] = acc;
     __syncthreads();
     const int gi = i * GP_TS + r;
-    if (h == 0 && gi < a.m)
-        a.var[gi + (long long)a.m * (s + a.S * l)] = (new_prior<FORM>(a, s, l) * a.p.yScale[s] - (acc + s_half[r])) + a.pred_noise;
+    if (h == 0 && gi < a.m) {
+        if constexpr (VEC) {
+            using LF = LevelForm<FORM>;
+            const double tl = a.p.tyLS[s], wt = 1.0 / (tl * tl);
+            const long long o = gi + (long long)a.m * l;
+            const double prior = LF::prior(LF::paired ? gp_rho(a.lv.doT[o], a.lv.base[o], wt) : 0.0, wt);
+            a.var[gi + (long long)a.m * (s + a.S * l)] = (prior * a.p.yScale[s] - (acc + s_half[r])) + (a.noise_s ? a.noise_s[s] : a.pred_noise);
+        } else {
+            a.var[gi + (long long)a.m * (s + a.S * l)] = (new_prior<FORM>(a, s, l) * a.p.yScale[s] - (acc + s_half[r])) + a.pred_noise;
+        }
+    }
 }
 
 // cov[i, i', s, l] from the lower tiles of Cm, both triangles from the one value (exactly symmetric); the diagonal is var's value
@@ -301,6 +335,139 @@ __global__ __launch_bounds__(256) void new_wsum_finish_kernel(NewWsumArgs a) {
     for (int l = tid; l < L; l += 256) a.sumdelta[b * L * G + l + (long long)L * g] = new_prior<FORM>(a, s, l) * beta;
 }
 
+// ---------------------------------------------------------------------------------------
+// Per-individual levels: mean[i, s, l] = sum_j B*_ij cross_ij(l) alpha_j with cross_ij from the ROW's dose a_il
+// (and b_il) and the column's T_j.  cross no longer factors into a per-column term, so the product (B* R) of new_mean_mfma_kernel
+// does not apply: a pass over the pairs in the shape of vec_pair_kernel<LB, false> (k_vec.hip).  One workgroup per (block of 128
+// new individuals, block of LB levels, sample); thread (o = tid & 127, half = tid >> 7) owns new individual o and visits half of
+// the 128 training individuals of every staged tile; the feature distance of a pair is evaluated once per level block, then one
+// table-driven exp per level (two for the contrast).  Order of a sum, fixed: per thread along its columns in ascending column
+// block, then half 0 + half 1.  A contrast with a_il == b_il is stored as 0.0.  New individuals that copy training rows, with the
+// outcome form, run vec_pair_kernel's arithmetic for those rows.
+// LDS (doubles): etab [32] | fo [F][128] new individuals | fk [F][128] training | tk [128] | ak [128] alpha | red [LB][128]
+// ---------------------------------------------------------------------------------------
+constexpr int new_mean_vec_lds_bytes(int F, int LB) { return (GP_EXP_TAB_DOUBLES + 2 * F * GP_TS + 2 * GP_TS + LB * GP_TS) * 8; }
+
+template <int LB, int FORM>
+__global__ __launch_bounds__(256) void new_mean_vec_kernel(NewArgs a) {
+    using LF = LevelForm<FORM>;
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int F = a.nU + a.nX;
+    double* etab = sm;
+    double* fo = etab + GP_EXP_TAB_DOUBLES;
+    double* fk = fo + F * GP_TS;
+    double* tk = fk + F * GP_TS;
+    double* ak = tk + GP_TS;
+    double* red = ak + GP_TS;
+    const int tid = threadIdx.x, o = tid & 127, half = tid >> 7;
+    const int ot = blockIdx.x, l0 = blockIdx.y * LB;
+    const long long b = blockIdx.z, s = a.s0 + b;
+    const int n = a.n, L = a.lv.L;
+    const int go = ot * GP_TS + o;
+    const bool own_in = go < a.m;
+
+    stage_scaled_new_features<GP_TS>(a, s, F, F, ot * GP_TS, fo);
+    gp_exp_tab_stage(etab, tid);
+
+    const double ys = a.p.yScale[s];
+    const double tl = a.p.tyLS[s];
+    const double wt = 1.0 / (tl * tl);
+    double da[LB], db[LB];     // own doses per level (levels beyond L repeat the last one; their results are not written)
+#pragma unroll
+    for (int ll = 0; ll < LB; ++ll) {
+        const long long at = go + (long long)a.m * min(l0 + ll, L - 1);
+        da[ll] = own_in ? a.lv.doT[at] : 0.0;
+        db[ll] = (LF::paired && own_in) ? a.lv.base[at] : 0.0;
+    }
+    double acc[LB];
+#pragma unroll
+    for (int ll = 0; ll < LB; ++ll) acc[ll] = 0.0;
+    const double* alpha = a.alpha + b * (long long)a.nt * GP_TS;
+
+    for (int kt = 0; kt < a.nt; ++kt) {
+        const int k0 = kt * GP_TS;
+        __syncthreads();
+        stage_scaled_features<GP_TS>(a, s, F, F, k0, fk);
+        if (tid < GP_TS) {
+            tk[tid] = k0 + tid < n ? a.T[k0 + tid] : 0.0;
+            ak[tid] = k0 + tid < n ? alpha[k0 + tid] : 0.0;
+        }
+        __syncthreads();
+        // this half's columns of the tile: [64 half, 64 half + 64) below n (uniform per wave)
+        const int rend = min(64, n - k0 - 64 * half);
+#pragma unroll 1
+        for (int rr = 0; rr < rend; ++rr) {
+            const int r = 64 * half + rr;
+            double lux = 0.0;
+            for (int f = 0; f < F; ++f) {
+                const double d = fo[f * GP_TS + o] - fk[f * GP_TS + r];
+                lux = fma(d, d, lux);
+            }
+            const double Bv = ys * gp_exp_neg_tab(-lux, etab);
+            const double tr = tk[r], al = ak[r];
+#pragma unroll
+            for (int ll = 0; ll < LB; ++ll) {
+                const double dt = tr - da[ll], dbt = tr - db[ll];
+                const double rb = LF::paired ? gp_exp_neg_tab(-((dbt * dbt) * wt), etab) : 0.0;
+                acc[ll] = fma(Bv, LF::cross(dt, gp_exp_neg_tab(-((dt * dt) * wt), etab), rb, wt) * al, acc[ll]);
+            }
+        }
+    }
+    __syncthreads();
+    if (half == 1) {
+#pragma unroll
+        for (int ll = 0; ll < LB; ++ll) red[ll * GP_TS + o] = acc[ll];
+    }
+    __syncthreads();
+    if (half == 1 || !own_in) return;
+    const int nl = min(LB, L - l0);
+#pragma unroll
+    for (int ll = 0; ll < LB; ++ll)
+        if (ll < nl)
+            a.mean[go + (long long)a.m * (s + a.S * (l0 + ll))] =
+                (LF::paired && LF::zero_level(da[ll], db[ll])) ? 0.0 : acc[ll] + red[ll * GP_TS + o];
+}
+
+template <int LB, int FORM>
+void launch_new_mean_vec_t(const NewArgs& a, int nbatch, hipStream_t st) {
+    static DeviceOnce attr_set;
+    lds_opt_in(attr_set, (const void*)new_mean_vec_kernel<LB, FORM>, new_mean_vec_lds_bytes(MAXF, LB));
+    hipLaunchKernelGGL((new_mean_vec_kernel<LB, FORM>), dim3(a.mt, (a.lv.L + LB - 1) / LB, nbatch), dim3(256),
+                       new_mean_vec_lds_bytes(a.nU + a.nX, LB), st, a);
+}
+
+// ---------------------------------------------------------------------------------------
+// The test-set score (gpslc_y_test) on top of the outcome form at the test set's own treatments: C = B** o P -
+// W* W*^T + yNoise I stands in the pair's Cm (mt + 1 tile rows, the identity on the padded diagonal) after minus_w_wt.
+// ---------------------------------------------------------------------------------------
+// the augmented row's tiles (mt, q): right-hand side 0 = Ytest - mean in row 0, zero on the padding; rows 1 .. 31 zero (the strip
+// kernels handle a short augmented row in 32-row units), the other 96 have no reader.  One workgroup per (tile column, pair).
+__global__ __launch_bounds__(256) void new_score_rhs_kernel(NewArgs a) {
+    const int q = blockIdx.x;
+    const long long b = blockIdx.y, s = a.s0 + b;
+    double* __restrict__ aug = tref_tile(a.Cm, b, a.mt, q);
+    const double* mean = a.mean + (long long)a.m * s;
+    for (int idx = threadIdx.x; idx < GP_TS * 32; idx += 256) {
+        const int c = idx >> 5, r = idx & 31, gi = GP_TS * q + c;
+        aug[c * GP_TS + r] = (r == 0 && gi < a.m) ? a.Ytest[gi] - mean[gi] : 0.0;
+    }
+}
+
+// lpd_i = log N(Ytest_i; mean_i, var_i); lpd_joint = -(m/2) log(2 pi) - log det(C)/2 - (Ytest - mean)^T C^-1 (Ytest - mean)/2, NaN
+// where the factorisation of C broke down.  One workgroup per (row tile, pair).
+__global__ __launch_bounds__(GP_TS) void new_score_finish_kernel(NewArgs a, int nbatch) {
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const long long b = blockIdx.y, s = a.s0 + b;
+    const int gi = GP_TS * i + tid;
+    if (a.lpd && gi < a.m) {
+        const long long o = gi + (long long)a.m * s;
+        const double v = a.var[o], r = a.Ytest[gi] - a.mean[o];
+        a.lpd[o] = -0.91893853320467274178 - 0.5 * log(v) - 0.5 * ((r * r) / v);
+    }
+    if (i == 0 && tid == 0 && a.lpd_joint)
+        a.lpd_joint[s] = a.pinfo[b] == 0 ? -0.91893853320467274178 * a.m - 0.5 * a.ldq[b] - 0.5 * a.ldq[nbatch + b] : NAN;
+}
+
 // the level forms new individuals can be asked for: the non-factual ones of level_form.h (run_predict refuses the others)
 template <typename F>
 void dispatch_new_form(int form, F&& f) {
@@ -308,6 +475,14 @@ void dispatch_new_form(int form, F&& f) {
         if constexpr (LevelForm<decltype(fm)::value>::factual) throw std::logic_error("new individuals have no factual treatment");
         else f(fm);
     });
+}
+
+// ... and those with per-individual levels: the outcome and the contrast
+template <typename F>
+void dispatch_new_vec_form(int form, F&& f) {
+    if (form == FORM_OUTCOME) f(std::integral_constant<int, FORM_OUTCOME>{});
+    else if (form == FORM_CONTRAST) f(std::integral_constant<int, FORM_CONTRAST>{});
+    else throw std::logic_error("this level form has no per-individual levels for new individuals");     // run_predict refuses the call
 }
 
 }  // namespace
@@ -332,20 +507,52 @@ void launch_new_mean(const NewArgs& a, int nbatch, hipStream_t st) {
     if (nbatch <= 0) return;
     dispatch_new_form(a.lv.form, [&](auto form) { launch_new_mean_t<decltype(form)::value>(a, nbatch, st); });
 }
+void launch_new_mean_vec(const NewArgs& a, int nbatch, hipStream_t st) {
+    if (nbatch <= 0) return;
+    dispatch_new_vec_form(a.lv.form, [&](auto form) {
+        constexpr int FORM = decltype(form)::value;
+        if (a.lv.L <= 1) launch_new_mean_vec_t<1, FORM>(a, nbatch, st);
+        else if (a.lv.L <= 4) launch_new_mean_vec_t<4, FORM>(a, nbatch, st);
+        else launch_new_mean_vec_t<8, FORM>(a, nbatch, st);
+    });
+}
+void launch_new_score_rhs(const NewArgs& a, int nbatch, hipStream_t st) {
+    if (nbatch <= 0) return;
+    hipLaunchKernelGGL(new_score_rhs_kernel, dim3(a.mt, nbatch), dim3(256), 0, st, a);
+}
+void launch_new_score_finish(const NewArgs& a, int nbatch, hipStream_t st) {
+    if (nbatch <= 0) return;
+    hipLaunchKernelGGL(new_score_finish_kernel, dim3(a.mt, nbatch), dim3(GP_TS), 0, st, a, nbatch);
+}
 void launch_new_build(const NewArgs& a, int nbatch, hipStream_t st) {
     if (nbatch <= 0) return;
     const int tiles = a.mt * a.nt + (a.Cm.base ? a.mt * (a.mt + 1) / 2 : 0);
+    if (a.lv.vec) {
+        dispatch_new_vec_form(a.lv.form, [&](auto form) {
+            constexpr int FORM = decltype(form)::value;
+            static DeviceOnce attr_set;
+            lds_opt_in(attr_set, (const void*)new_build_kernel<FORM, true>, new_build_lds_bytes(MAXF, true));
+            hipLaunchKernelGGL((new_build_kernel<FORM, true>), dim3(tiles, nbatch), dim3(256), new_build_lds_bytes(a.nU + a.nX, true), st, a);
+        });
+        return;
+    }
     dispatch_new_form(a.lv.form, [&](auto form) {
         constexpr int FORM = decltype(form)::value;
         static DeviceOnce attr_set;
-        lds_opt_in(attr_set, (const void*)new_build_kernel<FORM>, new_build_lds_bytes(MAXF));
-        hipLaunchKernelGGL((new_build_kernel<FORM>), dim3(tiles, nbatch), dim3(256), new_build_lds_bytes(a.nU + a.nX), st, a);
+        lds_opt_in(attr_set, (const void*)new_build_kernel<FORM, false>, new_build_lds_bytes(MAXF));
+        hipLaunchKernelGGL((new_build_kernel<FORM, false>), dim3(tiles, nbatch), dim3(256), new_build_lds_bytes(a.nU + a.nX), st, a);
     });
 }
 void launch_new_var(const NewArgs& a, int nbatch, hipStream_t st) {
     if (nbatch <= 0) return;
+    if (a.lv.vec) {
+        dispatch_new_vec_form(a.lv.form, [&](auto form) {
+            hipLaunchKernelGGL((new_var_kernel<decltype(form)::value, true>), dim3(a.mt, nbatch), dim3(256), 0, st, a);
+        });
+        return;
+    }
     dispatch_new_form(a.lv.form, [&](auto form) {
-        hipLaunchKernelGGL((new_var_kernel<decltype(form)::value>), dim3(a.mt, nbatch), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((new_var_kernel<decltype(form)::value, false>), dim3(a.mt, nbatch), dim3(256), 0, st, a);
     });
 }
 void launch_new_gather(const NewArgs& a, int nbatch, hipStream_t st) {

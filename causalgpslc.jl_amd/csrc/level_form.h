@@ -56,6 +56,17 @@ template <> struct LevelForm<FORM_OUTCOME> {
     __host__ __device__ static bool zero_level(double, double) { return false; }
 };
 
+// Levels that depend on the (new) individual (outcome and contrast): individual i is set to a_i (against b_i).  The
+// factor of B*_ij is cross with r_a = rho(T_j, a_i), r_b = rho(T_j, b_i), evaluated per pair; the factor of B**_ii' is joint between
+// the levels of i and of i' — P_ii' below.  rho(x, y) is the caller's exponential.  P_ii equals prior(rho(a_i, b_i)) bit for bit
+// ((1 - r) - (r - 1) and (1 - r) + (1 - r) round alike), and a contrast with a_i == b_i has P_ii' == 0.0 for every i'.
+template <int FORM, class Rho>
+__host__ __device__ inline double level_pair_prior(double ai, double bi, double aj, double bj, double wt, Rho&& rho) {
+    using LF = LevelForm<FORM>;
+    if constexpr (LF::paired) return LF::joint(rho(ai, aj), rho(ai, bj), rho(bi, aj), rho(bi, bj), ai - aj, wt);
+    else return LF::joint(rho(ai, aj), 0.0, 0.0, 0.0, ai - aj, wt);
+}
+
 // run-time form -> template argument: f(std::integral_constant<int, FORM_*>{})
 template <typename F>
 inline void dispatch_form(int form, F&& f) {

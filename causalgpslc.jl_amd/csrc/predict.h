@@ -83,6 +83,14 @@ struct NewIndividuals {              // predictions for m new individuals (gpslc
     const double *Xnew = nullptr, *Unew = nullptr;      // their features: m x nX, m x nU x S
     int m = 0;
     double *mean = nullptr, *var = nullptr, *cov = nullptr;     // m x S x L each and m x m x S x L; cov needs var: its diagonal
+    // per-individual levels (gpslc_predict_new_vec): Levels::doT / base are m x L over the NEW individuals (level l
+    // of new individual i at doT[i + m*l]); Levels::vec stays false, it speaks of the n training individuals
+    bool vec = false;
+    // the test-set score (gpslc_y_test): the outcome form with vec, L = 1, doT = the test set's treatments and yNoise for
+    // pred_noise; mean and var are always there, lpd (m x S) and lpd_joint (S) may be null
+    const double* Ytest = nullptr;
+    double *lpd = nullptr, *lpd_joint = nullptr;
+    bool score() const { return Ytest != nullptr; }
     bool pairs() const { return var || cov; }            // the (sample, level) pairs need tile workspace
     bool any() const { return mean || pairs(); }
     // weighted averages over them (gpslc_predict_new_weighted), a call of its own: Levels::W / G are then G weight

@@ -141,13 +141,22 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
         return by;
     }
     if (sh.new_pairs) {       // new individuals: W* (mt x nt) and, with the covariance, an mt triangle per (sample, level) pair
-        const size_t w_tiles = (size_t)sh.mt * nt, c_tiles = io.fresh.cov ? (size_t)sh.mlow : 0;
-        by.per_pair = (w_tiles + c_tiles) * GP_TSQ * 8 + 512;
+        // the joint density of a test set factorises C in place: one more tile row for its augmented row, the
+        // inverted diagonal tiles, log det C and the quadratic form, a failure code
+        const bool joint = io.fresh.lpd_joint != nullptr;
+        const size_t w_tiles = (size_t)sh.mt * nt, mt = (size_t)sh.mt;
+        const size_t c_tiles = joint ? (mt + 1) * (mt + 2) / 2 : io.fresh.cov ? (size_t)sh.mlow : 0;
+        by.per_pair = (w_tiles + c_tiles + (joint ? mt : 0)) * GP_TSQ * 8 + 512 + (joint ? 3 * 256 : 0);
         if (!ar) return by;
         b.lc_max = std::min(L, Bb);
         b.gs_max = std::max(1, Bb / b.lc_max);
         b.Wt = ar->take<double>((size_t)Bb * w_tiles * GP_TSQ);
         if (c_tiles) b.Ct = ar->take<double>((size_t)Bb * c_tiles * GP_TSQ);
+        if (joint) {
+            b.kf_inv = ar->take<double>((size_t)Bb * mt * GP_TSQ);
+            b.kf_ldq = ar->take<double>((size_t)Bb * 2);
+            b.pinfo = ar->take<int>((size_t)Bb);
+        }
         return by;
     }
     if (!sh.unitB) return by;
@@ -509,7 +518,9 @@ void unit_b(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
 // Predictions for new individuals of a chunk.  The mean is one pass over the m x n pairs per sample for all
 // levels and needs no workspace; variance and covariance batch over (sample, level) pairs like unit B: D*(l) (and prior_l B**)
 // into the pair's tiles, W* = D* L^-T against the sample's factor, var from the squared row norms of W*, cov from the lower
-// tiles of prior_l B** + pred_noise I - W* W*^T.
+// tiles of prior_l B** + pred_noise I - W* W*^T.  Per-individual levels (NewIndividuals::vec) take the mean's pass
+// over the pairs and the vector instantiations of the builder and the row norms; the test-set score adds, per pair, the
+// factorisation of C in place (the panel schedule, never the persistent launch), the epilogue and the kernel that writes the densities.
 void unit_new(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chunk& ch) {
     hipStream_t st = ch.s->st;
     const int nt = sh.nt, mt = sh.mt, nb = ch.nb;
@@ -520,18 +531,32 @@ void unit_new(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
     na.S = io.post.S; na.lv = io.lv.set(sh.L); na.l0 = 0; na.lc = 1; na.pred_noise = io.out.pred_noise;
     na.alpha = ch.zwork + (long long)nb * sh.Np;
     na.mean = f.mean; na.var = f.var; na.cov = f.cov;
-    if (f.mean) launch_new_mean(na, nb, st);
+    na.lv.vec = f.vec ? 1 : 0;
+    const bool joint = f.lpd_joint != nullptr;
+    if (f.score()) { na.noise_s = io.post.p.yNoise; na.Ytest = f.Ytest; na.lpd = f.lpd; na.lpd_joint = f.lpd_joint; na.score = joint ? 1 : 0; }
+    if (f.mean) (f.vec ? launch_new_mean_vec : launch_new_mean)(na, nb, st);
     if (sh.new_pairs) {
         na.W = rect_ref(ch.Wt, (long long)mt * nt * GP_TSQ, nt);
-        na.Cm = f.cov ? lower_ref(ch.Ct, sh.mlow * GP_TSQ) : TRef{};
+        na.Cm = joint ? lower_ref(ch.Ct, (long long)(mt + 1) * (mt + 2) / 2 * GP_TSQ) : f.cov ? lower_ref(ch.Ct, sh.mlow * GP_TSQ) : TRef{};
         for_pair_batches(sh, ch, [&](int g0, int, int l0, int lc, int ub, const TRef& Ls, const TRef& invref) {
             na.s0 = ch.s0 + g0; na.l0 = l0; na.lc = lc;
             launch_new_build(na, ub, st);
             w_solve(c, *ch.s, na.W, Ls, invref, nt, ub, mt);
             launch_new_var(na, ub, st);
-            if (!f.cov) return;
-            minus_w_wt(c, *ch.s, na.W, na.Cm, nt, ub, mt);
-            launch_new_gather(na, ub, st);
+            if (f.cov || joint) minus_w_wt(c, *ch.s, na.W, na.Cm, nt, ub, mt);
+            if (f.cov) launch_new_gather(na, ub, st);
+            if (!f.score()) return;
+            if (joint) {      // §28's steps on C: the residual as the one live augmented row, the panel schedule, the epilogue
+                launch_new_score_rhs(na, ub, st);
+                HC(hipMemsetAsync(ch.pinfo, 0, sizeof(int) * ub, st));
+                factor_panels(c, *ch.s, na.Cm, mt, mt + 1, ch.kf_inv, ch.pinfo, 0, ub, 1, true, 3);
+                EpiArgs ea{};
+                ea.M = na.Cm; ea.n = mt * GP_TS; ea.nt = mt; ea.naug = 1; ea.from_rows = 1;
+                ea.logdet = ch.kf_ldq; ea.quad = ch.kf_ldq + ub;       // sample index = batch element: s0 = 0
+                launch_epilogue(ea, ub, st);
+                na.pinfo = ch.pinfo; na.ldq = ch.kf_ldq;
+            }
+            launch_new_score_finish(na, ub, st);
         });
     }
     HC(hipGetLastError());
@@ -559,6 +584,10 @@ void run_predict(gpslc_ctx* c, const PredictIO& io_in) {
         if (io.lv.vec || io.fresh.m < 1) throw std::runtime_error("new individuals need scalar levels and m >= 1");
         if (io.fresh.cov && !io.fresh.var) throw std::runtime_error("the covariance of new individuals needs their variance: its diagonal");
         if (io.CovITEs || io.out.ite_draws) throw std::runtime_error("new individuals cannot be combined with CovITE or draws: one pair workspace");
+        if (io.fresh.vec && io.lv.form != FORM_OUTCOME && io.lv.form != FORM_CONTRAST)
+            throw std::runtime_error("per-individual levels of new individuals: outcomes and contrasts only");
+        if (io.fresh.score() && (!io.fresh.vec || io.lv.form != FORM_OUTCOME || io.lv.L != 1 || !io.fresh.mean || !io.fresh.var || io.fresh.cov))
+            throw std::runtime_error("the test-set score is the outcome form at one per-individual level, with mean and var");
     }
     if (io.fresh.weighted) {
         if (fr.factual) throw std::runtime_error("new individuals have no factual treatment: ordinary levels cannot be predicted for them");

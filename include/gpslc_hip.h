@@ -572,6 +572,51 @@ int gpslc_predict_new(gpslc_ctx* ctx, int64_t S, const double* U, const double* 
                       const double* Xnew, const double* Unew, int32_t form, int32_t L, const double* doT,
                       const double* doT_base, double pred_noise, double* mean, double* var, double* cov);
 
+/* gpslc_predict_new at levels that depend on the new individual: level l sets new individual i to the dose a_il = doT[i + m*l]
+ * (m x L host, every entry finite) and, for a contrast, against b_il = doT_base[i + m*l] (m x L; else NULL) — a policy for a new
+ * population, or with b_il = T*_i the ordinary effect f*(a) - f*(T*_i) of a new individual whose factual treatment is known.
+ * Arguments, output layouts, NULL conventions, NaN and status behaviour are gpslc_predict_new's.  Forms: GPSLC_NEW_OUTCOME and
+ * GPSLC_NEW_CONTRAST; GPSLC_NEW_SLOPE is refused (-12, "unsupported form").  Per sample, in the notation above:
+ *     cross_ij = rho(T_j, a_il) [- rho(T_j, b_il)]      D*_ij = B*_ij cross_ij      mean_i = sum_j D*_ij alpha_j      W* = D* L^-T
+ *     P_ii' = rho(a_i, a_i')   |   (rho(a_i, a_i') - rho(a_i, b_i')) - (rho(b_i, a_i') - rho(b_i, b_i'))
+ *     var_i = (P_ii yScale - ||row i of W*||^2) + pred_noise      cov_ii' = P_ii' B**_ii' - (W* W*')_ii' + pred_noise [i == i']
+ * cross does not factor into a per-column term: the mean is a pass over the m n pairs per level (one exp per pair and level for the
+ * outcome, two for the contrast), not gpslc_predict_new's matrix product.
+ * Exact identities: cov is exactly symmetric and its diagonal bit-identical to var; a row with a_il == b_il has mean 0.0, var
+ * pred_noise and 0.0 in its row and column of cov off the diagonal; mean and var of a new individual do not depend on which others
+ * share the call, and every output is bit-reproducible and independent of chunking, streams and the factorisation schedule.
+ * Doses that are the same for every new individual give gpslc_predict_new's results to rounding (var and cov from the same
+ * tiles, the mean in another summation order).
+ * Errors: gpslc_predict_new's (-9 ... -17; doT / doT_base are checked over their m x L entries); GPSLC_NEW_SLOPE: -12.  fp64 only
+ * (GPSLC_ERR_UNSUPPORTED on a GPSLC_FLAG_FP32_KERNEL ctx); no _dev variant; not sharded; no draws.   */
+int gpslc_predict_new_vec(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                          const double* tyLS, const double* yScale, const double* yNoise, int64_t m,
+                          const double* Xnew, const double* Unew, int32_t form, int32_t L, const double* doT,
+                          const double* doT_base, double pred_noise, double* mean, double* var, double* cov);
+
+/* The score of a held-out test set: m individuals the chain has never seen, with covariates Xtest (m x nX; NULL iff nX == 0),
+ * latent confounders Utest (m x nU x S; NULL iff nU == 0: gpslc_predict_new's Unew), treatments Ttest (m) and outcomes Ytest (m),
+ * every entry finite.  Per posterior sample this is gpslc_predict_new_vec's outcome form with L = 1, a_i = Ttest_i and the
+ * OBSERVATION's noise: yNoise_s takes the place of pred_noise in var and on the diagonal of C = B** o P - W* W*' + yNoise I.
+ *   mean[i + m*s], var[i + m*s]     the predictive mean and variance of Ytest_i given the n training individuals
+ *   lpd[i + m*s]                    log N(Ytest_i; mean, var): the pointwise log predictive density
+ *   lpd_joint[s]                    log N(Ytest; mean, C) = -(m/2) log(2 pi) - log det(C)/2 - r' C^-1 r / 2, r = Ytest - mean
+ * C is built as 128 x 128 tiles (mt = ceil(m / 128) tile rows) with r as its augmented row and factorised by the kernels that
+ * factorise A (gpslc_y_kfold's recipe); log det and the quadratic form come from that factor.  By the chain rule lpd_joint equals
+ * gpslc_y_logpdf of the n + m pooled individuals minus gpslc_y_logpdf of the n training individuals, to rounding; at m = 1 it
+ * equals lpd.  Each output may be NULL, not all four.
+ * A sample whose factorisation of A breaks down gets NaN in all its outputs; return value (first failing pivot) and
+ * gpslc_last_info as gpslc_predict_new.  A sample whose C loses positive definiteness gets NaN in lpd_joint and keeps mean, var and
+ * lpd; the return value and gpslc_last_info do not change.  Outputs are bit-reproducible and independent of chunking, streams and
+ * the factorisation schedule; mean, var and lpd of a test individual do not depend on the others.
+ * Errors: m < 1: -9; Xtest / Utest NULL-ness or a non-finite entry: -10 / -11; Ttest NULL or non-finite: -12; Ytest NULL or
+ * non-finite: -13; all outputs NULL: -14.  fp64 only (GPSLC_ERR_UNSUPPORTED on a GPSLC_FLAG_FP32_KERNEL ctx); no _dev variant;
+ * not sharded.  S = 0 is an empty call.   */
+int gpslc_y_test(gpslc_ctx* ctx, int64_t S, const double* U, const double* uyLS, const double* xyLS,
+                 const double* tyLS, const double* yScale, const double* yNoise, int64_t m,
+                 const double* Xtest, const double* Utest, const double* Ttest, const double* Ytest,
+                 double* mean, double* var, double* lpd, double* lpd_joint);
+
 /* Weighted averages over NEW individuals: tau_g(l) = w_g' f*(l) for G weight columns over the m new individuals of
  * gpslc_predict_new — the average effect in a target population that is not the sample (next year's cohort, another hospital, a
  * re-weighted grid of profiles, a held-out fold), its subgroups and their differences — with the variance that var of

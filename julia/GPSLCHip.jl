@@ -263,6 +263,46 @@ function predict_new(c::Ctx, S::Integer, U, uyLS, xyLS, tyLS::Vector{Float64}, y
     mean, var, cov
 end
 
+"""`predict_new` at levels that depend on the new individual (gpslc_predict_new_vec): `doT` is m x L, new individual i at level
+l is set to doT[i, l], and for NEW_CONTRAST against `doT_base[i, l]` (m x L; with doT_base[i, l] = T*_i the ordinary effect of
+a new individual whose own treatment is known).  NEW_SLOPE is refused.  Outputs as `predict_new`."""
+function predict_new_vec(c::Ctx, S::Integer, U, uyLS, xyLS, tyLS::Vector{Float64}, yScale::Vector{Float64},
+                         yNoise::Vector{Float64}, Xnew, Unew, form::Integer, doT::Matrix{Float64}, doT_base,
+                         pred_noise::Float64; want_var::Bool=true, want_cov::Bool=false)
+    m, L = size(doT)
+    Uf, uy, xy, Xn, Un, base = f64(U), f64(uyLS), f64(xyLS), f64(Xnew), f64(Unew), f64(doT_base)
+    base === nothing || size(base) == (m, L) || throw(DimensionMismatch("doT is $m x $L, doT_base $(size(base))"))
+    mean = Array{Float64}(undef, m, S, L)
+    var = (want_var || want_cov) ? Array{Float64}(undef, m, S, L) : nothing
+    cov = want_cov ? Array{Float64}(undef, m, m, S, L) : nothing
+    GC.@preserve Uf uy xy tyLS yScale yNoise Xn Un doT base mean var cov check(c, ccall((:gpslc_predict_new_vec, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}),
+        c.h, S, ptr(Uf), ptr(uy), ptr(xy), pointer(tyLS), pointer(yScale), pointer(yNoise), m, ptr(Xn), ptr(Un), form, L,
+        pointer(doT), ptr(base), pred_noise, ptr(mean), ptr(var), ptr(cov)))
+    mean, var, cov
+end
+
+"""The score of a held-out test set (gpslc_y_test): `(mean, var, lpd, lpd_joint)` — mean, var and lpd m x S: the predictive mean
+and variance (yNoise included) of Ytest[i] at the test individual's own treatment Ttest[i] and its log density; lpd_joint (S): the
+joint log density of the whole test set.  `Xtest` / `Utest` as `predict_new`'s Xnew / Unew.  A failed factorisation throws
+PosDefException."""
+function y_test(c::Ctx, S::Integer, U, uyLS, xyLS, tyLS::Vector{Float64}, yScale::Vector{Float64}, yNoise::Vector{Float64},
+                Xtest, Utest, Ttest::Vector{Float64}, Ytest::Vector{Float64})
+    m = length(Ttest)
+    length(Ytest) == m || throw(DimensionMismatch("Ttest has $m entries, Ytest $(length(Ytest))"))
+    Uf, uy, xy, Xn, Un = f64(U), f64(uyLS), f64(xyLS), f64(Xtest), f64(Utest)
+    mean, var, lpd = Array{Float64}(undef, m, S), Array{Float64}(undef, m, S), Array{Float64}(undef, m, S)
+    joint = Vector{Float64}(undef, S)
+    GC.@preserve Uf uy xy tyLS yScale yNoise Xn Un Ttest Ytest mean var lpd joint check(c, ccall((:gpslc_y_test, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        c.h, S, ptr(Uf), ptr(uy), ptr(xy), pointer(tyLS), pointer(yScale), pointer(yNoise), m, ptr(Xn), ptr(Un), pointer(Ttest),
+        pointer(Ytest), pointer(mean), pointer(var), pointer(lpd), pointer(joint)))
+    mean, var, lpd, joint
+end
+
 """Weighted averages over m individuals who are not in the data (gpslc_predict_new_weighted): `(meanW, varW, covW)` — meanW and
 varW S x L x G, covW S x L x L x G (`nothing` unless asked for) — of w_g' f* for the G columns of `weights` (m x G, used as
 given: 1/m is the average over the target population, a difference of two group columns the difference of the groups with its
