@@ -130,7 +130,7 @@ struct SampleParams {
 };
 
 // The samples of a chunk and their feature blocks [U_s | X]: what every kernel that evaluates the RBF kernel starts from.  The
-// two members carry address arithmetic and one load only; stage_scaled_features below is the one place that divides by ls.
+// two members carry address arithmetic and one load only; scaled_feature below is the one place that divides by ls.
 struct SampleGrid {
     const double* X;   // n x nX (ctx or override)
     const double* T;   // n
@@ -156,17 +156,35 @@ __device__ __forceinline__ double centred_value(const double* col, int i) {
     else return col[i];
 }
 
-// Features / lengthscale of COUNT consecutive individuals from g0 into LDS, by a workgroup of 256 threads: FS >= F rows of
-// COUNT, zeros beyond n and in the rows F .. FS - 1.  (x - x')^2 / ls^2 = (x / ls - x' / ls)^2, and every kernel that
+// Feature f of individual g as the pair loops take it: (x - x')^2 / ls^2 = (x / ls - x' / ls)^2, and every kernel that
 // evaluates B_ij forms x / ls as x * (1.0 / ls): the same product everywhere, so the same B_ij everywhere.  RT = float:
-// (x - x_0) * (1.0 / ls), centred_value above.
+// (x - x_0) * (1.0 / ls), centred_value above.  Its two callers: stage_scaled_features (into LDS, per workgroup) and
+// col_operands_kernel (k_gram.hip: into the chunk's operand array, once per sample).
+template <typename RT>
+__device__ __forceinline__ double scaled_feature(const SampleGrid& a, long long s, int f, int g) {
+    return centred_value<RT>(a.column(s, f), g) * (1.0 / a.lengthscale(s, f));
+}
+
+// Features / lengthscale of COUNT consecutive individuals from g0 into LDS, by a workgroup of 256 threads: FS >= F rows of
+// COUNT, zeros beyond n and in the rows F .. FS - 1.
 template <int COUNT, typename RT>
 __device__ __forceinline__ void stage_scaled_features(const SampleGrid& a, long long s, int F, int FS, int g0, RT* dst) {
     for (int idx = threadIdx.x; idx < FS * COUNT; idx += 256) {
         const int f = idx / COUNT, r = idx % COUNT;
-        dst[idx] = (RT)((f < F && g0 + r < a.n) ? centred_value<RT>(a.column(s, f), g0 + r) * (1.0 / a.lengthscale(s, f)) : 0.0);
+        dst[idx] = (RT)((f < F && g0 + r < a.n) ? scaled_feature<RT>(a, s, f, g0 + r) : 0.0);
     }
 }
+
+// The operand array of a chunk (fp64): per sample b and individual g < Np = 128 nt one row of FP doubles, FP = F rounded up
+// to a multiple of 8, at least 8 (a row starts on a 64-byte boundary): entry f is scaled_feature<double>, zero for g >= n and
+// f >= F.  It exists so that a pair loop whose column is the same for every lane of a wave can take the column's features through
+// scalar loads (gram_sop_kernel, k_gram.hip; ite_mean_sop_kernel, k_solve.hip) instead of staging them in LDS and reading them
+// back once per lane.  DESIGN.md §30.
+__host__ __device__ inline int col_operand_width(int F) { return F <= 8 ? 8 : (F + 7) & ~7; }     // F = 0 (no features): 8 zeros
+struct ColOperandArgs : SampleGrid {
+    double* cop;       // [b][Np][FP]
+};
+void launch_col_operands(const ColOperandArgs& a, int nbatch, hipStream_t st);
 
 // lower-packed tile index t = ii (ii + 1) / 2 + jj, 0 <= jj <= ii, back to (ii, jj)
 __host__ __device__ __forceinline__ void tri_decode(int t, int& ii, int& jj) {
@@ -183,7 +201,11 @@ struct GramArgs : SampleGrid {
     int f32;           // evaluate the RBF kernel in fp32 (GPSLC_FLAG_FP32_KERNEL)
     int binary_t;      // every T is 0 or 1: e_ij is 1 or exp(-1/tyLS^2), no per-pair exp (bit-identical)
     unsigned long long* dbg;   // measurement build only: per-workgroup s_memtime stamps [entry, staged, columns done, end], or null
+    const double* cop;         // non-null (gram_uses_operands): the chunk's operand array, already filled: gram_sop_kernel builds the tiles
 };
+// which calls the scalar-operand Gram kernel serves: fp64 and the exact feature counts up to 12 (two rows' features in registers).
+// The fp32 mode, the runtime-F instantiation and F = 20 keep gram_kernel.
+inline bool gram_uses_operands(int F, bool f32) { return !f32 && (F == 4 || F == 5 || F == 6 || F == 8 || F == 10 || F == 12); }
 
 // ---------------------------------------------------------------------------------------
 // The whole left-looking factorisation of a batch as ONE persistent launch (round 6, k_tilegemm.hip: potrf_tasks_kernel).
@@ -306,7 +328,16 @@ struct IteMeanArgs : SampleGrid {
     double* meanITE;       // element (i, s, l) at i*si + s*ss + l*sl
     long long si, ss, sl;
     int f32;
+    // the scalar-operand kernel (ite_mean_uses_operands): the chunk's operand array [b][Np][FP] (launch_col_operands) and the level
+    // vectors R[b][g][LCT], R = cross_g(l) alpha_g for the L <= LCT levels of the call (launch_ite_levels; zero for g >= n, l >= L)
+    const double* cop;
+    double* R;
 };
+// which calls the scalar-operand MeanITE kernel serves: fp64, the VALU rungs LCT = 1 and 4, every feature rung but the widest
+// (32 features are 64 SGPRs per column: beyond the budget in one piece).  The others keep ite_mean_kernel and its LDS staging.
+inline bool ite_mean_uses_operands(int F, int L, bool f32) { return !f32 && L >= 1 && L <= 4 && F <= 20; }
+inline int ite_mean_lct(int L) { return L <= 1 ? 1 : 4; }
+void launch_ite_levels(const IteMeanArgs& a, int nbatch, hipStream_t st);    // R from alpha: once per sample, after the solve
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st);
 
 // vector levels (per-individual interventions, k_vec.hip): the level sums and MeanITE as passes over the pairs

@@ -205,15 +205,254 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs g) {
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// The Gram build with the column's operands in scalar registers (fp64, exact feature counts; GramArgs::cop, the chunk's operand
+// array).  Wave w owns the columns 32 w .. 32 w + 31 of the tile, lane l the rows l and l + 64; the rows' features sit in
+// registers (2 FT doubles, loaded from the operand array), and a column's features and T come through wave-uniform addresses:
+// scalar loads, scalar operands of the v_add_f64 that forms the difference.  No feature goes through LDS and nothing is staged
+// behind a workgroup barrier: each wave keeps its own copy of the exp table (its index is per lane) and starts on its first
+// column as soon as its own loads are back.  A wave-instruction stores 64 consecutive rows of one column: 512 contiguous bytes.
+// Every element keeps gram_kernel's operations in gram_kernel's order.  So do the sums (partB / partK are part of the results):
+//   row r      the columns 8 t .. 8 t + 7 of a group are added one after the other from 0.0; a wave's four groups combine as
+//              (g0 + g1) + (g2 + g3), the waves as (w0 + w1) + (w2 + w3) through `red` — all but the last inside a lane;
+//   column c   gram_kernel adds, per ty = 0..15, the rows ty, ty + 16, .., ty + 112 one after the other and then the sixteen
+//              chains in a butterfly over ty.  Here row ty + 16 p lives in lane ty + 16 (p & 3), so four columns are finished
+//              first and their values transposed across the four 16-lane rows of the wave (v_permlane16_swap, v_permlane32_swap:
+//              register j of lane row k <-> register k of lane row j); lane row k then holds all eight rows of every chain of
+//              column 4 i + k, adds them in order, and runs the butterfly inside its row (DPP: a lane of a quad, of a half row,
+//              of a row holds the same partial sum as its neighbours, so mirrors serve as the xor 4 and xor 8 steps).
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ void lane_rows_transpose(double (&x)[4]) {
+    unsigned lo[4], hi[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { lo[j] = (unsigned)__double2loint(x[j]); hi[j] = (unsigned)__double2hiint(x[j]); }
+    auto t4 = [](unsigned (&v)[4]) {
+        auto s16 = [](unsigned& a, unsigned& b) { const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false); a = r[0]; b = r[1]; };
+        auto s32 = [](unsigned& a, unsigned& b) { const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false); a = r[0]; b = r[1]; };
+        s16(v[0], v[1]); s16(v[2], v[3]);      // odd lane rows of the first <-> even lane rows of the second
+        s32(v[0], v[2]); s32(v[1], v[3]);      // upper half of the first <-> lower half of the second
+    };
+    t4(lo); t4(hi);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = __hiloint2double((int)hi[j], (int)lo[j]);
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_row_move(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// the butterfly of __shfl_xor 1, 2, 4, 8 over the 16 lanes of a row, as lane ty = 0 of gram_kernel sees it
+__device__ __forceinline__ double row16_butterfly_sum(double v) {
+    v += dpp_row_move<0xB1>(v);      // quad_perm [1, 0, 3, 2]: xor 1
+    v += dpp_row_move<0x4E>(v);      // quad_perm [2, 3, 0, 1]: xor 2; the four lanes of a quad now hold the same sum
+    v += dpp_row_move<0x141>(v);     // row_half_mirror: a lane of the other quad of the half row
+    v += dpp_row_move<0x140>(v);     // row_mirror: a lane of the other half row
+    return v;
+}
+
+template <int BIN, int FT>
+__device__ __forceinline__ void gram_sop_body(const GramArgs& g, const double* __restrict__ cop, const double* __restrict__ Tv,
+                                              double* __restrict__ tile, double* __restrict__ partB, double* __restrict__ partK,
+                                              double* etab_all, double* red, int ti, int tj, long long b, long long s
+#ifdef GPSLC_DIAG
+                                              , unsigned long long dt0, unsigned long long dr0
+#endif
+                                              ) {
+    constexpr int FP = FT <= 8 ? 8 : (FT + 7) & ~7;      // col_operand_width(FT)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // the same for a whole wave: keeps the column addresses scalar
+    const int n = g.n, Np = g.nt * GP_TS;
+    const int gi0 = ti * GP_TS, gj0 = tj * GP_TS;
+
+    double* etab = etab_all + w * GP_EXP_TAB_DOUBLES;      // this wave's copy: written and read by the same wave, no barrier
+    etab[lane & 31] = gp_exp2_tab[lane & 31];
+    double fr[2][FT];
+    double tra[2];
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        const int gi = gi0 + lane + 64 * hh;
+        const double* rowp = cop + (b * Np + gi) * FP;      // zeros beyond n
+#pragma unroll
+        for (int f = 0; f < FT; ++f) fr[hh][f] = rowp[f];
+        const double t = Tv[min(gi, n - 1)];
+        tra[hh] = gi < n ? t : 0.0;
+    }
+    __builtin_amdgcn_wave_barrier();
+#ifdef GPSLC_DIAG
+    const unsigned long long dt1 = g.dbg ? __builtin_amdgcn_s_memtime() : 0;
+#endif
+    const double ys = g.p.yScale[s];
+    const double yn = g.p.yNoise[s];
+    const double tl = g.p.tyLS[s];
+    const double wt = 1.0 / (tl * tl);
+    const double ew = gp_exp_neg_tab(-wt, etab);     // e_ij for |T_i - T_j| = 1 (binary treatments)
+    const int krow = lane >> 4, ty = lane & 15;
+    const double* __restrict__ cbase = cop + (b * Np + gj0) * FP;
+
+    // A column's features are requested one column ahead, the T of four columns at the head of their block (its first use comes
+    // behind the first column's distance loop).
+    struct ColOps { double f[FT]; };
+    auto request = [&](int cq, ColOps& o) {
+        cq = min(cq, GP_TS - 1);        // one past the wave's last column: a request nobody uses, kept inside the tile
+        const double* __restrict__ cp = cbase + cq * FP;
+#pragma unroll
+        for (int f = 0; f < FT; ++f) o.f[f] = cp[f];
+    };
+    double rs[2][2];       // [row half][B | K]: (g0 + g1) + (g2 + g3) of this wave's 32 columns
+    auto columns = [&](auto fast_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        auto request_t = [&](int c4, double (&t)[4]) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = FAST ? Tv[gj0 + c4 + j] : Tv[min(gj0 + c4 + j, n - 1)];
+        };
+        ColOps cur;
+        request(32 * w, cur);
+#pragma unroll 1
+        for (int pr = 0; pr < 2; ++pr) {
+            double ps[2][2];
+#pragma unroll 1
+            for (int gg = 0; gg < 2; ++gg) {
+                double gs[2][2] = {{0.0, 0.0}, {0.0, 0.0}};      // one group of 8 consecutive columns, added in ascending order
+#pragma unroll 1
+                for (int blk = 0; blk < 2; ++blk) {
+                    const int c4 = 32 * w + 16 * pr + 8 * gg + 4 * blk;
+                    double vB[2][4], vK[2][4], tcur[4];
+                    request_t(c4, tcur);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int cq = c4 + j, gj = gj0 + cq;
+                        ColOps nxt;
+                        request(cq + 1, nxt);
+                        double lux[2] = {0.0, 0.0};
+#pragma unroll
+                        for (int f = 0; f < FT; ++f) {
+                            const double c = cur.f[f];
+#pragma unroll
+                            for (int hh = 0; hh < 2; ++hh) {
+                                const double d = fr[hh][f] - c;
+                                lux[hh] = fma(d, d, lux[hh]);
+                            }
+                        }
+                        const double tcq = (FAST || gj < n) ? tcur[j] : 0.0;
+#pragma unroll
+                        for (int hh = 0; hh < 2; ++hh) {
+                            const int rp = lane + 64 * hh;
+                            const int gi = gi0 + rp;
+                            const double dt = tra[hh] - tcq;
+                            const double Bq = ys * gp_exp_neg_tab(-lux[hh], etab);
+                            const double Eq = BIN ? (dt == 0.0 ? 1.0 : ew) : gp_exp_neg_tab(-((dt * dt) * wt), etab);
+                            double Bv, Kv, Av;
+                            if (FAST) {
+                                Bv = Bq; Kv = Bq * Eq; Av = Kv;
+                            } else {
+                                const bool inside = (gi < n) && (gj < n);
+                                Bv = inside ? Bq : 0.0;
+                                Kv = inside ? Bq * Eq : 0.0;
+                                // diagonal: + yNoise inside, identity on the padding
+                                Av = (gi == gj) ? (inside ? Kv + yn : 1.0) : Kv;
+                            }
+                            __builtin_nontemporal_store(Av, &tile[cq * GP_TS + rp]);
+                            gs[hh][0] += Bv; gs[hh][1] += Kv;
+                            vB[hh][j] = Bv; vK[hh][j] = Kv;
+                        }
+                        cur = nxt;
+                    }
+                    if (g.with_sums) {
+                        // column sums of the four columns: lane row k takes column c4 + k
+#pragma unroll
+                        for (int hh = 0; hh < 2; ++hh) { lane_rows_transpose(vB[hh]); lane_rows_transpose(vK[hh]); }
+                        double csB = 0.0, csK = 0.0;
+#pragma unroll
+                        for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) { csB += vB[hh][j]; csK += vK[hh][j]; }      // rows ty + 16 (j + 4 hh)
+                        csB = row16_butterfly_sum(csB);
+                        csK = row16_butterfly_sum(csK);
+                        if (ty == 0) {
+                            partB[(long long)ti * Np + gj0 + c4 + krow] = csB;
+                            partK[(long long)ti * Np + gj0 + c4 + krow] = csK;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) ps[hh][k] = gg == 0 ? gs[hh][k] : ps[hh][k] + gs[hh][k];
+            }
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                for (int k = 0; k < 2; ++k) rs[hh][k] = pr == 0 ? ps[hh][k] : rs[hh][k] + ps[hh][k];
+        }
+    };
+    if (ti != tj && gi0 + GP_TS <= n && gj0 + GP_TS <= n) columns(std::true_type{});
+    else columns(std::false_type{});
+#ifdef GPSLC_DIAG
+    if (g.dbg) {     // [entry, row operands loaded, columns done, tile stores drained]
+        const unsigned long long dt2 = __builtin_amdgcn_s_memtime();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (tid == 0) {
+            unsigned long long* d = g.dbg + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+            d[0] = dt0; d[1] = dt1; d[2] = dt2; d[3] = __builtin_amdgcn_s_memtime();
+            d[4] = dr0; d[5] = __builtin_amdgcn_s_memrealtime();
+        }
+    }
+#endif
+    // diagonal tile: the full square was computed, column sums are complete
+    if (!g.with_sums || ti == tj) return;
+    // row sums: the four waves' shares through LDS
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        red[(w * GP_TS + lane + 64 * hh) * 2 + 0] = rs[hh][0];
+        red[(w * GP_TS + lane + 64 * hh) * 2 + 1] = rs[hh][1];
+    }
+    __syncthreads();
+    if (tid < GP_TS) {
+        const double vb = (red[(0 * GP_TS + tid) * 2] + red[(1 * GP_TS + tid) * 2]) +
+                          (red[(2 * GP_TS + tid) * 2] + red[(3 * GP_TS + tid) * 2]);
+        const double vk = (red[(0 * GP_TS + tid) * 2 + 1] + red[(1 * GP_TS + tid) * 2 + 1]) +
+                          (red[(2 * GP_TS + tid) * 2 + 1] + red[(3 * GP_TS + tid) * 2 + 1]);
+        partB[(long long)tj * Np + gi0 + tid] = vb;
+        partK[(long long)tj * Np + gi0 + tid] = vk;
+    }
+}
+
+template <int BIN, int FT>
+__global__ __launch_bounds__(256) void gram_sop_kernel(GramArgs g) {
+    __shared__ double etab[4 * GP_EXP_TAB_DOUBLES];      // 2^(j/32) for the table-driven exp (gp_math.h), one copy per wave
+    __shared__ double red[4 * GP_TS * 2];                // [4][128][2] cross-wave row-sum staging
+    const long long b = blockIdx.y, s = g.s0 + b;
+#ifdef GPSLC_DIAG
+    const unsigned long long dt0 = g.dbg ? __builtin_amdgcn_s_memtime() : 0;
+    const unsigned long long dr0 = g.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
+#endif
+    int ti, tj;
+    tri_decode(blockIdx.x, ti, tj);
+    const int Np = g.nt * GP_TS;
+    gram_sop_body<BIN, FT>(g, g.cop, g.T, tref_tile(g.M, b, ti, tj), g.part + (b * 2 + 0) * g.nt * Np, g.part + (b * 2 + 1) * g.nt * Np,
+                           etab, red, ti, tj, b, s
+#ifdef GPSLC_DIAG
+                           , dt0, dr0
+#endif
+                           );
+}
+
 #define GRAM_LDS_BYTES(F, RTS) (4 * GP_TS * 2 * 8 + GP_EXP_TAB_DOUBLES * 8 + (2 * (F) * GP_TS + 2 * GP_TS) * (RTS))
 
 template <typename RT, int BIN, int FT>
 static void launch_gram_t(const GramArgs& g, int nbatch, hipStream_t st) {
     const int F = g.nU + g.nX;
+    const int nlow = g.nt * (g.nt + 1) / 2;
+    if constexpr (std::is_same<RT, double>::value && FT > 0 && FT <= 12) {
+        if (g.cop) {
+            hipLaunchKernelGGL((gram_sop_kernel<BIN, FT>), dim3(nlow, nbatch), dim3(256), 0, st, g);
+            return;
+        }
+    }
     static DeviceOnce attr_set;
     lds_opt_in(attr_set, (const void*)gram_kernel<RT, BIN, FT>, GRAM_LDS_BYTES(MAXF, (int)sizeof(RT)));
     // one workgroup per (tile, sample): a persistent variant measured 0.7 % slower (same-box A/B)
-    const int nlow = g.nt * (g.nt + 1) / 2;
     hipLaunchKernelGGL((gram_kernel<RT, BIN, FT>), dim3(nlow, nbatch), dim3(256), GRAM_LDS_BYTES(F, (int)sizeof(RT)), st, g);
 }
 template <typename RT, int BIN>
@@ -232,6 +471,25 @@ static void launch_gram_b(const GramArgs& g, int nbatch, hipStream_t st) {
 void launch_gram(const GramArgs& g, int nbatch, hipStream_t st) {
     if (g.f32) { if (g.binary_t) launch_gram_b<float, 1>(g, nbatch, st); else launch_gram_b<float, 0>(g, nbatch, st); }
     else { if (g.binary_t) launch_gram_b<double, 1>(g, nbatch, st); else launch_gram_b<double, 0>(g, nbatch, st); }
+}
+
+// ---------------------------------------------------------------------------------------
+// The chunk's operand array (gpslc_internal.h, ColOperandArgs): row g of sample b holds scaled_feature(f, g), f < F, then zeros
+// up to FP; rows g >= n are zero.  One thread per entry, the entries of a row on consecutive threads: every store instruction of a
+// wave writes 512 contiguous bytes.  The columns it reads are a few hundred KiB per sample and stay in L2.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void col_operands_kernel(ColOperandArgs a) {
+    const int F = a.nU + a.nX, FP = col_operand_width(F);
+    const long long b = blockIdx.y, s = a.s0 + b;
+    const int Np = a.nt * GP_TS;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Np * FP) return;
+    const int g = idx / FP, f = idx % FP;
+    a.cop[b * Np * FP + idx] = (f < F && g < a.n) ? scaled_feature<double>(a, s, f, g) : 0.0;
+}
+void launch_col_operands(const ColOperandArgs& a, int nbatch, hipStream_t st) {
+    const int tot = a.nt * GP_TS * col_operand_width(a.nU + a.nX);
+    hipLaunchKernelGGL(col_operands_kernel, dim3((tot + 255) / 256, nbatch), dim3(256), 0, st, a);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -78,6 +78,18 @@ void launch_backsolve(const BackArgs& a, int nbatch, hipStream_t st) {
 // in the store: only the factual form has the K alpha term and the T_i == doT rule; a level that is zero by its form (a contrast
 // with a == b stages exact zeros: r^a == r^b bit for bit) is stored as 0.0.  The pair loop is the same code.
 // ---------------------------------------------------------------------------------------
+// cross_g(l) alpha_g of column g at level l: what the pair loop multiplies B_ig with, for both MeanITE kernels below
+template <int FORM, typename RT>
+__device__ __forceinline__ double ite_level_value(const IteMeanArgs& a, int g, int l, const double* alpha, double wt, const double* etab) {
+    using LF = LevelForm<FORM>;
+    const RT wtq = (RT)wt;
+    // the difference in fp64, then ONE rounding (fp32 mode): its error does not grow with |T|
+    const double dt64 = a.T[g] - a.lv.doT[l];
+    const RT dt = (RT)dt64, db = LF::paired ? (RT)(a.T[g] - a.lv.base[l]) : (RT)0;
+    const double rb = LF::paired ? (double)RbfMath<RT>::exp_neg_t(-((db * db) * wtq), etab) : 0.0;
+    return LF::cross(dt64, (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab), rb, wt) * alpha[g];
+}
+
 template <int FREG, int LCT, typename RT, int RB, int FORM = FORM_ORDINARY>
 __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
     using LF = LevelForm<FORM>;
@@ -105,7 +117,6 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
     const double ys = a.p.yScale[s];
     const double tl = a.p.tyLS[s];
     const double wt = 1.0 / (tl * tl);
-    const RT wtq = (RT)wt;
     gp_exp_tab_stage(etab, tid);
     const double* alpha = a.alpha + b * Np;
 
@@ -125,13 +136,7 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
                 const int ll = idx >> 7, cc = idx & 127;
                 const int g = jt * GP_TS + cc;
                 double v = 0.0;
-                if (ll < nl && g < n) {
-                    // the difference in fp64, then ONE rounding (fp32 mode): its error does not grow with |T|
-                    const double dt64 = a.T[g] - doT[l0 + ll];
-                    const RT dt = (RT)dt64, db = LF::paired ? (RT)(a.T[g] - a.lv.base[l0 + ll]) : (RT)0;
-                    const double rb = LF::paired ? (double)RbfMath<RT>::exp_neg_t(-((db * db) * wtq), etab) : 0.0;
-                    v = LF::cross(dt64, (double)RbfMath<RT>::exp_neg_t(-((dt * dt) * wtq), etab), rb, wt) * alpha[g];
-                }
+                if (ll < nl && g < n) v = ite_level_value<FORM, RT>(a, g, l0 + ll, alpha, wt, etab);
                 rl[idx] = v;
             }
             __syncthreads();
@@ -196,6 +201,115 @@ __global__ __launch_bounds__(256) void ite_mean_kernel(IteMeanArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// The same pass with the column's operands in scalar registers (fp64, LCT = 1 | 4, F <= 20: ite_mean_uses_operands).  In
+// ite_mean_kernel the column c = h * 64 + cq is the same for every lane of a wave, yet each lane reads the column's FREG
+// features and LCT level values from LDS: the LDS array is then as busy as the VALU.  Here they come through wave-uniform
+// addresses, which the compiler turns into scalar loads and scalar operands of the v_add_f64 / v_fma_f64 that use them:
+//   - the features from the chunk's operand array (launch_col_operands): one row of FP doubles per (sample, individual);
+//   - the level values from R[b][g][LCT] = cross_g(l) alpha_g (ite_levels_kernel below), which every row-block workgroup
+//     of a sample recomputed for itself in ite_mean_kernel's staging loop.
+// No column tile is staged, so the two barriers per column tile are gone and only the exp table stays in LDS (its index is
+// per lane).  The arithmetic of a pair and the order of a row's sum are ite_mean_kernel's: h = 0 takes the columns
+// jt * 128 + 0..63 and h = 1 the columns 64..127, each ascending over jt, then acc(h = 0) + red(h = 1).
+// The body takes its global arrays as __restrict__ parameters: that is what lets the compiler prove that the store of the
+// results cannot change an operand, which a scalar load requires.
+// ---------------------------------------------------------------------------------------
+// R[b][g][LCT] for the g of one row block; one workgroup per (row block, sample)
+template <int LCT, int FORM>
+__global__ __launch_bounds__(256) void ite_levels_kernel(IteMeanArgs a) {
+    __shared__ double etab[GP_EXP_TAB_DOUBLES];
+    const int tid = threadIdx.x;
+    const long long b = blockIdx.y, s = a.s0 + b;
+    const int Np = a.nt * GP_TS;
+    gp_exp_tab_stage(etab, tid);
+    __syncthreads();
+    const double tl = a.p.tyLS[s];
+    const double wt = 1.0 / (tl * tl);
+    const double* alpha = a.alpha + b * Np;
+    for (int idx = tid; idx < LCT * GP_TS; idx += 256) {
+        const int ll = idx % LCT, g = blockIdx.x * GP_TS + idx / LCT;
+        double v = 0.0;
+        if (ll < a.lv.L && g < a.n) v = ite_level_value<FORM, double>(a, g, ll, alpha, wt, etab);
+        a.R[(b * Np + g) * LCT + ll] = v;
+    }
+}
+
+template <int FREG, int LCT, int FORM>
+__device__ __forceinline__ void ite_mean_sop_body(const IteMeanArgs& a, const double* __restrict__ cop, const double* __restrict__ R,
+                                                  double* __restrict__ out, const double* etab, double* red) {
+    using LF = LevelForm<FORM>;
+    const int tid = threadIdx.x, r = tid & 127;
+    const int h = __builtin_amdgcn_readfirstlane(tid >> 7);     // the same for a whole wave: keeps the column addresses scalar
+    const int ib = blockIdx.x;
+    const long long b = blockIdx.y, s = a.s0 + b;
+    const int n = a.n, Np = a.nt * GP_TS, L = a.lv.L;
+    const int FP = col_operand_width(a.nU + a.nX);
+    const int gi = ib * GP_TS + r;
+
+    double af[FREG];   // this thread's row's features / LS: its row of the operand array (zeros beyond n and F)
+    {
+        const double* rowp = cop + (b * Np + gi) * FP;
+#pragma unroll
+        for (int f = 0; f < FREG; ++f) af[f] = rowp[f];
+    }
+    const double ys = a.p.yScale[s];
+    double acc[LCT];
+#pragma unroll
+    for (int ll = 0; ll < LCT; ++ll) acc[ll] = 0.0;
+    for (int jt = 0; jt < a.nt; ++jt) {
+        const long long c0 = b * Np + jt * GP_TS + h * 64;
+        const double* __restrict__ cp = cop + c0 * FP;
+        const double* __restrict__ rp = R + c0 * LCT;
+#pragma unroll 2
+        for (int cq = 0; cq < 64; ++cq) {
+            double lux = 0.0;
+#pragma unroll
+            for (int f = 0; f < FREG; ++f) {
+                const double d = af[f] - cp[cq * FP + f];
+                lux = fma(d, d, lux);
+            }
+            const double Bv = ys * gp_exp_neg_tab(-lux, etab);
+#pragma unroll
+            for (int ll = 0; ll < LCT; ++ll) acc[ll] = fma(Bv, rp[cq * LCT + ll], acc[ll]);
+        }
+    }
+    if (h == 1) {
+#pragma unroll
+        for (int ll = 0; ll < LCT; ++ll) red[r * LCT + ll] = acc[ll];
+    }
+    __syncthreads();
+    if (h != 0 || gi >= n) return;
+    const double* doT = a.lv.doT;
+    if constexpr (!LF::factual) {
+#pragma unroll
+        for (int ll = 0; ll < LCT; ++ll)
+            if (ll < L) {
+                const double v = acc[ll] + red[r * LCT + ll];
+                out[(long long)gi * a.si + s * a.ss + (long long)ll * a.sl] = (LF::paired && LF::zero_level(doT[ll], a.lv.base[ll])) ? 0.0 : v;
+            }
+    } else {
+        // (K alpha)_i = Y_i - yNoise alpha_i: alpha solves (K + yNoise I) alpha = Y
+        const double ka = a.Y[s * a.y_sstride + gi] - a.yNoise[s] * a.alpha[b * Np + gi];
+        const double ti = a.T[gi];
+#pragma unroll
+        for (int ll = 0; ll < LCT; ++ll)
+            if (ll < L) {
+                const double v = (acc[ll] + red[r * LCT + ll]) - ka;
+                out[(long long)gi * a.si + s * a.ss + (long long)ll * a.sl] = (ti == doT[ll]) ? 0.0 : v;
+            }
+    }
+}
+
+template <int FREG, int LCT, int FORM>
+__global__ __launch_bounds__(256) void ite_mean_sop_kernel(IteMeanArgs a) {
+    __shared__ double etab[GP_EXP_TAB_DOUBLES];     // 2^(j/32): table-driven exp (gp_math.h)
+    __shared__ double red[GP_TS * LCT];
+    gp_exp_tab_stage(etab, threadIdx.x);
+    __syncthreads();
+    ite_mean_sop_body<FREG, LCT, FORM>(a, a.cop, a.R, a.meanITE, etab, red);
+}
+
+// ---------------------------------------------------------------------------------------
 // MeanITE for many intervention levels on the MFMA (L > 4, fp64):
 //   MeanITE[i, l] = sum_j B_ij (r_j(l) alpha_j)  -  (Y_i - yNoise alpha_i)
 // = (B R)[i, l] - (K alpha)[i],  R[j, l] = r_j(l) alpha_j  — a (128 x N)(N x 64) product per row block; K alpha from
@@ -257,6 +371,15 @@ static void launch_ite_mean_t(const IteMeanArgs& a, int nbatch, hipStream_t st) 
 }
 template <int FREG, typename RT, int FORM>
 static void launch_ite_mean_f(const IteMeanArgs& a, int nbatch, hipStream_t st) {
+    // a.cop: the caller prepared the operand array and R (ite_mean_uses_operands): the scalar-operand kernel, one workgroup per
+    // (row block, sample) as below
+    if constexpr (std::is_same<RT, double>::value && FREG <= 20) {
+        if (a.cop) {
+            if (a.lv.L <= 1) hipLaunchKernelGGL((ite_mean_sop_kernel<FREG, 1, FORM>), dim3(a.nt, nbatch), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((ite_mean_sop_kernel<FREG, 4, FORM>), dim3(a.nt, nbatch), dim3(256), 0, st, a);
+            return;
+        }
+    }
     if (a.lv.L <= 1) launch_ite_mean_t<FREG, 1, RT, FORM>(a, nbatch, st);
     else if (a.lv.L <= 4) launch_ite_mean_t<FREG, 4, RT, FORM>(a, nbatch, st);
     // L > 4 reaches this VALU ladder in the fp32 mode only (fp64: the MFMA kernel, launch_ite_mean), so only the forms with it get the rung
@@ -276,6 +399,13 @@ static void launch_ite_mean_r(const IteMeanArgs& a, int nbatch, hipStream_t st) 
     else if (F <= 16) launch_ite_mean_f<16, RT, FORM>(a, nbatch, st);
     else if (F <= 20) launch_ite_mean_f<20, RT, FORM>(a, nbatch, st);
     else launch_ite_mean_f<32, RT, FORM>(a, nbatch, st);
+}
+void launch_ite_levels(const IteMeanArgs& a, int nbatch, hipStream_t st) {
+    dispatch_form(a.lv.form, [&](auto form) {
+        constexpr int FORM = decltype(form)::value;
+        if (ite_mean_lct(a.lv.L) == 1) hipLaunchKernelGGL((ite_levels_kernel<1, FORM>), dim3(a.nt, nbatch), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((ite_levels_kernel<4, FORM>), dim3(a.nt, nbatch), dim3(256), 0, st, a);
+    });
 }
 void launch_ite_mean(const IteMeanArgs& a, int nbatch, hipStream_t st) {
     dispatch_form(a.lv.form, [&](auto form) {

@@ -47,6 +47,8 @@ struct PredictShape {
                                       // that need c = diag(A^-1) (yScale, yNoise)
     bool want_w;                      // W = L^-T is wanted (by any of them)
     bool want_alpha;                  // alpha = A^-1 Y is wanted (by the MeanITE pass or by them)
+    bool mean_operands;               // the MeanITE pass runs from the chunk's operand array (ite_mean_uses_operands)
+    bool gram_operands;               // ... and so does the Gram build (gram_uses_operands): unit_a fills the array, else mean_ite
     int mt;                           // new individuals: their row tiles, the tiles of an mt x mt triangle, and whether the
     long long mlow;                   // (sample, level) pairs need tile workspace (variance, covariance)
     bool want_new, new_pairs;
@@ -59,6 +61,8 @@ struct PredictShape {
           want_mean(io.out.meanITE || io.MeanITEs || want_draws), unitB(want_cov || want_draws),
           want_loo(io.loo.any()), want_lgo(io.lgo.any()), want_grad(io.grad.any()), grad_pairs(io.grad.pairs()),
           grad_c(io.grad.needs_c()), want_w(want_loo || want_lgo || want_grad), want_alpha(want_mean || want_w || io.fresh.mean),
+          mean_operands(want_mean && !io.lv.vec && ite_mean_uses_operands(io.nU + io.nX, io.lv.L, (c->flags & GPSLC_FLAG_FP32_KERNEL) != 0)),
+          gram_operands(gram_uses_operands(io.nU + io.nX, (c->flags & GPSLC_FLAG_FP32_KERNEL) != 0)),
           mt((io.fresh.m + GP_TS - 1) / GP_TS), mlow((long long)mt * (mt + 1) / 2), want_new(io.fresh.any()),
           new_pairs(io.fresh.pairs()), kfold_pairs(io.lgo.any() && io.lgo.kfold && io.lgo.nlarge > 0), kf_mt(io.lgo.mt_max()) {}
 };
@@ -71,6 +75,7 @@ struct Chunk {
     TRef M{};                        // the tile matrices of A over `tiles`
     double *tiles = nullptr, *inv = nullptr, *part = nullptr, *bsum = nullptr, *ksum = nullptr, *sumdelta = nullptr;
     double *vpart = nullptr, *zwork = nullptr, *znode = nullptr;
+    double *cop = nullptr, *rlev = nullptr;      // MeanITE from scalar operands: ColOperandArgs::cop [nb][Np][FP], IteMeanArgs::R [nb][Np][LCT]
     double *bw = nullptr, *kw = nullptr, *wnorm2 = nullptr;      // weighted effects: B W, K W [nb][G][Np], w_g . w_g [nb][G]
     double* cprior = nullptr;        // joint covariance across the levels: beta, kappa, gamma_l [nb][G][L + 2]
     double* wpart = nullptr;         // weighted averages over new individuals: the row blocks' shares of w' B** w [nb][mt][G]
@@ -118,6 +123,9 @@ ChunkBytes carve_chunk(const PredictShape& sh, const PredictIO& io, int Bb, Chun
     }
     if (io.lv.vec && sh.with_sums) b.vpart = take((size_t)L * nt);     // vector levels: per-tile shares of sum(Delta)
     b.zwork = take(2 * sh.Np);                                          // zwork + alpha
+    // the scalar-operand pair kernels: the operand array (Gram build, MeanITE pass) and the level vectors R (MeanITE pass)
+    if (sh.gram_operands || sh.mean_operands) b.cop = take((size_t)sh.Np * col_operand_width(io.nU + io.nX));
+    if (sh.mean_operands) b.rlev = take((size_t)sh.Np * ite_mean_lct(L));
     if (io.ndraw) b.znode = take(draws_image_doubles(1, sh.Np));        // operand image of the node draw's normals
     if (sh.want_w) b.loo_w = take((size_t)sh.nlow * GP_TSQ);
     if (sh.want_loo || sh.grad_c) b.loo_c = take(sh.Np);
@@ -222,6 +230,12 @@ bool unit_a(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const Chu
 #endif
     ga.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
     ga.binary_t = (c->binary_t && io.nU == c->nU && io.nX == c->nX && io.Y == c->dY) ? 1 : 0;   // ctx data only
+    if (sh.gram_operands) {      // once per chunk, before the Gram build: the operand array both pair kernels read
+        ColOperandArgs ca{ch.grid};
+        ca.cop = ch.cop;
+        launch_col_operands(ca, nb, st);
+        ga.cop = ch.cop;
+    }
     const bool over_new = io.fresh.weighted;      // the weight columns run over the new individuals
     if (over_new) {     // B*' W over the m x n pairs, w' B** w over the m x m pairs, and the sums the prepare kernels would form
         NewWsumArgs wa{};
@@ -321,6 +335,15 @@ void mean_ite(gpslc_ctx* c, const PredictIO& io, const PredictShape& sh, const C
     ia.S = S; ia.lv = io.lv.set(sh.L); ia.alpha = alpha;
     ia.Y = io.Y; ia.y_sstride = io.y_sstride; ia.yNoise = io.post.p.yNoise;
     ia.f32 = (c->flags & GPSLC_FLAG_FP32_KERNEL) ? 1 : 0;
+    if (sh.mean_operands) {      // once per chunk: the columns' features (unless the Gram build left them), and cross(l) alpha of every column
+        if (!sh.gram_operands) {
+            ColOperandArgs ca{ch.grid};
+            ca.cop = ch.cop;
+            launch_col_operands(ca, nb, st);
+        }
+        ia.cop = ch.cop; ia.R = ch.rlev;
+        launch_ite_levels(ia, nb, st);
+    }
     for (const auto& o : outs)
         if (o.out) { ia.meanITE = o.out; ia.si = o.si; ia.ss = o.ss; ia.sl = o.sl; launch_ite_mean(ia, nb, st); }
 }
